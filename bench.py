@@ -8,10 +8,15 @@
 One step = one forward over this rank's batch of synthetic pairs (inputs and weights resident in HBM),
 returning the stage-4 disparity; for N > 1 every rank runs its own pairs (weak scaling, no data-path
 collective) and the stage-4 maps are gathered on rank 0 with ONE RCCL gather per step.
+A plain run sets up, spins up, warms up, times exactly --steps steps and prints the headline line (metric, value, unit,
+higher_is_better, dtype, ms_per_step, ...); `--dump-outputs DIR` also writes the four stage maps of rank 0's last timed step
+(float32, DIR/stage1.npy .. stage4.npy) for output-by-output comparisons of two builds -- inputs and weights are seeded.
+Everything else below (roofline and its profiler passes, breakdown, latency, pipelined / split-bf16 extras, the CPU baseline,
+the gather checks and price, config 4) runs under `--full` only.
 Rank 0 prints one JSON line.  `roofline` describes the dominant kernel (stage-1 Conv3D 32->32 on fp32
 MFMA): algorithmic FLOPs per launch / average launch duration from hipEvents recorded by the library on
 the launch stream inside the timed region; `roofline.traffic` = 2 x FETCH_SIZE + WRITE_SIZE of that kernel from two `rocprofv3
---pmc` child passes of the same workload that a plain single-GPU run starts before it touches the GPU (separate passes, no trace
+--pmc` child passes of the same workload that a single-GPU --full run starts before it touches the GPU (separate passes, no trace
 domain; the committed summary under profiles/ is reported when the profiler is not available).  `cpu_baseline` is the literal oracle (torch-CPU ops) timed on
 the host cores of the same box, N = 1 only; it also carries the numerics account: per-stage max-abs distance of the GPU
 result and of the float32 literal oracle to the float64 literal oracle, for the smooth pair and for a white-noise pair.
@@ -24,7 +29,7 @@ supervisors start ONE fallback job in fresh workers whose gather goes over gloo 
 if nothing could be measured.  `python bench.py --gpus N` without torchrun's environment starts that torchrun job itself as a
 child (never an exec) and relays the line.  Workers pass `timeout=120 s` to init_process_group (torch's NCCL watchdog applies it
 to every collective) and fail at once when their LOCAL_RANK has no device.
-With N > 1 (or --config4) the same job also times BASELINE config 4's per-rank shape -- 8 pairs per GPU per step, batch 8 N in
+With N > 1 under --full (or with --config4) the same job also times BASELINE config 4's per-rank shape -- 8 pairs per GPU per step, batch 8 N in
 all -- and reports it under `config4`; `value` stays the 1-pair-per-GPU number so that N = 1 agrees with the single-GPU line.
 `--dry-run-cpu` runs the same launch / supervise / shard / gather / report plumbing on CPU over gloo with a per-pair stand-in
 for the forward (no GPU, nothing measured: "value" is null) -- it exists for tests/test_bench_cpu.py, which also injects a hung
@@ -130,7 +135,7 @@ def _measure_traffic(args):
     env = dict(os.environ, TMPDIR="/tmp")
     child = [sys.executable, os.path.abspath(__file__), "--traffic-child", "--steps", "3", "--warmup", "2", "--spinup", "0",
              "--batch", str(args.batch), "--size", args.size, "--maxdisp0", str(args.maxdisp0), "--no-cpu-baseline", "--no-pipelined",
-             "--no-measure-traffic"] + (["--feature-fp16"] if args.feature_fp16 else []) + [x for o in args.opt for x in ("--opt", o)]
+             "--no-measure-traffic", "--full"] + (["--feature-fp16"] if args.feature_fp16 else []) + [x for o in args.opt for x in ("--opt", o)]
     kb = {}
     t0 = time.perf_counter()
     try:
@@ -191,7 +196,8 @@ def _dry_forward(left, right):
 def dry_run(args, rank, world):
     """--dry-run-cpu: the N-rank launch, the per-rank shard of seeded pairs, the ONE gather to rank 0, the barrier-
     bracketed clock and the report -- with a CPU stand-in instead of the HIP forward.  Nothing is measured.  Like the measured
-    job it runs the main leg (--batch pairs per rank per step) and, for N > 1 or --config4, config 4's 8 pairs per rank."""
+    job it runs the main leg (--batch pairs per rank per step) and, for N > 1 under --full or with --config4, config 4's 8
+    pairs per rank."""
     import torch.distributed as dist
     from lwsnet_amd import dist as ldist
     from lwsnet_amd.synth import make_batch
@@ -234,7 +240,7 @@ def dry_run(args, rank, world):
 
     _inject("hang-collective", rank)
     main_leg = leg(args.batch, args.steps, args.warmup)
-    c4 = leg(8, min(args.steps, 4), 1) if (world > 1 or args.config4) else None
+    c4 = leg(8, min(args.steps, 4), 1) if (args.config4 or (world > 1 and args.full)) else None
     ok = True
     if rank == 0:
         out = {"metric": "stereo pairs/sec @256x512 maxdisp=192 (stage-4)", "value": None, "unit": "pairs/s",
@@ -289,14 +295,39 @@ def parse_args(argv=None):
                     help="seconds for init_process_group (and, through torch's NCCL watchdog, every collective)")
     ap.add_argument("--config4", action="store_true",
                     help="also time BASELINE config 4's per-rank shape (8 pairs per GPU per step) and report it under `config4`; "
-                         "on by itself for N > 1")
+                         "on by itself for N > 1 under --full")
     ap.add_argument("--no-measure-traffic", action="store_true",
                     help="skip the two rocprofv3 --pmc child passes that measure roofline.traffic in this run (single-GPU runs only); "
                          "the committed PMC summary of the same workload is reported instead")
     ap.add_argument("--traffic-timeout", type=float, default=60.0, help="seconds one rocprofv3 --pmc child pass may take")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)      # the child of _measure_traffic: timed steps only
     ap.add_argument("--config4-steps", type=int, default=None, help="timed steps of the config-4 leg (default: 10..50 following --steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline (in-run PMC passes, sampled kernel events, clock stamps), kernel "
+                         "breakdown, latency, the lws_pool and split-bf16 extras, the CPU baseline and numerics account, the gather "
+                         "checks and price, and config 4 for N > 1.  Without it a run sets up, warms up, times --steps steps and "
+                         "prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the four stage maps of rank 0's last timed step as DIR/stage<k>.npy (float32; a fixed, seeded sample "
+                         "of each when the four together exceed 64 MB)")
     return ap.parse_args(argv)
+
+
+DUMP_LIMIT_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(directory, preds):
+    """--dump-outputs: the stage maps a caller of the timed path receives (host copies taken right after the timed region),
+    float32, one file per stage.  Above 64 MB in all, every map is cut to the same fixed, seeded sample of its flat indices."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = [np.ascontiguousarray(p, dtype=np.float32) for p in preds]
+    total = sum(a.nbytes for a in arrays)
+    for k, a in enumerate(arrays):
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, a.size * DUMP_LIMIT_BYTES // total)
+            idx = np.sort(np.random.default_rng(1234 + k).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, f"stage{k + 1}.npy"), a)
 
 
 def main():
@@ -314,7 +345,7 @@ def main():
         launch.arm_watchdog(args.job_timeout, lambda: print(launch.error_line(
             1, args.steps, args.warmup, f"the run did not finish within --job-timeout {args.job_timeout:.0f} s"), flush=True))
         profiled = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ)      # (this process itself runs under rocprofv3)
-        if not (args.no_measure_traffic or args.traffic_child or args.dry_run_cpu or profiled):
+        if args.full and not (args.no_measure_traffic or args.traffic_child or args.dry_run_cpu or profiled):
             args.traffic_in_run = _measure_traffic(args)            # children first: this process has not touched the GPU yet
     try:
         return worker(args)
@@ -375,11 +406,12 @@ def worker(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    def run_leg(B, steps, warmup, spinup_s=0.0, before_timed=None, after_timed=None):
+    def run_leg(B, steps, warmup, spinup_s=0.0, before_timed=None, after_timed=None, capture=False):
         """W warm-up steps, then exactly K timed steps of B pairs per rank bracketed by barrier + synchronize on both sides; with a
-        process group every step's stage-4 map goes into the staged gather and the tail is flushed before the clock stops.  Then
-        the checks (rank 0's slot == its own last map; every other rank's slot == what rank 0 computes for that rank's pairs) and
-        the same K steps without the gather (what the ONE collective costs).  Times are the MAX over ranks."""
+        process group every step's stage-4 map goes into the staged gather and the tail is flushed before the clock stops.  Then,
+        under --full, the checks (rank 0's slot == its own last map; every other rank's slot == what rank 0 computes for that
+        rank's pairs) and the same K steps without the gather (what the ONE collective costs).  Times are the MAX over ranks.
+        `capture`: host copies of the last step's stage maps, taken right after the timed region."""
         left_np, right_np = make_batch(B, H, W, first_index=rank * B)
         left, right = torch.from_numpy(left_np).to(dev), torch.from_numpy(right_np).to(dev)
         for m in models:
@@ -450,10 +482,11 @@ def worker(args):
         if grouped:
             dist.barrier()
         elapsed = time.perf_counter() - t0
+        host_pred = [p.cpu().numpy() for p in pred] if capture else None
         if after_timed:
             after_timed()
         gather_ok = all_ok = None
-        if grouped and rank == 0:                            # rank 0's part of the last gather holds this rank's last stage-4 map
+        if args.full and grouped and rank == 0:              # rank 0's part of the last gather holds this rank's last stage-4 map
             mine, nvalid = sg.gathered(0)
             gather_ok = bool(torch.equal(mine[(nvalid - 1) * B:nvalid * B], pred[3]))
             # ... and every other rank's part must be what THIS rank computes for that rank's pairs (pure batch sharding: the
@@ -467,7 +500,7 @@ def worker(args):
         # what the ONE collective of the path costs ("<= 3 %"): the same K steps again without the
         # gather, same barriers, same clock -- measurable on one GPU under `torch.distributed.run --nproc-per-node 1`
         t_plain = None
-        if grouped:
+        if args.full and grouped:
             def plain_steps(n):
                 dist.barrier()
                 torch.cuda.synchronize()
@@ -482,7 +515,7 @@ def worker(args):
             t_plain = max_over_ranks(plain_steps(steps))
         return {"B": B, "steps": steps, "elapsed": max_over_ranks(elapsed), "pred": pred, "left": left, "right": right,
                 "left_np": left_np, "right_np": right_np, "G": G, "gathers": sg.count if grouped else 0, "spun_s": spun_s,
-                "gather_ok": gather_ok, "all_ok": all_ok, "t_plain": t_plain}
+                "gather_ok": gather_ok, "all_ok": all_ok, "t_plain": t_plain, "host_pred": host_pred}
 
     # inside the timed region only the dominant kernel class is bracketed by hipEvents (8 events per sampled step), and only
     # on every n-th step; the per-class breakdown comes from a separate, untimed pass below.  A kernel bracketed by its own
@@ -508,16 +541,20 @@ def worker(args):
             mid["n"] += cnt[KC_MID16]
 
     B = args.batch
-    leg = run_leg(B, args.steps, args.warmup, spinup_s=max(0.0, args.spinup), before_timed=arm_profiler, after_timed=read_profiler)
+    # a plain run times the steps uninstrumented; --full brackets the dominant kernel of every n-th timed step for the roofline
+    instrument = {"before_timed": arm_profiler, "after_timed": read_profiler} if args.full else {}
+    leg = run_leg(B, args.steps, args.warmup, spinup_s=max(0.0, args.spinup), capture=bool(args.dump_outputs) and rank == 0, **instrument)
     if args.traffic_child:
         return                               # (under rocprofv3 --pmc: the counters of the launches above are all that is wanted)
+    if leg["host_pred"] is not None:
+        dump_outputs(args.dump_outputs, leg["host_pred"])
     elapsed, pred, left, right, left_np, right_np = leg["elapsed"], leg["pred"], leg["left"], leg["right"], leg["left_np"], leg["right_np"]
     G, spun_s, gather_ok, all_ok = leg["G"], leg["spun_s"], leg["gather_ok"], leg["all_ok"]
     # the clock the dominant kernel held on this box / on every rank's GPU (lws_clock_stamp: s_memtime against s_memrealtime
     # inside k_conv3d_mid16): 16 more forwards right after the timed region -- same queue depth, same mix of kernels -- stamped;
     # the last stage-1 launch of the last forward is read
     clock_ghz = None
-    if c3_first != 8 and not (model.get_option("split_bf16") & 1):      # (k_conv3d_mid16x, the split-bf16 form, carries no stamps)
+    if args.full and c3_first != 8 and not (model.get_option("split_bf16") & 1):      # (k_conv3d_mid16x, the split-bf16 form, carries no stamps)
         ghz = ctypes.c_double(0.0)
         _lib.check(lib.lws_clock_stamp(model._h, 1), "lws_clock_stamp")
         for _ in range(16):
@@ -526,7 +563,7 @@ def worker(args):
         _lib.check(lib.lws_clock_stamp(model._h, 0), "lws_clock_stamp")
         clock_ghz = float(ghz.value)
     clock_per_rank = None
-    if grouped and world > 1:
+    if args.full and grouped and world > 1:
         t = torch.tensor([clock_ghz or 0.0], device=red_dev, dtype=torch.float64)
         allc = [torch.zeros_like(t) for _ in range(world)]
         dist.all_gather(allc, t)
@@ -534,12 +571,12 @@ def worker(args):
     mid_ms, mid_n = mid["ms"], mid["n"]
     mid_avg_us = 1e3 * mid_ms / max(mid_n, 1)
     collective_overhead = None
-    if grouped and not through_host:
+    if args.full and grouped and not through_host:
         collective_overhead = {"ms_per_step_without_gather": round(1e3 * leg["t_plain"] / args.steps, 4)}
     # BASELINE config 4's per-rank shape in the same job: 8 pairs per GPU per step (batch 8 N in all), its own warm-up, clock,
-    # staged gather, bit-equality check and gather price.  `value` above stays the 1-pair-per-GPU number.
+    # staged gather, bit-equality check and gather price.  `value` above stays the 1-pair-per-GPU number.  (--full for N > 1.)
     config4 = None
-    if (world > 1 or args.config4) and (H, W, args.maxdisp0) == (256, 512, 24) and not args.feature_fp16:
+    if (args.config4 or (args.full and world > 1)) and (H, W, args.maxdisp0) == (256, 512, 24) and not args.feature_fp16:
         k4 = args.config4_steps if args.config4_steps else max(10, min(args.steps, 50))
         l4 = leg if B == 8 else run_leg(8, k4, max(3, min(args.warmup, 10)))
         ms4 = 1e3 * l4["elapsed"] / l4["steps"]
@@ -558,6 +595,58 @@ def worker(args):
         if B != 8:                           # back to the main leg's shape for the untimed passes below
             for m in models:
                 _lib.check(lib.lws_reserve(m._h, B, H, W), "lws_reserve")
+
+    def headline():
+        """The result line's own fields: what the timed steps measured and how they ran."""
+        dtype_name = "f32 (fp16-rounded features)" if args.feature_fp16 else "f32"
+        if model.get_option("split_bf16") != 0:
+            # experiments only (--opt): the opt-in numerics mode, float32-level accuracy but not the oracle's bits
+            dtype_name += " with split-bf16 MFMA operands (3 x bf16 per f32, f32 accumulate; not bit-exact against the oracle)"
+        pairs = world * B * args.steps
+        return {
+            "metric": "stereo pairs/sec @256x512 maxdisp=192 (stage-4)",
+            "value": None if args.one_gpu else round(pairs / elapsed, 2), "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "spinup_s": round(spun_s, 3), "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": dtype_name, "data": "synthetic", "full": args.full,
+            "config": {"workload": (f"BASELINE config 2: batch={B}/GPU, {H}x{W} synthetic pair, maxdisplist=[24,5,5], all 4 stages"
+                                    if (H, W, args.maxdisp0) == (256, 512, 24) else
+                                    f"batch={B}/GPU, {H}x{W} synthetic pair, maxdisplist=[{args.maxdisp0},5,5], all 4 stages"),
+                       "pairs_per_gpu": B, "streams": S, "parallelism": f"batch-sharded x{world}, 1 RCCL gather of stage-4 per {G * B} pairs per rank" if grouped else "single GPU",
+                       "weights": "seeded synthetic (seed 7, calibrated BN)", "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES"), **({"options": args.opt} if args.opt else {})},
+            "config4": config4,
+        }
+
+    def report(out):
+        """Adds the collective's account (torchrun jobs) and prints the one JSON line of rank 0."""
+        if grouped:
+            out["collective"] = {"backend": "gloo-through-host" if through_host else dist.get_backend(),
+                                 "op": f"async gather of stage-4 maps to rank 0, one per {G} step(s) = {G * B} pairs per rank per gather",
+                                 "gather_every_steps": G, "gathers_in_timed_region": leg["gathers"],
+                                 "world": world, "rank0_slot_equals_local": gather_ok, "all_ranks_slots_equal_unsharded": all_ok}
+            if args.one_gpu:
+                out["shared_one_gpu"] = {"pairs_per_s_both_ranks_on_one_gpu": round(world * B * args.steps / elapsed, 2),
+                                         "note": f"{world} ranks of the HIP path sharing cuda:0 over gloo (device maps gathered through the "
+                                                 "host): a check of the N-rank code path, not a throughput -- value is null"}
+            if through_host:
+                # (the gloo form copies every shard through the host and blocks the issuing thread: its cost is not the collective's)
+                out["collective"]["overhead_pct"] = None
+                out["collective"]["note"] = ("device maps gathered over gloo through host memory: every gather synchronises the host, so "
+                                             "ms_per_step includes host round trips an RCCL gather does not have")
+            if collective_overhead:
+                base = collective_overhead["ms_per_step_without_gather"]
+                collective_overhead["overhead_pct"] = round(100.0 * (out["ms_per_step"] - base) / base, 2)
+                out["collective"].update(collective_overhead)
+        print(json.dumps(out), flush=True)
+        if grouped:
+            dist.destroy_process_group()
+
+    if not args.full:
+        # a plain run ends here: set-up, warm-up, the timed steps (and the dumped outputs) are all its headline needs
+        if rank == 0:
+            return report(headline())
+        if grouped:
+            dist.destroy_process_group()
+        return
     # untimed breakdown pass: every kernel class, 10 steps
     nb = 10
     KC_MID8 = 4
@@ -850,11 +939,6 @@ def worker(args):
                                               "what": "reference/left_test.png + right_test.png (config 1's pair), seeded weights"}
             _lib.check(lib.lws_reserve(model._h, B, H, W), "lws_reserve")
 
-    pairs = world * B * args.steps
-    dtype_name = "f32 (fp16-rounded features)" if args.feature_fp16 else "f32"
-    if model.get_option("split_bf16") != 0:
-        # experiments only (--opt): the opt-in numerics mode, float32-level accuracy but not the oracle's bits
-        dtype_name += " with split-bf16 MFMA operands (3 x bf16 per f32, f32 accumulate; not bit-exact against the oracle)"
     roof = _with_traffic(roof, B, H, W, args.maxdisp0, args.feature_fp16)
     measured, why_not = getattr(args, "traffic_in_run", (None, "not attempted (--no-measure-traffic, or not a plain single-GPU run)"))
     if roof is not None and measured is not None:
@@ -872,42 +956,14 @@ def worker(args):
         # this workload (keyed on the kernel source's sha256); under --gpus N > 1 the object describes rank 0's launches
         roof["traffic_measured_in_run"] = measured is not None
         roof["rank"] = 0
-    out = {
-        "metric": "stereo pairs/sec @256x512 maxdisp=192 (stage-4)",
-        "value": None if args.one_gpu else round(pairs / elapsed, 2), "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "spinup_s": round(spun_s, 3), "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": dtype_name, "data": "synthetic",
-        "config": {"workload": (f"BASELINE config 2: batch={B}/GPU, {H}x{W} synthetic pair, maxdisplist=[24,5,5], all 4 stages"
-                                if (H, W, args.maxdisp0) == (256, 512, 24) else
-                                f"batch={B}/GPU, {H}x{W} synthetic pair, maxdisplist=[{args.maxdisp0},5,5], all 4 stages"),
-                   "pairs_per_gpu": B, "streams": S, "parallelism": f"batch-sharded x{world}, 1 RCCL gather of stage-4 per {G * B} pairs per rank" if grouped else "single GPU",
-                   "weights": "seeded synthetic (seed 7, calibrated BN)", "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES"), **({"options": args.opt} if args.opt else {})},
+    out = headline()
+    out.update({
         "roofline": roof, "secondary": secondary, "cpu_baseline": cpu, "latency_ms": latency, "pipelined": pipelined,
-        "split_bf16": split_bf16, "config4": config4,
+        "split_bf16": split_bf16,
         "hbm_kernels": hbm,
         "hot_path_kernel_ms_per_step": round(hot_ms, 4), "all_kernel_ms_per_step": round(all_ms, 4), "kernels": {k: {a: round(b, 2) for a, b in v.items()} for k, v in kernels.items()},
-    }
-    if grouped:
-        out["collective"] = {"backend": "gloo-through-host" if through_host else dist.get_backend(),
-                             "op": f"async gather of stage-4 maps to rank 0, one per {G} step(s) = {G * B} pairs per rank per gather",
-                             "gather_every_steps": G, "gathers_in_timed_region": leg["gathers"],
-                             "world": world, "rank0_slot_equals_local": gather_ok, "all_ranks_slots_equal_unsharded": all_ok}
-        if args.one_gpu:
-            out["shared_one_gpu"] = {"pairs_per_s_both_ranks_on_one_gpu": round(pairs / elapsed, 2),
-                                     "note": f"{world} ranks of the HIP path sharing cuda:0 over gloo (device maps gathered through the "
-                                             "host): a check of the N-rank code path, not a throughput -- value is null"}
-        if through_host:
-            # (the gloo form copies every shard through the host and blocks the issuing thread: its cost is not the collective's)
-            out["collective"]["overhead_pct"] = None
-            out["collective"]["note"] = ("device maps gathered over gloo through host memory: every gather synchronises the host, so "
-                                         "ms_per_step includes host round trips an RCCL gather does not have")
-        if collective_overhead:
-            base = collective_overhead["ms_per_step_without_gather"]
-            collective_overhead["overhead_pct"] = round(100.0 * (out["ms_per_step"] - base) / base, 2)
-            out["collective"].update(collective_overhead)
-    print(json.dumps(out), flush=True)
-    if grouped:
-        dist.destroy_process_group()
+    })
+    report(out)
 
 
 if __name__ == "__main__":

@@ -54,8 +54,8 @@ def test_bench_eight_ranks_ragged_tail():
 
 def test_bench_n_rank_job_reports_config4():
     """under --gpus N > 1 the job also runs BASELINE config 4's per-rank shape (8 pairs per GPU per step,
-    batch 8 N) with its own gather check; `value` stays the --batch leg.  `--gpus 8 --dry-run-cpu` prints `config4`."""
-    d = _run("--gpus", "8")
+    batch 8 N) with its own gather check; `value` stays the --batch leg.  `--gpus 8 --dry-run-cpu --full` prints `config4`."""
+    d = _run("--gpus", "8", "--full")
     c4 = d["config4"]
     assert c4["pairs_per_gpu"] == 8 and c4["global_batch"] == 64 and c4["all_ranks_slots_equal_unsharded"] is True
     assert c4["pairs_gathered"] == 64 and d["pairs_gathered"] == 8          # (the main leg: 1 pair per rank)
@@ -70,7 +70,7 @@ def test_bench_as_the_driver_launches_it():
     with socket.socket() as sock:
         sock.bind(("127.0.0.1", 0))
         port = sock.getsockname()[1]
-    d = _run("--gpus", "2", "--batch", "2", launcher=("-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
+    d = _run("--gpus", "2", "--batch", "2", "--full", launcher=("-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
                                                       "127.0.0.1", "--master-port", str(port)))
     assert d["n_gpus"] == 2 and d["gather_equals_unsharded"] is True and d["config4"]["all_ranks_slots_equal_unsharded"] is True
     assert [a["ok"] for a in d["attempts"]] == [True]
@@ -174,3 +174,30 @@ def test_launch_child_deadline_and_peer_failure():
     assert c.watch(time.monotonic() + 30.0) == (False, "worker exited with status 7")
     d = json.loads(launch.error_line(8, 20, 5, "why"))
     assert d["value"] is None and d["n_gpus"] == 8 and d["error"] == "why" and d["unit"] == "pairs/s"
+
+
+def test_dump_outputs_float32_and_a_seeded_sample_above_the_cap(tmp_path):
+    """bench.py --dump-outputs: one float32 file per stage map; above the 64 MB cap every map is cut to the same fixed, seeded
+    sample of its flat indices, identical from run to run and within the cap in all."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(0)
+    small = [rng.standard_normal((1, 1, 8, 16)).astype(np.float32) for _ in range(4)]
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    for k, a in enumerate(small):
+        got = np.load(tmp_path / "small" / f"stage{k + 1}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, a)
+    big = [rng.standard_normal((1, 1, 64, 128)).astype(np.float32) for _ in range(4)]
+    bench.DUMP_LIMIT_BYTES = 40000                     # (the 64 MB cap, scaled down to these maps)
+    bench.dump_outputs(str(tmp_path / "a"), big)
+    bench.dump_outputs(str(tmp_path / "b"), big)
+    total = 0
+    for k, a in enumerate(big):
+        x, y = np.load(tmp_path / "a" / f"stage{k + 1}.npy"), np.load(tmp_path / "b" / f"stage{k + 1}.npy")
+        assert x.dtype == np.float32 and np.array_equal(x, y) and 0 < x.size < a.size
+        assert np.isin(x, a.reshape(-1)).all()
+        total += x.nbytes
+    assert total <= 40000

@@ -12,8 +12,8 @@ stand-in for the ~25 Paddle calls it makes (tools/paddle_shim.py), and
      oracle remains "parity unpinned" (DESIGN.md section 2).
 
   3. with --check-fixtures NAME..., re-run the reference's source and compare with the COMMITTED fixtures bit for bit
-     (tests/test_reference_source_cpu.py starts this mode as a child process: the reference's files are public,
-     untrusted content, so they are never imported into the pytest process).
+     (the reference's files are public, untrusted content: run this mode in a process of its own, never inside a test
+     process).
 
   4. with --real-paddle (VERDICT r4 item 5 -- the only route from "parity unpinned" to a pinned oracle): when `import paddle`
      finds a REAL PaddlePaddle, the stand-in is NOT installed; the reference's source runs on Paddle-CPU on the five committed
