@@ -6,7 +6,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <functional>
 #include <stdlib.h>
 
 #include "lws_common.h"
@@ -228,14 +227,10 @@ static void prof_clear(lws_ctx *h)
     h->prof.clear();
 }
 
-// low != nullptr: the soft-argmin is wanted too; *fused tells the caller whether it was done here
-// last_stop (optional): an event that must be complete once the stack's last kernel is (stop_after = 0) or once its
-// stop_after-th middle layer is -- bound to that kernel's completion signal (stop_ext, StopArm in lws_common.h) or recorded
-// behind it
+// low != nullptr: the soft-argmin is wanted too; *fused tells the caller whether it was done here.  fork: see Fork
 static int conv3d_stack(lws_ctx *h, int stage, const float *cost_in, float *cost_out, float *act_a, float *act_b,
                         int B, int D, int hh, int ww, hipStream_t st, float *low = nullptr, float start = 0.f,
-                        bool *fused = nullptr, bool first_done = false, hipEvent_t last_stop = nullptr, int stop_after = 0,
-                        bool stop_ext = false)
+                        bool *fused = nullptr, bool first_done = false, const Fork &fork = Fork())
 {
     const Stage3d &s = h->stage[stage];
     int rc = LWS_OK;
@@ -246,7 +241,7 @@ static int conv3d_stack(lws_ctx *h, int stage, const float *cost_in, float *cost
     if (rc) return rc;
     float *src = act_a, *dst = act_b;
     for (int j = 1; j <= h->cfg.layers_3d; ++j) {
-        StopArm stop(j == stop_after ? last_stop : nullptr, st, stop_ext);
+        StopArm stop(j == fork.after ? fork : Fork(), st);
         if (s.c3 != 8 && ((h->prof_mask >> LWS_KC_CONV3D_MID16) & 1u) && h->prof.size() < kMaxProfRecords) {
             // dominant kernel: timed by its own begin / end timestamps, not by events around the launch
             lws_prof_rec rec;
@@ -265,7 +260,7 @@ static int conv3d_stack(lws_ctx *h, int stage, const float *cost_in, float *cost
     }
     {
         ProfScope p(h, LWS_KC_CONV3D_LAST, st);
-        StopArm stop(stop_after == 0 ? last_stop : nullptr, st, stop_ext);
+        StopArm stop(fork.after == 0 ? fork : Fork(), st);
         if (low != nullptr && conv3d_last_can_fuse(s, D)) {
             *fused = true;
             rc = launch_conv3d_last_softargmin(s, src, cost_in, nullptr, low, start, B, D, hh, ww, st);
@@ -445,16 +440,19 @@ static void bind_net2d(lws_ctx *h, const Net2dOffsets &o)
     n.r2_last = h->params + o.r2_last;
 }
 
-static int feature_tail(lws_ctx *h, int N, int H, int W, const WsLayout &L, float *f8, float *f4, float *f2,
-                        hipStream_t st, hipEvent_t *ev, int part = 3);
+// One launch of the 2D networks (feature extractor, refinement) on stream `st`, timed as kernel class kc; returns on error
+#define LWS_TIMED(kc, call)            \
+    {                                  \
+        ProfScope p_(h, kc, st);       \
+        rc = (call);                   \
+    }                                  \
+    if (rc) return rc;
 
-// feature_extraction.forward (submodules.py:176-188) on N = nA + nB images read from two tensors (left batch, right batch) as
-// ONE batch.  head_only: only the layers up to the 1/8 map run here (stage 1 needs nothing else); the caller runs feature_tail
-// (conv5, conv6, classif1 -> f4, f2) on a side stream later, beside the volume stages.
-// fork_ev (optional): complete once f8 / pre are -- bound to the last head kernel's completion signal (fork_ext) or recorded
-static int feature_extraction(lws_ctx *h, const float *imgA, const float *imgB, int nA, int nB, int H, int W,
-                              const WsLayout &L, float *f8, float *f4, float *f2, hipStream_t st,
-                              bool head_only = false, hipEvent_t fork_ev = nullptr, bool fork_ext = false)
+// feature_extraction.forward (submodules.py:176-188) up to the 1/8 map f8, on N = nA + nB images read from two tensors (left
+// batch, right batch) as ONE batch.  Stage 1 needs nothing else: lws_forward runs feature_tail (conv5, conv6, classif1 -> f4, f2)
+// on a side stream later, beside the volume stages.  fork (optional): complete once f8 / pre are
+static int feature_head(lws_ctx *h, const float *imgA, const float *imgB, int nA, int nB, int H, int W, const WsLayout &L,
+                        float *f8, hipStream_t st, const Fork &fork = Fork())
 {
     const Net2d &n = h->net2d;
     const int N = nA + nB, H2 = half_up(H), W2 = half_up(W), H4 = H2 / 2, W4 = W2 / 2;
@@ -462,27 +460,18 @@ static int feature_extraction(lws_ctx *h, const float *imgA, const float *imgB, 
     float *o = ws + L.fe_o, *o2 = ws + L.fe_o2, *pre = ws + L.fe_pre;
     const float *img2 = nB > 0 ? imgB : nullptr;
     int rc;
-#define LWS_FE(call)                                   \
-    {                                                  \
-        ProfScope p_(h, LWS_KC_FEATURE2D, st);         \
-        rc = (call);                                   \
-    }                                                  \
-    if (rc) return rc;
     // dres0, dres1, hourglass conv1..conv4: consecutive layers run pairwise in one launch (k_conv2d_pair /
     // k_conv2d_pair_mfma, the same fma chains as one kernel per layer)
-    LWS_FE(launch_conv2d_pair(n.fe[0], n.fe[1], imgA, nullptr, o, N, H, W, st, img2, nA));          // dres0
-    LWS_FE(launch_conv2d_pair(n.fe[2], n.fe[3], o, o, o2, N, H2, W2, st));                           // dres1 + o (:179)
-    LWS_FE(launch_conv2d_pair(n.fe[4], n.fe[5], o2, nullptr, pre, N, H2, W2, st));                   // conv1, conv2 -> pre
+    LWS_TIMED(LWS_KC_FEATURE2D, launch_conv2d_pair(n.fe[0], n.fe[1], imgA, nullptr, o, N, H, W, st, img2, nA));    // dres0
+    LWS_TIMED(LWS_KC_FEATURE2D, launch_conv2d_pair(n.fe[2], n.fe[3], o, o, o2, N, H2, W2, st));                     // dres1 + o (:179)
+    LWS_TIMED(LWS_KC_FEATURE2D, launch_conv2d_pair(n.fe[4], n.fe[5], o2, nullptr, pre, N, H2, W2, st));             // conv1, conv2 -> pre
     {
-        StopArm stop(fork_ev, st, fork_ext);
+        StopArm stop(fork, st);
         ProfScope p_(h, LWS_KC_FEATURE2D, st);
         rc = launch_conv2d_pair(n.fe[6], n.fe[7], pre, nullptr, f8, N, H4, W4, st);                  // conv3, conv4 -> f8
         LWS_HIP(stop.finish(rc));
     }
-    if (rc) return rc;
-#undef LWS_FE
-    if (head_only) return LWS_OK;
-    return feature_tail(h, N, H, W, L, f8, f4, f2, st, nullptr);
+    return rc;
 }
 
 // conv5 (-> f4), conv6, classif1 (-> f2), submodules.py:103-107,182-186.  ev (optional): ev[1] recorded after f4,
@@ -495,34 +484,19 @@ static int feature_tail(lws_ctx *h, int N, int H, int W, const WsLayout &L, floa
     float *ws = h->ws;
     float *o2 = ws + L.fe_o2, *pre = ws + L.fe_pre, *o3 = ws + L.fe_o3, *cls = ws + L.fe_cls;
     int rc;
-#define LWS_FE(call)                                   \
-    {                                                  \
-        ProfScope p_(h, LWS_KC_FEATURE2D, st);         \
-        rc = (call);                                   \
-    }                                                  \
-    if (rc) return rc;
     if (part & 1) {
-        LWS_FE(launch_conv2d_nchw(n.fe[8], f8, pre, f4, N, H8, W8, st));                                    // relu(conv5 + pre) (:103)
+        LWS_TIMED(LWS_KC_FEATURE2D, launch_conv2d_nchw(n.fe[8], f8, pre, f4, N, H8, W8, st));          // relu(conv5 + pre) (:103)
         if (ev != nullptr) LWS_HIP(hipEventRecord(ev[1], st));
     }
     if (part & 2) {
-        LWS_FE(launch_conv2d_nchw(n.fe[9], f4, o2, o3, N, H4, W4, st));                                     // conv6 + output (:106,:182)
-        LWS_FE(launch_conv2d_nchw(n.fe[10], o3, nullptr, cls, N, H2, W2, st));                              // classif1.0
-        LWS_FE(launch_conv2d_nchw(n.fe[11], cls, nullptr, f2, N, H2, W2, st));                              // classif1.2 -> f2
+        LWS_TIMED(LWS_KC_FEATURE2D, launch_conv2d_nchw(n.fe[9], f4, o2, o3, N, H4, W4, st));           // conv6 + output (:106,:182)
+        LWS_TIMED(LWS_KC_FEATURE2D, launch_conv2d_nchw(n.fe[10], o3, nullptr, cls, N, H2, W2, st));    // classif1.0
+        LWS_TIMED(LWS_KC_FEATURE2D, launch_conv2d_nchw(n.fe[11], cls, nullptr, f2, N, H2, W2, st));    // classif1.2 -> f2
         if (ev != nullptr) LWS_HIP(hipEventRecord(ev[2], st));
     }
-#undef LWS_FE
     return LWS_OK;
 }
 
-#define LWS_RF(kc, call)               \
-    {                                  \
-        ProfScope p_(h, kc, st);       \
-        rc = (call);                   \
-    }                                  \
-    if (rc) return rc;
-
-// refinement1_left(left) (models.py:158): depends on the left image only -> result in r_a (r_c is its scratch)
 // The refinement maps are [B,H,W,32] float32 = 128 B per pixel (134 MB at 8 x 256x512) and every block reads one and writes
 // another.  A chunk of pairs runs its whole layer chain before the next chunk starts, sized so that one map of the chunk is
 // at most `ref_chunk_mb` MB: the three maps a block chain touches then stay in the 256 MiB Infinity Cache between a block's
@@ -537,70 +511,87 @@ static int refine_chunk(const lws_ctx *h, int B, int H, int W)
     return c < B ? c : B;
 }
 
-static int refine_left_chunk(lws_ctx *h, const float *left, int B, int H, int W, const WsLayout &L, hipStream_t st, int b0);
-
+// refinement1_left(left) (models.py:158): depends on the left image only -> result in r_a.  Each chunk keeps its slice of r_a;
+// the scratch map r_c is the SAME memory for every chunk (it stays cache-resident)
 static int refine_left(lws_ctx *h, const float *left, int B, int H, int W, const WsLayout &L, hipStream_t st)
 {
-    const int CH = refine_chunk(h, B, H, W);
-    for (int b0 = 0; b0 < B; b0 += CH) {
-        const int rc = refine_left_chunk(h, left + (size_t)b0 * 3 * H * W, std::min(CH, B - b0), H, W, L, st, b0);
-        if (rc) return rc;
-    }
-    return LWS_OK;
-}
-
-static int refine_left_chunk(lws_ctx *h, const float *left, int B, int H, int W, const WsLayout &L, hipStream_t st, int b0)
-{
     const Net2d &n = h->net2d;
-    // the result keeps its slice of r_a; the scratch map r_c is the SAME memory for every chunk (it stays cache-resident)
-    float *ra = h->ws + L.r_a + (size_t)b0 * H * W * 32, *rc_ = h->ws + L.r_c;
+    const int CH = refine_chunk(h, B, H, W);
+    float *rc_ = h->ws + L.r_c;
     int rc;
-    if ((h->opt.fuse_first & 2) && ref_first_dws_can_fuse(n.r1[0][0], 3)) {
-        // the 3 -> 32 convolution is recomputed inside the first block's staging: one launch less, and the 32-channel map
-        // it would write (and the block read back) never exists
-        LWS_RF(LWS_KC_REF_DWS, launch_ref_first_dws(n.r1[0][0], left, 3, n.r1_first_mfma[0], rc_, B, H, W, st));
-    } else {
-        LWS_RF(LWS_KC_REF_FIRST, launch_ref_first(left, 3, n.r1_first[0], ra, B, H, W, st));
-        LWS_RF(LWS_KC_REF_DWS, launch_ref_dws(n.r1[0][0], ra, rc_, B, H, W, st));
+    for (int b0 = 0; b0 < B; b0 += CH) {
+        const int nb = std::min(CH, B - b0);
+        float *ra = h->ws + L.r_a + (size_t)b0 * H * W * 32;
+        StageMap img{const_cast<float *>(left) + (size_t)b0 * 3 * H * W, true};
+        if ((h->opt.fuse_first & 2) && ref_first_dws_can_fuse(n.r1[0][0], 3)) {
+            // the 3 -> 32 convolution is recomputed inside the first block's staging: one launch less, and the 32-channel map
+            // it would write (and the block read back) never exists
+            LWS_TIMED(LWS_KC_REF_DWS, launch_ref_first_dws(n.r1[0][0], img, 3, n.r1_first_mfma[0], rc_, nb, H, W, st));
+        } else {
+            LWS_TIMED(LWS_KC_REF_FIRST, launch_ref_first(img.mem, 3, n.r1_first[0], ra, nb, H, W, st));
+            LWS_TIMED(LWS_KC_REF_DWS, launch_ref_dws(n.r1[0][0], ra, rc_, nb, H, W, st));
+        }
+        LWS_TIMED(LWS_KC_REF_DWS, launch_ref_dws(n.r1[0][1], rc_, ra, nb, H, W, st));
+        LWS_TIMED(LWS_KC_REF_DWS, launch_ref_dws(n.r1[0][2], ra, rc_, nb, H, W, st));
+        LWS_TIMED(LWS_KC_REF_DWS, launch_ref_dws(n.r1[0][3], rc_, ra, nb, H, W, st));
     }
-    LWS_RF(LWS_KC_REF_DWS, launch_ref_dws(n.r1[0][1], rc_, ra, B, H, W, st));
-    LWS_RF(LWS_KC_REF_DWS, launch_ref_dws(n.r1[0][2], ra, rc_, B, H, W, st));
-    LWS_RF(LWS_KC_REF_DWS, launch_ref_dws(n.r1[0][3], rc_, ra, B, H, W, st));
     return LWS_OK;
 }
 
-// models.py:159-162: refinement1_disp(pred3), refinement2(concat), + pred3.  Needs refine_left's result in r_a.
-// Deferred full-resolution maps: the fused last-layer + soft-argmin kernel of stage s (s = 1, 2) leaves the
-// low-resolution disparity low[s]; instead of a k_upsample_add launch on the critical chain, the consumer of
-// pred_out[s] (stage 3's warp kernel for s = 1, the refinement's first block for s = 2) evaluates
-// upsample(low[s]) + pred_out[s-1] on demand (DeferredMap, lws_device_math.h: the same operations, bit for bit) and
-// writes the map out as a by-product, since it is an output of the path.
-struct DeferState {
-    bool allow_last = false;                 // the caller will consume pred_out[2] through refine_rest
-    // stage 1 (round 5, batches <= 2): the last Conv3D layer + soft-argmin leave low[0] (def[0]) and NO launch materialises
-    // pred1: stage 2's warp kernel evaluates the four taps it needs from low[0]; stage 3's warp kernel, which evaluates and
-    // writes the deferred stage-2 map pred2 = upsample(low[1]) + pred1 on its 2 x 2 blocks, evaluates pred1 =
-    // upsample(low[0]) at the same pixels and writes it out too (two-level DeferredMap).  pred1_unwritten: nobody has yet.
-    bool allow_first = false;                // the caller runs the whole forward (lws_forward)
-    bool pred1_unwritten = false;
-    hipEvent_t stage1_stop = nullptr;        // lws_forward's second fork: complete once stage 1's Conv3D stack is (conv3d_stack's last_stop)
-    int stage1_stop_after = 0;               // ... or once its k-th middle layer is (option "fork2_after")
-    bool stage1_stop_ext = false;            // bound to that kernel's completion signal (not under hipGraph capture)
-    bool def[3] = {false, false, false};
-    const float *low[3] = {nullptr, nullptr, nullptr};
-    int lh[3] = {0, 0, 0}, lw[3] = {0, 0, 0};
+// One chunk of refine_rest: pairs b0 .. b0 + n - 1 on stream st, its scratch maps from pair `scratch` on.  after_disp
+// (optional): recorded once the chunk's refinement1_disp branch is done.
+struct RefChunk {
+    int b0, n, scratch;
+    hipStream_t st;
+    hipEvent_t after_disp;
 };
 
-static bool refine_can_defer(const lws_ctx *h);
-
-static int refine_rest_chunk(lws_ctx *h, float *pred3, int B, int H, int W, const WsLayout &L, float *pred4, hipStream_t st,
-                             const DeferState *ds, const float *pred2, int b0, int scratch_b0 = 0, hipEvent_t after_disp = nullptr,
-                             bool fuse_last = false);
-
-static int refine_rest(lws_ctx *h, float *pred3, int B, int H, int W, const WsLayout &L, float *pred4,
-                       hipStream_t st, const DeferState *ds = nullptr, const float *pred2 = nullptr)
+static int refine_rest_chunk(lws_ctx *h, const StageMap &pred3, const RefChunk &c, int H, int W, const WsLayout &L,
+                             float *pred4, bool fuse_last)
 {
-    const int CH = (ds != nullptr && ds->def[2]) ? B : refine_chunk(h, B, H, W);      // (deferred maps: batches <= 2, one chunk)
+    const Net2d &n = h->net2d;
+    const int B = c.n;
+    hipStream_t st = c.st;
+    const size_t po = (size_t)c.b0 * H * W;
+    StageMap p3 = pred3;          // this chunk's pairs (a deferred map is one chunk)
+    p3.mem += po;
+    pred4 += po;
+    // r_a: this chunk's slice (refinement1_left's result); r_b, r_c: the same memory for every chunk
+    float *ra = h->ws + L.r_a + po * 32, *rb = h->ws + L.r_b + (size_t)c.scratch * H * W * 32,
+          *rc_ = h->ws + L.r_c + (size_t)c.scratch * H * W * 32;
+    int rc;
+    if ((h->opt.fuse_first & 1) && ref_first_dws_can_fuse(n.r1[1][0], 1)) {
+        // refinement1_disp: the 1 -> 32 convolution is recomputed inside the first block's staging (one launch less); a deferred
+        // pred3 is evaluated there and written out
+        LWS_TIMED(LWS_KC_REF_DWS, launch_ref_first_dws(n.r1[1][0], p3, 1, n.r1_first_mfma[1], rc_, B, H, W, st, ioff_of(h)));
+    } else {
+        LWS_TIMED(LWS_KC_REF_FIRST, launch_ref_first(p3.mem, 1, n.r1_first[1], rb, B, H, W, st));
+        LWS_TIMED(LWS_KC_REF_DWS, launch_ref_dws(n.r1[1][0], rb, rc_, B, H, W, st));
+    }
+    // refinement1_disp blocks 2..4 (dil 4, 8, 16; block 1 ran above): rc_ -> ... -> rb
+    LWS_TIMED(LWS_KC_REF_DWS, launch_ref_dws(n.r1[1][1], rc_, rb, B, H, W, st));
+    LWS_TIMED(LWS_KC_REF_DWS, launch_ref_dws(n.r1[1][2], rb, rc_, B, H, W, st));
+    LWS_TIMED(LWS_KC_REF_DWS, launch_ref_dws(n.r1[1][3], rc_, rb, B, H, W, st));
+    if (c.after_disp != nullptr) LWS_HIP(hipEventRecord(c.after_disp, st));
+    LWS_TIMED(LWS_KC_REF_CONV64, launch_ref_conv64(n.r2_first, ra, rb, rc_, B, H, W, st));
+    LWS_TIMED(LWS_KC_REF_DWS, launch_ref_dws(n.r2[0], rc_, ra, B, H, W, st));
+    LWS_TIMED(LWS_KC_REF_DWS, launch_ref_dws(n.r2[1], ra, rc_, B, H, W, st));
+    LWS_TIMED(LWS_KC_REF_DWS, launch_ref_dws(n.r2[2], rc_, ra, B, H, W, st));
+    // refinement2[4] + refinement2[5] + pred3: one launch (k_ref_dws_last) or two (refine_rest decides)
+    if (fuse_last && ref_dws_last_can_fuse(n.r2[3])) {
+        LWS_TIMED(LWS_KC_REF_LAST, launch_ref_dws_last(n.r2[3], ra, n.r2_last, p3.mem, pred4, B, H, W, st));
+        return LWS_OK;
+    }
+    LWS_TIMED(LWS_KC_REF_DWS, launch_ref_dws(n.r2[3], ra, rc_, B, H, W, st));
+    LWS_TIMED(LWS_KC_REF_LAST, launch_ref_last(rc_, n.r2_last, p3.mem, pred4, B, H, W, st));
+    return LWS_OK;
+}
+#undef LWS_TIMED
+
+// models.py:159-162: refinement1_disp(pred3), refinement2(concat), + pred3.  Needs refine_left's result in r_a.
+static int refine_rest(lws_ctx *h, const StageMap &pred3, int B, int H, int W, const WsLayout &L, float *pred4, hipStream_t st)
+{
+    const int CH = pred3.written ? refine_chunk(h, B, H, W) : B;      // (a deferred map: batches <= 2, one chunk)
     // Option "ref_pipe": chunks alternate between the caller's stream and the side stream (idle by now), each starting once the
     // previous chunk has finished its disparity branch, so that one chunk's memory-bound blocks run beside the other's MFMA-bound
     // 64 -> 32 convolution; odd chunks use the second half of the (batch-sized) scratch maps.  Two chunks only add their
@@ -618,12 +609,10 @@ static int refine_rest(lws_ctx *h, float *pred3, int B, int H, int W, const WsLa
     }
     int k = 0;
     for (int b0 = 0; b0 < B; b0 += CH, ++k) {
-        const size_t po = (size_t)b0 * H * W;
-        hipStream_t cs = (pipe && (k & 1)) ? h->side : st;
-        if (pipe && k > 0) LWS_HIP(hipStreamWaitEvent(cs, h->ev_feat[(k - 1) & 1], 0));
-        const int rc = refine_rest_chunk(h, pred3 + po, std::min(CH, B - b0), H, W, L, pred4 + po, cs, ds,
-                                         pred2 != nullptr ? pred2 + po : nullptr, b0, pipe ? (k & 1) * CH : 0,
-                                         pipe ? h->ev_feat[k & 1] : nullptr, fuse_last);
+        const RefChunk c{b0, std::min(CH, B - b0), pipe ? (k & 1) * CH : 0, (pipe && (k & 1)) ? h->side : st,
+                         pipe ? h->ev_feat[k & 1] : nullptr};
+        if (pipe && k > 0) LWS_HIP(hipStreamWaitEvent(c.st, h->ev_feat[(k - 1) & 1], 0));
+        const int rc = refine_rest_chunk(h, pred3, c, H, W, L, pred4, fuse_last);
         if (rc) return rc;
     }
     if (pipe) {
@@ -633,182 +622,98 @@ static int refine_rest(lws_ctx *h, float *pred3, int B, int H, int W, const WsLa
     return LWS_OK;
 }
 
-static int refine_rest_chunk(lws_ctx *h, float *pred3, int B, int H, int W, const WsLayout &L, float *pred4, hipStream_t st,
-                             const DeferState *ds, const float *pred2, int b0, int scratch_b0, hipEvent_t after_disp, bool fuse_last)
+// Deferred maps (StageMap): where the caller lets map[s] wait for its consumer (keep), the fused last Conv3D layer + soft-argmin
+// leaves the low-resolution disparity and no launch on the critical chain materialises the map.  Stage 1's map is read by stage
+// 2's warp kernel (the four taps it needs) and written out by stage 3's, which evaluates it beside the deferred stage-2 map
+// (two-level DeferredMap); stage 3's map is written out by the refinement's first block.  Batches <= 2 only (two launches fewer
+// on a batch-1 chain; from batch 4 up the heavier consumers cost more than the launches, so large batches keep the separate
+// k_upsample_add launches), and only at exact 2x geometry: with odd H or W the four taps of a stage-3 pixel are not the 2x2
+// block it owns.  Stage 1: the fused last layer only pays when its map can leave the chain; otherwise the
+// k_softargmin_upsample launch does soft-argmin AND upsample in one kernel.
+static bool defers(const lws_ctx *h, int s, int B, int H, int W, bool keep)
 {
-    const Net2d &n = h->net2d;
-    // r_a: this chunk's slice (refinement1_left's result); r_b, r_c: the same memory for every chunk
-    float *ra = h->ws + L.r_a + (size_t)b0 * H * W * 32, *rb = h->ws + L.r_b + (size_t)scratch_b0 * H * W * 32,
-          *rc_ = h->ws + L.r_c + (size_t)scratch_b0 * H * W * 32;
-    int rc;
-    if ((h->opt.fuse_first & 1) && ref_first_dws_can_fuse(n.r1[1][0], 1)) {
-        // refinement1_disp: the 1 -> 32 convolution is recomputed inside the first block's staging (one launch less)
-        if (ds != nullptr && ds->def[2]) {
-            // pred3 = upsample(low[2]) + pred2 was not materialised: this kernel evaluates it and writes it out
-            LWS_RF(LWS_KC_REF_DWS, launch_ref_first_dws(n.r1[1][0], pred2, 1, n.r1_first_mfma[1], rc_, B, H, W, st, ds->low[2],
-                                                        ds->lh[2], ds->lw[2], pred3, ioff_of(h)));
-        } else {
-            LWS_RF(LWS_KC_REF_DWS, launch_ref_first_dws(n.r1[1][0], pred3, 1, n.r1_first_mfma[1], rc_, B, H, W, st));
-        }
-    } else {
-        LWS_RF(LWS_KC_REF_FIRST, launch_ref_first(pred3, 1, n.r1_first[1], rb, B, H, W, st));
-        LWS_RF(LWS_KC_REF_DWS, launch_ref_dws(n.r1[1][0], rb, rc_, B, H, W, st));
-    }
-    // refinement1_disp blocks 2..4 (dil 4, 8, 16; block 1 ran above): rc_ -> ... -> rb
-    LWS_RF(LWS_KC_REF_DWS, launch_ref_dws(n.r1[1][1], rc_, rb, B, H, W, st));
-    LWS_RF(LWS_KC_REF_DWS, launch_ref_dws(n.r1[1][2], rb, rc_, B, H, W, st));
-    LWS_RF(LWS_KC_REF_DWS, launch_ref_dws(n.r1[1][3], rc_, rb, B, H, W, st));
-    if (after_disp != nullptr) LWS_HIP(hipEventRecord(after_disp, st));
-    LWS_RF(LWS_KC_REF_CONV64, launch_ref_conv64(n.r2_first, ra, rb, rc_, B, H, W, st));
-    LWS_RF(LWS_KC_REF_DWS, launch_ref_dws(n.r2[0], rc_, ra, B, H, W, st));
-    LWS_RF(LWS_KC_REF_DWS, launch_ref_dws(n.r2[1], ra, rc_, B, H, W, st));
-    LWS_RF(LWS_KC_REF_DWS, launch_ref_dws(n.r2[2], rc_, ra, B, H, W, st));
-    // refinement2[4] + refinement2[5] + pred3: one launch (k_ref_dws_last) or two (refine_rest decides)
-    if (fuse_last && ref_dws_last_can_fuse(n.r2[3])) {
-        LWS_RF(LWS_KC_REF_LAST, launch_ref_dws_last(n.r2[3], ra, n.r2_last, pred3, pred4, B, H, W, st));
-        return LWS_OK;
-    }
-    LWS_RF(LWS_KC_REF_DWS, launch_ref_dws(n.r2[3], ra, rc_, B, H, W, st));
-    LWS_RF(LWS_KC_REF_LAST, launch_ref_last(rc_, n.r2_last, pred3, pred4, B, H, W, st));
-    return LWS_OK;
-}
-#undef LWS_RF
-
-static bool refine_can_defer(const lws_ctx *h)
-{
-    return (h->opt.fuse_first & 1) && h->have_2d && ref_first_dws_can_fuse(h->net2d.r1[1][0], 1);
+    return keep && h->opt.defer_upsample != 0 && B <= 2 && H % 2 == 0 && W % 2 == 0 && (s > 0 || h->opt.fuse_last1 != 0);
 }
 
-static int stages_impl(lws_ctx *h, const float *const featsL[3], const float *const featsR[3], int B, int H, int W,
-                       float *const pred_out[3], const WsLayout &L, hipStream_t st, hipEvent_t *feat_ready = nullptr,
-                       const std::function<int()> &after_stage1_stack = nullptr, DeferState *ds = nullptr);
-
-}  // namespace lws
-
-using namespace lws;
-
-namespace lws {
-
-// feat_ready (optional): events after which the stage-2 / stage-3 feature maps are complete (feat_ready[1], [2])
-static int stages_impl(lws_ctx *h, const float *const featsL[3], const float *const featsR[3], int B, int H, int W,
-                       float *const pred_out[3], const WsLayout &L, hipStream_t st, hipEvent_t *feat_ready,
-                       const std::function<int()> &after_stage1_stack, DeferState *ds)
+// Stage s of LWSNet.forward up to its Conv3D stack (models.py:119-138; fork: see Fork).  fused: the stack's last layer did the
+// soft-argmin too (into low[s]).
+static int stage_volume(lws_ctx *h, int s, const float *featL, const float *featR, int B, int H, int W, StageMap map[3],
+                        const WsLayout &L, hipStream_t st, bool defer, bool &fused, const Fork &fork = Fork())
 {
-    int rc;
-    float *act_a = h->ws + L.act_a, *act_b = h->ws + L.act_b, *raw = h->ws + L.cost_raw, *cost = h->ws + L.cost_out;
-    const bool defer_up = h->opt.defer_upsample != 0;
-    DeferState local;
-    if (ds == nullptr) ds = &local;
     static const int feat_c[3] = {16, 16, 8};   // feature_extraction outputs, submodules.py:101,104,186
-    // pred_out[0] as memory (k_upsample_add's `prev`): when stage 1 left its map deferred and the consumer that would have
-    // written it out (stage 3's warp kernel on a deferred stage-2 map) is not coming, one k_upsample_add materialises it
-    auto need_pred1 = [&]() -> int {
-        if (!ds->pred1_unwritten) return LWS_OK;
-        ds->pred1_unwritten = false;
-        ProfScope p(h, LWS_KC_UPSAMPLE, st);
-        return launch_upsample_add(ds->low[0], nullptr, pred_out[0], B, ds->lh[0], ds->lw[0], H, W, st, ioff_of(h));   // :145-148
-    };
-    for (int s = 0; s < 3; ++s) {
-        int D, hh, ww;
-        stage_dims(h, s, H, W, D, hh, ww);
-        float *low = h->ws + L.low[s];
-        if (s > 0 && feat_ready != nullptr && feat_ready[s] != nullptr) LWS_HIP(hipStreamWaitEvent(st, feat_ready[s], 0));
-        bool first_done = false;
-        if (s == 0 && shift_first_can_fuse(h->stage[0], feat_c[0])) {
-            // stage-1 volume and the first Conv3D layer in one launch (the raw volume is still written: skip input)
-            ProfScope p(h, LWS_KC_CONV3D_FIRST, st);
-            rc = launch_shift_first(h->stage[0], featsL[0], featsR[0], raw, act_a, B, feat_c[0], D, hh, ww, st,
-                                    h->cfg.feature_fp16 != 0);                                                   // :131
-            first_done = true;
-        } else if (s == 0) {
-            ProfScope p(h, LWS_KC_VOLUME_SHIFT, st);
-            rc = launch_volume_l1_shift(featsL[0], featsR[0], raw, B, feat_c[0], hh, ww, D, st, h->cfg.feature_fp16 != 0);   // :131
-        } else if (ds->def[s - 1]) {
-            // pred_out[s-1] is deferred: read it as upsample(low[s-1]) + pred_out[s-2] and (s == 2) write it out.  s == 1: stage
-            // 1's map has no predecessor and is not written here; s == 2 with pred1 still unwritten: pred1 = upsample(low[0]) is
-            // evaluated at the same pixels and written out as well
-            const bool two = s == 2 && ds->pred1_unwritten;
-            ProfScope p(h, LWS_KC_VOLUME_WARP, st);
-            rc = launch_volume_l1_warp(featsL[s], featsR[s], (s == 1 || two) ? nullptr : pred_out[s - 2], raw, nullptr, B, feat_c[s],
-                                       hh, ww, H, W, h->cfg.maxdisplist[s], st, h->cfg.feature_fp16 != 0, ds->low[s - 1],
-                                       ds->lh[s - 1], ds->lw[s - 1], s == 2 ? pred_out[s - 1] : nullptr, h->opt.warp_form,
-                                       two ? ds->low[0] : nullptr, two ? ds->lh[0] : 0, two ? ds->lw[0] : 0,
-                                       two ? pred_out[0] : nullptr, ioff_of(h));
-            if (two) ds->pred1_unwritten = false;
-        } else {
-            ProfScope p(h, LWS_KC_VOLUME_WARP, st);
-            rc = launch_volume_l1_warp(featsL[s], featsR[s], pred_out[s - 1], raw, nullptr, B, feat_c[s], hh, ww, H, W,
-                                       h->cfg.maxdisplist[s], st, h->cfg.feature_fp16 != 0, nullptr, 0, 0, nullptr,
-                                       h->opt.warp_form, nullptr, 0, 0, nullptr, ioff_of(h));                 // :119-127
-        }
-        if (rc) return rc;
-        const float start = s == 0 ? 0.0f : (float)(-h->cfg.maxdisplist[s] + 1);
-        bool fused = false;
-        // stage 1: the fused last layer only pays when the full-resolution map can leave the chain (below); otherwise the
-        // k_softargmin_upsample launch does soft-argmin AND upsample in one kernel
-        const bool defer_first = s == 0 && defer_up && h->opt.fuse_last1 != 0 && ds->allow_first && B <= 2 && H % 2 == 0 && W % 2 == 0;
-        rc = conv3d_stack(h, s, raw, cost, act_a, act_b, B, D, hh, ww, st, (s > 0 || defer_first) ? low : nullptr, start, &fused,
-                          first_done, s == 0 ? ds->stage1_stop : nullptr, s == 0 ? ds->stage1_stop_after : 0,
-                          s == 0 && ds->stage1_stop_ext);                                                        // :136-138
-        if (rc) return rc;
-        if (s == 0 && after_stage1_stack) {
-            rc = after_stage1_stack();
-            if (rc) return rc;
-        }
-        if (s == 0 && fused) {
-            ds->def[0] = true;
-            ds->low[0] = low;
-            ds->lh[0] = hh;
-            ds->lw[0] = ww;
-            ds->pred1_unwritten = true;
-            continue;
-        }
-        const bool defer_this = fused && defer_up && B <= 2 && H % 2 == 0 && W % 2 == 0 && (s == 1 || (s == 2 && ds->allow_last));
-        if (s >= 1 && !(s == 1 && defer_this)) {
-            // a launch below reads pred_out[0] (s == 1), or the path is about to end (s == 2) with pred1 still unwritten
-            rc = need_pred1();
-            if (rc) return rc;
-        }
-        if (!fused) {
-            // soft-argmin + rescale + upsample (+ previous stage) in one launch                             :142-148
-            if (H % hh == 0 && W % ww == 0) {
-                ProfScope p(h, LWS_KC_SOFTARGMIN, st);
-                rc = launch_softargmin_upsample(cost, s == 0 ? nullptr : pred_out[s - 1], pred_out[s], nullptr, B, D, hh, ww,
-                                                H, W, start, st, ioff_of(h));
-            } else {
-                // H or W = 8k-1: the resize ratio is not an integer, which the fused kernel's tile -> block map needs
-                {
-                    ProfScope p(h, LWS_KC_SOFTARGMIN, st);
-                    rc = launch_softargmin(cost, low, B, D, hh, ww, start, st);
-                }
-                if (rc) return rc;
-                ProfScope p(h, LWS_KC_UPSAMPLE, st);
-                rc = launch_upsample_add(low, s == 0 ? nullptr : pred_out[s - 1], pred_out[s], B, hh, ww, H, W, st, ioff_of(h));
-            }
-            if (rc) return rc;
-            continue;
-        }
-        // stage 2's map is consumed by stage 3's warp at exactly half resolution; stage 3's by the refinement (two launches
-        // fewer on a batch-1 chain; from batch 4 up the heavier consumers cost more than the launches, so large batches keep
-        // the separate k_upsample_add launches)
-        // (only at exact 2x geometry: with odd H or W the four taps of a stage-3 pixel are not the 2x2 block it owns)
-        if (defer_this) {
-            ds->def[s] = true;
-            ds->low[s] = low;
-            ds->lh[s] = hh;
-            ds->lw[s] = ww;
-            continue;
-        }
-        {
-            ProfScope p(h, LWS_KC_UPSAMPLE, st);
-            rc = launch_upsample_add(low, s == 0 ? nullptr : pred_out[s - 1], pred_out[s], B, hh, ww, H, W, st, ioff_of(h));   // :145-156
-        }
-        if (rc) return rc;
+    float *act_a = h->ws + L.act_a, *act_b = h->ws + L.act_b, *raw = h->ws + L.cost_raw, *cost = h->ws + L.cost_out;
+    float *low = h->ws + L.low[s];
+    int D, hh, ww;
+    stage_dims(h, s, H, W, D, hh, ww);
+    int rc;
+    bool first_done = false;
+    if (s == 0 && shift_first_can_fuse(h->stage[0], feat_c[0])) {
+        // stage-1 volume and the first Conv3D layer in one launch (the raw volume is still written: skip input)
+        ProfScope p(h, LWS_KC_CONV3D_FIRST, st);
+        rc = launch_shift_first(h->stage[0], featL, featR, raw, act_a, B, feat_c[0], D, hh, ww, st,
+                                h->cfg.feature_fp16 != 0);                                                          // :131
+        first_done = true;
+    } else if (s == 0) {
+        ProfScope p(h, LWS_KC_VOLUME_SHIFT, st);
+        rc = launch_volume_l1_shift(featL, featR, raw, B, feat_c[0], hh, ww, D, st, h->cfg.feature_fp16 != 0);         // :131
+    } else {
+        ProfScope p(h, LWS_KC_VOLUME_WARP, st);
+        rc = launch_volume_l1_warp(featL, featR, map[s - 1], raw, nullptr, B, feat_c[s], hh, ww, H, W, h->cfg.maxdisplist[s],
+                                   st, h->cfg.feature_fp16 != 0, h->opt.warp_form, ioff_of(h));                       // :119-127
     }
-    return LWS_OK;
+    if (rc) return rc;
+    const float start = s == 0 ? 0.0f : (float)(-h->cfg.maxdisplist[s] + 1);
+    fused = false;
+    return conv3d_stack(h, s, raw, cost, act_a, act_b, B, D, hh, ww, st, (s > 0 || defer) ? low : nullptr, start, &fused,
+                        first_done, fork);                                                                          // :136-138
 }
 
-}  // namespace lws
+// Materialises a deferred map with one k_upsample_add (models.py:145-148,153-156); the map before it is in memory
+static int write_out(lws_ctx *h, StageMap &m, int B, int H, int W, hipStream_t st)
+{
+    if (m.written) return LWS_OK;
+    ProfScope p(h, LWS_KC_UPSAMPLE, st);
+    const int rc = launch_upsample_add(m.low, m.prev != nullptr ? m.prev->mem : nullptr, m.mem, B, m.h, m.w, H, W, st, ioff_of(h));
+    m.written = rc == LWS_OK;
+    return rc;
+}
+
+// The map of stage s, after stage_volume: left deferred, or computed into memory (models.py:142-156).  A map before it that
+// is still unwritten is materialised first.
+static int stage_map(lws_ctx *h, int s, int B, int H, int W, StageMap map[3], const WsLayout &L, hipStream_t st, bool defer,
+                     bool fused)
+{
+    int D, hh, ww;
+    stage_dims(h, s, H, W, D, hh, ww);
+    const float start = s == 0 ? 0.0f : (float)(-h->cfg.maxdisplist[s] + 1);
+    float *cost = h->ws + L.cost_out, *low = h->ws + L.low[s];
+    StageMap &m = map[s];
+    m.low = low;
+    m.h = hh;
+    m.w = ww;
+    m.prev = s > 0 ? &map[s - 1] : nullptr;
+    if (fused && defer) return LWS_OK;
+    int rc;
+    if (m.prev != nullptr) {
+        rc = write_out(h, *m.prev, B, H, W, st);
+        if (rc) return rc;
+    }
+    if (!fused && H % hh == 0 && W % ww == 0) {
+        // soft-argmin + rescale + upsample (+ previous stage) in one launch                                     :142-148
+        ProfScope p(h, LWS_KC_SOFTARGMIN, st);
+        rc = launch_softargmin_upsample(cost, m.prev != nullptr ? m.prev->mem : nullptr, m.mem, nullptr, B, D, hh, ww, H, W,
+                                        start, st, ioff_of(h));
+        m.written = rc == LWS_OK;
+        return rc;
+    }
+    if (!fused) {
+        // H or W = 8k-1: the resize ratio is not an integer, which the fused kernel's tile -> block map needs
+        ProfScope p(h, LWS_KC_SOFTARGMIN, st);
+        rc = launch_softargmin(cost, low, B, D, hh, ww, start, st);
+        if (rc) return rc;
+    }
+    return write_out(h, m, B, H, W, st);                                                                          // :145-156
+}
 
 // Every entry point that touches the GPU through a handle requires the calling thread's current HIP device to be the
 // handle's (recorded by lws_create, or set with lws_set_option("device")): its parameter slab, workspace, streams and
@@ -836,6 +741,21 @@ static int check_device(const lws_ctx *h, const char *what)
         if (rc_dev_) return rc_dev_;           \
     } while (0)
 
+// The preamble of the entry points that run the network: the handle's device is current, lws_finalize has run (with every 2D
+// tensor set: need_2d; the error `state_msg` otherwise), the workspace holds `floats`, and no stop event is armed on this thread.
+static int begin_call(lws_ctx *h, const char *what, bool need_2d, const char *state_msg, size_t floats)
+{
+    LWS_CHECK_DEVICE(h, what);
+    if (!h->finalized || (need_2d && !h->have_2d)) {
+        set_error("%s", state_msg);
+        return LWS_ERR_STATE;
+    }
+    const int rc = ensure_ws(h, floats);
+    if (rc) return rc;
+    (void)stop_event_take();
+    return LWS_OK;
+}
+
 // side stream and cross-stream events of lws_forward: created by lws_reserve (which promises that later calls allocate
 // nothing) or, for callers that never reserve, on the first forward.  (A CU-masked side stream was built, measured and removed
 // in round 5: profiles/NOTES.md, "CU masks".)
@@ -850,6 +770,10 @@ static int ensure_streams(lws_ctx *h)
     LWS_HIP(hipEventCreateWithFlags(&h->ev_fork2, ef));
     return LWS_OK;
 }
+
+}  // namespace lws
+
+using namespace lws;
 
 extern "C" {
 
@@ -1240,7 +1164,8 @@ int lws_volume_l1_warp(const float *L, const float *R, const float *prev_disp, f
     LWS_CHECK_ARG(L && R && prev_disp && cost, "volume_l1_warp: null pointer");
     LWS_CHECK_ARG(B >= 1 && h >= 1 && w >= 1 && H >= h && W >= w && m >= 1 && 2 * m - 1 <= 64,
                   "volume_l1_warp: bad shape B=%d h=%d w=%d H=%d W=%d m=%d", B, h, w, H, W, m);
-    return launch_volume_l1_warp(L, R, prev_disp, cost, wflow_out, B, C, h, w, H, W, m, (hipStream_t)stream);
+    StageMap prev{const_cast<float *>(prev_disp), true};      // (a written map is only read)
+    return launch_volume_l1_warp(L, R, prev, cost, wflow_out, B, C, h, w, H, W, m, (hipStream_t)stream);
 }
 
 int lws_conv3d_stack(lws_handle h, int stage, const float *cost_in, float *cost_out, int B, int D, int hh, int ww,
@@ -1249,15 +1174,9 @@ int lws_conv3d_stack(lws_handle h, int stage, const float *cost_in, float *cost_
     LWS_CHECK_ARG(h && cost_in && cost_out && cost_in != cost_out, "conv3d_stack: bad pointer");
     LWS_CHECK_ARG(stage >= 0 && stage < 3, "conv3d_stack: stage must be 0..2 (got %d)", stage);
     LWS_CHECK_ARG(B >= 1 && D >= 1 && hh >= 1 && ww >= 1, "conv3d_stack: bad shape");
-    LWS_CHECK_DEVICE(h, "lws_conv3d_stack");
-    if (!h->finalized) {
-        set_error("conv3d_stack: lws_finalize has not been called");
-        return LWS_ERR_STATE;
-    }
     const size_t act = ((size_t)B * D * hh * ww * h->stage[stage].c3 + 63) & ~(size_t)63;
-    int rc = ensure_ws(h, 2 * act);
+    const int rc = begin_call(h, "lws_conv3d_stack", false, "conv3d_stack: lws_finalize has not been called", 2 * act);
     if (rc) return rc;
-    (void)stop_event_take();
     return conv3d_stack(h, stage, cost_in, cost_out, h->ws, h->ws + act, B, D, hh, ww, (hipStream_t)stream);
 }
 
@@ -1284,16 +1203,21 @@ int lws_disparity_stages(lws_handle h, const float *const featsL[3], const float
         LWS_CHECK_ARG(featsL[s] && featsR[s] && pred_out[s], "disparity_stages: null tensor for stage %d", s);
     int rc = check_size(h, B, H, W);
     if (rc) return rc;
-    LWS_CHECK_DEVICE(h, "lws_disparity_stages");
-    if (!h->finalized) {
-        set_error("disparity_stages: lws_finalize has not been called");
-        return LWS_ERR_STATE;
-    }
     const WsLayout L = ws_layout(h, B, H, W);
-    rc = ensure_ws(h, L.total);
+    rc = begin_call(h, "lws_disparity_stages", false, "disparity_stages: lws_finalize has not been called", L.total);
     if (rc) return rc;
-    (void)stop_event_take();
-    return stages_impl(h, featsL, featsR, B, H, W, pred_out, L, (hipStream_t)stream);
+    hipStream_t st = (hipStream_t)stream;
+    StageMap map[3] = {{pred_out[0]}, {pred_out[1]}, {pred_out[2]}};
+    for (int s = 0; s < 3; ++s) {
+        // only stage 2's map may wait for its consumer (stage 3's warp kernel writes it out): the caller reads all three
+        const bool defer = defers(h, s, B, H, W, s == 1);
+        bool fused;
+        rc = stage_volume(h, s, featsL[s], featsR[s], B, H, W, map, L, st, defer, fused);
+        if (rc) return rc;
+        rc = stage_map(h, s, B, H, W, map, L, st, defer, fused);
+        if (rc) return rc;
+    }
+    return LWS_OK;
 }
 
 int lws_feature_extraction(lws_handle h, const float *img, int N, int H, int W, float *f8, float *f4, float *f2,
@@ -1302,35 +1226,29 @@ int lws_feature_extraction(lws_handle h, const float *img, int N, int H, int W, 
     LWS_CHECK_ARG(h && img && f8 && f4 && f2, "feature_extraction: null pointer");
     LWS_CHECK_ARG(N >= 1 && H > 0 && W > 0 && half_up(H) % 4 == 0 && half_up(W) % 4 == 0,
                   "feature_extraction: unsupported size N=%d %dx%d (ceil(H/2), ceil(W/2) divisible by 4)", N, H, W);
-    LWS_CHECK_DEVICE(h, "lws_feature_extraction");
-    if (!h->finalized || !h->have_2d) {
-        set_error("feature_extraction: the 2D network tensors were not all set before lws_finalize");
-        return LWS_ERR_STATE;
-    }
     // workspace is planned per pair: N images = ceil(N/2) pairs
     const WsLayout L = ws_layout(h, (N + 1) / 2, H, W);
-    int rc = ensure_ws(h, L.total_all);
+    int rc = begin_call(h, "lws_feature_extraction", true,
+                        "feature_extraction: the 2D network tensors were not all set before lws_finalize", L.total_all);
     if (rc) return rc;
-    (void)stop_event_take();
-    return feature_extraction(h, img, nullptr, N, 0, H, W, L, f8, f4, f2, (hipStream_t)stream);
+    hipStream_t st = (hipStream_t)stream;
+    rc = feature_head(h, img, nullptr, N, 0, H, W, L, f8, st);
+    if (rc) return rc;
+    return feature_tail(h, N, H, W, L, f8, f4, f2, st, nullptr, 3);
 }
 
 int lws_refine(lws_handle h, const float *left, const float *pred3, int B, int H, int W, float *pred4, void *stream)
 {
     LWS_CHECK_ARG(h && left && pred3 && pred4, "refine: null pointer");
     LWS_CHECK_ARG(B >= 1 && H > 0 && W > 0, "refine: unsupported size B=%d %dx%d", B, H, W);
-    LWS_CHECK_DEVICE(h, "lws_refine");
-    if (!h->finalized || !h->have_2d) {
-        set_error("refine: the 2D network tensors were not all set before lws_finalize");
-        return LWS_ERR_STATE;
-    }
     const WsLayout L = ws_layout(h, B, H, W);
-    int rc = ensure_ws(h, L.total_all);
+    int rc = begin_call(h, "lws_refine", true, "refine: the 2D network tensors were not all set before lws_finalize",
+                        L.total_all);
     if (rc) return rc;
-    (void)stop_event_take();
     rc = refine_left(h, left, B, H, W, L, (hipStream_t)stream);
     if (rc) return rc;
-    return refine_rest(h, const_cast<float *>(pred3), B, H, W, L, pred4, (hipStream_t)stream);   // not written without a DeferState
+    const StageMap p3{const_cast<float *>(pred3), true};      // (a written map is only read)
+    return refine_rest(h, p3, B, H, W, L, pred4, (hipStream_t)stream);
 }
 
 int lws_forward(lws_handle h, const float *left, const float *right, int B, int H, int W, float *const pred_out[4],
@@ -1340,16 +1258,11 @@ int lws_forward(lws_handle h, const float *left, const float *right, int B, int 
     for (int s = 0; s < 4; ++s) LWS_CHECK_ARG(pred_out[s], "forward: null output for stage %d", s + 1);
     int rc = check_size(h, B, H, W);
     if (rc) return rc;
-    LWS_CHECK_DEVICE(h, "lws_forward");
-    if (!h->finalized || !h->have_2d) {
-        set_error("forward: set_state_dict/lws_finalize must be called with the full state dict first");
-        return LWS_ERR_STATE;
-    }
     const WsLayout L = ws_layout(h, B, H, W);
-    rc = ensure_ws(h, L.total_all);
+    rc = begin_call(h, "lws_forward", true, "forward: set_state_dict/lws_finalize must be called with the full state dict first",
+                    L.total_all);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    (void)stop_event_take();
     // Under hipGraph capture (tools/graph_pipeline.py; lws_reserve first, so that nothing allocates) the forks must be capture-
     // time records -- hipEventRecord on the capturing stream, which is what pulls the side stream into the graph; an event bound
     // to a kernel's completion signal is not one -- and nothing is profiled (timing events cannot be read back from a graph).
@@ -1383,8 +1296,7 @@ int lws_forward(lws_handle h, const float *left, const float *right, int B, int 
     hipStream_t side = multi ? h->side : st;
     const bool ext = multi && !capturing;       // forks ride on their producer kernel's completion signal (StopArm)
     float *f8 = h->ws + L.fe_f8, *f4 = h->ws + L.fe_f4, *f2 = h->ws + L.fe_f2;
-    rc = feature_extraction(h, left, right, B, B, H, W, L, f8, f4, f2, st, /*head_only=*/true,
-                            multi ? h->ev_feat[0] : nullptr, ext);                                    // models.py:110-111
+    rc = feature_head(h, left, right, B, B, H, W, L, f8, st, Fork{multi ? h->ev_feat[0] : nullptr, 0, ext});   // models.py:110-111
     if (rc) return rc;
     const size_t n2 = (size_t)B * 8 * half_up(H) * half_up(W), n4 = n2 / 2, n8 = n2 / 8;   // 8 / 16 / 16 channels
     const float *fl[3] = {f8, f4, f2};
@@ -1392,34 +1304,36 @@ int lws_forward(lws_handle h, const float *left, const float *right, int B, int 
     if (multi) LWS_HIP(hipStreamWaitEvent(side, h->ev_feat[0], 0));
     rc = feature_tail(h, 2 * B, H, W, L, f8, f4, f2, side, multi ? h->ev_feat : nullptr, 1);          // conv5 -> f4
     if (rc) return rc;
-    DeferState ds;
-    ds.allow_last = refine_can_defer(h);
-    ds.allow_first = true;
     // where the second fork sits: option "fork2_after" (k = behind stage 1's k-th middle layer, 0 = behind its last layer,
     // -1 = automatic: the last middle layer, which leaves every k_conv3d_mid16 launch undisturbed)
     const int L3 = h->cfg.layers_3d;
     int fork2 = h->opt.fork2_after;
     if (fork2 < 0) fork2 = L3;
     if (fork2 > L3) fork2 = 0;
-    if (multi) {
-        ds.stage1_stop = h->ev_fork2;
-        ds.stage1_stop_after = fork2;
-        ds.stage1_stop_ext = ext;
+    // stage 3's map may wait for the refinement when its first block computes the 1 -> 32 convolution itself
+    const bool ref_evaluates = (h->opt.fuse_first & 1) && ref_first_dws_can_fuse(h->net2d.r1[1][0], 1);
+    StageMap map[3] = {{pred_out[0]}, {pred_out[1]}, {pred_out[2]}};
+    for (int s = 0; s < 3; ++s) {                                                                   // :115-156
+        if (multi && s > 0) LWS_HIP(hipStreamWaitEvent(st, h->ev_feat[s], 0));    // joins: f4 before stage 2, f2 before stage 3
+        const bool defer = defers(h, s, B, H, W, s < 2 || ref_evaluates);
+        bool fused;
+        rc = stage_volume(h, s, fl[s], fr[s], B, H, W, map, L, st, defer, fused,
+                          Fork{multi && s == 0 ? h->ev_fork2 : nullptr, fork2, ext});
+        if (rc) return rc;
+        if (s == 0) {
+            // fork 2: the side branch starts once the event is complete (bound or recorded by conv3d_stack)
+            if (multi) LWS_HIP(hipStreamWaitEvent(side, h->ev_fork2, 0));
+            rc = feature_tail(h, 2 * B, H, W, L, f8, f4, f2, side, multi ? h->ev_feat : nullptr, 2);  // conv6, classif1 -> f2
+            if (rc) return rc;
+            rc = refine_left(h, left, B, H, W, L, side);                                               // models.py:158
+            if (rc) return rc;
+            if (multi) LWS_HIP(hipEventRecord(h->ev_join, side));
+        }
+        rc = stage_map(h, s, B, H, W, map, L, st, defer, fused);
+        if (rc) return rc;
     }
-    auto launch_tail = [&]() -> int {
-        if (multi) LWS_HIP(hipStreamWaitEvent(side, h->ev_fork2, 0));     // (bound or recorded by conv3d_stack)
-        int r2 = feature_tail(h, 2 * B, H, W, L, f8, f4, f2, side, multi ? h->ev_feat : nullptr, 2);   // conv6, classif1 -> f2
-        if (r2) return r2;
-        r2 = refine_left(h, left, B, H, W, L, side);                                                    // models.py:158
-        if (r2) return r2;
-        if (multi) LWS_HIP(hipEventRecord(h->ev_join, side));
-        return LWS_OK;
-    };
-    hipEvent_t ready[3] = {nullptr, h->ev_feat[1], h->ev_feat[2]};        // joins: f4 before stage 2, f2 before stage 3
-    rc = stages_impl(h, fl, fr, B, H, W, pred_out, L, st, multi ? ready : nullptr, launch_tail, &ds);   // :115-156
-    if (rc) return rc;
     if (multi) LWS_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
-    return refine_rest(h, pred_out[2], B, H, W, L, pred_out[3], st, &ds, pred_out[1]);       // :159-162
+    return refine_rest(h, map[2], B, H, W, L, pred_out[3], st);                                        // :159-162
 }
 
 }  // extern "C"

@@ -42,7 +42,7 @@ void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 // know about stop events stays correct; the guard's destructor disarms on every exit path, so an error return can never leave a
 // stale event armed for the next call on this thread.  Launch sites that honour it use LWS_LAUNCH_STOP instead of
 // hipLaunchKernelGGL.  Thread-local: handles are driven from their own host threads (lws_pool).
-// A kernel-bound event is NOT a capture-time record: under hipGraph capture (use_ext = false) the guard never arms and
+// A kernel-bound event is NOT a capture-time record: under hipGraph capture (Fork::ext = false) the guard never arms and
 // finish() records the event with hipEventRecord, which is what pulls the waiting stream into the capture.
 extern thread_local hipEvent_t tl_stop_event;
 static inline void stop_event_arm(hipEvent_t e) { tl_stop_event = e; }
@@ -52,11 +52,18 @@ static inline hipEvent_t stop_event_take()
     tl_stop_event = nullptr;
     return e;
 }
+// A fork of lws_forward: `ev` must be complete once its producer kernel is -- bound to that kernel's completion signal (ext) or
+// recorded behind it.  Inside a Conv3D stack the producer is the `after`-th middle layer, 0 = the stack's last layer.
+struct Fork {
+    hipEvent_t ev = nullptr;
+    int after = 0;
+    bool ext = false;
+};
 struct StopArm {
     hipEvent_t e;
     hipStream_t st;
     bool ext;
-    StopArm(hipEvent_t e_, hipStream_t st_, bool use_ext) : e(e_), st(st_), ext(use_ext && e_ != nullptr)
+    StopArm(const Fork &f, hipStream_t st_) : e(f.ev), st(st_), ext(f.ext && f.ev != nullptr)
     {
         if (ext) stop_event_arm(e);
     }
@@ -261,15 +268,29 @@ struct lws_ctx {
 
 namespace lws {
 
+// A full-resolution disparity map [B,H,W] of the stage loop (pred_out[s]).  Written: `mem` holds it.  Deferred: no launch has
+// materialised it yet; it is upsample(low [B,h,w]) + *prev (nothing added without a map before it), evaluated on demand by the
+// kernel that reads it (DeferredMap, lws_device_math.h: the operations of k_upsample_add, bit for bit).  That kernel also writes
+// the map to `mem` wherever it evaluates every pixel -- k_volume_l1_warp at exactly 2x (the four taps of a pixel are then the
+// 2 x 2 block it owns), the refinement's fused first block always -- and its launcher marks the map written.
+struct StageMap {
+    float *mem = nullptr;
+    bool written = false;
+    const float *low = nullptr;
+    int h = 0, w = 0;
+    StageMap *prev = nullptr;
+};
+// LWS_OK if a kernel can read `m`: written, or deferred over a written map; `nested` (k_volume_l1_warp's two-level
+// DeferredMap) also allows no map before it, or one more deferred map that has none before it.  Sets the error otherwise.
+int check_stage_map(const StageMap &m, bool nested, const char *who);
+
 // ---- kernel launchers (lws_volume.hip, lws_regress.hip, lws_conv3d.hip) ----
 // q16: round the feature values to fp16 where they are read (lws_config.feature_fp16)
 int launch_volume_l1_shift(const float *L, const float *R, float *cost, int B, int C, int h, int w, int D,
                            hipStream_t st, bool q16 = false);
-int launch_volume_l1_warp(const float *L, const float *R, const float *prev, float *cost, float *wflow_out,
+int launch_volume_l1_warp(const float *L, const float *R, StageMap &prev, float *cost, float *wflow_out,
                           int B, int C, int h, int w, int H, int W, int m, hipStream_t st, bool q16 = false,
-                          const float *plow = nullptr, int ph = 0, int pw = 0, float *pmat = nullptr,     // deferred prev map
                           int form = 1,    // 1 = right-feature window staged in LDS, 0 = every tap gathered from global memory
-                          const float *plow0 = nullptr, int ph0 = 0, int pw0 = 0, float *pmat0 = nullptr,    // prev == nullptr: its own deferred source
                           float ioff = 0.5f);   // src_index's offset: 0.5f = interp_align_mode 0, 0.0f = 1 (every `ioff` below)
 int launch_softargmin(const float *cost, float *low, int B, int D, int h, int w, float start, hipStream_t st);
 int launch_upsample_add(const float *low, const float *prev, float *out, int B, int h, int w, int H, int W,
@@ -299,9 +320,9 @@ int launch_conv2d_pair(const Conv2dLayer &a, const Conv2dLayer &b, const float *
 int launch_ref_first(const float *in, int cin, const float *w, float *out, int B, int H, int W, hipStream_t st);
 int launch_ref_dws(const RefDws &l, const float *in, float *out, int B, int H, int W, hipStream_t st);
 bool ref_first_dws_can_fuse(const RefDws &l, int cin);
-int launch_ref_first_dws(const RefDws &l, const float *img, int cin, const float *wfrag, float *out, int B, int H, int W,
-                         hipStream_t st, const float *plow = nullptr, int ph = 0, int pw = 0, float *pmat = nullptr,
-                         float ioff = 0.5f);
+// in: the image (cin = 3) or the disparity map (cin = 1, may be deferred), as a written StageMap
+int launch_ref_first_dws(const RefDws &l, StageMap &in, int cin, const float *wfrag, float *out, int B, int H, int W,
+                         hipStream_t st, float ioff = 0.5f);
 int packed_first_mfma_floats(int cin);
 void pack_first_mfma(const float *w /*[32][cin][3][3]*/, int cin, float *out);
 int launch_ref_conv64(const RefConv64 &l, const float *inL, const float *inD, float *out, int B, int H, int W,

@@ -1433,28 +1433,33 @@ void pack_first_mfma(const float *w, int cin, float *out)
             }
 }
 
-int launch_ref_first_dws(const RefDws &l, const float *img, int cin, const float *wfrag, float *out, int B, int H, int W,
-                         hipStream_t st, const float *plow, int ph, int pw, float *pmat, float ioff)
+int launch_ref_first_dws(const RefDws &l, StageMap &in, int cin, const float *wfrag, float *out, int B, int H, int W,
+                         hipStream_t st, float ioff)
 {
     if (!ref_first_dws_can_fuse(l, cin)) {
         set_error("ref_first_dws: cin %d / dilation %d unsupported", cin, l.dil);
         return LWS_ERR_INVALID;
     }
-    if (cin != 1 && (plow != nullptr || pmat != nullptr)) {
+    if (cin != 1 && !in.written) {
         set_error("ref_first_dws: only the one-channel (disparity) input can be a deferred map");
         return LWS_ERR_INVALID;
     }
+    const int rc = check_stage_map(in, false, "ref_first_dws");
+    if (rc) return rc;
+    const bool def = !in.written;      // (the kernel writes a deferred map out: its tiles partition the image)
     const int nbx = cdiv(W, RT_X * l.dil), nby = cdiv(H, RT_Y * l.dil);
     dim3 grid(nbx * nby * l.dil * l.dil * B), block(256);
     const int wt = use_wt_stores((size_t)B * H * W * 128);
     const float4 *pw4 = reinterpret_cast<const float4 *>(l.pw);
+    const float *img = def ? in.prev->mem : in.mem;
     if (cin == 3)
         hipLaunchKernelGGL(k_ref_dws<3>, grid, block, 0, st, img, wfrag, l.bn_s, l.bn_t, l.dw, pw4, out, H, W, l.dil, nbx, nby, wt,
                            (const float *)nullptr, 0, 0, (float *)nullptr, ioff);
     else
         hipLaunchKernelGGL(k_ref_dws<1>, grid, block, 0, st, img, wfrag, l.bn_s, l.bn_t, l.dw, pw4, out, H, W, l.dil, nbx, nby, wt,
-                           plow, ph, pw, pmat, ioff);
+                           def ? in.low : nullptr, def ? in.h : 0, def ? in.w : 0, def ? in.mem : nullptr, ioff);
     LWS_LAUNCH_CHECK();
+    in.written = true;
     return LWS_OK;
 }
 

@@ -375,31 +375,44 @@ __global__ __launch_bounds__(WARP_TX *WARP_NW) void k_volume_l1_warp(const float
     LWS_STAMPK(10, 3);
 }
 
-int launch_volume_l1_warp(const float *L, const float *R, const float *prev, float *cost, float *wflow_out,
-                          int B, int C, int h, int w, int H, int W, int m, hipStream_t st, bool q16, const float *plow,
-                          int ph, int pw, float *pmat, int form, const float *plow0, int ph0, int pw0, float *pmat0, float ioff)
+int check_stage_map(const StageMap &m, bool nested, const char *who)
 {
-    if ((pmat != nullptr || pmat0 != nullptr) && (plow == nullptr || H != 2 * h || W != 2 * w)) {
-        set_error("volume_l1_warp: the deferred map can only be written out at exactly half resolution");
+    if (m.mem == nullptr || (!m.written && m.low == nullptr)) {
+        set_error("%s: no map (neither materialised nor deferred)", who);
         return LWS_ERR_INVALID;
     }
-    if (prev == nullptr && plow == nullptr) {
-        set_error("volume_l1_warp: no previous map (neither materialised nor deferred)");
+    const StageMap *p = m.prev;
+    if (!m.written && !(p != nullptr && p->written) &&
+        !(nested && (p == nullptr || (p->low != nullptr && p->prev == nullptr)))) {
+        set_error("%s: a deferred map is read over a materialised one (or, two-level, over at most one deferred map)", who);
         return LWS_ERR_INVALID;
     }
-    if ((plow0 != nullptr && prev != nullptr) || (pmat0 != nullptr && plow0 == nullptr)) {
-        set_error("volume_l1_warp: the second deferred level stands in for a missing `prev`");
-        return LWS_ERR_INVALID;
-    }
+    return LWS_OK;
+}
+
+int launch_volume_l1_warp(const float *L, const float *R, StageMap &prev, float *cost, float *wflow_out,
+                          int B, int C, int h, int w, int H, int W, int m, hipStream_t st, bool q16, int form, float ioff)
+{
+    const int rc = check_stage_map(prev, true, "volume_l1_warp");
+    if (rc) return rc;
+    // prev deferred: the kernel evaluates it (and p0, the map before it, when that is deferred too); at exactly half
+    // resolution it writes both out
+    const bool def = !prev.written, out = def && H == 2 * h && W == 2 * w;
+    StageMap *p0 = def ? prev.prev : nullptr;
+    const bool def0 = p0 != nullptr && !p0->written;
+    const float *pmem = def ? (p0 != nullptr && p0->written ? p0->mem : nullptr) : prev.mem;
+    const float *plow = def ? prev.low : nullptr, *plow0 = def0 ? p0->low : nullptr;
+    const int ph = def ? prev.h : 0, pw = def ? prev.w : 0, ph0 = def0 ? p0->h : 0, pw0 = def0 ? p0->w : 0;
+    float *pmat = out ? prev.mem : nullptr, *pmat0 = out && def0 ? p0->mem : nullptr;
     dim3 grid(cdiv(w, WARP_TX), h, B), block(WARP_TX * WARP_NW);
     const float mul_a = (float)h, mul_b = 1.0f / (float)H;
     const int force_gather = form == 0 ? 1 : 0;
 #define LWS_VW(CC)                                                                                                   \
     if (q16)                                                                                                          \
-        hipLaunchKernelGGL((k_volume_l1_warp<CC, true>), grid, block, 0, st, L, R, prev, cost, wflow_out, h, w, H, W, m,  \
+        hipLaunchKernelGGL((k_volume_l1_warp<CC, true>), grid, block, 0, st, L, R, pmem, cost, wflow_out, h, w, H, W, m,  \
                            mul_a, mul_b, plow, ph, pw, pmat, force_gather, plow0, ph0, pw0, pmat0, ioff);                 \
     else                                                                                                              \
-        hipLaunchKernelGGL((k_volume_l1_warp<CC, false>), grid, block, 0, st, L, R, prev, cost, wflow_out, h, w, H, W, m, \
+        hipLaunchKernelGGL((k_volume_l1_warp<CC, false>), grid, block, 0, st, L, R, pmem, cost, wflow_out, h, w, H, W, m, \
                            mul_a, mul_b, plow, ph, pw, pmat, force_gather, plow0, ph0, pw0, pmat0, ioff)
     switch (C) {
         case 8: LWS_VW(8); break;
@@ -408,6 +421,10 @@ int launch_volume_l1_warp(const float *L, const float *R, const float *prev, flo
     }
 #undef LWS_VW
     LWS_LAUNCH_CHECK();
+    if (out) {
+        prev.written = true;
+        if (def0) p0->written = true;
+    }
     return LWS_OK;
 }
 
