@@ -147,6 +147,20 @@ int lws_preprocess_rgb8(const uint8_t *rgb, float *out, int B, int H, int W, con
  * disp [n] float32 -> rgb [n,3] uint8 = lut[(uint8)(int64)disp]; lut: 256 x 3 bytes in device memory (lwsnet_amd.imageio.jet_lut). */
 int lws_apply_lut8(const float *disp, const uint8_t *lut, uint8_t *rgb, int64_t n, void *stream);
 
+/* ---- evaluation: the metrics of finetune.py:184-219 (test + error_estimating) and train.py:169-199 (test) (additive after v8) ---- */
+/* For each stage map s and image b, over the ground-truth pixels: e = |pred - gt| (float32), valid = the reference's mask, bad =
+ * valid & e > 3 & e / gt > 0.05 (finetune.py:217), abs_sum = the fp64 sum of e over the valid pixels -- one IEEE float32 operation
+ * per step, so valid / bad are exactly numpy's counts; NaN / +inf ground truth is never valid, a NaN prediction never bad.
+ * Deterministic (no float atomics, fixed-order sums) and independent of B and of the other images of the batch.
+ * pred[s] [B,1,Hp,W], gt [B,Hg,W], both float32 contiguous in device memory; Hp = Hg + row_offset, row_offset >= 0 (SceneFlow's
+ * 544-row crop against its 540 ground-truth rows: 4, train.py:189 `output[:, 4:, :]`).  Two launches on `stream`. */
+/* bytes of device workspace lws_stage_metrics needs for this geometry */
+int64_t lws_stage_metrics_workspace(int B, int Hg, int Wg);
+/* mode 0: KITTI 3-px (valid = 0 < gt < maxdisp); mode 1: EPE (valid = gt < maxdisp).  Outputs (device):
+   counts[4][B][2] = {valid, bad}, abs_sum[4][B].  Hp = Hg + row_offset, row_offset >= 0. */
+int lws_stage_metrics(const float *const pred[4], int B, int Hp, int W, int row_offset, const float *gt, int Hg,
+                      float maxdisp, int mode, void *workspace, int64_t *counts, double *abs_sum, void *stream);
+
 /* Launch-plan options of lws_forward / lws_disparity_stages.  They change which kernels / streams carry the work, never
  * the arithmetic: every setting returns the same bits (tests/test_gpu_parity.py::test_forward_schedule_options) -- except
  * the opt-in numerics mode "split_bf16".  (ABI v8 removed the options two rounds of sweeps had retired: left_at, split_heads,

@@ -12,7 +12,8 @@ published metrics were computed on:
   - the SceneFlow "driving" subset lists the 15 mm focal-length folder twice and the 35 mm one never (sceneflow.py:106);
   - SceneFlow evaluation crops a 540-row frame to 544 rows from the bottom, i.e. 4 all-zero rows are added on top
     (PIL pads a crop box that leaves the image) while the ground truth keeps 540 rows -- train.py:189 drops the 4 rows.
-Everything returns plain numpy arrays ([3,H,W] float32 images, [H,W] float32 disparity) that `LWSNet` accepts as is.
+Everything returns plain numpy arrays ([3,H,W] float32 images, [H,W] float32 disparity) that `LWSNet` accepts as is;
+`StereoPairs.raw` returns the same crops as uint8 RGB before the normalisation (lwsnet_amd/evaluate.py's pipelined mode).
 """
 from __future__ import annotations
 
@@ -132,6 +133,15 @@ class StereoPairs:
         return np.ascontiguousarray(data, dtype=np.float32)
 
     def __getitem__(self, index):
+        left, right, d = self.raw(index)
+        lf = left.astype(np.float32) / 255
+        rf = right.astype(np.float32) / 255
+        return _normalise_chw(lf), _normalise_chw(rf), d
+
+    def raw(self, index):
+        """`ds[index]` before the normalisation: (left uint8 [h,w,3], right uint8 [h,w,3], disparity float32) with the same crop
+        and ground-truth rule (SceneFlow's 4 padded rows are PIL's zeros).  `ds[index]` is /255 + Normalize of these, in float32;
+        the evaluation pipeline uploads the bytes and normalises them on the device (ops.preprocess_rgb8, bit for bit the same)."""
         li = Image.open(self.left[index]).convert("RGB")
         ri = Image.open(self.right[index]).convert("RGB")
         d = self._disparity(self.disp[index])
@@ -149,6 +159,4 @@ class StereoPairs:
         else:                                                  # bottom-right 544x960: PIL pads the rows above the image
             th, tw = SCENEFLOW_EVAL_CROP                       # with zeros; the ground truth keeps its 540 rows
             box = (w - tw, h - th, w, h)
-        lf = np.array(li.crop(box), dtype=np.float32) / 255
-        rf = np.array(ri.crop(box), dtype=np.float32) / 255
-        return _normalise_chw(lf), _normalise_chw(rf), d
+        return np.asarray(li.crop(box), dtype=np.uint8), np.asarray(ri.crop(box), dtype=np.uint8), d

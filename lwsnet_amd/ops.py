@@ -217,3 +217,44 @@ def apply_lut8(disp, lut_dev, out=None):
         _lib.check(_lib.load().lws_apply_lut8(_ptr(d), _ptr(lut_dev.contiguous()), _ptr(out), ctypes.c_int64(d.numel()), _stream()),
                    "lws_apply_lut8")
     return out
+
+
+METRIC_MODES = {"kitti": 0, "epe": 1}
+
+
+def stage_metrics(preds, gt, row_offset, maxdisp, mode):
+    """The per-image sums behind the reference's test loops (finetune.py:184-219 error_estimating, mode 0 / "kitti";
+    train.py:169-199, mode 1 / "epe") on the device.  preds: the four [B,1,Hp,W] float32 stage maps; gt: [B,Hg,W] float32 with
+    Hp = Hg + row_offset.  Returns device tensors counts [4,B,2] int64 = {valid, bad} and abs_sum [4,B] float64 (include/lwsnet_hip.h,
+    lws_stage_metrics), allocated on the current stream."""
+    mode = METRIC_MODES.get(mode, mode)
+    if mode not in (0, 1):
+        raise ValueError(f"mode must be 0 / 'kitti' or 1 / 'epe', got {mode!r}")
+    if not isinstance(preds, (list, tuple)) or len(preds) != 4:
+        raise ValueError("preds must be the four stage maps")
+    g = _dev(gt, "gt")
+    if g.dim() != 3:
+        raise ValueError(f"gt must be [B,Hg,W]; got {tuple(g.shape)}")
+    B, Hg, W = g.shape
+    row_offset = int(row_offset)
+    if row_offset < 0:
+        raise ValueError(f"row_offset must be >= 0, got {row_offset}")
+    ps = []
+    for s, p in enumerate(preds):
+        p = _dev(p, f"preds[{s}]")
+        if tuple(p.shape) != (B, 1, Hg + row_offset, W) or p.device != g.device:
+            raise ValueError(f"preds[{s}] must be {(B, 1, Hg + row_offset, W)} on {g.device}; got {tuple(p.shape)} on {p.device}")
+        ps.append(p)
+    lib = _lib.load()
+    nbytes = int(lib.lws_stage_metrics_workspace(B, Hg, W))
+    if nbytes < 0:
+        _lib.check(nbytes, "lws_stage_metrics_workspace")
+    work = torch.empty((nbytes,), device=g.device, dtype=torch.uint8)
+    counts = torch.empty((4, B, 2), device=g.device, dtype=torch.int64)
+    abs_sum = torch.empty((4, B), device=g.device, dtype=torch.float64)
+    arr = ctypes.c_void_p * 4
+    with torch.cuda.device(g.device):
+        _lib.check(lib.lws_stage_metrics(arr(*[p.data_ptr() for p in ps]), B, Hg + row_offset, W, row_offset, _ptr(g), Hg,
+                                         float(maxdisp), int(mode), _ptr(work), _ptr(counts), _ptr(abs_sum), _stream()),
+                   "lws_stage_metrics")
+    return counts, abs_sum

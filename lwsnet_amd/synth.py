@@ -94,3 +94,64 @@ def make_batch(B, H, W, first_index=0):
         ls.append(l)
         rs.append(r)
     return np.ascontiguousarray(np.stack(ls)), np.ascontiguousarray(np.stack(rs))
+
+
+def to_rgb8(img):
+    """Inverse of the normalisation: [3,H,W] normalised float32 -> [H,W,3] uint8 RGB (rounded, clipped)."""
+    x = img.astype(np.float64) * IMAGENET_STD[:, None, None] + IMAGENET_MEAN[:, None, None]
+    return np.ascontiguousarray(np.clip(np.rint(x * 255.0), 0, 255).astype(np.uint8).transpose(1, 2, 0))
+
+
+def write_kitti_tree(root, n, H=375, W=1242):
+    """A miniature KITTI 2015 training tree (image_2/, image_3/, disp_occ_0/ with n `*_10.png` frames; ground truth as 16-bit
+    PNG x 256, 0 = no measurement in the top rows) and its split file root/val_set.txt listing all n frames.  Returns the split path."""
+    import os
+
+    from PIL import Image
+    for d in ("image_2", "image_3", "disp_occ_0"):
+        os.makedirs(os.path.join(root, d), exist_ok=True)
+    for i in range(n):
+        left, right, gt = make_pair(H, W, i)
+        name = f"{i:06d}_10.png"
+        Image.fromarray(to_rgb8(left)).save(os.path.join(root, "image_2", name))
+        Image.fromarray(to_rgb8(right)).save(os.path.join(root, "image_3", name))
+        g16 = np.rint(gt.astype(np.float64) * 256).astype(np.uint16)
+        g16[: H // 3] = 0                                    # KITTI's sparse ground truth: no value in the sky
+        Image.fromarray(g16).save(os.path.join(root, "disp_occ_0", name))
+    split = os.path.join(root, "val_set.txt")
+    with open(split, "w") as f:
+        f.write("".join(f"{i}\n" for i in range(n)))
+    return split
+
+
+def write_sceneflow_tree(root, n, H=540, W=960):
+    """A miniature SceneFlow tree in the layout lwsnet_amd.datasets.sceneflow_lists reads: n flyingthings3d TEST frames of H x W
+    (clean pass PNGs, ground truth PFM), empty monkaa / TRAIN / driving folders."""
+    import os
+
+    from PIL import Image
+
+    def mk(*p):
+        os.makedirs(os.path.join(root, *p), exist_ok=True)
+        return os.path.join(root, *p)
+
+    mk("monkaa_frames_cleanpass")
+    mk("monkaa_disparity")
+    for part in ("A", "B", "C"):
+        mk("frames_cleanpass", "TRAIN", part)
+        mk("frames_cleanpass", "TEST", part)
+        mk("frames_disparity", "TEST", part)
+    for direction in ("scene_backwards", "scene_forwards"):
+        for speed in ("fast", "slow"):
+            mk("driving_frames_cleanpass", "15mm_focallength", direction, speed, "left")
+            mk("driving_disparity", "15mm_focallength", direction, speed, "left")
+    for i in range(n):
+        left, right, gt = make_pair(H, W, 100 + i)
+        seq = f"{i:04d}"
+        Image.fromarray(to_rgb8(left)).save(os.path.join(mk("frames_cleanpass", "TEST", "A", seq, "left"), "0006.png"))
+        Image.fromarray(to_rgb8(right)).save(os.path.join(mk("frames_cleanpass", "TEST", "A", seq, "right"), "0006.png"))
+        gt = gt.copy()
+        gt[:, : W // 8] += 200.0                             # a band outside gt < maxdisp
+        with open(os.path.join(mk("frames_disparity", "TEST", "A", seq, "left"), "0006.pfm"), "wb") as f:
+            f.write(b"Pf\n" + f"{W} {H}\n".encode() + b"-1.0\n")
+            f.write(np.flipud(gt).astype("<f4").tobytes())
