@@ -161,6 +161,29 @@ int64_t lws_stage_metrics_workspace(int B, int Hg, int Wg);
 int lws_stage_metrics(const float *const pred[4], int B, int Hp, int W, int row_offset, const float *gt, int Hg,
                       float maxdisp, int mode, void *workspace, int64_t *counts, double *abs_sum, void *stream);
 
+/* ---- left-right consistency check of the stage maps (additive after v8) ---- */
+/* The right view's disparity is the same left-reference network run on the mirrored, swapped pair (mirror_w(R), mirror_w(L)),
+ * mirror_w(t)[..., x] = t[..., W-1-x]: lws_lr_pairs builds the input of ONE forward of 2B pairs, whose first B stage maps are the
+ * left-view maps dL and whose last B are the mirrored right-view maps dRm (positive disparities).  Both functions are one launch on
+ * `stream`, deterministic (no atomics) and independent of B and of the other images of the batch; argument errors return
+ * LWS_ERR_INVALID before any GPU call. */
+/* left, right [B,3,H,W] float32 -> left2 = [left; mirror_w(right)], right2 = [right; mirror_w(left)], each [2B,3,H,W]: bit copies. */
+int lws_lr_pairs(const float *left, const float *right, float *left2, float *right2, int B, int H, int W, void *stream);
+/* For s < nmaps (1..4), dL[s], dRm[s] [B,1,H,W] float32, W <= 8192 (the row is staged in LDS), tau finite and >= 0.  Per pixel x of
+ * row y, d = dL[x], one IEEE float32 operation per step:
+ *   t = (float)(W-1-x) + d                                        (mirrored column of the matching right pixel x - d)
+ *   NaN d: code 0;  !(0 <= t <= W-1) (+-inf included): code 2 (out of the right camera's view);  otherwise
+ *   i0 = (int)floorf(t), i1 = min(i0+1, W-1), a = t - i0, r = R[i0] + a * (R[i1] - R[i0]) (R = the dRm row), code = |d - r| <= tau
+ *   (1 = consistent, 0 = not; a NaN r gives 0).
+ * Outputs: mask[s] uint8 [B,1,H,W] = code;  out[s] float32 [B,1,H,W]: fill 0 -> d where code == 1, else 0.0f;  fill 1 -> code-1
+ * pixels keep d, every other pixel gets min(d at the nearest code-1 pixel to its left, d at the nearest to its right) in its row
+ * (the left value on a tie), one side's value when only that side has one, 0.0f when the row has none (background fill; O(W) per
+ * row: a max-scan of the last and a min-scan of the next consistent index);  right[s] (right or right[s] NULL: skipped) float32
+ * [B,1,H,W] = the un-mirrored right-view map dRm[W-1-x];  row_kept (NULL: skipped) int32 [nmaps][B][H] = the code-1 pixels of each
+ * row.  No scratch memory. */
+int lws_lr_check(const float *const dL[4], const float *const dRm[4], int nmaps, int B, int H, int W, float tau, int fill,
+                 float *const out[4], uint8_t *const mask[4], float *const right[4], int32_t *row_kept, void *stream);
+
 /* Launch-plan options of lws_forward / lws_disparity_stages.  They change which kernels / streams carry the work, never
  * the arithmetic: every setting returns the same bits (tests/test_gpu_parity.py::test_forward_schedule_options) -- except
  * the opt-in numerics mode "split_bf16".  (ABI v8 removed the options two rounds of sweeps had retired: left_at, split_heads,

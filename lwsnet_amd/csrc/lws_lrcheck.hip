@@ -1,0 +1,286 @@
+// Left-right consistency check of the stage maps: the right view's disparity comes from the same left-reference network run on
+// the mirrored, swapped pair (mirror(R), mirror(L)) in one forward of 2B pairs (k_lr_pairs builds its input), and k_lr_check
+// compares the two per pixel, marks the pixels to trust and optionally fills the others with background values.
+// Arithmetic contract (include/lwsnet_hip.h, lws_lr_check): one IEEE float32 operation per step (the build has no contraction),
+// so tests/lr_reference.py restates every output bit for bit in numpy.  Determinism: no atomics; a workgroup owns one row of one
+// image and map, so an image gives the same bits in any batch.  0 bytes of scratch; the row lives in LDS.
+#include "lws_common.h"
+
+namespace lws {
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr int kMaxW = 8192;                                 // dRm / dL row + two int per quad: 48 KiB of LDS at most
+constexpr int kNone = 0x7fffffff;                           // "no consistent pixel to the right"
+
+struct LrMaps {                                             // the nmaps stage maps of one call, by value in the kernel arguments
+    const float *dl[4];
+    const float *drm[4];
+    float *out[4];
+    uint8_t *mask[4];
+    float *right[4];
+};
+
+__device__ __forceinline__ bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// 1 = consistent, 0 = inconsistent (or NaN), 2 = the matching right pixel x - d is outside the right camera's view (incl. +-inf)
+__device__ __forceinline__ int lr_code(float d, int x, int W, const float *__restrict__ R, float tau)
+{
+    if (__builtin_isnan(d)) return 0;
+    const float t = (float)(W - 1 - x) + d;                 // mirrored column of x - d
+    if (!(t >= 0.0f && t <= (float)(W - 1))) return 2;
+    const int i0 = (int)floorf(t);
+    const int i1 = min(i0 + 1, W - 1);
+    const float a = t - (float)i0;
+    const float r = R[i0] + a * (R[i1] - R[i0]);
+    return fabsf(d - r) <= tau ? 1 : 0;                     // NaN r -> 0
+}
+
+// Stage `n` floats of a row into LDS: float4 where the row is 16-byte aligned, scalar for a misaligned row and the tail.
+__device__ __forceinline__ void stage_row(float *__restrict__ dst, const float *__restrict__ src, int W, int nq)
+{
+    const bool vec = aligned16(src);
+    for (int q = threadIdx.x; q < nq; q += kThreads) {
+        const int x = 4 * q;
+        if (vec && x + 4 <= W) {
+            *reinterpret_cast<float4 *>(dst + x) = *reinterpret_cast<const float4 *>(src + x);
+        } else {
+            for (int i = 0; i < 4 && x + i < W; ++i) dst[x + i] = src[x + i];
+        }
+    }
+}
+
+__device__ __forceinline__ void store_quad(float *__restrict__ p, int x, int W, bool vec, float v0, float v1, float v2, float v3)
+{
+    if (vec && x + 4 <= W) {
+        *reinterpret_cast<float4 *>(p + x) = make_float4(v0, v1, v2, v3);
+    } else {
+        const float v[4] = {v0, v1, v2, v3};
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (x + i < W) p[x + i] = v[i];
+    }
+}
+
+// grid (H, B, nmaps), 256 threads: one workgroup per row.  Thread t owns the quads t, t + 256, ... (pixels 4q .. 4q + 3) of the
+// row; W <= 8192 gives at most 8 quads, so the code == 1 flags of its pixels fit in one 32-bit word (bit 4k + i).
+// LDS (dynamic): row[4 nq] floats (first dRm, then dL for the fill), last[nq], first[nq] ints (fill only).
+__global__ __launch_bounds__(kThreads) void k_lr_check(LrMaps m, int H, int W, float tau, int fill, int *__restrict__ row_kept)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    __shared__ int s_wl[kWaves], s_wf[kWaves], s_kept[kWaves];
+    const int y = blockIdx.x, b = blockIdx.y, s = blockIdx.z, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int nq = (W + 3) >> 2;
+    float *s_row = lds;
+    int *s_last = reinterpret_cast<int *>(lds + 4 * nq), *s_first = s_last + nq;
+    const int64_t row = ((int64_t)b * H + y) * W;
+    const float *dl = m.dl[s] + row, *rm = m.drm[s] + row;
+    float *out = m.out[s] + row, *rt = m.right[s] ? m.right[s] + row : nullptr;
+    uint8_t *mk = m.mask[s] + row;
+    const bool vdl = aligned16(dl), vout = aligned16(out), vrt = aligned16(rt), vmk = ((uintptr_t)mk & 3) == 0;
+
+    stage_row(s_row, rm, W, nq);                            // the mirrored right-view row
+    __syncthreads();
+
+    // ---- phase 1: codes, mask, right, out (no fill), kept count, per-quad last / first consistent pixel ----
+    unsigned bits = 0;
+    int kept = 0;
+    const float nan = __builtin_nanf("");
+    for (int k = 0, q = t; q < nq; ++k, q += kThreads) {
+        const int x = 4 * q;
+        float d[4];
+        if (vdl && x + 4 <= W) {
+            const float4 v = *reinterpret_cast<const float4 *>(dl + x);
+            d[0] = v.x, d[1] = v.y, d[2] = v.z, d[3] = v.w;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) d[i] = x + i < W ? dl[x + i] : nan;      // beyond the row: code 0, never kept
+        }
+        int c[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) c[i] = lr_code(d[i], x + i, W, s_row, tau);
+        if (vmk && x + 4 <= W) {
+            *reinterpret_cast<uchar4 *>(mk + x) = make_uchar4((uint8_t)c[0], (uint8_t)c[1], (uint8_t)c[2], (uint8_t)c[3]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (x + i < W) mk[x + i] = (uint8_t)c[i];
+        }
+        if (rt) {                                           // right[x] = dRm[W-1-x]
+            const int xr = W - 1 - x;
+            store_quad(rt, x, W, vrt, s_row[xr], s_row[max(xr - 1, 0)], s_row[max(xr - 2, 0)], s_row[max(xr - 3, 0)]);
+        }
+        if (!fill) store_quad(out, x, W, vout, c[0] == 1 ? d[0] : 0.0f, c[1] == 1 ? d[1] : 0.0f, c[2] == 1 ? d[2] : 0.0f,
+                              c[3] == 1 ? d[3] : 0.0f);
+        int last = -1, first = kNone;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const bool ok = c[i] == 1;
+            kept += ok ? 1 : 0;
+            bits |= (ok ? 1u : 0u) << (4 * k + i);
+            last = ok ? x + i : last;
+        }
+#pragma unroll
+        for (int i = 3; i >= 0; --i) first = c[i] == 1 ? x + i : first;
+        if (fill) {
+            s_last[q] = last;
+            s_first[q] = first;
+        }
+    }
+
+    if (row_kept) {
+        for (int o = 32; o > 0; o >>= 1) kept += __shfl_down(kept, o, 64);
+        if (lane == 0) s_kept[wave] = kept;
+    }
+    if (fill) {
+        __syncthreads();                                    // every read of the staged dRm row is done
+        stage_row(s_row, dl, W, nq);                        // the left-view row, for the fill values
+
+        // ---- phase 2: inclusive max-scan of last (left to right), inclusive min-scan of first (right to left) over the quads:
+        // each thread a contiguous chunk of quads, the chunks' aggregates across the wave by shuffles, across waves through LDS
+        const int per = (nq + kThreads - 1) / kThreads;
+        const int q0 = min(t * per, nq), q1 = min(q0 + per, nq);
+        int agg_l = -1, agg_f = kNone;
+        for (int j = q0; j < q1; ++j) {
+            agg_l = max(agg_l, s_last[j]);
+            agg_f = min(agg_f, s_first[j]);
+        }
+        int inc_l = agg_l, inc_f = agg_f;
+        for (int o = 1; o < 64; o <<= 1) {
+            const int vl = __shfl_up(inc_l, o, 64), vf = __shfl_down(inc_f, o, 64);
+            inc_l = lane >= o ? max(inc_l, vl) : inc_l;
+            inc_f = lane + o < 64 ? min(inc_f, vf) : inc_f;
+        }
+        if (lane == 63) s_wl[wave] = inc_l;
+        if (lane == 0) s_wf[wave] = inc_f;
+        int exc_l = __shfl_up(inc_l, 1, 64), exc_f = __shfl_down(inc_f, 1, 64);
+        exc_l = lane == 0 ? -1 : exc_l;
+        exc_f = lane == 63 ? kNone : exc_f;
+        __syncthreads();
+        for (int w = 0; w < kWaves; ++w) {
+            exc_l = w < wave ? max(exc_l, s_wl[w]) : exc_l;
+            exc_f = w > wave ? min(exc_f, s_wf[w]) : exc_f;
+        }
+        for (int j = q0; j < q1; ++j) {
+            exc_l = max(exc_l, s_last[j]);
+            s_last[j] = exc_l;
+        }
+        for (int j = q1 - 1; j >= q0; --j) {
+            exc_f = min(exc_f, s_first[j]);
+            s_first[j] = exc_f;
+        }
+        __syncthreads();
+
+        // ---- phase 3: consistent pixels keep d, the others min(d at the nearest consistent pixel on the left, on the right); one
+        // side only: that side's value; neither: 0.  Ties keep the left value.
+        for (int k = 0, q = t; q < nq; ++k, q += kThreads) {
+            const int x = 4 * q;
+            const unsigned cb = bits >> (4 * k);
+            int prev = q > 0 ? s_last[q - 1] : -1;
+            int nxt[4];
+            int n = q + 1 < nq ? s_first[q + 1] : kNone;
+#pragma unroll
+            for (int i = 3; i >= 0; --i) {
+                n = (cb >> i) & 1 ? x + i : n;
+                nxt[i] = n;
+            }
+            float v[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if ((cb >> i) & 1) {
+                    prev = x + i;
+                    v[i] = s_row[x + i];
+                } else {
+                    const float vl = prev >= 0 ? s_row[prev] : 0.0f;
+                    const float vr = nxt[i] != kNone ? s_row[nxt[i]] : 0.0f;
+                    v[i] = prev >= 0 ? (nxt[i] != kNone ? (vr < vl ? vr : vl) : vl) : (nxt[i] != kNone ? vr : 0.0f);
+                }
+            }
+            store_quad(out, x, W, vout, v[0], v[1], v[2], v[3]);
+        }
+    }
+    if (row_kept) {
+        __syncthreads();
+        if (t == 0) row_kept[((int64_t)s * gridDim.y + b) * H + y] = (s_kept[0] + s_kept[1]) + (s_kept[2] + s_kept[3]);
+    }
+}
+
+// One thread per quad of a row of the [B,3,H,W] inputs (rows = B * 3 * H): left2 = [left; mirror_w(right)],
+// right2 = [right; mirror_w(left)].  vec (launch-uniform): W % 4 == 0 and every base 16-byte aligned, so every quad and its mirror
+// image are aligned float4s.
+__global__ __launch_bounds__(kThreads) void k_lr_pairs(const float *__restrict__ L, const float *__restrict__ R, float *__restrict__ L2,
+                                                      float *__restrict__ R2, int rows, int W, int nq, int vec)
+{
+    const int g = blockIdx.x * kThreads + threadIdx.x;
+    if (g >= rows * nq) return;
+    const int row = g / nq, x = 4 * (g - row * nq);
+    const int64_t top = (int64_t)row * W, bot = ((int64_t)rows + row) * W;
+    const float *l = L + top, *r = R + top;
+    float *lt = L2 + top, *rt = R2 + top, *lb = L2 + bot, *rb = R2 + bot;
+    if (vec) {
+        const float4 a = *reinterpret_cast<const float4 *>(l + x), c = *reinterpret_cast<const float4 *>(r + x);
+        *reinterpret_cast<float4 *>(lt + x) = a;
+        *reinterpret_cast<float4 *>(rt + x) = c;
+        *reinterpret_cast<float4 *>(lb + W - 4 - x) = make_float4(c.w, c.z, c.y, c.x);
+        *reinterpret_cast<float4 *>(rb + W - 4 - x) = make_float4(a.w, a.z, a.y, a.x);
+    } else {
+        for (int i = 0; i < 4 && x + i < W; ++i) {
+            const float a = l[x + i], c = r[x + i];
+            lt[x + i] = a;
+            rt[x + i] = c;
+            lb[W - 1 - x - i] = c;
+            rb[W - 1 - x - i] = a;
+        }
+    }
+}
+
+}  // namespace
+
+}  // namespace lws
+
+using namespace lws;
+
+extern "C" {
+
+int lws_lr_pairs(const float *left, const float *right, float *left2, float *right2, int B, int H, int W, void *stream)
+{
+    LWS_CHECK_ARG(left && right && left2 && right2, "lr_pairs: null pointer");
+    LWS_CHECK_ARG(B >= 1 && H >= 1 && W >= 1, "lr_pairs: bad shape B=%d H=%d W=%d", B, H, W);
+    const int64_t rows = (int64_t)B * 3 * H, nq = ((int64_t)W + 3) / 4;
+    LWS_CHECK_ARG(rows * nq <= (int64_t)INT32_MAX - kThreads, "lr_pairs: %dx3x%dx%d is too large", B, H, W);
+    const int vec = (W % 4 == 0) && ((((uintptr_t)left | (uintptr_t)right | (uintptr_t)left2 | (uintptr_t)right2) & 15) == 0);
+    const int64_t n = rows * nq;
+    hipLaunchKernelGGL(k_lr_pairs, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream, left, right,
+                       left2, right2, (int)rows, W, (int)nq, vec);
+    LWS_LAUNCH_CHECK();
+    return LWS_OK;
+}
+
+int lws_lr_check(const float *const dL[4], const float *const dRm[4], int nmaps, int B, int H, int W, float tau, int fill,
+                 float *const out[4], uint8_t *const mask[4], float *const right[4], int32_t *row_kept, void *stream)
+{
+    LWS_CHECK_ARG(dL && dRm && out && mask, "lr_check: null pointer");
+    LWS_CHECK_ARG(nmaps >= 1 && nmaps <= 4, "lr_check: nmaps %d outside 1..4", nmaps);
+    LWS_CHECK_ARG(B >= 1 && B <= 65535 && H >= 1 && W >= 1, "lr_check: bad shape B=%d H=%d W=%d", B, H, W);
+    LWS_CHECK_ARG(W <= kMaxW, "lr_check: W=%d exceeds %d (the row is staged in LDS)", W, kMaxW);
+    LWS_CHECK_ARG(tau >= 0.0f && tau <= 3.4028234663852886e38f, "lr_check: tau must be finite and >= 0, got %g", (double)tau);
+    LWS_CHECK_ARG(fill == 0 || fill == 1, "lr_check: fill %d (0 = zero, 1 = background fill)", fill);
+    LrMaps m = {};
+    for (int s = 0; s < nmaps; ++s) {
+        LWS_CHECK_ARG(dL[s] && dRm[s] && out[s] && mask[s], "lr_check: map %d has a null pointer", s);
+        m.dl[s] = dL[s];
+        m.drm[s] = dRm[s];
+        m.out[s] = out[s];
+        m.mask[s] = mask[s];
+        m.right[s] = right ? right[s] : nullptr;
+    }
+    const int nq = (W + 3) / 4;
+    const size_t lds = (size_t)4 * nq * sizeof(float) + (fill ? (size_t)2 * nq * sizeof(int) : 0);
+    hipLaunchKernelGGL(k_lr_check, dim3(H, B, nmaps), dim3(kThreads), lds, (hipStream_t)stream, m, H, W, tau, fill, row_kept);
+    LWS_LAUNCH_CHECK();
+    return LWS_OK;
+}
+
+}  // extern "C"

@@ -19,6 +19,9 @@ float32 as numpy computes it, counts exact, sums in fp64, deterministic; only 4 
 `--workers N` (not in the reference): N spawned host processes (numpy + PIL, never the GPU) decode and crop `StereoPairs.raw(i)`
 into shared-memory slots; a copy stream uploads the bytes and normalises them on the device (lws_preprocess_rgb8, bit for bit
 StereoPairs[i]); every batch is one lws_pool job of B pairs; the metric kernel runs behind it.  Same numbers as `--workers 0`.
+
+`--lr_check TAU [--lr_fill]` (not in the reference; sequential mode only): the lines score LWSNet.forward_lr's checked maps, and one
+more line gives the per-stage mean density of consistent pixels.
 """
 import argparse
 import json
@@ -28,6 +31,8 @@ import sys
 import time
 
 import numpy as np
+
+from .inference import add_lr_arguments, check_lr_arguments
 
 STAGES = 4
 KITTI_MAXDISP = 192                     # error_estimating's default (finetune.py:212), which test() never overrides
@@ -122,15 +127,19 @@ def _row_offset(H, Hg):
     return H - Hg
 
 
-def _sequential(model, dataset, mode, batches, maxdisp):
+def _sequential(model, dataset, mode, batches, maxdisp, lr=None):
     """StereoPairs[i] -> model(left, right) on the batch -> lws_stage_metrics, one batch after the other.  A generator like
-    _pipelined: "start" after a warm-up forward, then (counts, abs_sum) per batch."""
+    _pipelined: "start" after a warm-up forward, then (counts, abs_sum) per batch.  lr = (tau, fill): the metric scores the
+    checked maps of LWSNet.forward_lr instead, and each item gains the batch's density [4,b]."""
     import torch
     from . import ops
     dev = model.device
     H, W = dataset[batches[0][0]][0].shape[1:]
     x = np.zeros((len(batches[0]), 3, H, W), np.float32)
-    model(x, x)                                         # warm-up outside the clock: workspace for the largest batch
+    if lr is None:
+        model(x, x)                                     # warm-up outside the clock: workspace for the largest batch
+    else:
+        model.forward_lr(x, x, *lr)
     torch.cuda.synchronize(dev)
     yield "start"
     for rng in batches:
@@ -138,10 +147,17 @@ def _sequential(model, dataset, mode, batches, maxdisp):
         left = np.stack([it[0] for it in items])
         right = np.stack([it[1] for it in items])
         gt = torch.from_numpy(np.ascontiguousarray(np.stack([it[2] for it in items]), dtype=np.float32)).to(dev)
-        preds = model(left, right)
+        if lr is None:
+            preds, density = model(left, right), None
+        else:
+            res = model.forward_lr(left, right, *lr)
+            preds, density = res.disp, res.density
         with torch.cuda.device(dev):
             counts, sums = ops.stage_metrics(preds, gt, _row_offset(left.shape[2], gt.shape[1]), maxdisp, mode)
-            yield counts.cpu().numpy(), sums.cpu().numpy()
+            if density is None:
+                yield counts.cpu().numpy(), sums.cpu().numpy()
+            else:
+                yield counts.cpu().numpy(), sums.cpu().numpy(), density
 
 
 def _gt_offset(n_img):
@@ -332,12 +348,17 @@ def _pipelined(model, dataset, mode, batches, maxdisp, workers, gpu_workers):
             sl.close()
 
 
-def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, workers=0, gpu_workers=2, log=None):
+def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, workers=0, gpu_workers=2, log=None, lr_check=None,
+             lr_fill=False):
     """Runs the reference's test loop for `metric` ("kitti": finetune.py's 3-pixel error, "epe": train.py's EPE) over
     `dataset` (a StereoPairs with training=False).  maxdisp is the mask bound (the KITTI loop uses 192, see KITTI_MAXDISP).
-    Returns a dict: per-stage averages at full precision, per-batch values, per-image counts and sums, pairs, wall time, pairs/s."""
+    Returns a dict: per-stage averages at full precision, per-batch values, per-image counts and sums, pairs, wall time, pairs/s.
+    lr_check = TAU (sequential mode only): the metric scores the maps of LWSNet.forward_lr(tau=TAU, fill=lr_fill), and the dict
+    gains lr_tau and lr_density, the per-stage mean over the pairs of the fraction of consistent pixels."""
     if metric not in ("kitti", "epe"):
         raise ValueError(f"metric must be 'kitti' or 'epe', got {metric!r}")
+    if lr_check is not None and workers > 0:
+        raise ValueError("the left-right check runs in the sequential mode only (workers = 0)")
     if batch_size < 1:
         raise ValueError("batch_size must be >= 1")
     n = len(dataset)
@@ -348,14 +369,19 @@ def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, worker
     files = [[os.path.basename(dataset.left[i]) for i in r] for r in batches]
     meters = Meters(metric, len(batches))
     per_image = {"valid": [], "bad": [], "abs_sum": []}
+    lr = None if lr_check is None else (float(lr_check), bool(lr_fill))
+    densities = []
     if workers > 0:
         it = _pipelined(model, dataset, metric, batches, maxdisp, workers, gpu_workers)
     else:
-        it = _sequential(model, dataset, metric, batches, maxdisp)
+        it = _sequential(model, dataset, metric, batches, maxdisp, lr)
     if next(it) != "start":
         raise RuntimeError("the evaluation did not start")
     t0 = time.perf_counter()
-    for k, (counts, sums) in enumerate(it):
+    for k, item in enumerate(it):
+        counts, sums = item[0], item[1]
+        if lr is not None:
+            densities.append(item[2])
         line = meters.update(k, counts, sums, files[k])
         if line is not None:
             log.info(line)
@@ -364,11 +390,18 @@ def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, worker
         per_image["abs_sum"] += sums.T.tolist()
     wall = time.perf_counter() - t0
     log.info(meters.final_line())
-    return {"metric": metric, "maxdisp": maxdisp, "batch_size": batch_size, "pairs": n, "batches": len(batches),
-            "average": meters.averages(), "per_batch": meters.values,
-            "per_image": dict(files=[os.path.basename(p) for p in dataset.left], **per_image),
-            "wall_s": wall, "pairs_per_s": n / wall if wall > 0 else float("inf"),
-            "workers": int(workers), "gpu_workers": int(gpu_workers) if workers > 0 else 0}
+    res = {"metric": metric, "maxdisp": maxdisp, "batch_size": batch_size, "pairs": n, "batches": len(batches),
+           "average": meters.averages(), "per_batch": meters.values,
+           "per_image": dict(files=[os.path.basename(p) for p in dataset.left], **per_image),
+           "wall_s": wall, "pairs_per_s": n / wall if wall > 0 else float("inf"),
+           "workers": int(workers), "gpu_workers": int(gpu_workers) if workers > 0 else 0}
+    if lr is not None:
+        density = np.concatenate(densities, axis=1).mean(axis=1)           # [4]: mean over the pairs
+        log.info("LR check (tau = {:g}{}): mean density ".format(lr[0], ", filled" if lr[1] else "")
+                 + ", ".join("Stage {}={:.4f}".format(x, d) for x, d in enumerate(density)))
+        res["lr_tau"] = lr[0]
+        res["lr_density"] = [float(d) for d in density]
+    return res
 
 
 DEFAULT_DATAPATH = {"kitti2015": "dataset/kitti2015/training/", "sceneflow": "dataset/sceneflow/"}   # finetune.py:22, train.py:23
@@ -393,6 +426,7 @@ def build_parser():
                    help="host worker processes decoding into a pipelined GPU path (0 = the reference's sequential loop; not in the reference)")
     p.add_argument("--gpu_workers", type=int, default=2, help="with --workers: batches kept in flight by lws_pool")
     p.add_argument("--json", type=str, default=None, help="write the result (full-precision numbers) to this file")
+    add_lr_arguments(p)
     return p
 
 
@@ -410,7 +444,9 @@ def load_dataset(args):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    check_lr_arguments(parser, args)
     logging.basicConfig(stream=sys.stderr, level=logging.INFO,
                         format="[%(asctime)s %(filename)s:%(lineno)s] %(levelname)s: %(message)s")
     log = logging.getLogger("lwsnet_amd.evaluate")
@@ -434,7 +470,7 @@ def main(argv=None):
         log.info("Successful load model")
     model.eval()
     res = evaluate(model, dataset, metric, batch_size=args.test_batch_size, maxdisp=maxdisp, workers=args.workers,
-                   gpu_workers=args.gpu_workers, log=log)
+                   gpu_workers=args.gpu_workers, log=log, lr_check=args.lr_check, lr_fill=args.lr_fill)
     res["dataset"] = args.dataset
     log.info("%d pairs in %.3f s: %.2f pairs/s", res["pairs"], res["wall_s"], res["pairs_per_s"])
     if args.json:

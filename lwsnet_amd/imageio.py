@@ -70,26 +70,49 @@ def encode_png(rgb):
     PNG: what is compared is the decoded pixels (tests/test_gpu_parity.py::test_config1_*, tests/test_host_cpu.py).  PIL's own
     encoder at the same level spends twice the time choosing row filters (23 vs 12 ms for a 368x1232 map of noise-like disparities),
     which is most of what a host worker of the pipelined CLI does per pair."""
-    import struct
-    import zlib
     rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
     if rgb.ndim != 3 or rgb.shape[2] != 3:
         raise ValueError(f"encode_png wants [H,W,3] uint8, got {rgb.shape}")
     h, w, _ = rgb.shape
-    raw = np.empty((h, 1 + 3 * w), np.uint8)
+    return _encode_rows(rgb.reshape(h, 3 * w), w, 2)
+
+
+def encode_png_gray(img):
+    """[H,W] uint8 -> PNG bytes: 8-bit greyscale, encoded as encode_png encodes RGB."""
+    img = np.ascontiguousarray(img, dtype=np.uint8)
+    if img.ndim != 2:
+        raise ValueError(f"encode_png_gray wants [H,W] uint8, got {img.shape}")
+    return _encode_rows(img, img.shape[1], 0)
+
+
+def _encode_rows(rows, w, color_type):
+    """rows [H, channels * w] uint8 -> PNG bytes of 8-bit colour type `color_type` (2 RGB, 0 grey)."""
+    import struct
+    import zlib
+    h = rows.shape[0]
+    raw = np.empty((h, 1 + rows.shape[1]), np.uint8)
     raw[:, 0] = 0                                   # filter type None
-    raw[:, 1:] = rgb.reshape(h, 3 * w)
+    raw[:, 1:] = rows
 
     def chunk(tag, data):
         return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
 
-    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0))
+    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, color_type, 0, 0, 0))
             + chunk(b"IDAT", zlib.compress(raw.tobytes(), 1)) + chunk(b"IEND", b""))
 
 
 def save_png(path, rgb):
     with open(path, "wb") as f:
         f.write(encode_png(rgb))
+
+
+LR_MASK_GREY = np.array([0, 255, 128], np.uint8)   # lws_lr_check code 0 (inconsistent), 1 (consistent), 2 (out of view)
+
+
+def save_lr_mask_png(path, code):
+    """[H,W] uint8 left-right check codes -> 8-bit grey PNG: 1 -> 255, 0 -> 0, 2 -> 128."""
+    with open(path, "wb") as f:
+        f.write(encode_png_gray(LR_MASK_GREY[np.asarray(code, np.uint8)]))
 
 
 def read_pfm(path):

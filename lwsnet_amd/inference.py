@@ -17,6 +17,9 @@ second stream casts and colour-maps the stage-4 map on the device (lws_apply_lut
 slot, and the same workers PNG-encode them.  The files written are byte-identical to the sequential loop's
 (tests/test_gpu_parity.py::test_cli_directory_pipeline_writes_identical_files); the end-to-end rate and where the time goes
 are logged and returned (profiles/r06/e2e_cli.txt).
+
+`--lr_check TAU [--lr_fill]` (not in the reference; sequential mode only): the colour files come from LWSNet.forward_lr's checked maps
+and each gets a grey mask `<stem>_lr.png` beside it (consistent 255, inconsistent 0, out of the right view 128).
 """
 import argparse
 import glob
@@ -51,7 +54,28 @@ def build_parser():
                    help="directory mode: host worker processes for decode and encode around a pipelined GPU path (0 = the "
                         "reference's sequential loop; not in the reference)")
     p.add_argument("--gpu_workers", type=int, default=3, help="with --workers: forwards kept in flight by lws_pool")
+    add_lr_arguments(p)
     return p
+
+
+def add_lr_arguments(p):
+    """--lr_check TAU / --lr_fill (not in the reference; shared with lwsnet_amd.evaluate): LWSNet.forward_lr."""
+    p.add_argument("--lr_check", type=float, default=None, metavar="TAU",
+                   help="left-right consistency check: keep the pixels whose left- and right-view disparities differ by <= TAU "
+                        "(sequential mode only; not in the reference)")
+    p.add_argument("--lr_fill", action="store_true", help="with --lr_check: fill the dropped pixels with their row's background value")
+
+
+def check_lr_arguments(p, args):
+    """Rejects what the left-right check does not support, before any model or GPU work."""
+    if args.lr_check is None:
+        if args.lr_fill:
+            p.error("--lr_fill needs --lr_check TAU")
+        return
+    if not np.isfinite(args.lr_check) or args.lr_check < 0:
+        p.error(f"--lr_check TAU must be finite and >= 0, got {args.lr_check}")
+    if args.workers > 0:
+        p.error("--lr_check runs in the sequential mode only: use --workers 0")
 
 
 def _host_worker(task_q, done_q, slot_names, H, W):
@@ -303,6 +327,14 @@ def inference(model, left_imgs, right_imgs, args, log):
     from . import imageio as io
     written = []
     warm = False
+    lr = getattr(args, "lr_check", None) is not None
+
+    def run(l_in, r_in):
+        if not lr:
+            return model(l_in, r_in), None
+        res = model.forward_lr(l_in, r_in, tau=args.lr_check, fill=args.lr_fill)     # colour files from the checked maps
+        return res.disp, res.mask
+
     for li, ri in zip(left_imgs, right_imgs):
         left = io.crop_bottom_right(io.load_rgb(li))
         right = io.crop_bottom_right(io.load_rgb(ri))
@@ -310,11 +342,11 @@ def inference(model, left_imgs, right_imgs, args, log):
             continue
         l_in, r_in = io.to_input(left)[None], io.to_input(right)[None]
         if not warm:                                                    # one warm-up in all (the reference times its first call)
-            model(l_in, r_in)
+            run(l_in, r_in)
             warm = True
         torch.cuda.synchronize(model.device)
         t0 = time.time()
-        outputs = model(l_in, r_in)
+        outputs, masks = run(l_in, r_in)
         torch.cuda.synchronize(model.device)
         cost = time.time() - t0
         ss = "Inference 4 stages cost = {:.3f} sec, FPS = {:.1f}".format(cost, 1 / cost)
@@ -327,16 +359,32 @@ def inference(model, left_imgs, right_imgs, args, log):
                 io.save_png(path, color)
                 written.append(path)
                 log.info("{}\t\tSave img = {}".format(ss, path))
+                if lr:
+                    written.append(_save_lr_mask(path, masks[stage], log))
         if not args.left_img:                                           # :133-137 (stage-4 map only)
             path = os.path.join(args.save_path, os.path.basename(li))
             io.save_png(path, color)
             written.append(path)
             log.info("{}\t\tSave img = {}".format(ss, path))
+            if lr:
+                written.append(_save_lr_mask(path, masks[3], log))
     return written
 
 
+def _save_lr_mask(path, mask, log):
+    """The left-right check codes of the map written to `path`, as the grey PNG <stem>_lr.png next to it."""
+    from . import imageio as io
+    code = mask[0, 0].cpu().numpy()
+    mpath = os.path.splitext(path)[0] + "_lr.png"
+    io.save_lr_mask_png(mpath, code)
+    log.info("LR check: density = {:.4f}\t\tSave mask = {}".format(float((code == 1).mean()), mpath))
+    return mpath
+
+
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    check_lr_arguments(parser, args)
     logging.basicConfig(stream=sys.stderr, level=logging.INFO,
                         format="[%(asctime)s %(filename)s:%(lineno)s] %(levelname)s: %(message)s")
     log = logging.getLogger("lwsnet_amd.inference")

@@ -10,6 +10,7 @@ device buffers.  There is no CPU path.
 from __future__ import annotations
 
 import ctypes
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -17,6 +18,11 @@ import torch
 from . import _lib, ops
 from .synth import check_size
 from .weights import state_dict_spec
+
+LRResult = namedtuple("LRResult", ["left", "right", "disp", "mask", "density"])
+LRResult.__doc__ = """What LWSNet.forward_lr returns: the four left-view stage maps (the bits of model(left, right)), the four
+un-mirrored right-view maps, the four checked maps (background-filled if asked), the four uint8 code maps (1 consistent,
+0 inconsistent, 2 out of the right camera's view) and density, a numpy [4,B] array of consistent pixels / (H*W)."""
 
 
 class DisparityTensor(torch.Tensor):
@@ -215,6 +221,30 @@ class LWSNet:
             return [DisparityTensor.wrap(p) for p in ops.forward(self._h, left, right, out)]      # models.py:106-164
 
     __call__ = forward
+
+    def forward_lr(self, left_input, right_input, tau=1.0, fill=False):
+        """Stage maps with a left-right consistency check (not in the reference).  The right view's disparity is this same
+        left-reference network on the mirrored, swapped pair, so the call is one lws_lr_pairs, ONE lws_forward of 2B pairs and
+        one lws_lr_check of the four stages (include/lwsnet_hip.h).  A pixel is kept when |d - right-view d at x - d| <= tau;
+        `fill` gives the others the background value of their row.  Returns an LRResult."""
+        if self.device is None:
+            raise RuntimeError("no HIP device is available and lwsnet_amd has no CPU fallback")
+        if self._params is None:
+            raise RuntimeError("set_state_dict() must be called before forward_lr()")
+        left = self._input(left_input, "left_input")
+        right = self._input(right_input, "right_input")
+        if left.shape != right.shape:
+            raise ValueError(f"left/right shapes differ: {tuple(left.shape)} vs {tuple(right.shape)}")
+        B, _, H, W = left.shape
+        check_size(H, W, self.maxdisplist[0])
+        with torch.cuda.device(self.device):
+            left2, right2 = ops.lr_pairs(left, right)
+            maps = ops.forward(self._h, left2, right2)
+            dl, drm = [p[:B] for p in maps], [p[B:] for p in maps]
+            out, mask, rmaps, row_kept = ops.lr_check(dl, drm, tau, fill, want_right=True)
+            density = row_kept.sum(dim=2, dtype=torch.int64).cpu().numpy() / float(H * W)
+        wrap = DisparityTensor.wrap
+        return LRResult([wrap(p) for p in dl], [wrap(p) for p in rmaps], [wrap(p) for p in out], mask, density)
 
 
 class _PoolJob:

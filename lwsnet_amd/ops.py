@@ -258,3 +258,49 @@ def stage_metrics(preds, gt, row_offset, maxdisp, mode):
                                          float(maxdisp), int(mode), _ptr(work), _ptr(counts), _ptr(abs_sum), _stream()),
                    "lws_stage_metrics")
     return counts, abs_sum
+
+
+def lr_pairs(left, right):
+    """The input of the left-right check's one forward of 2B pairs (include/lwsnet_hip.h, lws_lr_pairs): left, right [B,3,H,W]
+    float32 -> left2 = [left; mirror_w(right)], right2 = [right; mirror_w(left)], each [2B,3,H,W], bit copies."""
+    l, r = _dev(left, "left"), _dev(right, "right")
+    if l.dim() != 4 or l.shape[1] != 3 or l.shape != r.shape or l.device != r.device:
+        raise ValueError(f"left/right must both be [B,3,H,W] on one device; got {tuple(l.shape)} and {tuple(r.shape)}")
+    B, _, H, W = l.shape
+    left2 = torch.empty((2 * B, 3, H, W), device=l.device, dtype=torch.float32)
+    right2 = torch.empty_like(left2)
+    with torch.cuda.device(l.device):
+        _lib.check(_lib.load().lws_lr_pairs(_ptr(l), _ptr(r), _ptr(left2), _ptr(right2), B, H, W, _stream()), "lws_lr_pairs")
+    return left2, right2
+
+
+def lr_check(dl, drm, tau, fill, want_right=True):
+    """Left-right consistency check of 1-4 stage maps (include/lwsnet_hip.h, lws_lr_check): dl[s] the left-view maps, drm[s] the
+    mirrored right-view maps, each [B,1,H,W] float32.  Returns (out, mask, right, row_kept): lists of [B,1,H,W] float32 checked
+    (filled if `fill`) maps, uint8 codes (1 consistent, 0 inconsistent, 2 out of view) and un-mirrored right-view maps (None
+    unless want_right), and an int32 [nmaps,B,H] device tensor of the consistent pixels per row."""
+    if not isinstance(dl, (list, tuple)) or not isinstance(drm, (list, tuple)) or len(dl) != len(drm) or not 1 <= len(dl) <= 4:
+        raise ValueError("dl and drm must be lists of the same 1-4 stage maps")
+    ls = [_dev(t, f"dl[{s}]") for s, t in enumerate(dl)]
+    rs = [_dev(t, f"drm[{s}]") for s, t in enumerate(drm)]
+    shape, dev = tuple(ls[0].shape), ls[0].device
+    if len(shape) != 4 or shape[1] != 1:
+        raise ValueError(f"dl[0] must be [B,1,H,W]; got {shape}")
+    for name, ts in (("dl", ls), ("drm", rs)):
+        for s, t in enumerate(ts):
+            if tuple(t.shape) != shape or t.device != dev:
+                raise ValueError(f"{name}[{s}] must be {shape} on {dev}; got {tuple(t.shape)} on {t.device}")
+    B, _, H, W = shape
+    n = len(ls)
+    out = [torch.empty(shape, device=dev, dtype=torch.float32) for _ in range(n)]
+    mask = [torch.empty(shape, device=dev, dtype=torch.uint8) for _ in range(n)]
+    right = [torch.empty(shape, device=dev, dtype=torch.float32) for _ in range(n)] if want_right else None
+    row_kept = torch.empty((n, B, H), device=dev, dtype=torch.int32)
+
+    def arr(ts):
+        return (ctypes.c_void_p * 4)(*[t.data_ptr() for t in ts])
+
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().lws_lr_check(arr(ls), arr(rs), n, B, H, W, float(tau), int(bool(fill)), arr(out), arr(mask),
+                                            arr(right if right is not None else []), _ptr(row_kept), _stream()), "lws_lr_check")
+    return out, mask, right, row_kept
