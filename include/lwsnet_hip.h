@@ -184,6 +184,31 @@ int lws_lr_pairs(const float *left, const float *right, float *left2, float *rig
 int lws_lr_check(const float *const dL[4], const float *const dRm[4], int nmaps, int B, int H, int W, float tau, int fill,
                  float *const out[4], uint8_t *const mask[4], float *const right[4], int32_t *row_kept, void *stream);
 
+/* ---- geometry of a disparity map: depth, KITTI 16-bit PNG values, point cloud (additive after v8) ---- */
+/* disp [B,1,H,W] float32; mask (NULL: every pixel) uint8 [B,1,H,W], the lws_lr_check code map; cam float32 [B][5] =
+ * {fx, fy, cx, cy, fb} in device memory, one row per image, cx / cy in the map's (cropped) coordinates, fb = fx * baseline
+ * (fx, fy, fb > 0).  min_disp finite and > 0, max_depth > 0 (+inf allowed); H*W < 2^31, B <= 65535.  Per pixel (b, y, x),
+ * d = disp[b,0,y,x], one IEEE float32 operation per step in this order:
+ *   ok_mask = mask == NULL || mask[b,0,y,x] == 1;   z = fb / d
+ *   valid   = ok_mask && isfinite(d) && d >= min_disp && z <= max_depth
+ *   X = (((float)x - cx) * z) / fx;   Y = (((float)y - cy) * z) / fy;   Z = z
+ *   u16(v)  = (uint16)fminf(fmaxf(rintf(v * 256.0f), 0.0f), 65535.0f)     (rintf: half to even)
+ * Deterministic (no atomics) and independent of B and of the other images of the batch; argument errors return
+ * LWS_ERR_INVALID before any GPU call.  No scratch memory. */
+/* One launch.  Each output may be NULL (skipped; not all three).  depth float32 [B,1,H,W] = valid ? z : 0.0f;  depth16 uint16 =
+ * valid ? u16(z) : 0 (KITTI depth PNG: metres = value / 256, 0 = none);  disp16 uint16 = (ok_mask && isfinite(d) && d > 0) ?
+ * u16(d) : 0 (KITTI disparity PNG; ignores min_disp, max_depth and cam).  cam may be NULL when only disp16 is requested. */
+int lws_depth_maps(const float *disp, const uint8_t *mask, const float *cam, int B, int H, int W, float min_disp, float max_depth,
+                   float *depth, uint16_t *depth16, uint16_t *disp16, void *stream);
+/* bytes of device workspace lws_point_cloud needs for this geometry */
+int64_t lws_point_cloud_workspace(int B, int H);
+/* The valid pixels of image b, packed in raster order from points + b*H*W records of 16 bytes {float X, Y, Z; uint8 r, g, b,
+ * a = 255} (points 16-byte aligned, room for B*H*W records); colour from rgb uint8 [B,H,W,3] (the cropped left image; NULL:
+ * white).  counts int64 [B] = the valid pixels per image; records past counts[b] are left unwritten.  Three launches on
+ * `stream`: per-row counts, a per-image exclusive scan of them (in the workspace), a per-row scatter ranked by wave ballots. */
+int lws_point_cloud(const float *disp, const uint8_t *mask, const uint8_t *rgb, const float *cam, int B, int H, int W, float min_disp,
+                    float max_depth, void *workspace, void *points, int64_t *counts, void *stream);
+
 /* Launch-plan options of lws_forward / lws_disparity_stages.  They change which kernels / streams carry the work, never
  * the arithmetic: every setting returns the same bits (tests/test_gpu_parity.py::test_forward_schedule_options) -- except
  * the opt-in numerics mode "split_bf16".  (ABI v8 removed the options two rounds of sweeps had retired: left_at, split_heads,

@@ -85,8 +85,23 @@ def encode_png_gray(img):
     return _encode_rows(img, img.shape[1], 0)
 
 
-def _encode_rows(rows, w, color_type):
-    """rows [H, channels * w] uint8 -> PNG bytes of 8-bit colour type `color_type` (2 RGB, 0 grey)."""
+def encode_png_gray16(img):
+    """[H,W] uint16 -> PNG bytes: 16-bit greyscale (big-endian samples, as PNG stores them), encoded as encode_png encodes RGB.
+    KITTI's disparity and depth maps are this format (value / 256, 0 = no value)."""
+    img = np.asarray(img)
+    if img.ndim != 2 or img.dtype != np.uint16:
+        raise ValueError(f"encode_png_gray16 wants [H,W] uint16, got {img.shape} {img.dtype}")
+    h, w = img.shape
+    return _encode_rows(np.ascontiguousarray(img, dtype=">u2").view(np.uint8).reshape(h, 2 * w), w, 0, 16)
+
+
+def save_png_gray16(path, img):
+    with open(path, "wb") as f:
+        f.write(encode_png_gray16(img))
+
+
+def _encode_rows(rows, w, color_type, bit_depth=8):
+    """rows [H, bytes per row] uint8 -> PNG bytes of colour type `color_type` (2 RGB, 0 grey) and `bit_depth` bits per sample."""
     import struct
     import zlib
     h = rows.shape[0]
@@ -97,7 +112,7 @@ def _encode_rows(rows, w, color_type):
     def chunk(tag, data):
         return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
 
-    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, color_type, 0, 0, 0))
+    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, bit_depth, color_type, 0, 0, 0))
             + chunk(b"IDAT", zlib.compress(raw.tobytes(), 1)) + chunk(b"IEND", b""))
 
 

@@ -20,6 +20,12 @@ are logged and returned (profiles/r06/e2e_cli.txt).
 
 `--lr_check TAU [--lr_fill]` (not in the reference; sequential mode only): the colour files come from LWSNet.forward_lr's checked maps
 and each gets a grey mask `<stem>_lr.png` beside it (consistent 255, inconsistent 0, out of the right view 128).
+
+`--save_disp16`, `--save_depth`, `--save_ply` (not in the reference; sequential mode only) write KITTI's 16-bit disparity PNG
+`<stem>_disp16.png`, the 16-bit depth PNG `<stem>_depth16.png` and a binary PLY point cloud `<stem>.ply` beside each colour file
+(lws_depth_maps / lws_point_cloud).  Depth and points need a camera: `--calib` (a KITTI calibration file, or in directory mode a
+folder of them named after the frames) or `--camera FX FY CX CY BASELINE` in the uncropped image's pixels; it is cropped as the
+images are.  With `--lr_check` they use the checked maps: without `--lr_fill` only consistent pixels are kept.
 """
 import argparse
 import glob
@@ -55,7 +61,69 @@ def build_parser():
                         "reference's sequential loop; not in the reference)")
     p.add_argument("--gpu_workers", type=int, default=3, help="with --workers: forwards kept in flight by lws_pool")
     add_lr_arguments(p)
+    add_geometry_arguments(p)
     return p
+
+
+def add_geometry_arguments(p):
+    """--calib / --camera, --min_disp / --max_depth and --save_disp16 / --save_depth / --save_ply (not in the reference)."""
+    cam = p.add_mutually_exclusive_group()
+    cam.add_argument("--calib", type=str, default=None, metavar="PATH",
+                     help="KITTI calibration file (P_rect_02/03 or P2/P3); in directory mode also a folder of <frame>.txt files")
+    cam.add_argument("--camera", type=float, nargs=5, default=None, metavar=("FX", "FY", "CX", "CY", "BASELINE"),
+                     help="camera in the uncropped image's pixels, baseline in metres")
+    p.add_argument("--min_disp", type=float, default=1.0, help="depth and points: smallest disparity kept (pixels)")
+    p.add_argument("--max_depth", type=float, default=float("inf"), help="depth and points: largest depth kept (metres)")
+    p.add_argument("--save_disp16", action="store_true", help="write <stem>_disp16.png, KITTI's 16-bit disparity PNG (d * 256)")
+    p.add_argument("--save_depth", action="store_true", help="write <stem>_depth16.png, a 16-bit depth PNG (metres * 256); needs a camera")
+    p.add_argument("--save_ply", action="store_true", help="write <stem>.ply, a binary point cloud of the kept pixels; needs a camera")
+
+
+def _list_pairs(args):
+    """The (left, right) image paths of directory mode (inference.py:50-60)."""
+    if os.path.isdir(args.img_path):
+        return (sorted(glob.glob(os.path.join(args.img_path, "image_2/*.png"))),
+                sorted(glob.glob(os.path.join(args.img_path, "image_3/*.png"))))
+    base, name = os.path.dirname(os.path.dirname(args.img_path)), os.path.basename(args.img_path)
+    return [os.path.join(base, "image_2", name)], [os.path.join(base, "image_3", name)]
+
+
+def _calib_path(args, left_path):
+    """The calibration file of a frame: --calib itself, or for a folder the KITTI naming 000123_10.png -> 000123.txt."""
+    if not os.path.isdir(args.calib):
+        return args.calib
+    return os.path.join(args.calib, os.path.splitext(os.path.basename(left_path))[0].split("_")[0] + ".txt")
+
+
+def check_geometry_arguments(p, args):
+    """Rejects what the geometry outputs do not support, before any model or GPU work; reads every calibration file."""
+    from .geometry import Camera
+    outputs = args.save_disp16 or args.save_depth or args.save_ply
+    if not (np.isfinite(args.min_disp) and args.min_disp > 0):
+        p.error(f"--min_disp must be finite and > 0, got {args.min_disp}")
+    if not args.max_depth > 0:
+        p.error(f"--max_depth must be > 0, got {args.max_depth}")
+    if (args.save_depth or args.save_ply) and args.calib is None and args.camera is None:
+        p.error("--save_depth and --save_ply need a camera: --calib PATH or --camera FX FY CX CY BASELINE")
+    if outputs and args.workers > 0:
+        p.error("--save_disp16 / --save_depth / --save_ply run in the sequential mode only: use --workers 0")
+    if args.camera is not None:
+        try:
+            Camera(*args.camera).check()
+        except ValueError as e:
+            p.error(f"--camera: {e}")
+    if args.calib is not None:
+        if os.path.isdir(args.calib):
+            if args.left_img:
+                p.error("--calib: a folder of calibration files needs directory mode (--img_path); give a file with --left_img")
+            paths = [_calib_path(args, li) for li in _list_pairs(args)[0]]
+        else:
+            paths = [args.calib]
+        for path in paths:
+            try:
+                Camera.from_kitti(path)
+            except (OSError, ValueError) as e:
+                p.error(f"--calib: cannot read {path}: {e}")
 
 
 def add_lr_arguments(p):
@@ -328,6 +396,7 @@ def inference(model, left_imgs, right_imgs, args, log):
     written = []
     warm = False
     lr = getattr(args, "lr_check", None) is not None
+    geo = getattr(args, "save_disp16", False) or getattr(args, "save_depth", False) or getattr(args, "save_ply", False)
 
     def run(l_in, r_in):
         if not lr:
@@ -336,10 +405,12 @@ def inference(model, left_imgs, right_imgs, args, log):
         return res.disp, res.mask
 
     for li, ri in zip(left_imgs, right_imgs):
-        left = io.crop_bottom_right(io.load_rgb(li))
+        full = io.load_rgb(li)
+        left = io.crop_bottom_right(full)
         right = io.crop_bottom_right(io.load_rgb(ri))
         if left is None or right is None:                               # :96-97
             continue
+        cam = _frame_camera(args, li, *full.shape[:2]) if geo else None
         l_in, r_in = io.to_input(left)[None], io.to_input(right)[None]
         if not warm:                                                    # one warm-up in all (the reference times its first call)
             run(l_in, r_in)
@@ -361,6 +432,8 @@ def inference(model, left_imgs, right_imgs, args, log):
                 log.info("{}\t\tSave img = {}".format(ss, path))
                 if lr:
                     written.append(_save_lr_mask(path, masks[stage], log))
+                if geo:
+                    written += _save_geometry(path, outputs[stage], masks[stage] if lr and not args.lr_fill else None, cam, left, args, log)
         if not args.left_img:                                           # :133-137 (stage-4 map only)
             path = os.path.join(args.save_path, os.path.basename(li))
             io.save_png(path, color)
@@ -368,6 +441,49 @@ def inference(model, left_imgs, right_imgs, args, log):
             log.info("{}\t\tSave img = {}".format(ss, path))
             if lr:
                 written.append(_save_lr_mask(path, masks[3], log))
+            if geo:
+                written += _save_geometry(path, outputs[3], masks[3] if lr and not args.lr_fill else None, cam, left, args, log)
+    return written
+
+
+def _frame_camera(args, left_path, h, w):
+    """The camera of a frame's cropped maps (None without --calib / --camera)."""
+    from . import imageio as io
+    from .geometry import Camera
+    if args.calib is not None:
+        cam = Camera.from_kitti(_calib_path(args, left_path))
+    elif args.camera is not None:
+        cam = Camera(*args.camera)
+    else:
+        return None
+    return cam.crop_bottom_right(h, w, io.CROP_H, io.CROP_W)
+
+
+def _save_geometry(path, disp, mask, cam, left_rgb, args, log):
+    """The geometry files of the map written to `path`, beside it: <stem>_disp16.png, <stem>_depth16.png, <stem>.ply.  mask: the
+    left-right check's codes (only code-1 pixels kept) or None."""
+    import torch
+
+    from . import imageio as io
+    from . import ops
+    from .geometry import write_ply
+    stem = os.path.splitext(path)[0]
+    written = []
+    if args.save_disp16 or args.save_depth:
+        _, depth16, disp16 = ops.depth_maps(disp, cam, mask, args.min_disp, args.max_depth, depth=False, depth16=args.save_depth,
+                                            disp16=args.save_disp16)
+        for t, suffix in ((disp16, "_disp16.png"), (depth16, "_depth16.png")):
+            if t is not None:
+                io.save_png_gray16(stem + suffix, t[0, 0].cpu().numpy())
+                written.append(stem + suffix)
+                log.info("Save {} = {}".format(suffix[1:-4], stem + suffix))
+    if args.save_ply:
+        rgb = torch.from_numpy(np.ascontiguousarray(left_rgb)[None]).to(disp.device)
+        points, counts = ops.point_cloud(disp, cam, mask, rgb, args.min_disp, args.max_depth)
+        n = int(counts[0])
+        write_ply(stem + ".ply", points[0, :n].cpu().numpy(), n)
+        written.append(stem + ".ply")
+        log.info("Save point cloud ({} points) = {}".format(n, stem + ".ply"))
     return written
 
 
@@ -385,6 +501,7 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     check_lr_arguments(parser, args)
+    check_geometry_arguments(parser, args)
     logging.basicConfig(stream=sys.stderr, level=logging.INFO,
                         format="[%(asctime)s %(filename)s:%(lineno)s] %(levelname)s: %(message)s")
     log = logging.getLogger("lwsnet_amd.inference")
@@ -410,12 +527,7 @@ def main(argv=None):
         model.set_option("split_bf16", 7)
         log.info("split-bf16 numerics mode")
     if not args.left_img:                                               # :50-63
-        if os.path.isdir(args.img_path):
-            lefts = sorted(glob.glob(os.path.join(args.img_path, "image_2/*.png")))
-            rights = sorted(glob.glob(os.path.join(args.img_path, "image_3/*.png")))
-        else:
-            base, name = os.path.dirname(os.path.dirname(args.img_path)), os.path.basename(args.img_path)
-            lefts, rights = [os.path.join(base, "image_2", name)], [os.path.join(base, "image_3", name)]
+        lefts, rights = _list_pairs(args)
         if os.path.exists(args.save_path):
             shutil.rmtree(args.save_path)
         os.makedirs(args.save_path)

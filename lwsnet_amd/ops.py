@@ -304,3 +304,71 @@ def lr_check(dl, drm, tau, fill, want_right=True):
         _lib.check(_lib.load().lws_lr_check(arr(ls), arr(rs), n, B, H, W, float(tau), int(bool(fill)), arr(out), arr(mask),
                                             arr(right if right is not None else []), _ptr(row_kept), _stream()), "lws_lr_check")
     return out, mask, right, row_kept
+
+
+def _geometry_inputs(disp, mask, cameras, min_disp, max_depth):
+    """Shared checks of depth_maps / point_cloud: disp [B,1,H,W] float32, mask None or uint8 of that shape, cameras (None, one
+    Camera or a list of B) -> (disp, mask, cam [B,5] float32 device tensor or None)."""
+    import math
+
+    from .geometry import camera_rows
+    d = _dev(disp, "disp")
+    if d.dim() != 4 or d.shape[1] != 1:
+        raise ValueError(f"disp must be [B,1,H,W]; got {tuple(d.shape)}")
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or tuple(mask.shape) != tuple(d.shape) or mask.device != d.device:
+            raise ValueError(f"mask must be a uint8 {tuple(d.shape)} tensor on {d.device} (the lws_lr_check code map)")
+        mask = mask.contiguous()
+    if not (math.isfinite(min_disp) and min_disp > 0):
+        raise ValueError(f"min_disp must be finite and > 0, got {min_disp}")
+    if not max_depth > 0:
+        raise ValueError(f"max_depth must be > 0 (inf allowed), got {max_depth}")
+    cam = None
+    if cameras is not None:
+        cam = torch.from_numpy(camera_rows(cameras, d.shape[0])).to(d.device)
+    return d, mask, cam
+
+
+def depth_maps(disp, cameras=None, mask=None, min_disp=1.0, max_depth=float("inf"), depth=True, depth16=True, disp16=True):
+    """Metric depth and KITTI's 16-bit disparity / depth PNG values of disparity maps (include/lwsnet_hip.h, lws_depth_maps).
+    disp [B,1,H,W] float32; cameras: one lwsnet_amd.geometry.Camera or a list of B (needed for depth / depth16); mask: None or the
+    uint8 lws_lr_check code map (only code-1 pixels count).  Returns (depth float32, depth16 uint16, disp16 uint16), each
+    [B,1,H,W] or None where not asked for."""
+    if not (depth or depth16 or disp16):
+        raise ValueError("depth_maps: ask for at least one of depth, depth16, disp16")
+    if (depth or depth16) and cameras is None:
+        raise ValueError("depth_maps: depth and depth16 need cameras")
+    d, mask, cam = _geometry_inputs(disp, mask, cameras if (depth or depth16) else None, min_disp, max_depth)
+    outs = [torch.empty(d.shape, device=d.device, dtype=dt) if want else None
+            for want, dt in ((depth, torch.float32), (depth16, torch.uint16), (disp16, torch.uint16))]
+    B, _, H, W = d.shape
+    with torch.cuda.device(d.device):
+        _lib.check(_lib.load().lws_depth_maps(_ptr(d), _ptr(mask), _ptr(cam), B, H, W, float(min_disp), float(max_depth), *map(_ptr, outs),
+                                              _stream()), "lws_depth_maps")
+    return tuple(outs)
+
+
+def point_cloud(disp, cameras, mask=None, rgb=None, min_disp=1.0, max_depth=float("inf")):
+    """The valid pixels of disparity maps as coloured 3-D points (include/lwsnet_hip.h, lws_point_cloud).  disp [B,1,H,W] float32;
+    cameras: one Camera or a list of B; mask: None or the uint8 lws_lr_check code map; rgb: None (white) or the uint8 [B,H,W,3]
+    cropped left images.  Returns (points uint8 [B,H*W,16], counts int64 [B]): image b's counts[b] records
+    {float X, Y, Z; uint8 r, g, b, 255} (lwsnet_amd.geometry.POINT_DTYPE) in raster order from points[b]; the rest is unwritten."""
+    if cameras is None:
+        raise ValueError("point_cloud needs cameras")
+    d, mask, cam = _geometry_inputs(disp, mask, cameras, min_disp, max_depth)
+    B, _, H, W = d.shape
+    if rgb is not None:
+        if not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8 or tuple(rgb.shape) != (B, H, W, 3) or rgb.device != d.device:
+            raise ValueError(f"rgb must be a uint8 {(B, H, W, 3)} tensor on {d.device}")
+        rgb = rgb.contiguous()
+    lib = _lib.load()
+    nbytes = int(lib.lws_point_cloud_workspace(B, H))
+    if nbytes < 0:
+        _lib.check(nbytes, "lws_point_cloud_workspace")
+    work = torch.empty((nbytes,), device=d.device, dtype=torch.uint8)
+    points = torch.empty((B, H * W, 16), device=d.device, dtype=torch.uint8)
+    counts = torch.empty((B,), device=d.device, dtype=torch.int64)
+    with torch.cuda.device(d.device):
+        _lib.check(lib.lws_point_cloud(_ptr(d), _ptr(mask), _ptr(rgb), _ptr(cam), B, H, W, float(min_disp), float(max_depth), _ptr(work),
+                                       _ptr(points), _ptr(counts), _stream()), "lws_point_cloud")
+    return points, counts
