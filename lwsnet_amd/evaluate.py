@@ -18,21 +18,24 @@ float32 as numpy computes it, counts exact, sums in fp64, deterministic; only 4 
 
 `--workers N` (not in the reference): N spawned host processes (numpy + PIL, never the GPU) decode and crop `StereoPairs.raw(i)`
 into shared-memory slots; a copy stream uploads the bytes and normalises them on the device (lws_preprocess_rgb8, bit for bit
-StereoPairs[i]); every batch is one lws_pool job of B pairs; the metric kernel runs behind it.  Same numbers as `--workers 0`.
+StereoPairs[i]); every batch is one lws_pool job of B pairs; the metric kernel runs behind it (lwsnet_amd/pipeline.py, as for
+`lwsnet_amd.inference --workers N`).  Same numbers as `--workers 0`.
 
 `--lr_check TAU [--lr_fill]` (not in the reference; sequential mode only): the lines score LWSNet.forward_lr's checked maps, and one
 more line gives the per-stage mean density of consistent pixels.
 """
 import argparse
+import contextlib
+import functools
 import json
 import logging
 import os
-import sys
 import time
 
 import numpy as np
 
-from .inference import add_lr_arguments, check_lr_arguments
+from . import pipeline
+from .inference import add_lr_arguments, add_model_arguments, check_lr_arguments, load_model, start_logging
 
 STAGES = 4
 KITTI_MAXDISP = 192                     # error_estimating's default (finetune.py:212), which test() never overrides
@@ -160,103 +163,52 @@ def _sequential(model, dataset, mode, batches, maxdisp, lr=None):
                 yield counts.cpu().numpy(), sums.cpu().numpy(), density
 
 
-def _gt_offset(n_img):
-    return (2 * n_img + 255) // 256 * 256
+def _decode_pair(dataset, shape, views, j, index):
+    """Host worker handler of the pipelined mode (lwsnet_amd/pipeline.py: a spawned process, numpy and PIL only):
+    StereoPairs.raw(index) into position j of the slot, views = [left, right (2,B,H,W,3) uint8 | ground truth (B,Hg,W) float32]."""
+    left, right, gt = dataset.raw(index)
+    H, W, Hg = shape
+    if left.shape != (H, W, 3) or gt.shape != (Hg, W):
+        raise ValueError(f"{dataset.left[index]}: crop {left.shape[:2]} / ground truth {gt.shape} differ from the first pair's "
+                         f"{(H, W)} / {(Hg, W)}")
+    img, g = views
+    np.copyto(img[0, j], left)
+    np.copyto(img[1, j], right)
+    np.copyto(g[j], gt)
+    return "decoded", None
 
 
-def _host_worker(task_q, done_q, lists, kitti_set, slot_names, B, H, W, Hg):
-    """Body of a host worker PROCESS of the pipelined mode (spawned: numpy and PIL only, never the GPU).  Task (slot, j, index):
-    StereoPairs.raw(index) into position j of the slot's shared memory [left B,H,W,3 | right B,H,W,3 | gt B,Hg,W float32]
-    (the ground truth at _gt_offset)."""
-    from multiprocessing import shared_memory
-
-    from lwsnet_amd.datasets import StereoPairs
-    ds = StereoPairs(*lists, training=False, kitti_set=kitti_set)
-    n_img = B * H * W * 3
-    shms = {}
-
-    def views(sid):
-        if sid not in shms:
-            shm = shared_memory.SharedMemory(name=slot_names[sid])
-            img = np.ndarray((2, B, H, W, 3), np.uint8, buffer=shm.buf)
-            gt = np.ndarray((B, Hg, W), np.float32, buffer=shm.buf, offset=_gt_offset(n_img))
-            shms[sid] = (shm, img, gt)
-        return shms[sid]
-
-    done_q.put(("ready", -1, -1, None))
-    while True:
-        task = task_q.get()
-        if task is None:
-            break
-        sid, j, index = task
-        try:
-            left, right, gt = ds.raw(index)
-            if left.shape != (H, W, 3) or gt.shape != (Hg, W):
-                raise ValueError(f"{ds.left[index]}: crop {left.shape[:2]} / ground truth {gt.shape} differ from the first pair's "
-                                 f"{(H, W)} / {(Hg, W)}")
-            _, img, g = views(sid)
-            np.copyto(img[0, j], left)
-            np.copyto(img[1, j], right)
-            np.copyto(g[j], gt)
-            done_q.put(("decoded", sid, j, None))
-        except Exception as e:                                          # noqa: BLE001 (reported to the parent, which raises)
-            done_q.put(("error", sid, j, f"pair {index}: {type(e).__name__}: {e}"))
-    for shm, _, _ in shms.values():
-        shm.close()
-
-
-class _Slot:
-    """One batch in flight: the shared-memory block the host workers fill, a pinned staging copy of it, the device copies, the
-    normalised inputs [left B | right B] and the four stage maps."""
+class _Slot(pipeline.Slot):
+    """One batch in flight: the shared block of _decode_pair, its device copies, the normalised inputs [left B | right B] and
+    the four stage maps."""
 
     def __init__(self, dev, B, H, W, Hg):
-        from multiprocessing import shared_memory
-
         import torch
-        self.n_img = B * H * W * 3
-        self.gt_off = _gt_offset(self.n_img)
-        size = self.gt_off + 4 * B * Hg * W
-        self.shm = shared_memory.SharedMemory(create=True, size=size)
-        self.host = torch.frombuffer(self.shm.buf, dtype=torch.uint8)
-        self.pinned = torch.empty((size,), dtype=torch.uint8).pin_memory()
-        self.dev_raw = torch.empty((size,), dtype=torch.uint8, device=dev)
+        super().__init__([((2, B, H, W, 3), np.uint8), ((B, Hg, W), np.float32)], dev)
+        self.dev_img = torch.empty((2, B, H, W, 3), dtype=torch.uint8, device=dev)
+        self.dev_gt = torch.empty((B, Hg, W), dtype=torch.float32, device=dev)
         self.dev_lr = torch.empty((2 * B, 3, H, W), dtype=torch.float32, device=dev)
         self.outs = [torch.empty((B, 1, H, W), dtype=torch.float32, device=dev) for _ in range(STAGES)]
-        self.shape = (B, H, W, Hg)
         self.batch, self.filled = -1, 0
 
     def upload(self, b):
-        """Host -> device for the first b pairs, then lws_preprocess_rgb8, on the current stream; returns (left, right, gt)."""
-        import torch
+        """Host -> device, then lws_preprocess_rgb8 for the first b pairs, on the current stream; returns (left, right, gt)."""
         from . import ops
-        B, H, W, Hg = self.shape
-        self.pinned.copy_(self.host)
-        self.dev_raw.copy_(self.pinned, non_blocking=True)
-        img = self.dev_raw[:2 * self.n_img].view(2, B, H, W, 3)[:, :b].reshape(2 * b, H, W, 3)
+        for i, dst in enumerate((self.dev_img, self.dev_gt)):
+            self.stage(i)
+            dst.copy_(self.pinned(i), non_blocking=True)
+        H, W = self.dev_img.shape[2:4]
         lr = self.dev_lr[:2 * b]
-        ops.preprocess_rgb8(img, out=lr)
-        gt = self.dev_raw[self.gt_off:].view(torch.float32).view(B, Hg, W)[:b]
-        return lr[:b], lr[b:], gt
-
-    def close(self):
-        self.host = None
-        try:
-            self.shm.close()
-        except BufferError:                                             # a view is still alive somewhere: unlink anyway
-            pass
-        self.shm.unlink()
+        ops.preprocess_rgb8(self.dev_img[:, :b].reshape(2 * b, H, W, 3), out=lr)
+        return lr[:b], lr[b:], self.dev_gt[:b]
 
 
 def _pipelined(model, dataset, mode, batches, maxdisp, workers, gpu_workers):
     """Host workers decode into slots; every batch is one lws_pool job; the metric kernel runs behind it (see the module
-    docstring).  A generator: yields "start" once everything is up, then (counts, abs_sum) per batch in order.  submit() and
-    result() of the pool are called on this thread only."""
-    import collections
-    import multiprocessing as mp
-    import queue
-
+    docstring).  A generator: yields "start" once everything is up, then (counts, abs_sum) per batch in order."""
     import torch
     from . import ops
+    from .datasets import StereoPairs
     dev = model.device
     N, P = max(1, int(workers)), max(1, int(gpu_workers))
     B = max(len(r) for r in batches)
@@ -264,88 +216,54 @@ def _pipelined(model, dataset, mode, batches, maxdisp, workers, gpu_workers):
     H, W, Hg = first[0].shape[0], first[0].shape[1], first[2].shape[0]
     row_offset = _row_offset(H, Hg)
     torch.cuda.set_device(dev)
-    slots = [_Slot(dev, B, H, W, Hg) for _ in range(min(len(batches), P + 2))]
-    ctx = mp.get_context("spawn")                       # fresh interpreters: a forked child of a process that holds HIP state is not safe
-    task_q, done_q = ctx.Queue(), ctx.Queue()
-    lists = (dataset.left, dataset.right, dataset.disp)
-    procs = [ctx.Process(target=_host_worker, args=(task_q, done_q, lists, dataset.kitti_set, [sl.shm.name for sl in slots],
-                                                    B, H, W, Hg), daemon=True) for _ in range(N)]
-    for pr in procs:
-        pr.start()
+    pairs = StereoPairs(dataset.left, dataset.right, dataset.disp, training=False, kitti_set=dataset.kitti_set, rng=None)  # picklable
     copy = torch.cuda.Stream(device=dev)
-    try:
-        with model.pool(workers=P) as gpool:
-            gpool.reserve(B, H, W)
-            sl = slots[0]                                   # warm-up outside the clock: library, pool workers and their workspaces
-            gpool.submit(sl.dev_lr[:B].zero_(), sl.dev_lr[B:].zero_(), out=sl.outs).result()
-            torch.cuda.synchronize(dev)
-            ready, t_wait = 0, time.perf_counter()
-            while ready < N:                                # every worker has started (spawn + imports: ~1 s, once)
-                try:
-                    msg = done_q.get(timeout=5.0)
-                except queue.Empty:
-                    if not all(pr.is_alive() for pr in procs) or time.perf_counter() - t_wait > 120.0:
-                        raise RuntimeError("the host worker processes did not start")
-                    continue
-                if msg[0] != "ready":
-                    raise RuntimeError(f"unexpected message from a host worker before its start-up: {msg}")
-                ready += 1
-            yield "start"
-            next_batch = 0
+    next_batch = 0
 
-            def assign(sid):
-                nonlocal next_batch
-                slots[sid].batch, slots[sid].filled = next_batch, 0
-                for j, i in enumerate(batches[next_batch]):
-                    task_q.put((sid, j, i))
-                next_batch += 1
+    def assign(sid):                                    # a free slot takes the next batch
+        nonlocal next_batch
+        if next_batch < len(batches):
+            slots[sid].batch, slots[sid].filled = next_batch, 0
+            for j, i in enumerate(batches[next_batch]):
+                host.put(sid, f"pair {i}", j, i)
+            next_batch += 1
 
-            for sid in range(len(slots)):
-                assign(sid)
-            inflight = collections.deque()                  # (batch, slot id, job, gt) in submission order
-            done, emitted = {}, 0
-            while emitted < len(batches):
-                decoding = any(sl.batch >= 0 and sl.filled < len(batches[sl.batch]) for sl in slots)
-                if inflight and (len(inflight) >= P or not decoding):
-                    k, sid, job, gt = inflight.popleft()
-                    preds = job.result()                    # the four stage maps are complete in device memory
-                    with torch.cuda.stream(copy):
-                        counts, sums = ops.stage_metrics(preds, gt, row_offset, maxdisp, mode)
-                        done[k] = (counts.cpu().numpy(), sums.cpu().numpy())
-                    slots[sid].batch = -1
-                    if next_batch < len(batches):
-                        assign(sid)
-                    while emitted in done:
-                        yield done.pop(emitted)
-                        emitted += 1
-                    continue
-                try:
-                    kind, sid, j, val = done_q.get(timeout=5.0)
-                except queue.Empty:
-                    if not all(pr.is_alive() for pr in procs):
-                        raise RuntimeError("a host worker process died")
-                    continue
-                if kind != "decoded":
-                    raise RuntimeError(val)
-                sl = slots[sid]
-                sl.filled += 1
-                k = sl.batch
-                b = len(batches[k])
-                if sl.filled == b:
-                    with torch.cuda.stream(copy):
-                        left, right, gt = sl.upload(b)
-                        job = gpool.submit(left, right, out=[o[:b] for o in sl.outs])     # starts behind the upload (after_stream = copy)
-                    inflight.append((k, sid, job, gt))
-    finally:
-        for _ in procs:
-            task_q.put(None)
-        for pr in procs:
-            pr.join(timeout=10.0)
-            if pr.is_alive():
-                pr.terminate()                              # (the exact children started above)
+    def handle(kind, sid, _):
+        sl = slots[sid]
+        sl.filled += 1
+        b = len(batches[sl.batch])
+        if sl.filled < b:
+            return None
+        with torch.cuda.stream(copy):
+            left, right, gt = sl.upload(b)
+            return sl.batch, sid, gpool.submit(left, right, out=[o[:b] for o in sl.outs]), gt     # starts behind the upload
+
+    def retire(item):
+        k, sid, job, gt = item
+        preds = job.result()                            # the four stage maps are complete in device memory
+        with torch.cuda.stream(copy):
+            counts, sums = ops.stage_metrics(preds, gt, row_offset, maxdisp, mode)
+            res = counts.cpu().numpy(), sums.cpu().numpy()
+        assign(sid)
+        return k, res
+
+    with contextlib.ExitStack() as stack:
+        slots = [stack.enter_context(_Slot(dev, B, H, W, Hg)) for _ in range(min(len(batches), P + 2))]
+        host = stack.enter_context(pipeline.HostWorkers(N, functools.partial(_decode_pair, pairs, (H, W, Hg)), slots))
+        gpool = stack.enter_context(model.pool(workers=P))
+        sl = slots[0]                                   # warm-up outside the clock: library, pool workers and their workspaces
+        gpool.submit(sl.dev_lr[:B].zero_(), sl.dev_lr[B:].zero_(), out=sl.outs).result()
         torch.cuda.synchronize(dev)
-        for sl in slots:
-            sl.close()
+        host.wait_ready()
+        yield "start"
+        for sid in range(len(slots)):
+            assign(sid)
+        done, emitted = {}, 0
+        for k, res in pipeline.schedule(host, P, handle, retire, lambda: host.pending > 0):
+            done[k] = res
+            while emitted in done:                      # in batch order
+                yield done.pop(emitted)
+                emitted += 1
 
 
 def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, workers=0, gpu_workers=2, log=None, lr_check=None,
@@ -415,13 +333,7 @@ def build_parser():
     p.add_argument("--test_batch_size", type=int, default=8)
     p.add_argument("--maxdisp", type=int, default=192, help="SceneFlow: the mask bound gt < maxdisp (the KITTI loop always uses 192)")
     p.add_argument("--model", type=str, default="checkpoint")
-    p.add_argument("--synthetic_weights", action="store_true",
-                   help="use the seeded synthetic weights instead of --model (the reference ships no checkpoint)")
-    p.add_argument("--maxdisplist", type=int, nargs="+", default=[24, 5, 5])
-    p.add_argument("--channels_3d", type=int, default=8)
-    p.add_argument("--layers_3d", type=int, default=4)
-    p.add_argument("--growth_rate", type=int, nargs="+", default=[4, 1, 1])
-    p.add_argument("--gpu_id", type=int, default=0)
+    add_model_arguments(p)
     p.add_argument("--workers", type=int, default=0,
                    help="host worker processes decoding into a pipelined GPU path (0 = the reference's sequential loop; not in the reference)")
     p.add_argument("--gpu_workers", type=int, default=2, help="with --workers: batches kept in flight by lws_pool")
@@ -447,28 +359,9 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     check_lr_arguments(parser, args)
-    logging.basicConfig(stream=sys.stderr, level=logging.INFO,
-                        format="[%(asctime)s %(filename)s:%(lineno)s] %(levelname)s: %(message)s")
-    log = logging.getLogger("lwsnet_amd.evaluate")
-    for k, v in vars(args).items():
-        log.info("%s: %s", k, v)
+    log = start_logging("lwsnet_amd.evaluate", args)
     dataset, metric, maxdisp = load_dataset(args)
-    import torch
-    from .checkpoint import load_state_dict
-    from .models import LWSNet
-    from .weights import make_state_dict
-    torch.cuda.set_device(args.gpu_id)
-    model = LWSNet(args, device=torch.device("cuda", args.gpu_id))
-    if args.synthetic_weights:
-        model.set_state_dict(make_state_dict(7, args))
-        log.info("Using seeded synthetic weights")
-    elif not os.path.isfile(args.model):
-        log.info("No model load")
-        raise SystemExit(1)
-    else:
-        model.set_state_dict(load_state_dict(args.model))
-        log.info("Successful load model")
-    model.eval()
+    model = load_model(args, log, missing_status=1)
     res = evaluate(model, dataset, metric, batch_size=args.test_batch_size, maxdisp=maxdisp, workers=args.workers,
                    gpu_workers=args.gpu_workers, log=log, lr_check=args.lr_check, lr_fill=args.lr_fill)
     res["dataset"] = args.dataset

@@ -14,9 +14,9 @@ per-pair work is pipelined: N host worker PROCESSES (spawned, numpy + PIL only, 
 slots that are registered with HIP as pinned memory; a copy stream uploads the uint8 pixels and normalises them on the device
 (lws_preprocess_rgb8: bit for bit the host transform), the forwards run through lws_pool (several batch-1 forwards in flight), a
 second stream casts and colour-maps the stage-4 map on the device (lws_apply_lut8) and brings 3 bytes per pixel back into the
-slot, and the same workers PNG-encode them.  The files written are byte-identical to the sequential loop's
-(tests/test_gpu_parity.py::test_cli_directory_pipeline_writes_identical_files); the end-to-end rate and where the time goes
-are logged and returned (profiles/r06/e2e_cli.txt).
+slot, and the same workers PNG-encode them (the processes, the slots and the one-thread scheduling loop: lwsnet_amd/pipeline.py).
+The files written are byte-identical to the sequential loop's (tests/test_gpu_parity.py::test_cli_directory_pipeline_writes_identical_files);
+the end-to-end rate and where the time goes are logged and returned (profiles/r06/e2e_cli.txt).
 
 `--lr_check TAU [--lr_fill]` (not in the reference; sequential mode only): the colour files come from LWSNet.forward_lr's checked maps
 and each gets a grey mask `<stem>_lr.png` beside it (consistent 255, inconsistent 0, out of the right view 128).
@@ -28,6 +28,7 @@ folder of them named after the frames) or `--camera FX FY CX CY BASELINE` in the
 images are.  With `--lr_check` they use the checked maps: without `--lr_fill` only consistent pixels are kept.
 """
 import argparse
+import contextlib
 import glob
 import logging
 import os
@@ -37,6 +38,9 @@ import time
 
 import numpy as np
 
+from . import imageio as io
+from . import pipeline
+
 
 def build_parser():
     p = argparse.ArgumentParser(description="Model Inference")        # inference.py:17-29
@@ -45,14 +49,8 @@ def build_parser():
     p.add_argument("--left_img", type=str, default="")
     p.add_argument("--model", type=str, default="results/finetune/checkpoint.pdparams")
     p.add_argument("--save_path", type=str, default="results/inference")
-    p.add_argument("--maxdisplist", type=int, nargs="+", default=[24, 5, 5])
-    p.add_argument("--channels_3d", type=int, default=8)
-    p.add_argument("--layers_3d", type=int, default=4)
-    p.add_argument("--growth_rate", type=int, nargs="+", default=[4, 1, 1])
-    p.add_argument("--gpu_id", type=int, default=0)
+    add_model_arguments(p)
     p.add_argument("--vis", action="store_true", default=False)
-    p.add_argument("--synthetic_weights", action="store_true",
-                   help="use the seeded synthetic weights instead of --model (the reference ships no checkpoint)")
     p.add_argument("--split_bf16", action="store_true",
                    help="opt-in numerics mode of this build (not in the reference): MFMA convolutions on split-bf16 operands, "
                         "float32-level accuracy, +20-25 %% speed, not bit-identical to the default (include/lwsnet_hip.h)")
@@ -134,6 +132,48 @@ def add_lr_arguments(p):
     p.add_argument("--lr_fill", action="store_true", help="with --lr_check: fill the dropped pixels with their row's background value")
 
 
+def add_model_arguments(p):
+    """The model's shape flags, --gpu_id and --synthetic_weights (shared with lwsnet_amd.evaluate; --model is per CLI)."""
+    p.add_argument("--maxdisplist", type=int, nargs="+", default=[24, 5, 5])
+    p.add_argument("--channels_3d", type=int, default=8)
+    p.add_argument("--layers_3d", type=int, default=4)
+    p.add_argument("--growth_rate", type=int, nargs="+", default=[4, 1, 1])
+    p.add_argument("--gpu_id", type=int, default=0)
+    p.add_argument("--synthetic_weights", action="store_true",
+                   help="use the seeded synthetic weights instead of --model (the reference ships no checkpoint)")
+
+
+def start_logging(name, args):
+    """The CLIs' log lines on stderr, opened with one line per argument; returns the logger `name`."""
+    logging.basicConfig(stream=sys.stderr, level=logging.INFO,
+                        format="[%(asctime)s %(filename)s:%(lineno)s] %(levelname)s: %(message)s")
+    log = logging.getLogger(name)
+    for k, v in vars(args).items():
+        log.info("%s: %s", k, v)
+    return log
+
+
+def load_model(args, log, missing_status=None):
+    """LWSNet on cuda:<gpu_id> in eval mode, with the seeded synthetic weights or the checkpoint --model.  When --model names
+    no file: "No model load" and SystemExit(missing_status) (inference.py:41-43 exits with None)."""
+    import torch
+    from .checkpoint import load_state_dict
+    from .models import LWSNet
+    from .weights import make_state_dict
+    torch.cuda.set_device(args.gpu_id)                                  # inference.py:38
+    model = LWSNet(args, device=torch.device("cuda", args.gpu_id))
+    if args.synthetic_weights:
+        model.set_state_dict(make_state_dict(7, args))
+        log.info("Using seeded synthetic weights")
+    elif not os.path.isfile(args.model):                                # inference.py:41-43
+        log.info("No model load")
+        raise SystemExit(missing_status)
+    else:
+        model.set_state_dict(load_state_dict(args.model))
+        log.info("Successful load model")
+    return model.eval()
+
+
 def check_lr_arguments(p, args):
     """Rejects what the left-right check does not support, before any model or GPU work."""
     if args.lr_check is None:
@@ -146,236 +186,120 @@ def check_lr_arguments(p, args):
         p.error("--lr_check runs in the sequential mode only: use --workers 0")
 
 
-def _host_worker(task_q, done_q, slot_names, H, W):
-    """Body of a host worker PROCESS of the pipelined directory mode (spawned: a fresh interpreter that imports numpy and PIL
-    only and never touches the GPU).  Tasks: ("decode", i, slot, left path, right path) -> PNG decode + crop of both images into
-    the slot's shared memory as uint8 RGB (inference.py:90-100; the normalisation of :102-103 runs on the GPU,
-    lws_preprocess_rgb8); ("encode", i, slot, out path) -> PNG of the slot's colour-mapped stage-4 map (inference.py:136; the
-    uint8 cast and the JET table of :114-115 run on the GPU, lws_apply_lut8).  Python threads do this work at most ~16-wide (the
-    interpreter lock); processes scale with the host's cores."""
-    from multiprocessing import shared_memory
-
-    from lwsnet_amd import imageio as io
-    n_px = H * W * 3
-    shms = {}
-
-    def views(sid):
-        if sid not in shms:
-            shm = shared_memory.SharedMemory(name=slot_names[sid])
-            buf = np.ndarray((3 * n_px,), np.uint8, buffer=shm.buf)
-            shms[sid] = (shm, buf[:n_px].reshape(H, W, 3), buf[n_px:2 * n_px].reshape(H, W, 3), buf[2 * n_px:].reshape(H, W, 3))
-        return shms[sid]
-
-    done_q.put(("ready", -1, -1, 0.0))                                  # interpreter up, numpy and PIL imported
-    while True:
-        task = task_q.get()
-        if task is None:
-            break
-        kind, i, sid = task[0], task[1], task[2]
-        t0 = time.perf_counter()
-        try:
-            if kind == "decode":
-                left = io.crop_bottom_right(io.load_rgb(task[3]))
-                right = io.crop_bottom_right(io.load_rgb(task[4]))
-                if left is None or right is None:                       # inference.py:96-97
-                    done_q.put(("skipped", i, sid, 0.0))
-                    continue
-                _, vl, vr, _ = views(sid)
-                np.copyto(vl, left)
-                np.copyto(vr, right)
-                done_q.put(("decoded", i, sid, time.perf_counter() - t0))
-            else:
-                io.save_png(task[3], views(sid)[3])
-                done_q.put(("encoded", i, sid, time.perf_counter() - t0))
-        except Exception as e:                                          # noqa: BLE001 (reported to the parent, which raises)
-            done_q.put(("error", i, sid, f"{kind} of pair {i}: {type(e).__name__}: {e}"))
-    for shm, *_ in shms.values():
-        shm.close()
+def _pair_task(views, op, *paths):
+    """Host worker handler of the pipelined directory mode (lwsnet_amd/pipeline.py: a spawned process, numpy and PIL only).
+    views = [left, right (2,H,W,3) | colour-mapped stage-4 map (H,W,3)], uint8 RGB.  ("decode", left path, right path): PNG
+    decode + crop of both images into the slot (inference.py:90-100; the normalisation of :102-103 runs on the GPU,
+    lws_preprocess_rgb8); ("encode", out path): PNG of the slot's colour-mapped map (inference.py:136; the uint8 cast and the
+    JET table of :114-115 run on the GPU, lws_apply_lut8).  Returns (kind, seconds spent)."""
+    t0 = time.perf_counter()
+    if op == "encode":
+        io.save_png(paths[0], views[1])
+        return "encoded", time.perf_counter() - t0
+    left = io.crop_bottom_right(io.load_rgb(paths[0]))
+    right = io.crop_bottom_right(io.load_rgb(paths[1]))
+    if left is None or right is None:                                   # inference.py:96-97
+        return "skipped", 0.0
+    np.copyto(views[0][0], left)
+    np.copyto(views[0][1], right)
+    return "decoded", time.perf_counter() - t0
 
 
-class _Slot:
-    """Buffers of one pair in flight: a shared-memory block [left RGB | right RGB | colour-mapped stage-4 map], all uint8 HWC,
-    that the host workers write and read -- registered with HIP as pinned memory when the runtime allows (otherwise staged
-    through pinned tensors) --, the device copies of the three images, the normalised device inputs and the four stage maps."""
+class _Slot(pipeline.Slot):
+    """One pair in flight: the shared block of _pair_task, the device copies of its three images, the normalised device
+    inputs [left | right], the four stage maps and the copy timing events."""
 
     def __init__(self, dev, H, W):
-        from multiprocessing import shared_memory
-
         import torch
-        n_px = H * W * 3
-        self.shm = shared_memory.SharedMemory(create=True, size=3 * n_px)
-        host = torch.frombuffer(self.shm.buf, dtype=torch.uint8)
-        self.registered = False
-        try:
-            if os.environ.get("LWS_CLI_NO_HOST_REGISTER") != "1":      # (tests force the staging path with it)
-                rc = torch.cuda.cudart().cudaHostRegister(host.data_ptr(), host.numel(), 0)
-                self.registered = int(rc) == 0 and host.is_pinned()
-        except Exception:                                               # noqa: BLE001 (fall back to staging copies)
-            self.registered = False
-        self.host_in, self.host_out = host[:2 * n_px].view(2, H, W, 3), host[2 * n_px:].view(H, W, 3)
-        if not self.registered:
-            self.pin_in = torch.empty((2, H, W, 3), dtype=torch.uint8).pin_memory()
-            self.pin_out = torch.empty((H, W, 3), dtype=torch.uint8).pin_memory()
+        super().__init__([((2, H, W, 3), np.uint8), ((H, W, 3), np.uint8)], dev)
         self.dev_in = torch.empty((2, H, W, 3), dtype=torch.uint8, device=dev)
         self.dev_rgb = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
-        self.dev_lr = torch.empty((2, 3, H, W), dtype=torch.float32, device=dev)      # [left | right], normalised
+        self.dev_lr = torch.empty((2, 3, H, W), dtype=torch.float32, device=dev)
         self.outs = [torch.empty((1, 1, H, W), dtype=torch.float32, device=dev) for _ in range(4)]
         self.ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]      # h2d begin / end, d2h begin / end
-        self.t0 = 0.0
-
-    def close(self):
-        import torch
-        ptr = self.host_in.data_ptr()
-        self.host_in = self.host_out = None
-        if self.registered:
-            try:
-                torch.cuda.cudart().cudaHostUnregister(ptr)
-            except Exception:                                           # noqa: BLE001
-                pass
-        try:
-            self.shm.close()
-        except BufferError:                                             # a view is still alive somewhere: unlink anyway
-            pass
-        self.shm.unlink()
+        self.pair, self.t0 = -1, 0.0
 
 
 def inference_pipelined(model, left_imgs, right_imgs, args, log):
     """The loop of inference.py:88-137 in directory mode, pipelined (see the module docstring).  Returns (written, stats)."""
-    import multiprocessing as mp
-    import queue
-    import threading
-
     import torch
-    from . import imageio as io
     from . import ops
     dev = model.device
     N, P = max(1, int(args.workers)), max(1, int(args.gpu_workers))
     H, W = io.CROP_H, io.CROP_W
     total = len(left_imgs)
     torch.cuda.set_device(dev)
-    slots = [_Slot(dev, H, W) for _ in range(2 * P + 2 * N)]
     lut_dev = torch.from_numpy(io.jet_lut()).to(dev)
-    ctx = mp.get_context("spawn")                        # fresh interpreters: a forked child of a process that holds HIP state is not safe
-    task_q, done_q = ctx.Queue(), ctx.Queue()
-    names = [sl.shm.name for sl in slots]
-    procs = [ctx.Process(target=_host_worker, args=(task_q, done_q, names, H, W), daemon=True) for _ in range(N)]
-    for pr in procs:
-        pr.start()
-    free = queue.Queue()
-    for sid in range(len(slots)):
-        free.put(sid)
-    inflight = queue.Queue()
+    h2d, d2h = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
     written = {}
     acc = {"decode_s": 0.0, "encode_s": 0.0, "h2d_ms": 0.0, "d2h_ms": 0.0, "pairs": 0, "skipped": 0, "latency_s": 0.0}
-    errors = []
-    h2d, d2h = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
+    nxt = decoding = 0
 
-    def feeder():
-        for i in range(total):
-            sid = free.get()
-            slots[sid].t0 = time.perf_counter()
-            task_q.put(("decode", i, sid, left_imgs[i], right_imgs[i]))
+    def out_path(i):
+        return os.path.join(args.save_path, os.path.basename(left_imgs[i]))
 
-    def collector():
-        torch.cuda.set_device(dev)
-        while True:
-            item = inflight.get()
-            if item is None:
-                return
-            i, sid, job = item
-            sl = slots[sid]
-            try:
-                job.result()                                            # the four stage maps are complete in device memory
-                dst = sl.host_out if sl.registered else sl.pin_out
-                with torch.cuda.stream(d2h):
-                    sl.ev[2].record()
-                    ops.apply_lut8(sl.outs[3][0, 0], lut_dev, out=sl.dev_rgb)   # inference.py:114-115; directory mode keeps stage 4 (:133-137)
-                    dst.copy_(sl.dev_rgb, non_blocking=True)
-                    sl.ev[3].record()
-                sl.ev[3].synchronize()
-                if not sl.registered:
-                    sl.host_out.copy_(sl.pin_out)
-                task_q.put(("encode", i, sid, os.path.join(args.save_path, os.path.basename(left_imgs[i]))))
-            except Exception as e:                                      # noqa: BLE001
-                errors.append(e)
-                done_q.put(("error", i, sid, repr(e)))
+    def feed(sid):                                                      # a free slot takes the next pair
+        nonlocal nxt, decoding
+        if nxt < total:
+            slots[sid].pair, slots[sid].t0 = nxt, time.perf_counter()
+            host.put(sid, f"decode of pair {nxt}", "decode", left_imgs[nxt], right_imgs[nxt])
+            nxt += 1
+            decoding += 1
 
-    wall = 0.0
-    try:
+    def handle(kind, sid, seconds):
+        nonlocal decoding
+        sl = slots[sid]
+        if kind == "decoded":
+            decoding -= 1
+            acc["decode_s"] += seconds
+            sl.stage(0)
+            with torch.cuda.stream(h2d):
+                sl.ev[0].record()
+                sl.dev_in.copy_(sl.pinned(0), non_blocking=True)
+                ops.preprocess_rgb8(sl.dev_in, out=sl.dev_lr)               # inference.py:102-103 (ToTensor + Normalize)
+                sl.ev[1].record()
+                return sid, gpool.submit(sl.dev_lr[:1], sl.dev_lr[1:], out=sl.outs)    # starts behind them (after_stream = h2d)
+        if kind == "skipped":
+            decoding -= 1
+            acc["skipped"] += 1
+        else:                                                           # encoded: the slot's pair is on disk
+            acc["encode_s"] += seconds
+            acc["h2d_ms"] += sl.ev[0].elapsed_time(sl.ev[1])
+            acc["d2h_ms"] += sl.ev[2].elapsed_time(sl.ev[3])
+            acc["pairs"] += 1
+            acc["latency_s"] += time.perf_counter() - sl.t0
+            written[sl.pair] = out_path(sl.pair)
+        feed(sid)
+        return None
+
+    def retire(item):
+        sid, job = item
+        sl = slots[sid]
+        job.result()                                                    # the four stage maps are complete in device memory
+        with torch.cuda.stream(d2h):
+            sl.ev[2].record()
+            ops.apply_lut8(sl.outs[3][0, 0], lut_dev, out=sl.dev_rgb)   # inference.py:114-115; directory mode keeps stage 4 (:133-137)
+            sl.pinned(1).copy_(sl.dev_rgb, non_blocking=True)
+            sl.ev[3].record()
+        sl.ev[3].synchronize()
+        sl.unstage(1)
+        host.put(sid, f"encode of pair {sl.pair}", "encode", out_path(sl.pair))
+
+    with contextlib.ExitStack() as stack:
+        slots = [stack.enter_context(_Slot(dev, H, W)) for _ in range(2 * P + 2 * N)]
+        host = stack.enter_context(pipeline.HostWorkers(N, _pair_task, slots))
+        gpool = stack.enter_context(model.pool(workers=P))
         # warm-up outside the clock (the reference times its first call; this build never does): library, pool and workers up
-        with model.pool(workers=P) as gpool:
-            gpool.reserve(1, H, W)
-            gpool.submit(slots[0].dev_lr[:1].zero_(), slots[0].dev_lr[1:].zero_(), out=slots[0].outs).result()
-            torch.cuda.synchronize(dev)
-            ready, t_wait = 0, time.perf_counter()
-            while ready < N:                                            # every worker has started (spawn + imports: ~1 s, once)
-                try:
-                    msg = done_q.get(timeout=5.0)
-                except queue.Empty:
-                    if not all(pr.is_alive() for pr in procs) or time.perf_counter() - t_wait > 120.0:
-                        raise RuntimeError("the host worker processes did not start")
-                    continue
-                if msg[0] == "ready":
-                    ready += 1
-                else:
-                    raise RuntimeError(f"unexpected message from a host worker before its start-up: {msg[:3]}")
-            t_begin = time.perf_counter()
-            tf = threading.Thread(target=feeder, daemon=True)
-            tc = threading.Thread(target=collector, daemon=True)
-            tf.start()
-            tc.start()
-            done = 0
-            while done < total and not errors:
-                try:
-                    kind, i, sid, val = done_q.get(timeout=5.0)
-                except queue.Empty:
-                    if not all(pr.is_alive() for pr in procs):
-                        errors.append(RuntimeError("a host worker process died"))
-                    continue
-                sl = slots[sid]
-                if kind == "decoded":
-                    acc["decode_s"] += val
-                    src = sl.host_in if sl.registered else sl.pin_in
-                    if not sl.registered:
-                        sl.pin_in.copy_(sl.host_in)
-                    with torch.cuda.stream(h2d):
-                        sl.ev[0].record()
-                        sl.dev_in.copy_(src, non_blocking=True)
-                        ops.preprocess_rgb8(sl.dev_in, out=sl.dev_lr)           # inference.py:102-103 (ToTensor + Normalize)
-                        sl.ev[1].record()
-                        job = gpool.submit(sl.dev_lr[:1], sl.dev_lr[1:], out=sl.outs)   # starts behind them (after_stream = h2d)
-                    inflight.put((i, sid, job))
-                elif kind == "encoded":
-                    acc["encode_s"] += val
-                    acc["h2d_ms"] += sl.ev[0].elapsed_time(sl.ev[1])
-                    acc["d2h_ms"] += sl.ev[2].elapsed_time(sl.ev[3])
-                    acc["pairs"] += 1
-                    acc["latency_s"] += time.perf_counter() - sl.t0
-                    written[i] = os.path.join(args.save_path, os.path.basename(left_imgs[i]))
-                    free.put(sid)
-                    done += 1
-                elif kind == "skipped":
-                    acc["skipped"] += 1
-                    free.put(sid)
-                    done += 1
-                else:
-                    errors.append(RuntimeError(val))
-            wall = time.perf_counter() - t_begin
-            inflight.put(None)
-            tc.join(timeout=30.0)
-    finally:
-        for _ in procs:
-            task_q.put(None)
-        for pr in procs:
-            pr.join(timeout=10.0)
-            if pr.is_alive():
-                pr.terminate()                                          # (the exact children started above)
-        registered = all(sl.registered for sl in slots)
+        gpool.submit(slots[0].dev_lr[:1].zero_(), slots[0].dev_lr[1:].zero_(), out=slots[0].outs).result()
         torch.cuda.synchronize(dev)
-        for sl in slots:
-            sl.close()
-    if errors:
-        raise errors[0]
+        host.wait_ready()
+        t_begin = time.perf_counter()
+        for sid in range(len(slots)):
+            feed(sid)
+        for _ in pipeline.schedule(host, P, handle, retire, lambda: decoding > 0):
+            pass
+        wall = time.perf_counter() - t_begin
+    registered = all(sl.registered for sl in slots)
     n = max(acc["pairs"], 1)
     stats = {"pairs": acc["pairs"], "skipped": acc["skipped"], "wall_s": round(wall, 4), "pairs_per_s": round(acc["pairs"] / wall, 2),
              "host_processes": N, "gpu_workers": P, "shared_memory_pinned": registered,
@@ -392,7 +316,6 @@ def inference_pipelined(model, left_imgs, right_imgs, args, log):
 def inference(model, left_imgs, right_imgs, args, log):
     """inference.py:78-138."""
     import torch
-    from . import imageio as io
     written = []
     warm = False
     lr = getattr(args, "lr_check", None) is not None
@@ -403,6 +326,15 @@ def inference(model, left_imgs, right_imgs, args, log):
             return model(l_in, r_in), None
         res = model.forward_lr(l_in, r_in, tau=args.lr_check, fill=args.lr_fill)     # colour files from the checked maps
         return res.disp, res.mask
+
+    def save(path, color, stage):                                       # the colour file, then the mask and geometry files beside it
+        io.save_png(path, color)
+        written.append(path)
+        log.info("{}\t\tSave img = {}".format(ss, path))
+        if lr:
+            written.append(_save_lr_mask(path, masks[stage], log))
+        if geo:
+            written.extend(_save_geometry(path, outputs[stage], masks[stage] if lr and not args.lr_fill else None, cam, left, args, log))
 
     for li, ri in zip(left_imgs, right_imgs):
         full = io.load_rgb(li)
@@ -426,29 +358,14 @@ def inference(model, left_imgs, right_imgs, args, log):
             disp = outputs[stage].squeeze(axis=[0, 1]).numpy()          # :114 (the uint8 cast is inside disparity_to_color)
             color = io.disparity_to_color(disp)
             if args.left_img:                                           # :117-122
-                path = os.path.join(os.path.dirname(args.left_img), str(stage + 1) + ".png")
-                io.save_png(path, color)
-                written.append(path)
-                log.info("{}\t\tSave img = {}".format(ss, path))
-                if lr:
-                    written.append(_save_lr_mask(path, masks[stage], log))
-                if geo:
-                    written += _save_geometry(path, outputs[stage], masks[stage] if lr and not args.lr_fill else None, cam, left, args, log)
+                save(os.path.join(os.path.dirname(args.left_img), str(stage + 1) + ".png"), color, stage)
         if not args.left_img:                                           # :133-137 (stage-4 map only)
-            path = os.path.join(args.save_path, os.path.basename(li))
-            io.save_png(path, color)
-            written.append(path)
-            log.info("{}\t\tSave img = {}".format(ss, path))
-            if lr:
-                written.append(_save_lr_mask(path, masks[3], log))
-            if geo:
-                written += _save_geometry(path, outputs[3], masks[3] if lr and not args.lr_fill else None, cam, left, args, log)
+            save(os.path.join(args.save_path, os.path.basename(li)), color, 3)
     return written
 
 
 def _frame_camera(args, left_path, h, w):
     """The camera of a frame's cropped maps (None without --calib / --camera)."""
-    from . import imageio as io
     from .geometry import Camera
     if args.calib is not None:
         cam = Camera.from_kitti(_calib_path(args, left_path))
@@ -464,7 +381,6 @@ def _save_geometry(path, disp, mask, cam, left_rgb, args, log):
     left-right check's codes (only code-1 pixels kept) or None."""
     import torch
 
-    from . import imageio as io
     from . import ops
     from .geometry import write_ply
     stem = os.path.splitext(path)[0]
@@ -489,7 +405,6 @@ def _save_geometry(path, disp, mask, cam, left_rgb, args, log):
 
 def _save_lr_mask(path, mask, log):
     """The left-right check codes of the map written to `path`, as the grey PNG <stem>_lr.png next to it."""
-    from . import imageio as io
     code = mask[0, 0].cpu().numpy()
     mpath = os.path.splitext(path)[0] + "_lr.png"
     io.save_lr_mask_png(mpath, code)
@@ -502,27 +417,8 @@ def main(argv=None):
     args = parser.parse_args(argv)
     check_lr_arguments(parser, args)
     check_geometry_arguments(parser, args)
-    logging.basicConfig(stream=sys.stderr, level=logging.INFO,
-                        format="[%(asctime)s %(filename)s:%(lineno)s] %(levelname)s: %(message)s")
-    log = logging.getLogger("lwsnet_amd.inference")
-    for k, v in vars(args).items():
-        log.info("%s: %s", k, v)
-    import torch
-    from .checkpoint import load_state_dict
-    from .models import LWSNet
-    from .weights import make_state_dict
-    torch.cuda.set_device(args.gpu_id)                                  # inference.py:38
-    model = LWSNet(args, device=torch.device("cuda", args.gpu_id))
-    if args.synthetic_weights:
-        model.set_state_dict(make_state_dict(7, args))
-        log.info("Using seeded synthetic weights")
-    elif not os.path.isfile(args.model):                                # inference.py:41-43
-        log.info("No model load")
-        raise SystemExit
-    else:
-        model.set_state_dict(load_state_dict(args.model))
-        log.info("Successful load model")
-    model.eval()
+    log = start_logging("lwsnet_amd.inference", args)
+    model = load_model(args, log)
     if getattr(args, "split_bf16", False):
         model.set_option("split_bf16", 7)
         log.info("split-bf16 numerics mode")

@@ -259,7 +259,8 @@ class _PoolJob:
 
 
 class ForwardPool:
-    """Python face of lws_pool (see LWSNet.pool).  `submit` returns at once; `.result()` of the job waits for it."""
+    """Python face of lws_pool (see LWSNet.pool).  `submit` returns at once; `.result()` of the job waits for it.  Use a pool
+    from one thread: submit() and result() share the bookkeeping of the jobs in flight without a lock."""
 
     def __init__(self, model, workers, side_streams=False):
         self._model = model                     # keeps the source handle alive
