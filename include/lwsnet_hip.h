@@ -209,6 +209,38 @@ int64_t lws_point_cloud_workspace(int B, int H);
 int lws_point_cloud(const float *disp, const uint8_t *mask, const uint8_t *rgb, const float *cam, int B, int H, int W, float min_disp,
                     float max_depth, void *workspace, void *points, int64_t *counts, void *stream);
 
+/* ---- speckle filter: connected components of a disparity map (additive after v8) ---- */
+/* bytes of device workspace lws_speckle_filter needs for this geometry: per pixel one int32 parent word and one int32 size word
+ * (8 bytes), plus three int32 per row for the counts, each part rounded up to 256 bytes */
+int64_t lws_speckle_workspace(int B, int H, int W);
+/* Removes the small connected blobs of a disparity map -- OpenCV's filterSpeckles rule on float32 instead of 12.4 fixed point.
+ * disp, out float32 [B,1,H,W]; mask (NULL: every pixel) and mask_out uint8 [B,1,H,W], the lws_lr_check code map; labels (NULL:
+ * skipped) int32 [B,1,H,W]; counts (NULL: skipped) int64 [B][3]; workspace: lws_speckle_workspace(B, H, W) bytes, 16-byte
+ * aligned, contents undefined before and after.  max_diff finite and >= 0, max_size >= 0, fill 0 or 1 (1 needs W <= 8192: the
+ * row is staged in LDS, as in lws_lr_check); H*W < 2^31, B <= 65535.  Per image, d = disp[b,0,y,x]:
+ *   valid     = (mask == NULL || mask[b,0,y,x] == 1) && isfinite(d) && d > 0.0f     (the d > 0 rule of disp16; 0.0f is what
+ *               lws_lr_check writes for a dropped pixel, so an unfilled checked map can be passed with or without its mask)
+ *   joined    two valid pixels p, q that are 4-neighbours are joined iff fabsf(dp - dq) <= max_diff (one float32 subtraction,
+ *               one compare); a component is a class of the transitive closure
+ *   speckle   a component of size <= max_size pixels (OpenCV's maxSpeckleSize; max_size = 0 removes nothing)
+ *   mask_out  1 for a valid pixel of a kept component, 3 ("speckle") for a valid pixel of a removed one; for an invalid pixel
+ *             the input code if a mask was given and that code is not 1, else 0.  lws_depth_maps / lws_point_cloud keep code 1
+ *             only, so they take mask_out as it is
+ *   out       fill = 0: d where mask_out == 1, else 0.0f;  fill = 1: the background fill of lws_lr_check applied to mask_out
+ *             (code-1 pixels keep d, every other pixel the smaller of d at the nearest code-1 pixel to its left and to its right
+ *             in its row, the left one on a tie, one side's value if only that side exists, 0.0f if the row has none)
+ *   labels    for a valid pixel the raster index y*W + x of the first pixel of its component in raster order (speckles keep
+ *             theirs); -1 for an invalid pixel
+ *   counts[b] = {valid pixels, kept pixels (code 1 in mask_out), removed components}
+ * Every output is a pure function of the image: the same bytes in any batch, at any position in it, on every run (the atomics
+ * inside are integer min / add, whose order cannot show).  out may be disp itself and mask_out may be mask itself (in place);
+ * any other overlap between disp, mask, out, mask_out, labels, counts and the workspace returns LWS_ERR_INVALID, as every
+ * argument error does, before any GPU call.  Four launches on `stream` (tile labelling in LDS, unions across tile edges,
+ * flatten + sizes, apply with the row fill) plus one when counts is requested: a fixed list that does not depend on the data,
+ * with no device-to-host read, so the call can be captured into a hipGraph.  No scratch memory. */
+int lws_speckle_filter(const float *disp, const uint8_t *mask, int B, int H, int W, float max_diff, int max_size, int fill,
+                       void *workspace, float *out, uint8_t *mask_out, int32_t *labels, int64_t *counts, void *stream);
+
 /* Launch-plan options of lws_forward / lws_disparity_stages.  They change which kernels / streams carry the work, never
  * the arithmetic: every setting returns the same bits (tests/test_gpu_parity.py::test_forward_schedule_options) -- except
  * the opt-in numerics mode "split_bf16".  (ABI v8 removed the options two rounds of sweeps had retired: left_at, split_heads,

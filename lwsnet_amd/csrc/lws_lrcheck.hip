@@ -5,6 +5,7 @@
 // so tests/lr_reference.py restates every output bit for bit in numpy.  Determinism: no atomics; a workgroup owns one row of one
 // image and map, so an image gives the same bits in any batch.  0 bytes of scratch; the row lives in LDS.
 #include "lws_common.h"
+#include "lws_rowfill.h"
 
 namespace lws {
 
@@ -12,8 +13,12 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-constexpr int kMaxW = 8192;                                 // dRm / dL row + two int per quad: 48 KiB of LDS at most
-constexpr int kNone = 0x7fffffff;                           // "no consistent pixel to the right"
+constexpr int kMaxW = rowfill::kFillMaxW;                   // dRm / dL row + two int per quad: 48 KiB of LDS at most
+static_assert(kThreads == rowfill::kFillThreads, "k_lr_check runs rowfill::fill_row");
+using rowfill::aligned16;
+using rowfill::kNone;
+using rowfill::stage_row;
+using rowfill::store_quad;
 
 struct LrMaps {                                             // the nmaps stage maps of one call, by value in the kernel arguments
     const float *dl[4];
@@ -22,8 +27,6 @@ struct LrMaps {                                             // the nmaps stage m
     uint8_t *mask[4];
     float *right[4];
 };
-
-__device__ __forceinline__ bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 // 1 = consistent, 0 = inconsistent (or NaN), 2 = the matching right pixel x - d is outside the right camera's view (incl. +-inf)
 __device__ __forceinline__ int lr_code(float d, int x, int W, const float *__restrict__ R, float tau)
@@ -36,32 +39,6 @@ __device__ __forceinline__ int lr_code(float d, int x, int W, const float *__res
     const float a = t - (float)i0;
     const float r = R[i0] + a * (R[i1] - R[i0]);
     return fabsf(d - r) <= tau ? 1 : 0;                     // NaN r -> 0
-}
-
-// Stage `n` floats of a row into LDS: float4 where the row is 16-byte aligned, scalar for a misaligned row and the tail.
-__device__ __forceinline__ void stage_row(float *__restrict__ dst, const float *__restrict__ src, int W, int nq)
-{
-    const bool vec = aligned16(src);
-    for (int q = threadIdx.x; q < nq; q += kThreads) {
-        const int x = 4 * q;
-        if (vec && x + 4 <= W) {
-            *reinterpret_cast<float4 *>(dst + x) = *reinterpret_cast<const float4 *>(src + x);
-        } else {
-            for (int i = 0; i < 4 && x + i < W; ++i) dst[x + i] = src[x + i];
-        }
-    }
-}
-
-__device__ __forceinline__ void store_quad(float *__restrict__ p, int x, int W, bool vec, float v0, float v1, float v2, float v3)
-{
-    if (vec && x + 4 <= W) {
-        *reinterpret_cast<float4 *>(p + x) = make_float4(v0, v1, v2, v3);
-    } else {
-        const float v[4] = {v0, v1, v2, v3};
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if (x + i < W) p[x + i] = v[i];
-    }
 }
 
 // grid (H, B, nmaps), 256 threads: one workgroup per row.  Thread t owns the quads t, t + 256, ... (pixels 4q .. 4q + 3) of the
@@ -138,68 +115,9 @@ __global__ __launch_bounds__(kThreads) void k_lr_check(LrMaps m, int H, int W, f
         __syncthreads();                                    // every read of the staged dRm row is done
         stage_row(s_row, dl, W, nq);                        // the left-view row, for the fill values
 
-        // ---- phase 2: inclusive max-scan of last (left to right), inclusive min-scan of first (right to left) over the quads:
-        // each thread a contiguous chunk of quads, the chunks' aggregates across the wave by shuffles, across waves through LDS
-        const int per = (nq + kThreads - 1) / kThreads;
-        const int q0 = min(t * per, nq), q1 = min(q0 + per, nq);
-        int agg_l = -1, agg_f = kNone;
-        for (int j = q0; j < q1; ++j) {
-            agg_l = max(agg_l, s_last[j]);
-            agg_f = min(agg_f, s_first[j]);
-        }
-        int inc_l = agg_l, inc_f = agg_f;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int vl = __shfl_up(inc_l, o, 64), vf = __shfl_down(inc_f, o, 64);
-            inc_l = lane >= o ? max(inc_l, vl) : inc_l;
-            inc_f = lane + o < 64 ? min(inc_f, vf) : inc_f;
-        }
-        if (lane == 63) s_wl[wave] = inc_l;
-        if (lane == 0) s_wf[wave] = inc_f;
-        int exc_l = __shfl_up(inc_l, 1, 64), exc_f = __shfl_down(inc_f, 1, 64);
-        exc_l = lane == 0 ? -1 : exc_l;
-        exc_f = lane == 63 ? kNone : exc_f;
-        __syncthreads();
-        for (int w = 0; w < kWaves; ++w) {
-            exc_l = w < wave ? max(exc_l, s_wl[w]) : exc_l;
-            exc_f = w > wave ? min(exc_f, s_wf[w]) : exc_f;
-        }
-        for (int j = q0; j < q1; ++j) {
-            exc_l = max(exc_l, s_last[j]);
-            s_last[j] = exc_l;
-        }
-        for (int j = q1 - 1; j >= q0; --j) {
-            exc_f = min(exc_f, s_first[j]);
-            s_first[j] = exc_f;
-        }
-        __syncthreads();
-
-        // ---- phase 3: consistent pixels keep d, the others min(d at the nearest consistent pixel on the left, on the right); one
-        // side only: that side's value; neither: 0.  Ties keep the left value.
-        for (int k = 0, q = t; q < nq; ++k, q += kThreads) {
-            const int x = 4 * q;
-            const unsigned cb = bits >> (4 * k);
-            int prev = q > 0 ? s_last[q - 1] : -1;
-            int nxt[4];
-            int n = q + 1 < nq ? s_first[q + 1] : kNone;
-#pragma unroll
-            for (int i = 3; i >= 0; --i) {
-                n = (cb >> i) & 1 ? x + i : n;
-                nxt[i] = n;
-            }
-            float v[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if ((cb >> i) & 1) {
-                    prev = x + i;
-                    v[i] = s_row[x + i];
-                } else {
-                    const float vl = prev >= 0 ? s_row[prev] : 0.0f;
-                    const float vr = nxt[i] != kNone ? s_row[nxt[i]] : 0.0f;
-                    v[i] = prev >= 0 ? (nxt[i] != kNone ? (vr < vl ? vr : vl) : vl) : (nxt[i] != kNone ? vr : 0.0f);
-                }
-            }
-            store_quad(out, x, W, vout, v[0], v[1], v[2], v[3]);
-        }
+        // ---- phases 2 and 3 (lws_rowfill.h): scans of last / first over the quads, then consistent pixels keep d and the others
+        // take the background value of their row
+        rowfill::fill_row(s_row, s_last, s_first, s_wl, s_wf, bits, nq, W, out, vout);
     }
     if (row_kept) {
         __syncthreads();

@@ -23,6 +23,10 @@ StereoPairs[i]); every batch is one lws_pool job of B pairs; the metric kernel r
 
 `--lr_check TAU [--lr_fill]` (not in the reference; sequential mode only): the lines score LWSNet.forward_lr's checked maps, and one
 more line gives the per-stage mean density of consistent pixels.
+
+`--speckle SIZE [--speckle_diff D] [--speckle_fill]` (not in the reference; sequential mode only): the lines score the maps after
+lws_speckle_filter (behind the left-right check when both are on: the check runs unfilled, and `--speckle_fill` or `--lr_fill` fills
+what either dropped), and one more line gives the per-stage mean density of kept pixels.
 """
 import argparse
 import contextlib
@@ -35,7 +39,8 @@ import time
 import numpy as np
 
 from . import pipeline
-from .inference import add_lr_arguments, add_model_arguments, check_lr_arguments, load_model, start_logging
+from .inference import (add_lr_arguments, add_model_arguments, add_speckle_arguments, check_lr_arguments, check_speckle_arguments,
+                        load_model, speckle_stages, start_logging)
 
 STAGES = 4
 KITTI_MAXDISP = 192                     # error_estimating's default (finetune.py:212), which test() never overrides
@@ -130,15 +135,19 @@ def _row_offset(H, Hg):
     return H - Hg
 
 
-def _sequential(model, dataset, mode, batches, maxdisp, lr=None):
+def _sequential(model, dataset, mode, batches, maxdisp, lr=None, sp=None):
     """StereoPairs[i] -> model(left, right) on the batch -> lws_stage_metrics, one batch after the other.  A generator like
     _pipelined: "start" after a warm-up forward, then (counts, abs_sum) per batch.  lr = (tau, fill): the metric scores the
-    checked maps of LWSNet.forward_lr instead, and each item gains the batch's density [4,b]."""
+    checked maps of LWSNet.forward_lr instead, and each item gains the batch's density [4,b].  sp = (size, diff, fill): the maps go
+    through ops.speckle_filter first (the check then runs unfilled and `fill` covers both), and each item gains the batch's kept
+    density [4,b]."""
     import torch
     from . import ops
     dev = model.device
     H, W = dataset[batches[0][0]][0].shape[1:]
     x = np.zeros((len(batches[0]), 3, H, W), np.float32)
+    if sp is not None and lr is not None:
+        lr = (lr[0], False)
     if lr is None:
         model(x, x)                                     # warm-up outside the clock: workspace for the largest batch
     else:
@@ -155,12 +164,13 @@ def _sequential(model, dataset, mode, batches, maxdisp, lr=None):
         else:
             res = model.forward_lr(left, right, *lr)
             preds, density = res.disp, res.density
+        extra = [] if density is None else [density]
+        if sp is not None:
+            preds, _, sp_counts = speckle_stages(preds, None if lr is None else res.mask, *sp)
+            extra.append(sp_counts[:, :, 1].cpu().numpy() / float(H * W))
         with torch.cuda.device(dev):
             counts, sums = ops.stage_metrics(preds, gt, _row_offset(left.shape[2], gt.shape[1]), maxdisp, mode)
-            if density is None:
-                yield counts.cpu().numpy(), sums.cpu().numpy()
-            else:
-                yield counts.cpu().numpy(), sums.cpu().numpy(), density
+            yield (counts.cpu().numpy(), sums.cpu().numpy(), *extra)
 
 
 def _decode_pair(dataset, shape, views, j, index):
@@ -267,16 +277,20 @@ def _pipelined(model, dataset, mode, batches, maxdisp, workers, gpu_workers):
 
 
 def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, workers=0, gpu_workers=2, log=None, lr_check=None,
-             lr_fill=False):
+             lr_fill=False, speckle=None, speckle_diff=1.0, speckle_fill=False):
     """Runs the reference's test loop for `metric` ("kitti": finetune.py's 3-pixel error, "epe": train.py's EPE) over
     `dataset` (a StereoPairs with training=False).  maxdisp is the mask bound (the KITTI loop uses 192, see KITTI_MAXDISP).
     Returns a dict: per-stage averages at full precision, per-batch values, per-image counts and sums, pairs, wall time, pairs/s.
     lr_check = TAU (sequential mode only): the metric scores the maps of LWSNet.forward_lr(tau=TAU, fill=lr_fill), and the dict
-    gains lr_tau and lr_density, the per-stage mean over the pairs of the fraction of consistent pixels."""
+    gains lr_tau and lr_density, the per-stage mean over the pairs of the fraction of consistent pixels.  speckle = SIZE (sequential
+    mode only): the maps go through ops.speckle_filter(SIZE, speckle_diff, fill=speckle_fill or lr_fill) before they are scored, and
+    the dict gains speckle_size, speckle_diff and speckle_density, the per-stage mean over the pairs of kept pixels / (H*W)."""
     if metric not in ("kitti", "epe"):
         raise ValueError(f"metric must be 'kitti' or 'epe', got {metric!r}")
     if lr_check is not None and workers > 0:
         raise ValueError("the left-right check runs in the sequential mode only (workers = 0)")
+    if speckle is not None and workers > 0:
+        raise ValueError("the speckle filter runs in the sequential mode only (workers = 0)")
     if batch_size < 1:
         raise ValueError("batch_size must be >= 1")
     n = len(dataset)
@@ -288,11 +302,12 @@ def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, worker
     meters = Meters(metric, len(batches))
     per_image = {"valid": [], "bad": [], "abs_sum": []}
     lr = None if lr_check is None else (float(lr_check), bool(lr_fill))
-    densities = []
+    sp = None if speckle is None else (int(speckle), float(speckle_diff), bool(speckle_fill or lr_fill))
+    densities, sp_densities = [], []
     if workers > 0:
         it = _pipelined(model, dataset, metric, batches, maxdisp, workers, gpu_workers)
     else:
-        it = _sequential(model, dataset, metric, batches, maxdisp, lr)
+        it = _sequential(model, dataset, metric, batches, maxdisp, lr, sp)
     if next(it) != "start":
         raise RuntimeError("the evaluation did not start")
     t0 = time.perf_counter()
@@ -300,6 +315,8 @@ def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, worker
         counts, sums = item[0], item[1]
         if lr is not None:
             densities.append(item[2])
+        if sp is not None:
+            sp_densities.append(item[-1])
         line = meters.update(k, counts, sums, files[k])
         if line is not None:
             log.info(line)
@@ -319,6 +336,13 @@ def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, worker
                  + ", ".join("Stage {}={:.4f}".format(x, d) for x, d in enumerate(density)))
         res["lr_tau"] = lr[0]
         res["lr_density"] = [float(d) for d in density]
+    if sp is not None:
+        density = np.concatenate(sp_densities, axis=1).mean(axis=1)        # [4]: mean over the pairs
+        log.info("Speckle filter (size <= {}, diff <= {:g}{}): mean kept density ".format(sp[0], sp[1], ", filled" if sp[2] else "")
+                 + ", ".join("Stage {}={:.4f}".format(x, d) for x, d in enumerate(density)))
+        res["speckle_size"] = sp[0]
+        res["speckle_diff"] = sp[1]
+        res["speckle_density"] = [float(d) for d in density]
     return res
 
 
@@ -339,6 +363,7 @@ def build_parser():
     p.add_argument("--gpu_workers", type=int, default=2, help="with --workers: batches kept in flight by lws_pool")
     p.add_argument("--json", type=str, default=None, help="write the result (full-precision numbers) to this file")
     add_lr_arguments(p)
+    add_speckle_arguments(p)
     return p
 
 
@@ -359,11 +384,13 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     check_lr_arguments(parser, args)
+    check_speckle_arguments(parser, args)
     log = start_logging("lwsnet_amd.evaluate", args)
     dataset, metric, maxdisp = load_dataset(args)
     model = load_model(args, log, missing_status=1)
     res = evaluate(model, dataset, metric, batch_size=args.test_batch_size, maxdisp=maxdisp, workers=args.workers,
-                   gpu_workers=args.gpu_workers, log=log, lr_check=args.lr_check, lr_fill=args.lr_fill)
+                   gpu_workers=args.gpu_workers, log=log, lr_check=args.lr_check, lr_fill=args.lr_fill, speckle=args.speckle,
+                   speckle_diff=args.speckle_diff, speckle_fill=args.speckle_fill)
     res["dataset"] = args.dataset
     log.info("%d pairs in %.3f s: %.2f pairs/s", res["pairs"], res["wall_s"], res["pairs_per_s"])
     if args.json:

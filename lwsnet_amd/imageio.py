@@ -121,11 +121,12 @@ def save_png(path, rgb):
         f.write(encode_png(rgb))
 
 
-LR_MASK_GREY = np.array([0, 255, 128], np.uint8)   # lws_lr_check code 0 (inconsistent), 1 (consistent), 2 (out of view)
+# lws_lr_check code 0 (inconsistent), 1 (consistent), 2 (out of view); lws_speckle_filter adds 3 (speckle)
+LR_MASK_GREY = np.array([0, 255, 128, 64], np.uint8)
 
 
 def save_lr_mask_png(path, code):
-    """[H,W] uint8 left-right check codes -> 8-bit grey PNG: 1 -> 255, 0 -> 0, 2 -> 128."""
+    """[H,W] uint8 left-right check / speckle filter codes -> 8-bit grey PNG: 1 -> 255, 0 -> 0, 2 -> 128, 3 -> 64."""
     with open(path, "wb") as f:
         f.write(encode_png_gray(LR_MASK_GREY[np.asarray(code, np.uint8)]))
 

@@ -26,6 +26,13 @@ and each gets a grey mask `<stem>_lr.png` beside it (consistent 255, inconsisten
 (lws_depth_maps / lws_point_cloud).  Depth and points need a camera: `--calib` (a KITTI calibration file, or in directory mode a
 folder of them named after the frames) or `--camera FX FY CX CY BASELINE` in the uncropped image's pixels; it is cropped as the
 images are.  With `--lr_check` they use the checked maps: without `--lr_fill` only consistent pixels are kept.
+
+`--speckle SIZE [--speckle_diff D] [--speckle_fill]` (not in the reference; sequential mode only): the connected blobs of at most
+SIZE pixels (4-neighbours joined when their disparities differ by <= D, default 1) are removed from the stage maps on the device
+(lws_speckle_filter) before the colour, 16-bit and point-cloud files are written, and each colour file gets a grey code map
+`<stem>_sp.png` beside it (kept 255, speckle 64, the left-right check's 0 / 128 where it dropped the pixel).  With `--lr_check` the
+filter runs on the unfilled checked maps and their masks; `--speckle_fill` or `--lr_fill` then fills every dropped pixel with its
+row's background value.
 """
 import argparse
 import contextlib
@@ -59,6 +66,7 @@ def build_parser():
                         "reference's sequential loop; not in the reference)")
     p.add_argument("--gpu_workers", type=int, default=3, help="with --workers: forwards kept in flight by lws_pool")
     add_lr_arguments(p)
+    add_speckle_arguments(p)
     add_geometry_arguments(p)
     return p
 
@@ -130,6 +138,47 @@ def add_lr_arguments(p):
                    help="left-right consistency check: keep the pixels whose left- and right-view disparities differ by <= TAU "
                         "(sequential mode only; not in the reference)")
     p.add_argument("--lr_fill", action="store_true", help="with --lr_check: fill the dropped pixels with their row's background value")
+
+
+def add_speckle_arguments(p):
+    """--speckle SIZE / --speckle_diff D / --speckle_fill (not in the reference; shared with lwsnet_amd.evaluate): ops.speckle_filter."""
+    p.add_argument("--speckle", type=int, default=None, metavar="SIZE",
+                   help="speckle filter: remove the connected blobs of at most SIZE pixels from the disparity maps (sequential mode "
+                        "only; not in the reference)")
+    p.add_argument("--speckle_diff", type=float, default=None, metavar="D",
+                   help="with --speckle: neighbours are connected when their disparities differ by <= D (default 1.0)")
+    p.add_argument("--speckle_fill", action="store_true",
+                   help="with --speckle: fill the removed pixels with their row's background value")
+
+
+def check_speckle_arguments(p, args):
+    """Rejects what the speckle filter does not support, before any model or GPU work; sets the default of --speckle_diff."""
+    if args.speckle is None:
+        if args.speckle_fill or args.speckle_diff is not None:
+            p.error("--speckle_fill and --speckle_diff need --speckle SIZE")
+        return
+    if args.speckle_diff is None:
+        args.speckle_diff = 1.0
+    if args.speckle <= 0 or args.speckle >= 2 ** 31:
+        p.error(f"--speckle SIZE must be an integer > 0, got {args.speckle}")
+    if not np.isfinite(args.speckle_diff) or args.speckle_diff < 0:
+        p.error(f"--speckle_diff D must be finite and >= 0, got {args.speckle_diff}")
+    if args.workers > 0:
+        p.error("--speckle runs in the sequential mode only: use --workers 0")
+
+
+def speckle_stages(disp, masks, size, diff, fill):
+    """ops.speckle_filter on the four stage maps of one forward ([B,1,H,W] each, concatenated along B: every image is filtered on
+    its own) with the left-right check's masks (or None).  Returns (filtered maps, code maps, counts [4,B,3] on the device)."""
+    import torch
+    from . import ops
+    from .models import DisparityTensor
+    B = disp[0].shape[0]
+    with torch.cuda.device(disp[0].device):
+        res = ops.speckle_filter(torch.cat([d.as_subclass(torch.Tensor) for d in disp]), size, diff,
+                                 torch.cat(list(masks)) if masks is not None else None, fill=fill)
+    return ([DisparityTensor.wrap(res.disp[s * B:(s + 1) * B]) for s in range(4)], [res.mask[s * B:(s + 1) * B] for s in range(4)],
+            res.counts.view(4, B, 3))
 
 
 def add_model_arguments(p):
@@ -319,22 +368,32 @@ def inference(model, left_imgs, right_imgs, args, log):
     written = []
     warm = False
     lr = getattr(args, "lr_check", None) is not None
+    sp = getattr(args, "speckle", None) is not None
+    filled = getattr(args, "lr_fill", False) or (sp and args.speckle_fill)     # no mask for the geometry files of a filled map
     geo = getattr(args, "save_disp16", False) or getattr(args, "save_depth", False) or getattr(args, "save_ply", False)
 
-    def run(l_in, r_in):
+    def run(l_in, r_in):                                                # -> stage maps, LR masks, codes to keep == 1 of, speckle codes
         if not lr:
-            return model(l_in, r_in), None
-        res = model.forward_lr(l_in, r_in, tau=args.lr_check, fill=args.lr_fill)     # colour files from the checked maps
-        return res.disp, res.mask
+            disp, lr_masks = model(l_in, r_in), None
+        else:                                                           # colour files from the checked maps
+            res = model.forward_lr(l_in, r_in, tau=args.lr_check, fill=args.lr_fill and not sp)
+            disp, lr_masks = res.disp, res.mask
+        if not sp:
+            return disp, lr_masks, lr_masks, None
+        disp, sp_masks, _ = speckle_stages(disp, lr_masks, args.speckle, args.speckle_diff, filled)
+        return disp, lr_masks, sp_masks, sp_masks
 
     def save(path, color, stage):                                       # the colour file, then the mask and geometry files beside it
         io.save_png(path, color)
         written.append(path)
         log.info("{}\t\tSave img = {}".format(ss, path))
         if lr:
-            written.append(_save_lr_mask(path, masks[stage], log))
+            written.append(_save_lr_mask(path, lr_masks[stage], log))
+        if sp:
+            written.append(_save_sp_mask(path, sp_masks[stage], log))
         if geo:
-            written.extend(_save_geometry(path, outputs[stage], masks[stage] if lr and not args.lr_fill else None, cam, left, args, log))
+            written.extend(_save_geometry(path, outputs[stage], masks[stage] if masks is not None and not filled else None, cam, left,
+                                          args, log))
 
     for li, ri in zip(left_imgs, right_imgs):
         full = io.load_rgb(li)
@@ -349,7 +408,7 @@ def inference(model, left_imgs, right_imgs, args, log):
             warm = True
         torch.cuda.synchronize(model.device)
         t0 = time.time()
-        outputs, masks = run(l_in, r_in)
+        outputs, lr_masks, masks, sp_masks = run(l_in, r_in)
         torch.cuda.synchronize(model.device)
         cost = time.time() - t0
         ss = "Inference 4 stages cost = {:.3f} sec, FPS = {:.1f}".format(cost, 1 / cost)
@@ -412,10 +471,21 @@ def _save_lr_mask(path, mask, log):
     return mpath
 
 
+def _save_sp_mask(path, mask, log):
+    """The speckle filter's codes of the map written to `path`, as the grey PNG <stem>_sp.png next to it."""
+    code = mask[0, 0].cpu().numpy()
+    mpath = os.path.splitext(path)[0] + "_sp.png"
+    io.save_lr_mask_png(mpath, code)
+    log.info("Speckle filter: kept = {:.4f}, removed = {:.4f}\t\tSave codes = {}".format(float((code == 1).mean()),
+                                                                                      float((code == 3).mean()), mpath))
+    return mpath
+
+
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     check_lr_arguments(parser, args)
+    check_speckle_arguments(parser, args)
     check_geometry_arguments(parser, args)
     log = start_logging("lwsnet_amd.inference", args)
     model = load_model(args, log)

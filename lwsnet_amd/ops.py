@@ -7,6 +7,7 @@ tensors must live on a HIP device.
 from __future__ import annotations
 
 import ctypes
+from collections import namedtuple
 
 import torch
 
@@ -372,3 +373,43 @@ def point_cloud(disp, cameras, mask=None, rgb=None, min_disp=1.0, max_depth=floa
         _lib.check(lib.lws_point_cloud(_ptr(d), _ptr(mask), _ptr(rgb), _ptr(cam), B, H, W, float(min_disp), float(max_depth), _ptr(work),
                                        _ptr(points), _ptr(counts), _stream()), "lws_point_cloud")
     return points, counts
+
+
+SpeckleResult = namedtuple("SpeckleResult", ["disp", "mask", "labels", "counts"])
+SpeckleResult.__doc__ = """What speckle_filter returns: the filtered (filled if asked) maps float32 [B,1,H,W], the uint8 code map (1 kept,
+3 speckle, the input code or 0 for an invalid pixel), labels int32 [B,1,H,W] (None unless want_labels) and counts, an int64
+[B,3] device tensor {valid pixels, kept pixels, removed components}."""
+
+
+def speckle_filter(disp, max_size, max_diff=1.0, mask=None, fill=False, want_labels=False):
+    """Removes the connected blobs of at most `max_size` pixels from disparity maps (include/lwsnet_hip.h, lws_speckle_filter:
+    4-neighbours are joined iff their float32 disparities differ by <= max_diff).  disp [B,1,H,W] float32 (four stage maps:
+    torch.cat them along B, every image is filtered on its own); mask: None or the uint8 lws_lr_check code map (only code-1
+    pixels are valid); fill: give the removed and invalid pixels the background value of their row.  The workspace (8 bytes per
+    pixel) and the outputs are allocated per call on the current stream.  Returns a SpeckleResult."""
+    import math
+    d = _dev(disp, "disp")
+    if d.dim() != 4 or d.shape[1] != 1:
+        raise ValueError(f"disp must be [B,1,H,W]; got {tuple(d.shape)}")
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or tuple(mask.shape) != tuple(d.shape) or mask.device != d.device:
+            raise ValueError(f"mask must be a uint8 {tuple(d.shape)} tensor on {d.device} (the lws_lr_check code map)")
+        mask = mask.contiguous()
+    if not (math.isfinite(max_diff) and max_diff >= 0):
+        raise ValueError(f"max_diff must be finite and >= 0, got {max_diff}")
+    if int(max_size) != max_size or max_size < 0 or max_size >= 2 ** 31:
+        raise ValueError(f"max_size must be an integer in 0 .. 2^31 - 1, got {max_size}")
+    B, _, H, W = d.shape
+    lib = _lib.load()
+    nbytes = int(lib.lws_speckle_workspace(B, H, W))
+    if nbytes < 0:
+        _lib.check(nbytes, "lws_speckle_workspace")
+    work = torch.empty((nbytes,), device=d.device, dtype=torch.uint8)
+    out = torch.empty_like(d)
+    mask_out = torch.empty(d.shape, device=d.device, dtype=torch.uint8)
+    labels = torch.empty(d.shape, device=d.device, dtype=torch.int32) if want_labels else None
+    counts = torch.empty((B, 3), device=d.device, dtype=torch.int64)
+    with torch.cuda.device(d.device):
+        _lib.check(lib.lws_speckle_filter(_ptr(d), _ptr(mask), B, H, W, float(max_diff), int(max_size), int(bool(fill)), _ptr(work),
+                                          _ptr(out), _ptr(mask_out), _ptr(labels), _ptr(counts), _stream()), "lws_speckle_filter")
+    return SpeckleResult(out, mask_out, labels, counts)
