@@ -329,6 +329,16 @@ const char *lws_kernel_class_name(int kernel_class);
  * or rank that holds a lower clock shows up there, not as an unexplained slower step.  LWS_ERR_STATE when stage 1's C3 is 8. */
 int lws_clock_stamp(lws_handle h, int enable);
 int lws_clock_read(lws_handle h, double *ghz);
+/* Test hook (additive after v8): fills the handle's WHOLE current activation workspace -- the one slab lws_reserve / the first
+ * call of a geometry allocates and every later call carves up per (B, H, W) -- with the 32-bit pattern `word`, as one asynchronous
+ * 32-bit memset on `stream`.  The library never clears that slab and promises that no result depends on what it holds
+ * ("memory contract"); tests/test_gpu_memory_contract.py poisons it with a quiet NaN and with +-FLT_MAX before every
+ * call to hold the kernels to that.  Only the workspace is touched: the parameter slab and the clock buffer are left alone.
+ * LWS_ERR_INVALID unless the handle's device is the current one (the rule of every handle call), LWS_ERR_STATE when no workspace
+ * exists yet -- call lws_reserve first, at the largest geometry that will follow: a call that has to regrow the slab swaps the
+ * poison for fresh memory.  Must NOT be called while `stream` is being captured into a hipGraph (a replay would poison the
+ * slab under whatever runs then), nor while a forward of this handle is in flight on another stream. */
+int lws_debug_fill_workspace(lws_handle h, uint32_t word, void *stream);
 
 /* ---- several forwards in flight (no counterpart in the reference: inference.py:105-109 is one thread, one stream) ---- */
 /* A second handle for the same model on the same device: shares src's (read-only) parameter slab, owns its workspace,

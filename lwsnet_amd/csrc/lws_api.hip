@@ -984,6 +984,19 @@ int lws_clock_read(lws_handle h, double *ghz)
     return LWS_OK;
 }
 
+int lws_debug_fill_workspace(lws_handle h, uint32_t word, void *stream)
+{
+    LWS_CHECK_ARG(h, "lws_debug_fill_workspace: null handle");
+    LWS_CHECK_DEVICE(h, "lws_debug_fill_workspace");
+    if (!h->ws || h->ws_bytes == 0) {
+        set_error("lws_debug_fill_workspace: the handle has no workspace yet (lws_reserve first)");
+        return LWS_ERR_STATE;
+    }
+    // (the slab is a whole number of floats: ensure_ws)
+    LWS_HIP(hipMemsetD32Async((hipDeviceptr_t)h->ws, (int)word, h->ws_bytes / sizeof(uint32_t), (hipStream_t)stream));
+    return LWS_OK;
+}
+
 const char *lws_kernel_class_name(int kc)
 {
     static const char *names[LWS_KC_COUNT] = {"volume_l1_shift", "volume_l1_warp", "conv3d_first", "conv3d_mid16",
