@@ -241,6 +241,38 @@ int64_t lws_speckle_workspace(int B, int H, int W);
 int lws_speckle_filter(const float *disp, const uint8_t *mask, int B, int H, int W, float max_diff, int max_size, int fill,
                        void *workspace, float *out, uint8_t *mask_out, int32_t *labels, int64_t *counts, void *stream);
 
+/* ---- edge-aware weighted median filter of a disparity map (additive after v8) ---- */
+/* Smooths a disparity map and fills its small holes without smearing across colour edges: every pixel takes the lower weighted
+ * median of the valid disparities in its window, the integer weights coming from the colour distance to the window's centre in
+ * the left image.  disp, out float32 [B,1,H,W]; mask (NULL: every pixel) uint8 [B,1,H,W], the lws_lr_check / lws_speckle_filter
+ * code map; rgb (NULL: the unweighted median -- every weight is 1 and wlut is ignored) uint8 [B,H,W,3], the guide: the cropped left
+ * image in the layout lws_point_cloud takes; wlut uint16 [766] in device memory, required when rgb is not NULL (Python:
+ * lwsnet_amd.ops.wmedian_lut); radius 1, 2 or 3 (windows of 3x3, 5x5, 7x7); fill_min >= 0 (0: holes are not filled); counts (NULL:
+ * skipped) int64 [B][2]; any H, W > 0 with H*W < 2^31, B <= 65535.  Per image, d_q = disp[b,0,qy,qx]:
+ *   valid(q)    = (mask == NULL || mask[q] == 1) && isfinite(d_q) && d_q > 0.0f              (the rule of lws_speckle_filter)
+ *   window of p = the pixels q with |qx - px| <= radius and |qy - py| <= radius that lie inside the image (the window is clipped
+ *                 at the border; nothing is replicated or mirrored)
+ *   s(p,q)      = |r_p - r_q| + |g_p - g_q| + |b_p - b_q|                                    (0 .. 765, on the uint8 guide)
+ *   w(p,q)      = rgb ? wlut[s(p,q)] : 1
+ *   candidates  = the valid q of the window with w(p,q) > 0 (a valid p is its own candidate when wlut[0] > 0);  n(p) = their number,
+ *                 T(p) = the sum of their weights (int32: 49 x 65535 fits)
+ *   m(p)        = the smallest candidate value v with 2 * sum{w(p,q) : q a candidate, d_q <= v} >= T(p): the LOWER weighted median
+ *                 (float32 compares and integer sums only, so the order in which candidates are visited cannot show; with equal
+ *                 weights and odd n the ordinary median, with even n the lower of the two middle values)
+ *   out[p]      = valid p:   m(p), or d_p itself when T(p) == 0
+ *                 invalid p: m(p) when fill_min > 0 && n(p) >= fill_min, else 0.0f
+ *   counts[b]   = {valid pixels whose out bits differ from their disp bits, invalid pixels that were filled}
+ * No code map is written: the filter never changes which pixels are trusted, and a filled pixel keeps its input code (as with the
+ * row fill, pass no mask to lws_depth_maps / lws_point_cloud for a filled map).  Every output is a pure function of the image: the
+ * same bytes in any batch, at any position in it, on every run (no float atomics; the counts are integer adds, whose order
+ * cannot show).  out must not overlap disp (a neighbourhood is read); an overlap between any two of disp, mask, rgb, wlut, out,
+ * counts that involves an output (out, counts) returns LWS_ERR_INVALID, as every argument error does -- radius outside 1..3,
+ * fill_min < 0, rgb without wlut, NULL disp or out, sizes outside the limits -- before any GPU call.  One launch on `stream` plus
+ * one (clearing counts) when counts is requested: a fixed list that does not depend on the data, with no device-to-host read, so
+ * the call can be captured into a hipGraph.  No workspace and no scratch memory. */
+int lws_wmedian_filter(const float *disp, const uint8_t *mask, const uint8_t *rgb, const uint16_t *wlut, int B, int H, int W, int radius,
+                       int fill_min, float *out, int64_t *counts, void *stream);
+
 /* Launch-plan options of lws_forward / lws_disparity_stages.  They change which kernels / streams carry the work, never
  * the arithmetic: every setting returns the same bits (tests/test_gpu_parity.py::test_forward_schedule_options) -- except
  * the opt-in numerics mode "split_bf16".  (ABI v8 removed the options two rounds of sweeps had retired: left_at, split_heads,

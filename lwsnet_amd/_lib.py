@@ -53,6 +53,7 @@ PROTOTYPES = {
     "lws_point_cloud": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp]),
     "lws_speckle_workspace": (ctypes.c_int64, [_i, _i, _i]),
     "lws_speckle_filter": (_i, [_vp, _vp, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lws_wmedian_filter": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "lws_set_option": (_i, [_vp, ctypes.c_char_p, _i]),
     "lws_get_option": (_i, [_vp, ctypes.c_char_p, ctypes.POINTER(_i)]),
     "lws_profile_enable": (_i, [_vp, _i]),

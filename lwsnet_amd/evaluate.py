@@ -27,6 +27,11 @@ more line gives the per-stage mean density of consistent pixels.
 `--speckle SIZE [--speckle_diff D] [--speckle_fill]` (not in the reference; sequential mode only): the lines score the maps after
 lws_speckle_filter (behind the left-right check when both are on: the check runs unfilled, and `--speckle_fill` or `--lr_fill` fills
 what either dropped), and one more line gives the per-stage mean density of kept pixels.
+
+`--wmedian R [--wmedian_sigma S] [--wmedian_fill N]` (not in the reference; sequential mode only): the lines score the maps after
+lws_wmedian_filter, the last step in front of the metric (behind the check and the speckle filter when they are on, with their code
+map while their maps are unfilled); the guide is the batch's uint8 left images, uploaded once and normalised on the device
+(lws_preprocess_rgb8), and one more line gives the per-stage mean fraction of pixels the filter changed or filled.
 """
 import argparse
 import contextlib
@@ -39,8 +44,8 @@ import time
 import numpy as np
 
 from . import pipeline
-from .inference import (add_lr_arguments, add_model_arguments, add_speckle_arguments, check_lr_arguments, check_speckle_arguments,
-                        load_model, speckle_stages, start_logging)
+from .inference import (add_lr_arguments, add_model_arguments, add_speckle_arguments, add_wmedian_arguments, check_lr_arguments,
+                        check_speckle_arguments, check_wmedian_arguments, load_model, speckle_stages, start_logging, wmedian_stages)
 
 STAGES = 4
 KITTI_MAXDISP = 192                     # error_estimating's default (finetune.py:212), which test() never overrides
@@ -135,12 +140,14 @@ def _row_offset(H, Hg):
     return H - Hg
 
 
-def _sequential(model, dataset, mode, batches, maxdisp, lr=None, sp=None):
+def _sequential(model, dataset, mode, batches, maxdisp, lr=None, sp=None, wm=None):
     """StereoPairs[i] -> model(left, right) on the batch -> lws_stage_metrics, one batch after the other.  A generator like
     _pipelined: "start" after a warm-up forward, then (counts, abs_sum) per batch.  lr = (tau, fill): the metric scores the
     checked maps of LWSNet.forward_lr instead, and each item gains the batch's density [4,b].  sp = (size, diff, fill): the maps go
     through ops.speckle_filter first (the check then runs unfilled and `fill` covers both), and each item gains the batch's kept
-    density [4,b]."""
+    density [4,b].  wm = (radius, sigma, fill_min): the maps go through ops.wmedian_filter last, with the code map of the steps
+    before it unless they filled their maps, and each item gains the batch's changed + filled fraction [4,b]; with sigma > 0 the
+    batch is read as bytes (StereoPairs.raw), uploaded once and normalised on the device, and its left images are the guide."""
     import torch
     from . import ops
     dev = model.device
@@ -155,9 +162,17 @@ def _sequential(model, dataset, mode, batches, maxdisp, lr=None, sp=None):
     torch.cuda.synchronize(dev)
     yield "start"
     for rng in batches:
-        items = [dataset[i] for i in rng]
-        left = np.stack([it[0] for it in items])
-        right = np.stack([it[1] for it in items])
+        guide = None
+        if wm is not None and wm[1] > 0:
+            items = [dataset.raw(i) for i in rng]
+            with torch.cuda.device(dev):
+                u8 = torch.from_numpy(np.stack([it[0] for it in items] + [it[1] for it in items])).to(dev)
+                both = ops.preprocess_rgb8(u8)                  # bit for bit StereoPairs[i]
+            left, right, guide = both[:len(items)], both[len(items):], u8[:len(items)]
+        else:
+            items = [dataset[i] for i in rng]
+            left = np.stack([it[0] for it in items])
+            right = np.stack([it[1] for it in items])
         gt = torch.from_numpy(np.ascontiguousarray(np.stack([it[2] for it in items]), dtype=np.float32)).to(dev)
         if lr is None:
             preds, density = model(left, right), None
@@ -166,8 +181,13 @@ def _sequential(model, dataset, mode, batches, maxdisp, lr=None, sp=None):
             preds, density = res.disp, res.density
         extra = [] if density is None else [density]
         if sp is not None:
-            preds, _, sp_counts = speckle_stages(preds, None if lr is None else res.mask, *sp)
+            preds, sp_masks, sp_counts = speckle_stages(preds, None if lr is None else res.mask, *sp)
             extra.append(sp_counts[:, :, 1].cpu().numpy() / float(H * W))
+        if wm is not None:
+            row_filled = (lr is not None and lr[1]) or (sp is not None and sp[2])
+            keep = sp_masks if sp is not None else (None if lr is None else res.mask)
+            preds, wm_counts = wmedian_stages(preds, None if row_filled else keep, guide, *wm)
+            extra.append(wm_counts.sum(dim=2).cpu().numpy() / float(H * W))
         with torch.cuda.device(dev):
             counts, sums = ops.stage_metrics(preds, gt, _row_offset(left.shape[2], gt.shape[1]), maxdisp, mode)
             yield (counts.cpu().numpy(), sums.cpu().numpy(), *extra)
@@ -277,20 +297,28 @@ def _pipelined(model, dataset, mode, batches, maxdisp, workers, gpu_workers):
 
 
 def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, workers=0, gpu_workers=2, log=None, lr_check=None,
-             lr_fill=False, speckle=None, speckle_diff=1.0, speckle_fill=False):
+             lr_fill=False, speckle=None, speckle_diff=1.0, speckle_fill=False, wmedian=None, wmedian_sigma=10.0, wmedian_fill=0):
     """Runs the reference's test loop for `metric` ("kitti": finetune.py's 3-pixel error, "epe": train.py's EPE) over
     `dataset` (a StereoPairs with training=False).  maxdisp is the mask bound (the KITTI loop uses 192, see KITTI_MAXDISP).
     Returns a dict: per-stage averages at full precision, per-batch values, per-image counts and sums, pairs, wall time, pairs/s.
     lr_check = TAU (sequential mode only): the metric scores the maps of LWSNet.forward_lr(tau=TAU, fill=lr_fill), and the dict
     gains lr_tau and lr_density, the per-stage mean over the pairs of the fraction of consistent pixels.  speckle = SIZE (sequential
     mode only): the maps go through ops.speckle_filter(SIZE, speckle_diff, fill=speckle_fill or lr_fill) before they are scored, and
-    the dict gains speckle_size, speckle_diff and speckle_density, the per-stage mean over the pairs of kept pixels / (H*W)."""
+    the dict gains speckle_size, speckle_diff and speckle_density, the per-stage mean over the pairs of kept pixels / (H*W).
+    wmedian = R (sequential mode only): the maps go through ops.wmedian_filter(R, the left images, ops.wmedian_lut(wmedian_sigma),
+    fill_min=wmedian_fill) last (wmedian_sigma = 0: no guide), and the dict gains wmedian_radius, wmedian_sigma, wmedian_fill and
+    wmedian_changed, the per-stage mean over the pairs of (changed + filled pixels) / (H*W)."""
     if metric not in ("kitti", "epe"):
         raise ValueError(f"metric must be 'kitti' or 'epe', got {metric!r}")
     if lr_check is not None and workers > 0:
         raise ValueError("the left-right check runs in the sequential mode only (workers = 0)")
     if speckle is not None and workers > 0:
         raise ValueError("the speckle filter runs in the sequential mode only (workers = 0)")
+    if wmedian is not None and workers > 0:
+        raise ValueError("the weighted median filter runs in the sequential mode only (workers = 0)")
+    if wmedian is not None and (not 1 <= int(wmedian) <= 3 or not (np.isfinite(wmedian_sigma) and wmedian_sigma >= 0) or wmedian_fill < 0):
+        raise ValueError(f"wmedian must be 1, 2 or 3, wmedian_sigma finite and >= 0, wmedian_fill >= 0; got {wmedian}, {wmedian_sigma}, "
+                         f"{wmedian_fill}")
     if batch_size < 1:
         raise ValueError("batch_size must be >= 1")
     n = len(dataset)
@@ -303,11 +331,12 @@ def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, worker
     per_image = {"valid": [], "bad": [], "abs_sum": []}
     lr = None if lr_check is None else (float(lr_check), bool(lr_fill))
     sp = None if speckle is None else (int(speckle), float(speckle_diff), bool(speckle_fill or lr_fill))
-    densities, sp_densities = [], []
+    wm = None if wmedian is None else (int(wmedian), float(wmedian_sigma), int(wmedian_fill))
+    densities, sp_densities, wm_changed = [], [], []
     if workers > 0:
         it = _pipelined(model, dataset, metric, batches, maxdisp, workers, gpu_workers)
     else:
-        it = _sequential(model, dataset, metric, batches, maxdisp, lr, sp)
+        it = _sequential(model, dataset, metric, batches, maxdisp, lr, sp, wm)
     if next(it) != "start":
         raise RuntimeError("the evaluation did not start")
     t0 = time.perf_counter()
@@ -316,7 +345,9 @@ def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, worker
         if lr is not None:
             densities.append(item[2])
         if sp is not None:
-            sp_densities.append(item[-1])
+            sp_densities.append(item[3 if lr is not None else 2])
+        if wm is not None:
+            wm_changed.append(item[-1])
         line = meters.update(k, counts, sums, files[k])
         if line is not None:
             log.info(line)
@@ -343,6 +374,14 @@ def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, worker
         res["speckle_size"] = sp[0]
         res["speckle_diff"] = sp[1]
         res["speckle_density"] = [float(d) for d in density]
+    if wm is not None:
+        changed = np.concatenate(wm_changed, axis=1).mean(axis=1)          # [4]: mean over the pairs
+        log.info("Weighted median (radius {}, sigma {:g}, fill {}): mean changed fraction ".format(*wm)
+                 + ", ".join("Stage {}={:.4f}".format(x, d) for x, d in enumerate(changed)))
+        res["wmedian_radius"] = wm[0]
+        res["wmedian_sigma"] = wm[1]
+        res["wmedian_fill"] = wm[2]
+        res["wmedian_changed"] = [float(d) for d in changed]
     return res
 
 
@@ -364,6 +403,7 @@ def build_parser():
     p.add_argument("--json", type=str, default=None, help="write the result (full-precision numbers) to this file")
     add_lr_arguments(p)
     add_speckle_arguments(p)
+    add_wmedian_arguments(p)
     return p
 
 
@@ -385,12 +425,14 @@ def main(argv=None):
     args = parser.parse_args(argv)
     check_lr_arguments(parser, args)
     check_speckle_arguments(parser, args)
+    check_wmedian_arguments(parser, args)
     log = start_logging("lwsnet_amd.evaluate", args)
     dataset, metric, maxdisp = load_dataset(args)
     model = load_model(args, log, missing_status=1)
     res = evaluate(model, dataset, metric, batch_size=args.test_batch_size, maxdisp=maxdisp, workers=args.workers,
                    gpu_workers=args.gpu_workers, log=log, lr_check=args.lr_check, lr_fill=args.lr_fill, speckle=args.speckle,
-                   speckle_diff=args.speckle_diff, speckle_fill=args.speckle_fill)
+                   speckle_diff=args.speckle_diff, speckle_fill=args.speckle_fill, wmedian=args.wmedian,
+                   wmedian_sigma=args.wmedian_sigma, wmedian_fill=args.wmedian_fill)
     res["dataset"] = args.dataset
     log.info("%d pairs in %.3f s: %.2f pairs/s", res["pairs"], res["wall_s"], res["pairs_per_s"])
     if args.json:

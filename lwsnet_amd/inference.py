@@ -33,6 +33,14 @@ SIZE pixels (4-neighbours joined when their disparities differ by <= D, default 
 `<stem>_sp.png` beside it (kept 255, speckle 64, the left-right check's 0 / 128 where it dropped the pixel).  With `--lr_check` the
 filter runs on the unfilled checked maps and their masks; `--speckle_fill` or `--lr_fill` then fills every dropped pixel with its
 row's background value.
+
+`--wmedian R [--wmedian_sigma S] [--wmedian_fill N]` (not in the reference; sequential mode only): the stage maps go through the
+edge-aware weighted median filter (lws_wmedian_filter: a (2R + 1)^2 window, R in 1..3, weights rint(4096 exp(-s / 3S)) of the colour
+distance s to the window's centre in the cropped left image; S = 0: the unweighted median, no guide) as the last step before the
+colour, 16-bit and point-cloud files are made, behind the left-right check and the speckle filter when they are on.  The filter
+takes their code map while their maps are unfilled (only trusted pixels vote, and with `--wmedian_fill N` a dropped pixel with at
+least N voting neighbours takes their median); a map `--lr_fill` / `--speckle_fill` has filled is filtered as a whole.  No code
+map is written: the `_lr` / `_sp` files are what they were, and the geometry files drop the mask once anything was filled.
 """
 import argparse
 import contextlib
@@ -67,6 +75,7 @@ def build_parser():
     p.add_argument("--gpu_workers", type=int, default=3, help="with --workers: forwards kept in flight by lws_pool")
     add_lr_arguments(p)
     add_speckle_arguments(p)
+    add_wmedian_arguments(p)
     add_geometry_arguments(p)
     return p
 
@@ -179,6 +188,56 @@ def speckle_stages(disp, masks, size, diff, fill):
                                  torch.cat(list(masks)) if masks is not None else None, fill=fill)
     return ([DisparityTensor.wrap(res.disp[s * B:(s + 1) * B]) for s in range(4)], [res.mask[s * B:(s + 1) * B] for s in range(4)],
             res.counts.view(4, B, 3))
+
+
+def add_wmedian_arguments(p):
+    """--wmedian R / --wmedian_sigma S / --wmedian_fill N (not in the reference; shared with lwsnet_amd.evaluate): ops.wmedian_filter."""
+    p.add_argument("--wmedian", type=int, default=None, metavar="R",
+                   help="edge-aware weighted median filter of the disparity maps over a (2R + 1)^2 window, R in 1..3, weighted by "
+                        "the left image (sequential mode only; not in the reference)")
+    p.add_argument("--wmedian_sigma", type=float, default=None, metavar="S",
+                   help="with --wmedian: colour scale of the weights in grey levels per channel (default 10.0; 0 = the unweighted "
+                        "median, no guide)")
+    p.add_argument("--wmedian_fill", type=int, default=None, metavar="N",
+                   help="with --wmedian: a dropped pixel with at least N trusted neighbours in its window takes their median "
+                        "(default 0 = holes are not filled)")
+
+
+def check_wmedian_arguments(p, args):
+    """Rejects what the weighted median filter does not support, before any model or GPU work; sets the defaults of
+    --wmedian_sigma and --wmedian_fill."""
+    if args.wmedian is None:
+        if args.wmedian_sigma is not None or args.wmedian_fill is not None:
+            p.error("--wmedian_sigma and --wmedian_fill need --wmedian R")
+        return
+    if args.wmedian_sigma is None:
+        args.wmedian_sigma = 10.0
+    if args.wmedian_fill is None:
+        args.wmedian_fill = 0
+    if not 1 <= args.wmedian <= 3:
+        p.error(f"--wmedian R must be 1, 2 or 3, got {args.wmedian}")
+    if not np.isfinite(args.wmedian_sigma) or args.wmedian_sigma < 0:
+        p.error(f"--wmedian_sigma S must be finite and >= 0, got {args.wmedian_sigma}")
+    if args.wmedian_fill < 0 or args.wmedian_fill >= 2 ** 31:
+        p.error(f"--wmedian_fill N must be an integer >= 0, got {args.wmedian_fill}")
+    if args.workers > 0:
+        p.error("--wmedian runs in the sequential mode only: use --workers 0")
+
+
+def wmedian_stages(disp, masks, rgb, radius, sigma, fill_min):
+    """ops.wmedian_filter on the four stage maps of one forward ([B,1,H,W] each, concatenated along B: every image is filtered on
+    its own) with their code maps (or None) and the guide rgb (uint8 [B,H,W,3] on the device, repeated per stage; unused when
+    sigma == 0).  Returns (filtered maps, counts [4,B,2] on the device)."""
+    import torch
+    from . import ops
+    from .models import DisparityTensor
+    B = disp[0].shape[0]
+    guided = sigma > 0
+    with torch.cuda.device(disp[0].device):
+        res = ops.wmedian_filter(torch.cat([d.as_subclass(torch.Tensor) for d in disp]), radius,
+                                 rgb=rgb.repeat(4, 1, 1, 1) if guided else None, wlut=ops.wmedian_lut(sigma) if guided else None,
+                                 mask=torch.cat(list(masks)) if masks is not None else None, fill_min=fill_min)
+    return [DisparityTensor.wrap(res.disp[s * B:(s + 1) * B]) for s in range(4)], res.counts.view(4, B, 2)
 
 
 def add_model_arguments(p):
@@ -369,19 +428,26 @@ def inference(model, left_imgs, right_imgs, args, log):
     warm = False
     lr = getattr(args, "lr_check", None) is not None
     sp = getattr(args, "speckle", None) is not None
-    filled = getattr(args, "lr_fill", False) or (sp and args.speckle_fill)     # no mask for the geometry files of a filled map
+    wm = getattr(args, "wmedian", None) is not None
+    row_filled = getattr(args, "lr_fill", False) or (sp and args.speckle_fill)
+    filled = row_filled or (wm and args.wmedian_fill > 0)              # no mask for the geometry files of a filled map
     geo = getattr(args, "save_disp16", False) or getattr(args, "save_depth", False) or getattr(args, "save_ply", False)
 
-    def run(l_in, r_in):                                                # -> stage maps, LR masks, codes to keep == 1 of, speckle codes
+    def run(l_in, r_in):                                # -> stage maps, LR masks, codes to keep == 1 of, speckle codes, median counts
         if not lr:
             disp, lr_masks = model(l_in, r_in), None
         else:                                                           # colour files from the checked maps
             res = model.forward_lr(l_in, r_in, tau=args.lr_check, fill=args.lr_fill and not sp)
             disp, lr_masks = res.disp, res.mask
-        if not sp:
-            return disp, lr_masks, lr_masks, None
-        disp, sp_masks, _ = speckle_stages(disp, lr_masks, args.speckle, args.speckle_diff, filled)
-        return disp, lr_masks, sp_masks, sp_masks
+        sp_masks = None
+        if sp:
+            disp, sp_masks, _ = speckle_stages(disp, lr_masks, args.speckle, args.speckle_diff, row_filled)
+        keep, wm_counts = sp_masks if sp else lr_masks, None
+        if wm:                                                          # the last step: a row-filled map is filtered as a whole
+            guide = torch.from_numpy(np.ascontiguousarray(left)[None]).to(model.device) if args.wmedian_sigma > 0 else None
+            disp, wm_counts = wmedian_stages(disp, None if row_filled else keep, guide, args.wmedian, args.wmedian_sigma,
+                                             args.wmedian_fill)
+        return disp, lr_masks, keep, sp_masks, wm_counts
 
     def save(path, color, stage):                                       # the colour file, then the mask and geometry files beside it
         io.save_png(path, color)
@@ -408,10 +474,14 @@ def inference(model, left_imgs, right_imgs, args, log):
             warm = True
         torch.cuda.synchronize(model.device)
         t0 = time.time()
-        outputs, lr_masks, masks, sp_masks = run(l_in, r_in)
+        outputs, lr_masks, masks, sp_masks, wm_counts = run(l_in, r_in)
         torch.cuda.synchronize(model.device)
         cost = time.time() - t0
         ss = "Inference 4 stages cost = {:.3f} sec, FPS = {:.1f}".format(cost, 1 / cost)
+        if wm:
+            for stage, (changed, refilled) in enumerate(wm_counts[:, 0].cpu().tolist()):
+                log.info("Weighted median (radius {}, sigma {:g}, fill {}): stage {} changed = {}, filled = {}".format(
+                    args.wmedian, args.wmedian_sigma, args.wmedian_fill, stage + 1, changed, refilled))
         color = None
         for stage in range(4):
             disp = outputs[stage].squeeze(axis=[0, 1]).numpy()          # :114 (the uint8 cast is inside disparity_to_color)
@@ -486,6 +556,7 @@ def main(argv=None):
     args = parser.parse_args(argv)
     check_lr_arguments(parser, args)
     check_speckle_arguments(parser, args)
+    check_wmedian_arguments(parser, args)
     check_geometry_arguments(parser, args)
     log = start_logging("lwsnet_amd.inference", args)
     model = load_model(args, log)

@@ -413,3 +413,70 @@ def speckle_filter(disp, max_size, max_diff=1.0, mask=None, fill=False, want_lab
         _lib.check(lib.lws_speckle_filter(_ptr(d), _ptr(mask), B, H, W, float(max_diff), int(max_size), int(bool(fill)), _ptr(work),
                                           _ptr(out), _ptr(mask_out), _ptr(labels), _ptr(counts), _stream()), "lws_speckle_filter")
     return SpeckleResult(out, mask_out, labels, counts)
+
+
+WMEDIAN_LUT_SIZE = 766                  # s = |dr| + |dg| + |db| between two uint8 colours: 0 .. 765
+
+
+def wmedian_lut(sigma, scale=4096):
+    """The weight table of wmedian_filter: numpy uint16 [766], wlut[s] = rint(scale * exp(-s / (3 * sigma))) in float64, s the sum
+    of the absolute colour differences to the window's centre (so sigma is in grey levels per channel).  sigma finite and > 0,
+    scale an integer in 1 .. 65535 (the weight of equal colours).  The only transcendental of the filter: the table is data."""
+    import math
+
+    import numpy as np
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float, np.integer, np.floating)) or not (math.isfinite(sigma) and sigma > 0):
+        raise ValueError(f"sigma must be finite and > 0, got {sigma!r}")
+    if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)) or not 1 <= scale <= 65535:
+        raise ValueError(f"scale must be an integer in 1 .. 65535, got {scale!r}")
+    s = np.arange(WMEDIAN_LUT_SIZE, dtype=np.float64)
+    return np.rint(np.float64(scale) * np.exp(-s / (3.0 * np.float64(sigma)))).astype(np.uint16)
+
+
+WMedianResult = namedtuple("WMedianResult", ["disp", "counts"])
+WMedianResult.__doc__ = """What wmedian_filter returns: the filtered maps float32 [B,1,H,W] and counts, an int64 [B,2] device tensor {valid
+pixels whose value changed, invalid pixels that were filled}."""
+
+
+def wmedian_filter(disp, radius, rgb=None, wlut=None, mask=None, fill_min=0):
+    """Edge-aware weighted median of disparity maps (include/lwsnet_hip.h, lws_wmedian_filter): every pixel takes the lower weighted
+    median of the valid disparities in its (2 radius + 1)^2 window, weighted by wlut[colour distance to the centre in rgb].  disp
+    [B,1,H,W] float32 (four stage maps: torch.cat them along B and repeat the guide, every image is filtered on its own); radius
+    1, 2 or 3; rgb: None (the unweighted median) or the uint8 [B,H,W,3] cropped left images; wlut: with rgb, the 766 uint16 weights
+    as a numpy array (wmedian_lut; uploaded here) or a device tensor; mask: None or the uint8 lws_lr_check / lws_speckle_filter
+    code map (only code-1 pixels are valid); fill_min: an invalid pixel with at least this many candidates takes their median (0:
+    never).  The outputs are allocated per call on the current stream.  Returns a WMedianResult."""
+    import numpy as np
+    d = _dev(disp, "disp")
+    if d.dim() != 4 or d.shape[1] != 1:
+        raise ValueError(f"disp must be [B,1,H,W]; got {tuple(d.shape)}")
+    if isinstance(radius, bool) or int(radius) != radius or not 1 <= radius <= 3:
+        raise ValueError(f"radius must be 1, 2 or 3, got {radius!r}")
+    if isinstance(fill_min, bool) or int(fill_min) != fill_min or fill_min < 0 or fill_min >= 2 ** 31:
+        raise ValueError(f"fill_min must be an integer in 0 .. 2^31 - 1, got {fill_min!r}")
+    B, _, H, W = d.shape
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or tuple(mask.shape) != tuple(d.shape) or mask.device != d.device:
+            raise ValueError(f"mask must be a uint8 {tuple(d.shape)} tensor on {d.device} (the lws_lr_check code map)")
+        mask = mask.contiguous()
+    if rgb is None:
+        if wlut is not None:
+            raise ValueError("wlut is the weight table of a guide: give rgb with it")
+    else:
+        if not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8 or tuple(rgb.shape) != (B, H, W, 3) or rgb.device != d.device:
+            raise ValueError(f"rgb must be a uint8 {(B, H, W, 3)} tensor on {d.device}")
+        rgb = rgb.contiguous()
+        if isinstance(wlut, np.ndarray):
+            if wlut.dtype != np.uint16 or wlut.shape != (WMEDIAN_LUT_SIZE,):
+                raise ValueError(f"wlut must hold {WMEDIAN_LUT_SIZE} uint16 weights; got {wlut.dtype} {wlut.shape}")
+            wlut = torch.from_numpy(np.ascontiguousarray(wlut)).to(d.device)
+        elif not (isinstance(wlut, torch.Tensor) and wlut.dtype == torch.uint16 and tuple(wlut.shape) == (WMEDIAN_LUT_SIZE,)
+                  and wlut.device == d.device):
+            raise ValueError(f"rgb needs wlut: a numpy array or a tensor on {d.device} of {WMEDIAN_LUT_SIZE} uint16 weights (wmedian_lut)")
+        wlut = wlut.contiguous()
+    out = torch.empty_like(d)
+    counts = torch.empty((B, 2), device=d.device, dtype=torch.int64)
+    with torch.cuda.device(d.device):
+        _lib.check(_lib.load().lws_wmedian_filter(_ptr(d), _ptr(mask), _ptr(rgb), _ptr(wlut), B, H, W, int(radius), int(fill_min), _ptr(out),
+                                                  _ptr(counts), _stream()), "lws_wmedian_filter")
+    return WMedianResult(out, counts)
