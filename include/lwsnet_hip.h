@@ -273,6 +273,51 @@ int lws_speckle_filter(const float *disp, const uint8_t *mask, int B, int H, int
 int lws_wmedian_filter(const float *disp, const uint8_t *mask, const uint8_t *rgb, const uint16_t *wlut, int B, int H, int W, int radius,
                        int fill_min, float *out, int64_t *counts, void *stream);
 
+/* ---- undistortion + rectification of a raw stereo pair, fused with the input transform (additive after v8) ---- */
+/* The front end of the chain: raw left and right camera images in, the rectified window of both views out, as uint8 images (the
+ * rgb of lws_point_cloud / lws_wmedian_filter), as the network's float32 input planes, with a validity map and, on request, the
+ * sampling map itself.  raw[c] (c = 0 left, 1 right) uint8 [B,Hs,Ws,3], both cameras of one raw size; the window is rows
+ * [y0, y0+H) x columns [x0, x0+W) of the rectified frame.  Outputs, per camera c:
+ *   rect[c]  uint8   [B,H,W,3]   the rectified image
+ *   input[c] float32 [B,3,H,W]   exactly the bits lws_preprocess_rgb8(rect[c], mean, std) gives; mean, std: HOST pointers to 3
+ *                                floats, read before the launch, required only when an input is requested
+ *   valid[c] uint8   [B,1,H,W]   1 where all four taps lie inside the raw image, else 0
+ *   map[c]   float32 [B,H,W,2]   (sx, sy), the raw position sampled (for tests and callers that want the map; a NaN in it is some
+ *                                NaN: IEEE 754 fixes neither its sign nor its payload)
+ * Each of the four array pointers and each element may be NULL (that output is skipped); at least one output must be requested.
+ * params float32 [B][2][18] in device memory, one record per image and camera:
+ *   {iR[9] row-major, fx, fy, cx, cy, k1, k2, p1, p2, k3}
+ * iR = inv(P_rect[:, :3] * R_rect) computed in float64 and rounded to float32 (the matrix cv2.initUndistortRectifyMap uses),
+ * fx .. cy the raw camera's intrinsics, k1 .. k3 its radial-tangential distortion coefficients in OpenCV's order (Python:
+ * lwsnet_amd.geometry.RectifyCalib.params).  Per output pixel (b, c, v, u), one IEEE float32 operation per step in the order
+ * written, products and sums left to right (no fused multiply-add, correctly rounded division):
+ *   xr = (float)(u + x0);  yr = (float)(v + y0)
+ *   X  = iR0*xr + iR1*yr + iR2;   Y = iR3*xr + iR4*yr + iR5;   Wc = iR6*xr + iR7*yr + iR8
+ *   x  = X / Wc;  y = Y / Wc;  x2 = x*x;  y2 = y*y;  r2 = x2 + y2;  t = (2.0f*x)*y
+ *   kr = 1.0f + ((k3*r2 + k2)*r2 + k1)*r2
+ *   xd = (x*kr + p1*t) + p2*(r2 + 2.0f*x2)
+ *   yd = (y*kr + p1*(r2 + 2.0f*y2)) + p2*t
+ *   sx = fx*xd + cx;   sy = fy*yd + cy                                  -> map
+ *   ok = fabsf(sx) <= 32768.0f && fabsf(sy) <= 32768.0f                 (false for NaN)
+ *   qx = (int)rintf(sx*32.0f);  qy = (int)rintf(sy*32.0f)               (half to even; only when ok)
+ *   X0 = qx >> 5;  ax = qx & 31;  Y0 = qy >> 5;  ay = qy & 31           (arithmetic shift = floor)
+ *   tap(X,Y) = raw[c][b, Y, X, ch] inside the raw image, else `border` (an int 0..255, on every channel)
+ *   rect  = ((32-ax)*(32-ay)*tap(X0,Y0) + ax*(32-ay)*tap(X0+1,Y0) + (32-ax)*ay*tap(X0,Y0+1) + ax*ay*tap(X0+1,Y0+1) + 512) >> 10
+ *   valid = ok && 0 <= X0 && X0 <= Ws-2 && 0 <= Y0 && Y0 <= Hs-2
+ *   !ok:  rect = border on every channel, valid = 0
+ *   input[ch] = (((float)rect[ch] / 255.0f) - mean[ch]) / std[ch]
+ * This is OpenCV's INTER_LINEAR / BORDER_CONSTANT rule with five fractional bits, written in plain integers: the result is exact
+ * bits (tests/rectify_reference.py restates it in numpy), NOT OpenCV's bits -- cv2.remap rounds a float weight table to int16.
+ * Limits: Hs, Ws <= 16384; Hs*Ws < 2^31 and H*W < 2^31; B <= 32767; x0, y0 >= 0; x0+W, y0+H <= 32768.  Every output is a pure
+ * function of its own image and record: the same bytes in any batch, at any position in it, on every run (no atomics).  An overlap
+ * between an output and any other device buffer of the call (another output, raw, params), a NULL raw element or NULL params,
+ * border outside 0..255, std[ch] == 0 with an input requested, no output requested and sizes outside the limits return
+ * LWS_ERR_INVALID before any GPU call.  One launch on `stream`, no workspace, no scratch memory and no device-to-host read, so the
+ * call can be captured into a hipGraph. */
+int lws_rectify_pair(const uint8_t *const raw[2], const float *params, int B, int Hs, int Ws, int H, int W, int x0, int y0, int border,
+                     const float *mean, const float *std, uint8_t *const rect[2], float *const input[2], uint8_t *const valid[2],
+                     float *const map[2], void *stream);
+
 /* Launch-plan options of lws_forward / lws_disparity_stages.  They change which kernels / streams carry the work, never
  * the arithmetic: every setting returns the same bits (tests/test_gpu_parity.py::test_forward_schedule_options) -- except
  * the opt-in numerics mode "split_bf16".  (ABI v8 removed the options two rounds of sweeps had retired: left_at, split_heads,

@@ -1,5 +1,6 @@
 """Cameras and point-cloud files for the geometry outputs (metric depth, KITTI 16-bit PNGs, point clouds; include/lwsnet_hip.h,
-lws_depth_maps / lws_point_cloud).  numpy only: the device side is lwsnet_amd.ops.depth_maps / point_cloud."""
+lws_depth_maps / lws_point_cloud) and the calibration of a raw stereo rig for the rectifying front end (lws_rectify_pair).  numpy
+only: the device side is lwsnet_amd.ops.depth_maps / point_cloud / rectify_pair."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -41,17 +42,7 @@ class Camera:
         """Reads a KITTI calibration file: the 2015 `calib_cam_to_cam/*.txt` (P_rect_02, P_rect_03) or the object / odometry
         `calib/*.txt` (P2, P3).  fx, fy, cx, cy come from the left colour camera's projection matrix; baseline =
         (P2[0,3] - P3[0,3]) / fx."""
-        mats = {}
-        with open(path, encoding="utf-8", errors="replace") as f:
-            for line in f:
-                key, sep, rest = line.partition(":")
-                if not sep:
-                    continue
-                try:
-                    vals = [float(v) for v in rest.split()]
-                except ValueError:                              # calib_time: 09-Jan-2012 13:57:47
-                    continue
-                mats[key.strip()] = vals
+        mats = _read_kitti_values(path)
         for k2, k3 in (("P_rect_02", "P_rect_03"), ("P2", "P3")):
             if k2 in mats and k3 in mats:
                 break
@@ -83,6 +74,155 @@ def camera_rows(cameras, B):
     if len(cams) != B or not all(isinstance(c, Camera) for c in cams):
         raise ValueError(f"cameras must be one Camera or a list of {B}")
     return np.stack([c.check().row() for c in cams])
+
+
+def _read_kitti_values(path):
+    """key -> list of floats for every `key: v v v` line of a KITTI calibration file (lines without numbers are skipped)."""
+    mats = {}
+    with open(path, encoding="utf-8", errors="replace") as f:
+        for line in f:
+            key, sep, rest = line.partition(":")
+            if not sep:
+                continue
+            try:
+                mats[key.strip()] = [float(v) for v in rest.split()]
+            except ValueError:                                  # calib_time: 09-Jan-2012 13:57:47
+                continue
+    return mats
+
+
+def _rodrigues(om):
+    """Rotation vector -> rotation matrix, float64."""
+    om = np.asarray(om, np.float64)
+    th = float(np.linalg.norm(om))
+    if th == 0.0:
+        return np.eye(3)
+    k = om / th
+    K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+    return np.eye(3) + np.sin(th) * K + (1.0 - np.cos(th)) * (K @ K)
+
+
+def _rotation_vector(R):
+    """Rotation matrix -> rotation vector (angle < pi), float64."""
+    R = np.asarray(R, np.float64)
+    axis = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    s = float(np.linalg.norm(axis)) / 2.0                       # sin(angle)
+    th = float(np.arctan2(s, (np.trace(R) - 1.0) / 2.0))
+    return np.zeros(3) if s == 0.0 else axis / (2.0 * s) * th
+
+
+@dataclass(frozen=True, eq=False)
+class RectifyCalib:
+    """A raw stereo rig and its rectification, as a KITTI raw `calib_cam_to_cam.txt` states it: the raw and the rectified image
+    size (height, width) and, per camera (0 = left, 1 = right), the raw intrinsics K [3,3], the distortion coefficients
+    D = (k1, k2, p1, p2, k3) in OpenCV's order, the rectifying rotation R_rect [3,3] and the rectified projection P_rect [3,4].
+    All float64 numpy."""
+    raw_hw: tuple
+    rect_hw: tuple
+    K: tuple
+    D: tuple
+    R_rect: tuple
+    P_rect: tuple
+
+    def __post_init__(self):
+        for name, shape in (("K", (3, 3)), ("D", (5,)), ("R_rect", (3, 3)), ("P_rect", (3, 4))):
+            pair = tuple(np.array(a, np.float64) for a in getattr(self, name))
+            if len(pair) != 2 or any(a.shape != shape for a in pair):
+                raise ValueError(f"{name} must hold two arrays of shape {shape}")
+            object.__setattr__(self, name, pair)
+        object.__setattr__(self, "raw_hw", tuple(int(v) for v in self.raw_hw))
+        object.__setattr__(self, "rect_hw", tuple(int(v) for v in self.rect_hw))
+
+    def check(self):
+        if len(self.raw_hw) != 2 or len(self.rect_hw) != 2 or min(self.raw_hw + self.rect_hw) < 1:
+            raise ValueError(f"image sizes must be positive (height, width) pairs; got {self.raw_hw} and {self.rect_hw}")
+        for c, side in enumerate(("left", "right")):
+            arrays = (self.K[c], self.D[c], self.R_rect[c], self.P_rect[c])
+            if not all(np.isfinite(a).all() for a in arrays):
+                raise ValueError(f"{side} camera: the calibration holds values that are not finite")
+            if not (self.K[c][0, 0] > 0 and self.K[c][1, 1] > 0 and self.P_rect[c][0, 0] > 0 and self.P_rect[c][1, 1] > 0):
+                raise ValueError(f"{side} camera: focal lengths must be > 0")
+            m = self.P_rect[c][:, :3] @ self.R_rect[c]
+            if not (np.linalg.matrix_rank(m) == 3 and np.isfinite(np.linalg.cond(m)) and np.linalg.cond(m) < 1e12):
+                raise ValueError(f"{side} camera: P_rect[:, :3] @ R_rect is not invertible")
+        return self
+
+    def params(self):
+        """The two float32 records of lws_rectify_pair, [2,18]: {inv(P_rect[:, :3] @ R_rect) row-major, fx, fy, cx, cy, k1, k2, p1,
+        p2, k3}; the inverse is taken in float64 and rounded once."""
+        self.check()
+        rows = []
+        for c in range(2):
+            inv = np.linalg.inv(self.P_rect[c][:, :3] @ self.R_rect[c])
+            k = self.K[c]
+            rows.append(np.concatenate([inv.reshape(-1), [k[0, 0], k[1, 1], k[0, 2], k[1, 2]], self.D[c]]))
+        return np.stack(rows).astype(np.float32)
+
+    def camera(self):
+        """The Camera of the rectified left view, by the formulas of Camera.from_kitti."""
+        p2, p3 = self.P_rect
+        fx = p2[0, 0]
+        return Camera(float(fx), float(p2[1, 1]), float(p2[0, 2]), float(p2[1, 2]), float((p2[0, 3] - p3[0, 3]) / fx)).check()
+
+    @classmethod
+    def from_kitti(cls, path, left="02", right="03"):
+        """Reads S_xx, K_xx, D_xx, R_rect_xx, P_rect_xx and S_rect_xx of the two cameras from a KITTI raw `calib_cam_to_cam.txt`.
+        KITTI-2015's per-frame files hold no K_ / D_ lines: they describe rectified images only."""
+        mats = _read_kitti_values(path)
+        fields = {name: [] for name in ("S", "K", "D", "R_rect", "P_rect", "S_rect")}
+        sizes = {"S": 2, "K": 9, "D": 5, "R_rect": 9, "P_rect": 12, "S_rect": 2}
+        for cam in (left, right):
+            for name, n in sizes.items():
+                key = f"{name}_{cam}"
+                if key not in mats:
+                    raise ValueError(f"{path}: missing key {key} (a raw calib_cam_to_cam.txt with S_, K_, D_, R_rect_, P_rect_ and "
+                                     f"S_rect_ lines is needed)")
+                if len(mats[key]) != n:
+                    raise ValueError(f"{path}: {key} must hold {n} values, found {len(mats[key])}")
+                fields[name].append(np.array(mats[key], np.float64))
+        if fields["S"][0].tolist() != fields["S"][1].tolist() or fields["S_rect"][0].tolist() != fields["S_rect"][1].tolist():
+            raise ValueError(f"{path}: the two cameras must share one raw and one rectified image size")
+        (ws, hs), (wr, hr) = fields["S"][0], fields["S_rect"][0]                # KITTI writes width height
+        try:
+            return cls((hs, ws), (hr, wr), [k.reshape(3, 3) for k in fields["K"]], fields["D"],
+                       [r.reshape(3, 3) for r in fields["R_rect"]], [p.reshape(3, 4) for p in fields["P_rect"]]).check()
+        except ValueError as e:
+            raise ValueError(f"{path}: {e}") from None
+
+    @classmethod
+    def from_rig(cls, K1, D1, K2, D2, R, T, size):
+        """Bouguet's rectification of a horizontal rig (the algorithm of cv2.stereoRectify without its alpha / ROI logic; the
+        caller crops), in float64.  A point x1 in camera 1 (left) is R @ x1 + T in camera 2 (right); size = (height, width) of both
+        raw images and of the rectified frame.  R is split in half between the cameras, the baseline is turned onto +x, both
+        cameras get the focal length min(K1[1,1], K2[1,1]) on both axes and the mean of the two raw principal points, and
+        P_right[0,3] = -f |T|."""
+        K1, K2, R = (np.array(a, np.float64).reshape(3, 3) for a in (K1, K2, R))
+        T = np.array(T, np.float64).reshape(3)
+        half = _rodrigues(-0.5 * _rotation_vector(R))           # turns camera 2 half way back; its transpose turns camera 1
+        t = half @ T
+        if not t[0] < 0:
+            raise ValueError("from_rig: camera 2 must lie to the right of camera 1 (T[0] < 0 after the rotation is split)")
+        uu = np.array([-1.0, 0.0, 0.0])
+        ww = np.cross(t, uu)
+        nw = float(np.linalg.norm(ww))
+        if nw > 0.0:
+            ww *= np.arccos(abs(t[0]) / np.linalg.norm(t)) / nw
+        wr = _rodrigues(ww)
+        r1, r2 = wr @ half.T, wr @ half
+        f = min(K1[1, 1], K2[1, 1])
+        cx, cy = 0.5 * (K1[0, 2] + K2[0, 2]), 0.5 * (K1[1, 2] + K2[1, 2])
+        p1 = np.array([[f, 0.0, cx, 0.0], [0.0, f, cy, 0.0], [0.0, 0.0, 1.0, 0.0]])
+        p2 = p1.copy()
+        p2[0, 3] = -f * np.linalg.norm(T)
+        return cls(size, size, (K1, K2), (D1, D2), (r1, r2), (p1, p2)).check()
+
+
+def rectify_params(calibs, B):
+    """One RectifyCalib or a list of B -> float32 [B,2,18], the params of lws_rectify_pair."""
+    cals = [calibs] * B if isinstance(calibs, RectifyCalib) else list(calibs)
+    if len(cals) != B or not all(isinstance(c, RectifyCalib) for c in cals):
+        raise ValueError(f"calibs must be one RectifyCalib or a list of {B}")
+    return np.stack([c.params() for c in cals])
 
 
 def ply_bytes(points_bytes, n):

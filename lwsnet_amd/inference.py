@@ -41,6 +41,17 @@ colour, 16-bit and point-cloud files are made, behind the left-right check and t
 takes their code map while their maps are unfilled (only trusted pixels vote, and with `--wmedian_fill N` a dropped pixel with at
 least N voting neighbours takes their median); a map `--lr_fill` / `--speckle_fill` has filled is filtered as a whole.  No code
 map is written: the `_lr` / `_sp` files are what they were, and the geometry files drop the mask once anything was filled.
+
+`--rectify PATH [--save_rect]` (not in the reference; sequential mode only): the inputs are RAW pairs -- a camera driver's frames,
+KITTI's unsynced "extract" recordings -- and PATH is the rig's calibration, a KITTI raw `calib_cam_to_cam.txt` with S_, K_, D_,
+R_rect_, P_rect_ and S_rect_ lines (or, in directory mode, a folder of such files named after the frames, as for `--calib`).  Both
+images are undistorted, rectified and normalised on the device in one launch (lws_rectify_pair), which computes only the
+bottom-right 368 x 1232 window of the rectified frame: its float planes feed the forward directly, its left uint8 image is the guide
+of `--wmedian` and the colour of `--save_ply`, and the pixels whose taps fall outside the raw left image are dropped from the depth
+and point-cloud files (code 2 in the mask they are given).  A frame whose size is not the calibration's S_xx is an error for that
+frame (logged, nothing written); a rectified frame smaller than the crop is skipped, by the reference's rule.  Without `--calib` /
+`--camera` the geometry outputs use the calibration's own rectified left camera.  `--save_rect` writes the two rectified crops as
+`<left stem>_rect_left.png` and `<left stem>_rect_right.png` into the output folder.
 """
 import argparse
 import contextlib
@@ -77,7 +88,39 @@ def build_parser():
     add_speckle_arguments(p)
     add_wmedian_arguments(p)
     add_geometry_arguments(p)
+    add_rectify_arguments(p)
     return p
+
+
+def add_rectify_arguments(p):
+    """--rectify PATH / --save_rect (not in the reference): ops.rectify_pair in front of the forward."""
+    p.add_argument("--rectify", type=str, default=None, metavar="PATH",
+                   help="the inputs are raw pairs: undistort and rectify them on the device with this KITTI raw calib_cam_to_cam.txt "
+                        "(in directory mode also a folder of <frame>.txt files; sequential mode only; not in the reference)")
+    p.add_argument("--save_rect", action="store_true",
+                   help="with --rectify: write <left stem>_rect_left.png and <left stem>_rect_right.png, the rectified crops")
+
+
+def check_rectify_arguments(p, args):
+    """Rejects what the rectifying front end does not support, before any model or GPU work; reads every calibration file."""
+    from .geometry import RectifyCalib
+    if args.rectify is None:
+        if args.save_rect:
+            p.error("--save_rect needs --rectify PATH")
+        return
+    if args.workers > 0:
+        p.error("--rectify runs in the sequential mode only: use --workers 0")
+    if os.path.isdir(args.rectify):
+        if args.left_img:
+            p.error("--rectify: a folder of calibration files needs directory mode (--img_path); give a file with --left_img")
+        paths = [_frame_file(args.rectify, li) for li in _list_pairs(args)[0]]
+    else:
+        paths = [args.rectify]
+    for path in paths:
+        try:
+            RectifyCalib.from_kitti(path)
+        except (OSError, ValueError) as e:
+            p.error(f"--rectify: cannot read {path}: {e}")
 
 
 def add_geometry_arguments(p):
@@ -103,11 +146,15 @@ def _list_pairs(args):
     return [os.path.join(base, "image_2", name)], [os.path.join(base, "image_3", name)]
 
 
+def _frame_file(path, left_path):
+    """The calibration file of a frame: `path` itself, or for a folder the KITTI naming 000123_10.png -> 000123.txt."""
+    if not os.path.isdir(path):
+        return path
+    return os.path.join(path, os.path.splitext(os.path.basename(left_path))[0].split("_")[0] + ".txt")
+
+
 def _calib_path(args, left_path):
-    """The calibration file of a frame: --calib itself, or for a folder the KITTI naming 000123_10.png -> 000123.txt."""
-    if not os.path.isdir(args.calib):
-        return args.calib
-    return os.path.join(args.calib, os.path.splitext(os.path.basename(left_path))[0].split("_")[0] + ".txt")
+    return _frame_file(args.calib, left_path)
 
 
 def check_geometry_arguments(p, args):
@@ -118,7 +165,7 @@ def check_geometry_arguments(p, args):
         p.error(f"--min_disp must be finite and > 0, got {args.min_disp}")
     if not args.max_depth > 0:
         p.error(f"--max_depth must be > 0, got {args.max_depth}")
-    if (args.save_depth or args.save_ply) and args.calib is None and args.camera is None:
+    if (args.save_depth or args.save_ply) and args.calib is None and args.camera is None and getattr(args, "rectify", None) is None:
         p.error("--save_depth and --save_ply need a camera: --calib PATH or --camera FX FY CX CY BASELINE")
     if outputs and args.workers > 0:
         p.error("--save_disp16 / --save_depth / --save_ply run in the sequential mode only: use --workers 0")
@@ -432,6 +479,7 @@ def inference(model, left_imgs, right_imgs, args, log):
     row_filled = getattr(args, "lr_fill", False) or (sp and args.speckle_fill)
     filled = row_filled or (wm and args.wmedian_fill > 0)              # no mask for the geometry files of a filled map
     geo = getattr(args, "save_disp16", False) or getattr(args, "save_depth", False) or getattr(args, "save_ply", False)
+    rc = getattr(args, "rectify", None) is not None
 
     def run(l_in, r_in):                                # -> stage maps, LR masks, codes to keep == 1 of, speckle codes, median counts
         if not lr:
@@ -444,7 +492,7 @@ def inference(model, left_imgs, right_imgs, args, log):
             disp, sp_masks, _ = speckle_stages(disp, lr_masks, args.speckle, args.speckle_diff, row_filled)
         keep, wm_counts = sp_masks if sp else lr_masks, None
         if wm:                                                          # the last step: a row-filled map is filtered as a whole
-            guide = torch.from_numpy(np.ascontiguousarray(left)[None]).to(model.device) if args.wmedian_sigma > 0 else None
+            guide = _rgb_on_device(left, model.device) if args.wmedian_sigma > 0 else None
             disp, wm_counts = wmedian_stages(disp, None if row_filled else keep, guide, args.wmedian, args.wmedian_sigma,
                                              args.wmedian_fill)
         return disp, lr_masks, keep, sp_masks, wm_counts
@@ -458,17 +506,25 @@ def inference(model, left_imgs, right_imgs, args, log):
         if sp:
             written.append(_save_sp_mask(path, sp_masks[stage], log))
         if geo:
-            written.extend(_save_geometry(path, outputs[stage], masks[stage] if masks is not None and not filled else None, cam, left,
-                                          args, log))
+            keep = masks[stage] if masks is not None and not filled else None
+            if rc:                                                      # a pixel sampled outside the raw left image: out of view
+                keep = valid_left if keep is None else torch.where(valid_left == 0, torch.full_like(keep, 2), keep)
+            written.extend(_save_geometry(path, outputs[stage], keep, cam, left, args, log))
 
     for li, ri in zip(left_imgs, right_imgs):
         full = io.load_rgb(li)
-        left = io.crop_bottom_right(full)
-        right = io.crop_bottom_right(io.load_rgb(ri))
-        if left is None or right is None:                               # :96-97
-            continue
-        cam = _frame_camera(args, li, *full.shape[:2]) if geo else None
-        l_in, r_in = io.to_input(left)[None], io.to_input(right)[None]
+        if rc:
+            front = _rectify_frame(args, li, full, io.load_rgb(ri), model.device, geo, written, log)
+            if front is None:
+                continue
+            l_in, r_in, left, valid_left, cam = front
+        else:
+            left = io.crop_bottom_right(full)
+            right = io.crop_bottom_right(io.load_rgb(ri))
+            if left is None or right is None:                           # :96-97
+                continue
+            cam = _frame_camera(args, li, *full.shape[:2]) if geo else None
+            l_in, r_in = io.to_input(left)[None], io.to_input(right)[None]
         if not warm:                                                    # one warm-up in all (the reference times its first call)
             run(l_in, r_in)
             warm = True
@@ -491,6 +547,46 @@ def inference(model, left_imgs, right_imgs, args, log):
         if not args.left_img:                                           # :133-137 (stage-4 map only)
             save(os.path.join(args.save_path, os.path.basename(li)), color, 3)
     return written
+
+
+def _rgb_on_device(rgb, device):
+    """A uint8 [H,W,3] image (numpy) or [1,H,W,3] device tensor as the [1,H,W,3] device tensor the kernels take."""
+    import torch
+    if isinstance(rgb, torch.Tensor):
+        return rgb
+    return torch.from_numpy(np.ascontiguousarray(rgb)[None]).to(device)
+
+
+def _rectify_frame(args, left_path, raw_left, raw_right, device, geo, written, log):
+    """--rectify: one raw pair -> (left input, right input, rectified left crop uint8 [1,H,W,3], valid map of the left view, camera
+    of the crop or None), all on the device; None when the frame is skipped (rectified frame smaller than the crop) or in error
+    (image size other than the calibration's).  --save_rect: the two crops are written and their paths appended to `written`."""
+    import torch
+    from . import ops
+    from .geometry import RectifyCalib
+    calib = RectifyCalib.from_kitti(_frame_file(args.rectify, left_path))
+    for name, img in (("left", raw_left), ("right", raw_right)):
+        if tuple(img.shape[:2]) != calib.raw_hw:
+            log.error("%s: the %s image is %dx%d but the calibration's raw size is %dx%d; frame not processed", left_path, name,
+                      img.shape[0], img.shape[1], *calib.raw_hw)
+            return None
+    hr, wr = calib.rect_hw
+    if hr < io.CROP_H or wr < io.CROP_W:                                # :96-97, on the rectified frame
+        return None
+    raws = [torch.from_numpy(np.ascontiguousarray(img)[None]).to(device) for img in (raw_left, raw_right)]
+    with torch.cuda.device(device):
+        out = ops.rectify_pair(raws[0], raws[1], calib.params(), (io.CROP_H, io.CROP_W), origin=(hr - io.CROP_H, wr - io.CROP_W))
+    cam = None
+    if geo:
+        cam = _frame_camera(args, left_path, hr, wr) or calib.camera().crop_bottom_right(hr, wr, io.CROP_H, io.CROP_W)
+    if args.save_rect:
+        folder = os.path.dirname(args.left_img) if args.left_img else args.save_path
+        stem = os.path.join(folder, os.path.splitext(os.path.basename(left_path))[0])
+        for side, img in zip(("left", "right"), out["rect"]):
+            io.save_png(f"{stem}_rect_{side}.png", img[0].cpu().numpy())
+            written.append(f"{stem}_rect_{side}.png")
+            log.info("Save rectified %s image = %s_rect_%s.png", side, stem, side)
+    return out["input"][0], out["input"][1], out["rect"][0], out["valid"][0], cam
 
 
 def _frame_camera(args, left_path, h, w):
@@ -523,7 +619,7 @@ def _save_geometry(path, disp, mask, cam, left_rgb, args, log):
                 written.append(stem + suffix)
                 log.info("Save {} = {}".format(suffix[1:-4], stem + suffix))
     if args.save_ply:
-        rgb = torch.from_numpy(np.ascontiguousarray(left_rgb)[None]).to(disp.device)
+        rgb = _rgb_on_device(left_rgb, disp.device)
         points, counts = ops.point_cloud(disp, cam, mask, rgb, args.min_disp, args.max_depth)
         n = int(counts[0])
         write_ply(stem + ".ply", points[0, :n].cpu().numpy(), n)
@@ -558,6 +654,7 @@ def main(argv=None):
     check_speckle_arguments(parser, args)
     check_wmedian_arguments(parser, args)
     check_geometry_arguments(parser, args)
+    check_rectify_arguments(parser, args)
     log = start_logging("lwsnet_amd.inference", args)
     model = load_model(args, log)
     if getattr(args, "split_bf16", False):

@@ -480,3 +480,57 @@ def wmedian_filter(disp, radius, rgb=None, wlut=None, mask=None, fill_min=0):
         _lib.check(_lib.load().lws_wmedian_filter(_ptr(d), _ptr(mask), _ptr(rgb), _ptr(wlut), B, H, W, int(radius), int(fill_min), _ptr(out),
                                                   _ptr(counts), _stream()), "lws_wmedian_filter")
     return WMedianResult(out, counts)
+
+
+def rectify_pair(raw_left, raw_right, params, out_hw, origin=(0, 0), border=0, want_rect=True, want_input=True, want_valid=True,
+                 want_map=False):
+    """Undistorts and rectifies raw stereo pairs and normalises them for the network in one launch (include/lwsnet_hip.h,
+    lws_rectify_pair).  raw_left, raw_right: uint8 [B,Hs,Ws,3] device tensors of one size; params: the float32 [B,2,18] records
+    (lwsnet_amd.geometry.rectify_params; numpy, uploaded here, or a device tensor; [2,18] serves every image); out_hw = (H, W) and
+    origin = (y0, x0): the window of the rectified frame to compute; border: the grey level 0..255 of the taps outside the raw image.
+    Returns a dict with the outputs asked for, each a (left, right) pair of device tensors: "rect" uint8 [B,H,W,3], "input" float32
+    [B,3,H,W] (the bits of preprocess_rgb8(rect)), "valid" uint8 [B,1,H,W], "map" float32 [B,H,W,2].  The outputs are allocated per
+    call on the current stream."""
+    import numpy as np
+
+    from .synth import IMAGENET_MEAN, IMAGENET_STD
+    for name, t in (("raw_left", raw_left), ("raw_right", raw_right)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{name} must be a torch tensor on a HIP device (the rectification has no CPU fallback)")
+        if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3:
+            raise ValueError(f"{name} must be a [B,Hs,Ws,3] uint8 tensor; got {t.dtype} {tuple(t.shape)}")
+    if raw_left.shape != raw_right.shape or raw_left.device != raw_right.device:
+        raise ValueError(f"raw_left and raw_right must share one shape and device; got {tuple(raw_left.shape)} and {tuple(raw_right.shape)}")
+    if not (want_rect or want_input or want_valid or want_map):
+        raise ValueError("rectify_pair: ask for at least one of rect, input, valid, map")
+    raw_left, raw_right = raw_left.contiguous(), raw_right.contiguous()
+    dev = raw_left.device
+    B, Hs, Ws, _ = raw_left.shape
+    if isinstance(params, np.ndarray):
+        params = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float32)).to(dev)
+    if not isinstance(params, torch.Tensor) or params.dtype != torch.float32 or params.device != dev:
+        raise ValueError(f"params must be a float32 numpy array or a float32 tensor on {dev}")
+    if tuple(params.shape) == (2, 18):
+        params = params.expand(B, 2, 18)
+    if tuple(params.shape) != (B, 2, 18):
+        raise ValueError(f"params must be [{B},2,18] or [2,18]; got {tuple(params.shape)}")
+    params = params.contiguous()
+    (H, W), (y0, x0) = (int(v) for v in out_hw), (int(v) for v in origin)
+    if isinstance(border, bool) or int(border) != border or not 0 <= border <= 255:
+        raise ValueError(f"border must be an integer in 0 .. 255, got {border!r}")
+    if H < 1 or W < 1:
+        raise ValueError(f"out_hw must be positive, got {(H, W)}")
+    res, arrays = {}, []
+    for key, want, shape, dt in (("rect", want_rect, (H, W, 3), torch.uint8), ("input", want_input, (3, H, W), torch.float32),
+                                 ("valid", want_valid, (1, H, W), torch.uint8), ("map", want_map, (H, W, 2), torch.float32)):
+        pair = torch.empty((2, B) + shape, device=dev, dtype=dt) if want else None     # one allocation for both cameras
+        if want:
+            res[key] = (pair[0], pair[1])
+        arrays.append((ctypes.c_void_p * 2)(*[pair[c].data_ptr() if want else None for c in range(2)]))
+    mean = (ctypes.c_float * 3)(*[float(v) for v in IMAGENET_MEAN])
+    std = (ctypes.c_float * 3)(*[float(v) for v in IMAGENET_STD])
+    raws = (ctypes.c_void_p * 2)(raw_left.data_ptr(), raw_right.data_ptr())
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().lws_rectify_pair(raws, _ptr(params), B, Hs, Ws, H, W, x0, y0, int(border), mean, std, *arrays, _stream()),
+                   "lws_rectify_pair")
+    return res
