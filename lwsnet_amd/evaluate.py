@@ -21,17 +21,18 @@ into shared-memory slots; a copy stream uploads the bytes and normalises them on
 StereoPairs[i]); every batch is one lws_pool job of B pairs; the metric kernel runs behind it (lwsnet_amd/pipeline.py, as for
 `lwsnet_amd.inference --workers N`).  Same numbers as `--workers 0`.
 
-`--lr_check TAU [--lr_fill]` (not in the reference; sequential mode only): the lines score LWSNet.forward_lr's checked maps, and one
-more line gives the per-stage mean density of consistent pixels.
+`--lr_check`, `--speckle` and `--wmedian` (not in the reference; sequential mode only) put the post-processing chain in front of
+the metric; how its steps combine is stated once, in the docstring of lwsnet_amd/postprocess.py.
 
-`--speckle SIZE [--speckle_diff D] [--speckle_fill]` (not in the reference; sequential mode only): the lines score the maps after
-lws_speckle_filter (behind the left-right check when both are on: the check runs unfilled, and `--speckle_fill` or `--lr_fill` fills
-what either dropped), and one more line gives the per-stage mean density of kept pixels.
+`--lr_check TAU [--lr_fill]`: the lines score LWSNet.forward_lr's checked maps, and one more line gives the per-stage mean density
+of consistent pixels.
 
-`--wmedian R [--wmedian_sigma S] [--wmedian_fill N]` (not in the reference; sequential mode only): the lines score the maps after
-lws_wmedian_filter, the last step in front of the metric (behind the check and the speckle filter when they are on, with their code
-map while their maps are unfilled); the guide is the batch's uint8 left images, uploaded once and normalised on the device
-(lws_preprocess_rgb8), and one more line gives the per-stage mean fraction of pixels the filter changed or filled.
+`--speckle SIZE [--speckle_diff D] [--speckle_fill]`: the lines score the maps after lws_speckle_filter, and one more line gives the
+per-stage mean density of kept pixels.
+
+`--wmedian R [--wmedian_sigma S] [--wmedian_fill N]`: the lines score the maps after lws_wmedian_filter, the last step in front of
+the metric; the guide is the batch's uint8 left images, uploaded once and normalised on the device (lws_preprocess_rgb8), and one
+more line gives the per-stage mean fraction of pixels the filter changed or filled.
 """
 import argparse
 import contextlib
@@ -44,8 +45,8 @@ import time
 import numpy as np
 
 from . import pipeline
-from .inference import (add_lr_arguments, add_model_arguments, add_speckle_arguments, add_wmedian_arguments, check_lr_arguments,
-                        check_speckle_arguments, check_wmedian_arguments, load_model, speckle_stages, start_logging, wmedian_stages)
+from . import postprocess as post
+from .inference import add_model_arguments, load_model, start_logging
 
 STAGES = 4
 KITTI_MAXDISP = 192                     # error_estimating's default (finetune.py:212), which test() never overrides
@@ -140,30 +141,26 @@ def _row_offset(H, Hg):
     return H - Hg
 
 
-def _sequential(model, dataset, mode, batches, maxdisp, lr=None, sp=None, wm=None):
-    """StereoPairs[i] -> model(left, right) on the batch -> lws_stage_metrics, one batch after the other.  A generator like
-    _pipelined: "start" after a warm-up forward, then (counts, abs_sum) per batch.  lr = (tau, fill): the metric scores the
-    checked maps of LWSNet.forward_lr instead, and each item gains the batch's density [4,b].  sp = (size, diff, fill): the maps go
-    through ops.speckle_filter first (the check then runs unfilled and `fill` covers both), and each item gains the batch's kept
-    density [4,b].  wm = (radius, sigma, fill_min): the maps go through ops.wmedian_filter last, with the code map of the steps
-    before it unless they filled their maps, and each item gains the batch's changed + filled fraction [4,b]; with sigma > 0 the
-    batch is read as bytes (StereoPairs.raw), uploaded once and normalised on the device, and its left images are the guide."""
+def _sequential(model, dataset, mode, batches, maxdisp, options):
+    """StereoPairs[i] -> postprocess.run_chain on the batch -> lws_stage_metrics, one batch after the other.  A generator: "start"
+    after a warm-up forward, then (counts, abs_sum, stats) per batch.  stats has a [4,b] array per stage of `options` that is on:
+    lr_density (the check's consistent pixels / (H*W)), speckle_density (the speckle filter's kept pixels / (H*W)) and
+    wmedian_changed (the median's changed + filled pixels / (H*W)).  When the median needs a guide the batch is read as bytes
+    (StereoPairs.raw), uploaded once and normalised on the device, and its left images are the guide."""
     import torch
     from . import ops
     dev = model.device
     H, W = dataset[batches[0][0]][0].shape[1:]
     x = np.zeros((len(batches[0]), 3, H, W), np.float32)
-    if sp is not None and lr is not None:
-        lr = (lr[0], False)
-    if lr is None:
+    if options.lr_check is None:
         model(x, x)                                     # warm-up outside the clock: workspace for the largest batch
     else:
-        model.forward_lr(x, x, *lr)
+        model.forward_lr(x, x, options.lr_check, options.forward_fills)
     torch.cuda.synchronize(dev)
     yield "start"
     for rng in batches:
         guide = None
-        if wm is not None and wm[1] > 0:
+        if options.needs_guide:
             items = [dataset.raw(i) for i in rng]
             with torch.cuda.device(dev):
                 u8 = torch.from_numpy(np.stack([it[0] for it in items] + [it[1] for it in items])).to(dev)
@@ -174,23 +171,17 @@ def _sequential(model, dataset, mode, batches, maxdisp, lr=None, sp=None, wm=Non
             left = np.stack([it[0] for it in items])
             right = np.stack([it[1] for it in items])
         gt = torch.from_numpy(np.ascontiguousarray(np.stack([it[2] for it in items]), dtype=np.float32)).to(dev)
-        if lr is None:
-            preds, density = model(left, right), None
-        else:
-            res = model.forward_lr(left, right, *lr)
-            preds, density = res.disp, res.density
-        extra = [] if density is None else [density]
-        if sp is not None:
-            preds, sp_masks, sp_counts = speckle_stages(preds, None if lr is None else res.mask, *sp)
-            extra.append(sp_counts[:, :, 1].cpu().numpy() / float(H * W))
-        if wm is not None:
-            row_filled = (lr is not None and lr[1]) or (sp is not None and sp[2])
-            keep = sp_masks if sp is not None else (None if lr is None else res.mask)
-            preds, wm_counts = wmedian_stages(preds, None if row_filled else keep, guide, *wm)
-            extra.append(wm_counts.sum(dim=2).cpu().numpy() / float(H * W))
+        res = post.run_chain(model, left, right, options, guide)
+        stats = {}
+        if res.lr_density is not None:
+            stats["lr_density"] = res.lr_density
+        if res.speckle_counts is not None:
+            stats["speckle_density"] = res.speckle_counts[:, :, 1].cpu().numpy() / float(H * W)
+        if res.wmedian_counts is not None:
+            stats["wmedian_changed"] = res.wmedian_counts.sum(dim=2).cpu().numpy() / float(H * W)
         with torch.cuda.device(dev):
-            counts, sums = ops.stage_metrics(preds, gt, _row_offset(left.shape[2], gt.shape[1]), maxdisp, mode)
-            yield (counts.cpu().numpy(), sums.cpu().numpy(), *extra)
+            counts, sums = ops.stage_metrics(res.disp, gt, _row_offset(left.shape[2], gt.shape[1]), maxdisp, mode)
+            yield counts.cpu().numpy(), sums.cpu().numpy(), stats
 
 
 def _decode_pair(dataset, shape, views, j, index):
@@ -296,29 +287,40 @@ def _pipelined(model, dataset, mode, batches, maxdisp, workers, gpu_workers):
                 emitted += 1
 
 
+def _stage_reports(o):
+    """Per stage of the options `o` that is on: (its key in _sequential's stats and in the result, the prefix of its log line, the
+    settings the result records in front of it)."""
+    reports = []
+    if o.lr_check is not None:
+        reports.append(("lr_density", "LR check (tau = {:g}{}): mean density ".format(o.lr_check, ", filled" if o.lr_fill else ""),
+                        {"lr_tau": o.lr_check}))
+    if o.speckle is not None:
+        reports.append(("speckle_density", "Speckle filter (size <= {}, diff <= {:g}{}): mean kept density ".format(
+            o.speckle, o.speckle_diff, ", filled" if o.speckle_fills else ""), {"speckle_size": o.speckle, "speckle_diff": o.speckle_diff}))
+    if o.wmedian is not None:
+        reports.append(("wmedian_changed", "Weighted median (radius {}, sigma {:g}, fill {}): mean changed fraction ".format(
+            o.wmedian, o.wmedian_sigma, o.wmedian_fill),
+            {"wmedian_radius": o.wmedian, "wmedian_sigma": o.wmedian_sigma, "wmedian_fill": o.wmedian_fill}))
+    return reports
+
+
 def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, workers=0, gpu_workers=2, log=None, lr_check=None,
              lr_fill=False, speckle=None, speckle_diff=1.0, speckle_fill=False, wmedian=None, wmedian_sigma=10.0, wmedian_fill=0):
     """Runs the reference's test loop for `metric` ("kitti": finetune.py's 3-pixel error, "epe": train.py's EPE) over
     `dataset` (a StereoPairs with training=False).  maxdisp is the mask bound (the KITTI loop uses 192, see KITTI_MAXDISP).
     Returns a dict: per-stage averages at full precision, per-batch values, per-image counts and sums, pairs, wall time, pairs/s.
-    lr_check = TAU (sequential mode only): the metric scores the maps of LWSNet.forward_lr(tau=TAU, fill=lr_fill), and the dict
-    gains lr_tau and lr_density, the per-stage mean over the pairs of the fraction of consistent pixels.  speckle = SIZE (sequential
-    mode only): the maps go through ops.speckle_filter(SIZE, speckle_diff, fill=speckle_fill or lr_fill) before they are scored, and
-    the dict gains speckle_size, speckle_diff and speckle_density, the per-stage mean over the pairs of kept pixels / (H*W).
-    wmedian = R (sequential mode only): the maps go through ops.wmedian_filter(R, the left images, ops.wmedian_lut(wmedian_sigma),
-    fill_min=wmedian_fill) last (wmedian_sigma = 0: no guide), and the dict gains wmedian_radius, wmedian_sigma, wmedian_fill and
-    wmedian_changed, the per-stage mean over the pairs of (changed + filled pixels) / (H*W)."""
+    lr_check = TAU, speckle = SIZE and wmedian = R (sequential mode only) switch on the stages of postprocess.run_chain in front of
+    the metric, with the flags named after them (postprocess.Options; the module docstring there says how they combine); a value
+    a stage does not support is a ValueError.  Per stage the dict gains its settings and a per-stage mean over the pairs: lr_tau
+    and lr_density (consistent pixels / (H*W)); speckle_size, speckle_diff and speckle_density (kept pixels / (H*W));
+    wmedian_radius, wmedian_sigma, wmedian_fill and wmedian_changed ((changed + filled pixels) / (H*W))."""
     if metric not in ("kitti", "epe"):
         raise ValueError(f"metric must be 'kitti' or 'epe', got {metric!r}")
-    if lr_check is not None and workers > 0:
-        raise ValueError("the left-right check runs in the sequential mode only (workers = 0)")
-    if speckle is not None and workers > 0:
-        raise ValueError("the speckle filter runs in the sequential mode only (workers = 0)")
-    if wmedian is not None and workers > 0:
-        raise ValueError("the weighted median filter runs in the sequential mode only (workers = 0)")
-    if wmedian is not None and (not 1 <= int(wmedian) <= 3 or not (np.isfinite(wmedian_sigma) and wmedian_sigma >= 0) or wmedian_fill < 0):
-        raise ValueError(f"wmedian must be 1, 2 or 3, wmedian_sigma finite and >= 0, wmedian_fill >= 0; got {wmedian}, {wmedian_sigma}, "
-                         f"{wmedian_fill}")
+    options = post.Options.make(lr_check=lr_check, lr_fill=lr_fill, speckle=speckle, speckle_diff=speckle_diff, speckle_fill=speckle_fill,
+                                wmedian=wmedian, wmedian_sigma=wmedian_sigma, wmedian_fill=wmedian_fill)
+    if options.stages_on and workers > 0:
+        raise ValueError(f"the {options.stages_on[0]} runs in the sequential mode only (workers = 0)")
+    options.check()
     if batch_size < 1:
         raise ValueError("batch_size must be >= 1")
     n = len(dataset)
@@ -329,25 +331,17 @@ def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, worker
     files = [[os.path.basename(dataset.left[i]) for i in r] for r in batches]
     meters = Meters(metric, len(batches))
     per_image = {"valid": [], "bad": [], "abs_sum": []}
-    lr = None if lr_check is None else (float(lr_check), bool(lr_fill))
-    sp = None if speckle is None else (int(speckle), float(speckle_diff), bool(speckle_fill or lr_fill))
-    wm = None if wmedian is None else (int(wmedian), float(wmedian_sigma), int(wmedian_fill))
-    densities, sp_densities, wm_changed = [], [], []
+    stats = {}
     if workers > 0:
         it = _pipelined(model, dataset, metric, batches, maxdisp, workers, gpu_workers)
     else:
-        it = _sequential(model, dataset, metric, batches, maxdisp, lr, sp, wm)
+        it = _sequential(model, dataset, metric, batches, maxdisp, options)
     if next(it) != "start":
         raise RuntimeError("the evaluation did not start")
     t0 = time.perf_counter()
-    for k, item in enumerate(it):
-        counts, sums = item[0], item[1]
-        if lr is not None:
-            densities.append(item[2])
-        if sp is not None:
-            sp_densities.append(item[3 if lr is not None else 2])
-        if wm is not None:
-            wm_changed.append(item[-1])
+    for k, (counts, sums, *batch_stats) in enumerate(it):               # _pipelined runs no stage and yields no stats
+        for key, value in (batch_stats[0].items() if batch_stats else ()):
+            stats.setdefault(key, []).append(value)
         line = meters.update(k, counts, sums, files[k])
         if line is not None:
             log.info(line)
@@ -361,27 +355,11 @@ def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, worker
            "per_image": dict(files=[os.path.basename(p) for p in dataset.left], **per_image),
            "wall_s": wall, "pairs_per_s": n / wall if wall > 0 else float("inf"),
            "workers": int(workers), "gpu_workers": int(gpu_workers) if workers > 0 else 0}
-    if lr is not None:
-        density = np.concatenate(densities, axis=1).mean(axis=1)           # [4]: mean over the pairs
-        log.info("LR check (tau = {:g}{}): mean density ".format(lr[0], ", filled" if lr[1] else "")
-                 + ", ".join("Stage {}={:.4f}".format(x, d) for x, d in enumerate(density)))
-        res["lr_tau"] = lr[0]
-        res["lr_density"] = [float(d) for d in density]
-    if sp is not None:
-        density = np.concatenate(sp_densities, axis=1).mean(axis=1)        # [4]: mean over the pairs
-        log.info("Speckle filter (size <= {}, diff <= {:g}{}): mean kept density ".format(sp[0], sp[1], ", filled" if sp[2] else "")
-                 + ", ".join("Stage {}={:.4f}".format(x, d) for x, d in enumerate(density)))
-        res["speckle_size"] = sp[0]
-        res["speckle_diff"] = sp[1]
-        res["speckle_density"] = [float(d) for d in density]
-    if wm is not None:
-        changed = np.concatenate(wm_changed, axis=1).mean(axis=1)          # [4]: mean over the pairs
-        log.info("Weighted median (radius {}, sigma {:g}, fill {}): mean changed fraction ".format(*wm)
-                 + ", ".join("Stage {}={:.4f}".format(x, d) for x, d in enumerate(changed)))
-        res["wmedian_radius"] = wm[0]
-        res["wmedian_sigma"] = wm[1]
-        res["wmedian_fill"] = wm[2]
-        res["wmedian_changed"] = [float(d) for d in changed]
+    for key, prefix, settings in _stage_reports(options):
+        mean = np.concatenate(stats[key], axis=1).mean(axis=1)             # [4]: mean over the pairs
+        log.info(prefix + ", ".join("Stage {}={:.4f}".format(x, d) for x, d in enumerate(mean)))
+        res.update(settings)
+        res[key] = [float(d) for d in mean]
     return res
 
 
@@ -401,9 +379,9 @@ def build_parser():
                    help="host worker processes decoding into a pipelined GPU path (0 = the reference's sequential loop; not in the reference)")
     p.add_argument("--gpu_workers", type=int, default=2, help="with --workers: batches kept in flight by lws_pool")
     p.add_argument("--json", type=str, default=None, help="write the result (full-precision numbers) to this file")
-    add_lr_arguments(p)
-    add_speckle_arguments(p)
-    add_wmedian_arguments(p)
+    post.add_lr_arguments(p)
+    post.add_speckle_arguments(p)
+    post.add_wmedian_arguments(p)
     return p
 
 
@@ -423,9 +401,9 @@ def load_dataset(args):
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
-    check_lr_arguments(parser, args)
-    check_speckle_arguments(parser, args)
-    check_wmedian_arguments(parser, args)
+    post.check_lr_arguments(parser, args)
+    post.check_speckle_arguments(parser, args)
+    post.check_wmedian_arguments(parser, args)
     log = start_logging("lwsnet_amd.evaluate", args)
     dataset, metric, maxdisp = load_dataset(args)
     model = load_model(args, log, missing_status=1)

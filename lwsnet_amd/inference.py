@@ -18,31 +18,29 @@ slot, and the same workers PNG-encode them (the processes, the slots and the one
 The files written are byte-identical to the sequential loop's (tests/test_gpu_parity.py::test_cli_directory_pipeline_writes_identical_files);
 the end-to-end rate and where the time goes are logged and returned (profiles/r06/e2e_cli.txt).
 
-`--lr_check TAU [--lr_fill]` (not in the reference; sequential mode only): the colour files come from LWSNet.forward_lr's checked maps
-and each gets a grey mask `<stem>_lr.png` beside it (consistent 255, inconsistent 0, out of the right view 128).
+The flags below are not in the reference and run in the sequential mode only.  `--lr_check`, `--speckle` and `--wmedian` are the
+post-processing chain; the order of its steps, which step fills, and which code map the median and the geometry files are given
+are stated once, in the docstring of lwsnet_amd/postprocess.py.
 
-`--save_disp16`, `--save_depth`, `--save_ply` (not in the reference; sequential mode only) write KITTI's 16-bit disparity PNG
-`<stem>_disp16.png`, the 16-bit depth PNG `<stem>_depth16.png` and a binary PLY point cloud `<stem>.ply` beside each colour file
-(lws_depth_maps / lws_point_cloud).  Depth and points need a camera: `--calib` (a KITTI calibration file, or in directory mode a
-folder of them named after the frames) or `--camera FX FY CX CY BASELINE` in the uncropped image's pixels; it is cropped as the
-images are.  With `--lr_check` they use the checked maps: without `--lr_fill` only consistent pixels are kept.
+`--lr_check TAU [--lr_fill]`: the colour files come from LWSNet.forward_lr's checked maps and each gets a grey mask `<stem>_lr.png`
+beside it (consistent 255, inconsistent 0, out of the right view 128).
 
-`--speckle SIZE [--speckle_diff D] [--speckle_fill]` (not in the reference; sequential mode only): the connected blobs of at most
-SIZE pixels (4-neighbours joined when their disparities differ by <= D, default 1) are removed from the stage maps on the device
-(lws_speckle_filter) before the colour, 16-bit and point-cloud files are written, and each colour file gets a grey code map
-`<stem>_sp.png` beside it (kept 255, speckle 64, the left-right check's 0 / 128 where it dropped the pixel).  With `--lr_check` the
-filter runs on the unfilled checked maps and their masks; `--speckle_fill` or `--lr_fill` then fills every dropped pixel with its
-row's background value.
+`--save_disp16`, `--save_depth`, `--save_ply` write KITTI's 16-bit disparity PNG `<stem>_disp16.png`, the 16-bit depth PNG
+`<stem>_depth16.png` and a binary PLY point cloud `<stem>.ply` beside each colour file (lws_depth_maps / lws_point_cloud).  Depth and
+points need a camera: `--calib` (a KITTI calibration file, or in directory mode a folder of them named after the frames) or
+`--camera FX FY CX CY BASELINE` in the uncropped image's pixels; it is cropped as the images are.
 
-`--wmedian R [--wmedian_sigma S] [--wmedian_fill N]` (not in the reference; sequential mode only): the stage maps go through the
-edge-aware weighted median filter (lws_wmedian_filter: a (2R + 1)^2 window, R in 1..3, weights rint(4096 exp(-s / 3S)) of the colour
-distance s to the window's centre in the cropped left image; S = 0: the unweighted median, no guide) as the last step before the
-colour, 16-bit and point-cloud files are made, behind the left-right check and the speckle filter when they are on.  The filter
-takes their code map while their maps are unfilled (only trusted pixels vote, and with `--wmedian_fill N` a dropped pixel with at
-least N voting neighbours takes their median); a map `--lr_fill` / `--speckle_fill` has filled is filtered as a whole.  No code
-map is written: the `_lr` / `_sp` files are what they were, and the geometry files drop the mask once anything was filled.
+`--speckle SIZE [--speckle_diff D] [--speckle_fill]`: the connected blobs of at most SIZE pixels (4-neighbours joined when their
+disparities differ by <= D, default 1) are removed from the stage maps on the device (lws_speckle_filter) before the colour, 16-bit
+and point-cloud files are written, and each colour file gets a grey code map `<stem>_sp.png` beside it (kept 255, speckle 64, the
+left-right check's 0 / 128 where it dropped the pixel).
 
-`--rectify PATH [--save_rect]` (not in the reference; sequential mode only): the inputs are RAW pairs -- a camera driver's frames,
+`--wmedian R [--wmedian_sigma S] [--wmedian_fill N]`: the stage maps go through the edge-aware weighted median filter
+(lws_wmedian_filter: a (2R + 1)^2 window, R in 1..3, weights rint(4096 exp(-s / 3S)) of the colour distance s to the window's centre
+in the cropped left image; S = 0: the unweighted median, no guide) as the last step before the colour, 16-bit and point-cloud files
+are made.  No code map is written: the `_lr` / `_sp` files are what they were.
+
+`--rectify PATH [--save_rect]`: the inputs are RAW pairs -- a camera driver's frames,
 KITTI's unsynced "extract" recordings -- and PATH is the rig's calibration, a KITTI raw `calib_cam_to_cam.txt` with S_, K_, D_,
 R_rect_, P_rect_ and S_rect_ lines (or, in directory mode, a folder of such files named after the frames, as for `--calib`).  Both
 images are undistorted, rectified and normalised on the device in one launch (lws_rectify_pair), which computes only the
@@ -66,6 +64,9 @@ import numpy as np
 
 from . import imageio as io
 from . import pipeline
+from . import postprocess as post
+from .postprocess import (add_lr_arguments, add_speckle_arguments, add_wmedian_arguments, check_lr_arguments, check_speckle_arguments,
+                          check_wmedian_arguments)
 
 
 def build_parser():
@@ -188,105 +189,6 @@ def check_geometry_arguments(p, args):
                 p.error(f"--calib: cannot read {path}: {e}")
 
 
-def add_lr_arguments(p):
-    """--lr_check TAU / --lr_fill (not in the reference; shared with lwsnet_amd.evaluate): LWSNet.forward_lr."""
-    p.add_argument("--lr_check", type=float, default=None, metavar="TAU",
-                   help="left-right consistency check: keep the pixels whose left- and right-view disparities differ by <= TAU "
-                        "(sequential mode only; not in the reference)")
-    p.add_argument("--lr_fill", action="store_true", help="with --lr_check: fill the dropped pixels with their row's background value")
-
-
-def add_speckle_arguments(p):
-    """--speckle SIZE / --speckle_diff D / --speckle_fill (not in the reference; shared with lwsnet_amd.evaluate): ops.speckle_filter."""
-    p.add_argument("--speckle", type=int, default=None, metavar="SIZE",
-                   help="speckle filter: remove the connected blobs of at most SIZE pixels from the disparity maps (sequential mode "
-                        "only; not in the reference)")
-    p.add_argument("--speckle_diff", type=float, default=None, metavar="D",
-                   help="with --speckle: neighbours are connected when their disparities differ by <= D (default 1.0)")
-    p.add_argument("--speckle_fill", action="store_true",
-                   help="with --speckle: fill the removed pixels with their row's background value")
-
-
-def check_speckle_arguments(p, args):
-    """Rejects what the speckle filter does not support, before any model or GPU work; sets the default of --speckle_diff."""
-    if args.speckle is None:
-        if args.speckle_fill or args.speckle_diff is not None:
-            p.error("--speckle_fill and --speckle_diff need --speckle SIZE")
-        return
-    if args.speckle_diff is None:
-        args.speckle_diff = 1.0
-    if args.speckle <= 0 or args.speckle >= 2 ** 31:
-        p.error(f"--speckle SIZE must be an integer > 0, got {args.speckle}")
-    if not np.isfinite(args.speckle_diff) or args.speckle_diff < 0:
-        p.error(f"--speckle_diff D must be finite and >= 0, got {args.speckle_diff}")
-    if args.workers > 0:
-        p.error("--speckle runs in the sequential mode only: use --workers 0")
-
-
-def speckle_stages(disp, masks, size, diff, fill):
-    """ops.speckle_filter on the four stage maps of one forward ([B,1,H,W] each, concatenated along B: every image is filtered on
-    its own) with the left-right check's masks (or None).  Returns (filtered maps, code maps, counts [4,B,3] on the device)."""
-    import torch
-    from . import ops
-    from .models import DisparityTensor
-    B = disp[0].shape[0]
-    with torch.cuda.device(disp[0].device):
-        res = ops.speckle_filter(torch.cat([d.as_subclass(torch.Tensor) for d in disp]), size, diff,
-                                 torch.cat(list(masks)) if masks is not None else None, fill=fill)
-    return ([DisparityTensor.wrap(res.disp[s * B:(s + 1) * B]) for s in range(4)], [res.mask[s * B:(s + 1) * B] for s in range(4)],
-            res.counts.view(4, B, 3))
-
-
-def add_wmedian_arguments(p):
-    """--wmedian R / --wmedian_sigma S / --wmedian_fill N (not in the reference; shared with lwsnet_amd.evaluate): ops.wmedian_filter."""
-    p.add_argument("--wmedian", type=int, default=None, metavar="R",
-                   help="edge-aware weighted median filter of the disparity maps over a (2R + 1)^2 window, R in 1..3, weighted by "
-                        "the left image (sequential mode only; not in the reference)")
-    p.add_argument("--wmedian_sigma", type=float, default=None, metavar="S",
-                   help="with --wmedian: colour scale of the weights in grey levels per channel (default 10.0; 0 = the unweighted "
-                        "median, no guide)")
-    p.add_argument("--wmedian_fill", type=int, default=None, metavar="N",
-                   help="with --wmedian: a dropped pixel with at least N trusted neighbours in its window takes their median "
-                        "(default 0 = holes are not filled)")
-
-
-def check_wmedian_arguments(p, args):
-    """Rejects what the weighted median filter does not support, before any model or GPU work; sets the defaults of
-    --wmedian_sigma and --wmedian_fill."""
-    if args.wmedian is None:
-        if args.wmedian_sigma is not None or args.wmedian_fill is not None:
-            p.error("--wmedian_sigma and --wmedian_fill need --wmedian R")
-        return
-    if args.wmedian_sigma is None:
-        args.wmedian_sigma = 10.0
-    if args.wmedian_fill is None:
-        args.wmedian_fill = 0
-    if not 1 <= args.wmedian <= 3:
-        p.error(f"--wmedian R must be 1, 2 or 3, got {args.wmedian}")
-    if not np.isfinite(args.wmedian_sigma) or args.wmedian_sigma < 0:
-        p.error(f"--wmedian_sigma S must be finite and >= 0, got {args.wmedian_sigma}")
-    if args.wmedian_fill < 0 or args.wmedian_fill >= 2 ** 31:
-        p.error(f"--wmedian_fill N must be an integer >= 0, got {args.wmedian_fill}")
-    if args.workers > 0:
-        p.error("--wmedian runs in the sequential mode only: use --workers 0")
-
-
-def wmedian_stages(disp, masks, rgb, radius, sigma, fill_min):
-    """ops.wmedian_filter on the four stage maps of one forward ([B,1,H,W] each, concatenated along B: every image is filtered on
-    its own) with their code maps (or None) and the guide rgb (uint8 [B,H,W,3] on the device, repeated per stage; unused when
-    sigma == 0).  Returns (filtered maps, counts [4,B,2] on the device)."""
-    import torch
-    from . import ops
-    from .models import DisparityTensor
-    B = disp[0].shape[0]
-    guided = sigma > 0
-    with torch.cuda.device(disp[0].device):
-        res = ops.wmedian_filter(torch.cat([d.as_subclass(torch.Tensor) for d in disp]), radius,
-                                 rgb=rgb.repeat(4, 1, 1, 1) if guided else None, wlut=ops.wmedian_lut(sigma) if guided else None,
-                                 mask=torch.cat(list(masks)) if masks is not None else None, fill_min=fill_min)
-    return [DisparityTensor.wrap(res.disp[s * B:(s + 1) * B]) for s in range(4)], res.counts.view(4, B, 2)
-
-
 def add_model_arguments(p):
     """The model's shape flags, --gpu_id and --synthetic_weights (shared with lwsnet_amd.evaluate; --model is per CLI)."""
     p.add_argument("--maxdisplist", type=int, nargs="+", default=[24, 5, 5])
@@ -327,18 +229,6 @@ def load_model(args, log, missing_status=None):
         model.set_state_dict(load_state_dict(args.model))
         log.info("Successful load model")
     return model.eval()
-
-
-def check_lr_arguments(p, args):
-    """Rejects what the left-right check does not support, before any model or GPU work."""
-    if args.lr_check is None:
-        if args.lr_fill:
-            p.error("--lr_fill needs --lr_check TAU")
-        return
-    if not np.isfinite(args.lr_check) or args.lr_check < 0:
-        p.error(f"--lr_check TAU must be finite and >= 0, got {args.lr_check}")
-    if args.workers > 0:
-        p.error("--lr_check runs in the sequential mode only: use --workers 0")
 
 
 def _pair_task(views, op, *paths):
@@ -473,43 +363,23 @@ def inference(model, left_imgs, right_imgs, args, log):
     import torch
     written = []
     warm = False
-    lr = getattr(args, "lr_check", None) is not None
-    sp = getattr(args, "speckle", None) is not None
-    wm = getattr(args, "wmedian", None) is not None
-    row_filled = getattr(args, "lr_fill", False) or (sp and args.speckle_fill)
-    filled = row_filled or (wm and args.wmedian_fill > 0)              # no mask for the geometry files of a filled map
+    opts = post.Options.from_args(args)
     geo = getattr(args, "save_disp16", False) or getattr(args, "save_depth", False) or getattr(args, "save_ply", False)
     rc = getattr(args, "rectify", None) is not None
-
-    def run(l_in, r_in):                                # -> stage maps, LR masks, codes to keep == 1 of, speckle codes, median counts
-        if not lr:
-            disp, lr_masks = model(l_in, r_in), None
-        else:                                                           # colour files from the checked maps
-            res = model.forward_lr(l_in, r_in, tau=args.lr_check, fill=args.lr_fill and not sp)
-            disp, lr_masks = res.disp, res.mask
-        sp_masks = None
-        if sp:
-            disp, sp_masks, _ = speckle_stages(disp, lr_masks, args.speckle, args.speckle_diff, row_filled)
-        keep, wm_counts = sp_masks if sp else lr_masks, None
-        if wm:                                                          # the last step: a row-filled map is filtered as a whole
-            guide = _rgb_on_device(left, model.device) if args.wmedian_sigma > 0 else None
-            disp, wm_counts = wmedian_stages(disp, None if row_filled else keep, guide, args.wmedian, args.wmedian_sigma,
-                                             args.wmedian_fill)
-        return disp, lr_masks, keep, sp_masks, wm_counts
 
     def save(path, color, stage):                                       # the colour file, then the mask and geometry files beside it
         io.save_png(path, color)
         written.append(path)
         log.info("{}\t\tSave img = {}".format(ss, path))
-        if lr:
-            written.append(_save_lr_mask(path, lr_masks[stage], log))
-        if sp:
-            written.append(_save_sp_mask(path, sp_masks[stage], log))
+        if res.lr_masks is not None:
+            written.append(_save_lr_mask(path, res.lr_masks[stage], log))
+        if res.speckle_masks is not None:
+            written.append(_save_sp_mask(path, res.speckle_masks[stage], log))
         if geo:
-            keep = masks[stage] if masks is not None and not filled else None
+            keep = res.keep[stage] if res.keep is not None else None
             if rc:                                                      # a pixel sampled outside the raw left image: out of view
                 keep = valid_left if keep is None else torch.where(valid_left == 0, torch.full_like(keep, 2), keep)
-            written.extend(_save_geometry(path, outputs[stage], keep, cam, left, args, log))
+            written.extend(_save_geometry(path, res.disp[stage], keep, cam, left, args, log))
 
     for li, ri in zip(left_imgs, right_imgs):
         full = io.load_rgb(li)
@@ -525,22 +395,22 @@ def inference(model, left_imgs, right_imgs, args, log):
                 continue
             cam = _frame_camera(args, li, *full.shape[:2]) if geo else None
             l_in, r_in = io.to_input(left)[None], io.to_input(right)[None]
-        if not warm:                                                    # one warm-up in all (the reference times its first call)
-            run(l_in, r_in)
-            warm = True
-        torch.cuda.synchronize(model.device)
-        t0 = time.time()
-        outputs, lr_masks, masks, sp_masks, wm_counts = run(l_in, r_in)
-        torch.cuda.synchronize(model.device)
-        cost = time.time() - t0
+        for _ in range(1 if warm else 2):                   # the first frame runs twice: one warm-up in all (the reference times its first call)
+            torch.cuda.synchronize(model.device)
+            t0 = time.time()
+            guide = _rgb_on_device(left, model.device) if opts.needs_guide else None
+            res = post.run_chain(model, l_in, r_in, opts, guide)
+            torch.cuda.synchronize(model.device)
+            cost = time.time() - t0
+        warm = True
         ss = "Inference 4 stages cost = {:.3f} sec, FPS = {:.1f}".format(cost, 1 / cost)
-        if wm:
-            for stage, (changed, refilled) in enumerate(wm_counts[:, 0].cpu().tolist()):
+        if res.wmedian_counts is not None:
+            for stage, (changed, refilled) in enumerate(res.wmedian_counts[:, 0].cpu().tolist()):
                 log.info("Weighted median (radius {}, sigma {:g}, fill {}): stage {} changed = {}, filled = {}".format(
-                    args.wmedian, args.wmedian_sigma, args.wmedian_fill, stage + 1, changed, refilled))
+                    opts.wmedian, opts.wmedian_sigma, opts.wmedian_fill, stage + 1, changed, refilled))
         color = None
         for stage in range(4):
-            disp = outputs[stage].squeeze(axis=[0, 1]).numpy()          # :114 (the uint8 cast is inside disparity_to_color)
+            disp = res.disp[stage].squeeze(axis=[0, 1]).numpy()         # :114 (the uint8 cast is inside disparity_to_color)
             color = io.disparity_to_color(disp)
             if args.left_img:                                           # :117-122
                 save(os.path.join(os.path.dirname(args.left_img), str(stage + 1) + ".png"), color, stage)

@@ -30,6 +30,31 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+def _code_map(mask, d):
+    """mask: None, or the uint8 code map of the maps d (same shape and device), made contiguous."""
+    if mask is None:
+        return None
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or tuple(mask.shape) != tuple(d.shape) or mask.device != d.device:
+        raise ValueError(f"mask must be a uint8 {tuple(d.shape)} tensor on {d.device} (the lws_lr_check code map)")
+    return mask.contiguous()
+
+
+def _guide(rgb, d):
+    """rgb: the uint8 [B,H,W,3] images that go with the maps d [B,1,H,W], made contiguous."""
+    B, _, H, W = d.shape
+    if not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8 or tuple(rgb.shape) != (B, H, W, 3) or rgb.device != d.device:
+        raise ValueError(f"rgb must be a uint8 {(B, H, W, 3)} tensor on {d.device}")
+    return rgb.contiguous()
+
+
+def _workspace(lib, name, device, *dims):
+    """The uint8 workspace of the size the library's `name`(*dims) asks for."""
+    nbytes = int(getattr(lib, name)(*dims))
+    if nbytes < 0:
+        _lib.check(nbytes, name)
+    return torch.empty((nbytes,), device=device, dtype=torch.uint8)
+
+
 def volume_l1_shift(feat_l, feat_r, maxdisp):
     """LWSNet._build_volume_2d (models/models.py:58-76)."""
     L, R = _dev(feat_l, "feat_l"), _dev(feat_r, "feat_r")
@@ -247,10 +272,7 @@ def stage_metrics(preds, gt, row_offset, maxdisp, mode):
             raise ValueError(f"preds[{s}] must be {(B, 1, Hg + row_offset, W)} on {g.device}; got {tuple(p.shape)} on {p.device}")
         ps.append(p)
     lib = _lib.load()
-    nbytes = int(lib.lws_stage_metrics_workspace(B, Hg, W))
-    if nbytes < 0:
-        _lib.check(nbytes, "lws_stage_metrics_workspace")
-    work = torch.empty((nbytes,), device=g.device, dtype=torch.uint8)
+    work = _workspace(lib, "lws_stage_metrics_workspace", g.device, B, Hg, W)
     counts = torch.empty((4, B, 2), device=g.device, dtype=torch.int64)
     abs_sum = torch.empty((4, B), device=g.device, dtype=torch.float64)
     arr = ctypes.c_void_p * 4
@@ -316,10 +338,7 @@ def _geometry_inputs(disp, mask, cameras, min_disp, max_depth):
     d = _dev(disp, "disp")
     if d.dim() != 4 or d.shape[1] != 1:
         raise ValueError(f"disp must be [B,1,H,W]; got {tuple(d.shape)}")
-    if mask is not None:
-        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or tuple(mask.shape) != tuple(d.shape) or mask.device != d.device:
-            raise ValueError(f"mask must be a uint8 {tuple(d.shape)} tensor on {d.device} (the lws_lr_check code map)")
-        mask = mask.contiguous()
+    mask = _code_map(mask, d)
     if not (math.isfinite(min_disp) and min_disp > 0):
         raise ValueError(f"min_disp must be finite and > 0, got {min_disp}")
     if not max_depth > 0:
@@ -359,14 +378,9 @@ def point_cloud(disp, cameras, mask=None, rgb=None, min_disp=1.0, max_depth=floa
     d, mask, cam = _geometry_inputs(disp, mask, cameras, min_disp, max_depth)
     B, _, H, W = d.shape
     if rgb is not None:
-        if not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8 or tuple(rgb.shape) != (B, H, W, 3) or rgb.device != d.device:
-            raise ValueError(f"rgb must be a uint8 {(B, H, W, 3)} tensor on {d.device}")
-        rgb = rgb.contiguous()
+        rgb = _guide(rgb, d)
     lib = _lib.load()
-    nbytes = int(lib.lws_point_cloud_workspace(B, H))
-    if nbytes < 0:
-        _lib.check(nbytes, "lws_point_cloud_workspace")
-    work = torch.empty((nbytes,), device=d.device, dtype=torch.uint8)
+    work = _workspace(lib, "lws_point_cloud_workspace", d.device, B, H)
     points = torch.empty((B, H * W, 16), device=d.device, dtype=torch.uint8)
     counts = torch.empty((B,), device=d.device, dtype=torch.int64)
     with torch.cuda.device(d.device):
@@ -391,20 +405,14 @@ def speckle_filter(disp, max_size, max_diff=1.0, mask=None, fill=False, want_lab
     d = _dev(disp, "disp")
     if d.dim() != 4 or d.shape[1] != 1:
         raise ValueError(f"disp must be [B,1,H,W]; got {tuple(d.shape)}")
-    if mask is not None:
-        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or tuple(mask.shape) != tuple(d.shape) or mask.device != d.device:
-            raise ValueError(f"mask must be a uint8 {tuple(d.shape)} tensor on {d.device} (the lws_lr_check code map)")
-        mask = mask.contiguous()
+    mask = _code_map(mask, d)
     if not (math.isfinite(max_diff) and max_diff >= 0):
         raise ValueError(f"max_diff must be finite and >= 0, got {max_diff}")
     if int(max_size) != max_size or max_size < 0 or max_size >= 2 ** 31:
         raise ValueError(f"max_size must be an integer in 0 .. 2^31 - 1, got {max_size}")
     B, _, H, W = d.shape
     lib = _lib.load()
-    nbytes = int(lib.lws_speckle_workspace(B, H, W))
-    if nbytes < 0:
-        _lib.check(nbytes, "lws_speckle_workspace")
-    work = torch.empty((nbytes,), device=d.device, dtype=torch.uint8)
+    work = _workspace(lib, "lws_speckle_workspace", d.device, B, H, W)
     out = torch.empty_like(d)
     mask_out = torch.empty(d.shape, device=d.device, dtype=torch.uint8)
     labels = torch.empty(d.shape, device=d.device, dtype=torch.int32) if want_labels else None
@@ -455,17 +463,12 @@ def wmedian_filter(disp, radius, rgb=None, wlut=None, mask=None, fill_min=0):
     if isinstance(fill_min, bool) or int(fill_min) != fill_min or fill_min < 0 or fill_min >= 2 ** 31:
         raise ValueError(f"fill_min must be an integer in 0 .. 2^31 - 1, got {fill_min!r}")
     B, _, H, W = d.shape
-    if mask is not None:
-        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or tuple(mask.shape) != tuple(d.shape) or mask.device != d.device:
-            raise ValueError(f"mask must be a uint8 {tuple(d.shape)} tensor on {d.device} (the lws_lr_check code map)")
-        mask = mask.contiguous()
+    mask = _code_map(mask, d)
     if rgb is None:
         if wlut is not None:
             raise ValueError("wlut is the weight table of a guide: give rgb with it")
     else:
-        if not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8 or tuple(rgb.shape) != (B, H, W, 3) or rgb.device != d.device:
-            raise ValueError(f"rgb must be a uint8 {(B, H, W, 3)} tensor on {d.device}")
-        rgb = rgb.contiguous()
+        rgb = _guide(rgb, d)
         if isinstance(wlut, np.ndarray):
             if wlut.dtype != np.uint16 or wlut.shape != (WMEDIAN_LUT_SIZE,):
                 raise ValueError(f"wlut must hold {WMEDIAN_LUT_SIZE} uint16 weights; got {wlut.dtype} {wlut.shape}")

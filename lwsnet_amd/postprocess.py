@@ -1,0 +1,238 @@
+"""The disparity post-processing chain of both CLIs (lwsnet_amd.inference and lwsnet_amd.evaluate, sequential mode): the
+left-right check (`--lr_check`, LWSNet.forward_lr), the speckle filter (`--speckle`, ops.speckle_filter) and the edge-aware
+weighted median (`--wmedian`, ops.wmedian_filter), in this order, each one optional.  This module alone knows how they combine:
+
+- With the speckle filter on, the left-right check runs unfilled, and ONE row fill by the speckle filter (`--speckle_fill` or
+  `--lr_fill`) then covers what either step dropped.  Without it, `--lr_fill` is the check's own fill.
+- The code map handed to the next step is the speckle filter's when it ran, otherwise the check's.
+- The weighted median takes that code map only while no row fill has happened (only trusted pixels vote; with `--wmedian_fill N`
+  a dropped pixel with at least N voting neighbours takes their median).  A row-filled map is filtered as a whole.
+- The guide (the uint8 left images) is needed only when sigma > 0; sigma = 0 is the unweighted median.
+- The geometry outputs of the inference CLI (`_disp16`, `_depth16`, `.ply`) take the code map only while NOTHING has been filled:
+  a row fill and `--wmedian_fill N > 0` both count as filling.
+- The four stage maps go through each filter as one call, concatenated along the batch dimension (every image is filtered on its
+  own), with the guide repeated four times.
+
+Options holds the flags and names these facts; run_chain runs one batch; the add_* / check_* functions are the CLIs' flags.
+"""
+import dataclasses
+from collections import namedtuple
+
+import numpy as np
+
+
+@dataclasses.dataclass(frozen=True)
+class Options:
+    """The flags of the three stages, named as the CLIs and evaluate.evaluate name them.  A stage is off while its main flag
+    (lr_check = TAU, speckle = SIZE, wmedian = R) is None."""
+    lr_check: float = None
+    lr_fill: bool = False
+    speckle: int = None
+    speckle_diff: float = 1.0
+    speckle_fill: bool = False
+    wmedian: int = None
+    wmedian_sigma: float = 10.0
+    wmedian_fill: int = 0
+
+    @classmethod
+    def make(cls, **flags):
+        """From keyword arguments named as the fields, converted to the fields' types; a flag that is None keeps its default."""
+        types = {f.name: f.type for f in dataclasses.fields(cls)}
+        return cls(**{k: types[k](v) for k, v in flags.items() if v is not None})
+
+    @classmethod
+    def from_args(cls, args):
+        """From parsed arguments; a flag the namespace does not have is off."""
+        return cls.make(**{f.name: getattr(args, f.name, None) for f in dataclasses.fields(cls)})
+
+    def check(self):
+        """Raises ValueError for every value a stage that is on does not support."""
+        if self.lr_check is not None and not (np.isfinite(self.lr_check) and self.lr_check >= 0):
+            raise ValueError(f"--lr_check TAU must be finite and >= 0, got {self.lr_check}")
+        if self.speckle is not None:
+            if self.speckle <= 0 or self.speckle >= 2 ** 31:
+                raise ValueError(f"--speckle SIZE must be an integer > 0, got {self.speckle}")
+            if not np.isfinite(self.speckle_diff) or self.speckle_diff < 0:
+                raise ValueError(f"--speckle_diff D must be finite and >= 0, got {self.speckle_diff}")
+        if self.wmedian is not None:
+            if not 1 <= self.wmedian <= 3:
+                raise ValueError(f"--wmedian R must be 1, 2 or 3, got {self.wmedian}")
+            if not np.isfinite(self.wmedian_sigma) or self.wmedian_sigma < 0:
+                raise ValueError(f"--wmedian_sigma S must be finite and >= 0, got {self.wmedian_sigma}")
+            if self.wmedian_fill < 0 or self.wmedian_fill >= 2 ** 31:
+                raise ValueError(f"--wmedian_fill N must be an integer >= 0, got {self.wmedian_fill}")
+
+    @property
+    def stages_on(self):
+        """The names of the stages that are on, in the chain's order."""
+        names = (("lr_check", "left-right check"), ("speckle", "speckle filter"), ("wmedian", "weighted median filter"))
+        return [name for flag, name in names if getattr(self, flag) is not None]
+
+    @property
+    def forward_fills(self):
+        """The left-right check fills its own maps: only without the speckle filter behind it."""
+        return self.lr_check is not None and self.lr_fill and self.speckle is None
+
+    @property
+    def speckle_fills(self):
+        """The speckle filter's row fill, which also covers what the check dropped."""
+        return self.speckle is not None and (self.speckle_fill or self.lr_fill)
+
+    @property
+    def row_filled(self):
+        return self.forward_fills or self.speckle_fills
+
+    @property
+    def filled(self):
+        """Anything was filled, by a row fill or by the median's hole filling."""
+        return self.row_filled or (self.wmedian is not None and self.wmedian_fill > 0)
+
+    @property
+    def has_codes(self):
+        return self.lr_check is not None or self.speckle is not None
+
+    @property
+    def needs_guide(self):
+        return self.wmedian is not None and self.wmedian_sigma > 0
+
+    @property
+    def wmedian_takes_codes(self):
+        return self.wmedian is not None and self.has_codes and not self.row_filled
+
+    @property
+    def geometry_takes_codes(self):
+        return self.has_codes and not self.filled
+
+
+ChainResult = namedtuple("ChainResult", ["disp", "lr_masks", "speckle_masks", "keep", "lr_density", "speckle_counts", "wmedian_counts"])
+ChainResult.__doc__ = """What run_chain returns: the four final stage maps; the left-right check's four code maps and the speckle filter's
+(None when the stage is off); keep, the four code maps the geometry outputs keep code 1 of (None once anything was filled);
+lr_density, the check's numpy [4,B]; speckle_counts [4,B,3] and wmedian_counts [4,B,2], int64 on the device (ops.speckle_filter,
+ops.wmedian_filter)."""
+
+
+def run_chain(model, left, right, options, guide=None):
+    """One batch through the forward (or forward_lr), the speckle filter and the weighted median, as `options` has them on (the
+    module docstring has the rules).  guide: the uint8 [B,H,W,3] left images on the device, needed when options.needs_guide.
+    Returns a ChainResult."""
+    o = options
+    lr_masks = sp_masks = density = sp_counts = wm_counts = None
+    if o.lr_check is None:
+        disp = model(left, right)
+    else:
+        res = model.forward_lr(left, right, tau=o.lr_check, fill=o.forward_fills)
+        disp, lr_masks, density = res.disp, res.mask, res.density
+    codes = lr_masks
+    if o.speckle is not None:
+        disp, sp_masks, sp_counts = speckle_stages(disp, lr_masks, o.speckle, o.speckle_diff, o.speckle_fills)
+        codes = sp_masks
+    if o.wmedian is not None:
+        disp, wm_counts = wmedian_stages(disp, codes if o.wmedian_takes_codes else None, guide, o.wmedian, o.wmedian_sigma, o.wmedian_fill)
+    return ChainResult(disp, lr_masks, sp_masks, codes if o.geometry_takes_codes else None, density, sp_counts, wm_counts)
+
+
+def speckle_stages(disp, masks, size, diff, fill):
+    """ops.speckle_filter on the four stage maps of one forward ([B,1,H,W] each, concatenated along B: every image is filtered on
+    its own) with the left-right check's masks (or None).  Returns (filtered maps, code maps, counts [4,B,3] on the device)."""
+    import torch
+    from . import ops
+    from .models import DisparityTensor
+    B = disp[0].shape[0]
+    with torch.cuda.device(disp[0].device):
+        res = ops.speckle_filter(torch.cat([d.as_subclass(torch.Tensor) for d in disp]), size, diff,
+                                 torch.cat(list(masks)) if masks is not None else None, fill=fill)
+    return ([DisparityTensor.wrap(res.disp[s * B:(s + 1) * B]) for s in range(4)], [res.mask[s * B:(s + 1) * B] for s in range(4)],
+            res.counts.view(4, B, 3))
+
+
+def wmedian_stages(disp, masks, rgb, radius, sigma, fill_min):
+    """ops.wmedian_filter on the four stage maps of one forward ([B,1,H,W] each, concatenated along B: every image is filtered on
+    its own) with their code maps (or None) and the guide rgb (uint8 [B,H,W,3] on the device, repeated per stage; unused when
+    sigma == 0).  Returns (filtered maps, counts [4,B,2] on the device)."""
+    import torch
+    from . import ops
+    from .models import DisparityTensor
+    B = disp[0].shape[0]
+    guided = sigma > 0
+    with torch.cuda.device(disp[0].device):
+        res = ops.wmedian_filter(torch.cat([d.as_subclass(torch.Tensor) for d in disp]), radius,
+                                 rgb=rgb.repeat(4, 1, 1, 1) if guided else None, wlut=ops.wmedian_lut(sigma) if guided else None,
+                                 mask=torch.cat(list(masks)) if masks is not None else None, fill_min=fill_min)
+    return [DisparityTensor.wrap(res.disp[s * B:(s + 1) * B]) for s in range(4)], res.counts.view(4, B, 2)
+
+
+def add_lr_arguments(p):
+    """--lr_check TAU / --lr_fill (not in the reference): LWSNet.forward_lr."""
+    p.add_argument("--lr_check", type=float, default=None, metavar="TAU",
+                   help="left-right consistency check: keep the pixels whose left- and right-view disparities differ by <= TAU "
+                        "(sequential mode only; not in the reference)")
+    p.add_argument("--lr_fill", action="store_true", help="with --lr_check: fill the dropped pixels with their row's background value")
+
+
+def add_speckle_arguments(p):
+    """--speckle SIZE / --speckle_diff D / --speckle_fill (not in the reference): ops.speckle_filter."""
+    p.add_argument("--speckle", type=int, default=None, metavar="SIZE",
+                   help="speckle filter: remove the connected blobs of at most SIZE pixels from the disparity maps (sequential mode "
+                        "only; not in the reference)")
+    p.add_argument("--speckle_diff", type=float, default=None, metavar="D",
+                   help="with --speckle: neighbours are connected when their disparities differ by <= D (default 1.0)")
+    p.add_argument("--speckle_fill", action="store_true",
+                   help="with --speckle: fill the removed pixels with their row's background value")
+
+
+def add_wmedian_arguments(p):
+    """--wmedian R / --wmedian_sigma S / --wmedian_fill N (not in the reference): ops.wmedian_filter."""
+    p.add_argument("--wmedian", type=int, default=None, metavar="R",
+                   help="edge-aware weighted median filter of the disparity maps over a (2R + 1)^2 window, R in 1..3, weighted by "
+                        "the left image (sequential mode only; not in the reference)")
+    p.add_argument("--wmedian_sigma", type=float, default=None, metavar="S",
+                   help="with --wmedian: colour scale of the weights in grey levels per channel (default 10.0; 0 = the unweighted "
+                        "median, no guide)")
+    p.add_argument("--wmedian_fill", type=int, default=None, metavar="N",
+                   help="with --wmedian: a dropped pixel with at least N trusted neighbours in its window takes their median "
+                        "(default 0 = holes are not filled)")
+
+
+def sequential_only(p, args, flag):
+    """The stages run in the CLIs' sequential mode: a parser error for `flag` with --workers N > 0."""
+    if args.workers > 0:
+        p.error(f"{flag} runs in the sequential mode only: use --workers 0")
+
+
+# main flag -> (the flags that depend on it, the error when one of them comes without it)
+_DEPENDENT = {"lr_check": (("lr_fill",), "--lr_fill needs --lr_check TAU"),
+              "speckle": (("speckle_diff", "speckle_fill"), "--speckle_fill and --speckle_diff need --speckle SIZE"),
+              "wmedian": (("wmedian_sigma", "wmedian_fill"), "--wmedian_sigma and --wmedian_fill need --wmedian R")}
+
+
+def _check_stage(p, args, main):
+    """One stage's flags, before any model or GPU work: a dependent flag without the main one, Options.check on the stage's values
+    (the defaults of its dependent flags are written back into args), --workers."""
+    dependent, lonely = _DEPENDENT[main]
+    if getattr(args, main) is None:
+        if any(getattr(args, f) is not None and getattr(args, f) is not False for f in dependent):
+            p.error(lonely)
+        return
+    options = Options.make(**{f: getattr(args, f) for f in (main, *dependent)})
+    for f in dependent:
+        setattr(args, f, getattr(options, f))
+    try:
+        options.check()
+    except ValueError as e:
+        p.error(str(e))
+    sequential_only(p, args, "--" + main)
+
+
+def check_lr_arguments(p, args):
+    """Rejects what the left-right check does not support."""
+    _check_stage(p, args, "lr_check")
+
+
+def check_speckle_arguments(p, args):
+    """Rejects what the speckle filter does not support; sets the default of --speckle_diff."""
+    _check_stage(p, args, "speckle")
+
+
+def check_wmedian_arguments(p, args):
+    """Rejects what the weighted median filter does not support; sets the defaults of --wmedian_sigma and --wmedian_fill."""
+    _check_stage(p, args, "wmedian")
