@@ -234,7 +234,7 @@ struct lws_ctx {
         int fuse_last1 = 1;        // batches <= 2: stage 1's last Conv3D layer + soft-argmin in one launch, pred1 evaluated by its consumers
         int fork2_after = -1;      // the second fork: 0 = behind stage 1's last Conv3D layer, k = behind its k-th middle layer, -1 = automatic (the last middle layer)
         int fuse_ref_last = -1;    // refinement2's last block + the 32 -> 1 convolution + pred3 in one launch: -1 = batch 1 only, 0 / 1
-        int ref_chunk_mb = 72;     // refinement in chunks of pairs whose maps are at most this many MB each (0 = one chunk); see refine_chunk
+        int ref_chunk_mb = 72;     // refinement in chunks of pairs whose maps are at most this many MB each (0 = one chunk); see refine_chunk (lws_forward.hip)
     } opt;
     unsigned prof_mask = 0;                  // kernel classes being timed in the current call
     unsigned prof_mask_cfg = 0;              // ... as configured by lws_profile_enable
@@ -283,6 +283,18 @@ struct StageMap {
 // LWS_OK if a kernel can read `m`: written, or deferred over a written map; `nested` (k_volume_l1_warp's two-level
 // DeferredMap) also allows no map before it, or one more deferred map that has none before it.  Sets the error otherwise.
 int check_stage_map(const StageMap &m, bool nested, const char *who);
+
+// ---- shared by lws_api.hip (handle, options, profiler read-out), lws_params.hip (state dict -> device slab) and
+// lws_forward.hip (workspace, launch plan) ----
+int check_device(const lws_ctx *h, const char *what);        // lws_api.hip: LWS_OK if the handle's device is the current one
+#define LWS_CHECK_DEVICE(h, what)                     \
+    do {                                              \
+        int rc_dev_ = ::lws::check_device((h), what); \
+        if (rc_dev_) return rc_dev_;                  \
+    } while (0)
+void apply_options(lws_ctx *h);                                                        // lws_api.hip
+void prof_clear(lws_ctx *h);                                                           // lws_forward.hip
+std::map<std::string, std::vector<int64_t>> build_spec(const lws_config &cfg);         // lws_params.hip
 
 // ---- kernel launchers (lws_volume.hip, lws_regress.hip, lws_conv3d.hip) ----
 // q16: round the feature values to fp16 where they are read (lws_config.feature_fp16)
@@ -339,7 +351,7 @@ bool conv3d_last_can_fuse(const Stage3d &s, int D);
 int launch_conv3d_last_softargmin(const Stage3d &s, const float *act_in, const float *cost_skip, float *cost_out,
                                   float *low, float start, int B, int D, int h, int w, hipStream_t st);
 
-// host-side weight packing used by lws_finalize
+// host-side weight packing used by lws_finalize (lws_params.hip)
 size_t packed_mid_weight_floats(int c3);
 void pack_mid_weights(const float *w /*[c3][c3][27]*/, int c3, float *out);
 void pack_first8_weights(const float *w /*[8][27]*/, float *out /*[9][64]*/);

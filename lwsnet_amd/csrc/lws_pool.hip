@@ -136,7 +136,7 @@ int lws_clone(lws_handle src, lws_handle *out)
     h->cfg = src->cfg;
     h->opt = src->opt;
     h->device = src->device;
-    h->cu_count = src->cu_count;         // (apply_options copies it into stage[]: a clone must not fall back to the 256 default)
+    h->cu_count = src->cu_count;         // (apply_options, lws_api.hip, copies it into stage[]: a clone must not fall back to the 256 default)
     h->spec = src->spec;
     h->params = src->params;             // shared, read-only; owned by src
     h->params_bytes = src->params_bytes;

@@ -72,6 +72,25 @@ def test_set_tensor_validates_keys_and_shapes(hip_lib):
     assert hip_lib.lws_destroy(h) == 0
 
 
+@pytest.mark.parametrize("kw", [{}, dict(maxdisplist=(8, 1, 1), layers_3d=1, channels_3d=16, growth_rate=(1, 1, 1)),
+                                dict(maxdisplist=(30, 5, 5), layers_3d=4, channels_3d=8, growth_rate=(4, 4, 4))],
+                         ids=["default", "c3=16,layers=1", "c3=32x3,layers=4"])
+def test_set_tensor_accepts_the_python_spec(hip_lib, kw):
+    """The library's key table against lwsnet_amd/weights.py:state_dict_spec, the independent statement of the contract:
+    every (key, shape) of the spec is accepted, the same key with its last dimension + 1 is refused."""
+    from lwsnet_amd.weights import state_dict_spec
+    rc, h = _create(hip_lib, **kw)
+    assert rc == 0
+    for key, shape, _ in state_dict_spec(default_args(**kw)):
+        v = np.zeros(shape[:-1] + (shape[-1] + 1,), np.float32)
+        shp = (ctypes.c_int64 * len(shape))(*shape)
+        assert hip_lib.lws_set_tensor(h, key.encode(), v.ctypes.data_as(_lib.c_float_p), shp, len(shape)) == 0, key
+        bad = (ctypes.c_int64 * len(shape))(*v.shape)
+        assert hip_lib.lws_set_tensor(h, key.encode(), v.ctypes.data_as(_lib.c_float_p), bad, len(shape)) == _lib.LWS_ERR_INVALID, key
+        assert b"shape mismatch" in hip_lib.lws_last_error(), key
+    assert hip_lib.lws_destroy(h) == 0
+
+
 def test_model_shim_validates_on_host(hip_lib):
     from lwsnet_amd.models import LWSNet
     m = LWSNet(default_args(), device=None) if False else None   # constructed below without a device

@@ -892,6 +892,26 @@ def test_forward_other_constructor_args(dev, hip_lib):
         assert_bits(pred[s], want[s], f"non-default args, stage {s + 1}")
 
 
+def test_second_state_dict_rebuilds_the_parameters(dev, hip_lib):
+    """lws_finalize a second time on one handle (model.set_state_dict with other weights after a forward): the slab is
+    rebuilt and every layer struct points into the new one.  Both forwards bit-exact against the C oracle with the
+    respective dict, and the second differs from the first."""
+    from lwsnet_amd.models import LWSNet
+    from oracle import c_oracle as C
+    left, right = make_batch(1, 32, 256, 4)
+    m = LWSNet(default_args(), device=dev).eval()
+    preds = []
+    for seed in (11, 12):
+        sd = make_state_dict(seed, calibrated=False)
+        m.set_state_dict(sd)
+        pred = [p.detach().cpu().numpy() for p in m(left, right)]
+        want = C.forward(left, right, sd)
+        for s in range(4):
+            assert_bits(pred[s], want[s], f"state dict of seed {seed}, stage {s + 1}")
+        preds.append(pred)
+    assert all((a != b).any() for a, b in zip(*preds))
+
+
 @pytest.mark.parametrize("mdl,l3,c3,gr", [((24, 5, 5), 4, 8, (1, 1, 1)), ((16, 2, 6), 2, 8, (4, 2, 1)), ((8, 1, 1), 1, 16, (1, 1, 1)),
                                           ((24, 5, 5), 1, 8, (4, 1, 1)), ((12, 4, 2), 3, 8, (2, 2, 2)), ((24, 7, 9), 4, 8, (4, 1, 1)),
                                           ((30, 5, 5), 4, 8, (4, 4, 4))])
