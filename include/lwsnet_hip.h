@@ -184,6 +184,33 @@ int lws_lr_pairs(const float *left, const float *right, float *left2, float *rig
 int lws_lr_check(const float *const dL[4], const float *const dRm[4], int nmaps, int B, int H, int W, float tau, int fill,
                  float *const out[4], uint8_t *const mask[4], float *const right[4], int32_t *row_kept, void *stream);
 
+/* ---- one-forward occlusion check of the stage maps (additive after v8) ---- */
+/* The classical alternative to lws_lr_check that needs no right-view map: the left-view disparities are splatted into the right
+ * view with a z-buffer (the nearest surface, i.e. the largest disparity, wins), and a left pixel is occluded when something nearer
+ * landed where it lands.  It finds occlusions, not mismatches.  For s < nmaps (1..4), dL[s] [B,1,H,W] float32, W <= 8192 (the row
+ * and its z-buffer are held in LDS), tau finite and >= 0, fill 0 or 1.  One IEEE float32 operation per step, no contraction.
+ *   key(d) = bits ^ (bits >> 31 ? 0xffffffff : 0x80000000), the order-preserving 32-bit word of a float (unsigned order of the keys
+ *            = float order of the values, -0.0 below +0.0), unkey its inverse.  0 is no finite float's or infinity's key: "empty".
+ *   Pass 1, splat.  Per row, Z[0..W-1] = 0.  Per pixel x, d = dL[x], t = (float)x - d.  A NaN d does not splat;
+ *            !(0 <= t <= W-1) (+-inf included) does not splat; otherwise Z[j] = max(Z[j], key(d)) for j = (int)floorf(t) and, when
+ *            ceilf(t) != floorf(t), also for j + 1 (<= W-1 because t <= W-1).  The max is over unsigned words.  Two taps keep a
+ *            surface watertight while neighbouring targets are at most 2 columns apart.
+ *   Pass 2, test.  NaN d: code 0;  !(0 <= t <= W-1): code 2 (out of the right camera's view);  otherwise j = (int)rintf(t) (half
+ *            to even), z = unkey(Z[j]) (non-empty: x itself splatted there), code = z - d <= tau (1 = visible, 0 = occluded by a
+ *            nearer surface).
+ * Outputs: mask[s] uint8 [B,1,H,W] = code, with the meaning of lws_lr_check's codes, so every consumer of a code map takes it
+ * unchanged;  out[s] float32 [B,1,H,W] = lws_lr_check's rule on these codes: fill 0 -> d where code == 1, else 0.0f;  fill 1 ->
+ * code-1 pixels keep d, every other pixel gets min(d at the nearest code-1 pixel to its left, d at the nearest to its right) in its
+ * row (the left value on a tie), one side's value when only that side has one, 0.0f when the row has none;  right[s] (right or
+ * right[s] NULL: skipped) float32 [B,1,H,W]: right[x] = Z[x] == 0 ? 0.0f : unkey(Z[x]), the right-view disparity in the right
+ * camera's own frame, 0 = a hole;  row_kept (NULL: skipped) int32 [nmaps][B][H] = the code-1 pixels of each row.
+ * One launch on `stream`, no workspace, no device-to-host read (capturable into a hipGraph), element alignment only; out[s] may
+ * be dL[s] (in place).  Deterministic: the only atomics are unsigned integer max on LDS words of the workgroup's own row, whose
+ * order cannot show; nothing is shared between rows, images or maps, so an image gives the same bytes in any batch.  Argument
+ * errors return LWS_ERR_INVALID before any GPU call.  No scratch memory. */
+int lws_occlusion_check(const float *const dL[4], int nmaps, int B, int H, int W, float tau, int fill, float *const out[4],
+                        uint8_t *const mask[4], float *const right[4], int32_t *row_kept, void *stream);
+
 /* ---- geometry of a disparity map: depth, KITTI 16-bit PNG values, point cloud (additive after v8) ---- */
 /* disp [B,1,H,W] float32; mask (NULL: every pixel) uint8 [B,1,H,W], the lws_lr_check code map; cam float32 [B][5] =
  * {fx, fy, cx, cy, fb} in device memory, one row per image, cx / cy in the map's (cropped) coordinates, fb = fx * baseline

@@ -48,6 +48,7 @@ PROTOTYPES = {
     "lws_stage_metrics": (_i, [_vp * 4, _i, _i, _i, _i, _vp, _i, _f, _i, _vp, _vp, _vp, _vp]),
     "lws_lr_pairs": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "lws_lr_check": (_i, [_vp * 4, _vp * 4, _i, _i, _i, _i, _f, _i, _vp * 4, _vp * 4, _vp * 4, _vp, _vp]),
+    "lws_occlusion_check": (_i, [_vp * 4, _i, _i, _i, _i, _f, _i, _vp * 4, _vp * 4, _vp * 4, _vp, _vp]),
     "lws_depth_maps": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp]),
     "lws_point_cloud_workspace": (ctypes.c_int64, [_i, _i]),
     "lws_point_cloud": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp]),

@@ -21,11 +21,14 @@ into shared-memory slots; a copy stream uploads the bytes and normalises them on
 StereoPairs[i]); every batch is one lws_pool job of B pairs; the metric kernel runs behind it (lwsnet_amd/pipeline.py, as for
 `lwsnet_amd.inference --workers N`).  Same numbers as `--workers 0`.
 
-`--lr_check`, `--speckle` and `--wmedian` (not in the reference; sequential mode only) put the post-processing chain in front of
+`--lr_check` (or `--occ_check`), `--speckle` and `--wmedian` (not in the reference; sequential mode only) put the post-processing chain in front of
 the metric; how its steps combine is stated once, in the docstring of lwsnet_amd/postprocess.py.
 
 `--lr_check TAU [--lr_fill]`: the lines score LWSNet.forward_lr's checked maps, and one more line gives the per-stage mean density
 of consistent pixels.
+
+`--occ_check TAU [--occ_fill]`: the one-forward alternative -- the lines score LWSNet.forward_occ's checked maps, and one more line
+gives the per-stage mean density of visible pixels.
 
 `--speckle SIZE [--speckle_diff D] [--speckle_fill]`: the lines score the maps after lws_speckle_filter, and one more line gives the
 per-stage mean density of kept pixels.
@@ -144,7 +147,7 @@ def _row_offset(H, Hg):
 def _sequential(model, dataset, mode, batches, maxdisp, options):
     """StereoPairs[i] -> postprocess.run_chain on the batch -> lws_stage_metrics, one batch after the other.  A generator: "start"
     after a warm-up forward, then (counts, abs_sum, stats) per batch.  stats has a [4,b] array per stage of `options` that is on:
-    lr_density (the check's consistent pixels / (H*W)), speckle_density (the speckle filter's kept pixels / (H*W)) and
+    lr_density (the check's consistent pixels / (H*W)), occ_density (the occlusion check's visible pixels / (H*W)), speckle_density (the speckle filter's kept pixels / (H*W)) and
     wmedian_changed (the median's changed + filled pixels / (H*W)).  When the median needs a guide the batch is read as bytes
     (StereoPairs.raw), uploaded once and normalised on the device, and its left images are the guide."""
     import torch
@@ -152,10 +155,12 @@ def _sequential(model, dataset, mode, batches, maxdisp, options):
     dev = model.device
     H, W = dataset[batches[0][0]][0].shape[1:]
     x = np.zeros((len(batches[0]), 3, H, W), np.float32)
-    if options.lr_check is None:
-        model(x, x)                                     # warm-up outside the clock: workspace for the largest batch
-    else:
+    if options.lr_check is not None:                    # warm-up outside the clock: workspace for the largest batch
         model.forward_lr(x, x, options.lr_check, options.forward_fills)
+    elif options.occ_check is not None:
+        model.forward_occ(x, x, options.occ_check, options.forward_fills)
+    else:
+        model(x, x)
     torch.cuda.synchronize(dev)
     yield "start"
     for rng in batches:
@@ -175,6 +180,8 @@ def _sequential(model, dataset, mode, batches, maxdisp, options):
         stats = {}
         if res.lr_density is not None:
             stats["lr_density"] = res.lr_density
+        if res.occ_density is not None:
+            stats["occ_density"] = res.occ_density
         if res.speckle_counts is not None:
             stats["speckle_density"] = res.speckle_counts[:, :, 1].cpu().numpy() / float(H * W)
         if res.wmedian_counts is not None:
@@ -294,6 +301,9 @@ def _stage_reports(o):
     if o.lr_check is not None:
         reports.append(("lr_density", "LR check (tau = {:g}{}): mean density ".format(o.lr_check, ", filled" if o.lr_fill else ""),
                         {"lr_tau": o.lr_check}))
+    if o.occ_check is not None:
+        reports.append(("occ_density", "Occlusion check (tau = {:g}{}): mean density ".format(o.occ_check, ", filled" if o.occ_fill else ""),
+                        {"occ_tau": o.occ_check}))
     if o.speckle is not None:
         reports.append(("speckle_density", "Speckle filter (size <= {}, diff <= {:g}{}): mean kept density ".format(
             o.speckle, o.speckle_diff, ", filled" if o.speckle_fills else ""), {"speckle_size": o.speckle, "speckle_diff": o.speckle_diff}))
@@ -305,19 +315,21 @@ def _stage_reports(o):
 
 
 def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, workers=0, gpu_workers=2, log=None, lr_check=None,
-             lr_fill=False, speckle=None, speckle_diff=1.0, speckle_fill=False, wmedian=None, wmedian_sigma=10.0, wmedian_fill=0):
+             lr_fill=False, speckle=None, speckle_diff=1.0, speckle_fill=False, wmedian=None, wmedian_sigma=10.0, wmedian_fill=0,
+             occ_check=None, occ_fill=False):
     """Runs the reference's test loop for `metric` ("kitti": finetune.py's 3-pixel error, "epe": train.py's EPE) over
     `dataset` (a StereoPairs with training=False).  maxdisp is the mask bound (the KITTI loop uses 192, see KITTI_MAXDISP).
     Returns a dict: per-stage averages at full precision, per-batch values, per-image counts and sums, pairs, wall time, pairs/s.
-    lr_check = TAU, speckle = SIZE and wmedian = R (sequential mode only) switch on the stages of postprocess.run_chain in front of
+    lr_check = TAU (or occ_check = TAU, the one-forward alternative), speckle = SIZE and wmedian = R (sequential mode only) switch on the stages of postprocess.run_chain in front of
     the metric, with the flags named after them (postprocess.Options; the module docstring there says how they combine); a value
     a stage does not support is a ValueError.  Per stage the dict gains its settings and a per-stage mean over the pairs: lr_tau
-    and lr_density (consistent pixels / (H*W)); speckle_size, speckle_diff and speckle_density (kept pixels / (H*W));
+    and lr_density (consistent pixels / (H*W)); occ_tau and occ_density (visible pixels / (H*W)); speckle_size, speckle_diff and speckle_density (kept pixels / (H*W));
     wmedian_radius, wmedian_sigma, wmedian_fill and wmedian_changed ((changed + filled pixels) / (H*W))."""
     if metric not in ("kitti", "epe"):
         raise ValueError(f"metric must be 'kitti' or 'epe', got {metric!r}")
     options = post.Options.make(lr_check=lr_check, lr_fill=lr_fill, speckle=speckle, speckle_diff=speckle_diff, speckle_fill=speckle_fill,
-                                wmedian=wmedian, wmedian_sigma=wmedian_sigma, wmedian_fill=wmedian_fill)
+                                wmedian=wmedian, wmedian_sigma=wmedian_sigma, wmedian_fill=wmedian_fill, occ_check=occ_check,
+                                occ_fill=occ_fill)
     if options.stages_on and workers > 0:
         raise ValueError(f"the {options.stages_on[0]} runs in the sequential mode only (workers = 0)")
     options.check()
@@ -380,6 +392,7 @@ def build_parser():
     p.add_argument("--gpu_workers", type=int, default=2, help="with --workers: batches kept in flight by lws_pool")
     p.add_argument("--json", type=str, default=None, help="write the result (full-precision numbers) to this file")
     post.add_lr_arguments(p)
+    post.add_occ_arguments(p)
     post.add_speckle_arguments(p)
     post.add_wmedian_arguments(p)
     return p
@@ -402,6 +415,7 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     post.check_lr_arguments(parser, args)
+    post.check_occ_arguments(parser, args)
     post.check_speckle_arguments(parser, args)
     post.check_wmedian_arguments(parser, args)
     log = start_logging("lwsnet_amd.evaluate", args)
@@ -410,7 +424,7 @@ def main(argv=None):
     res = evaluate(model, dataset, metric, batch_size=args.test_batch_size, maxdisp=maxdisp, workers=args.workers,
                    gpu_workers=args.gpu_workers, log=log, lr_check=args.lr_check, lr_fill=args.lr_fill, speckle=args.speckle,
                    speckle_diff=args.speckle_diff, speckle_fill=args.speckle_fill, wmedian=args.wmedian,
-                   wmedian_sigma=args.wmedian_sigma, wmedian_fill=args.wmedian_fill)
+                   wmedian_sigma=args.wmedian_sigma, wmedian_fill=args.wmedian_fill, occ_check=args.occ_check, occ_fill=args.occ_fill)
     res["dataset"] = args.dataset
     log.info("%d pairs in %.3f s: %.2f pairs/s", res["pairs"], res["wall_s"], res["pairs_per_s"])
     if args.json:

@@ -18,12 +18,16 @@ slot, and the same workers PNG-encode them (the processes, the slots and the one
 The files written are byte-identical to the sequential loop's (tests/test_gpu_parity.py::test_cli_directory_pipeline_writes_identical_files);
 the end-to-end rate and where the time goes are logged and returned (profiles/r06/e2e_cli.txt).
 
-The flags below are not in the reference and run in the sequential mode only.  `--lr_check`, `--speckle` and `--wmedian` are the
+The flags below are not in the reference and run in the sequential mode only.  `--lr_check` (or `--occ_check`), `--speckle` and `--wmedian` are the
 post-processing chain; the order of its steps, which step fills, and which code map the median and the geometry files are given
 are stated once, in the docstring of lwsnet_amd/postprocess.py.
 
 `--lr_check TAU [--lr_fill]`: the colour files come from LWSNet.forward_lr's checked maps and each gets a grey mask `<stem>_lr.png`
 beside it (consistent 255, inconsistent 0, out of the right view 128).
+
+`--occ_check TAU [--occ_fill]`: the alternative that runs the network once -- the colour files come from LWSNet.forward_occ's
+checked maps (lws_occlusion_check: the left-view map splatted into the right view with a z-buffer) and each gets a grey mask
+`<stem>_occ.png` beside it (visible 255, occluded 0, out of the right view 128).
 
 `--save_disp16`, `--save_depth`, `--save_ply` write KITTI's 16-bit disparity PNG `<stem>_disp16.png`, the 16-bit depth PNG
 `<stem>_depth16.png` and a binary PLY point cloud `<stem>.ply` beside each colour file (lws_depth_maps / lws_point_cloud).  Depth and
@@ -65,8 +69,8 @@ import numpy as np
 from . import imageio as io
 from . import pipeline
 from . import postprocess as post
-from .postprocess import (add_lr_arguments, add_speckle_arguments, add_wmedian_arguments, check_lr_arguments, check_speckle_arguments,
-                          check_wmedian_arguments)
+from .postprocess import (add_lr_arguments, add_occ_arguments, add_speckle_arguments, add_wmedian_arguments, check_lr_arguments,
+                          check_occ_arguments, check_speckle_arguments, check_wmedian_arguments)
 
 
 def build_parser():
@@ -86,6 +90,7 @@ def build_parser():
                         "reference's sequential loop; not in the reference)")
     p.add_argument("--gpu_workers", type=int, default=3, help="with --workers: forwards kept in flight by lws_pool")
     add_lr_arguments(p)
+    add_occ_arguments(p)
     add_speckle_arguments(p)
     add_wmedian_arguments(p)
     add_geometry_arguments(p)
@@ -373,6 +378,8 @@ def inference(model, left_imgs, right_imgs, args, log):
         log.info("{}\t\tSave img = {}".format(ss, path))
         if res.lr_masks is not None:
             written.append(_save_lr_mask(path, res.lr_masks[stage], log))
+        if res.occ_masks is not None:
+            written.append(_save_occ_mask(path, res.occ_masks[stage], log))
         if res.speckle_masks is not None:
             written.append(_save_sp_mask(path, res.speckle_masks[stage], log))
         if geo:
@@ -507,6 +514,15 @@ def _save_lr_mask(path, mask, log):
     return mpath
 
 
+def _save_occ_mask(path, mask, log):
+    """The occlusion check codes of the map written to `path`, as the grey PNG <stem>_occ.png next to it."""
+    code = mask[0, 0].cpu().numpy()
+    mpath = os.path.splitext(path)[0] + "_occ.png"
+    io.save_lr_mask_png(mpath, code)
+    log.info("Occlusion check: density = {:.4f}\t\tSave mask = {}".format(float((code == 1).mean()), mpath))
+    return mpath
+
+
 def _save_sp_mask(path, mask, log):
     """The speckle filter's codes of the map written to `path`, as the grey PNG <stem>_sp.png next to it."""
     code = mask[0, 0].cpu().numpy()
@@ -521,6 +537,7 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     check_lr_arguments(parser, args)
+    check_occ_arguments(parser, args)
     check_speckle_arguments(parser, args)
     check_wmedian_arguments(parser, args)
     check_geometry_arguments(parser, args)

@@ -24,6 +24,12 @@ LRResult.__doc__ = """What LWSNet.forward_lr returns: the four left-view stage m
 un-mirrored right-view maps, the four checked maps (background-filled if asked), the four uint8 code maps (1 consistent,
 0 inconsistent, 2 out of the right camera's view) and density, a numpy [4,B] array of consistent pixels / (H*W)."""
 
+OccResult = namedtuple("OccResult", LRResult._fields)
+OccResult.__doc__ = """What LWSNet.forward_occ returns, under LRResult's field names: the four left-view stage maps (the bits of
+model(left, right)), the four right-view maps splatted from them (the right camera's frame; 0 in the holes), the four checked maps
+(background-filled if asked), the four uint8 code maps (1 visible, 0 occluded by a nearer surface, 2 out of the right camera's
+view) and density, a numpy [4,B] array of visible pixels / (H*W)."""
+
 
 class DisparityTensor(torch.Tensor):
     """What ``model(left, right)`` returns per stage: a device-resident ``torch.Tensor`` that also answers the Paddle
@@ -245,6 +251,29 @@ class LWSNet:
             density = row_kept.sum(dim=2, dtype=torch.int64).cpu().numpy() / float(H * W)
         wrap = DisparityTensor.wrap
         return LRResult([wrap(p) for p in dl], [wrap(p) for p in rmaps], [wrap(p) for p in out], mask, density)
+
+    def forward_occ(self, left_input, right_input, tau=1.0, fill=False):
+        """Stage maps with a one-forward occlusion check (not in the reference): one plain forward of the B pairs plus one
+        lws_occlusion_check of the four stages (include/lwsnet_hip.h), which splats each left-view map into the right view with a
+        z-buffer.  A pixel is kept when the nearest surface that lands on its right-view column is at most tau nearer; `fill`
+        gives the others the background value of their row.  It finds occlusions, not mismatches (forward_lr does, at the price
+        of a second network).  Returns an OccResult."""
+        if self.device is None:
+            raise RuntimeError("no HIP device is available and lwsnet_amd has no CPU fallback")
+        if self._params is None:
+            raise RuntimeError("set_state_dict() must be called before forward_occ()")
+        left = self._input(left_input, "left_input")
+        right = self._input(right_input, "right_input")
+        if left.shape != right.shape:
+            raise ValueError(f"left/right shapes differ: {tuple(left.shape)} vs {tuple(right.shape)}")
+        B, _, H, W = left.shape
+        check_size(H, W, self.maxdisplist[0])
+        with torch.cuda.device(self.device):
+            dl = ops.forward(self._h, left, right)
+            out, mask, rmaps, row_kept = ops.occlusion_check(dl, tau, fill, want_right=True)
+            density = row_kept.sum(dim=2, dtype=torch.int64).cpu().numpy() / float(H * W)
+        wrap = DisparityTensor.wrap
+        return OccResult([wrap(p) for p in dl], [wrap(p) for p in rmaps], [wrap(p) for p in out], mask, density)
 
 
 class _PoolJob:

@@ -329,6 +329,38 @@ def lr_check(dl, drm, tau, fill, want_right=True):
     return out, mask, right, row_kept
 
 
+def occlusion_check(dl, tau, fill, want_right=True):
+    """One-forward occlusion check of 1-4 stage maps (include/lwsnet_hip.h, lws_occlusion_check): dl[s] the left-view maps,
+    each [B,1,H,W] float32, splatted into the right view with a z-buffer.  Returns (out, mask, right, row_kept) as lr_check does:
+    lists of [B,1,H,W] float32 checked (filled if `fill`) maps, uint8 codes (1 visible, 0 occluded by a nearer surface, 2 out of
+    view) and right-view maps in the right camera's frame with 0 in the holes (None unless want_right), and an int32
+    [nmaps,B,H] device tensor of the visible pixels per row."""
+    if not isinstance(dl, (list, tuple)) or not 1 <= len(dl) <= 4:
+        raise ValueError("dl must be a list of 1-4 stage maps")
+    ls = [_dev(t, f"dl[{s}]") for s, t in enumerate(dl)]
+    shape, dev = tuple(ls[0].shape), ls[0].device
+    if len(shape) != 4 or shape[1] != 1:
+        raise ValueError(f"dl[0] must be [B,1,H,W]; got {shape}")
+    for s, t in enumerate(ls):
+        if tuple(t.shape) != shape or t.device != dev:
+            raise ValueError(f"dl[{s}] must be {shape} on {dev}; got {tuple(t.shape)} on {t.device}")
+    B, _, H, W = shape
+    n = len(ls)
+    out = [torch.empty(shape, device=dev, dtype=torch.float32) for _ in range(n)]
+    mask = [torch.empty(shape, device=dev, dtype=torch.uint8) for _ in range(n)]
+    right = [torch.empty(shape, device=dev, dtype=torch.float32) for _ in range(n)] if want_right else None
+    row_kept = torch.empty((n, B, H), device=dev, dtype=torch.int32)
+
+    def arr(ts):
+        return (ctypes.c_void_p * 4)(*[t.data_ptr() for t in ts])
+
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().lws_occlusion_check(arr(ls), n, B, H, W, float(tau), int(bool(fill)), arr(out), arr(mask),
+                                                   arr(right if right is not None else []), _ptr(row_kept), _stream()),
+                   "lws_occlusion_check")
+    return out, mask, right, row_kept
+
+
 def _geometry_inputs(disp, mask, cameras, min_disp, max_depth):
     """Shared checks of depth_maps / point_cloud: disp [B,1,H,W] float32, mask None or uint8 of that shape, cameras (None, one
     Camera or a list of B) -> (disp, mask, cam [B,5] float32 device tensor or None)."""

@@ -1,9 +1,13 @@
 """The disparity post-processing chain of both CLIs (lwsnet_amd.inference and lwsnet_amd.evaluate, sequential mode): the
-left-right check (`--lr_check`, LWSNet.forward_lr), the speckle filter (`--speckle`, ops.speckle_filter) and the edge-aware
+left-right check (`--lr_check`, LWSNet.forward_lr) or, in its place, the one-forward occlusion check (`--occ_check`,
+LWSNet.forward_occ), the speckle filter (`--speckle`, ops.speckle_filter) and the edge-aware
 weighted median (`--wmedian`, ops.wmedian_filter), in this order, each one optional.  This module alone knows how they combine:
 
-- With the speckle filter on, the left-right check runs unfilled, and ONE row fill by the speckle filter (`--speckle_fill` or
-  `--lr_fill`) then covers what either step dropped.  Without it, `--lr_fill` is the check's own fill.
+- The occlusion check stands exactly where the left-right check stands, with `--occ_fill` for `--lr_fill`: every rule below
+  that names "the check" holds for whichever of the two is on.  They are alternatives (one run of the network against two; the
+  occlusion check finds no mismatches), and asking for both is an error.
+- With the speckle filter on, the check runs unfilled, and ONE row fill by the speckle filter (`--speckle_fill`, `--lr_fill` or
+  `--occ_fill`) then covers what either step dropped.  Without it, `--lr_fill` / `--occ_fill` is the check's own fill.
 - The code map handed to the next step is the speckle filter's when it ran, otherwise the check's.
 - The weighted median takes that code map only while no row fill has happened (only trusted pixels vote; with `--wmedian_fill N`
   a dropped pixel with at least N voting neighbours takes their median).  A row-filled map is filtered as a whole.
@@ -23,8 +27,8 @@ import numpy as np
 
 @dataclasses.dataclass(frozen=True)
 class Options:
-    """The flags of the three stages, named as the CLIs and evaluate.evaluate name them.  A stage is off while its main flag
-    (lr_check = TAU, speckle = SIZE, wmedian = R) is None."""
+    """The flags of the stages, named as the CLIs and evaluate.evaluate name them.  A stage is off while its main flag
+    (lr_check = TAU, occ_check = TAU, speckle = SIZE, wmedian = R) is None."""
     lr_check: float = None
     lr_fill: bool = False
     speckle: int = None
@@ -33,6 +37,8 @@ class Options:
     wmedian: int = None
     wmedian_sigma: float = 10.0
     wmedian_fill: int = 0
+    occ_check: float = None
+    occ_fill: bool = False
 
     @classmethod
     def make(cls, **flags):
@@ -49,6 +55,11 @@ class Options:
         """Raises ValueError for every value a stage that is on does not support."""
         if self.lr_check is not None and not (np.isfinite(self.lr_check) and self.lr_check >= 0):
             raise ValueError(f"--lr_check TAU must be finite and >= 0, got {self.lr_check}")
+        if self.occ_check is not None:
+            if not (np.isfinite(self.occ_check) and self.occ_check >= 0):
+                raise ValueError(f"--occ_check TAU must be finite and >= 0, got {self.occ_check}")
+            if self.lr_check is not None:
+                raise ValueError("--occ_check and --lr_check are alternatives: give one of them")
         if self.speckle is not None:
             if self.speckle <= 0 or self.speckle >= 2 ** 31:
                 raise ValueError(f"--speckle SIZE must be an integer > 0, got {self.speckle}")
@@ -65,18 +76,18 @@ class Options:
     @property
     def stages_on(self):
         """The names of the stages that are on, in the chain's order."""
-        names = (("lr_check", "left-right check"), ("speckle", "speckle filter"), ("wmedian", "weighted median filter"))
+        names = (("lr_check", "left-right check"), ("occ_check", "occlusion check"), ("speckle", "speckle filter"), ("wmedian", "weighted median filter"))
         return [name for flag, name in names if getattr(self, flag) is not None]
 
     @property
     def forward_fills(self):
-        """The left-right check fills its own maps: only without the speckle filter behind it."""
-        return self.lr_check is not None and self.lr_fill and self.speckle is None
+        """The left-right check (or the occlusion check) fills its own maps: only without the speckle filter behind it."""
+        return ((self.lr_check is not None and self.lr_fill) or (self.occ_check is not None and self.occ_fill)) and self.speckle is None
 
     @property
     def speckle_fills(self):
         """The speckle filter's row fill, which also covers what the check dropped."""
-        return self.speckle is not None and (self.speckle_fill or self.lr_fill)
+        return self.speckle is not None and (self.speckle_fill or self.lr_fill or self.occ_fill)
 
     @property
     def row_filled(self):
@@ -89,7 +100,7 @@ class Options:
 
     @property
     def has_codes(self):
-        return self.lr_check is not None or self.speckle is not None
+        return self.lr_check is not None or self.occ_check is not None or self.speckle is not None
 
     @property
     def needs_guide(self):
@@ -104,36 +115,47 @@ class Options:
         return self.has_codes and not self.filled
 
 
-ChainResult = namedtuple("ChainResult", ["disp", "lr_masks", "speckle_masks", "keep", "lr_density", "speckle_counts", "wmedian_counts"])
-ChainResult.__doc__ = """What run_chain returns: the four final stage maps; the left-right check's four code maps and the speckle filter's
-(None when the stage is off); keep, the four code maps the geometry outputs keep code 1 of (None once anything was filled);
-lr_density, the check's numpy [4,B]; speckle_counts [4,B,3] and wmedian_counts [4,B,2], int64 on the device (ops.speckle_filter,
-ops.wmedian_filter)."""
+class ChainResult(namedtuple("ChainResult", ["disp", "lr_masks", "speckle_masks", "keep", "lr_density", "speckle_counts", "wmedian_counts"])):
+    """What run_chain returns: the four final stage maps; the left-right check's four code maps and the speckle filter's
+    (None when the stage is off); keep, the four code maps the geometry outputs keep code 1 of (None once anything was filled);
+    lr_density, the check's numpy [4,B]; speckle_counts [4,B,3] and wmedian_counts [4,B,2], int64 on the device (ops.speckle_filter,
+    ops.wmedian_filter).  Behind these seven, as attributes that default to None and are no part of the tuple (a caller that
+    unpacks or slices the seven sees what it saw before the occlusion check existed): occ_masks and occ_density, the occlusion
+    check's four code maps and its numpy [4,B]."""
+
+    def __new__(cls, disp, lr_masks, speckle_masks, keep, lr_density, speckle_counts, wmedian_counts, occ_masks=None, occ_density=None):
+        self = super().__new__(cls, disp, lr_masks, speckle_masks, keep, lr_density, speckle_counts, wmedian_counts)
+        self.occ_masks, self.occ_density = occ_masks, occ_density
+        return self
 
 
 def run_chain(model, left, right, options, guide=None):
-    """One batch through the forward (or forward_lr), the speckle filter and the weighted median, as `options` has them on (the
+    """One batch through the forward (or forward_lr, or forward_occ), the speckle filter and the weighted median, as `options` has them on (the
     module docstring has the rules).  guide: the uint8 [B,H,W,3] left images on the device, needed when options.needs_guide.
     Returns a ChainResult."""
     o = options
-    lr_masks = sp_masks = density = sp_counts = wm_counts = None
-    if o.lr_check is None:
-        disp = model(left, right)
-    else:
+    lr_masks = occ_masks = sp_masks = density = occ_density = sp_counts = wm_counts = None
+    if o.lr_check is not None:
         res = model.forward_lr(left, right, tau=o.lr_check, fill=o.forward_fills)
         disp, lr_masks, density = res.disp, res.mask, res.density
-    codes = lr_masks
+    elif o.occ_check is not None:
+        res = model.forward_occ(left, right, tau=o.occ_check, fill=o.forward_fills)
+        disp, occ_masks, occ_density = res.disp, res.mask, res.density
+    else:
+        disp = model(left, right)
+    codes = lr_masks if lr_masks is not None else occ_masks
     if o.speckle is not None:
-        disp, sp_masks, sp_counts = speckle_stages(disp, lr_masks, o.speckle, o.speckle_diff, o.speckle_fills)
+        disp, sp_masks, sp_counts = speckle_stages(disp, codes, o.speckle, o.speckle_diff, o.speckle_fills)
         codes = sp_masks
     if o.wmedian is not None:
         disp, wm_counts = wmedian_stages(disp, codes if o.wmedian_takes_codes else None, guide, o.wmedian, o.wmedian_sigma, o.wmedian_fill)
-    return ChainResult(disp, lr_masks, sp_masks, codes if o.geometry_takes_codes else None, density, sp_counts, wm_counts)
+    return ChainResult(disp, lr_masks, sp_masks, codes if o.geometry_takes_codes else None, density, sp_counts, wm_counts, occ_masks,
+                       occ_density)
 
 
 def speckle_stages(disp, masks, size, diff, fill):
     """ops.speckle_filter on the four stage maps of one forward ([B,1,H,W] each, concatenated along B: every image is filtered on
-    its own) with the left-right check's masks (or None).  Returns (filtered maps, code maps, counts [4,B,3] on the device)."""
+    its own) with the left-right (or occlusion) check's masks (or None).  Returns (filtered maps, code maps, counts [4,B,3] on the device)."""
     import torch
     from . import ops
     from .models import DisparityTensor
@@ -169,6 +191,16 @@ def add_lr_arguments(p):
     p.add_argument("--lr_fill", action="store_true", help="with --lr_check: fill the dropped pixels with their row's background value")
 
 
+def add_occ_arguments(p):
+    """--occ_check TAU / --occ_fill (not in the reference): LWSNet.forward_occ.  A command line without them parses to the
+    namespace it parsed to before they existed (argparse.SUPPRESS); check_occ_arguments writes their defaults, None and False."""
+    import argparse
+    p.add_argument("--occ_check", type=float, default=argparse.SUPPRESS, metavar="TAU",
+                   help="one-forward occlusion check, the alternative to --lr_check: splat the left-view disparities into the right "
+                        "view and drop the pixels behind a surface more than TAU nearer (sequential mode only; not in the reference)")
+    p.add_argument("--occ_fill", action="store_true", default=argparse.SUPPRESS, help="with --occ_check: fill the dropped pixels with their row's background value")
+
+
 def add_speckle_arguments(p):
     """--speckle SIZE / --speckle_diff D / --speckle_fill (not in the reference): ops.speckle_filter."""
     p.add_argument("--speckle", type=int, default=None, metavar="SIZE",
@@ -201,6 +233,7 @@ def sequential_only(p, args, flag):
 
 # main flag -> (the flags that depend on it, the error when one of them comes without it)
 _DEPENDENT = {"lr_check": (("lr_fill",), "--lr_fill needs --lr_check TAU"),
+              "occ_check": (("occ_fill",), "--occ_fill needs --occ_check TAU"),
               "speckle": (("speckle_diff", "speckle_fill"), "--speckle_fill and --speckle_diff need --speckle SIZE"),
               "wmedian": (("wmedian_sigma", "wmedian_fill"), "--wmedian_sigma and --wmedian_fill need --wmedian R")}
 
@@ -226,6 +259,14 @@ def _check_stage(p, args, main):
 def check_lr_arguments(p, args):
     """Rejects what the left-right check does not support."""
     _check_stage(p, args, "lr_check")
+
+
+def check_occ_arguments(p, args):
+    """Rejects what the occlusion check does not support, --lr_check beside it included; sets the flags' defaults."""
+    args.occ_check, args.occ_fill = getattr(args, "occ_check", None), getattr(args, "occ_fill", False)
+    if args.occ_check is not None and getattr(args, "lr_check", None) is not None:
+        p.error("--occ_check and --lr_check are alternatives: give one of them")
+    _check_stage(p, args, "occ_check")
 
 
 def check_speckle_arguments(p, args):
