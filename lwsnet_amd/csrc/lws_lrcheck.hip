@@ -5,20 +5,13 @@
 // so tests/lr_reference.py restates every output bit for bit in numpy.  Determinism: no atomics; a workgroup owns one row of one
 // image and map, so an image gives the same bits in any batch.  0 bytes of scratch; the row lives in LDS.
 #include "lws_common.h"
-#include "lws_rowfill.h"
+#include "lws_rowkit.h"
 
 namespace lws {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kMaxW = rowfill::kFillMaxW;                   // dRm / dL row + two int per quad: 48 KiB of LDS at most
-static_assert(kThreads == rowfill::kFillThreads, "k_lr_check runs rowfill::fill_row");
-using rowfill::aligned16;
-using rowfill::kNone;
-using rowfill::stage_row;
-using rowfill::store_quad;
+using namespace rowkit;                                     // kThreads, kWaves, kMaxW: dRm / dL row + two int per quad, 48 KiB of LDS at most
 
 struct LrMaps {                                             // the nmaps stage maps of one call, by value in the kernel arguments
     const float *dl[4];
@@ -41,14 +34,13 @@ __device__ __forceinline__ int lr_code(float d, int x, int W, const float *__res
     return fabsf(d - r) <= tau ? 1 : 0;                     // NaN r -> 0
 }
 
-// grid (H, B, nmaps), 256 threads: one workgroup per row.  Thread t owns the quads t, t + 256, ... (pixels 4q .. 4q + 3) of the
-// row; W <= 8192 gives at most 8 quads, so the code == 1 flags of its pixels fit in one 32-bit word (bit 4k + i).
+// grid (H, B, nmaps), 256 threads: one workgroup per row, thread t owns the quads t, t + 256, ... of it (lws_rowkit.h).
 // LDS (dynamic): row[4 nq] floats (first dRm, then dL for the fill), last[nq], first[nq] ints (fill only).
 __global__ __launch_bounds__(kThreads) void k_lr_check(LrMaps m, int H, int W, float tau, int fill, int *__restrict__ row_kept)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ int s_wl[kWaves], s_wf[kWaves], s_kept[kWaves];
-    const int y = blockIdx.x, b = blockIdx.y, s = blockIdx.z, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int y = blockIdx.x, b = blockIdx.y, s = blockIdx.z, t = threadIdx.x;
     const int nq = (W + 3) >> 2;
     float *s_row = lds;
     int *s_last = reinterpret_cast<int *>(lds + 4 * nq), *s_first = s_last + nq;
@@ -56,72 +48,42 @@ __global__ __launch_bounds__(kThreads) void k_lr_check(LrMaps m, int H, int W, f
     const float *dl = m.dl[s] + row, *rm = m.drm[s] + row;
     float *out = m.out[s] + row, *rt = m.right[s] ? m.right[s] + row : nullptr;
     uint8_t *mk = m.mask[s] + row;
-    const bool vdl = aligned16(dl), vout = aligned16(out), vrt = aligned16(rt), vmk = ((uintptr_t)mk & 3) == 0;
+    const bool vdl = aligned16(dl), vout = aligned16(out), vrt = aligned16(rt), vmk = aligned4(mk);
 
     stage_row(s_row, rm, W, nq);                            // the mirrored right-view row
     __syncthreads();
 
     // ---- phase 1: codes, mask, right, out (no fill), kept count, per-quad last / first consistent pixel ----
-    unsigned bits = 0;
-    int kept = 0;
-    const float nan = __builtin_nanf("");
+    KeptFlags kept;
     for (int k = 0, q = t; q < nq; ++k, q += kThreads) {
         const int x = 4 * q;
         float d[4];
-        if (vdl && x + 4 <= W) {
-            const float4 v = *reinterpret_cast<const float4 *>(dl + x);
-            d[0] = v.x, d[1] = v.y, d[2] = v.z, d[3] = v.w;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) d[i] = x + i < W ? dl[x + i] : nan;      // beyond the row: code 0, never kept
-        }
         int c[4];
+        load_quad(dl, x, W, vdl, __builtin_nanf(""), d);    // NaN beyond the row: code 0, never kept
 #pragma unroll
         for (int i = 0; i < 4; ++i) c[i] = lr_code(d[i], x + i, W, s_row, tau);
-        if (vmk && x + 4 <= W) {
-            *reinterpret_cast<uchar4 *>(mk + x) = make_uchar4((uint8_t)c[0], (uint8_t)c[1], (uint8_t)c[2], (uint8_t)c[3]);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (x + i < W) mk[x + i] = (uint8_t)c[i];
-        }
+        store_codes(mk, x, W, vmk, c);
         if (rt) {                                           // right[x] = dRm[W-1-x]
             const int xr = W - 1 - x;
             store_quad(rt, x, W, vrt, s_row[xr], s_row[max(xr - 1, 0)], s_row[max(xr - 2, 0)], s_row[max(xr - 3, 0)]);
         }
-        if (!fill) store_quad(out, x, W, vout, c[0] == 1 ? d[0] : 0.0f, c[1] == 1 ? d[1] : 0.0f, c[2] == 1 ? d[2] : 0.0f,
-                              c[3] == 1 ? d[3] : 0.0f);
-        int last = -1, first = kNone;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const bool ok = c[i] == 1;
-            kept += ok ? 1 : 0;
-            bits |= (ok ? 1u : 0u) << (4 * k + i);
-            last = ok ? x + i : last;
-        }
-#pragma unroll
-        for (int i = 3; i >= 0; --i) first = c[i] == 1 ? x + i : first;
-        if (fill) {
-            s_last[q] = last;
-            s_first[q] = first;
-        }
+        if (!fill) store_kept(out, x, W, vout, c, d);
+        bool ok[4];
+        kept.add(k, c, ok);
+        if (fill) quad_last_first(ok, x, s_last[q], s_first[q]);
     }
 
-    if (row_kept) {
-        for (int o = 32; o > 0; o >>= 1) kept += __shfl_down(kept, o, 64);
-        if (lane == 0) s_kept[wave] = kept;
-    }
+    if (row_kept) wave_sums<1>({kept.count}, s_kept);
     if (fill) {
         __syncthreads();                                    // every read of the staged dRm row is done
         stage_row(s_row, dl, W, nq);                        // the left-view row, for the fill values
-
-        // ---- phases 2 and 3 (lws_rowfill.h): scans of last / first over the quads, then consistent pixels keep d and the others
-        // take the background value of their row
-        rowfill::fill_row(s_row, s_last, s_first, s_wl, s_wf, bits, nq, W, out, vout);
+        // phases 2 and 3: scans of last / first over the quads, then consistent pixels keep d and the others take the background
+        // value of their row
+        fill_row(s_row, s_last, s_first, s_wl, s_wf, kept.bits, nq, W, out, vout);
     }
     if (row_kept) {
         __syncthreads();
-        if (t == 0) row_kept[((int64_t)s * gridDim.y + b) * H + y] = (s_kept[0] + s_kept[1]) + (s_kept[2] + s_kept[3]);
+        if (t == 0) row_kept[((int64_t)s * gridDim.y + b) * H + y] = row_total<1>(s_kept, 0);
     }
 }
 
@@ -180,14 +142,10 @@ int lws_lr_check(const float *const dL[4], const float *const dRm[4], int nmaps,
                  float *const out[4], uint8_t *const mask[4], float *const right[4], int32_t *row_kept, void *stream)
 {
     LWS_CHECK_ARG(dL && dRm && out && mask, "lr_check: null pointer");
-    LWS_CHECK_ARG(nmaps >= 1 && nmaps <= 4, "lr_check: nmaps %d outside 1..4", nmaps);
-    LWS_CHECK_ARG(B >= 1 && B <= 65535 && H >= 1 && W >= 1, "lr_check: bad shape B=%d H=%d W=%d", B, H, W);
-    LWS_CHECK_ARG(W <= kMaxW, "lr_check: W=%d exceeds %d (the row is staged in LDS)", W, kMaxW);
-    LWS_CHECK_ARG(tau >= 0.0f && tau <= 3.4028234663852886e38f, "lr_check: tau must be finite and >= 0, got %g", (double)tau);
-    LWS_CHECK_ARG(fill == 0 || fill == 1, "lr_check: fill %d (0 = zero, 1 = background fill)", fill);
+    const int rc = check_row_check_args("lr_check", "(the row is staged in LDS)", kMaxW, dL, dRm, nmaps, B, H, W, tau, fill, out, mask);
+    if (rc != LWS_OK) return rc;
     LrMaps m = {};
     for (int s = 0; s < nmaps; ++s) {
-        LWS_CHECK_ARG(dL[s] && dRm[s] && out[s] && mask[s], "lr_check: map %d has a null pointer", s);
         m.dl[s] = dL[s];
         m.drm[s] = dRm[s];
         m.out[s] = out[s];

@@ -7,7 +7,7 @@
 //                 (-1: invalid pixel), size[p] = the pixels of the tile-local component at its root, 0 elsewhere
 //   k_sp_border   one thread per pair of pixels across a tile edge: unions of the tile-local roots, agent-scope atomics
 //   k_sp_flatten  every tile-local root finds its global root, points at it and adds its size to the global root's
-//   k_sp_apply    one workgroup per row: codes, out (with the row fill of lws_rowfill.h), labels, per-row counts
+//   k_sp_apply    one workgroup per row: codes, out (with the row fill of lws_rowkit.h), labels, per-row counts
 //   k_sp_counts   (counts != NULL) one workgroup per image: the per-row counts summed in a fixed order
 //
 // The invariant every loop rests on: parent[p] <= p in raster order, always (a root is the FIRST pixel of its set, a union hangs
@@ -21,21 +21,16 @@
 // atomic add per tile-local component to its global root: a 450 k-pixel component costs a few hundred adds on its word, not 450 k.
 // Integer atomics only, so the result does not depend on their order.  0 bytes of scratch.
 #include "lws_common.h"
-#include "lws_rowfill.h"
+#include "lws_rowkit.h"
 
 namespace lws {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-static_assert(kThreads == rowfill::kFillThreads, "k_sp_apply runs rowfill::fill_row");
+using namespace rowkit;                                     // kThreads, kWaves, kMaxW and the pieces of k_sp_apply
 constexpr int kTH = 32, kTW = 64;                           // the tile of k_sp_tile
 constexpr int kTile = kTH * kTW;
 constexpr int kQuadsPerThread = kTile / 4 / kThreads;       // 2
-using rowfill::aligned16;
-using rowfill::store_quad;
-
 __host__ __device__ __forceinline__ bool aligned(const void *p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
 
 __device__ __forceinline__ bool sp_valid(float d, bool ok) { return ok && __builtin_isfinite(d) && d > 0.0f; }
@@ -254,17 +249,17 @@ __global__ __launch_bounds__(kThreads) void k_sp_flatten(int HW, int *__restrict
     __hip_atomic_fetch_add(sz + r, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// grid (H, B), 256 threads: one workgroup per row; thread t owns the quads t, t + 256, ...  parent[] and size[] were written by
-// earlier launches: plain loads.  out may be disp and mask_out may be mask (no __restrict__ on them): a thread reads its quad
-// before it writes it, and the fill stages the row before any of it is written.  LDS (dynamic, fill only): row[4 nq] floats,
-// last[nq], first[nq] ints.
+// grid (H, B), 256 threads: one workgroup per row, thread t owns the quads t, t + 256, ... of it (lws_rowkit.h).  parent[] and
+// size[] were written by earlier launches: plain loads.  out may be disp and mask_out may be mask (no __restrict__ on them): a
+// thread reads its quad before it writes it, and the fill stages the row before any of it is written.  LDS (dynamic, fill only):
+// row[4 nq] floats, last[nq], first[nq] ints.
 __global__ __launch_bounds__(kThreads) void k_sp_apply(const float *disp, const uint8_t *mask, int H, int W, int max_size, int fill,
                                                       const int *__restrict__ parent, const int *__restrict__ size, float *out,
                                                       uint8_t *mask_out, int32_t *__restrict__ labels, int *__restrict__ row_cnt)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    __shared__ int s_wl[kWaves], s_wf[kWaves], s_n[kWaves][3];
-    const int y = blockIdx.x, b = blockIdx.y, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    __shared__ int s_wl[kWaves], s_wf[kWaves], s_n[kWaves * 3];
+    const int y = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
     const int nq = (W + 3) >> 2;
     float *s_row = lds;
     int *s_last = reinterpret_cast<int *>(lds + 4 * nq), *s_first = s_last + nq;
@@ -274,21 +269,15 @@ __global__ __launch_bounds__(kThreads) void k_sp_apply(const float *disp, const 
     const int *par = parent + img, *sz = size + img;
     float *op = out + row;
     uint8_t *mo = mask_out + row;
-    const bool vd = aligned16(dp), vout = aligned16(op), vmk = aligned(mk, 4), vmo = aligned(mo, 4);
+    const bool vd = aligned16(dp), vout = aligned16(op), vmk = aligned4(mk), vmo = aligned4(mo);
 
-    unsigned bits = 0;
-    int n_valid = 0, n_kept = 0, n_removed = 0;
+    KeptFlags kept;
+    int n_valid = 0, n_removed = 0;
     for (int k = 0, q = t; q < nq; ++k, q += kThreads) {
         const int x = 4 * q;
         float d[4];
         int m[4] = {0, 0, 0, 0};
-        if (vd && x + 4 <= W) {
-            const float4 v = *reinterpret_cast<const float4 *>(dp + x);
-            d[0] = v.x, d[1] = v.y, d[2] = v.z, d[3] = v.w;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) d[i] = x + i < W ? dp[x + i] : 0.0f;
-        }
+        load_quad(dp, x, W, vd, 0.0f, d);
         if (mk) {
             if (vmk && x + 4 <= W) {
                 const uchar4 v = *reinterpret_cast<const uchar4 *>(mk + x);
@@ -299,7 +288,6 @@ __global__ __launch_bounds__(kThreads) void k_sp_apply(const float *disp, const 
             }
         }
         int c[4], lab[4];
-        bool ok[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int p = y * W + x + i;
@@ -315,40 +303,26 @@ __global__ __launch_bounds__(kThreads) void k_sp_apply(const float *disp, const 
                 n_valid += 1;
                 n_removed += speckle && r == p ? 1 : 0;
             }
-            ok[i] = c[i] == 1;
-            n_kept += ok[i] ? 1 : 0;
-            bits |= (ok[i] ? 1u : 0u) << ((4 * k + i) & 31);
         }
-        if (vmo && x + 4 <= W) {
-            *reinterpret_cast<uchar4 *>(mo + x) = make_uchar4((uint8_t)c[0], (uint8_t)c[1], (uint8_t)c[2], (uint8_t)c[3]);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (x + i < W) mo[x + i] = (uint8_t)c[i];
-        }
+        bool ok[4];
+        kept.add(k, c, ok);
+        store_codes(mo, x, W, vmo, c);
         if (labels) store_quad_i(labels + row, x, W, lab);
         if (fill) {
-            rowfill::quad_last_first(ok, x, s_last[q], s_first[q]);
+            quad_last_first(ok, x, s_last[q], s_first[q]);
         } else {
-            store_quad(op, x, W, vout, ok[0] ? d[0] : 0.0f, ok[1] ? d[1] : 0.0f, ok[2] ? d[2] : 0.0f, ok[3] ? d[3] : 0.0f);
+            store_kept(op, x, W, vout, c, d);
         }
     }
-    if (row_cnt) {
-        for (int o = 32; o > 0; o >>= 1) {
-            n_valid += __shfl_down(n_valid, o, 64);
-            n_kept += __shfl_down(n_kept, o, 64);
-            n_removed += __shfl_down(n_removed, o, 64);
-        }
-        if (lane == 0) s_n[wave][0] = n_valid, s_n[wave][1] = n_kept, s_n[wave][2] = n_removed;
-    }
-    if (fill) {                                             // W <= kFillMaxW: at most 8 quads per thread, `bits` holds them all
-        rowfill::stage_row(s_row, dp, W, nq);               // (out may be disp itself: the row is read before it is written)
+    if (row_cnt) wave_sums<3>({n_valid, kept.count, n_removed}, s_n);
+    if (fill) {
+        stage_row(s_row, dp, W, nq);                        // (out may be disp itself: the row is read before it is written)
         __syncthreads();
-        rowfill::fill_row(s_row, s_last, s_first, s_wl, s_wf, bits, nq, W, op, vout);
+        fill_row(s_row, s_last, s_first, s_wl, s_wf, kept.bits, nq, W, op, vout);
     }
     if (row_cnt) {
         __syncthreads();
-        if (t < 3) row_cnt[3 * ((int64_t)b * H + y) + t] = (s_n[0][t] + s_n[1][t]) + (s_n[2][t] + s_n[3][t]);
+        if (t < 3) row_cnt[3 * ((int64_t)b * H + y) + t] = row_total<3>(s_n, t);
     }
 }
 
@@ -411,8 +385,7 @@ int lws_speckle_filter(const float *disp, const uint8_t *mask, int B, int H, int
                   (double)max_diff);
     LWS_CHECK_ARG(max_size >= 0, "speckle_filter: max_size must be >= 0, got %d", max_size);
     LWS_CHECK_ARG(fill == 0 || fill == 1, "speckle_filter: fill %d (0 = zero, 1 = background fill)", fill);
-    LWS_CHECK_ARG(!fill || W <= rowfill::kFillMaxW, "speckle_filter: fill needs W <= %d (the row is staged in LDS), got %d",
-                  rowfill::kFillMaxW, W);
+    LWS_CHECK_ARG(!fill || W <= kMaxW, "speckle_filter: fill needs W <= %d (the row is staged in LDS), got %d", kMaxW, W);
     LWS_CHECK_ARG(aligned(disp, 4) && aligned(out, 4) && aligned(workspace, 16) && aligned(labels, 4) && aligned(counts, 8),
                   "speckle_filter: disp / out / labels must be 4-byte, counts 8-byte, workspace 16-byte aligned");
     const int64_t px = (int64_t)B * H * W;

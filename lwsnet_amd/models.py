@@ -207,22 +207,24 @@ class LWSNet:
         return torch.cuda.device(self.device)
 
     # ---- forward -------------------------------------------------------------------------------
-    def _input(self, x, name):
-        return as_input(x, name, self.device)
-
-    def forward(self, left_input, right_input, out=None):
-        """model(left, right) -> [pred1 .. pred4] (models.py:106-164).  `out` (not in the reference): optional list of
-        four pre-allocated [B,1,H,W] device tensors (None entries are allocated) that receive the stage maps."""
+    def _pair(self, left_input, right_input, who):
+        """What every forward starts with: a device and parameters must be there (`who`: the caller, for the message), both inputs
+        become contiguous float32 [B,3,H,W] device tensors of one shape that the network takes.  Returns (left, right, B, H, W)."""
         if self.device is None:
             raise RuntimeError("no HIP device is available and lwsnet_amd has no CPU fallback")
         if self._params is None:
-            raise RuntimeError("set_state_dict() must be called before forward()")
-        left = self._input(left_input, "left_input")
-        right = self._input(right_input, "right_input")
+            raise RuntimeError(f"set_state_dict() must be called before {who}()")
+        left, right = as_input(left_input, "left_input", self.device), as_input(right_input, "right_input", self.device)
         if left.shape != right.shape:
             raise ValueError(f"left/right shapes differ: {tuple(left.shape)} vs {tuple(right.shape)}")
         B, _, H, W = left.shape
         check_size(H, W, self.maxdisplist[0])
+        return left, right, B, H, W
+
+    def forward(self, left_input, right_input, out=None):
+        """model(left, right) -> [pred1 .. pred4] (models.py:106-164).  `out` (not in the reference): optional list of
+        four pre-allocated [B,1,H,W] device tensors (None entries are allocated) that receive the stage maps."""
+        left, right, B, H, W = self._pair(left_input, right_input, "forward")
         with torch.cuda.device(self.device):
             return [DisparityTensor.wrap(p) for p in ops.forward(self._h, left, right, out)]      # models.py:106-164
 
@@ -233,16 +235,7 @@ class LWSNet:
         left-reference network on the mirrored, swapped pair, so the call is one lws_lr_pairs, ONE lws_forward of 2B pairs and
         one lws_lr_check of the four stages (include/lwsnet_hip.h).  A pixel is kept when |d - right-view d at x - d| <= tau;
         `fill` gives the others the background value of their row.  Returns an LRResult."""
-        if self.device is None:
-            raise RuntimeError("no HIP device is available and lwsnet_amd has no CPU fallback")
-        if self._params is None:
-            raise RuntimeError("set_state_dict() must be called before forward_lr()")
-        left = self._input(left_input, "left_input")
-        right = self._input(right_input, "right_input")
-        if left.shape != right.shape:
-            raise ValueError(f"left/right shapes differ: {tuple(left.shape)} vs {tuple(right.shape)}")
-        B, _, H, W = left.shape
-        check_size(H, W, self.maxdisplist[0])
+        left, right, B, H, W = self._pair(left_input, right_input, "forward_lr")
         with torch.cuda.device(self.device):
             left2, right2 = ops.lr_pairs(left, right)
             maps = ops.forward(self._h, left2, right2)
@@ -258,16 +251,7 @@ class LWSNet:
         z-buffer.  A pixel is kept when the nearest surface that lands on its right-view column is at most tau nearer; `fill`
         gives the others the background value of their row.  It finds occlusions, not mismatches (forward_lr does, at the price
         of a second network).  Returns an OccResult."""
-        if self.device is None:
-            raise RuntimeError("no HIP device is available and lwsnet_amd has no CPU fallback")
-        if self._params is None:
-            raise RuntimeError("set_state_dict() must be called before forward_occ()")
-        left = self._input(left_input, "left_input")
-        right = self._input(right_input, "right_input")
-        if left.shape != right.shape:
-            raise ValueError(f"left/right shapes differ: {tuple(left.shape)} vs {tuple(right.shape)}")
-        B, _, H, W = left.shape
-        check_size(H, W, self.maxdisplist[0])
+        left, right, B, H, W = self._pair(left_input, right_input, "forward_occ")
         with torch.cuda.device(self.device):
             dl = ops.forward(self._h, left, right)
             out, mask, rmaps, row_kept = ops.occlusion_check(dl, tau, fill, want_right=True)
@@ -310,11 +294,7 @@ class ForwardPool:
 
     def submit(self, left_input, right_input, out=None):
         m = self._model
-        left, right = m._input(left_input, "left_input"), m._input(right_input, "right_input")
-        if left.shape != right.shape:
-            raise ValueError(f"left/right shapes differ: {tuple(left.shape)} vs {tuple(right.shape)}")
-        B, _, H, W = left.shape
-        check_size(H, W, m.maxdisplist[0])
+        left, right, B, H, W = m._pair(left_input, right_input, "submit")
         outs = ops.stage_outputs(out, B, H, W, left.device)          # validated: raw pointers go to a worker thread
         ticket = ctypes.c_int64(-1)
         with torch.cuda.device(m.device):

@@ -30,6 +30,46 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+def _arr4(ts):
+    """The device pointers of up to four tensors as the void *[4] of the C ABI (missing entries: NULL)."""
+    return (ctypes.c_void_p * 4)(*[t.data_ptr() for t in ts])
+
+
+def _imagenet_stats():
+    """The (mean, std) float[3] arguments of the kernels that normalise an image for the network."""
+    from .synth import IMAGENET_MEAN, IMAGENET_STD
+    return tuple((ctypes.c_float * 3)(*[float(v) for v in a]) for a in (IMAGENET_MEAN, IMAGENET_STD))
+
+
+def _disp_map(t, name):
+    """t as a contiguous float32 device tensor that must be [B,1,H,W]."""
+    t = _dev(t, name)
+    if t.dim() != 4 or t.shape[1] != 1:
+        raise ValueError(f"{name} must be [B,1,H,W]; got {tuple(t.shape)}")
+    return t
+
+
+def _stage_maps(**lists):
+    """name = list of 1-4 stage maps: every map float32 on one device and of the shape [B,1,H,W] of the first.  Returns the lists
+    of contiguous tensors, that shape and the device."""
+    ts = {name: [_dev(t, f"{name}[{s}]") for s, t in enumerate(v)] for name, v in lists.items()}
+    first = next(iter(lists))
+    shape, dev = tuple(_disp_map(ts[first][0], f"{first}[0]").shape), ts[first][0].device
+    for name, v in ts.items():
+        for s, t in enumerate(v):
+            if tuple(t.shape) != shape or t.device != dev:
+                raise ValueError(f"{name}[{s}] must be {shape} on {dev}; got {tuple(t.shape)} on {t.device}")
+    return list(ts.values()), shape, dev
+
+
+def _check_outputs(n, shape, dev, want_right):
+    """The (out, mask, right, row_kept) outputs of a check of n maps of `shape` = [B,1,H,W]; right is None unless want_right."""
+    out = [torch.empty(shape, device=dev, dtype=torch.float32) for _ in range(n)]
+    mask = [torch.empty(shape, device=dev, dtype=torch.uint8) for _ in range(n)]
+    right = [torch.empty(shape, device=dev, dtype=torch.float32) for _ in range(n)] if want_right else None
+    return out, mask, right, torch.empty((n, shape[0], shape[2]), device=dev, dtype=torch.int32)
+
+
 def _code_map(mask, d):
     """mask: None, or the uint8 code map of the maps d (same shape and device), made contiguous."""
     if mask is None:
@@ -213,7 +253,6 @@ def forward(handle, left, right, out=None):
 def preprocess_rgb8(rgb_u8, out=None):
     """ToTensor + Normalize(imagenet) of inference.py:83-85,102-103 on the device: rgb_u8 [B,H,W,3] uint8 -> [B,3,H,W] float32,
     bit for bit lwsnet_amd.imageio.to_input (numpy)."""
-    from .synth import IMAGENET_MEAN, IMAGENET_STD
     if not isinstance(rgb_u8, torch.Tensor) or not rgb_u8.is_cuda or rgb_u8.dtype != torch.uint8 or rgb_u8.dim() != 4 or rgb_u8.shape[3] != 3:
         raise ValueError("rgb_u8 must be a [B,H,W,3] uint8 tensor on a HIP device")
     rgb_u8 = rgb_u8.contiguous()
@@ -222,8 +261,7 @@ def preprocess_rgb8(rgb_u8, out=None):
         out = torch.empty((B, 3, H, W), device=rgb_u8.device, dtype=torch.float32)
     elif tuple(out.shape) != (B, 3, H, W) or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
         raise ValueError("out must be a contiguous [B,3,H,W] float32 device tensor")
-    mean = (ctypes.c_float * 3)(*[float(v) for v in IMAGENET_MEAN])
-    std = (ctypes.c_float * 3)(*[float(v) for v in IMAGENET_STD])
+    mean, std = _imagenet_stats()
     with torch.cuda.device(rgb_u8.device):
         _lib.check(_lib.load().lws_preprocess_rgb8(_ptr(rgb_u8), _ptr(out), B, H, W, mean, std, _stream()), "lws_preprocess_rgb8")
     return out
@@ -275,9 +313,8 @@ def stage_metrics(preds, gt, row_offset, maxdisp, mode):
     work = _workspace(lib, "lws_stage_metrics_workspace", g.device, B, Hg, W)
     counts = torch.empty((4, B, 2), device=g.device, dtype=torch.int64)
     abs_sum = torch.empty((4, B), device=g.device, dtype=torch.float64)
-    arr = ctypes.c_void_p * 4
     with torch.cuda.device(g.device):
-        _lib.check(lib.lws_stage_metrics(arr(*[p.data_ptr() for p in ps]), B, Hg + row_offset, W, row_offset, _ptr(g), Hg,
+        _lib.check(lib.lws_stage_metrics(_arr4(ps), B, Hg + row_offset, W, row_offset, _ptr(g), Hg,
                                          float(maxdisp), int(mode), _ptr(work), _ptr(counts), _ptr(abs_sum), _stream()),
                    "lws_stage_metrics")
     return counts, abs_sum
@@ -304,28 +341,12 @@ def lr_check(dl, drm, tau, fill, want_right=True):
     unless want_right), and an int32 [nmaps,B,H] device tensor of the consistent pixels per row."""
     if not isinstance(dl, (list, tuple)) or not isinstance(drm, (list, tuple)) or len(dl) != len(drm) or not 1 <= len(dl) <= 4:
         raise ValueError("dl and drm must be lists of the same 1-4 stage maps")
-    ls = [_dev(t, f"dl[{s}]") for s, t in enumerate(dl)]
-    rs = [_dev(t, f"drm[{s}]") for s, t in enumerate(drm)]
-    shape, dev = tuple(ls[0].shape), ls[0].device
-    if len(shape) != 4 or shape[1] != 1:
-        raise ValueError(f"dl[0] must be [B,1,H,W]; got {shape}")
-    for name, ts in (("dl", ls), ("drm", rs)):
-        for s, t in enumerate(ts):
-            if tuple(t.shape) != shape or t.device != dev:
-                raise ValueError(f"{name}[{s}] must be {shape} on {dev}; got {tuple(t.shape)} on {t.device}")
+    (ls, rs), shape, dev = _stage_maps(dl=dl, drm=drm)
     B, _, H, W = shape
-    n = len(ls)
-    out = [torch.empty(shape, device=dev, dtype=torch.float32) for _ in range(n)]
-    mask = [torch.empty(shape, device=dev, dtype=torch.uint8) for _ in range(n)]
-    right = [torch.empty(shape, device=dev, dtype=torch.float32) for _ in range(n)] if want_right else None
-    row_kept = torch.empty((n, B, H), device=dev, dtype=torch.int32)
-
-    def arr(ts):
-        return (ctypes.c_void_p * 4)(*[t.data_ptr() for t in ts])
-
+    out, mask, right, row_kept = _check_outputs(len(ls), shape, dev, want_right)
     with torch.cuda.device(dev):
-        _lib.check(_lib.load().lws_lr_check(arr(ls), arr(rs), n, B, H, W, float(tau), int(bool(fill)), arr(out), arr(mask),
-                                            arr(right if right is not None else []), _ptr(row_kept), _stream()), "lws_lr_check")
+        _lib.check(_lib.load().lws_lr_check(_arr4(ls), _arr4(rs), len(ls), B, H, W, float(tau), int(bool(fill)), _arr4(out), _arr4(mask),
+                                            _arr4(right or []), _ptr(row_kept), _stream()), "lws_lr_check")
     return out, mask, right, row_kept
 
 
@@ -337,27 +358,12 @@ def occlusion_check(dl, tau, fill, want_right=True):
     [nmaps,B,H] device tensor of the visible pixels per row."""
     if not isinstance(dl, (list, tuple)) or not 1 <= len(dl) <= 4:
         raise ValueError("dl must be a list of 1-4 stage maps")
-    ls = [_dev(t, f"dl[{s}]") for s, t in enumerate(dl)]
-    shape, dev = tuple(ls[0].shape), ls[0].device
-    if len(shape) != 4 or shape[1] != 1:
-        raise ValueError(f"dl[0] must be [B,1,H,W]; got {shape}")
-    for s, t in enumerate(ls):
-        if tuple(t.shape) != shape or t.device != dev:
-            raise ValueError(f"dl[{s}] must be {shape} on {dev}; got {tuple(t.shape)} on {t.device}")
+    (ls,), shape, dev = _stage_maps(dl=dl)
     B, _, H, W = shape
-    n = len(ls)
-    out = [torch.empty(shape, device=dev, dtype=torch.float32) for _ in range(n)]
-    mask = [torch.empty(shape, device=dev, dtype=torch.uint8) for _ in range(n)]
-    right = [torch.empty(shape, device=dev, dtype=torch.float32) for _ in range(n)] if want_right else None
-    row_kept = torch.empty((n, B, H), device=dev, dtype=torch.int32)
-
-    def arr(ts):
-        return (ctypes.c_void_p * 4)(*[t.data_ptr() for t in ts])
-
+    out, mask, right, row_kept = _check_outputs(len(ls), shape, dev, want_right)
     with torch.cuda.device(dev):
-        _lib.check(_lib.load().lws_occlusion_check(arr(ls), n, B, H, W, float(tau), int(bool(fill)), arr(out), arr(mask),
-                                                   arr(right if right is not None else []), _ptr(row_kept), _stream()),
-                   "lws_occlusion_check")
+        _lib.check(_lib.load().lws_occlusion_check(_arr4(ls), len(ls), B, H, W, float(tau), int(bool(fill)), _arr4(out), _arr4(mask),
+                                                   _arr4(right or []), _ptr(row_kept), _stream()), "lws_occlusion_check")
     return out, mask, right, row_kept
 
 
@@ -367,9 +373,7 @@ def _geometry_inputs(disp, mask, cameras, min_disp, max_depth):
     import math
 
     from .geometry import camera_rows
-    d = _dev(disp, "disp")
-    if d.dim() != 4 or d.shape[1] != 1:
-        raise ValueError(f"disp must be [B,1,H,W]; got {tuple(d.shape)}")
+    d = _disp_map(disp, "disp")
     mask = _code_map(mask, d)
     if not (math.isfinite(min_disp) and min_disp > 0):
         raise ValueError(f"min_disp must be finite and > 0, got {min_disp}")
@@ -434,9 +438,7 @@ def speckle_filter(disp, max_size, max_diff=1.0, mask=None, fill=False, want_lab
     pixels are valid); fill: give the removed and invalid pixels the background value of their row.  The workspace (8 bytes per
     pixel) and the outputs are allocated per call on the current stream.  Returns a SpeckleResult."""
     import math
-    d = _dev(disp, "disp")
-    if d.dim() != 4 or d.shape[1] != 1:
-        raise ValueError(f"disp must be [B,1,H,W]; got {tuple(d.shape)}")
+    d = _disp_map(disp, "disp")
     mask = _code_map(mask, d)
     if not (math.isfinite(max_diff) and max_diff >= 0):
         raise ValueError(f"max_diff must be finite and >= 0, got {max_diff}")
@@ -487,9 +489,7 @@ def wmedian_filter(disp, radius, rgb=None, wlut=None, mask=None, fill_min=0):
     code map (only code-1 pixels are valid); fill_min: an invalid pixel with at least this many candidates takes their median (0:
     never).  The outputs are allocated per call on the current stream.  Returns a WMedianResult."""
     import numpy as np
-    d = _dev(disp, "disp")
-    if d.dim() != 4 or d.shape[1] != 1:
-        raise ValueError(f"disp must be [B,1,H,W]; got {tuple(d.shape)}")
+    d = _disp_map(disp, "disp")
     if isinstance(radius, bool) or int(radius) != radius or not 1 <= radius <= 3:
         raise ValueError(f"radius must be 1, 2 or 3, got {radius!r}")
     if isinstance(fill_min, bool) or int(fill_min) != fill_min or fill_min < 0 or fill_min >= 2 ** 31:
@@ -527,8 +527,6 @@ def rectify_pair(raw_left, raw_right, params, out_hw, origin=(0, 0), border=0, w
     [B,3,H,W] (the bits of preprocess_rgb8(rect)), "valid" uint8 [B,1,H,W], "map" float32 [B,H,W,2].  The outputs are allocated per
     call on the current stream."""
     import numpy as np
-
-    from .synth import IMAGENET_MEAN, IMAGENET_STD
     for name, t in (("raw_left", raw_left), ("raw_right", raw_right)):
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
             raise RuntimeError(f"{name} must be a torch tensor on a HIP device (the rectification has no CPU fallback)")
@@ -562,8 +560,7 @@ def rectify_pair(raw_left, raw_right, params, out_hw, origin=(0, 0), border=0, w
         if want:
             res[key] = (pair[0], pair[1])
         arrays.append((ctypes.c_void_p * 2)(*[pair[c].data_ptr() if want else None for c in range(2)]))
-    mean = (ctypes.c_float * 3)(*[float(v) for v in IMAGENET_MEAN])
-    std = (ctypes.c_float * 3)(*[float(v) for v in IMAGENET_STD])
+    mean, std = _imagenet_stats()
     raws = (ctypes.c_void_p * 2)(raw_left.data_ptr(), raw_right.data_ptr())
     with torch.cuda.device(dev):
         _lib.check(_lib.load().lws_rectify_pair(raws, _ptr(params), B, Hs, Ws, H, W, x0, y0, int(border), mean, std, *arrays, _stream()),

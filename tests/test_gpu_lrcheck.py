@@ -119,6 +119,45 @@ def test_lr_check_without_row_kept(dev, hip_lib):
     assert_bits(mask, wm, "mask")
 
 
+@pytest.mark.parametrize("skew", [0, 1], ids=["aligned", "skewed"])
+@pytest.mark.parametrize("W", [3, 8, 8189, 8192])
+def test_lr_check_row_corners(dev, hip_lib, W, skew):
+    """The corners of the row scaffolding, two rows each (the kernel shares nothing between rows): less than one quad (W = 3), a
+    thread's eighth quad (W = 8192: bit 31 of its flags word), that quad with a ragged tail (8189), and every base one float past a
+    16-byte boundary, where an aligned width (8, 8192) takes the scalar path too; fill off and on, right / row_kept there and not."""
+    import ctypes
+    from lwsnet_amd import _lib
+    B, H = 1, 2
+    n = B * H * W
+    dl_np, drm_np = maps(B, H, W, W)
+
+    def place(a=None, dtype=torch.float32):
+        t = torch.empty(n + 8, dtype=dtype, device=dev)[4 + skew:4 + skew + n].view(B, 1, H, W)
+        assert dtype != torch.float32 or t.data_ptr() % 16 == 4 * skew
+        return t if a is None else t.copy_(cu(a, dev))
+
+    arr = ctypes.c_void_p * 4
+    for fill in (0, 1):
+        wo, wm, wr, wk = R.lr_check(dl_np, drm_np, 1.0, fill)
+        if W >= 8189:
+            assert (wm[..., 7171::4] == 1).any(), "a kept pixel under bit 31 of a thread's flags"
+        for optional in (True, False):
+            dl, drm, out, mask = place(dl_np), place(drm_np), place(), place(dtype=torch.uint8)
+            right = place() if optional else None
+            kept = torch.empty((1, B, H), dtype=torch.int32, device=dev) if optional else None
+            with torch.cuda.device(dev):
+                _lib.check(hip_lib.lws_lr_check(arr(dl.data_ptr()), arr(drm.data_ptr()), 1, B, H, W, 1.0, fill, arr(out.data_ptr()),
+                                                arr(mask.data_ptr()), arr(right.data_ptr()) if optional else arr(),
+                                                ctypes.c_void_p(kept.data_ptr()) if optional else None,
+                                                ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "lws_lr_check")
+            what = f"W={W} skew={skew} fill={fill} optional={optional}"
+            assert_bits(out, wo, what + " out")
+            assert_bits(mask, wm, what + " mask")
+            if optional:
+                assert_bits(right, wr, what + " right")
+                assert_bits(kept[0], wk, what + " row_kept")
+
+
 def test_lr_check_is_batch_independent(dev, hip_lib):
     from lwsnet_amd import ops
     H, W = 63, 255

@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-WIDTHS = [1, 3, 4, 5, 63, 64, 65, 257, 1023, 1232, 8192]
+WIDTHS = [1, 3, 4, 5, 63, 64, 65, 257, 1023, 1232, 8189, 8192]
 TAUS = (0.0, 0.5, 1.0)
 _REF = {}
 
@@ -156,7 +156,7 @@ def test_ramp_onto_one_column_constant_zero_and_all_nan_rows(dev, hip_lib, W):
             assert wk[0].tolist() == [1 if tau < 1 or W == 1 else 2, W, 0]
 
 
-@pytest.mark.parametrize("W", [5, 64, 1232])
+@pytest.mark.parametrize("W", [5, 64, 1232, 8189])
 def test_addresses_offset_by_one_float_and_in_place(dev, hip_lib, W):
     """Every tensor one float past a 16-byte boundary (the scalar load / store path of an aligned width too), and out[s] == dL[s]."""
     B, H = 2, 3

@@ -179,6 +179,55 @@ def test_c_abi_optional_arguments_and_in_place(dev, hip_lib):
         assert_bits(m2, wm, f"in place mask_out fill={fill}")
 
 
+@pytest.mark.parametrize("skew", [0, 1], ids=["aligned", "skewed"])
+@pytest.mark.parametrize("W", [3, 8, 8189, 8192])
+def test_apply_row_corners(dev, hip_lib, W, skew):
+    """The corners of k_sp_apply's row scaffolding, two rows each: less than one quad (W = 3), a thread's eighth quad (W = 8192, the
+    widest row the fill takes: bit 31 of its flags word), that quad with a ragged tail (8189), and disp / mask / out / mask_out /
+    labels one element past a 16-byte boundary, where an aligned width (8, 8192) takes the scalar path too; fill off and on, labels
+    and counts there and not, out of place and in place."""
+    B, H = 1, 2
+    n = B * H * W
+    d_np, m_np = I.plateaus(B, H, W, W), I.random_mask(B, H, W, W + 1)
+    work = torch.empty((int(hip_lib.lws_speckle_workspace(B, H, W)),), dtype=torch.uint8, device=dev)
+
+    def place(a=None, dtype=torch.float32):
+        t = torch.empty(n + 8, dtype=dtype, device=dev)[4 + skew:4 + skew + n].view(B, 1, H, W)
+        return t if a is None else t.copy_(cu(a, dev))
+
+    for fill in (0, 1):
+        wo, wm, wl, wc = R.speckle_filter(d_np, m_np, 0.5, 50, fill)
+        if W >= 8189:
+            assert (wm[..., 7171::4] == 1).any(), "a kept pixel under bit 31 of a thread's flags"
+        for optional, in_place in ((True, False), (False, False), (False, True)):
+            d, m = place(d_np), place(m_np, torch.uint8)
+            assert d.data_ptr() % 16 == 4 * skew
+            out, mask_out = (d, m) if in_place else (place(), place(dtype=torch.uint8))
+            labels = place(dtype=torch.int32) if optional else None
+            counts = torch.empty((B, 3), dtype=torch.int64, device=dev) if optional else None
+            _raw_call(hip_lib, dev, d, m, 0.5, 50, fill, out, mask_out, labels, counts, work)
+            what = f"W={W} skew={skew} fill={fill} optional={optional} in_place={in_place}"
+            assert_bits(out, wo, what + " out")
+            assert_bits(mask_out, wm, what + " mask_out")
+            if optional:
+                assert_bits(labels, wl, what + " labels")
+                assert_bits(counts, wc, what + " counts")
+
+
+def test_rows_wider_than_the_fill_takes_without_fill(dev, hip_lib):
+    """fill = 0 has no bound on W: at W = 8200 a thread of k_sp_apply owns a ninth quad, whose kept pixels must still be counted and
+    written; every output, with and without a mask."""
+    from lwsnet_amd import ops
+    B, H, W = 1, 2, 8200
+    d_np, m_np = I.plateaus(B, H, W, W), I.random_mask(B, H, W, W + 1)
+    for m in (None, m_np):
+        wo, wm, wl, wc = R.speckle_filter(d_np, m, 0.5, 50, 0)
+        assert (wm[..., 8192:] == 1).any(), "a kept pixel in a thread's ninth quad"
+        res = ops.speckle_filter(cu(d_np, dev), 50, 0.5, mask=None if m is None else cu(m, dev), fill=False, want_labels=True)
+        for got, want, what in ((res.disp, wo, "out"), (res.mask, wm, "mask_out"), (res.labels, wl, "labels"), (res.counts, wc, "counts")):
+            assert_bits(got, want, f"W={W} mask={'on' if m is not None else 'off'} {what}")
+
+
 def test_graph_capture_replays_the_filter(dev, hip_lib):
     from lwsnet_amd import ops
     B, H, W = 2, 256, 512
