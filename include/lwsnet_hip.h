@@ -138,6 +138,34 @@ int lws_refine(lws_handle h, const float *left, const float *pred3, int B, int H
 int lws_forward(lws_handle h, const float *left, const float *right, int B, int H, int W, float *const pred_out[4],
                 void *stream);
 
+/* ---- per-pixel confidence and disparity sigma of a stage's soft-argmin (not in the reference) ---------------------------
+ * The softmax over the D hypotheses that the regression takes the mean of, kept: how peaked it is and how wide.
+ * cost [B,D,h,w], hypothesis values v_k = start + (float)k, full resolution H x W (H >= h, W >= w, H/h and W/w <= 1024).
+ * Per low-resolution pixel, every step one IEEE float32 operation, sums ascending in k from 0.0f:
+ *   m = max_k(-c_k);  e_k = expf(-c_k - m) (the library's own polynomial);  S = sum e_k;  p_k = e_k / S;
+ *   d = sum p_k * v_k                     -- lws_softargmin's operations in its order: d is bit-equal to its output;
+ *   t_k = v_k - d;
+ *   peak = sum over {k : |t_k| <= 1.0f} p_k   -- the probability mass within one hypothesis step of the regressed value: about 1
+ *                                            for a unimodal match, about 3/D for a flat volume, low for a bimodal one;
+ *   var = sum p_k * (t_k * t_k)           -- separate multiply and add, no fused multiply-add;
+ *   sig = sqrtf(var), correctly rounded.
+ * Full resolution, with the source taps and the blend expression of lws_upsample_add (half-pixel centres):
+ *   conf  [B,1,H,W] = bilinear_resize(peak)
+ *   sigma [B,1,H,W] = bilinear_resize((sig * (float)H) * (1.0f / (float)h)) -- the standard deviation in full-resolution pixels.
+ * disp_low, peak_low, sigma_low [B,h,w] receive d, peak and sig (sig in hypothesis steps, not rescaled).  Each of the five
+ * outputs may be NULL (not written), not all of them.  Costs are assumed finite; what NaN costs give is whatever this arithmetic
+ * gives.  One launch, no atomics, no workspace: an image gives the same bytes in any batch.  Element alignment only. */
+int lws_softargmin_conf(const float *cost, int B, int D, int h, int w, float start, int H, int W, float *disp_low,
+                        float *peak_low, float *sigma_low, float *conf, float *sigma, void *stream);
+
+/* lws_forward plus the confidence and sigma maps of the three volume stages: pred_out[0..3] are lws_forward's bits;
+ * conf_out[s], sigma_out[s] [B,1,H,W] (s = 0..2; an entry, or a whole array, may be NULL) are lws_softargmin_conf of stage s's
+ * filtered cost, resized the way the handle's interp_align_mode says.  It runs the plan that keeps every filtered cost (no fused
+ * last Conv3D layer, no deferred map; bit-exact like every plan) and one more launch per stage, under kernel class
+ * LWS_KC_CONFIDENCE.  lws_reserve(B, H, W) covers it, and it is capturable into a hipGraph like lws_forward.  B <= 65535. */
+int lws_forward_conf(lws_handle h, const float *left, const float *right, int B, int H, int W, float *const pred_out[4],
+                     float *const conf_out[3], float *const sigma_out[3], void *stream);
+
 /* ---- the per-pixel steps of the I/O harness on either side of forward (ABI v8) ------------- */
 /* inference.py:83-85,102-103: ToTensor + Normalize of the (already cropped) image.  rgb [B,H,W,3] uint8, device memory ->
  * out [B,3,H,W] float32 = ((v / 255) - mean[c]) / std[c], one IEEE float32 operation each -- bit for bit what numpy computes in
@@ -405,7 +433,8 @@ typedef enum {
     LWS_KC_REF_DWS = 10,       /* k_ref_dws                              */
     LWS_KC_REF_CONV64 = 11,    /* k_ref_conv64                           */
     LWS_KC_REF_LAST = 12,      /* k_ref_last                             */
-    LWS_KC_COUNT = 13
+    LWS_KC_CONFIDENCE = 13,    /* k_softargmin_conf (lws_forward_conf only) */
+    LWS_KC_COUNT = 14
 } lws_kernel_class;
 
 /* class_mask != 0: every launch whose kernel class bit (1 << lws_kernel_class) is set is bracketed from now

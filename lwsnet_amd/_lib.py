@@ -42,6 +42,8 @@ PROTOTYPES = {
     "lws_feature_extraction": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "lws_refine": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "lws_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp * 4, _vp]),
+    "lws_softargmin_conf": (_i, [_vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lws_forward_conf": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp * 4, _vp * 3, _vp * 3, _vp]),
     "lws_preprocess_rgb8": (_i, [_vp, _vp, _i, _i, _i, c_float_p, c_float_p, _vp]),
     "lws_apply_lut8": (_i, [_vp, _vp, _vp, ctypes.c_int64, _vp]),
     "lws_stage_metrics_workspace": (ctypes.c_int64, [_i, _i, _i]),
@@ -79,7 +81,7 @@ PROTOTYPES = {
     "lws_pool_profile_read": (_i, [_vp, ctypes.POINTER(ctypes.c_double), c_int64_p]),
 }
 LWS_POOL_SIDE_STREAMS = 1
-LWS_KC_COUNT = 13
+LWS_KC_COUNT = 14
 
 _lib = None
 

@@ -274,7 +274,7 @@ const char *lws_kernel_class_name(int kc)
     static const char *names[LWS_KC_COUNT] = {"volume_l1_shift", "volume_l1_warp", "conv3d_first", "conv3d_mid16",
                                               "conv3d_mid8",     "conv3d_last",    "softargmin",   "upsample_add",
                                               "feature_conv2d",  "ref_first",      "ref_dws",      "ref_conv64",
-                                              "ref_last"};
+                                              "ref_last",        "softargmin_conf"};
     return kc >= 0 && kc < LWS_KC_COUNT ? names[kc] : "?";
 }
 

@@ -324,6 +324,9 @@ int launch_upsample_add(const float *low, const float *prev, float *out, int B, 
                         hipStream_t st, float ioff = 0.5f);
 int launch_softargmin_upsample(const float *cost, const float *prev, float *out, float *low_out, int B, int D, int h,
                                int w, int H, int W, float start, hipStream_t st, float ioff = 0.5f);
+// lws_confidence.hip: every output pointer is optional (nullptr = not written)
+int launch_softargmin_conf(const float *cost, float *disp_low, float *peak_low, float *sigma_low, float *conf, float *sigma, int B,
+                           int D, int h, int w, int H, int W, float start, hipStream_t st, float ioff = 0.5f);
 
 // conv3d stack pieces; activations are channels-last [B,D,h,w,C3]
 bool shift_first_can_fuse(const Stage3d &s, int C);

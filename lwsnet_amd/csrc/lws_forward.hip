@@ -385,9 +385,10 @@ static bool defers(const lws_ctx *h, int s, int B, int H, int W, bool keep)
 }
 
 // Stage s of LWSNet.forward up to its Conv3D stack (models.py:119-138; fork: see Fork).  fused: the stack's last layer did the
-// soft-argmin too (into low[s]).
+// soft-argmin too (into low[s]).  keep_cost (lws_forward_conf): the last layer never fuses, so the filtered cost is in L.cost_out.
 static int stage_volume(lws_ctx *h, int s, const StageDims &d, const float *featL, const float *featR, int B, int H, int W,
-                        StageMap map[3], const WsLayout &L, hipStream_t st, bool defer, bool &fused, const Fork &fork = Fork())
+                        StageMap map[3], const WsLayout &L, hipStream_t st, bool defer, bool &fused, const Fork &fork = Fork(),
+                        bool keep_cost = false)
 {
     static const int feat_c[3] = {16, 16, 8};   // feature_extraction outputs, submodules.py:101,104,186
     float *act_a = h->ws + L.act_a, *act_b = h->ws + L.act_b, *raw = h->ws + L.cost_raw, *cost = h->ws + L.cost_out;
@@ -411,7 +412,7 @@ static int stage_volume(lws_ctx *h, int s, const StageDims &d, const float *feat
     }
     if (rc) return rc;
     fused = false;
-    return conv3d_stack(h, s, raw, cost, act_a, act_b, B, D, hh, ww, st, (s > 0 || defer) ? low : nullptr, d.start, &fused,
+    return conv3d_stack(h, s, raw, cost, act_a, act_b, B, D, hh, ww, st, (!keep_cost && (s > 0 || defer)) ? low : nullptr, d.start, &fused,
                         first_done, fork);                                                                          // :136-138
 }
 
@@ -579,18 +580,24 @@ int lws_refine(lws_handle h, const float *left, const float *pred3, int B, int H
     return refine_rest(h, p3, B, H, W, L, pred4, (hipStream_t)stream);
 }
 
-int lws_forward(lws_handle h, const float *left, const float *right, int B, int H, int W, float *const pred_out[4],
-                void *stream)
+}  // extern "C"
+
+// What lws_forward_conf adds to the forward: conf[s] / sigma[s] (either may be null) receive stage s's confidence and sigma maps
+struct ConfOut {
+    float *const *conf;
+    float *const *sigma;
+};
+
+// LWSNet.forward on a handle (lws_forward; arguments checked by the caller).  co != nullptr (lws_forward_conf): the plan that
+// keeps every stage's filtered cost -- no stage defers its map and no last Conv3D layer fuses the soft-argmin (low = nullptr
+// in conv3d_stack), so stage_map runs the soft-argmin from L.cost_out -- plus one k_softargmin_conf launch per stage.
+static int run_forward(lws_ctx *h, const char *what, const float *left, const float *right, int B, int H, int W,
+                       float *const pred_out[4], const ConfOut *co, hipStream_t st)
 {
-    LWS_CHECK_ARG(h && left && right && pred_out, "forward: null pointer");
-    for (int s = 0; s < 4; ++s) LWS_CHECK_ARG(pred_out[s], "forward: null output for stage %d", s + 1);
-    int rc = check_size(h, B, H, W);
-    if (rc) return rc;
     const WsLayout L = ws_layout(h, B, H, W);
-    rc = begin_call(h, "lws_forward", true, "forward: set_state_dict/lws_finalize must be called with the full state dict first",
-                    L.total_all);
+    int rc = begin_call(h, what, true, "forward: set_state_dict/lws_finalize must be called with the full state dict first",
+                        L.total_all);
     if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
     // Under hipGraph capture (tools/graph_pipeline.py; lws_reserve first, so that nothing allocates) the forks must be capture-
     // time records -- hipEventRecord on the capturing stream, which is what pulls the side stream into the graph; an event bound
     // to a kernel's completion signal is not one -- and nothing is profiled (timing events cannot be read back from a graph).
@@ -643,11 +650,11 @@ int lws_forward(lws_handle h, const float *left, const float *right, int B, int 
     StageMap map[3] = {{pred_out[0]}, {pred_out[1]}, {pred_out[2]}};
     for (int s = 0; s < 3; ++s) {                                                                   // :115-156
         if (multi && s > 0) LWS_HIP(hipStreamWaitEvent(st, h->ev_feat[s], 0));    // joins: f4 before stage 2, f2 before stage 3
-        const bool defer = defers(h, s, B, H, W, s < 2 || ref_evaluates);
+        const bool defer = co == nullptr && defers(h, s, B, H, W, s < 2 || ref_evaluates);
         const StageDims d = stage_dims(h, s, H, W);
         bool fused;
         rc = stage_volume(h, s, d, fl[s], fr[s], B, H, W, map, L, st, defer, fused,
-                          Fork{multi && s == 0 ? h->ev_fork2 : nullptr, fork2, ext});
+                          Fork{multi && s == 0 ? h->ev_fork2 : nullptr, fork2, ext}, co != nullptr);
         if (rc) return rc;
         if (s == 0) {
             // fork 2: the side branch starts once the event is complete (bound or recorded by conv3d_stack)
@@ -660,9 +667,44 @@ int lws_forward(lws_handle h, const float *left, const float *right, int B, int 
         }
         rc = stage_map(h, s, d, B, H, W, map, L, st, defer, fused);
         if (rc) return rc;
+        float *conf = co != nullptr && co->conf != nullptr ? co->conf[s] : nullptr;
+        float *sigma = co != nullptr && co->sigma != nullptr ? co->sigma[s] : nullptr;
+        if (conf != nullptr || sigma != nullptr) {
+            // Lifetime of the filtered cost: L.cost_out is ONE buffer for the three stages (ws_layout), written by this stage's
+            // last Conv3D layer and overwritten by the next stage's.  Both, and this launch between them, are on the chain
+            // stream st, and the side stream's branches (feature tail, refinement1_left) never touch it.
+            ProfScope p(h, LWS_KC_CONFIDENCE, st);
+            rc = launch_softargmin_conf(h->ws + L.cost_out, nullptr, nullptr, nullptr, conf, sigma, B, d.D, d.hh, d.ww, H, W,
+                                        d.start, st, ioff_of(h));
+            if (rc) return rc;
+        }
     }
     if (multi) LWS_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
     return refine_rest(h, map[2], B, H, W, L, pred_out[3], st);                                        // :159-162
+}
+
+extern "C" {
+
+int lws_forward(lws_handle h, const float *left, const float *right, int B, int H, int W, float *const pred_out[4],
+                void *stream)
+{
+    LWS_CHECK_ARG(h && left && right && pred_out, "forward: null pointer");
+    for (int s = 0; s < 4; ++s) LWS_CHECK_ARG(pred_out[s], "forward: null output for stage %d", s + 1);
+    const int rc = check_size(h, B, H, W);
+    if (rc) return rc;
+    return run_forward(h, "lws_forward", left, right, B, H, W, pred_out, nullptr, (hipStream_t)stream);
+}
+
+int lws_forward_conf(lws_handle h, const float *left, const float *right, int B, int H, int W, float *const pred_out[4],
+                     float *const conf_out[3], float *const sigma_out[3], void *stream)
+{
+    LWS_CHECK_ARG(h && left && right && pred_out, "forward_conf: null pointer");
+    for (int s = 0; s < 4; ++s) LWS_CHECK_ARG(pred_out[s], "forward_conf: null output for stage %d", s + 1);
+    LWS_CHECK_ARG(B <= 65535, "forward_conf: batch %d above 65535", B);
+    const int rc = check_size(h, B, H, W);
+    if (rc) return rc;
+    const ConfOut co{conf_out, sigma_out};
+    return run_forward(h, "lws_forward_conf", left, right, B, H, W, pred_out, &co, (hipStream_t)stream);
 }
 
 }  // extern "C"

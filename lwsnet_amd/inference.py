@@ -54,6 +54,14 @@ and point-cloud files (code 2 in the mask they are given).  A frame whose size i
 frame (logged, nothing written); a rectified frame smaller than the crop is skipped, by the reference's rule.  Without `--calib` /
 `--camera` the geometry outputs use the calibration's own rectified left camera.  `--save_rect` writes the two rectified crops as
 `<left stem>_rect_left.png` and `<left stem>_rect_right.png` into the output folder.
+
+`--save_conf [--sigma_max MAX]`, `--conf_min C`, `--sigma_max_keep S`: the forward is LWSNet.forward_conf, which also returns each volume
+stage's confidence (the probability mass its soft-argmin puts within one hypothesis step of the disparity) and sigma (the standard
+deviation of that distribution in pixels).  `--save_conf` writes the finest stage's (stage 3's) two maps as 8-bit grey files, two per
+pair, beside the colour file (with `--left_img` beside `3.png`): `<stem>_conf.png` = rint(clip(conf, 0, 1) * 255) and `<stem>_sigma.png` = rint(min(sigma, MAX) * 255 / MAX), MAX = 8 px by
+default.  `--conf_min C` and `--sigma_max_keep S` keep a pixel in the `_disp16`, `_depth16` and `.ply` files only where its stage's
+conf >= C and sigma <= S (ops.confidence_codes; stage 4, the refined map, goes by stage 3's), on top of what the speckle filter's
+codes drop.  They are not part of the post-processing chain, and not available with `--lr_check`, `--occ_check` or `--workers`.
 """
 import argparse
 import contextlib
@@ -95,7 +103,74 @@ def build_parser():
     add_wmedian_arguments(p)
     add_geometry_arguments(p)
     add_rectify_arguments(p)
+    add_conf_arguments(p)
     return p
+
+
+def add_conf_arguments(p):
+    """--save_conf / --sigma_max MAX / --conf_min C / --sigma_max_keep S (not in the reference): LWSNet.forward_conf.  A command line
+    without them parses to the namespace it parsed to before they existed (argparse.SUPPRESS); check_conf_arguments writes their
+    defaults."""
+    p.add_argument("--save_conf", action="store_true", default=argparse.SUPPRESS,
+                   help="write <stem>_conf.png and <stem>_sigma.png, the finest stage's confidence and disparity sigma as 8-bit grey "
+                        "maps (sequential mode only; not in the reference)")
+    p.add_argument("--sigma_max", type=float, default=argparse.SUPPRESS, metavar="MAX", help="with --save_conf: the sigma, in pixels, that maps to 255 (default 8)")
+    p.add_argument("--conf_min", type=float, default=argparse.SUPPRESS, metavar="C",
+                   help="--save_disp16 / --save_depth / --save_ply keep only the pixels whose confidence is >= C")
+    p.add_argument("--sigma_max_keep", type=float, default=argparse.SUPPRESS, metavar="S",
+                   help="--save_disp16 / --save_depth / --save_ply keep only the pixels whose disparity sigma is <= S pixels")
+
+
+def conf_requested(args):
+    return bool(getattr(args, "save_conf", False)) or getattr(args, "conf_min", None) is not None or getattr(args, "sigma_max_keep", None) is not None
+
+
+def check_conf_arguments(p, args):
+    """Rejects what the confidence outputs do not support, before any model or GPU work; sets the flags' defaults (--sigma_max: 8)."""
+    args.save_conf = getattr(args, "save_conf", False)
+    for flag in ("sigma_max", "conf_min", "sigma_max_keep"):
+        setattr(args, flag, getattr(args, flag, None))
+    if args.sigma_max is not None and not args.save_conf:
+        p.error("--sigma_max needs --save_conf")
+    if args.sigma_max is None:
+        args.sigma_max = 8.0
+    if not (np.isfinite(args.sigma_max) and args.sigma_max > 0):
+        p.error(f"--sigma_max MAX must be finite and > 0, got {args.sigma_max}")
+    for flag in ("conf_min", "sigma_max_keep"):
+        v = getattr(args, flag)
+        if v is not None and np.isnan(v):
+            p.error(f"--{flag} must be a number, got {v}")
+    if not conf_requested(args):
+        return
+    flags = "--save_conf / --conf_min / --sigma_max_keep"
+    if args.lr_check is not None or getattr(args, "occ_check", None) is not None:
+        p.error(f"{flags} use the network's own confidence and do not combine with --lr_check or --occ_check")
+    if args.workers > 0:
+        p.error(f"{flags} run in the sequential mode only: use --workers 0")
+    if (args.conf_min is not None or args.sigma_max_keep is not None) and not (args.save_disp16 or args.save_depth or args.save_ply):
+        p.error("--conf_min and --sigma_max_keep mask --save_disp16 / --save_depth / --save_ply: give one of them")
+
+
+def conf_to_u8(conf):
+    """[H,W] confidence -> the bytes of <stem>_conf.png: rint(clip(conf, 0, 1) * 255)."""
+    return np.rint(np.clip(np.asarray(conf, np.float64), 0.0, 1.0) * 255.0).astype(np.uint8)
+
+
+def sigma_to_u8(sigma, sigma_max):
+    """[H,W] sigma in pixels -> the bytes of <stem>_sigma.png: rint(min(sigma, MAX) * 255 / MAX)."""
+    return np.rint(np.minimum(np.asarray(sigma, np.float64), float(sigma_max)) * 255.0 / float(sigma_max)).astype(np.uint8)
+
+
+class _ConfModel:
+    """What the chain calls as model(left, right) when the confidence outputs are on: LWSNet.forward_conf, whose ConfResult stays
+    in `last` for the files written after the chain."""
+
+    def __init__(self, model):
+        self.model, self.last = model, None
+
+    def __call__(self, left, right):
+        self.last = self.model.forward_conf(left, right)
+        return self.last.preds
 
 
 def add_rectify_arguments(p):
@@ -371,6 +446,9 @@ def inference(model, left_imgs, right_imgs, args, log):
     opts = post.Options.from_args(args)
     geo = getattr(args, "save_disp16", False) or getattr(args, "save_depth", False) or getattr(args, "save_ply", False)
     rc = getattr(args, "rectify", None) is not None
+    conf_on = conf_requested(args)
+    conf_mask = conf_on and (args.conf_min is not None or args.sigma_max_keep is not None)
+    chain_model = _ConfModel(model) if conf_on else model
 
     def save(path, color, stage):                                       # the colour file, then the mask and geometry files beside it
         io.save_png(path, color)
@@ -382,8 +460,14 @@ def inference(model, left_imgs, right_imgs, args, log):
             written.append(_save_occ_mask(path, res.occ_masks[stage], log))
         if res.speckle_masks is not None:
             written.append(_save_sp_mask(path, res.speckle_masks[stage], log))
+        if conf_on and args.save_conf and (stage == 2 or not args.left_img):    # --left_img: beside 3.png, the stage they belong to
+            written.extend(_save_conf(path, chain_model.last, args.sigma_max, log))
         if geo:
             keep = res.keep[stage] if res.keep is not None else None
+            if conf_mask:                                               # each map by its own stage's confidence, the refined one by stage 3's
+                from . import ops
+                low = ops.confidence_codes(chain_model.last.conf, chain_model.last.sigma, args.conf_min, args.sigma_max_keep, stages=(min(stage, 2),))
+                keep = low if keep is None else torch.where(low == 0, torch.zeros_like(keep), keep)
             if rc:                                                      # a pixel sampled outside the raw left image: out of view
                 keep = valid_left if keep is None else torch.where(valid_left == 0, torch.full_like(keep, 2), keep)
             written.extend(_save_geometry(path, res.disp[stage], keep, cam, left, args, log))
@@ -406,7 +490,7 @@ def inference(model, left_imgs, right_imgs, args, log):
             torch.cuda.synchronize(model.device)
             t0 = time.time()
             guide = _rgb_on_device(left, model.device) if opts.needs_guide else None
-            res = post.run_chain(model, l_in, r_in, opts, guide)
+            res = post.run_chain(chain_model, l_in, r_in, opts, guide)
             torch.cuda.synchronize(model.device)
             cost = time.time() - t0
         warm = True
@@ -505,6 +589,18 @@ def _save_geometry(path, disp, mask, cam, left_rgb, args, log):
     return written
 
 
+def _save_conf(path, result, sigma_max, log):
+    """The finest stage's confidence and sigma of the pair whose map was written to `path`, as <stem>_conf.png and <stem>_sigma.png."""
+    stem = os.path.splitext(path)[0]
+    conf, sigma = result.conf[2][0, 0].cpu().numpy(), result.sigma[2][0, 0].cpu().numpy()
+    for suffix, img in (("_conf.png", conf_to_u8(conf)), ("_sigma.png", sigma_to_u8(sigma, sigma_max))):
+        with open(stem + suffix, "wb") as f:
+            f.write(io.encode_png_gray(img))
+    log.info("Confidence: mean = {:.4f}, sigma: median = {:.3f} px\t\tSave maps = {}_conf.png, {}_sigma.png".format(
+        float(conf.mean()), float(np.median(sigma)), stem, stem))
+    return [stem + "_conf.png", stem + "_sigma.png"]
+
+
 def _save_lr_mask(path, mask, log):
     """The left-right check codes of the map written to `path`, as the grey PNG <stem>_lr.png next to it."""
     code = mask[0, 0].cpu().numpy()
@@ -542,6 +638,7 @@ def main(argv=None):
     check_wmedian_arguments(parser, args)
     check_geometry_arguments(parser, args)
     check_rectify_arguments(parser, args)
+    check_conf_arguments(parser, args)
     log = start_logging("lwsnet_amd.inference", args)
     model = load_model(args, log)
     if getattr(args, "split_bf16", False):

@@ -30,6 +30,11 @@ model(left, right)), the four right-view maps splatted from them (the right came
 (background-filled if asked), the four uint8 code maps (1 visible, 0 occluded by a nearer surface, 2 out of the right camera's
 view) and density, a numpy [4,B] array of visible pixels / (H*W)."""
 
+ConfResult = namedtuple("ConfResult", ["preds", "conf", "sigma"])
+ConfResult.__doc__ = """What LWSNet.forward_conf returns: the four stage maps (the bits of model(left, right)) and, for the three volume
+stages, conf -- the probability mass the stage's soft-argmin puts within one hypothesis step of its disparity -- and sigma, the
+standard deviation of that distribution in full-resolution pixels (include/lwsnet_hip.h: lws_softargmin_conf)."""
+
 
 class DisparityTensor(torch.Tensor):
     """What ``model(left, right)`` returns per stage: a device-resident ``torch.Tensor`` that also answers the Paddle
@@ -258,6 +263,16 @@ class LWSNet:
             density = row_kept.sum(dim=2, dtype=torch.int64).cpu().numpy() / float(H * W)
         wrap = DisparityTensor.wrap
         return OccResult([wrap(p) for p in dl], [wrap(p) for p in rmaps], [wrap(p) for p in out], mask, density)
+
+    def forward_conf(self, left_input, right_input):
+        """Stage maps with the network's own per-pixel confidence and disparity sigma (not in the reference): one lws_forward_conf,
+        the forward on the plan that keeps each stage's filtered cost plus one launch per stage.  ops.confidence_codes turns the
+        maps into the code map the filters and the geometry outputs take.  Returns a ConfResult."""
+        left, right, B, H, W = self._pair(left_input, right_input, "forward_conf")
+        with torch.cuda.device(self.device):
+            preds, conf, sigma = ops.forward_conf(self._h, left, right)
+        wrap = DisparityTensor.wrap
+        return ConfResult([wrap(p) for p in preds], [wrap(p) for p in conf], [wrap(p) for p in sigma])
 
 
 class _PoolJob:

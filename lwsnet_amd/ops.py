@@ -152,6 +152,26 @@ def softargmin(cost, start):
     return low
 
 
+SoftargminConf = namedtuple("SoftargminConf", ["disp_low", "peak_low", "sigma_low", "conf", "sigma"])
+
+
+def softargmin_conf(cost, start, H, W, disp_low=True, peak_low=True, sigma_low=True, conf=True, sigma=True):
+    """lws_softargmin_conf (include/lwsnet_hip.h): the soft-argmin of cost [B,D,h,w] with the confidence and the standard deviation of
+    its distribution.  Returns a SoftargminConf: disp_low (bit-equal to softargmin), peak_low, sigma_low [B,h,w] and conf, sigma
+    [B,1,H,W]; an output switched off by its keyword is None and is not computed."""
+    c = _dev(cost, "cost")
+    if c.dim() != 4:
+        raise ValueError(f"cost must be [B,D,h,w]; got {tuple(c.shape)}")
+    B, D, h, w = c.shape
+    outs = [torch.empty((B, h, w), device=c.device, dtype=torch.float32) if on else None for on in (disp_low, peak_low, sigma_low)]
+    outs += [torch.empty((B, 1, int(H), int(W)), device=c.device, dtype=torch.float32) if on else None for on in (conf, sigma)]
+    lib = _lib.load()
+    with torch.cuda.device(c.device):
+        _lib.check(lib.lws_softargmin_conf(_ptr(c), B, D, h, w, float(start), int(H), int(W), *[_ptr(t) for t in outs], _stream()),
+                   "lws_softargmin_conf")
+    return SoftargminConf(*outs)
+
+
 def upsample_add(disp_low, prev, H, W):
     """models/models.py:145-148,153-156."""
     low = _dev(disp_low, "disp_low")
@@ -248,6 +268,52 @@ def forward(handle, left, right, out=None):
         _lib.check(lib.lws_forward(handle, _ptr(l), _ptr(r), B, H, W, arr(*[t.data_ptr() for t in preds]), _stream()),
                    "lws_forward")
     return preds
+
+
+def forward_conf(handle, left, right, conf=True, sigma=True):
+    """lws_forward_conf (include/lwsnet_hip.h): the forward plus the confidence and sigma maps of the three volume stages.  Returns
+    (preds, conf, sigma): four, three and three [B,1,H,W] maps; conf / sigma is None when switched off by its keyword."""
+    l, r = _dev(left, "left"), _dev(right, "right")
+    B, _, H, W = l.shape
+    preds = stage_outputs(None, B, H, W, l.device)
+    cs, ss = ([torch.empty((B, 1, H, W), device=l.device, dtype=torch.float32) for _ in range(3)] if on else None for on in (conf, sigma))
+    arr4, arr3 = ctypes.c_void_p * 4, ctypes.c_void_p * 3
+    lib = _lib.load()
+    with torch.cuda.device(l.device):
+        _lib.check(lib.lws_forward_conf(handle, _ptr(l), _ptr(r), B, H, W, arr4(*[t.data_ptr() for t in preds]),
+                                        arr3(*[t.data_ptr() for t in cs]) if cs else arr3(),
+                                        arr3(*[t.data_ptr() for t in ss]) if ss else arr3(), _stream()), "lws_forward_conf")
+    return preds, cs, ss
+
+
+def confidence_codes(conf, sigma, min_conf=None, max_sigma=None, stages=(0, 1, 2)):
+    """A uint8 code map with lws_lr_check's meaning from forward_conf's maps: 1 where every stage in `stages` has conf >= min_conf and
+    sigma <= max_sigma (a threshold that is None is not applied; NaN fails both), else 0.  Plain comparisons on the device;
+    speckle_filter, wmedian_filter, depth_maps and point_cloud take the result as their `mask`."""
+    stages = tuple(int(s) for s in stages)
+    if not stages or any(s < 0 or s > 2 for s in stages):
+        raise ValueError(f"stages must be a non-empty selection of 0, 1, 2; got {stages}")
+    if (min_conf is not None and conf is None) or (max_sigma is not None and sigma is None):
+        raise ValueError("a threshold was given for maps that are None")
+    maps = conf if conf is not None else sigma
+    if maps is None:
+        raise ValueError("conf and sigma are both None")
+    first = maps[stages[0]]
+
+    def stage_map(ts, name, s):                 # plain torch on whatever device the maps live on
+        t = ts[s]
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 4 or t.shape[1] != 1 or t.shape != first.shape \
+                or t.device != first.device:
+            raise ValueError(f"{name}[{s}] must be a float32 [B,1,H,W] tensor of the shape and device of the other maps")
+        return t.as_subclass(torch.Tensor)
+
+    ok = torch.ones(first.shape, device=first.device, dtype=torch.bool)
+    for s in stages:
+        if min_conf is not None:
+            ok &= stage_map(conf, "conf", s) >= float(min_conf)
+        if max_sigma is not None:
+            ok &= stage_map(sigma, "sigma", s) <= float(max_sigma)
+    return ok.to(torch.uint8)
 
 
 def preprocess_rgb8(rgb_u8, out=None):
