@@ -189,6 +189,29 @@ int64_t lws_stage_metrics_workspace(int B, int Hg, int Wg);
 int lws_stage_metrics(const float *const pred[4], int B, int Hp, int W, int row_offset, const float *gt, int Hg,
                       float maxdisp, int mode, void *workspace, int64_t *counts, double *abs_sum, void *stream);
 
+/* ---- sparsification histograms: how well sigma or conf ranks the pixels by their error (additive after v8) ---- */
+/* The inputs of the sparsification curve and its area against the oracle curve (AUSE, Ilg et al. 2018), as integers.  pred[s],
+ * unc[s] [B,1,Hp,W] float32 for s < nmaps (1..4); gt [B,Hg,W]; Hp = Hg + row_offset, maxdisp and mode as for lws_stage_metrics.
+ * Per ground-truth pixel, one IEEE float32 operation per step, no contraction:
+ *   valid, bad  as lws_stage_metrics (mode 0: valid = 0 < g < maxdisp, mode 1: g < maxdisp; bad = valid & e > 3 & e / g > 0.05);
+ *               an invalid pixel contributes nothing;
+ *   e  = fabsf(p - g);  ec = fminf(e, 65536.0f) (a NaN e becomes 65536: the worst error, never dropped);
+ *   q  = (int64)rintf(ec * 1024.0f), the error in 1/1024 px (the scaling is exact: the only rounding is to the 2^-10 grid);
+ *   u  = unc (kind 0: sigma, lower = more trusted) or 1.0f - unc (kind 1: conf);
+ *   bin(v) = 1025 if v is NaN or v >= 256.0f;  0 if v < 0x1p-24f (negatives and both zeros);  otherwise
+ *            1 + ((bits(v) >> 18) - 3296): 32 logarithmic bins per octave over [2^-24, 2^8), 3296 = (127 - 24) << 5;
+ *   hist[s][b][0][bin(u)] += {1, bad, q}   (the ranking under test)
+ *   hist[s][b][1][bin(e)] += {1, bad, q}   (the oracle ranking)
+ * hist: int64 [nmaps][B][2][LWS_SPARS_BINS][3] in device memory; bin 0 is the most trusted, bin 1025 the least.  The call clears
+ * hist with one asynchronous memset on `stream` and runs one kernel: a fixed launch list, no workspace, no device-to-host read
+ * (capturable into a hipGraph), element alignment only.  All accumulation is integer (LDS and global integer atomics, no float
+ * atomics), so an image gives the same bytes in any batch, at any position, on every run.  Argument errors -- a NULL pointer (an
+ * element below nmaps included), nmaps outside 1..4, kind or mode outside 0 / 1, row_offset < 0, Hp != Hg + row_offset, maxdisp
+ * not > 0, B outside 1..65535, hist overlapping an input -- return LWS_ERR_INVALID before any GPU call. */
+#define LWS_SPARS_BINS 1026
+int lws_sparsification(const float *const pred[4], const float *const unc[4], int nmaps, int kind, int B, int Hp, int W,
+                       int row_offset, const float *gt, int Hg, float maxdisp, int mode, int64_t *hist, void *stream);
+
 /* ---- left-right consistency check of the stage maps (additive after v8) ---- */
 /* The right view's disparity is the same left-reference network run on the mirrored, swapped pair (mirror_w(R), mirror_w(L)),
  * mirror_w(t)[..., x] = t[..., W-1-x]: lws_lr_pairs builds the input of ONE forward of 2B pairs, whose first B stage maps are the

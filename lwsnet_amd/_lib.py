@@ -48,6 +48,7 @@ PROTOTYPES = {
     "lws_apply_lut8": (_i, [_vp, _vp, _vp, ctypes.c_int64, _vp]),
     "lws_stage_metrics_workspace": (ctypes.c_int64, [_i, _i, _i]),
     "lws_stage_metrics": (_i, [_vp * 4, _i, _i, _i, _i, _vp, _i, _f, _i, _vp, _vp, _vp, _vp]),
+    "lws_sparsification": (_i, [_vp * 4, _vp * 4, _i, _i, _i, _i, _i, _i, _vp, _i, _f, _i, _vp, _vp]),
     "lws_lr_pairs": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "lws_lr_check": (_i, [_vp * 4, _vp * 4, _i, _i, _i, _i, _f, _i, _vp * 4, _vp * 4, _vp * 4, _vp, _vp]),
     "lws_occlusion_check": (_i, [_vp * 4, _i, _i, _i, _i, _f, _i, _vp * 4, _vp * 4, _vp * 4, _vp, _vp]),
@@ -82,6 +83,7 @@ PROTOTYPES = {
 }
 LWS_POOL_SIDE_STREAMS = 1
 LWS_KC_COUNT = 14
+LWS_SPARS_BINS = 1026
 
 _lib = None
 

@@ -36,6 +36,17 @@ per-stage mean density of kept pixels.
 `--wmedian R [--wmedian_sigma S] [--wmedian_fill N]`: the lines score the maps after lws_wmedian_filter, the last step in front of
 the metric; the guide is the batch's uint8 left images, uploaded once and normalised on the device (lws_preprocess_rgb8), and one
 more line gives the per-stage mean fraction of pixels the filter changed or filled.
+
+`--sparsification` (not in the reference; sequential mode only, without the post-processing chain) scores the confidence maps: the
+batch runs LWSNet.forward_conf, whose stage maps are the forward's bits, so every line above and every other field of the result
+is what it is without the flag.  Behind the metric, lws_sparsification (lwsnet_amd/csrc/lws_sparsification.hip) bins every valid
+pixel of every stage map twice, by its uncertainty and by its error, once with sigma and once with 1 - conf as the uncertainty
+(the refined map goes by stage 3's maps, the rule of `--conf_min`); the integer histograms are summed on the host over the
+dataset, and lwsnet_amd.metrics.sparsification_curves turns them into the sparsification curve (the error of the pixels left
+after the least trusted fraction is removed), the oracle curve (removal by the true error) and the area between the two (AUSE,
+Ilg et al. 2018), for the run's metric.  Two more log lines give the per-stage AUSE of either ranking, and the result gains the key
+"sparsification".  Its curves, and "all", their value at fraction 0, are pooled over the PIXELS of the dataset: "all" is therefore
+not the reference's average over batches that the lines above print.
 """
 import argparse
 import contextlib
@@ -144,12 +155,14 @@ def _row_offset(H, Hg):
     return H - Hg
 
 
-def _sequential(model, dataset, mode, batches, maxdisp, options):
+def _sequential(model, dataset, mode, batches, maxdisp, options, sparsification=False):
     """StereoPairs[i] -> postprocess.run_chain on the batch -> lws_stage_metrics, one batch after the other.  A generator: "start"
     after a warm-up forward, then (counts, abs_sum, stats) per batch.  stats has a [4,b] array per stage of `options` that is on:
     lr_density (the check's consistent pixels / (H*W)), occ_density (the occlusion check's visible pixels / (H*W)), speckle_density (the speckle filter's kept pixels / (H*W)) and
     wmedian_changed (the median's changed + filled pixels / (H*W)).  When the median needs a guide the batch is read as bytes
-    (StereoPairs.raw), uploaded once and normalised on the device, and its left images are the guide."""
+    (StereoPairs.raw), uploaded once and normalised on the device, and its left images are the guide.  With `sparsification` (no
+    stage of the chain is on then) the batch runs LWSNet.forward_conf instead and stats has "sparsification": per kind ("conf",
+    "sigma") the host copy of ops.sparsification's histogram [4,b,2,1026,3]."""
     import torch
     from . import ops
     dev = model.device
@@ -159,6 +172,8 @@ def _sequential(model, dataset, mode, batches, maxdisp, options):
         model.forward_lr(x, x, options.lr_check, options.forward_fills)
     elif options.occ_check is not None:
         model.forward_occ(x, x, options.occ_check, options.forward_fills)
+    elif sparsification:
+        model.forward_conf(x, x)
     else:
         model(x, x)
     torch.cuda.synchronize(dev)
@@ -176,18 +191,28 @@ def _sequential(model, dataset, mode, batches, maxdisp, options):
             left = np.stack([it[0] for it in items])
             right = np.stack([it[1] for it in items])
         gt = torch.from_numpy(np.ascontiguousarray(np.stack([it[2] for it in items]), dtype=np.float32)).to(dev)
-        res = post.run_chain(model, left, right, options, guide)
         stats = {}
-        if res.lr_density is not None:
-            stats["lr_density"] = res.lr_density
-        if res.occ_density is not None:
-            stats["occ_density"] = res.occ_density
-        if res.speckle_counts is not None:
-            stats["speckle_density"] = res.speckle_counts[:, :, 1].cpu().numpy() / float(H * W)
-        if res.wmedian_counts is not None:
-            stats["wmedian_changed"] = res.wmedian_counts.sum(dim=2).cpu().numpy() / float(H * W)
+        if sparsification:
+            conf_res = model.forward_conf(left, right)
+            disp = conf_res.preds
+        else:
+            res = post.run_chain(model, left, right, options, guide)
+            disp = res.disp
+            if res.lr_density is not None:
+                stats["lr_density"] = res.lr_density
+            if res.occ_density is not None:
+                stats["occ_density"] = res.occ_density
+            if res.speckle_counts is not None:
+                stats["speckle_density"] = res.speckle_counts[:, :, 1].cpu().numpy() / float(H * W)
+            if res.wmedian_counts is not None:
+                stats["wmedian_changed"] = res.wmedian_counts.sum(dim=2).cpu().numpy() / float(H * W)
         with torch.cuda.device(dev):
-            counts, sums = ops.stage_metrics(res.disp, gt, _row_offset(left.shape[2], gt.shape[1]), maxdisp, mode)
+            row_offset = _row_offset(left.shape[2], gt.shape[1])
+            counts, sums = ops.stage_metrics(disp, gt, row_offset, maxdisp, mode)
+            if sparsification:                              # the refined map goes by stage 3's uncertainty
+                unc = {"conf": conf_res.conf, "sigma": conf_res.sigma}
+                hists = {kind: ops.sparsification(disp, [*u, u[2]], gt, row_offset, maxdisp, mode, kind) for kind, u in unc.items()}
+                stats["sparsification"] = {kind: h.cpu().numpy() for kind, h in hists.items()}
             yield counts.cpu().numpy(), sums.cpu().numpy(), stats
 
 
@@ -314,9 +339,50 @@ def _stage_reports(o):
     return reports
 
 
+class Sparsification:
+    """The host side of `--sparsification`, fed one batch at a time in order: per kind ("conf", "sigma") the per-image AUSE of the
+    four stage maps and the histograms' sum over the dataset (integers: pooling is exact)."""
+    KINDS = ("conf", "sigma")
+
+    def __init__(self, metric):
+        self.metric = metric
+        self.pooled = {}
+        self.per_image = {kind: [] for kind in self.KINDS}
+
+    def update(self, hists):
+        """hists: per kind, the int64 [4,b,2,1026,3] histograms of one batch."""
+        from .metrics import sparsification_curves
+        for kind in self.KINDS:
+            h = np.asarray(hists[kind], dtype=np.int64)
+            self.pooled[kind] = self.pooled.get(kind, 0) + h.sum(axis=1)
+            for b in range(h.shape[1]):
+                if h[0, b, 0, :, 0].sum() == 0:             # no valid pixel: the same for every stage, it depends on gt alone
+                    self.per_image[kind].append([None] * STAGES)
+                else:
+                    self.per_image[kind].append([sparsification_curves(h[s, b], self.metric)["ause"] for s in range(STAGES)])
+
+    def result(self):
+        """The "sparsification" entry of evaluate()'s result (ValueError when the dataset has no valid pixel at all)."""
+        from .metrics import sparsification_curves
+        curves = {kind: [sparsification_curves(self.pooled[kind][s], self.metric) for s in range(STAGES)] for kind in self.KINDS}
+        first = curves[self.KINDS[0]]                       # fractions, the oracle curve and `all` do not depend on the kind
+        res = {"fractions": first[0]["fractions"].tolist()}
+        for kind in self.KINDS:
+            res[kind] = {"ause": [c["ause"] for c in curves[kind]], "ause_rel": [c["ause_rel"] for c in curves[kind]],
+                         "curve": [c["unc"].tolist() for c in curves[kind]]}
+        res["oracle"] = {"curve": [c["oracle"].tolist() for c in first]}
+        res["all"] = [c["all"] for c in first]
+        res["per_image_ause"] = self.per_image
+        return res
+
+    def lines(self, res):
+        return ["Sparsification ({}): AUSE ".format(kind) + ", ".join("Stage {}={:.4f}".format(x, a) for x, a in enumerate(res[kind]["ause"]))
+                for kind in self.KINDS]
+
+
 def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, workers=0, gpu_workers=2, log=None, lr_check=None,
              lr_fill=False, speckle=None, speckle_diff=1.0, speckle_fill=False, wmedian=None, wmedian_sigma=10.0, wmedian_fill=0,
-             occ_check=None, occ_fill=False):
+             occ_check=None, occ_fill=False, sparsification=False):
     """Runs the reference's test loop for `metric` ("kitti": finetune.py's 3-pixel error, "epe": train.py's EPE) over
     `dataset` (a StereoPairs with training=False).  maxdisp is the mask bound (the KITTI loop uses 192, see KITTI_MAXDISP).
     Returns a dict: per-stage averages at full precision, per-batch values, per-image counts and sums, pairs, wall time, pairs/s.
@@ -324,7 +390,9 @@ def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, worker
     the metric, with the flags named after them (postprocess.Options; the module docstring there says how they combine); a value
     a stage does not support is a ValueError.  Per stage the dict gains its settings and a per-stage mean over the pairs: lr_tau
     and lr_density (consistent pixels / (H*W)); occ_tau and occ_density (visible pixels / (H*W)); speckle_size, speckle_diff and speckle_density (kept pixels / (H*W));
-    wmedian_radius, wmedian_sigma, wmedian_fill and wmedian_changed ((changed + filled pixels) / (H*W))."""
+    wmedian_radius, wmedian_sigma, wmedian_fill and wmedian_changed ((changed + filled pixels) / (H*W)).
+    sparsification = True (sequential mode only, with no stage of the chain: a ValueError otherwise) adds the key "sparsification",
+    the curves and AUSE of the confidence and sigma maps (the module docstring; Sparsification.result)."""
     if metric not in ("kitti", "epe"):
         raise ValueError(f"metric must be 'kitti' or 'epe', got {metric!r}")
     options = post.Options.make(lr_check=lr_check, lr_fill=lr_fill, speckle=speckle, speckle_diff=speckle_diff, speckle_fill=speckle_fill,
@@ -333,6 +401,10 @@ def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, worker
     if options.stages_on and workers > 0:
         raise ValueError(f"the {options.stages_on[0]} runs in the sequential mode only (workers = 0)")
     options.check()
+    if sparsification and workers > 0:
+        raise ValueError("the sparsification curves run in the sequential mode only (workers = 0)")
+    if sparsification and options.stages_on:
+        raise ValueError(f"the sparsification curves score the forward's own maps: they do not combine with the {options.stages_on[0]}")
     if batch_size < 1:
         raise ValueError("batch_size must be >= 1")
     n = len(dataset)
@@ -347,13 +419,17 @@ def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, worker
     if workers > 0:
         it = _pipelined(model, dataset, metric, batches, maxdisp, workers, gpu_workers)
     else:
-        it = _sequential(model, dataset, metric, batches, maxdisp, options)
+        it = _sequential(model, dataset, metric, batches, maxdisp, options, sparsification)
+    spars = Sparsification(metric) if sparsification else None
     if next(it) != "start":
         raise RuntimeError("the evaluation did not start")
     t0 = time.perf_counter()
     for k, (counts, sums, *batch_stats) in enumerate(it):               # _pipelined runs no stage and yields no stats
         for key, value in (batch_stats[0].items() if batch_stats else ()):
-            stats.setdefault(key, []).append(value)
+            if key == "sparsification":
+                spars.update(value)
+            else:
+                stats.setdefault(key, []).append(value)
         line = meters.update(k, counts, sums, files[k])
         if line is not None:
             log.info(line)
@@ -372,6 +448,10 @@ def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, worker
         log.info(prefix + ", ".join("Stage {}={:.4f}".format(x, d) for x, d in enumerate(mean)))
         res.update(settings)
         res[key] = [float(d) for d in mean]
+    if spars is not None:
+        res["sparsification"] = spars.result()
+        for line in spars.lines(res["sparsification"]):
+            log.info(line)
     return res
 
 
@@ -395,7 +475,27 @@ def build_parser():
     post.add_occ_arguments(p)
     post.add_speckle_arguments(p)
     post.add_wmedian_arguments(p)
+    add_sparsification_argument(p)
     return p
+
+
+def add_sparsification_argument(p):
+    """--sparsification (not in the reference).  A command line without it parses to the namespace it parsed to before the flag
+    existed (argparse.SUPPRESS); check_sparsification_argument writes its default, False."""
+    p.add_argument("--sparsification", action="store_true", default=argparse.SUPPRESS,
+                   help="score the confidence and sigma maps: sparsification curves and AUSE per stage (sequential mode only, without "
+                        "the post-processing flags; not in the reference)")
+
+
+def check_sparsification_argument(p, args):
+    """Rejects what --sparsification does not combine with, before any model or GPU work; sets the flag's default."""
+    args.sparsification = getattr(args, "sparsification", False)
+    if not args.sparsification:
+        return
+    post.sequential_only(p, args, "--sparsification")
+    for flag in ("lr_check", "occ_check", "speckle", "wmedian"):
+        if getattr(args, flag, None) is not None:
+            p.error(f"--sparsification scores the forward's own maps: it does not combine with --{flag}")
 
 
 def load_dataset(args):
@@ -418,13 +518,15 @@ def main(argv=None):
     post.check_occ_arguments(parser, args)
     post.check_speckle_arguments(parser, args)
     post.check_wmedian_arguments(parser, args)
+    check_sparsification_argument(parser, args)
     log = start_logging("lwsnet_amd.evaluate", args)
     dataset, metric, maxdisp = load_dataset(args)
     model = load_model(args, log, missing_status=1)
     res = evaluate(model, dataset, metric, batch_size=args.test_batch_size, maxdisp=maxdisp, workers=args.workers,
                    gpu_workers=args.gpu_workers, log=log, lr_check=args.lr_check, lr_fill=args.lr_fill, speckle=args.speckle,
                    speckle_diff=args.speckle_diff, speckle_fill=args.speckle_fill, wmedian=args.wmedian,
-                   wmedian_sigma=args.wmedian_sigma, wmedian_fill=args.wmedian_fill, occ_check=args.occ_check, occ_fill=args.occ_fill)
+                   wmedian_sigma=args.wmedian_sigma, wmedian_fill=args.wmedian_fill, occ_check=args.occ_check, occ_fill=args.occ_fill,
+                   sparsification=args.sparsification)
     res["dataset"] = args.dataset
     log.info("%d pairs in %.3f s: %.2f pairs/s", res["pairs"], res["wall_s"], res["pairs_per_s"])
     if args.json:

@@ -386,6 +386,47 @@ def stage_metrics(preds, gt, row_offset, maxdisp, mode):
     return counts, abs_sum
 
 
+SPARS_KINDS = {"sigma": 0, "conf": 1}
+
+
+def sparsification(preds, unc, gt, row_offset, maxdisp, mode, kind):
+    """The integer histograms behind the sparsification curves (include/lwsnet_hip.h, lws_sparsification; the curves and AUSE:
+    lwsnet_amd.metrics.sparsification_curves).  preds, unc: 1-4 [B,1,Hp,W] float32 maps each, unc[s] the uncertainty that ranks the
+    pixels of preds[s]: kind 0 / "sigma" (lower = more trusted) or 1 / "conf" (ranked by 1 - conf); gt, row_offset, maxdisp and
+    mode as for stage_metrics.  Returns the device tensor hist [nmaps,B,2,1026,3] int64 = per map, image, ranking (0: by unc, 1: the
+    oracle, by the error itself) and bin {pixels, bad pixels, error sum in 1/1024 px}, allocated on the current stream."""
+    mode = METRIC_MODES.get(mode, mode)
+    if mode not in (0, 1):
+        raise ValueError(f"mode must be 0 / 'kitti' or 1 / 'epe', got {mode!r}")
+    kind = SPARS_KINDS.get(kind, kind)
+    if kind not in (0, 1):
+        raise ValueError(f"kind must be 0 / 'sigma' or 1 / 'conf', got {kind!r}")
+    if not isinstance(preds, (list, tuple)) or not isinstance(unc, (list, tuple)) or not 1 <= len(preds) <= 4 or len(unc) != len(preds):
+        raise ValueError("preds and unc must be lists of the same 1-4 maps")
+    g = _dev(gt, "gt")
+    if g.dim() != 3:
+        raise ValueError(f"gt must be [B,Hg,W]; got {tuple(g.shape)}")
+    B, Hg, W = g.shape
+    row_offset = int(row_offset)
+    if row_offset < 0:
+        raise ValueError(f"row_offset must be >= 0, got {row_offset}")
+    ps, us = [], []
+    for name, src, dst in (("preds", preds, ps), ("unc", unc, us)):
+        for s, p in enumerate(src):
+            p = _dev(p, f"{name}[{s}]")
+            if tuple(p.shape) != (B, 1, Hg + row_offset, W) or p.device != g.device:
+                raise ValueError(f"{name}[{s}] must be {(B, 1, Hg + row_offset, W)} on {g.device}; got {tuple(p.shape)} on {p.device}")
+            dst.append(p)
+    hist = torch.empty((len(ps), B, 2, _lib.LWS_SPARS_BINS, 3), device=g.device, dtype=torch.int64)
+    pad = [None] * (4 - len(ps))
+    arr = ctypes.c_void_p * 4
+    with torch.cuda.device(g.device):
+        _lib.check(_lib.load().lws_sparsification(arr(*[t.data_ptr() for t in ps], *pad), arr(*[t.data_ptr() for t in us], *pad), len(ps),
+                                                  int(kind), B, Hg + row_offset, W, row_offset, _ptr(g), Hg, float(maxdisp), int(mode),
+                                                  _ptr(hist), _stream()), "lws_sparsification")
+    return hist
+
+
 def lr_pairs(left, right):
     """The input of the left-right check's one forward of 2B pairs (include/lwsnet_hip.h, lws_lr_pairs): left, right [B,3,H,W]
     float32 -> left2 = [left; mirror_w(right)], right2 = [right; mirror_w(left)], each [2B,3,H,W], bit copies."""
