@@ -89,21 +89,6 @@ struct StopArm {
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
-// The argument checks lws_lr_check and lws_occlusion_check share, under the caller's prefix `who`; `why` is the parenthesis that
-// says what the caller keeps in LDS, so that W <= max_w.  dRm: NULL for a check without right-view maps.
-static inline int check_row_check_args(const char *who, const char *why, int max_w, const float *const dL[4], const float *const dRm[4],
-                                       int nmaps, int B, int H, int W, float tau, int fill, float *const out[4], uint8_t *const mask[4])
-{
-    LWS_CHECK_ARG(nmaps >= 1 && nmaps <= 4, "%s: nmaps %d outside 1..4", who, nmaps);
-    LWS_CHECK_ARG(B >= 1 && B <= 65535 && H >= 1 && W >= 1, "%s: bad shape B=%d H=%d W=%d", who, B, H, W);
-    LWS_CHECK_ARG(W <= max_w, "%s: W=%d exceeds %d %s", who, W, max_w, why);
-    LWS_CHECK_ARG(tau >= 0.0f && tau <= 3.4028234663852886e38f, "%s: tau must be finite and >= 0, got %g", who, (double)tau);
-    LWS_CHECK_ARG(fill == 0 || fill == 1, "%s: fill %d (0 = zero, 1 = background fill)", who, fill);
-    for (int s = 0; s < nmaps; ++s)
-        LWS_CHECK_ARG(dL[s] && (!dRm || dRm[s]) && out[s] && mask[s], "%s: map %d has a null pointer", who, s);
-    return LWS_OK;
-}
-
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of (function, device).  One mask per launch site, one bit per
 // device; handles on different host threads reach a launch site concurrently (lws_pool, bench.py's pipelined mode), so the
 // mask is atomic -- a lost race only repeats the idempotent call.  Devices >= 64 set the attribute on every launch.

@@ -5,6 +5,7 @@
 // full-resolution maps are k_upsample_add's resize of the two.  One IEEE float32 operation per step.
 #include "lws_common.h"
 #include "lws_device_math.h"
+#include "lws_opkit.h"
 
 namespace lws {
 
@@ -182,7 +183,7 @@ extern "C" int lws_softargmin_conf(const float *cost, int B, int D, int h, int w
 {
     LWS_CHECK_ARG(cost, "softargmin_conf: null cost");
     LWS_CHECK_ARG(disp_low || peak_low || sigma_low || conf || sigma, "softargmin_conf: every output is null");
-    LWS_CHECK_ARG(B >= 1 && B <= 65535 && D >= 1 && h >= 1 && w >= 1, "softargmin_conf: bad shape B=%d D=%d h=%d w=%d", B, D, h, w);
+    LWS_CHECK_ARG(opkit::shape_ok(B, h, w) && D >= 1, "softargmin_conf: bad shape B=%d D=%d h=%d w=%d", B, D, h, w);
     // (float)H and the source coordinates are exact up to 2^24; the tile grid's y extent is h / 2 at most
     LWS_CHECK_ARG(H >= h && W >= w && H <= (1 << 24) && W <= (1 << 24) && h <= 2 * 65535,
                   "softargmin_conf: bad full-resolution size %dx%d for a %dx%d map", H, W, h, w);

@@ -4,11 +4,13 @@
 // Determinism: no atomics; the point cloud is packed in raster order by a per-row count, a per-image scan and a per-row scatter
 // whose ranks come from wave ballots, so an image gives the same bytes in any batch.  0 bytes of scratch.
 #include "lws_common.h"
+#include "lws_opkit.h"
 
 namespace lws {
 
 namespace {
 
+using namespace opkit;
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 
@@ -22,8 +24,6 @@ __device__ __forceinline__ Cam load_cam(const float *__restrict__ cam, int b)
     const float *c = cam + 5 * (int64_t)b;
     return Cam{c[0], c[1], c[2], c[3], c[4]};
 }
-
-__host__ __device__ __forceinline__ bool aligned(const void *p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
 
 // The 4 pixels x .. x+3 of a row: float4 where the row is 16-byte aligned, scalar for a misaligned row and the tail (NaN beyond
 // the row: never valid).
@@ -161,10 +161,10 @@ __global__ __launch_bounds__(kThreads) void k_pc_count(const float *__restrict__
         float d[4], z[4];
         n += __builtin_popcount(quad_valid(dp, mk, vd, vm, q, W, c, min_disp, max_depth, d, z));
     }
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o, 64);
+    n = wave_sum(n);
     if ((t & 63) == 0) s_n[t >> 6] = n;
     __syncthreads();
-    if (t == 0) row_count[(int64_t)b * H + y] = (s_n[0] + s_n[1]) + (s_n[2] + s_n[3]);
+    if (t == 0) row_count[(int64_t)b * H + y] = sum4(s_n[0], s_n[1], s_n[2], s_n[3]);
 }
 
 // grid (B), 256 threads: row_count[b][.] -> its exclusive scan, in place; counts[b] = the total.
@@ -269,10 +269,8 @@ __global__ __launch_bounds__(kThreads) void k_pc_scatter(const float *__restrict
 int check_geometry_args(const char *who, const float *disp, int B, int H, int W, float min_disp, float max_depth)
 {
     LWS_CHECK_ARG(disp, "%s: disp is null", who);
-    LWS_CHECK_ARG(B >= 1 && B <= 65535 && H >= 1 && W >= 1, "%s: bad shape B=%d H=%d W=%d", who, B, H, W);
-    LWS_CHECK_ARG((int64_t)H * W < ((int64_t)1 << 31), "%s: H*W = %dx%d must be < 2^31", who, H, W);
-    LWS_CHECK_ARG(min_disp > 0.0f && min_disp <= 3.4028234663852886e38f, "%s: min_disp must be finite and > 0, got %g", who,
-                  (double)min_disp);
+    LWS_CHECK_RC(check_image_shape(who, B, H, W, 31));
+    LWS_CHECK_ARG(min_disp > 0.0f && finite_nonneg(min_disp), "%s: min_disp must be finite and > 0, got %g", who, (double)min_disp);
     LWS_CHECK_ARG(max_depth > 0.0f, "%s: max_depth must be > 0 (+inf allowed), got %g", who, (double)max_depth);   // (false for NaN)
     LWS_CHECK_ARG(aligned(disp, 4), "%s: disp is not 4-byte aligned", who);
     return LWS_OK;
@@ -289,8 +287,7 @@ extern "C" {
 int lws_depth_maps(const float *disp, const uint8_t *mask, const float *cam, int B, int H, int W, float min_disp, float max_depth,
                    float *depth, uint16_t *depth16, uint16_t *disp16, void *stream)
 {
-    const int rc = check_geometry_args("depth_maps", disp, B, H, W, min_disp, max_depth);
-    if (rc != LWS_OK) return rc;
+    LWS_CHECK_RC(check_geometry_args("depth_maps", disp, B, H, W, min_disp, max_depth));
     LWS_CHECK_ARG(depth || depth16 || disp16, "depth_maps: no output requested (depth, depth16 and disp16 are all null)");
     LWS_CHECK_ARG(cam || !(depth || depth16), "depth_maps: cam is null but depth or depth16 is requested");
     LWS_CHECK_ARG(aligned(cam, 4) && aligned(depth, 4) && aligned(depth16, 2) && aligned(disp16, 2),
@@ -312,8 +309,7 @@ int64_t lws_point_cloud_workspace(int B, int H)
 int lws_point_cloud(const float *disp, const uint8_t *mask, const uint8_t *rgb, const float *cam, int B, int H, int W, float min_disp,
                     float max_depth, void *workspace, void *points, int64_t *counts, void *stream)
 {
-    const int rc = check_geometry_args("point_cloud", disp, B, H, W, min_disp, max_depth);
-    if (rc != LWS_OK) return rc;
+    LWS_CHECK_RC(check_geometry_args("point_cloud", disp, B, H, W, min_disp, max_depth));
     LWS_CHECK_ARG(cam && workspace && points && counts, "point_cloud: cam, workspace, points and counts must not be null");
     LWS_CHECK_ARG(aligned(cam, 4) && aligned(workspace, 4) && aligned(points, 16) && aligned(counts, 8),
                   "point_cloud: cam / workspace must be 4-byte, points 16-byte, counts 8-byte aligned");

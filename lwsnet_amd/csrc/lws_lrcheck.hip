@@ -48,7 +48,7 @@ __global__ __launch_bounds__(kThreads) void k_lr_check(LrMaps m, int H, int W, f
     const float *dl = m.dl[s] + row, *rm = m.drm[s] + row;
     float *out = m.out[s] + row, *rt = m.right[s] ? m.right[s] + row : nullptr;
     uint8_t *mk = m.mask[s] + row;
-    const bool vdl = aligned16(dl), vout = aligned16(out), vrt = aligned16(rt), vmk = aligned4(mk);
+    const bool vdl = aligned(dl, 16), vout = aligned(out, 16), vrt = aligned(rt, 16), vmk = aligned(mk, 4);
 
     stage_row(s_row, rm, W, nq);                            // the mirrored right-view row
     __syncthreads();
@@ -142,8 +142,7 @@ int lws_lr_check(const float *const dL[4], const float *const dRm[4], int nmaps,
                  float *const out[4], uint8_t *const mask[4], float *const right[4], int32_t *row_kept, void *stream)
 {
     LWS_CHECK_ARG(dL && dRm && out && mask, "lr_check: null pointer");
-    const int rc = check_row_check_args("lr_check", "(the row is staged in LDS)", kMaxW, dL, dRm, nmaps, B, H, W, tau, fill, out, mask);
-    if (rc != LWS_OK) return rc;
+    LWS_CHECK_RC(opkit::check_row_check_args("lr_check", "(the row is staged in LDS)", kMaxW, dL, dRm, nmaps, B, H, W, tau, fill, out, mask));
     LrMaps m = {};
     for (int s = 0; s < nmaps; ++s) {
         m.dl[s] = dL[s];

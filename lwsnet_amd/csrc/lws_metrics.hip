@@ -10,11 +10,13 @@
 // workgroup owns depends on the image's geometry only, and the float4 and the scalar loads feed the same order, so an image gives the
 // same bits in any batch, at any alignment (tests/test_gpu_evaluate.py).
 #include "lws_common.h"
+#include "lws_opkit.h"
 
 namespace lws {
 
 namespace {
 
+using namespace opkit;                                      // wave_sum, sum4, gt_pixel, load_gt_quad and the ground-truth checks
 constexpr int kThreads = 256;
 constexpr int kSteps = 4;                                   // quads per thread
 constexpr int kQuadsPerBlock = kThreads * kSteps;           // 1024 quads = 4096 pixels per workgroup
@@ -27,22 +29,6 @@ struct Partial {                                            // one (image, workg
 
 int64_t blocks_per_image(int64_t npix) { return (npix + 4 * kQuadsPerBlock - 1) / (4 * kQuadsPerBlock); }
 
-__device__ __forceinline__ int wave_sum_i(int v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ long long wave_sum_ll(long long v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 struct Acc {
     int valid = 0, bad = 0;
     double sum = 0.0;
@@ -50,11 +36,10 @@ struct Acc {
 
 __device__ __forceinline__ void pixel(Acc &a, float p, float g, float md, int mode)
 {
-    const bool valid = (mode == 0 ? g > 0.0f : true) && g < md;
-    const float e = fabsf(p - g);
-    a.valid += valid ? 1 : 0;
-    a.bad += (valid && e > 3.0f && e / g > 0.05f) ? 1 : 0;
-    if (valid) a.sum += (double)e;                          // NaN e of a valid pixel propagates, as np.mean does
+    const GtPixel x = gt_pixel(p, g, md, mode);
+    a.valid += x.valid ? 1 : 0;
+    a.bad += x.bad ? 1 : 0;
+    if (x.valid) a.sum += (double)x.e;                      // NaN e of a valid pixel propagates, as np.mean does
 }
 
 // grid (blocks_per_image, B), 256 threads.  pred[s] + b * pred_img + pred_off is image b's first ground-truth row of stage s.
@@ -65,8 +50,8 @@ __global__ __launch_bounds__(kThreads) void k_stage_metrics(const float *__restr
 {
     const int b = blockIdx.y, t = threadIdx.x;
     const float *g = gt + (int64_t)b * npix;
-    const float *ps[4] = {p0 + b * pred_img + pred_off, p1 + b * pred_img + pred_off, p2 + b * pred_img + pred_off,
-                          p3 + b * pred_img + pred_off};
+    const float *const ps[4] = {p0 + b * pred_img + pred_off, p1 + b * pred_img + pred_off, p2 + b * pred_img + pred_off,
+                                p3 + b * pred_img + pred_off};
     uintptr_t bits = (uintptr_t)g;
 #pragma unroll
     for (int s = 0; s < 4; ++s) bits |= (uintptr_t)ps[s];
@@ -77,18 +62,7 @@ __global__ __launch_bounds__(kThreads) void k_stage_metrics(const float *__restr
         const int64_t i = 4 * ((int64_t)blockIdx.x * kQuadsPerBlock + k * kThreads + t);
         if (i >= npix) break;
         float4 gq, pq[4];
-        if (vec && i + 4 <= npix) {
-            gq = *reinterpret_cast<const float4 *>(g + i);
-#pragma unroll
-            for (int s = 0; s < 4; ++s) pq[s] = *reinterpret_cast<const float4 *>(ps[s] + i);
-        } else {                                            // misaligned image or the last, partial quad: a missing pixel has
-            const float nan = __builtin_nanf("");           // gt = NaN, which no mode counts as valid
-            gq = make_float4(g[i], i + 1 < npix ? g[i + 1] : nan, i + 2 < npix ? g[i + 2] : nan, i + 3 < npix ? g[i + 3] : nan);
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-                pq[s] = make_float4(ps[s][i], i + 1 < npix ? ps[s][i + 1] : 0.0f, i + 2 < npix ? ps[s][i + 2] : 0.0f,
-                                    i + 3 < npix ? ps[s][i + 3] : 0.0f);
-        }
+        load_gt_quad(g, ps, i, npix, vec, gq, pq);
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             pixel(acc[s], pq[s].x, gq.x, md, mode);
@@ -102,8 +76,8 @@ __global__ __launch_bounds__(kThreads) void k_stage_metrics(const float *__restr
     const int wave = t >> 6, lane = t & 63;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-        const int v = wave_sum_i(acc[s].valid), bd = wave_sum_i(acc[s].bad);
-        const double sm = wave_sum_d(acc[s].sum);
+        const int v = wave_sum(acc[s].valid), bd = wave_sum(acc[s].bad);
+        const double sm = wave_sum(acc[s].sum);
         if (lane == 0) {
             s_cnt[wave][s][0] = v;
             s_cnt[wave][s][1] = bd;
@@ -113,9 +87,9 @@ __global__ __launch_bounds__(kThreads) void k_stage_metrics(const float *__restr
     __syncthreads();
     if (t < 4) {
         Partial o;
-        o.valid = (long long)s_cnt[0][t][0] + s_cnt[1][t][0] + s_cnt[2][t][0] + s_cnt[3][t][0];
-        o.bad = (long long)s_cnt[0][t][1] + s_cnt[1][t][1] + s_cnt[2][t][1] + s_cnt[3][t][1];
-        o.abs_sum = (s_sum[0][t] + s_sum[1][t]) + (s_sum[2][t] + s_sum[3][t]);
+        o.valid = sum4<long long>(s_cnt[0][t][0], s_cnt[1][t][0], s_cnt[2][t][0], s_cnt[3][t][0]);
+        o.bad = sum4<long long>(s_cnt[0][t][1], s_cnt[1][t][1], s_cnt[2][t][1], s_cnt[3][t][1]);
+        o.abs_sum = sum4(s_sum[0][t], s_sum[1][t], s_sum[2][t], s_sum[3][t]);
         part[((int64_t)b * gridDim.x + blockIdx.x) * 4 + t] = o;
     }
 }
@@ -133,9 +107,9 @@ __global__ __launch_bounds__(kThreads) void k_stage_metrics_sum(const Partial *_
         bd += q.bad;
         sm += q.abs_sum;
     }
-    v = wave_sum_ll(v);
-    bd = wave_sum_ll(bd);
-    sm = wave_sum_d(sm);
+    v = wave_sum(v);
+    bd = wave_sum(bd);
+    sm = wave_sum(sm);
     __shared__ long long s_cnt[kWaves][2];
     __shared__ double s_sum[kWaves];
     const int wave = t >> 6;
@@ -147,13 +121,11 @@ __global__ __launch_bounds__(kThreads) void k_stage_metrics_sum(const Partial *_
     __syncthreads();
     if (t == 0) {
         const int64_t o = (int64_t)s * B + b;
-        counts[2 * o] = s_cnt[0][0] + s_cnt[1][0] + s_cnt[2][0] + s_cnt[3][0];
-        counts[2 * o + 1] = s_cnt[0][1] + s_cnt[1][1] + s_cnt[2][1] + s_cnt[3][1];
-        abs_sum[o] = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
+        counts[2 * o] = sum4(s_cnt[0][0], s_cnt[1][0], s_cnt[2][0], s_cnt[3][0]);
+        counts[2 * o + 1] = sum4(s_cnt[0][1], s_cnt[1][1], s_cnt[2][1], s_cnt[3][1]);
+        abs_sum[o] = sum4(s_sum[0], s_sum[1], s_sum[2], s_sum[3]);
     }
 }
-
-constexpr int64_t kMaxPixels = (int64_t)1 << 40;            // blocks per image stay far below the grid limit
 
 }  // namespace
 
@@ -165,10 +137,8 @@ extern "C" {
 
 int64_t lws_stage_metrics_workspace(int B, int Hg, int Wg)
 {
-    LWS_CHECK_ARG(B >= 1 && B <= 65535 && Hg >= 1 && Wg >= 1, "stage_metrics_workspace: bad shape B=%d %dx%d", B, Hg, Wg);
-    const int64_t npix = (int64_t)Hg * Wg;
-    LWS_CHECK_ARG(npix <= kMaxPixels, "stage_metrics_workspace: %dx%d is too large", Hg, Wg);
-    return (int64_t)B * blocks_per_image(npix) * 4 * (int64_t)sizeof(Partial);
+    LWS_CHECK_RC(check_gt_args("stage_metrics_workspace", B, Hg, Wg, nullptr));
+    return (int64_t)B * blocks_per_image((int64_t)Hg * Wg) * 4 * (int64_t)sizeof(Partial);
 }
 
 int lws_stage_metrics(const float *const pred[4], int B, int Hp, int W, int row_offset, const float *gt, int Hg, float maxdisp,
@@ -176,13 +146,9 @@ int lws_stage_metrics(const float *const pred[4], int B, int Hp, int W, int row_
 {
     LWS_CHECK_ARG(pred && gt && workspace && counts && abs_sum, "stage_metrics: null pointer");
     for (int s = 0; s < 4; ++s) LWS_CHECK_ARG(pred[s], "stage_metrics: pred[%d] is null", s);
-    LWS_CHECK_ARG(B >= 1 && B <= 65535 && Hg >= 1 && W >= 1, "stage_metrics: bad shape B=%d Hg=%d W=%d", B, Hg, W);
-    LWS_CHECK_ARG(row_offset >= 0, "stage_metrics: row_offset %d < 0", row_offset);
-    LWS_CHECK_ARG(Hp == Hg + row_offset, "stage_metrics: Hp=%d must be Hg + row_offset = %d + %d", Hp, Hg, row_offset);
-    LWS_CHECK_ARG(mode == 0 || mode == 1, "stage_metrics: mode %d (0 = KITTI 3-px, 1 = EPE)", mode);
-    LWS_CHECK_ARG(maxdisp > 0.0f, "stage_metrics: maxdisp must be > 0, got %g", (double)maxdisp);   // (false for NaN)
+    const GtRows rows = {Hp, row_offset, maxdisp, mode};
+    LWS_CHECK_RC(check_gt_args("stage_metrics", B, Hg, W, &rows));
     const int64_t npix = (int64_t)Hg * W;
-    LWS_CHECK_ARG(npix <= kMaxPixels, "stage_metrics: %dx%d is too large", Hg, W);
     const int64_t nblk = blocks_per_image(npix);
     Partial *part = static_cast<Partial *>(workspace);
     hipStream_t st = (hipStream_t)stream;

@@ -50,7 +50,7 @@ __global__ __launch_bounds__(kThreads) void k_occ_check(OccMaps m, int H, int W,
     const float *dl = m.dl[s] + row;
     float *out = m.out[s] + row, *rt = m.right[s] ? m.right[s] + row : nullptr;
     uint8_t *mk = m.mask[s] + row;
-    const bool vout = aligned16(out), vrt = aligned16(rt), vmk = aligned4(mk);
+    const bool vout = aligned(out, 16), vrt = aligned(rt, 16), vmk = aligned(mk, 4);
     const float wmax = (float)(W - 1);
 
     stage_row(s_row, dl, W, nq);                            // out may be dl: every load of the row is done before any store
@@ -128,9 +128,8 @@ int lws_occlusion_check(const float *const dL[4], int nmaps, int B, int H, int W
                         uint8_t *const mask[4], float *const right[4], int32_t *row_kept, void *stream)
 {
     LWS_CHECK_ARG(dL && out && mask, "occlusion_check: null pointer");
-    const int rc = check_row_check_args("occlusion_check", "(the row and its z-buffer are held in LDS)", kMaxW, dL, nullptr, nmaps, B, H, W, tau,
-                                        fill, out, mask);
-    if (rc != LWS_OK) return rc;
+    LWS_CHECK_RC(opkit::check_row_check_args("occlusion_check", "(the row and its z-buffer are held in LDS)", kMaxW, dL, nullptr, nmaps, B, H, W,
+                                             tau, fill, out, mask));
     OccMaps m = {};
     for (int s = 0; s < nmaps; ++s) {
         m.dl[s] = dL[s];

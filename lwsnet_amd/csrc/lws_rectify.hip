@@ -13,11 +13,13 @@
 // stride of 3, the packed row segment is 48 aligned dword stores (plus up to 3 head and 3 tail bytes on a misaligned row).
 // Determinism: no atomics, no data-dependent loop, every pixel a pure function of its image and record.  0 bytes of scratch.
 #include "lws_common.h"
+#include "lws_opkit.h"
 
 namespace lws {
 
 namespace {
 
+using namespace opkit;
 constexpr int kTW = 64;                 // tile width: one wave = 64 consecutive pixels of a row
 constexpr int kTH = 4;                  // tile height: one wave per row
 constexpr int kThreads = kTW * kTH;
@@ -114,15 +116,6 @@ __global__ __launch_bounds__(kThreads) void k_rectify_pair(const RectifyArgs a, 
     if (lane < tail) g[head + 4 * ndw + lane] = s[shift + head + 4 * ndw + lane];
 }
 
-// true when the byte ranges [a, a + na) and [b, b + nb) intersect (a null pointer is no range)
-bool overlap(const void *a, int64_t na, const void *b, int64_t nb)
-{
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return a && b && pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
-}
-
-bool aligned4(const void *p) { return ((uintptr_t)p & 3) == 0; }
-
 }  // namespace
 
 }  // namespace lws
@@ -163,22 +156,15 @@ int lws_rectify_pair(const uint8_t *const raw[2], const float *params, int B, in
             a.mean[ch] = mean[ch], a.std[ch] = std[ch];
         }
     }
-    LWS_CHECK_ARG(aligned4(params) && aligned4(a.input[0]) && aligned4(a.input[1]) && aligned4(a.map[0]) && aligned4(a.map[1]),
+    LWS_CHECK_ARG(aligned(params, 4) && aligned(a.input[0], 4) && aligned(a.input[1], 4) && aligned(a.map[0], 4) && aligned(a.map[1], 4),
                   "rectify_pair: params, input and map must be 4-byte aligned");
     // the eight outputs are written; an overlap of any of them with any other buffer is an error
     const int64_t src = (int64_t)B * Hs * Ws, px = (int64_t)B * H * W;
-    const struct {
-        const void *p;
-        int64_t n;
-        const char *name;
-    } bufs[] = {{a.rect[0], 3 * px, "rect[0]"},   {a.rect[1], 3 * px, "rect[1]"},   {a.input[0], 12 * px, "input[0]"},
-                {a.input[1], 12 * px, "input[1]"}, {a.valid[0], px, "valid[0]"},     {a.valid[1], px, "valid[1]"},
-                {a.map[0], 8 * px, "map[0]"},     {a.map[1], 8 * px, "map[1]"},     {raw[0], 3 * src, "raw[0]"},
-                {raw[1], 3 * src, "raw[1]"},      {params, (int64_t)B * 2 * kParams * 4, "params"}};
-    for (int i = 0; i < 8; ++i)
-        for (int j = i + 1; j < 11; ++j)
-            LWS_CHECK_ARG(!overlap(bufs[i].p, bufs[i].n, bufs[j].p, bufs[j].n), "rectify_pair: %s and %s overlap", bufs[j].name,
-                          bufs[i].name);
+    const Buf bufs[] = {{a.rect[0], 3 * px, "rect[0]"},   {a.rect[1], 3 * px, "rect[1]"},   {a.input[0], 12 * px, "input[0]"},
+                        {a.input[1], 12 * px, "input[1]"}, {a.valid[0], px, "valid[0]"},     {a.valid[1], px, "valid[1]"},
+                        {a.map[0], 8 * px, "map[0]"},     {a.map[1], 8 * px, "map[1]"},     {raw[0], 3 * src, "raw[0]"},
+                        {raw[1], 3 * src, "raw[1]"},      {params, (int64_t)B * 2 * kParams * 4, "params"}};
+    LWS_CHECK_RC(check_no_overlap("rectify_pair", bufs, 11, 8));
 
     const int ntx = cdiv(W, kTW), nty = cdiv(H, kTH);
     hipLaunchKernelGGL(k_rectify_pair, dim3((unsigned)((int64_t)ntx * nty), 2, B), dim3(kThreads), 0, (hipStream_t)stream, a, params, Hs,

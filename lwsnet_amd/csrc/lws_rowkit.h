@@ -7,7 +7,7 @@
 // No pointer a caller may alias with an output is __restrict__ here: out may be disp, mask_out may be mask, out[s] may be dL[s].
 #ifndef LWS_ROWKIT_H
 #define LWS_ROWKIT_H
-#include "lws_common.h"
+#include "lws_opkit.h"
 
 namespace lws {
 
@@ -17,14 +17,12 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kMaxW = 8192;                                 // a row of floats + two int per quad: 48 KiB of LDS at most
 constexpr int kNone = 0x7fffffff;                           // "no trusted pixel to the right"
-
-__device__ __forceinline__ bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-__device__ __forceinline__ bool aligned4(const void *p) { return ((uintptr_t)p & 3) == 0; }
+using opkit::aligned;
 
 // Stage `n` floats of a row into LDS: float4 where the row is 16-byte aligned, scalar for a misaligned row and the tail.
 __device__ __forceinline__ void stage_row(float *__restrict__ dst, const float *__restrict__ src, int W, int nq)
 {
-    const bool vec = aligned16(src);
+    const bool vec = aligned(src, 16);
     for (int q = threadIdx.x; q < nq; q += kThreads) {
         const int x = 4 * q;
         if (vec && x + 4 <= W) {
@@ -133,9 +131,7 @@ __device__ __forceinline__ void wave_sums(const int (&n)[N], int *slots)
     int v[N];
 #pragma unroll
     for (int j = 0; j < N; ++j) v[j] = n[j];
-    for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-        for (int j = 0; j < N; ++j) v[j] += __shfl_down(v[j], o, 64);
+    opkit::wave_sum_n(v);
     if ((threadIdx.x & 63) == 0)
 #pragma unroll
         for (int j = 0; j < N; ++j) slots[(threadIdx.x >> 6) * N + j] = v[j];
@@ -145,7 +141,7 @@ template <int N>
 __device__ __forceinline__ int row_total(const int *slots, int j)
 {
     static_assert(kWaves == 4, "the fixed order of the sum");
-    return (slots[j] + slots[N + j]) + (slots[2 * N + j] + slots[3 * N + j]);
+    return opkit::sum4(slots[j], slots[N + j], slots[2 * N + j], slots[3 * N + j]);
 }
 
 // Called by all kThreads threads once s_row holds the row's values and s_last[q] / s_first[q] the last / first trusted pixel

@@ -2,7 +2,7 @@
 // (Ilg et al. 2018).  For every map s, image b and valid ground-truth pixel, {1, bad, q} is added to two 1026-bin histograms: one
 // indexed by the uncertainty u (the ranking under test), one by the error e itself (the oracle ranking); q is e in 1/1024 px.  The
 // host turns the cumulative sums over ascending bins into the two sparsification curves (lwsnet_amd/metrics.py).
-// Arithmetic contract (include/lwsnet_hip.h): valid, bad and e are pixel() of lws_metrics.hip; every step is one IEEE float32
+// Arithmetic contract (include/lwsnet_hip.h): valid, bad and e are gt_pixel() of lws_opkit.h; every step is one IEEE float32
 // operation (the build has correctly rounded division and no contraction); the bin of a value is a function of its bits.
 // Determinism: every sum is an integer.  A workgroup owns 2 x 1026 private bins in LDS ({count | bad << 32} and the q sum, one
 // 64-bit word each), adds to them with LDS integer atomics and flushes its non-zero bins with 64-bit integer global atomics into
@@ -13,16 +13,17 @@
 // first valid lane add once per wave when there are at least kAggMin of them: the counts are popcounts of ballots, q is one
 // 64-bit wave sum.  The other lanes add on their own.
 #include "lws_common.h"
+#include "lws_opkit.h"
 
 namespace lws {
 
 namespace {
 
+using namespace opkit;                                      // wave_sum, gt_pixel, load_gt_quad, overlap and the ground-truth checks
 constexpr int kBins = LWS_SPARS_BINS;
 constexpr int kThreads = 512;
 constexpr int kMaxSteps = 8;                                // quads per thread: at most 16384 pixels per workgroup
 constexpr int kAggMin = 16;                                 // lanes on one bin from which one wave-level add replaces theirs
-constexpr int64_t kMaxPixels = (int64_t)1 << 40;            // blocks per image stay far below the grid limit
 
 typedef unsigned long long u64;
 
@@ -33,12 +34,6 @@ __device__ __forceinline__ int spars_bin(float v)
     if (!(v < 256.0f)) return kBins - 1;
     if (v < 0x1p-24f) return 0;
     return 1 + (int)((__float_as_uint(v) >> 18) - 3296u);
-}
-
-__device__ __forceinline__ u64 wave_sum_u64(u64 v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;                                               // lane 0 has the sum
 }
 
 // One pixel per lane into one ranking's bins, the whole wave converged.  cb: count | bad << 32 (a workgroup has fewer than 2^32
@@ -53,7 +48,7 @@ __device__ __forceinline__ void add_pixel(u64 *cb, u64 *qs, bool valid, int bin,
     bool own = valid;
     if (__popcll(m) >= kAggMin) {                           // wave-uniform
         const u64 nbad = (u64)__popcll(__ballot(same && bad));
-        const u64 qsum = wave_sum_u64(same ? q : 0);
+        const u64 qsum = wave_sum<u64>(same ? q : 0);
         if (lane == 0) {
             atomicAdd(&cb[lbin], (u64)__popcll(m) | (nbad << 32));
             if (qsum != 0) atomicAdd(&qs[lbin], qsum);
@@ -68,9 +63,9 @@ __device__ __forceinline__ void add_pixel(u64 *cb, u64 *qs, bool valid, int bin,
 
 __device__ __forceinline__ void pixel(u64 *cb, u64 *qs, float p, float uin, float g, float md, int mode, int kind, int lane)
 {
-    const bool valid = (mode == 0 ? g > 0.0f : true) && g < md;             // pixel() of lws_metrics.hip
-    const float e = fabsf(p - g);
-    const bool bad = valid && e > 3.0f && e / g > 0.05f;
+    const GtPixel x = gt_pixel(p, g, md, mode);
+    const bool valid = x.valid, bad = x.bad;
+    const float e = x.e;
     const float ec = e < 65536.0f ? e : 65536.0f;                           // fminf(e, 65536.0f): a NaN e is the worst error
     const u64 q = (u64)(long long)rintf(ec * 1024.0f);                      // 1/1024 px; the scaling is exact
     const float u = kind == 0 ? uin : 1.0f - uin;
@@ -91,10 +86,9 @@ __global__ __launch_bounds__(kThreads) void k_sparsification(Maps maps, int kind
     __shared__ u64 s_cb[2 * kBins], s_q[2 * kBins];
     const int b = blockIdx.y, B = gridDim.y, s = blockIdx.z, t = threadIdx.x, lane = t & 63;
     const float *g = gt + (int64_t)b * npix;
-    const float *p = maps.pred[s] + b * pred_img + pred_off, *un = maps.unc[s] + b * pred_img + pred_off;
-    const bool vec = ((((uintptr_t)g) | ((uintptr_t)p) | ((uintptr_t)un)) & 15) == 0;          // image-uniform
+    const float *const pu[2] = {maps.pred[s] + b * pred_img + pred_off, maps.unc[s] + b * pred_img + pred_off};
+    const bool vec = ((((uintptr_t)g) | ((uintptr_t)pu[0]) | ((uintptr_t)pu[1])) & 15) == 0;   // image-uniform
     const int64_t first = (int64_t)blockIdx.x * steps * kThreads * 4;
-    const float nan = __builtin_nanf("");
     for (int j = t; j < 2 * kBins; j += kThreads) {
         s_cb[j] = 0;
         s_q[j] = 0;
@@ -102,25 +96,13 @@ __global__ __launch_bounds__(kThreads) void k_sparsification(Maps maps, int kind
     __syncthreads();
     for (int k = 0; k < steps; ++k) {                       // every lane takes every step: the wave stays converged
         const int64_t i = first + 4 * ((int64_t)k * kThreads + t);
-        float4 gq = make_float4(nan, nan, nan, nan), pq = make_float4(0.0f, 0.0f, 0.0f, 0.0f), uq = pq;
-        if (vec && i + 4 <= npix) {
-            gq = *reinterpret_cast<const float4 *>(g + i);
-            pq = *reinterpret_cast<const float4 *>(p + i);
-            uq = *reinterpret_cast<const float4 *>(un + i);
-        } else if (i < npix) {                              // misaligned image or the last, partial quad: a missing pixel has
-            float *gv = &gq.x, *pv = &pq.x, *uv = &uq.x;        // gt = NaN, which no mode counts as valid
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-                if (i + c < npix) {
-                    gv[c] = g[i + c];
-                    pv[c] = p[i + c];
-                    uv[c] = un[i + c];
-                }
-        }
-        pixel(s_cb, s_q, pq.x, uq.x, gq.x, md, mode, kind, lane);
-        pixel(s_cb, s_q, pq.y, uq.y, gq.y, md, mode, kind, lane);
-        pixel(s_cb, s_q, pq.z, uq.z, gq.z, md, mode, kind, lane);
-        pixel(s_cb, s_q, pq.w, uq.w, gq.w, md, mode, kind, lane);
+        const float nan = __builtin_nanf("");               // a quad beyond the image: gt = NaN, no pixel of it is valid
+        float4 gq = make_float4(nan, nan, nan, nan), q[2] = {make_float4(0.0f, 0.0f, 0.0f, 0.0f), make_float4(0.0f, 0.0f, 0.0f, 0.0f)};
+        if (i < npix) load_gt_quad(g, pu, i, npix, vec, gq, q);
+        pixel(s_cb, s_q, q[0].x, q[1].x, gq.x, md, mode, kind, lane);
+        pixel(s_cb, s_q, q[0].y, q[1].y, gq.y, md, mode, kind, lane);
+        pixel(s_cb, s_q, q[0].z, q[1].z, gq.z, md, mode, kind, lane);
+        pixel(s_cb, s_q, q[0].w, q[1].w, gq.w, md, mode, kind, lane);
     }
     __syncthreads();
     u64 *h = hist + ((int64_t)s * B + b) * (2 * kBins * 3);
@@ -132,13 +114,6 @@ __global__ __launch_bounds__(kThreads) void k_sparsification(Maps maps, int kind
             if (q != 0) atomicAdd(&h[3 * j + 2], q);
         }
     }
-}
-
-// true when the byte ranges [a, a + na) and [b, b + nb) intersect
-bool overlap(const void *a, int64_t na, const void *b, int64_t nb)
-{
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
 }
 
 // Quads per thread.  A workgroup's flush costs up to 3 global atomics per bin whatever it has counted, so a workgroup takes as many
@@ -165,15 +140,12 @@ int lws_sparsification(const float *const pred[4], const float *const unc[4], in
     LWS_CHECK_ARG(nmaps >= 1 && nmaps <= 4, "sparsification: nmaps %d outside 1..4", nmaps);
     for (int s = 0; s < nmaps; ++s) LWS_CHECK_ARG(pred[s] && unc[s], "sparsification: pred[%d] or unc[%d] is null", s, s);
     LWS_CHECK_ARG(kind == 0 || kind == 1, "sparsification: kind %d (0 = sigma, 1 = conf)", kind);
-    LWS_CHECK_ARG(B >= 1 && B <= 65535 && Hg >= 1 && W >= 1, "sparsification: bad shape B=%d Hg=%d W=%d", B, Hg, W);
-    LWS_CHECK_ARG(row_offset >= 0, "sparsification: row_offset %d < 0", row_offset);
-    LWS_CHECK_ARG(Hp == Hg + row_offset, "sparsification: Hp=%d must be Hg + row_offset = %d + %d", Hp, Hg, row_offset);
-    LWS_CHECK_ARG(mode == 0 || mode == 1, "sparsification: mode %d (0 = KITTI 3-px, 1 = EPE)", mode);
-    LWS_CHECK_ARG(maxdisp > 0.0f, "sparsification: maxdisp must be > 0, got %g", (double)maxdisp);      // (false for NaN)
+    const GtRows rows = {Hp, row_offset, maxdisp, mode};
+    LWS_CHECK_RC(check_gt_args("sparsification", B, Hg, W, &rows));
     const int64_t npix = (int64_t)Hg * W;
-    LWS_CHECK_ARG(npix <= kMaxPixels, "sparsification: %dx%d is too large", Hg, W);
     const int64_t hist_bytes = (int64_t)nmaps * B * 2 * kBins * 3 * (int64_t)sizeof(int64_t);
     const int64_t map_bytes = (int64_t)B * Hp * W * 4;
+    // (not opkit's table: the written buffer is named first here, and pred and unc may overlap each other as they like)
     LWS_CHECK_ARG(!overlap(hist, hist_bytes, gt, (int64_t)B * npix * 4), "sparsification: hist and gt overlap");
     Maps maps = {};
     for (int s = 0; s < nmaps; ++s) {

@@ -28,10 +28,10 @@ namespace lws {
 namespace {
 
 using namespace rowkit;                                     // kThreads, kWaves, kMaxW and the pieces of k_sp_apply
+using namespace opkit;
 constexpr int kTH = 32, kTW = 64;                           // the tile of k_sp_tile
 constexpr int kTile = kTH * kTW;
 constexpr int kQuadsPerThread = kTile / 4 / kThreads;       // 2
-__host__ __device__ __forceinline__ bool aligned(const void *p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
 
 __device__ __forceinline__ bool sp_valid(float d, bool ok) { return ok && __builtin_isfinite(d) && d > 0.0f; }
 
@@ -40,7 +40,7 @@ __device__ __forceinline__ bool sp_joined(float a, float b, float max_diff) { re
 
 __device__ __forceinline__ void store_quad_i(int *__restrict__ p, int x, int W, const int v[4])
 {
-    if (x + 4 <= W && aligned16(p + x)) {
+    if (x + 4 <= W && aligned(p + x, 16)) {
         *reinterpret_cast<int4 *>(p + x) = make_int4(v[0], v[1], v[2], v[3]);
     } else {
 #pragma unroll
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(kThreads) void k_sp_tile(const float *__restrict__ 
             const float *dp = disp + img + (int64_t)y * W;
             const uint8_t *mk = mask ? mask + img + (int64_t)y * W : nullptr;
             bool ok[4] = {true, true, true, true};
-            if (x + 4 <= W && aligned16(dp + x)) {
+            if (x + 4 <= W && aligned(dp + x, 16)) {
                 const float4 v = *reinterpret_cast<const float4 *>(dp + x);
                 d[0] = v.x, d[1] = v.y, d[2] = v.z, d[3] = v.w;
             } else {
@@ -269,7 +269,7 @@ __global__ __launch_bounds__(kThreads) void k_sp_apply(const float *disp, const 
     const int *par = parent + img, *sz = size + img;
     float *op = out + row;
     uint8_t *mo = mask_out + row;
-    const bool vd = aligned16(dp), vout = aligned16(op), vmk = aligned4(mk), vmo = aligned4(mo);
+    const bool vd = aligned(dp, 16), vout = aligned(op, 16), vmk = aligned(mk, 4), vmo = aligned(mo, 4);
 
     KeptFlags kept;
     int n_valid = 0, n_removed = 0;
@@ -335,29 +335,15 @@ __global__ __launch_bounds__(kThreads) void k_sp_counts(const int *__restrict__ 
     long long n[3] = {0, 0, 0};
     for (int64_t y = t; y < H; y += kThreads)
         for (int j = 0; j < 3; ++j) n[j] += r[3 * y + j];
-    for (int o = 32; o > 0; o >>= 1)
+    for (int o = 32; o > 0; o >>= 1)                        // (wave_sum_n, spelt out: through it the 64-bit adds come out commuted)
         for (int j = 0; j < 3; ++j) n[j] += __shfl_down(n[j], o, 64);
     if (lane == 0)
         for (int j = 0; j < 3; ++j) s_n[wave][j] = n[j];
     __syncthreads();
-    if (t < 3) counts[3 * (int64_t)b + t] = (s_n[0][t] + s_n[1][t]) + (s_n[2][t] + s_n[3][t]);
+    if (t < 3) counts[3 * (int64_t)b + t] = sum4(s_n[0][t], s_n[1][t], s_n[2][t], s_n[3][t]);
 }
 
 constexpr int64_t round256(int64_t n) { return (n + 255) / 256 * 256; }
-
-int check_speckle_shape(const char *who, int B, int H, int W)
-{
-    LWS_CHECK_ARG(B >= 1 && B <= 65535 && H >= 1 && W >= 1, "%s: bad shape B=%d H=%d W=%d", who, B, H, W);
-    LWS_CHECK_ARG((int64_t)H * W < ((int64_t)1 << 31), "%s: H*W = %dx%d must be < 2^31", who, H, W);
-    return LWS_OK;
-}
-
-// true when the byte ranges [a, a + na) and [b, b + nb) intersect (a null pointer is no range)
-bool overlap(const void *a, int64_t na, const void *b, int64_t nb)
-{
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return a && b && pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
-}
 
 }  // namespace
 
@@ -369,8 +355,7 @@ extern "C" {
 
 int64_t lws_speckle_workspace(int B, int H, int W)
 {
-    const int rc = check_speckle_shape("speckle_workspace", B, H, W);
-    if (rc != LWS_OK) return rc;
+    LWS_CHECK_RC(check_image_shape("speckle_workspace", B, H, W, 31));
     const int64_t px = (int64_t)B * H * W;
     return 2 * round256(px * (int64_t)sizeof(int)) + round256(3 * (int64_t)B * H * (int64_t)sizeof(int));
 }
@@ -378,32 +363,22 @@ int64_t lws_speckle_workspace(int B, int H, int W)
 int lws_speckle_filter(const float *disp, const uint8_t *mask, int B, int H, int W, float max_diff, int max_size, int fill,
                        void *workspace, float *out, uint8_t *mask_out, int32_t *labels, int64_t *counts, void *stream)
 {
-    const int rc = check_speckle_shape("speckle_filter", B, H, W);
-    if (rc != LWS_OK) return rc;
+    LWS_CHECK_RC(check_image_shape("speckle_filter", B, H, W, 31));
     LWS_CHECK_ARG(disp && workspace && out && mask_out, "speckle_filter: disp, workspace, out and mask_out must not be null");
-    LWS_CHECK_ARG(max_diff >= 0.0f && max_diff <= 3.4028234663852886e38f, "speckle_filter: max_diff must be finite and >= 0, got %g",
-                  (double)max_diff);
+    LWS_CHECK_ARG(finite_nonneg(max_diff), "speckle_filter: max_diff must be finite and >= 0, got %g", (double)max_diff);
     LWS_CHECK_ARG(max_size >= 0, "speckle_filter: max_size must be >= 0, got %d", max_size);
-    LWS_CHECK_ARG(fill == 0 || fill == 1, "speckle_filter: fill %d (0 = zero, 1 = background fill)", fill);
+    LWS_CHECK_RC(check_fill("speckle_filter", fill));
     LWS_CHECK_ARG(!fill || W <= kMaxW, "speckle_filter: fill needs W <= %d (the row is staged in LDS), got %d", kMaxW, W);
     LWS_CHECK_ARG(aligned(disp, 4) && aligned(out, 4) && aligned(workspace, 16) && aligned(labels, 4) && aligned(counts, 8),
                   "speckle_filter: disp / out / labels must be 4-byte, counts 8-byte, workspace 16-byte aligned");
     const int64_t px = (int64_t)B * H * W;
     const int64_t ws = lws_speckle_workspace(B, H, W);
     // out may be disp itself and mask_out may be mask itself (a row is read before it is written, the labelling before both);
-    // any other overlap between an input, an output and the workspace is an error
-    const struct {
-        const void *p;
-        int64_t n;
-        const char *name;
-    } bufs[] = {{disp, 4 * px, "disp"}, {mask, px, "mask"},           {out, 4 * px, "out"},    {mask_out, px, "mask_out"},
-                {labels, 4 * px, "labels"}, {counts, 24 * (int64_t)B, "counts"}, {workspace, ws, "workspace"}};
-    for (int i = 0; i < 7; ++i)
-        for (int j = i + 1; j < 7; ++j) {
-            const bool same_ok = ((i == 0 && j == 2) || (i == 1 && j == 3)) && bufs[i].p == bufs[j].p;
-            LWS_CHECK_ARG(same_ok || !overlap(bufs[i].p, bufs[i].n, bufs[j].p, bufs[j].n), "speckle_filter: %s and %s overlap",
-                          bufs[i].name, bufs[j].name);
-        }
+    // any other overlap between an input, an output and the workspace is an error, disp and mask included: every pair is checked
+    const Buf bufs[] = {{workspace, ws, "workspace"}, {counts, 24 * (int64_t)B, "counts"}, {labels, 4 * px, "labels"}, {mask_out, px, "mask_out"},
+                        {out, 4 * px, "out"},         {mask, px, "mask"},                  {disp, 4 * px, "disp"}};
+    const int in_place[][2] = {{4, 6}, {3, 5}};             // out / disp, mask_out / mask
+    LWS_CHECK_RC(check_no_overlap("speckle_filter", bufs, 7, 7, in_place, 2));
 
     int *parent = static_cast<int *>(workspace);
     int *size = reinterpret_cast<int *>(static_cast<char *>(workspace) + round256(px * (int64_t)sizeof(int)));

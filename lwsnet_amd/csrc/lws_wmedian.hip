@@ -25,19 +25,19 @@
 // The counts are summed per wave by shuffles, per workgroup in LDS, and added to counts[b] with one 64-bit integer atomic per
 // workgroup and counter: integer adds, so their order cannot show.  0 bytes of scratch.
 #include "lws_common.h"
+#include "lws_opkit.h"
 
 namespace lws {
 
 namespace {
 
+using namespace opkit;
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kTH = 16, kTW = 64;                           // the output tile
 constexpr int kRowsPerThread = kTH / kWaves;                // 4
 constexpr int kLut = 766;                                   // s = |dr| + |dg| + |db| in 0 .. 765
 static_assert(kTW == 64 && kTH % kWaves == 0, "a wave owns one row of the tile at a time");
-
-__host__ __device__ __forceinline__ bool aligned(const void *p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
 
 __device__ __forceinline__ bool wm_valid(float d, bool ok) { return ok && __builtin_isfinite(d) && d > 0.0f; }
 
@@ -133,24 +133,15 @@ __global__ __launch_bounds__(kThreads) void k_wm_filter(const float *__restrict_
         n_filled += fill ? 1 : 0;
     }
     if (counts) {                                           // (uniform)
-        for (int o = 32; o > 0; o >>= 1) {
-            n_changed += __shfl_down(n_changed, o, 64);
-            n_filled += __shfl_down(n_filled, o, 64);
-        }
-        if (lane == 0) s_n[wave][0] = n_changed, s_n[wave][1] = n_filled;
+        int n[2] = {n_changed, n_filled};
+        wave_sum_n(n);
+        if (lane == 0) s_n[wave][0] = n[0], s_n[wave][1] = n[1];
         __syncthreads();
         if (t < 2) {
-            const int v = (s_n[0][t] + s_n[1][t]) + (s_n[2][t] + s_n[3][t]);
+            const int v = sum4(s_n[0][t], s_n[1][t], s_n[2][t], s_n[3][t]);
             if (v) atomicAdd(counts + 2 * (int64_t)b + t, (unsigned long long)v);
         }
     }
-}
-
-// true when the byte ranges [a, a + na) and [b, b + nb) intersect (a null pointer is no range)
-bool overlap(const void *a, int64_t na, const void *b, int64_t nb)
-{
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return a && b && pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
 }
 
 template <int R>
@@ -174,8 +165,7 @@ extern "C" {
 int lws_wmedian_filter(const float *disp, const uint8_t *mask, const uint8_t *rgb, const uint16_t *wlut, int B, int H, int W, int radius,
                        int fill_min, float *out, int64_t *counts, void *stream)
 {
-    LWS_CHECK_ARG(B >= 1 && B <= 65535 && H >= 1 && W >= 1, "wmedian_filter: bad shape B=%d H=%d W=%d", B, H, W);
-    LWS_CHECK_ARG((int64_t)H * W < ((int64_t)1 << 31), "wmedian_filter: H*W = %dx%d must be < 2^31", H, W);
+    LWS_CHECK_RC(check_image_shape("wmedian_filter", B, H, W, 31));
     LWS_CHECK_ARG(disp && out, "wmedian_filter: disp and out must not be null");
     LWS_CHECK_ARG(radius >= 1 && radius <= 3, "wmedian_filter: radius must be 1, 2 or 3, got %d", radius);
     LWS_CHECK_ARG(fill_min >= 0, "wmedian_filter: fill_min must be >= 0, got %d", fill_min);
@@ -185,16 +175,9 @@ int lws_wmedian_filter(const float *disp, const uint8_t *mask, const uint8_t *rg
     const int64_t px = (int64_t)B * H * W;
     // out and counts are written; an overlap of either with anything else is an error (a neighbourhood of disp is read, so out may
     // not be disp either).  wlut is ignored without rgb.
-    const struct {
-        const void *p;
-        int64_t n;
-        const char *name;
-    } bufs[] = {{out, 4 * px, "out"}, {counts, 16 * (int64_t)B, "counts"}, {disp, 4 * px, "disp"},
-                {mask, px, "mask"},   {rgb, 3 * px, "rgb"},                {rgb ? wlut : nullptr, 2 * kLut, "wlut"}};
-    for (int i = 0; i < 2; ++i)
-        for (int j = i + 1; j < 6; ++j)
-            LWS_CHECK_ARG(!overlap(bufs[i].p, bufs[i].n, bufs[j].p, bufs[j].n), "wmedian_filter: %s and %s overlap", bufs[j].name,
-                          bufs[i].name);
+    const Buf bufs[] = {{out, 4 * px, "out"}, {counts, 16 * (int64_t)B, "counts"}, {disp, 4 * px, "disp"},
+                        {mask, px, "mask"},   {rgb, 3 * px, "rgb"},                {rgb ? wlut : nullptr, 2 * kLut, "wlut"}};
+    LWS_CHECK_RC(check_no_overlap("wmedian_filter", bufs, 6, 2));
 
     hipStream_t st = (hipStream_t)stream;
     if (counts) {

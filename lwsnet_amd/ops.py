@@ -49,12 +49,12 @@ def _disp_map(t, name):
     return t
 
 
-def _stage_maps(**lists):
-    """name = list of 1-4 stage maps: every map float32 on one device and of the shape [B,1,H,W] of the first.  Returns the lists
-    of contiguous tensors, that shape and the device."""
+def _stage_maps(like=None, **lists):
+    """name = list of 1-4 stage maps: every map float32 on one device and of the shape [B,1,H,W] of the first, or of the (shape,
+    device) `like`.  Returns the lists of contiguous tensors, that shape and the device."""
     ts = {name: [_dev(t, f"{name}[{s}]") for s, t in enumerate(v)] for name, v in lists.items()}
     first = next(iter(lists))
-    shape, dev = tuple(_disp_map(ts[first][0], f"{first}[0]").shape), ts[first][0].device
+    shape, dev = like or (tuple(_disp_map(ts[first][0], f"{first}[0]").shape), ts[first][0].device)
     for name, v in ts.items():
         for s, t in enumerate(v):
             if tuple(t.shape) != shape or t.device != dev:
@@ -352,16 +352,12 @@ def apply_lut8(disp, lut_dev, out=None):
 METRIC_MODES = {"kitti": 0, "epe": 1}
 
 
-def stage_metrics(preds, gt, row_offset, maxdisp, mode):
-    """The per-image sums behind the reference's test loops (finetune.py:184-219 error_estimating, mode 0 / "kitti";
-    train.py:169-199, mode 1 / "epe") on the device.  preds: the four [B,1,Hp,W] float32 stage maps; gt: [B,Hg,W] float32 with
-    Hp = Hg + row_offset.  Returns device tensors counts [4,B,2] int64 = {valid, bad} and abs_sum [4,B] float64 (include/lwsnet_hip.h,
-    lws_stage_metrics), allocated on the current stream."""
+def _gt_maps(gt, row_offset, mode, **lists):
+    """The inputs the evaluation ops share: mode as 0 / 1, gt [B,Hg,W], row_offset >= 0 and, per name, a list of maps that must
+    be [B,1,Hg + row_offset,W] on gt's device.  Returns mode, the contiguous gt, row_offset and the lists of contiguous maps."""
     mode = METRIC_MODES.get(mode, mode)
     if mode not in (0, 1):
         raise ValueError(f"mode must be 0 / 'kitti' or 1 / 'epe', got {mode!r}")
-    if not isinstance(preds, (list, tuple)) or len(preds) != 4:
-        raise ValueError("preds must be the four stage maps")
     g = _dev(gt, "gt")
     if g.dim() != 3:
         raise ValueError(f"gt must be [B,Hg,W]; got {tuple(g.shape)}")
@@ -369,12 +365,18 @@ def stage_metrics(preds, gt, row_offset, maxdisp, mode):
     row_offset = int(row_offset)
     if row_offset < 0:
         raise ValueError(f"row_offset must be >= 0, got {row_offset}")
-    ps = []
-    for s, p in enumerate(preds):
-        p = _dev(p, f"preds[{s}]")
-        if tuple(p.shape) != (B, 1, Hg + row_offset, W) or p.device != g.device:
-            raise ValueError(f"preds[{s}] must be {(B, 1, Hg + row_offset, W)} on {g.device}; got {tuple(p.shape)} on {p.device}")
-        ps.append(p)
+    return mode, g, row_offset, _stage_maps(like=((B, 1, Hg + row_offset, W), g.device), **lists)[0]
+
+
+def stage_metrics(preds, gt, row_offset, maxdisp, mode):
+    """The per-image sums behind the reference's test loops (finetune.py:184-219 error_estimating, mode 0 / "kitti";
+    train.py:169-199, mode 1 / "epe") on the device.  preds: the four [B,1,Hp,W] float32 stage maps; gt: [B,Hg,W] float32 with
+    Hp = Hg + row_offset.  Returns device tensors counts [4,B,2] int64 = {valid, bad} and abs_sum [4,B] float64 (include/lwsnet_hip.h,
+    lws_stage_metrics), allocated on the current stream."""
+    if not isinstance(preds, (list, tuple)) or len(preds) != 4:
+        raise ValueError("preds must be the four stage maps")
+    mode, g, row_offset, (ps,) = _gt_maps(gt, row_offset, mode, preds=preds)
+    B, Hg, W = g.shape
     lib = _lib.load()
     work = _workspace(lib, "lws_stage_metrics_workspace", g.device, B, Hg, W)
     counts = torch.empty((4, B, 2), device=g.device, dtype=torch.int64)
@@ -395,28 +397,13 @@ def sparsification(preds, unc, gt, row_offset, maxdisp, mode, kind):
     pixels of preds[s]: kind 0 / "sigma" (lower = more trusted) or 1 / "conf" (ranked by 1 - conf); gt, row_offset, maxdisp and
     mode as for stage_metrics.  Returns the device tensor hist [nmaps,B,2,1026,3] int64 = per map, image, ranking (0: by unc, 1: the
     oracle, by the error itself) and bin {pixels, bad pixels, error sum in 1/1024 px}, allocated on the current stream."""
-    mode = METRIC_MODES.get(mode, mode)
-    if mode not in (0, 1):
-        raise ValueError(f"mode must be 0 / 'kitti' or 1 / 'epe', got {mode!r}")
     kind = SPARS_KINDS.get(kind, kind)
     if kind not in (0, 1):
         raise ValueError(f"kind must be 0 / 'sigma' or 1 / 'conf', got {kind!r}")
     if not isinstance(preds, (list, tuple)) or not isinstance(unc, (list, tuple)) or not 1 <= len(preds) <= 4 or len(unc) != len(preds):
         raise ValueError("preds and unc must be lists of the same 1-4 maps")
-    g = _dev(gt, "gt")
-    if g.dim() != 3:
-        raise ValueError(f"gt must be [B,Hg,W]; got {tuple(g.shape)}")
+    mode, g, row_offset, (ps, us) = _gt_maps(gt, row_offset, mode, preds=preds, unc=unc)
     B, Hg, W = g.shape
-    row_offset = int(row_offset)
-    if row_offset < 0:
-        raise ValueError(f"row_offset must be >= 0, got {row_offset}")
-    ps, us = [], []
-    for name, src, dst in (("preds", preds, ps), ("unc", unc, us)):
-        for s, p in enumerate(src):
-            p = _dev(p, f"{name}[{s}]")
-            if tuple(p.shape) != (B, 1, Hg + row_offset, W) or p.device != g.device:
-                raise ValueError(f"{name}[{s}] must be {(B, 1, Hg + row_offset, W)} on {g.device}; got {tuple(p.shape)} on {p.device}")
-            dst.append(p)
     hist = torch.empty((len(ps), B, 2, _lib.LWS_SPARS_BINS, 3), device=g.device, dtype=torch.int64)
     pad = [None] * (4 - len(ps))
     arr = ctypes.c_void_p * 4

@@ -191,3 +191,23 @@ def test_stage_metrics_validates_on_host(hip_lib):
     for kw, msg in cases:
         assert call(**kw) == _lib.LWS_ERR_INVALID, kw
         assert msg in L.lws_last_error(), (kw, L.lws_last_error())
+    # the ground-truth checks shared with lws_sparsification and the workspace query: the whole text
+    texts = [(dict(B=0), b"stage_metrics: bad shape B=0 Hg=8 W=8"), (dict(B=65536), b"stage_metrics: bad shape B=65536 Hg=8 W=8"),
+             (dict(Hg=0, Hp=0), b"stage_metrics: bad shape B=1 Hg=0 W=8"), (dict(W=-1), b"stage_metrics: bad shape B=1 Hg=8 W=-1"),
+             (dict(off=-1, Hp=7), b"stage_metrics: row_offset -1 < 0"),
+             (dict(Hp=9), b"stage_metrics: Hp=9 must be Hg + row_offset = 8 + 0"),
+             (dict(off=2), b"stage_metrics: Hp=8 must be Hg + row_offset = 8 + 2"),
+             (dict(mode=2), b"stage_metrics: mode 2 (0 = KITTI 3-px, 1 = EPE)"),
+             (dict(md=0.0), b"stage_metrics: maxdisp must be > 0, got 0"),
+             (dict(md=float("nan")), b"stage_metrics: maxdisp must be > 0, got nan"),
+             (dict(Hg=1048577, Hp=1048577, W=1048576), b"stage_metrics: 1048577x1048576 is too large"),
+             (dict(gt=None), b"stage_metrics: null pointer"), (dict(pred=(ctypes.c_void_p * 4)(16, 16, 0, 16)), b"stage_metrics: pred[2] is null")]
+    for kw, msg in texts:
+        assert call(**kw) == _lib.LWS_ERR_INVALID, kw
+        assert L.lws_last_error() == msg, kw
+    for shape, msg in (((0, 4, 4), b"stage_metrics_workspace: bad shape B=0 4x4"), ((65536, 4, 4), b"stage_metrics_workspace: bad shape B=65536 4x4"),
+                       ((1, 0, 4), b"stage_metrics_workspace: bad shape B=1 0x4"), ((1, 4, -1), b"stage_metrics_workspace: bad shape B=1 4x-1"),
+                       ((1, 1048577, 1048576), b"stage_metrics_workspace: 1048577x1048576 is too large")):
+        assert L.lws_stage_metrics_workspace(*shape) == _lib.LWS_ERR_INVALID
+        assert L.lws_last_error() == msg
+    assert L.lws_stage_metrics_workspace(1, 1048576, 1048576) == (1 << 28) * 4 * 24      # 2^40 pixels are still allowed

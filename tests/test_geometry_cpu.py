@@ -203,6 +203,21 @@ def test_depth_maps_rejects_bad_arguments(hip_lib):
     for kw, msg in cases:
         assert call(**kw) == _lib.LWS_ERR_INVALID, kw
         assert msg in hip_lib.lws_last_error(), (kw, hip_lib.lws_last_error())
+    texts = [
+        (dict(B=0), b"depth_maps: bad shape B=0 H=8 W=16"), (dict(B=65536), b"depth_maps: bad shape B=65536 H=8 W=16"),
+        (dict(H=0), b"depth_maps: bad shape B=1 H=0 W=16"), (dict(W=-1), b"depth_maps: bad shape B=1 H=8 W=-1"),
+        (dict(H=1 << 16, W=1 << 15), b"depth_maps: H*W = 65536x32768 must be < 2^31"),
+        (dict(min_disp=0.0), b"depth_maps: min_disp must be finite and > 0, got 0"),
+        (dict(min_disp=-1.0), b"depth_maps: min_disp must be finite and > 0, got -1"),
+        (dict(min_disp=float("inf")), b"depth_maps: min_disp must be finite and > 0, got inf"),
+        (dict(min_disp=float("nan")), b"depth_maps: min_disp must be finite and > 0, got nan"),
+        (dict(disp=ctypes.c_void_p(258)), b"depth_maps: disp is not 4-byte aligned"),
+        (dict(cam=ctypes.c_void_p(258)), b"depth_maps: cam / depth must be 4-byte, depth16 / disp16 2-byte aligned"),
+        (dict(disp16=ctypes.c_void_p(257)), b"depth_maps: cam / depth must be 4-byte, depth16 / disp16 2-byte aligned"),
+    ]
+    for kw, msg in texts:
+        assert call(**kw) == _lib.LWS_ERR_INVALID, kw
+        assert hip_lib.lws_last_error() == msg, kw
 
 
 def test_point_cloud_rejects_bad_arguments(hip_lib):
@@ -218,7 +233,17 @@ def test_point_cloud_rejects_bad_arguments(hip_lib):
     for kw, msg in cases:
         assert call(**kw) == _lib.LWS_ERR_INVALID, kw
         assert msg in hip_lib.lws_last_error(), (kw, hip_lib.lws_last_error())
-    assert hip_lib.lws_point_cloud_workspace(2, 368) == 3072                             # 2 x 368 int32, in 256-byte units
+    texts = [
+        (dict(B=0), b"point_cloud: bad shape B=0 H=8 W=16"), (dict(W=0), b"point_cloud: bad shape B=1 H=8 W=0"),
+        (dict(H=1 << 20, W=1 << 11), b"point_cloud: H*W = 1048576x2048 must be < 2^31"),
+        (dict(min_disp=float("inf")), b"point_cloud: min_disp must be finite and > 0, got inf"),
+        (dict(disp=ctypes.c_void_p(258)), b"point_cloud: disp is not 4-byte aligned"),
+        (dict(counts=ctypes.c_void_p(260)), b"point_cloud: cam / workspace must be 4-byte, points 16-byte, counts 8-byte aligned"),
+    ]
+    for kw, msg in texts:
+        assert call(**kw) == _lib.LWS_ERR_INVALID, kw
+        assert hip_lib.lws_last_error() == msg, kw
+    assert hip_lib.lws_point_cloud_workspace(2, 368) == 3072                            # 2 x 368 int32, in 256-byte units
     assert hip_lib.lws_point_cloud_workspace(0, 368) == _lib.LWS_ERR_INVALID
 
 

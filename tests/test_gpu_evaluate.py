@@ -129,6 +129,24 @@ def test_stage_metrics_are_deterministic_and_batch_independent():
             assert np.array_equal(sb[:, 0].cpu().numpy().view(np.int64), s1[:, b].cpu().numpy().view(np.int64)), (B, W, b)
 
 
+@pytest.mark.parametrize("B,Hg,W,off", [(2, 3, 5, 0),          # one partial quad at the end of each image, one workgroup
+                                        (2, 37, 61, 3),        # misaligned images: the scalar loads
+                                        (1, 33, 125, 0),       # 4125 pixels: two workgroups, the second nearly empty
+                                        (1, 1025, 1024, 0)])   # 257 workgroups: the second launch's strided loop steps twice
+@pytest.mark.parametrize("mode", [0, 1])
+def test_stage_metrics_keep_the_documented_summation_order(B, Hg, W, off, mode):
+    """abs_sum bit for bit against tests/metrics_reference.py, which restates the order of float64 additions written in the header
+    of lws_metrics.hip: a sum in any other order passes check()'s rtol, this does not."""
+    import metrics_reference as REF
+    preds, gt = make(B, Hg, W, off, seed=B * 1000 + Hg + W + off)
+    got_c, got_s = run(preds, gt, off, 192, mode)
+    want_c, want_s = REF.stage_metrics(preds, gt, off, 192, mode)
+    assert np.array_equal(got_c, want_c), (mode, np.argwhere(got_c != want_c)[:5])
+    assert np.isfinite(want_s).all()
+    assert np.array_equal(got_s.view(np.int64), want_s.view(np.int64)), (mode, got_s, want_s)
+    np.testing.assert_allclose(want_s, expected(preds, gt, off, 192, mode)[1], rtol=1e-12)    # the restatement sums the same terms
+
+
 def test_stage_metrics_validate_shapes():
     from lwsnet_amd import ops
     dev = _dev()

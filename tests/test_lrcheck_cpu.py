@@ -117,6 +117,17 @@ def test_lr_check_rejects_bad_arguments(hip_lib):
     for kw, msg in cases:
         assert call(**kw) == _lib.LWS_ERR_INVALID, kw
         assert msg in hip_lib.lws_last_error(), (kw, hip_lib.lws_last_error())
+    texts = [
+        (dict(nmaps=5), b"lr_check: nmaps 5 outside 1..4"), (dict(B=0), b"lr_check: bad shape B=0 H=8 W=16"),
+        (dict(B=65536), b"lr_check: bad shape B=65536 H=8 W=16"), (dict(W=-1), b"lr_check: bad shape B=1 H=8 W=-1"),
+        (dict(W=8193), b"lr_check: W=8193 exceeds 8192 (the row is staged in LDS)"),
+        (dict(tau=-0.5), b"lr_check: tau must be finite and >= 0, got -0.5"), (dict(tau=float("inf")), b"lr_check: tau must be finite and >= 0, got inf"),
+        (dict(tau=float("nan")), b"lr_check: tau must be finite and >= 0, got nan"),
+        (dict(fill=2), b"lr_check: fill 2 (0 = zero, 1 = background fill)"), (dict(mask=_arr(3)), b"lr_check: map 3 has a null pointer"),
+    ]
+    for kw, msg in texts:
+        assert call(**kw) == _lib.LWS_ERR_INVALID, kw
+        assert hip_lib.lws_last_error() == msg, kw
     null4 = _arr(0)
     assert hip_lib.lws_lr_check(null4, _arr(), 1, 1, 8, 16, 1.0, 0, _arr(), _arr(), null4, None, None) == _lib.LWS_ERR_INVALID
     assert hip_lib.lws_lr_check(_arr(), _arr(), 1, 1, 8, 16, 1.0, 0, null4, _arr(), null4, None, None) == _lib.LWS_ERR_INVALID

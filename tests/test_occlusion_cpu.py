@@ -224,6 +224,17 @@ def test_occlusion_check_rejects_bad_arguments(hip_lib):
         assert call(**kw) == _lib.LWS_ERR_INVALID, kw
         err = hip_lib.lws_last_error()
         assert msg in err and b"occlusion_check" in err, (kw, err)
+    texts = [
+        (dict(nmaps=5), b"occlusion_check: nmaps 5 outside 1..4"), (dict(B=0), b"occlusion_check: bad shape B=0 H=8 W=16"),
+        (dict(B=65536), b"occlusion_check: bad shape B=65536 H=8 W=16"), (dict(W=-1), b"occlusion_check: bad shape B=1 H=8 W=-1"),
+        (dict(tau=-0.5), b"occlusion_check: tau must be finite and >= 0, got -0.5"),
+        (dict(tau=float("inf")), b"occlusion_check: tau must be finite and >= 0, got inf"),
+        (dict(tau=float("nan")), b"occlusion_check: tau must be finite and >= 0, got nan"),
+        (dict(fill=2), b"occlusion_check: fill 2 (0 = zero, 1 = background fill)"), (dict(out=_arr(2)), b"occlusion_check: map 2 has a null pointer"),
+    ]
+    for kw, msg in texts:
+        assert call(**kw) == _lib.LWS_ERR_INVALID, kw
+        assert hip_lib.lws_last_error() == msg, kw
     # dL, out, mask themselves NULL: through a second handle of the library, whose prototype takes the arrays as plain pointers
     _, args = _lib.PROTOTYPES["lws_occlusion_check"]
     fn = ctypes.CDLL(_lib.LIB_PATH).lws_occlusion_check

@@ -191,6 +191,76 @@ def test_argument_errors_through_the_c_abi(hip_lib):
     assert _call(lib, std=(0.0, 0.0, 0.0), border=300) == _lib.LWS_ERR_INVALID and b"border" in lib.lws_last_error()
 
 
+# (moved buffer, the written buffer it is moved 4 bytes into, the whole error): every written / any pair of the table, each alone
+_OVERLAPS = [
+    ("rect[1]", "rect[0]", b"rectify_pair: rect[1] and rect[0] overlap"),
+    ("input[0]", "rect[0]", b"rectify_pair: input[0] and rect[0] overlap"),
+    ("input[1]", "rect[0]", b"rectify_pair: input[1] and rect[0] overlap"),
+    ("valid[0]", "rect[0]", b"rectify_pair: valid[0] and rect[0] overlap"),
+    ("valid[1]", "rect[0]", b"rectify_pair: valid[1] and rect[0] overlap"),
+    ("map[0]", "rect[0]", b"rectify_pair: map[0] and rect[0] overlap"), ("map[1]", "rect[0]", b"rectify_pair: map[1] and rect[0] overlap"),
+    ("raw[0]", "rect[0]", b"rectify_pair: raw[0] and rect[0] overlap"), ("raw[1]", "rect[0]", b"rectify_pair: raw[1] and rect[0] overlap"),
+    ("params", "rect[0]", b"rectify_pair: params and rect[0] overlap"),
+    ("input[0]", "rect[1]", b"rectify_pair: input[0] and rect[1] overlap"),
+    ("input[1]", "rect[1]", b"rectify_pair: input[1] and rect[1] overlap"),
+    ("valid[0]", "rect[1]", b"rectify_pair: valid[0] and rect[1] overlap"),
+    ("valid[1]", "rect[1]", b"rectify_pair: valid[1] and rect[1] overlap"),
+    ("map[0]", "rect[1]", b"rectify_pair: map[0] and rect[1] overlap"), ("map[1]", "rect[1]", b"rectify_pair: map[1] and rect[1] overlap"),
+    ("raw[0]", "rect[1]", b"rectify_pair: raw[0] and rect[1] overlap"), ("raw[1]", "rect[1]", b"rectify_pair: raw[1] and rect[1] overlap"),
+    ("params", "rect[1]", b"rectify_pair: params and rect[1] overlap"),
+    ("input[1]", "input[0]", b"rectify_pair: input[1] and input[0] overlap"),
+    ("valid[0]", "input[0]", b"rectify_pair: valid[0] and input[0] overlap"),
+    ("valid[1]", "input[0]", b"rectify_pair: valid[1] and input[0] overlap"),
+    ("map[0]", "input[0]", b"rectify_pair: map[0] and input[0] overlap"),
+    ("map[1]", "input[0]", b"rectify_pair: map[1] and input[0] overlap"),
+    ("raw[0]", "input[0]", b"rectify_pair: raw[0] and input[0] overlap"),
+    ("raw[1]", "input[0]", b"rectify_pair: raw[1] and input[0] overlap"),
+    ("params", "input[0]", b"rectify_pair: params and input[0] overlap"),
+    ("valid[0]", "input[1]", b"rectify_pair: valid[0] and input[1] overlap"),
+    ("valid[1]", "input[1]", b"rectify_pair: valid[1] and input[1] overlap"),
+    ("map[0]", "input[1]", b"rectify_pair: map[0] and input[1] overlap"),
+    ("map[1]", "input[1]", b"rectify_pair: map[1] and input[1] overlap"),
+    ("raw[0]", "input[1]", b"rectify_pair: raw[0] and input[1] overlap"),
+    ("raw[1]", "input[1]", b"rectify_pair: raw[1] and input[1] overlap"),
+    ("params", "input[1]", b"rectify_pair: params and input[1] overlap"),
+    ("valid[1]", "valid[0]", b"rectify_pair: valid[1] and valid[0] overlap"),
+    ("map[0]", "valid[0]", b"rectify_pair: map[0] and valid[0] overlap"),
+    ("map[1]", "valid[0]", b"rectify_pair: map[1] and valid[0] overlap"),
+    ("raw[0]", "valid[0]", b"rectify_pair: raw[0] and valid[0] overlap"),
+    ("raw[1]", "valid[0]", b"rectify_pair: raw[1] and valid[0] overlap"),
+    ("params", "valid[0]", b"rectify_pair: params and valid[0] overlap"),
+    ("map[0]", "valid[1]", b"rectify_pair: map[0] and valid[1] overlap"),
+    ("map[1]", "valid[1]", b"rectify_pair: map[1] and valid[1] overlap"),
+    ("raw[0]", "valid[1]", b"rectify_pair: raw[0] and valid[1] overlap"),
+    ("raw[1]", "valid[1]", b"rectify_pair: raw[1] and valid[1] overlap"),
+    ("params", "valid[1]", b"rectify_pair: params and valid[1] overlap"), ("map[1]", "map[0]", b"rectify_pair: map[1] and map[0] overlap"),
+    ("raw[0]", "map[0]", b"rectify_pair: raw[0] and map[0] overlap"), ("raw[1]", "map[0]", b"rectify_pair: raw[1] and map[0] overlap"),
+    ("params", "map[0]", b"rectify_pair: params and map[0] overlap"), ("raw[0]", "map[1]", b"rectify_pair: raw[0] and map[1] overlap"),
+    ("raw[1]", "map[1]", b"rectify_pair: raw[1] and map[1] overlap"), ("params", "map[1]", b"rectify_pair: params and map[1] overlap"),
+]
+
+
+def test_every_overlapping_pair_is_named(hip_lib):
+    names = ["rect[0]", "rect[1]", "input[0]", "input[1]", "valid[0]", "valid[1]", "map[0]", "map[1]", "raw[0]", "raw[1]", "params"]
+    base = {n: (k + 1) << 24 for k, n in enumerate(names)}
+    assert len({frozenset(c[:2]) for c in _OVERLAPS}) == len(_OVERLAPS) == sum(10 - i for i in range(8))
+    for moved, onto, msg in _OVERLAPS:
+        a = {**base, moved: base[onto] + 4}
+        pair = lambda n: (a[n + "[0]"], a[n + "[1]"])         # noqa: E731
+        rc = _call(hip_lib, raw=pair("raw"), params=a["params"], rect=pair("rect"), inp=pair("input"), valid=pair("valid"), mp=pair("map"))
+        assert rc == _lib.LWS_ERR_INVALID, (moved, onto)
+        assert hip_lib.lws_last_error() == msg
+
+
+def test_shared_checks_keep_their_whole_text(hip_lib):
+    cases = [(dict(inp=((1 << 32) + 2, None)), b"rectify_pair: params, input and map must be 4-byte aligned"),
+             (dict(mp=(None, (1 << 33) + 1)), b"rectify_pair: params, input and map must be 4-byte aligned"),
+             (dict(params=(1 << 28) + 1), b"rectify_pair: params, input and map must be 4-byte aligned")]
+    for kw, msg in cases:
+        assert _call(hip_lib, **kw) == _lib.LWS_ERR_INVALID, kw
+        assert hip_lib.lws_last_error() == msg, kw
+
+
 def test_ops_validates_before_the_library():
     from lwsnet_amd import ops
     z = np.zeros((1, 8, 8, 3), np.uint8)

@@ -146,6 +146,38 @@ def test_sparsification_rejects_bad_arguments(hip_lib):
         assert call(**kw) == _lib.LWS_ERR_INVALID, kw
         err = hip_lib.lws_last_error()
         assert msg in err and b"sparsification" in err, (kw, err)
+    # the checks shared with lws_stage_metrics and every pair of the written histogram with a buffer that is read: the whole text
+    def one(s, p):
+        a = _arr()
+        a[s] = p
+        return a
+
+    texts = [
+        (dict(B=0), b"sparsification: bad shape B=0 Hg=8 W=16"), (dict(B=65536), b"sparsification: bad shape B=65536 Hg=8 W=16"),
+        (dict(Hg=0, Hp=0), b"sparsification: bad shape B=1 Hg=0 W=16"), (dict(W=-1), b"sparsification: bad shape B=1 Hg=8 W=-1"),
+        (dict(off=-1, Hp=7), b"sparsification: row_offset -1 < 0"),
+        (dict(Hp=9), b"sparsification: Hp=9 must be Hg + row_offset = 8 + 0"),
+        (dict(off=2), b"sparsification: Hp=8 must be Hg + row_offset = 8 + 2"),
+        (dict(mode=2), b"sparsification: mode 2 (0 = KITTI 3-px, 1 = EPE)"),
+        (dict(maxdisp=0.0), b"sparsification: maxdisp must be > 0, got 0"),
+        (dict(maxdisp=float("nan")), b"sparsification: maxdisp must be > 0, got nan"),
+        (dict(Hg=1048577, Hp=1048577, W=1048576), b"sparsification: 1048577x1048576 is too large"),
+        (dict(nmaps=5), b"sparsification: nmaps 5 outside 1..4"), (dict(kind=2), b"sparsification: kind 2 (0 = sigma, 1 = conf)"),
+        (dict(gt=hist + 8), b"sparsification: hist and gt overlap"),
+        (dict(pred=one(0, hist + 8)), b"sparsification: hist and pred[0] overlap"),
+        (dict(pred=one(1, hist + 8)), b"sparsification: hist and pred[1] overlap"),
+        (dict(pred=one(2, hist + 8)), b"sparsification: hist and pred[2] overlap"),
+        (dict(pred=one(3, hist + 8)), b"sparsification: hist and pred[3] overlap"),
+        (dict(unc=one(0, hist + 8)), b"sparsification: hist and unc[0] overlap"),
+        (dict(unc=one(1, hist + 8)), b"sparsification: hist and unc[1] overlap"),
+        (dict(unc=one(2, hist + 8)), b"sparsification: hist and unc[2] overlap"),
+        (dict(unc=one(3, hist + 8)), b"sparsification: hist and unc[3] overlap"),
+    ]
+    for kw, msg in texts:
+        assert call(**kw) == _lib.LWS_ERR_INVALID, kw
+        assert hip_lib.lws_last_error() == msg, kw
+    # maps beyond nmaps are not looked at
+    assert call(nmaps=2, pred=one(1, hist + 8)) == _lib.LWS_ERR_INVALID and hip_lib.lws_last_error() == b"sparsification: hist and pred[1] overlap"
     # pred, unc themselves NULL: through a second handle of the library, whose prototype takes the arrays as plain pointers
     _, args = _lib.PROTOTYPES["lws_sparsification"]
     fn = ctypes.CDLL(_lib.LIB_PATH).lws_sparsification

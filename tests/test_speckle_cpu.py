@@ -163,6 +163,53 @@ def test_argument_errors_through_the_c_abi(hip_lib):
     assert _call(lib, out=(1 << 20) + 64) == _lib.LWS_ERR_INVALID and b"disp and out overlap" in lib.lws_last_error()
 
 
+# (moved buffer, the buffer it is moved 16 bytes into, the whole error): every pair of the seven buffers, each alone
+_OVERLAPS = [
+    ("mask", "disp", b"speckle_filter: disp and mask overlap"), ("out", "disp", b"speckle_filter: disp and out overlap"),
+    ("mask_out", "disp", b"speckle_filter: disp and mask_out overlap"), ("labels", "disp", b"speckle_filter: disp and labels overlap"),
+    ("counts", "disp", b"speckle_filter: disp and counts overlap"), ("disp", "workspace", b"speckle_filter: disp and workspace overlap"),
+    ("out", "mask", b"speckle_filter: mask and out overlap"), ("mask_out", "mask", b"speckle_filter: mask and mask_out overlap"),
+    ("labels", "mask", b"speckle_filter: mask and labels overlap"), ("counts", "mask", b"speckle_filter: mask and counts overlap"),
+    ("mask", "workspace", b"speckle_filter: mask and workspace overlap"), ("mask_out", "out", b"speckle_filter: out and mask_out overlap"),
+    ("labels", "out", b"speckle_filter: out and labels overlap"), ("counts", "out", b"speckle_filter: out and counts overlap"),
+    ("out", "workspace", b"speckle_filter: out and workspace overlap"), ("labels", "mask_out", b"speckle_filter: mask_out and labels overlap"),
+    ("counts", "mask_out", b"speckle_filter: mask_out and counts overlap"),
+    ("mask_out", "workspace", b"speckle_filter: mask_out and workspace overlap"),
+    ("counts", "labels", b"speckle_filter: labels and counts overlap"), ("labels", "workspace", b"speckle_filter: labels and workspace overlap"),
+    ("counts", "workspace", b"speckle_filter: counts and workspace overlap"),
+]
+
+
+def test_every_overlapping_pair_is_named(hip_lib):
+    base = dict(disp=1 << 20, mask=1 << 23, workspace=1 << 24, out=1 << 21, mask_out=1 << 22, labels=1 << 25, counts=1 << 26)
+    assert len({frozenset(c[:2]) for c in _OVERLAPS}) == 7 * 6 // 2
+    for moved, onto, msg in _OVERLAPS:
+        assert _call(hip_lib, **{**base, moved: base[onto] + 16}) == _lib.LWS_ERR_INVALID, (moved, onto)
+        assert hip_lib.lws_last_error() == msg
+
+
+def test_shared_checks_keep_their_whole_text(hip_lib):
+    cases = [(dict(B=0), b"speckle_filter: bad shape B=0 H=8 W=8"), (dict(B=65536), b"speckle_filter: bad shape B=65536 H=8 W=8"),
+             (dict(H=0), b"speckle_filter: bad shape B=1 H=0 W=8"), (dict(W=-1), b"speckle_filter: bad shape B=1 H=8 W=-1"),
+             (dict(H=65536, W=32768), b"speckle_filter: H*W = 65536x32768 must be < 2^31"),
+             (dict(max_diff=-0.5), b"speckle_filter: max_diff must be finite and >= 0, got -0.5"),
+             (dict(max_diff=float("inf")), b"speckle_filter: max_diff must be finite and >= 0, got inf"),
+             (dict(max_diff=float("nan")), b"speckle_filter: max_diff must be finite and >= 0, got nan"),
+             (dict(fill=2), b"speckle_filter: fill 2 (0 = zero, 1 = background fill)"),
+             (dict(fill=-1), b"speckle_filter: fill -1 (0 = zero, 1 = background fill)"),
+             (dict(fill=1, W=8193, H=1), b"speckle_filter: fill needs W <= 8192 (the row is staged in LDS), got 8193"),
+             (dict(disp=(1 << 20) + 2), b"speckle_filter: disp / out / labels must be 4-byte, counts 8-byte, workspace 16-byte aligned"),
+             (dict(counts=(1 << 26) + 4), b"speckle_filter: disp / out / labels must be 4-byte, counts 8-byte, workspace 16-byte aligned"),
+             (dict(workspace=(1 << 24) + 8), b"speckle_filter: disp / out / labels must be 4-byte, counts 8-byte, workspace 16-byte aligned")]
+    for kw, msg in cases:
+        assert _call(hip_lib, **kw) == _lib.LWS_ERR_INVALID, kw
+        assert hip_lib.lws_last_error() == msg, kw
+    for shape, msg in (((0, 8, 8), b"speckle_workspace: bad shape B=0 H=8 W=8"), ((1, 8, 0), b"speckle_workspace: bad shape B=1 H=8 W=0"),
+                       ((1, 65536, 32768), b"speckle_workspace: H*W = 65536x32768 must be < 2^31")):
+        assert hip_lib.lws_speckle_workspace(*shape) == _lib.LWS_ERR_INVALID
+        assert hip_lib.lws_last_error() == msg
+
+
 def test_workspace_size(hip_lib):
     lib = hip_lib
     sizes = [lib.lws_speckle_workspace(B, 368, 1232) for B in (1, 2, 3, 8)]

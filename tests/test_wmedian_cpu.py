@@ -168,6 +168,35 @@ def test_argument_errors_through_the_c_abi(hip_lib):
     assert _call(lib, out=(1 << 20) + 64) == _lib.LWS_ERR_INVALID and b"disp and out overlap" in lib.lws_last_error()
 
 
+# (moved buffer, the written buffer it is moved 8 bytes into, the whole error): every written / any pair, each alone
+_OVERLAPS = [
+    ("counts", "out", b"wmedian_filter: counts and out overlap"), ("disp", "out", b"wmedian_filter: disp and out overlap"),
+    ("mask", "out", b"wmedian_filter: mask and out overlap"), ("rgb", "out", b"wmedian_filter: rgb and out overlap"),
+    ("wlut", "out", b"wmedian_filter: wlut and out overlap"), ("disp", "counts", b"wmedian_filter: disp and counts overlap"),
+    ("mask", "counts", b"wmedian_filter: mask and counts overlap"), ("rgb", "counts", b"wmedian_filter: rgb and counts overlap"),
+    ("wlut", "counts", b"wmedian_filter: wlut and counts overlap"),
+]
+
+
+def test_every_overlapping_pair_is_named(hip_lib):
+    base = dict(disp=1 << 20, out=1 << 21, mask=1 << 22, wlut=1 << 23, counts=1 << 24, rgb=1 << 25)
+    for moved, onto, msg in _OVERLAPS:
+        assert _call(hip_lib, **{**base, moved: base[onto] + 8}) == _lib.LWS_ERR_INVALID, (moved, onto)
+        assert hip_lib.lws_last_error() == msg
+
+
+def test_shared_checks_keep_their_whole_text(hip_lib):
+    cases = [(dict(B=0), b"wmedian_filter: bad shape B=0 H=8 W=8"), (dict(B=65536), b"wmedian_filter: bad shape B=65536 H=8 W=8"),
+             (dict(H=0), b"wmedian_filter: bad shape B=1 H=0 W=8"), (dict(W=-1), b"wmedian_filter: bad shape B=1 H=8 W=-1"),
+             (dict(H=65536, W=32768), b"wmedian_filter: H*W = 65536x32768 must be < 2^31"),
+             (dict(disp=(1 << 20) + 2), b"wmedian_filter: disp / out must be 4-byte, counts 8-byte, wlut 2-byte aligned"),
+             (dict(counts=(1 << 24) + 4), b"wmedian_filter: disp / out must be 4-byte, counts 8-byte, wlut 2-byte aligned"),
+             (dict(rgb=1 << 22, wlut=(1 << 23) + 1), b"wmedian_filter: disp / out must be 4-byte, counts 8-byte, wlut 2-byte aligned")]
+    for kw, msg in cases:
+        assert _call(hip_lib, **kw) == _lib.LWS_ERR_INVALID, kw
+        assert hip_lib.lws_last_error() == msg, kw
+
+
 def test_ops_validates_before_the_library():
     from lwsnet_amd import ops
     with pytest.raises(RuntimeError, match="HIP device"):
