@@ -396,6 +396,46 @@ int lws_rectify_pair(const uint8_t *const raw[2], const float *params, int B, in
                      const float *mean, const float *std, uint8_t *const rect[2], float *const input[2], uint8_t *const valid[2],
                      float *const map[2], void *stream);
 
+/* ---- photometric reprojection error: a score for disparity maps that needs no ground truth (additive after v8) ---- */
+/* The right image is warped into the left view with the map and compared with the left image by L1 and a 3 x 3 SSIM term (Godard
+ * et al. 2017): a correct map reproduces the left image, a wrong one does not.  disp[s] [B,1,H,W] float32 for s < nmaps (1..4);
+ * left, right uint8 [B,H,W,3] RGB (the layout of lws_preprocess_rgb8 and of lws_wmedian_filter's guide); mask (NULL, or per map NULL:
+ * every pixel) uint8 [B,1,H,W], the lws_lr_check code map; rvalid (NULL: every tap) uint8 [B,1,H,W], lws_rectify_pair's valid map
+ * of the right camera; alpha finite, in [0, 1]; H*W < 2^31, B * nmaps <= 65535; element alignment only (an image row has a pitch
+ * of 3 W bytes).  Per pixel (y, x) of image b and map s, d = disp[s][b,0,y,x], every step one IEEE float32 operation in the order
+ * written (no contraction, correctly rounded division):
+ *   t  = (float)x - d
+ *   warpable = !isnan(d) && 0 <= t && t <= W-1                       (a disparity of +-inf fails the range test)
+ *   i0 = (int)floorf(t);  i1 = min(i0+1, W-1);  with rvalid, warpable also needs rvalid[y,i0] == 1 && rvalid[y,i1] == 1
+ *   a  = t - (float)i0
+ *   per channel c: r0 = (float)right[y,i0,c];  r1 = (float)right[y,i1,c];  w_c = r0 + a * (r1 - r0)   (multiply, then add)
+ *   warped[y,x,c] = warpable ? (uint8)rintf(w_c) : 0                 (w_c stays in [0, 255]: rounding is monotonic)
+ *   scored   = every pixel of the 3 x 3 window of (y, x) lies inside the image and is warpable, (y, x) itself included, and
+ *              (mask == NULL || mask[y,x] == 1) at the pixel itself (the neighbours' codes do not matter); H < 3 or W < 3 scores nothing
+ *   l1 = (((|L_r - w_r| + |L_g - w_g|) + |L_b - w_b|) / 3.0f) / 255.0f,  L_c = (float)left[y,x,c]
+ *   per channel, with X = L_c, Y = w_c, five quantities v in {X, Y, X*X, Y*Y, X*Y} (each product rounded first), summed over the
+ *   window HORIZONTALLY FIRST:  h(y',x) = (v(y',x-1) + v(y',x)) + v(y',x+1);  S = (h(y-1,x) + h(y,x)) + h(y+1,x)
+ *   mx = Sx/9.0f;  my = Sy/9.0f;  vx = Sxx/9.0f - mx*mx;  vy = Syy/9.0f - my*my;  cxy = Sxy/9.0f - mx*my
+ *   n  = ((2.0f*mx)*my + C1) * (2.0f*cxy + C2);   m = ((mx*mx + my*my) + C1) * ((vx + vy) + C2)
+ *   C1 = 6.5025f, C2 = 58.5225f  ((0.01 * 255)^2, (0.03 * 255)^2;  m > 0: the rounding of the variances is far below C2)
+ *   ds_c = fminf(fmaxf((1.0f - n/m) * 0.5f, 0.0f), 1.0f);   ds = ((ds_r + ds_g) + ds_b) / 3.0f
+ *   pe = alpha*ds + (1.0f - alpha)*l1                                 (in [0, 1])
+ * Outputs, each optional per map (the array pointer or its element NULL: skipped) except sums:
+ *   err[s]    float32 [B,1,H,W] = scored ? pe : 0.0f
+ *   scored[s] uint8   [B,1,H,W] = scored ? 1 : 0
+ *   warped[s] uint8   [B,H,W,3]
+ *   sums      int64   [nmaps][B][4] = {scored pixels, sum q(pe), sum q(l1), sum q(ds)} over the scored pixels,
+ *             q(v) = (int64)rintf(v * 1048576.0f): the scaling is exact, the only rounding is to the 2^-20 grid
+ * The call clears sums with one small kernel on `stream` and runs one more: a fixed launch list of two, no workspace, no
+ * device-to-host read (capturable into a hipGraph: two kernel nodes), no scratch memory.  All accumulation is integer (wave sums, then one 64-bit
+ * integer atomic per workgroup and counter; no float atomics), so an image gives the same bytes in any batch, at any position, on
+ * every run.  The call writes every element of every output it is given and nothing else.  Argument errors -- NULL disp, disp[s]
+ * below nmaps, left, right or sums; nmaps outside 1..4; alpha outside [0, 1] or NaN; sizes outside the limits; an output
+ * overlapping an input or another output -- return LWS_ERR_INVALID before any GPU call. */
+int lws_photometric(const float *const disp[4], int nmaps, const uint8_t *left, const uint8_t *right, const uint8_t *const mask[4],
+                    const uint8_t *rvalid, int B, int H, int W, float alpha, float *const err[4], uint8_t *const scored[4],
+                    uint8_t *const warped[4], int64_t *sums, void *stream);
+
 /* Launch-plan options of lws_forward / lws_disparity_stages.  They change which kernels / streams carry the work, never
  * the arithmetic: every setting returns the same bits (tests/test_gpu_parity.py::test_forward_schedule_options) -- except
  * the opt-in numerics mode "split_bf16".  (ABI v8 removed the options two rounds of sweeps had retired: left_at, split_heads,

@@ -59,6 +59,7 @@ PROTOTYPES = {
     "lws_speckle_filter": (_i, [_vp, _vp, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lws_wmedian_filter": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "lws_rectify_pair": (_i, [_vp * 2, _vp, _i, _i, _i, _i, _i, _i, _i, _i, c_float_p, c_float_p, _vp * 2, _vp * 2, _vp * 2, _vp * 2, _vp]),
+    "lws_photometric": (_i, [_vp * 4, _i, _vp, _vp, _vp * 4, _vp, _i, _i, _i, _f, _vp * 4, _vp * 4, _vp * 4, _vp, _vp]),
     "lws_set_option": (_i, [_vp, ctypes.c_char_p, _i]),
     "lws_get_option": (_i, [_vp, ctypes.c_char_p, ctypes.POINTER(_i)]),
     "lws_profile_enable": (_i, [_vp, _i]),

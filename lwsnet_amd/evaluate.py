@@ -47,6 +47,14 @@ after the least trusted fraction is removed), the oracle curve (removal by the t
 Ilg et al. 2018), for the run's metric.  Two more log lines give the per-stage AUSE of either ranking, and the result gains the key
 "sparsification".  Its curves, and "all", their value at fraction 0, are pooled over the PIXELS of the dataset: "all" is therefore
 not the reference's average over batches that the lines above print.
+
+`--photometric [--photo_alpha A]` (not in the reference; sequential mode only) scores the maps WITHOUT the ground truth, by the
+photometric reprojection error (lws_photometric, lwsnet_amd/csrc/lws_photometric.hip: the right image warped into the left view
+with the map against the left image, A * DSSIM + (1 - A) * L1, A = 0.85 by default).  The batch is read as bytes
+(StereoPairs.raw), as for the guided median; the maps scored are the ones the metric scores, the chain's final maps when the chain
+is on, and only the pixels the chain's codes keep are scored, under the rule of the geometry outputs (lwsnet_amd/postprocess.py: the
+codes count while nothing has been filled).  One more log line gives the per-stage mean error and density, pooled over the pixels
+of the dataset, and the result gains the key "photometric"; nothing else in it changes.
 """
 import argparse
 import contextlib
@@ -155,14 +163,16 @@ def _row_offset(H, Hg):
     return H - Hg
 
 
-def _sequential(model, dataset, mode, batches, maxdisp, options, sparsification=False):
+def _sequential(model, dataset, mode, batches, maxdisp, options, sparsification=False, photo_alpha=None):
     """StereoPairs[i] -> postprocess.run_chain on the batch -> lws_stage_metrics, one batch after the other.  A generator: "start"
     after a warm-up forward, then (counts, abs_sum, stats) per batch.  stats has a [4,b] array per stage of `options` that is on:
     lr_density (the check's consistent pixels / (H*W)), occ_density (the occlusion check's visible pixels / (H*W)), speckle_density (the speckle filter's kept pixels / (H*W)) and
     wmedian_changed (the median's changed + filled pixels / (H*W)).  When the median needs a guide the batch is read as bytes
     (StereoPairs.raw), uploaded once and normalised on the device, and its left images are the guide.  With `sparsification` (no
     stage of the chain is on then) the batch runs LWSNet.forward_conf instead and stats has "sparsification": per kind ("conf",
-    "sigma") the host copy of ops.sparsification's histogram [4,b,2,1026,3]."""
+    "sigma") the host copy of ops.sparsification's histogram [4,b,2,1026,3].  With photo_alpha = A the batch is read as bytes too
+    and stats has "photometric": the host copy of ops.photometric's sums [4,b,4] for the maps the metric scores, masked by the
+    chain's `keep` codes (None: every pixel), and H * W."""
     import torch
     from . import ops
     dev = model.device
@@ -179,13 +189,13 @@ def _sequential(model, dataset, mode, batches, maxdisp, options, sparsification=
     torch.cuda.synchronize(dev)
     yield "start"
     for rng in batches:
-        guide = None
-        if options.needs_guide:
+        guide = keep = None
+        if options.needs_guide or photo_alpha is not None:
             items = [dataset.raw(i) for i in rng]
             with torch.cuda.device(dev):
                 u8 = torch.from_numpy(np.stack([it[0] for it in items] + [it[1] for it in items])).to(dev)
                 both = ops.preprocess_rgb8(u8)                  # bit for bit StereoPairs[i]
-            left, right, guide = both[:len(items)], both[len(items):], u8[:len(items)]
+            left, right, guide = both[:len(items)], both[len(items):], u8[:len(items)] if options.needs_guide else None
         else:
             items = [dataset[i] for i in rng]
             left = np.stack([it[0] for it in items])
@@ -197,7 +207,7 @@ def _sequential(model, dataset, mode, batches, maxdisp, options, sparsification=
             disp = conf_res.preds
         else:
             res = post.run_chain(model, left, right, options, guide)
-            disp = res.disp
+            disp, keep = res.disp, res.keep
             if res.lr_density is not None:
                 stats["lr_density"] = res.lr_density
             if res.occ_density is not None:
@@ -213,6 +223,9 @@ def _sequential(model, dataset, mode, batches, maxdisp, options, sparsification=
                 unc = {"conf": conf_res.conf, "sigma": conf_res.sigma}
                 hists = {kind: ops.sparsification(disp, [*u, u[2]], gt, row_offset, maxdisp, mode, kind) for kind, u in unc.items()}
                 stats["sparsification"] = {kind: h.cpu().numpy() for kind, h in hists.items()}
+            if photo_alpha is not None:
+                photo = ops.photometric(list(disp), u8[:len(items)], u8[len(items):], mask=keep, alpha=photo_alpha, want_err=False)
+                stats["photometric"] = photo.sums.cpu().numpy(), H * W
             yield counts.cpu().numpy(), sums.cpu().numpy(), stats
 
 
@@ -380,9 +393,37 @@ class Sparsification:
                 for kind in self.KINDS]
 
 
+class Photometric:
+    """The host side of `--photometric`, fed one batch at a time in order: ops.photometric's integer sums of every image."""
+
+    def __init__(self, alpha):
+        self.alpha, self.pixels, self.sums = float(alpha), None, []
+
+    def update(self, sums, pixels):
+        """sums: the int64 [4,b,4] of one batch; pixels: H * W of its images."""
+        self.sums.append(np.asarray(sums, dtype=np.int64))
+        self.pixels = int(pixels)
+
+    def result(self):
+        """The "photometric" entry of evaluate()'s result: alpha, the per-stage means pooled over the pixels of the dataset
+        (metrics.photometric_means: pe, l1, dssim, scored, density; None for a stage without a scored pixel) and per_image, the same
+        four means per image."""
+        from .metrics import photometric_means
+        sums = np.concatenate(self.sums, axis=1)
+        res = {"alpha": self.alpha, **photometric_means(sums, self.pixels)}
+        each = [photometric_means(sums[:, i:i + 1], self.pixels) for i in range(sums.shape[1])]
+        res["per_image"] = {key: [m[key] for m in each] for key in ("pe", "l1", "dssim", "density")}
+        return res
+
+    def line(self, res):
+        fmt = lambda v: "none" if v is None else "{:.4f}".format(v)     # noqa: E731
+        return "Photometric (alpha = {:g}): mean error ".format(self.alpha) + ", ".join(
+            "Stage {}={} (density {:.4f})".format(x, fmt(e), d) for x, (e, d) in enumerate(zip(res["pe"], res["density"])))
+
+
 def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, workers=0, gpu_workers=2, log=None, lr_check=None,
              lr_fill=False, speckle=None, speckle_diff=1.0, speckle_fill=False, wmedian=None, wmedian_sigma=10.0, wmedian_fill=0,
-             occ_check=None, occ_fill=False, sparsification=False):
+             occ_check=None, occ_fill=False, sparsification=False, photometric=False, photo_alpha=0.85):
     """Runs the reference's test loop for `metric` ("kitti": finetune.py's 3-pixel error, "epe": train.py's EPE) over
     `dataset` (a StereoPairs with training=False).  maxdisp is the mask bound (the KITTI loop uses 192, see KITTI_MAXDISP).
     Returns a dict: per-stage averages at full precision, per-batch values, per-image counts and sums, pairs, wall time, pairs/s.
@@ -392,7 +433,9 @@ def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, worker
     and lr_density (consistent pixels / (H*W)); occ_tau and occ_density (visible pixels / (H*W)); speckle_size, speckle_diff and speckle_density (kept pixels / (H*W));
     wmedian_radius, wmedian_sigma, wmedian_fill and wmedian_changed ((changed + filled pixels) / (H*W)).
     sparsification = True (sequential mode only, with no stage of the chain: a ValueError otherwise) adds the key "sparsification",
-    the curves and AUSE of the confidence and sigma maps (the module docstring; Sparsification.result)."""
+    the curves and AUSE of the confidence and sigma maps (the module docstring; Sparsification.result).
+    photometric = True (sequential mode only; photo_alpha in [0, 1]: a ValueError otherwise) adds the key "photometric", the
+    photometric reprojection error of the maps the metric scores (the module docstring; Photometric.result)."""
     if metric not in ("kitti", "epe"):
         raise ValueError(f"metric must be 'kitti' or 'epe', got {metric!r}")
     options = post.Options.make(lr_check=lr_check, lr_fill=lr_fill, speckle=speckle, speckle_diff=speckle_diff, speckle_fill=speckle_fill,
@@ -405,6 +448,10 @@ def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, worker
         raise ValueError("the sparsification curves run in the sequential mode only (workers = 0)")
     if sparsification and options.stages_on:
         raise ValueError(f"the sparsification curves score the forward's own maps: they do not combine with the {options.stages_on[0]}")
+    if photometric and workers > 0:
+        raise ValueError("the photometric error runs in the sequential mode only (workers = 0)")
+    if photometric and not (isinstance(photo_alpha, (int, float)) and 0.0 <= photo_alpha <= 1.0):
+        raise ValueError(f"photo_alpha must be in [0, 1], got {photo_alpha!r}")
     if batch_size < 1:
         raise ValueError("batch_size must be >= 1")
     n = len(dataset)
@@ -419,8 +466,9 @@ def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, worker
     if workers > 0:
         it = _pipelined(model, dataset, metric, batches, maxdisp, workers, gpu_workers)
     else:
-        it = _sequential(model, dataset, metric, batches, maxdisp, options, sparsification)
+        it = _sequential(model, dataset, metric, batches, maxdisp, options, sparsification, float(photo_alpha) if photometric else None)
     spars = Sparsification(metric) if sparsification else None
+    photo = Photometric(photo_alpha) if photometric else None
     if next(it) != "start":
         raise RuntimeError("the evaluation did not start")
     t0 = time.perf_counter()
@@ -428,6 +476,8 @@ def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, worker
         for key, value in (batch_stats[0].items() if batch_stats else ()):
             if key == "sparsification":
                 spars.update(value)
+            elif key == "photometric":
+                photo.update(*value)
             else:
                 stats.setdefault(key, []).append(value)
         line = meters.update(k, counts, sums, files[k])
@@ -452,6 +502,9 @@ def evaluate(model, dataset, metric, batch_size=8, maxdisp=KITTI_MAXDISP, worker
         res["sparsification"] = spars.result()
         for line in spars.lines(res["sparsification"]):
             log.info(line)
+    if photo is not None:
+        res["photometric"] = photo.result()
+        log.info(photo.line(res["photometric"]))
     return res
 
 
@@ -476,6 +529,7 @@ def build_parser():
     post.add_speckle_arguments(p)
     post.add_wmedian_arguments(p)
     add_sparsification_argument(p)
+    post.add_photometric_arguments(p)
     return p
 
 
@@ -519,6 +573,7 @@ def main(argv=None):
     post.check_speckle_arguments(parser, args)
     post.check_wmedian_arguments(parser, args)
     check_sparsification_argument(parser, args)
+    post.check_photometric_arguments(parser, args)
     log = start_logging("lwsnet_amd.evaluate", args)
     dataset, metric, maxdisp = load_dataset(args)
     model = load_model(args, log, missing_status=1)
@@ -526,7 +581,7 @@ def main(argv=None):
                    gpu_workers=args.gpu_workers, log=log, lr_check=args.lr_check, lr_fill=args.lr_fill, speckle=args.speckle,
                    speckle_diff=args.speckle_diff, speckle_fill=args.speckle_fill, wmedian=args.wmedian,
                    wmedian_sigma=args.wmedian_sigma, wmedian_fill=args.wmedian_fill, occ_check=args.occ_check, occ_fill=args.occ_fill,
-                   sparsification=args.sparsification)
+                   sparsification=args.sparsification, photometric=args.photometric, photo_alpha=args.photo_alpha)
     res["dataset"] = args.dataset
     log.info("%d pairs in %.3f s: %.2f pairs/s", res["pairs"], res["wall_s"], res["pairs_per_s"])
     if args.json:

@@ -62,6 +62,14 @@ pair, beside the colour file (with `--left_img` beside `3.png`): `<stem>_conf.pn
 default.  `--conf_min C` and `--sigma_max_keep S` keep a pixel in the `_disp16`, `_depth16` and `.ply` files only where its stage's
 conf >= C and sigma <= S (ops.confidence_codes; stage 4, the refined map, goes by stage 3's), on top of what the speckle filter's
 codes drop.  They are not part of the post-processing chain, and not available with `--lr_check`, `--occ_check` or `--workers`.
+
+`--photometric [--photo_alpha A] [--save_photo]`: every frame's four final maps are scored without ground truth by the photometric
+reprojection error (lws_photometric: the right crop warped into the left view with the map against the left crop, A * DSSIM +
+(1 - A) * L1, A = 0.85 by default), and one log line per frame gives the four stages' mean error and the density of scored pixels.
+Only the pixels the chain's codes keep are scored, under the rule of the geometry files (the codes count while nothing has been
+filled); with `--rectify` the left valid map merges into those codes as it does for the geometry files, and a right tap outside the
+right valid map cannot be used.  `--save_photo` writes two files beside each colour file: `<stem>_pe.png`, the error map as 8-bit
+grey rint(pe * 255) (0 where the pixel is not scored), and `<stem>_warp.png`, the warped right image.
 """
 import argparse
 import contextlib
@@ -104,6 +112,7 @@ def build_parser():
     add_geometry_arguments(p)
     add_rectify_arguments(p)
     add_conf_arguments(p)
+    post.add_photometric_arguments(p, save=True)
     return p
 
 
@@ -449,6 +458,7 @@ def inference(model, left_imgs, right_imgs, args, log):
     conf_on = conf_requested(args)
     conf_mask = conf_on and (args.conf_min is not None or args.sigma_max_keep is not None)
     chain_model = _ConfModel(model) if conf_on else model
+    photo_on, save_photo = getattr(args, "photometric", False), getattr(args, "save_photo", False)
 
     def save(path, color, stage):                                       # the colour file, then the mask and geometry files beside it
         io.save_png(path, color)
@@ -471,6 +481,8 @@ def inference(model, left_imgs, right_imgs, args, log):
             if rc:                                                      # a pixel sampled outside the raw left image: out of view
                 keep = valid_left if keep is None else torch.where(valid_left == 0, torch.full_like(keep, 2), keep)
             written.extend(_save_geometry(path, res.disp[stage], keep, cam, left, args, log))
+        if photo_on and save_photo:
+            written.extend(_save_photo(path, photo.err[stage], photo.warped[stage], log))
 
     for li, ri in zip(left_imgs, right_imgs):
         full = io.load_rgb(li)
@@ -478,7 +490,7 @@ def inference(model, left_imgs, right_imgs, args, log):
             front = _rectify_frame(args, li, full, io.load_rgb(ri), model.device, geo, written, log)
             if front is None:
                 continue
-            l_in, r_in, left, valid_left, cam = front
+            l_in, r_in, left, valid_left, cam, right, valid_right = front
         else:
             left = io.crop_bottom_right(full)
             right = io.crop_bottom_right(io.load_rgb(ri))
@@ -499,6 +511,9 @@ def inference(model, left_imgs, right_imgs, args, log):
             for stage, (changed, refilled) in enumerate(res.wmedian_counts[:, 0].cpu().tolist()):
                 log.info("Weighted median (radius {}, sigma {:g}, fill {}): stage {} changed = {}, filled = {}".format(
                     opts.wmedian, opts.wmedian_sigma, opts.wmedian_fill, stage + 1, changed, refilled))
+        if photo_on:
+            photo = _photometric(res, left, right, valid_left if rc else None, valid_right if rc else None, getattr(args, "photo_alpha", 0.85),
+                                 save_photo, model.device, log)
         color = None
         for stage in range(4):
             disp = res.disp[stage].squeeze(axis=[0, 1]).numpy()         # :114 (the uint8 cast is inside disparity_to_color)
@@ -521,7 +536,8 @@ def _rgb_on_device(rgb, device):
 def _rectify_frame(args, left_path, raw_left, raw_right, device, geo, written, log):
     """--rectify: one raw pair -> (left input, right input, rectified left crop uint8 [1,H,W,3], valid map of the left view, camera
     of the crop or None), all on the device; None when the frame is skipped (rectified frame smaller than the crop) or in error
-    (image size other than the calibration's).  --save_rect: the two crops are written and their paths appended to `written`."""
+    (image size other than the calibration's).  --save_rect: the two crops are written and their paths appended to `written`.
+    Behind the five, for --photometric: the rectified right crop and the valid map of the right view."""
     import torch
     from . import ops
     from .geometry import RectifyCalib
@@ -547,7 +563,7 @@ def _rectify_frame(args, left_path, raw_left, raw_right, device, geo, written, l
             io.save_png(f"{stem}_rect_{side}.png", img[0].cpu().numpy())
             written.append(f"{stem}_rect_{side}.png")
             log.info("Save rectified %s image = %s_rect_%s.png", side, stem, side)
-    return out["input"][0], out["input"][1], out["rect"][0], out["valid"][0], cam
+    return out["input"][0], out["input"][1], out["rect"][0], out["valid"][0], cam, out["rect"][1], out["valid"][1]
 
 
 def _frame_camera(args, left_path, h, w):
@@ -587,6 +603,43 @@ def _save_geometry(path, disp, mask, cam, left_rgb, args, log):
         written.append(stem + ".ply")
         log.info("Save point cloud ({} points) = {}".format(n, stem + ".ply"))
     return written
+
+
+def photo_to_u8(err):
+    """[H,W] photometric error in [0, 1] -> the bytes of <stem>_pe.png: rint(pe * 255)."""
+    return np.rint(np.asarray(err, np.float64) * 255.0).astype(np.uint8)
+
+
+def _photometric(res, left, right, valid_left, valid_right, alpha, want_maps, device, log):
+    """--photometric: ops.photometric on the chain's four final maps of one frame, masked by the codes the geometry files keep (with
+    --rectify: merged with the left valid map as for them; the right valid map is rvalid); logs the frame's line.  left, right: the
+    uint8 crops (numpy [H,W,3] or device [1,H,W,3])."""
+    import torch
+
+    from . import ops
+    from .metrics import photometric_means
+    keep = list(res.keep) if res.keep is not None else None
+    if valid_left is not None:
+        keep = [valid_left if k is None else torch.where(valid_left == 0, torch.full_like(k, 2), k) for k in (keep or [None] * 4)]
+    with torch.cuda.device(device):
+        photo = ops.photometric(list(res.disp), _rgb_on_device(left, device), _rgb_on_device(right, device), mask=keep, rvalid=valid_right,
+                                alpha=alpha, want_err=want_maps, want_warped=want_maps)
+    H, W = res.disp[0].shape[2:]
+    m = photometric_means(photo.sums, H * W)
+    log.info("Photometric (alpha = {:g}): ".format(alpha) + ", ".join(
+        "Stage {} = {} (density {:.4f})".format(s + 1, "none" if e is None else "{:.4f}".format(e), d)
+        for s, (e, d) in enumerate(zip(m["pe"], m["density"]))))
+    return photo
+
+
+def _save_photo(path, err, warped, log):
+    """The photometric error and the warped right image of the map written to `path`, as <stem>_pe.png and <stem>_warp.png."""
+    stem = os.path.splitext(path)[0]
+    with open(stem + "_pe.png", "wb") as f:
+        f.write(io.encode_png_gray(photo_to_u8(err[0, 0].cpu().numpy())))
+    io.save_png(stem + "_warp.png", warped[0].cpu().numpy())
+    log.info("Save photometric maps = {}_pe.png, {}_warp.png".format(stem, stem))
+    return [stem + "_pe.png", stem + "_warp.png"]
 
 
 def _save_conf(path, result, sigma_max, log):
@@ -639,6 +692,7 @@ def main(argv=None):
     check_geometry_arguments(parser, args)
     check_rectify_arguments(parser, args)
     check_conf_arguments(parser, args)
+    post.check_photometric_arguments(parser, args, save=True)
     log = start_logging("lwsnet_amd.inference", args)
     model = load_model(args, log)
     if getattr(args, "split_bf16", False):

@@ -76,3 +76,27 @@ def sparsification_curves(hist, metric, fractions=None):
     ause = float(np.mean(curves[0] - curves[1]))
     return {"fractions": fractions, "unc": curves[0], "oracle": curves[1], "all": total, "ause": ause,
             "ause_rel": ause / total if total != 0 else None}
+
+
+# ---- the photometric reprojection error from the integer sums of lws_photometric ----
+PHOTO_SCALE = 1 << 20
+
+
+def photometric_means(sums, pixels=None):
+    """The per-map means of ops.photometric's sums, an integer [nmaps,B,4] array (or tensor) {scored pixels, sum q(pe), sum q(l1),
+    sum q(dssim)} with q(v) = rint(v * 2**20), pooled over the PIXELS of the B images: sum q / (2**20 * sum count).  Returns a dict
+    of lists with one entry per map: "pe", "l1", "dssim" (None for a map without a scored pixel), "scored" (the pixel count) and
+    "density" = scored / (B * pixels), pixels = H * W of one image (None when pixels is not given)."""
+    if hasattr(sums, "detach"):
+        sums = sums.detach().cpu().numpy()
+    sums = np.asarray(sums)
+    if sums.ndim != 3 or sums.shape[2] != 4 or sums.dtype.kind not in "iu":
+        raise ValueError(f"sums must be an integer [nmaps,B,4] array; got {sums.dtype} {sums.shape}")
+    if pixels is not None and (int(pixels) != pixels or pixels < 1):
+        raise ValueError(f"pixels must be a positive integer, got {pixels!r}")
+    tot = [[int(v) for v in row] for row in sums.astype(np.int64).sum(axis=1)]          # python integers: exact
+    res = {"scored": [t[0] for t in tot]}
+    for k, name in ((1, "pe"), (2, "l1"), (3, "dssim")):
+        res[name] = [t[k] / (PHOTO_SCALE * t[0]) if t[0] > 0 else None for t in tot]
+    res["density"] = [t[0] / (sums.shape[1] * int(pixels)) if pixels is not None else None for t in tot]
+    return res

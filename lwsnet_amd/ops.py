@@ -660,3 +660,48 @@ def rectify_pair(raw_left, raw_right, params, out_hw, origin=(0, 0), border=0, w
         _lib.check(_lib.load().lws_rectify_pair(raws, _ptr(params), B, Hs, Ws, H, W, x0, y0, int(border), mean, std, *arrays, _stream()),
                    "lws_rectify_pair")
     return res
+
+
+PhotometricResult = namedtuple("PhotometricResult", ["err", "scored", "warped", "sums"])
+PhotometricResult.__doc__ = """What photometric returns: per map the error maps float32 [B,1,H,W] (0 where not scored), the uint8 [B,1,H,W]
+scored maps and the uint8 [B,H,W,3] right images warped into the left view -- each a list like `disp`, or one tensor when `disp` was
+one tensor, or None when not asked for -- and sums, an int64 [nmaps,B,4] device tensor {scored pixels, sum q(pe), sum q(l1),
+sum q(dssim)}, q(v) = rint(v * 2^20) (lwsnet_amd.metrics.photometric_means turns it into means)."""
+
+
+def photometric(disp, left_u8, right_u8, mask=None, rvalid=None, alpha=0.85, want_err=True, want_scored=False, want_warped=False):
+    """Photometric reprojection error of disparity maps, a score that needs no ground truth (include/lwsnet_hip.h, lws_photometric):
+    the right image warped into the left view with the map against the left image, alpha * DSSIM (3 x 3) + (1 - alpha) * L1.  disp: one
+    [B,1,H,W] float32 map or a list of 1-4; left_u8, right_u8: the uint8 [B,H,W,3] images; mask: None, one uint8 [B,1,H,W]
+    lws_lr_check code map for every map, or a list with one (or None) per map: only code-1 pixels are scored; rvalid: None or the
+    uint8 [B,1,H,W] valid map of the right camera (rectify_pair): a tap outside it cannot be used; alpha in [0, 1].  The outputs are
+    allocated per call on the current stream.  Returns a PhotometricResult."""
+    import math
+    single = isinstance(disp, torch.Tensor)
+    maps = [disp] if single else disp
+    if not isinstance(maps, (list, tuple)) or not 1 <= len(maps) <= 4:
+        raise ValueError("disp must be one map or a list of 1-4 maps")
+    (ds,), shape, dev = _stage_maps(disp=[d.as_subclass(torch.Tensor) if isinstance(d, torch.Tensor) else d for d in maps])
+    B, _, H, W = shape
+    left, right = (_guide(t, ds[0]) for t in (left_u8, right_u8))
+    if mask is None or isinstance(mask, torch.Tensor):
+        mask = [mask] * len(ds)
+    if not isinstance(mask, (list, tuple)) or len(mask) != len(ds):
+        raise ValueError("mask must be None, one code map or a list with one entry per map")
+    masks = [_code_map(k, ds[0]) for k in mask]
+    rvalid = _code_map(rvalid, ds[0])
+    if isinstance(alpha, bool) or not (math.isfinite(alpha) and 0.0 <= alpha <= 1.0):
+        raise ValueError(f"alpha must be in [0, 1], got {alpha!r}")
+    n = len(ds)
+    err = [torch.empty(shape, device=dev, dtype=torch.float32) for _ in range(n)] if want_err else None
+    scored = [torch.empty(shape, device=dev, dtype=torch.uint8) for _ in range(n)] if want_scored else None
+    warped = [torch.empty((B, H, W, 3), device=dev, dtype=torch.uint8) for _ in range(n)] if want_warped else None
+    sums = torch.empty((n, B, 4), device=dev, dtype=torch.int64)
+    arr = ctypes.c_void_p * 4
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().lws_photometric(_arr4(ds), n, _ptr(left), _ptr(right), arr(*[k.data_ptr() if k is not None else None for k in masks]),
+                                               _ptr(rvalid), B, H, W, float(alpha), _arr4(err or []), _arr4(scored or []), _arr4(warped or []),
+                                               _ptr(sums), _stream()), "lws_photometric")
+    if single:
+        err, scored, warped = (v[0] if v is not None else None for v in (err, scored, warped))
+    return PhotometricResult(err, scored, warped, sums)

@@ -277,3 +277,34 @@ def check_speckle_arguments(p, args):
 def check_wmedian_arguments(p, args):
     """Rejects what the weighted median filter does not support; sets the defaults of --wmedian_sigma and --wmedian_fill."""
     _check_stage(p, args, "wmedian")
+
+
+def add_photometric_arguments(p, save=False):
+    """--photometric / --photo_alpha A (and, for the inference CLI, --save_photo; not in the reference): ops.photometric.  A command
+    line without them parses to the namespace it parsed to before they existed (argparse.SUPPRESS); check_photometric_arguments
+    writes their defaults."""
+    import argparse
+    p.add_argument("--photometric", action="store_true", default=argparse.SUPPRESS,
+                   help="score the disparity maps without ground truth: the photometric reprojection error of the right image warped "
+                        "into the left view (sequential mode only; not in the reference)")
+    p.add_argument("--photo_alpha", type=float, default=argparse.SUPPRESS, metavar="A",
+                   help="with --photometric: the error is A * DSSIM + (1 - A) * L1, A in [0, 1] (default 0.85)")
+    if save:
+        p.add_argument("--save_photo", action="store_true", default=argparse.SUPPRESS,
+                       help="with --photometric: write <stem>_pe.png, the error map as rint(pe * 255), and <stem>_warp.png, the warped right image")
+
+
+def check_photometric_arguments(p, args, save=False):
+    """Rejects what the photometric error does not support, before any model or GPU work; sets the flags' defaults (False, 0.85
+    and, for the CLI that has --save_photo, False)."""
+    args.photometric = getattr(args, "photometric", False)
+    alpha = getattr(args, "photo_alpha", None)
+    if save:
+        args.save_photo = getattr(args, "save_photo", False)
+    if not args.photometric and (alpha is not None or (save and args.save_photo)):
+        p.error("--photo_alpha and --save_photo need --photometric" if save else "--photo_alpha needs --photometric")
+    args.photo_alpha = 0.85 if alpha is None else alpha
+    if not 0.0 <= args.photo_alpha <= 1.0:                              # (false for NaN)
+        p.error(f"--photo_alpha A must be in [0, 1], got {args.photo_alpha}")
+    if args.photometric:
+        sequential_only(p, args, "--photometric")
