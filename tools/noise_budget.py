@@ -3,6 +3,10 @@
 Runs the literal restatement (oracle/lws_oracle.py) in float64 with ONE component at a time in float32 (inputs cast
 down, result cast up) and reports each stage's max-abs distance to the all-float64 run.  The all-float32 line is the
 reference algorithm's own noise floor.  Usage: python tools/noise_budget.py [--size 256x512] [--noise]
+
+--per-op: instead, every per-op case of tests/float64_floor.py through the C restatement (oracle/lws_oracle.c, whose bits are the
+HIP kernels' bits) against the literal oracle in float32 and float64, one line of ratios per gate and the worst per op: the
+per-op table of DESIGN.md section 2.  --e2e: the end-to-end table beside it, from the committed tests/golden/ref_source_*.npz.
 """
 import argparse
 import os
@@ -59,13 +63,51 @@ def forward_mixed(left, right, sd, low=()):
     return pred
 
 
+def per_op():
+    """|C - fp64| over the gate's denominator (the literal float32 floor + tiny), whole tensor and border ring, per case."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import float64_floor as FF
+    rows = []
+    for family, cases in FF.CASES.items():
+        for params in cases:
+            c = FF.case(family, params)
+            rows += [(family, label, r) for label, r in FF.check(c, FF.C_RUNNERS[family](c), show=lambda line: print(line, flush=True))]
+    print(f"\n{'worst per op':19s} {'max':>5s} {'mean':>5s} {'ring max':>9s} {'ring mean':>10s}   (gates: {FF.MAX_FACTOR} / {FF.MEAN_FACTOR})")
+    for family, r in FF.worst_per_family(rows).items():
+        print(f"{family:19s} {r.max:5.2f} {r.mean:5.2f} {r.ring_max:9.2f} {r.ring_mean:10.2f}")
+
+
+def e2e():
+    """The distribution statistics of the C restatement's stage maps on the six reference-source fixtures."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import float64_floor as FF
+    from oracle import c_oracle as C
+    print(f"{'fixture':20s} stage  mean  median  |bias|  within 1e-3 px: build / reference float32")
+    for name in FF.E2E_SMOOTH + FF.E2E_CHAOTIC:
+        g, args, sd, align = FF.ref_source_case(name)
+        with O.variant(align_mode=align):
+            got = C.forward(g["left"], g["right"], sd, tuple(args.maxdisplist))
+        for s in range(4):
+            st = FF.assert_e2e_distribution(got[s], g[f"pred{s}"], g[f"pred64_{s}"], f"{name} stage {s + 1}", None, None, None)
+            print(f"{name:20s} {s + 1:5d} {st.mean_ratio:5.2f} {st.median_ratio:7.2f} {st.bias_ratio:7.2f}  {100 * st.within_1e3:6.2f} % / "
+                  f"{100 * st.floor_within_1e3:6.2f} %", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", default="256x512")
     ap.add_argument("--noise", action="store_true")
     ap.add_argument("--threads", type=int, default=8)
+    ap.add_argument("--per-op", action="store_true", help="the per-op ratio table of the C restatement (tests/float64_floor.py)")
+    ap.add_argument("--e2e", action="store_true", help="the end-to-end distribution table of the C restatement")
     a = ap.parse_args()
     torch.set_num_threads(a.threads)
+    if a.per_op or a.e2e:
+        if a.per_op:
+            per_op()
+        if a.e2e:
+            e2e()
+        return
     H, W = (int(v) for v in a.size.split("x"))
     if a.noise:
         l, r = make_noise_pair(H, W, 0)
