@@ -7,6 +7,7 @@
 #include <atomic>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "lwsnet_hip.h"
@@ -88,6 +89,22 @@ struct StopArm {
     } while (0)
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// Soft-argmin launchers (lws_regress.hip, lws_confidence.hip).  D -> DT: the depths of the three stages have a register-resident
+// kernel each, every other D runs the generic DT = 0 form; f is a generic lambda called with std::integral_constant<int, DT>.
+template <class F>
+static inline void dispatch_dt(int D, F &&f)
+{
+    switch (D) {
+        case 9: f(std::integral_constant<int, 9>{}); break;
+        case 24: f(std::integral_constant<int, 24>{}); break;
+        case 32: f(std::integral_constant<int, 32>{}); break;
+        default: f(std::integral_constant<int, 0>{}); break;
+    }
+}
+// Tile of the kernels that regress and upsample in one launch: 4 x 8 low-resolution pixels, or 2 x 4 (true) when that leaves most
+// CUs without a workgroup (one pair at 256x512: 64 tiles).
+static inline bool softargmin_small_tile(int h, int w, int B) { return (long)cdiv(w, 8) * cdiv(h, 4) * B < 256; }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of (function, device).  One mask per launch site, one bit per
 // device; handles on different host threads reach a launch site concurrently (lws_pool, bench.py's pipelined mode), so the
@@ -296,7 +313,7 @@ void apply_options(lws_ctx *h);                                                 
 void prof_clear(lws_ctx *h);                                                           // lws_forward.hip
 std::map<std::string, std::vector<int64_t>> build_spec(const lws_config &cfg);         // lws_params.hip
 
-// ---- kernel launchers (lws_volume.hip, lws_regress.hip, lws_conv3d.hip) ----
+// ---- kernel launchers (lws_volume.hip, lws_regress.hip, lws_confidence.hip, lws_conv3d.hip) ----
 // q16: round the feature values to fp16 where they are read (lws_config.feature_fp16)
 int launch_volume_l1_shift(const float *L, const float *R, float *cost, int B, int C, int h, int w, int D,
                            hipStream_t st, bool q16 = false);
@@ -325,13 +342,14 @@ int launch_conv3d_mid(const Stage3d &s, int layer, const float *act_in, float *a
 int launch_conv3d_last(const Stage3d &s, const float *act_in, const float *cost_skip, float *cost_out, int B,
                        int D, int h, int w, hipStream_t st);
 
-// 2D networks (lws_conv2d.hip)
+// feature extractor (lws_feature2d.hip)
 int launch_conv2d_nchw(const Conv2dLayer &l, const float *in, const float *res, float *out, int N, int H, int W,
                        hipStream_t st, const float *in2 = nullptr, int n1 = 0);
 int conv2d_pair_groups(int layer);
 void pack_pair_mfma(const float *w, int cin, float *out);
 int launch_conv2d_pair(const Conv2dLayer &a, const Conv2dLayer &b, const float *in, const float *res, float *out, int N,
                        int H, int W, hipStream_t st, const float *in2 = nullptr, int n1 = 0);
+// refinement (lws_refine.hip)
 int launch_ref_first(const float *in, int cin, const float *w, float *out, int B, int H, int W, hipStream_t st);
 int launch_ref_dws(const RefDws &l, const float *in, float *out, int B, int H, int W, hipStream_t st);
 bool ref_first_dws_can_fuse(const RefDws &l, int cin);

@@ -1,39 +1,24 @@
 // Per-pixel confidence and disparity sigma of a stage's soft-argmin (HBM-bound, float32, -ffp-contract=off).
 //
-// Arithmetic contract (include/lwsnet_hip.h, lws_softargmin_conf): the softmax over the D hypotheses is k_softargmin's, operation
-// for operation; `peak` is its mass within one hypothesis step of the regressed value, `sig` its standard deviation, and the
-// full-resolution maps are k_upsample_add's resize of the two.  One IEEE float32 operation per step.
+// Arithmetic contract (include/lwsnet_hip.h, lws_softargmin_conf): the softmax over the D hypotheses is k_softargmin's -- both call the
+// same functions of lws_device_math.h; `peak` is its mass within one hypothesis step of the regressed value, `sig` its standard
+// deviation, and the full-resolution maps are k_upsample_add's resize of the two.  One IEEE float32 operation per step.
 #include "lws_common.h"
 #include "lws_device_math.h"
 #include "lws_opkit.h"
 
 namespace lws {
 
-// d, peak and sig of one low-resolution pixel.  DT = compile-time D: the D costs are D coalesced plane reads issued before the first
-// use and stay in registers, p_k = e_k / S overwrites e_k so that the second-moment pass divides nothing again.  DT = 0: the generic
-// fallback re-reads the costs through L1 and recomputes e_k (a pure function of its input, so the same bits).
+// d, peak and sig of one low-resolution pixel: the shared softmax and expectation, then the moment pass over the same p_k.  DT =
+// compile-time D: the p_k stay in registers, so the moment pass divides nothing again.  DT = 0: the generic fallback re-reads the
+// costs through L1 and recomputes e_k (a pure function of its input, so the same bits).
 template <int DT>
 __device__ __forceinline__ void conf_pixel(const float *c, int64_t plane, int D, float start, float &d, float &peak, float &sig)
 {
-    float acc = 0.0f, pk = 0.0f, var = 0.0f;
-    if (DT > 0) {
-        float v[DT > 0 ? DT : 1];
-#pragma unroll
-        for (int k = 0; k < DT; ++k) v[k] = c[(int64_t)k * plane];
-        float m = -v[0];
-#pragma unroll
-        for (int k = 1; k < DT; ++k) m = fmaxf(m, -v[k]);
-        float S = 0.0f;
-#pragma unroll
-        for (int k = 0; k < DT; ++k) {
-            v[k] = lws_expf(-v[k] - m);
-            S = S + v[k];
-        }
-#pragma unroll
-        for (int k = 0; k < DT; ++k) {
-            v[k] = v[k] / S;
-            acc = acc + v[k] * (start + (float)k);
-        }
+    float acc, pk = 0.0f, var = 0.0f;
+    if constexpr (DT > 0) {
+        float v[DT];
+        acc = softargmin_regs<DT>(c, plane, start, v);
 #pragma unroll
         for (int k = 0; k < DT; ++k) {
             const float t = (start + (float)k) - acc;
@@ -41,10 +26,9 @@ __device__ __forceinline__ void conf_pixel(const float *c, int64_t plane, int D,
             var = var + v[k] * (t * t);
         }
     } else {
-        float m = -c[0];
-        for (int k = 1; k < D; ++k) m = fmaxf(m, -c[(int64_t)k * plane]);
-        float S = 0.0f;
-        for (int k = 0; k < D; ++k) S = S + lws_expf(-c[(int64_t)k * plane] - m);
+        float m, S;
+        softmax_max_sum(c, plane, D, m, S);
+        acc = 0.0f;
         for (int k = 0; k < D; ++k) {
             const float p = lws_expf(-c[(int64_t)k * plane] - m) / S;
             acc = acc + p * (start + (float)k);
@@ -132,18 +116,11 @@ __global__ __launch_bounds__(256) void k_softargmin_conf(const float *__restrict
         const int i10 = (y1 - ly0 + 1) * HX + (x0 - lx0 + 1), i11 = (y1 - ly0 + 1) * HX + (x1 - lx0 + 1);
         const int64_t o = ((int64_t)b * H + y) * W + x;
         if (conf != nullptr) {
-            const float top = sPeak[i00] * wx0 + sPeak[i01] * wx1;
-            const float bot = sPeak[i10] * wx0 + sPeak[i11] * wx1;
-            conf[o] = hy0 * top + hy1 * bot;
+            conf[o] = bilinear_blend(sPeak[i00], sPeak[i01], sPeak[i10], sPeak[i11], wx0, wx1, hy0, hy1);
         }
         if (sigma != nullptr) {
-            const float p00 = (sSig[i00] * mul_a) * mul_b;
-            const float p01 = (sSig[i01] * mul_a) * mul_b;
-            const float p10 = (sSig[i10] * mul_a) * mul_b;
-            const float p11 = (sSig[i11] * mul_a) * mul_b;
-            const float top = p00 * wx0 + p01 * wx1;
-            const float bot = p10 * wx0 + p11 * wx1;
-            sigma[o] = hy0 * top + hy1 * bot;
+            sigma[o] = bilinear_blend(scaled_tap(sSig[i00], mul_a, mul_b), scaled_tap(sSig[i01], mul_a, mul_b),
+                                      scaled_tap(sSig[i10], mul_a, mul_b), scaled_tap(sSig[i11], mul_a, mul_b), wx0, wx1, hy0, hy1);
         }
     }
 }
@@ -151,25 +128,19 @@ __global__ __launch_bounds__(256) void k_softargmin_conf(const float *__restrict
 int launch_softargmin_conf(const float *cost, float *disp_low, float *peak_low, float *sigma_low, float *conf, float *sigma, int B,
                            int D, int h, int w, int H, int W, float start, hipStream_t st, float ioff)
 {
-    // Tile: 4 x 8 low-resolution pixels, or 2 x 4 when that leaves most CUs without a workgroup (launch_softargmin_upsample's rule)
-    const bool small = (long)cdiv(w, 8) * cdiv(h, 4) * B < 256;
+    const bool small = softargmin_small_tile(h, w, B);
     dim3 grid(cdiv(w, small ? 4 : 8), cdiv(h, small ? 2 : 4), B), block(256);
     const float mul_a = (float)H, mul_b = 1.0f / (float)h;
     const int exact = (H % h == 0 && W % w == 0) ? 1 : 0;
-#define LWS_SC(DT)                                                                                                                \
-    if (small)                                                                                                                    \
-        hipLaunchKernelGGL((k_softargmin_conf<DT, 2, 4>), grid, block, 0, st, cost, disp_low, peak_low, sigma_low, conf, sigma, D, h, \
-                           w, H, W, start, mul_a, mul_b, ioff, exact);                                                             \
-    else                                                                                                                          \
-        hipLaunchKernelGGL((k_softargmin_conf<DT, 4, 8>), grid, block, 0, st, cost, disp_low, peak_low, sigma_low, conf, sigma, D, h, \
-                           w, H, W, start, mul_a, mul_b, ioff, exact)
-    switch (D) {
-        case 9: LWS_SC(9); break;
-        case 24: LWS_SC(24); break;
-        case 32: LWS_SC(32); break;
-        default: LWS_SC(0); break;
-    }
-#undef LWS_SC
+    dispatch_dt(D, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        if (small)
+            hipLaunchKernelGGL((k_softargmin_conf<DT, 2, 4>), grid, block, 0, st, cost, disp_low, peak_low, sigma_low, conf, sigma, D, h,
+                               w, H, W, start, mul_a, mul_b, ioff, exact);
+        else
+            hipLaunchKernelGGL((k_softargmin_conf<DT, 4, 8>), grid, block, 0, st, cost, disp_low, peak_low, sigma_low, conf, sigma, D, h,
+                               w, H, W, start, mul_a, mul_b, ioff, exact);
+    });
     LWS_LAUNCH_CHECK();
     return LWS_OK;
 }

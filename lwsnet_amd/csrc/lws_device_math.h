@@ -1,4 +1,4 @@
-// Device math shared by the regression kernels.
+// Device math shared by the kernels: the arithmetic chains that more than one kernel computes are defined here, once.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -108,6 +108,10 @@ __device__ __forceinline__ float4 bn_relu4(const float4 &x, const float4 &s, con
     return make_float4(lo.x, lo.y, hi.x, hi.y);
 }
 
+// scalar forms used by the 2D networks (lws_feature2d.hip, lws_refine.hip): BatchNorm(eval) + ReLU, and component j of a float4
+__device__ __forceinline__ float bn_relu2(float x, float s, float t) { return fmaxf(fmaf(x, s, t), 0.0f); }
+__device__ __forceinline__ float f4c(const float4 &v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
+
 // exp(x) for x <= 0 from IEEE mul / fma / rint only (Cephes expf polynomial), so the result is a
 // pure function of the float32 input on any IEEE machine; returns 0 below -80 (e^-80 ~ 1.8e-35).
 __device__ __forceinline__ float lws_expf(float x)
@@ -143,6 +147,17 @@ __device__ __forceinline__ void src_index(int dst, float ratio, int in, int &i0,
     i1 = (a < in - 1) ? a + 1 : a;
     l1 = s - (float)a;
     l0 = 1.0f - l1;
+}
+
+// The bilinear blend of every resize of the path, written once: a tap of a rescaled map is (t * mul_a) * mul_b, two
+// multiplications in this order ((float)H, then 1/(float)h: models.py:145-148); the blend is rows first, columns second.
+__device__ __forceinline__ float scaled_tap(float t, float mul_a, float mul_b) { return (t * mul_a) * mul_b; }
+__device__ __forceinline__ float bilinear_blend(float t00, float t01, float t10, float t11, float wx0, float wx1, float hy0,
+                                                float hy1)
+{
+    const float top = t00 * wx0 + t01 * wx1;
+    const float bot = t10 * wx0 + t11 * wx1;
+    return hy0 * top + hy1 * bot;
 }
 
 // A "deferred" full-resolution disparity map: pred(Y,X) = upsample(low * H / h)(Y,X) + prev(Y,X) evaluated on demand
@@ -181,13 +196,8 @@ __device__ __forceinline__ void upsample_at_n(const float *low, int h, int w, fl
     }
 #pragma unroll
     for (int i = 0; i < N; ++i) {
-        const float p00 = (t[i][0] * mul_a) * mul_b;
-        const float p01 = (t[i][1] * mul_a) * mul_b;
-        const float p10 = (t[i][2] * mul_a) * mul_b;
-        const float p11 = (t[i][3] * mul_a) * mul_b;
-        const float top = p00 * wx0[i] + p01 * wx1[i];
-        const float bot = p10 * wx0[i] + p11 * wx1[i];
-        out[i] = hy0[i] * top + hy1[i] * bot;
+        out[i] = bilinear_blend(scaled_tap(t[i][0], mul_a, mul_b), scaled_tap(t[i][1], mul_a, mul_b), scaled_tap(t[i][2], mul_a, mul_b),
+                                scaled_tap(t[i][3], mul_a, mul_b), wx0[i], wx1[i], hy0[i], hy1[i]);
     }
 }
 
@@ -225,21 +235,66 @@ __device__ __forceinline__ void deferred_at_n(const DeferredMap &m, const int (&
     for (int i = 0; i < N; ++i) out[i] = have_prev ? v[i] + pv[i] : v[i];
 }
 
-// sum_k softmax_k(-c) * (start + k) over D values c[k*stride]: max-subtracted, S summed ascending,
-// p_k = e_k / S (IEEE division), expectation summed ascending.  e_k is recomputed in the third
-// pass instead of being kept in a D-sized register array (it is a pure function, so identical).
+// ---- the soft-argmin chain, written once (k_softargmin, k_softargmin_upsample, k_softargmin_conf) -------------------------
+// softmax_k(-c) over D values c[k*stride]: m = max_k(-c_k), e_k = lws_expf(-c_k - m), S = sum e_k ascending, p_k = e_k / S (IEEE
+// division); the regressed value is sum_k p_k * (start + k), ascending.
+//
+// Register form, DT = compile-time D: the DT loads are issued before the first use and the values stay in registers (one memory
+// round trip).  Returns the regressed value and leaves the normalised p_k in v for a caller that needs further moments.  (The
+// division and the expectation share one loop: as two loops the same operations cost k_softargmin_conf<32> three more VGPRs.)
+template <int DT>
+__device__ __forceinline__ float softargmin_regs(const float *c, int64_t stride, float start, float (&v)[DT])
+{
+#pragma unroll
+    for (int k = 0; k < DT; ++k) v[k] = c[(int64_t)k * stride];
+    float m = -v[0];
+#pragma unroll
+    for (int k = 1; k < DT; ++k) m = fmaxf(m, -v[k]);
+    float S = 0.0f;
+#pragma unroll
+    for (int k = 0; k < DT; ++k) {
+        v[k] = lws_expf(-v[k] - m);
+        S = S + v[k];
+    }
+    float acc = 0.0f;
+#pragma unroll
+    for (int k = 0; k < DT; ++k) {
+        v[k] = v[k] / S;
+        acc = acc + v[k] * (start + (float)k);
+    }
+    return acc;
+}
+
+// Generic form (any D): the costs are re-read through L1 and e_k is recomputed where it is needed instead of being kept in a
+// D-sized register array (it is a pure function of its input, so the same bits).
+__device__ __forceinline__ void softmax_max_sum(const float *c, int64_t stride, int D, float &m, float &S)
+{
+    m = -c[0];
+    for (int k = 1; k < D; ++k) m = fmaxf(m, -c[(int64_t)k * stride]);
+    S = 0.0f;
+    for (int k = 0; k < D; ++k) S = S + lws_expf(-c[(int64_t)k * stride] - m);
+}
 __device__ __forceinline__ float softargmin_pixel(const float *c, int64_t stride, int D, float start)
 {
-    float m = -c[0];
-    for (int k = 1; k < D; ++k) m = fmaxf(m, -c[(int64_t)k * stride]);
-    float S = 0.0f;
-    for (int k = 0; k < D; ++k) S = S + lws_expf(-c[(int64_t)k * stride] - m);
+    float m, S;
+    softmax_max_sum(c, stride, D, m, S);
     float acc = 0.0f;
     for (int k = 0; k < D; ++k) {
         float pk = lws_expf(-c[(int64_t)k * stride] - m) / S;
         acc = acc + pk * (start + (float)k);
     }
     return acc;
+}
+// the regressed value of one pixel: the register form for DT > 0, the generic one for DT = 0
+template <int DT>
+__device__ __forceinline__ float softargmin_dt(const float *c, int64_t stride, int D, float start)
+{
+    if constexpr (DT > 0) {
+        float v[DT];
+        return softargmin_regs<DT>(c, stride, start, v);
+    } else {
+        return softargmin_pixel(c, stride, D, start);
+    }
 }
 
 }  // namespace lws

@@ -2,7 +2,7 @@
 // lws_confidence, lws_sparsification, lws_photometric; lws_rowkit.h builds on it).  An op is its own arithmetic and its own limits between these
 // pieces.  Host half: the argument checks their entry points share, under the caller's name `who`, so that a text is written once.
 // Device half: the 64-lane sum, the four-wave combine in its fixed order, and the ground-truth contract of the evaluation kernels.
-// The translation units of the forward (conv2d, conv3d, volume, regress, forward, params, api, pool) do not include this header.
+// The translation units of the forward (feature2d, refine, conv3d, volume, regress, forward, params, api, pool) do not include this header.
 #pragma once
 #include "lws_common.h"
 

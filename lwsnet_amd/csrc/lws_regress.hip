@@ -11,7 +11,7 @@ namespace lws {
 // One thread per pixel.  The D costs of a pixel are D coalesced plane reads, all issued before the first use
 // (DT = compile-time D keeps them in registers: one memory round trip instead of three dependent passes);
 // DT = 0 is the generic fallback that re-reads through L1.  p_k = e_k / S is a correctly rounded division, as in
-// the literal softmax followed by the expectation.
+// the literal softmax followed by the expectation (softargmin_dt, lws_device_math.h).
 template <int DT>
 __global__ __launch_bounds__(64) void k_softargmin(const float *__restrict__ cost, float *__restrict__ low,
                                                    int64_t plane, int D, float start)
@@ -20,30 +20,7 @@ __global__ __launch_bounds__(64) void k_softargmin(const float *__restrict__ cos
     const int b = blockIdx.y;
     if (p >= plane) return;
     const float *c = cost + (int64_t)b * D * plane + p;
-    float r;
-    if (DT > 0) {
-        float v[DT > 0 ? DT : 1];
-#pragma unroll
-        for (int k = 0; k < DT; ++k) v[k] = c[(int64_t)k * plane];
-        float m = -v[0];
-#pragma unroll
-        for (int k = 1; k < DT; ++k) m = fmaxf(m, -v[k]);
-        float S = 0.0f;
-#pragma unroll
-        for (int k = 0; k < DT; ++k) {
-            v[k] = lws_expf(-v[k] - m);
-            S = S + v[k];
-        }
-        float acc = 0.0f;
-#pragma unroll
-        for (int k = 0; k < DT; ++k) {
-            float pk = v[k] / S;
-            acc = acc + pk * (start + (float)k);
-        }
-        r = acc;
-    } else {
-        r = softargmin_pixel(c, plane, D, start);
-    }
+    const float r = softargmin_dt<DT>(c, plane, D, start);
     low[(int64_t)b * plane + p] = r;
 }
 
@@ -51,12 +28,9 @@ int launch_softargmin(const float *cost, float *low, int B, int D, int h, int w,
 {
     const int64_t plane = (int64_t)h * w;
     dim3 grid((unsigned)((plane + 63) / 64), B), block(64);   // 64-thread blocks: the stage-1 map has only h*w = 2048 pixels
-    switch (D) {
-        case 9: hipLaunchKernelGGL(k_softargmin<9>, grid, block, 0, st, cost, low, plane, D, start); break;
-        case 24: hipLaunchKernelGGL(k_softargmin<24>, grid, block, 0, st, cost, low, plane, D, start); break;
-        case 32: hipLaunchKernelGGL(k_softargmin<32>, grid, block, 0, st, cost, low, plane, D, start); break;
-        default: hipLaunchKernelGGL(k_softargmin<0>, grid, block, 0, st, cost, low, plane, D, start); break;
-    }
+    dispatch_dt(D, [&](auto dt) {
+        hipLaunchKernelGGL(k_softargmin<decltype(dt)::value>, grid, block, 0, st, cost, low, plane, D, start);
+    });
     LWS_LAUNCH_CHECK();
     return LWS_OK;
 }
@@ -77,13 +51,9 @@ __global__ __launch_bounds__(256) void k_upsample_add(const float *__restrict__ 
     src_index(y, rh, h, y0, y1, hy0, hy1, ioff);
     src_index(x, rw, w, x0, x1, wx0, wx1, ioff);
     const float *p = low + (int64_t)b * h * w;
-    float p00 = (p[(int64_t)y0 * w + x0] * mul_a) * mul_b;
-    float p01 = (p[(int64_t)y0 * w + x1] * mul_a) * mul_b;
-    float p10 = (p[(int64_t)y1 * w + x0] * mul_a) * mul_b;
-    float p11 = (p[(int64_t)y1 * w + x1] * mul_a) * mul_b;
-    float top = p00 * wx0 + p01 * wx1;
-    float bot = p10 * wx0 + p11 * wx1;
-    float v = hy0 * top + hy1 * bot;
+    float v = bilinear_blend(scaled_tap(p[(int64_t)y0 * w + x0], mul_a, mul_b), scaled_tap(p[(int64_t)y0 * w + x1], mul_a, mul_b),
+                             scaled_tap(p[(int64_t)y1 * w + x0], mul_a, mul_b), scaled_tap(p[(int64_t)y1 * w + x1], mul_a, mul_b),
+                             wx0, wx1, hy0, hy1);
     const int64_t o = ((int64_t)b * H + y) * W + x;
     if (prev != nullptr) v = v + prev[o];
     out[o] = v;
@@ -122,29 +92,7 @@ __global__ __launch_bounds__(256) void k_softargmin_upsample(const float *__rest
         float r = 0.0f;
         if (y >= 0 && y < h && x >= 0 && x < w) {
             const float *c = cost + (int64_t)b * D * plane + (int64_t)y * w + x;
-            if (DT > 0) {
-                float v[DT > 0 ? DT : 1];
-#pragma unroll
-                for (int k = 0; k < DT; ++k) v[k] = c[(int64_t)k * plane];
-                float m = -v[0];
-#pragma unroll
-                for (int k = 1; k < DT; ++k) m = fmaxf(m, -v[k]);
-                float S = 0.0f;
-#pragma unroll
-                for (int k = 0; k < DT; ++k) {
-                    v[k] = lws_expf(-v[k] - m);
-                    S = S + v[k];
-                }
-                float acc = 0.0f;
-#pragma unroll
-                for (int k = 0; k < DT; ++k) {
-                    float pk = v[k] / S;
-                    acc = acc + pk * (start + (float)k);
-                }
-                r = acc;
-            } else {
-                r = softargmin_pixel(c, plane, D, start);
-            }
+            r = softargmin_dt<DT>(c, plane, D, start);
             if (low_out != nullptr && hy >= 1 && hy <= SU_TY && hx >= 1 && hx <= SU_TX)
                 low_out[(int64_t)b * plane + (int64_t)y * w + x] = r;
         }
@@ -163,13 +111,9 @@ __global__ __launch_bounds__(256) void k_softargmin_upsample(const float *__rest
         src_index(y, rh, h, y0, y1, hy0, hy1, ioff);
         src_index(x, rw, w, x0, x1, wx0, wx1, ioff);
         const float *p = sLow + (1 - ly0) * SU_HX + (1 - lx0);      // low-res (y,x) -> sLow[(y-ly0+1)*HX + x-lx0+1]
-        float p00 = (p[y0 * SU_HX + x0] * mul_a) * mul_b;
-        float p01 = (p[y0 * SU_HX + x1] * mul_a) * mul_b;
-        float p10 = (p[y1 * SU_HX + x0] * mul_a) * mul_b;
-        float p11 = (p[y1 * SU_HX + x1] * mul_a) * mul_b;
-        float top = p00 * wx0 + p01 * wx1;
-        float bot = p10 * wx0 + p11 * wx1;
-        float v = hy0 * top + hy1 * bot;
+        float v = bilinear_blend(scaled_tap(p[y0 * SU_HX + x0], mul_a, mul_b), scaled_tap(p[y0 * SU_HX + x1], mul_a, mul_b),
+                                 scaled_tap(p[y1 * SU_HX + x0], mul_a, mul_b), scaled_tap(p[y1 * SU_HX + x1], mul_a, mul_b), wx0,
+                                 wx1, hy0, hy1);
         const int64_t o = ((int64_t)b * H + y) * W + x;
         if (prev != nullptr) v = v + prev[o];
         out[o] = v;
@@ -179,23 +123,18 @@ __global__ __launch_bounds__(256) void k_softargmin_upsample(const float *__rest
 int launch_softargmin_upsample(const float *cost, const float *prev, float *out, float *low_out, int B, int D, int h,
                                int w, int H, int W, float start, hipStream_t st, float ioff)
 {
-    const bool small = (long)cdiv(w, 8) * cdiv(h, 4) * B < 256;
+    const bool small = softargmin_small_tile(h, w, B);
     dim3 grid(cdiv(w, small ? 4 : 8), cdiv(h, small ? 2 : 4), B), block(256);
     const float mul_a = (float)H, mul_b = 1.0f / (float)h;
-#define LWS_SU(DT)                                                                                                              \
-    if (small)                                                                                                                  \
-        hipLaunchKernelGGL((k_softargmin_upsample<DT, 2, 4>), grid, block, 0, st, cost, prev, out, low_out, D, h, w, H, W, start, \
-                           mul_a, mul_b, ioff);                                                                                  \
-    else                                                                                                                        \
-        hipLaunchKernelGGL((k_softargmin_upsample<DT, 4, 8>), grid, block, 0, st, cost, prev, out, low_out, D, h, w, H, W, start, \
-                           mul_a, mul_b, ioff)
-    switch (D) {
-        case 9: LWS_SU(9); break;
-        case 24: LWS_SU(24); break;
-        case 32: LWS_SU(32); break;
-        default: LWS_SU(0); break;
-    }
-#undef LWS_SU
+    dispatch_dt(D, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        if (small)
+            hipLaunchKernelGGL((k_softargmin_upsample<DT, 2, 4>), grid, block, 0, st, cost, prev, out, low_out, D, h, w, H, W, start,
+                               mul_a, mul_b, ioff);
+        else
+            hipLaunchKernelGGL((k_softargmin_upsample<DT, 4, 8>), grid, block, 0, st, cost, prev, out, low_out, D, h, w, H, W, start,
+                               mul_a, mul_b, ioff);
+    });
     LWS_LAUNCH_CHECK();
     return LWS_OK;
 }

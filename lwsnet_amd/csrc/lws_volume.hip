@@ -231,9 +231,7 @@ __global__ __launch_bounds__(WARP_TX *WARP_NW) void k_volume_l1_warp(const float
                 pm[(int64_t)y1 * W + x0] = q0[2];
                 pm[(int64_t)y1 * W + x1] = q0[3];
             }
-            const float top = q[0] * wx0 + q[1] * wx1;
-            const float bot = q[2] * wx0 + q[3] * wx1;
-            wf = hy0 * top + hy1 * bot;
+            wf = bilinear_blend(q[0], q[1], q[2], q[3], wx0, wx1, hy0, hy1);
             wf = wf * mul_a;
             wf = wf * mul_b;
             if (wflow_out != nullptr) wflow_out[(int64_t)b * plane + (int64_t)y * w + x] = wf;

@@ -15,13 +15,13 @@ KERNELS = {  # name: (stamp id, translation unit, driver, arg)
     "last1": (3, "conv3d", "stack", 0), "last3": (3, "conv3d", "stack", 2),
     "first1": (4, "conv3d", "stack", 0), "first3": (4, "conv3d", "stack", 2),
     
-    "dws": (5, "conv2d", "refine", None), "conv64": (6, "conv2d", "refine", None),
-    "feat": (7, "conv2d", "feat", None), "pair0": (13, "conv2d", "feat", None), "pair1": (14, "conv2d", "feat", None),
-    "pair2": (15, "conv2d", "feat", None), "pair3": (16, "conv2d", "feat", None), "ref_last": (9, "conv2d", "refine", None),
+    "dws": (5, "refine", "refine", None), "conv64": (6, "refine", "refine", None),
+    "feat": (7, "feature2d", "feat", None), "pair0": (13, "feature2d", "feat", None), "pair1": (14, "feature2d", "feat", None),
+    "pair2": (15, "feature2d", "feat", None), "pair3": (16, "feature2d", "feat", None), "ref_last": (9, "refine", "refine", None),
     "warp2": (10, "volume", "stages", None), "warp3": (10, "volume", "stages", None),
     "mid8q3": (18, "conv3d", "stack", 2), "mid8q2": (18, "conv3d", "stack", 1),
     "mid16x": (19, "conv3d", "stack", 0), "mid8x3": (20, "conv3d", "stack", 2), "mid8x2": (20, "conv3d", "stack", 1),
-    "conv64x": (21, "conv2d", "refine", None),
+    "conv64x": (21, "refine", "refine", None),
 }
 what = sys.argv[1]
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 1
