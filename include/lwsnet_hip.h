@@ -287,6 +287,57 @@ int64_t lws_point_cloud_workspace(int B, int H);
 int lws_point_cloud(const float *disp, const uint8_t *mask, const uint8_t *rgb, const float *cam, int B, int H, int W, float min_disp,
                     float max_depth, void *workspace, void *points, int64_t *counts, void *stream);
 
+/* ---- surface normals and a triangle mesh of a disparity map: the pixel grid as neighbourhood (additive after v8) ---- */
+/* disp, mask, cam, min_disp, max_depth: as lws_depth_maps, with its validity rule and its P = (X, Y, Z) unchanged; cam is required.
+ * max_jump float32, finite and >= 0: the largest disparity step a surface may take between two neighbouring pixels.  H*W < 2^30
+ * (a face count fits an int32), B <= 65535.  One IEEE float32 operation per step, no fmaf:
+ *   connected  two pixels p, q are connected iff both are valid and fabsf(d_p - d_q) <= max_jump (one subtraction, one compare:
+ *              the join rule of lws_speckle_filter)
+ *   normal of a valid pixel p with the neighbours R (x+1), D (y+1), L (x-1), U (y-1); a pixel outside the image is invalid:
+ *     e_Q = P_Q - P_p componentwise, for a connected neighbour Q
+ *     the quadrants are the ordered pairs (D,R), (R,U), (U,L), (L,D), in this order; (A,B) is present iff A and B are both connected
+ *     to p.  0, 1, 2 or 4 quadrants are present, never 3: three present quadrants need all four neighbours connected
+ *     c = cross(e_A, e_B):  c.x = a.y*b.z - a.z*b.y;  c.y = a.z*b.x - a.x*b.z;  c.z = a.x*b.y - a.y*b.x
+ *     s = (0, 0, 0);  s += c for the present quadrants in the order above
+ *     len = sqrtf((s.x*s.x + s.y*s.y) + s.z*s.z);  n = s / len (three divisions)
+ *     n = (+0, +0, +0) if no quadrant is present, or len is not finite, or not len > 0; and for an invalid pixel
+ *   a surface that faces the camera has n.z < 0; a fronto-parallel plane gives exactly (0, 0, -1)
+ *   u8(v) = (uint8)(int)rintf((v * 0.5f + 0.5f) * 255.0f)      (separate operations, rintf: half to even, the low 8 bits of the int)
+ *   normal-map pixel = {u8(n.x), u8(-n.y), u8(-n.z)}: OpenGL convention (x right, y up, z towards the viewer); the zero normal
+ *   gives 128, 128, 128
+ * Deterministic (no atomics) and independent of B and of the other images of the batch; argument errors -- a null or misaligned
+ * pointer, a bad shape or threshold, outputs that overlap each other or an input -- return LWS_ERR_INVALID before any GPU call.
+ * No scratch memory. */
+/* One launch, no workspace.  normals float32 [B,3,H,W] planar (NULL: skipped), normals8 uint8 [B,H,W,3] (NULL: skipped; any
+ * alignment); not both NULL. */
+int lws_surface_normals(const float *disp, const uint8_t *mask, const float *cam, int B, int H, int W, float min_disp, float max_depth,
+                        float max_jump, float *normals, uint8_t *normals8, void *stream);
+/* bytes of device workspace lws_surface_mesh needs for this geometry: two int32 per row (vertex and face counts), each part
+ * rounded up to 256 bytes */
+int64_t lws_surface_mesh_workspace(int B, int H);
+/* An indexed triangle mesh that does not span depth discontinuities.
+ *   vertices  the valid pixels of image b in raster order: vertex i is record i of lws_point_cloud, with the same bits (points:
+ *             16-byte records {float X, Y, Z; uint8 r, g, b, a = 255} from points + b*H*W, 16-byte aligned, room for B*H*W; colour
+ *             from rgb uint8 [B,H,W,3], NULL: white).  A vertex no face uses stays.
+ *   vnormals  16-byte records {n.x, n.y, n.z, 0.0f}, record i = normals[b,:,y,x] of vertex i's pixel, where normals float32 [B,3,H,W]
+ *             is what lws_surface_normals wrote (same layout and alignment as points).  vnormals is required iff normals is given,
+ *             and NULL otherwise
+ *   faces     int32 [B][2*(H-1)*(W-1)][3] (never NULL: at least one record).  The cell (x, y), x < W-1, y < H-1, has the corners
+ *             a = (x, y), b = (x+1, y), c = (x, y+1), e = (x+1, y+1).  A triangle is emitted iff all three of its corner pairs are
+ *             connected (so its corners are valid), the diagonal included.  If b and c are both valid the diagonal is b-c:
+ *             T0 = (a, c, b), T1 = (b, c, e).  Otherwise, if a and e are both valid, it is a-e: T0 = (a, c, e), T1 = (a, e, b), of which
+ *             at most one passes.  Otherwise nothing.  Faces are packed per image in raster order of the cells, T0 before T1, each
+ *             three vertex indices of image b in the order written; each has a geometric normal with negative z
+ *   index     (NULL: skipped) int32 [B,1,H,W]: a pixel's vertex index, -1 for an invalid pixel
+ *   counts    int64 [B][2] = {vertices, faces}; records of points, vnormals and faces past them are left unwritten
+ * workspace: lws_surface_mesh_workspace(B, H) bytes, 4-byte aligned, contents undefined before and after.  Three launches on
+ * `stream` -- per-row counts of vertices and faces, a per-image exclusive scan of both, a per-row scatter that ranks the pixels of
+ * rows y and y+1 and the faces of cell row y by wave ballots -- a fixed list with no device-to-host read, so the call can be
+ * captured into a hipGraph. */
+int lws_surface_mesh(const float *disp, const uint8_t *mask, const uint8_t *rgb, const float *cam, const float *normals, int B, int H,
+                     int W, float min_disp, float max_depth, float max_jump, void *workspace, void *points, void *vnormals,
+                     int32_t *faces, int32_t *index, int64_t *counts, void *stream);
+
 /* ---- speckle filter: connected components of a disparity map (additive after v8) ---- */
 /* bytes of device workspace lws_speckle_filter needs for this geometry: per pixel one int32 parent word and one int32 size word
  * (8 bytes), plus three int32 per row for the counts, each part rounded up to 256 bytes */

@@ -55,6 +55,9 @@ PROTOTYPES = {
     "lws_depth_maps": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp]),
     "lws_point_cloud_workspace": (ctypes.c_int64, [_i, _i]),
     "lws_point_cloud": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp]),
+    "lws_surface_normals": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp]),
+    "lws_surface_mesh_workspace": (ctypes.c_int64, [_i, _i]),
+    "lws_surface_mesh": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lws_speckle_workspace": (ctypes.c_int64, [_i, _i, _i]),
     "lws_speckle_filter": (_i, [_vp, _vp, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lws_wmedian_filter": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),

@@ -1,6 +1,7 @@
-"""Cameras and point-cloud files for the geometry outputs (metric depth, KITTI 16-bit PNGs, point clouds; include/lwsnet_hip.h,
-lws_depth_maps / lws_point_cloud) and the calibration of a raw stereo rig for the rectifying front end (lws_rectify_pair).  numpy
-only: the device side is lwsnet_amd.ops.depth_maps / point_cloud / rectify_pair."""
+"""Cameras, point-cloud and mesh files for the geometry outputs (metric depth, KITTI 16-bit PNGs, point clouds, triangle meshes;
+include/lwsnet_hip.h, lws_depth_maps / lws_point_cloud / lws_surface_mesh) and the calibration of a raw stereo rig for the rectifying
+front end (lws_rectify_pair).  numpy only: the device side is lwsnet_amd.ops.depth_maps / point_cloud / surface_normals /
+surface_mesh / rectify_pair."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -247,3 +248,61 @@ def read_ply(path):
     end = data.index(b"end_header\n") + len(b"end_header\n")
     n = int(next(l for l in data[:end].decode("ascii").splitlines() if l.startswith("element vertex")).split()[2])
     return np.frombuffer(data, POINT_DTYPE, count=n, offset=end)
+
+
+VERTEX_NORMAL_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("red", "u1"),
+                                ("green", "u1"), ("blue", "u1"), ("alpha", "u1")])   # a vertex of a mesh file with normals
+FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])   # `property list uchar int vertex_indices` of a triangle: 13 bytes
+
+
+def mesh_ply_bytes(points_bytes, n, faces, vnormals=None):
+    """Binary little-endian PLY of a triangle mesh (lws_surface_mesh): n vertices laid out as the device writes them
+    (POINT_DTYPE), faces int32 [m,3], vnormals None or float32 [n,4] records {nx, ny, nz, 0} (the device's vnormals).  Vertex:
+    x y z [nx ny nz] red green blue alpha; face: a uchar count of 3 and three int indices."""
+    data = memoryview(points_bytes).cast("B")
+    if len(data) < 16 * n:
+        raise ValueError(f"{len(data)} bytes hold fewer than {n} points")
+    pts = np.frombuffer(data, POINT_DTYPE, count=n)
+    faces = np.asarray(faces)
+    if faces.dtype != np.int32 or faces.ndim != 2 or faces.shape[1] != 3:
+        raise ValueError(f"faces must be int32 [m,3]; got {faces.dtype} {faces.shape}")
+    if len(faces) and (faces.min() < 0 or faces.max() >= n):
+        raise ValueError(f"a face index lies outside 0 .. {n - 1}")
+    props = "property float x\nproperty float y\nproperty float z\n"
+    if vnormals is None:
+        verts = pts
+    else:
+        vn = np.asarray(vnormals)
+        if vn.dtype != np.float32 or vn.shape != (n, 4):
+            raise ValueError(f"vnormals must be float32 [{n},4]; got {vn.dtype} {vn.shape}")
+        verts = np.empty(n, VERTEX_NORMAL_DTYPE)
+        for name in POINT_DTYPE.names:
+            verts[name] = pts[name]
+        verts["nx"], verts["ny"], verts["nz"] = vn[:, 0], vn[:, 1], vn[:, 2]
+        props += "property float nx\nproperty float ny\nproperty float nz\n"
+    rec = np.empty(len(faces), FACE_DTYPE)
+    rec["n"], rec["v"] = 3, faces
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex {}\n{}property uchar red\nproperty uchar green\nproperty uchar blue\n"
+              "property uchar alpha\nelement face {}\nproperty list uchar int vertex_indices\nend_header\n").format(n, props, len(faces))
+    return header.encode("ascii") + verts.tobytes() + rec.tobytes()
+
+
+def write_mesh_ply(path, points_bytes, n, faces, vnormals=None):
+    with open(path, "wb") as f:
+        f.write(mesh_ply_bytes(points_bytes, n, faces, vnormals))
+
+
+def read_mesh_ply(path):
+    """A file write_mesh_ply wrote -> (vertices: a VERTEX_NORMAL_DTYPE array, or POINT_DTYPE without normals; faces int32 [m,3])."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    lines = data[:end].decode("ascii").splitlines()
+    n = int(next(l for l in lines if l.startswith("element vertex")).split()[2])
+    m = int(next(l for l in lines if l.startswith("element face")).split()[2])
+    dtype = VERTEX_NORMAL_DTYPE if "property float nx" in lines else POINT_DTYPE
+    verts = np.frombuffer(data, dtype, count=n, offset=end)
+    rec = np.frombuffer(data, FACE_DTYPE, count=m, offset=end + n * dtype.itemsize)
+    if not np.all(rec["n"] == 3):
+        raise ValueError(f"{path}: a face is not a triangle")
+    return verts, np.ascontiguousarray(rec["v"])

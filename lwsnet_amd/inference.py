@@ -34,6 +34,12 @@ checked maps (lws_occlusion_check: the left-view map splatted into the right vie
 points need a camera: `--calib` (a KITTI calibration file, or in directory mode a folder of them named after the frames) or
 `--camera FX FY CX CY BASELINE` in the uncropped image's pixels; it is cropped as the images are.
 
+`--save_normals`, `--save_mesh [--max_jump J]`: an OpenGL-convention normal map `<stem>_normals.png` and a binary PLY triangle mesh
+`<stem>_mesh.ply` (the vertices of `<stem>.ply` with their normals, two triangles per grid cell) beside each colour file
+(lws_surface_normals / lws_surface_mesh).  Two neighbouring pixels belong to one surface when their disparities differ by <= J
+(default 1), so no triangle spans a depth discontinuity.  Both need a camera and the sequential mode, as `--save_ply` does, and keep
+the pixels it keeps.
+
 `--speckle SIZE [--speckle_diff D] [--speckle_fill]`: the connected blobs of at most SIZE pixels (4-neighbours joined when their
 disparities differ by <= D, default 1) are removed from the stage maps on the device (lws_speckle_filter) before the colour, 16-bit
 and point-cloud files are written, and each colour file gets a grey code map `<stem>_sp.png` beside it (kept 255, speckle 64, the
@@ -59,7 +65,7 @@ frame (logged, nothing written); a rectified frame smaller than the crop is skip
 stage's confidence (the probability mass its soft-argmin puts within one hypothesis step of the disparity) and sigma (the standard
 deviation of that distribution in pixels).  `--save_conf` writes the finest stage's (stage 3's) two maps as 8-bit grey files, two per
 pair, beside the colour file (with `--left_img` beside `3.png`): `<stem>_conf.png` = rint(clip(conf, 0, 1) * 255) and `<stem>_sigma.png` = rint(min(sigma, MAX) * 255 / MAX), MAX = 8 px by
-default.  `--conf_min C` and `--sigma_max_keep S` keep a pixel in the `_disp16`, `_depth16` and `.ply` files only where its stage's
+default.  `--conf_min C` and `--sigma_max_keep S` keep a pixel in the `_disp16`, `_depth16`, `.ply`, `_normals` and `_mesh.ply` files only where its stage's
 conf >= C and sigma <= S (ops.confidence_codes; stage 4, the refined map, goes by stage 3's), on top of what the speckle filter's
 codes drop.  They are not part of the post-processing chain, and not available with `--lr_check`, `--occ_check` or `--workers`.
 
@@ -125,9 +131,14 @@ def add_conf_arguments(p):
                         "maps (sequential mode only; not in the reference)")
     p.add_argument("--sigma_max", type=float, default=argparse.SUPPRESS, metavar="MAX", help="with --save_conf: the sigma, in pixels, that maps to 255 (default 8)")
     p.add_argument("--conf_min", type=float, default=argparse.SUPPRESS, metavar="C",
-                   help="--save_disp16 / --save_depth / --save_ply keep only the pixels whose confidence is >= C")
+                   help="--save_disp16 / --save_depth / --save_ply / --save_normals / --save_mesh keep only the pixels whose confidence is >= C")
     p.add_argument("--sigma_max_keep", type=float, default=argparse.SUPPRESS, metavar="S",
-                   help="--save_disp16 / --save_depth / --save_ply keep only the pixels whose disparity sigma is <= S pixels")
+                   help="--save_disp16 / --save_depth / --save_ply / --save_normals / --save_mesh keep only the pixels whose disparity sigma is <= S pixels")
+
+
+def _geometry_requested(args):
+    """One of the files _save_geometry writes is asked for."""
+    return any(getattr(args, flag, False) for flag in ("save_disp16", "save_depth", "save_ply", "save_normals", "save_mesh"))
 
 
 def conf_requested(args):
@@ -156,8 +167,8 @@ def check_conf_arguments(p, args):
         p.error(f"{flags} use the network's own confidence and do not combine with --lr_check or --occ_check")
     if args.workers > 0:
         p.error(f"{flags} run in the sequential mode only: use --workers 0")
-    if (args.conf_min is not None or args.sigma_max_keep is not None) and not (args.save_disp16 or args.save_depth or args.save_ply):
-        p.error("--conf_min and --sigma_max_keep mask --save_disp16 / --save_depth / --save_ply: give one of them")
+    if (args.conf_min is not None or args.sigma_max_keep is not None) and not _geometry_requested(args):
+        p.error("--conf_min and --sigma_max_keep mask --save_disp16 / --save_depth / --save_ply / --save_normals / --save_mesh: give one of them")
 
 
 def conf_to_u8(conf):
@@ -225,6 +236,14 @@ def add_geometry_arguments(p):
     p.add_argument("--save_disp16", action="store_true", help="write <stem>_disp16.png, KITTI's 16-bit disparity PNG (d * 256)")
     p.add_argument("--save_depth", action="store_true", help="write <stem>_depth16.png, a 16-bit depth PNG (metres * 256); needs a camera")
     p.add_argument("--save_ply", action="store_true", help="write <stem>.ply, a binary point cloud of the kept pixels; needs a camera")
+    # a command line without the next three parses to the namespace it parsed to before they existed; check_geometry_arguments
+    # writes their defaults
+    p.add_argument("--save_normals", action="store_true", default=argparse.SUPPRESS,
+                   help="write <stem>_normals.png, the surface normals of the kept pixels as an OpenGL-convention normal map; needs a camera")
+    p.add_argument("--save_mesh", action="store_true", default=argparse.SUPPRESS,
+                   help="write <stem>_mesh.ply, a binary triangle mesh of the kept pixels with vertex normals; needs a camera")
+    p.add_argument("--max_jump", type=float, default=argparse.SUPPRESS, metavar="J",
+                   help="normals and mesh: the largest disparity step between two neighbouring pixels of one surface (default 1)")
 
 
 def _list_pairs(args):
@@ -250,15 +269,20 @@ def _calib_path(args, left_path):
 def check_geometry_arguments(p, args):
     """Rejects what the geometry outputs do not support, before any model or GPU work; reads every calibration file."""
     from .geometry import Camera
-    outputs = args.save_disp16 or args.save_depth or args.save_ply
+    args.save_normals, args.save_mesh = getattr(args, "save_normals", False), getattr(args, "save_mesh", False)
+    args.max_jump = getattr(args, "max_jump", 1.0)
+    surface = args.save_normals or args.save_mesh
+    outputs = args.save_disp16 or args.save_depth or args.save_ply or surface
+    if not (np.isfinite(args.max_jump) and args.max_jump >= 0):
+        p.error(f"--max_jump must be finite and >= 0, got {args.max_jump}")
     if not (np.isfinite(args.min_disp) and args.min_disp > 0):
         p.error(f"--min_disp must be finite and > 0, got {args.min_disp}")
     if not args.max_depth > 0:
         p.error(f"--max_depth must be > 0, got {args.max_depth}")
-    if (args.save_depth or args.save_ply) and args.calib is None and args.camera is None and getattr(args, "rectify", None) is None:
-        p.error("--save_depth and --save_ply need a camera: --calib PATH or --camera FX FY CX CY BASELINE")
+    if (args.save_depth or args.save_ply or surface) and args.calib is None and args.camera is None and getattr(args, "rectify", None) is None:
+        p.error("--save_depth, --save_ply, --save_normals and --save_mesh need a camera: --calib PATH or --camera FX FY CX CY BASELINE")
     if outputs and args.workers > 0:
-        p.error("--save_disp16 / --save_depth / --save_ply run in the sequential mode only: use --workers 0")
+        p.error("--save_disp16 / --save_depth / --save_ply / --save_normals / --save_mesh run in the sequential mode only: use --workers 0")
     if args.camera is not None:
         try:
             Camera(*args.camera).check()
@@ -453,7 +477,7 @@ def inference(model, left_imgs, right_imgs, args, log):
     written = []
     warm = False
     opts = post.Options.from_args(args)
-    geo = getattr(args, "save_disp16", False) or getattr(args, "save_depth", False) or getattr(args, "save_ply", False)
+    geo = _geometry_requested(args)
     rc = getattr(args, "rectify", None) is not None
     conf_on = conf_requested(args)
     conf_mask = conf_on and (args.conf_min is not None or args.sigma_max_keep is not None)
@@ -579,12 +603,12 @@ def _frame_camera(args, left_path, h, w):
 
 
 def _save_geometry(path, disp, mask, cam, left_rgb, args, log):
-    """The geometry files of the map written to `path`, beside it: <stem>_disp16.png, <stem>_depth16.png, <stem>.ply.  mask: the
-    left-right check's codes (only code-1 pixels kept) or None."""
+    """The geometry files of the map written to `path`, beside it: <stem>_disp16.png, <stem>_depth16.png, <stem>.ply,
+    <stem>_normals.png, <stem>_mesh.ply.  mask: the left-right check's codes (only code-1 pixels kept) or None."""
     import torch
 
     from . import ops
-    from .geometry import write_ply
+    from .geometry import write_mesh_ply, write_ply
     stem = os.path.splitext(path)[0]
     written = []
     if args.save_disp16 or args.save_depth:
@@ -602,6 +626,18 @@ def _save_geometry(path, disp, mask, cam, left_rgb, args, log):
         write_ply(stem + ".ply", points[0, :n].cpu().numpy(), n)
         written.append(stem + ".ply")
         log.info("Save point cloud ({} points) = {}".format(n, stem + ".ply"))
+    if getattr(args, "save_normals", False):
+        _, n8 = ops.surface_normals(disp, cam, mask, args.min_disp, args.max_depth, args.max_jump, normals=False, normals8=True)
+        io.save_png(stem + "_normals.png", n8[0].cpu().numpy())
+        written.append(stem + "_normals.png")
+        log.info("Save normal map = {}".format(stem + "_normals.png"))
+    if getattr(args, "save_mesh", False):
+        rgb = _rgb_on_device(left_rgb, disp.device)
+        mesh = ops.surface_mesh(disp, cam, mask, rgb, args.min_disp, args.max_depth, args.max_jump)
+        n, m = (int(v) for v in mesh.counts[0].cpu())
+        write_mesh_ply(stem + "_mesh.ply", mesh.points[0, :n].cpu().numpy(), n, mesh.faces[0, :m].cpu().numpy(), mesh.vnormals[0, :n].cpu().numpy())
+        written.append(stem + "_mesh.ply")
+        log.info("Save mesh ({} vertices, {} faces) = {}".format(n, m, stem + "_mesh.ply"))
     return written
 
 

@@ -519,6 +519,69 @@ def point_cloud(disp, cameras, mask=None, rgb=None, min_disp=1.0, max_depth=floa
     return points, counts
 
 
+def _max_jump(max_jump):
+    import math
+    if not (math.isfinite(max_jump) and max_jump >= 0):
+        raise ValueError(f"max_jump must be finite and >= 0, got {max_jump}")
+    return float(max_jump)
+
+
+def surface_normals(disp, cameras, mask=None, min_disp=1.0, max_depth=float("inf"), max_jump=1.0, normals=True, normals8=False):
+    """Per-pixel surface normals of disparity maps from the 3 x 3 stencil of the pixel grid (include/lwsnet_hip.h,
+    lws_surface_normals).  disp, cameras, mask, min_disp, max_depth as point_cloud; max_jump: the largest disparity step between
+    two neighbouring pixels of one surface.  Returns (normals float32 [B,3,H,W], normals8 uint8 [B,H,W,3] -- the bytes of an
+    OpenGL-convention normal map), each None where not asked for; an invalid pixel and one without two connected neighbours has
+    the zero normal (128, 128, 128)."""
+    if not (normals or normals8):
+        raise ValueError("surface_normals: ask for at least one of normals, normals8")
+    if cameras is None:
+        raise ValueError("surface_normals needs cameras")
+    d, mask, cam = _geometry_inputs(disp, mask, cameras, min_disp, max_depth)
+    B, _, H, W = d.shape
+    n = torch.empty((B, 3, H, W), device=d.device, dtype=torch.float32) if normals else None
+    n8 = torch.empty((B, H, W, 3), device=d.device, dtype=torch.uint8) if normals8 else None
+    with torch.cuda.device(d.device):
+        _lib.check(_lib.load().lws_surface_normals(_ptr(d), _ptr(mask), _ptr(cam), B, H, W, float(min_disp), float(max_depth),
+                                                   _max_jump(max_jump), _ptr(n), _ptr(n8), _stream()), "lws_surface_normals")
+    return n, n8
+
+
+SurfaceMesh = namedtuple("SurfaceMesh", ["points", "vnormals", "faces", "index", "counts"])
+SurfaceMesh.__doc__ = """What surface_mesh returns: points uint8 [B,H*W,16] (the records of point_cloud), vnormals float32 [B,H*W,4]
+{n.x, n.y, n.z, 0} per vertex (None without normals), faces int32 [B,max(1, 2*(H-1)*(W-1)),3], index int32 [B,1,H,W] (a pixel's
+vertex index or -1; None unless want_index) and counts, an int64 [B,2] device tensor {vertices, faces}: image b's vertices are
+points[b, :counts[b,0]], its faces faces[b, :counts[b,1]]; the rest is unwritten."""
+
+
+def surface_mesh(disp, cameras, mask=None, rgb=None, min_disp=1.0, max_depth=float("inf"), max_jump=1.0, with_normals=True,
+                 want_index=False):
+    """An indexed triangle mesh of disparity maps that does not span depth discontinuities (include/lwsnet_hip.h,
+    lws_surface_mesh): the vertices are point_cloud's records, two triangles per grid cell whose corners are connected (disparity
+    steps <= max_jump).  with_normals: surface_normals runs first and its normals are gathered per vertex.  Returns a SurfaceMesh."""
+    if cameras is None:
+        raise ValueError("surface_mesh needs cameras")
+    d, mask, cam = _geometry_inputs(disp, mask, cameras, min_disp, max_depth)
+    B, _, H, W = d.shape
+    if rgb is not None:
+        rgb = _guide(rgb, d)
+    lib = _lib.load()
+    dev = d.device
+    work = _workspace(lib, "lws_surface_mesh_workspace", dev, B, H)
+    n = torch.empty((B, 3, H, W), device=dev, dtype=torch.float32) if with_normals else None
+    vn = torch.empty((B, H * W, 4), device=dev, dtype=torch.float32) if with_normals else None
+    points = torch.empty((B, H * W, 16), device=dev, dtype=torch.uint8)
+    faces = torch.empty((B, max(1, 2 * (H - 1) * (W - 1)), 3), device=dev, dtype=torch.int32)
+    index = torch.empty((B, 1, H, W), device=dev, dtype=torch.int32) if want_index else None
+    counts = torch.empty((B, 2), device=dev, dtype=torch.int64)
+    args = (B, H, W, float(min_disp), float(max_depth), _max_jump(max_jump))
+    with torch.cuda.device(dev):
+        if with_normals:
+            _lib.check(lib.lws_surface_normals(_ptr(d), _ptr(mask), _ptr(cam), *args, _ptr(n), _ptr(None), _stream()), "lws_surface_normals")
+        _lib.check(lib.lws_surface_mesh(_ptr(d), _ptr(mask), _ptr(rgb), _ptr(cam), _ptr(n), *args, _ptr(work), _ptr(points), _ptr(vn),
+                                        _ptr(faces), _ptr(index), _ptr(counts), _stream()), "lws_surface_mesh")
+    return SurfaceMesh(points, vn, faces, index, counts)
+
+
 SpeckleResult = namedtuple("SpeckleResult", ["disp", "mask", "labels", "counts"])
 SpeckleResult.__doc__ = """What speckle_filter returns: the filtered (filled if asked) maps float32 [B,1,H,W], the uint8 code map (1 kept,
 3 speckle, the input code or 0 for an invalid pixel), labels int32 [B,1,H,W] (None unless want_labels) and counts, an int64
