@@ -338,6 +338,82 @@ int lws_surface_mesh(const float *disp, const uint8_t *mask, const uint8_t *rgb,
                      int W, float min_disp, float max_depth, float max_jump, void *workspace, void *points, void *vnormals,
                      int32_t *faces, int32_t *index, int64_t *counts, void *stream);
 
+/* ---- the road under a disparity map: v-disparity, ground plane, obstacle codes, bird's-eye grid (additive after v8) ---- */
+/* disp, mask, cam, min_disp, max_depth: as lws_depth_maps, with its validity rule, its P = (X, Y, Z) and its u16() unchanged.  One
+ * IEEE operation per step in the order written, no fma: float32 per pixel, float64 for the plane, integers for every sum.  What
+ * crosses lanes or workgroups is an integer add or an integer max, whose order cannot show, so every output is a pure function
+ * of the image: the same bytes in any batch, at any position in it, on every run.  Argument errors -- a null or misaligned
+ * pointer, a bad shape, range or threshold, outputs that overlap each other or an input -- return LWS_ERR_INVALID before any
+ * GPU call.  Every call is a fixed list of launches on `stream` with no device-to-host read, so it can be captured into a
+ * hipGraph.  No scratch memory.
+ * Limits, stated and left as they are: the fit starts from a line without roll.  On synthetic roads a roll of 2 degrees at 96 x 160
+ * and of 1.5 degrees at KITTI size is recovered within three passes; a roll of 3 degrees with a pitch of 2 degrees is not (the
+ * inliers of pass 0 then lie on one side of the image, and the passes do not leave it).  u-disparity, stixels and tracking over
+ * frames are not here. */
+/* Row histograms of a disparity map (the v-disparity image).  sub in 1..16: bins per pixel of disparity; nbins in 1..4096 and
+ * <= 256 * sub (disparities below 256 px: the 64-bit sums of lws_ground_fit stay in range).  Per pixel, d = disp[b,0,y,x]:
+ *   t = floorf(d * (float)sub);   counted = ok_mask && isfinite(d) && d >= min_disp && t < (float)nbins;   q = (int)t
+ * (the compare is on the float, so a huge product is never converted).  hist uint32 [B,H,nbins]: hist[b,y,k] = the counted
+ * pixels of row y with q = k.  Every bin is written, zeros included: the caller does not clear the buffer.  One launch. */
+int lws_vdisparity(const float *disp, const uint8_t *mask, int B, int H, int W, float min_disp, int sub, int nbins, uint32_t *hist,
+                   void *stream);
+/* bytes of device workspace lws_ground_fit needs: 16 64-bit words per image, rounded up to 256 bytes */
+int64_t lws_ground_workspace(int B, int H, int nbins);
+/* The road's plane in disparity space, d = a*x + b*y + c in the map's pixel coordinates: a Hough vote on hist for a start, then
+ * iters + 1 least-squares passes on the map.  hist: what lws_vdisparity wrote for the same disp, mask, min_disp, sub, nbins.
+ * H, W <= 16384.
+ * Step A, integers only.  The candidates are the pairs (yh, qB), yh_lo <= yh <= yh_hi, qb_lo <= qB <= qb_hi: a line through the
+ * horizon row yh (disparity 0) and the bin qB of the bottom row H - 1.  -65536 <= yh_lo (the horizon may lie above the image),
+ * yh_hi <= H - 2, 1 <= qb_lo <= qb_hi < nbins, at most 2^22 candidates; tol_bins in 0..8; min_score >= 0.  With
+ * den = H - 1 - yh, a row y > yh expects the bin k(y) = (2*qB*(y - yh) + den) / (2*den) (integer division of non-negative values);
+ *   score(yh, qB) = sum over y = max(yh + 1, 0) .. H - 1 of hist[b, y, max(k - tol_bins, 0) .. min(k + tol_bins, nbins - 1)]
+ * The winner has the highest score; ties go to the smaller qB, then to the smaller yh.  A best score < min_score: status 1.
+ * Step B.  Q = u16(d) as an integer: the fit is to what a _disp16.png stores.  The plane Q = a*x + b*y + c is held in float64.
+ * Pass 0 takes the winner's line, with den of the winner:
+ *   a = 0.0;   b = (256.0 * qB) / ((double)sub * den);   c = (-b) * yh + 128.0 / sub        (half a bin, for the floor in q)
+ * and the tolerance tol0 pixels; passes 1 .. iters (iters in 0..8) take the plane of the pass before and tol pixels (both
+ * float32, finite, >= 0).  In each pass a pixel is an inlier iff lws_vdisparity counts it and
+ *   fabs((double)Q - ((a*x + b*y) + c)) <= (double)tol * 256.0
+ * and n, Sx, Sy, SQ, Sxx, Sxy, Syy, SxQ, SyQ are the int64 sums of 1, x, y, Q, x*x, x*y, y*y, x*Q, y*Q over the inliers.  Then
+ *   mx = Sx / n;  my = Sy / n;  mq = SQ / n                                (each sum converted to float64, rounded to nearest)
+ *   cxx = Sxx / n - mx*mx;  cxy = Sxy / n - mx*my;  cyy = Syy / n - my*my;  cxq = SxQ / n - mx*mq;  cyq = SyQ / n - my*mq
+ *   det = cxx*cyy - cxy*cxy
+ *   a = (cxq*cyy - cyq*cxy) / det;   b = (cyq*cxx - cxq*cxy) / det;   c = (mq - a*mx) - b*my
+ * n < 3, or not det > 0, or an a, b or c that is not finite: status 2, and no further pass runs.
+ * plane float32 [B][4] = {(float)(a / 256.0), (float)(b / 256.0), (float)(c / 256.0), 0.0f} of the last pass, in pixels of
+ * disparity; four NaN unless the status is 0.  info int32 [B][8] = {status (0 ok, 1 no ground, 2 degenerate), yh, qB and score
+ * of the winner, the inliers of the last pass that ran (0 with status 1), 0, 0, 0}.
+ * workspace: lws_ground_workspace(B, H, nbins) bytes, 8-byte aligned, contents undefined before and after: the call clears what
+ * it uses.  3 + 2 * (iters + 1) launches: clear, vote (one packed 64-bit atomic max of (score << 32) | ~candidate per workgroup, the
+ * candidates numbered by qB, then yh), seed, and per pass the sums (wave sums, then 64-bit atomic adds) and the solve. */
+int lws_ground_fit(const float *disp, const uint8_t *mask, const uint32_t *hist, int B, int H, int W, float min_disp, int sub, int nbins,
+                   int yh_lo, int yh_hi, int qb_lo, int qb_hi, int tol_bins, int min_score, float tol0, float tol, int iters,
+                   void *workspace, float *plane, int32_t *info, void *stream);
+/* Height over the plane and a code per pixel.  cam is required; plane float32 [B][4] in device memory, one row per image, as
+ * lws_ground_fit writes it; ground_tol and max_height in metres, finite, 0 <= ground_tol <= max_height.  With (a, b, c) = plane[b],
+ * valid and z of lws_depth_maps, in float32:
+ *   dp = (a*(float)x + b*(float)y) + c
+ *   nx = a*fx;   ny = b*fy;   nz = (a*cx + b*cy) + c;   len = sqrtf((nx*nx + ny*ny) + nz*nz)
+ *   h  = ((d - dp) * z) / len
+ * h is the signed distance of the pixel's point from the plane nx*X + ny*Y + nz*Z = fb, positive on the camera's side; the camera
+ * stands fb / len above the plane.  Codes, tested in this order: 0 invalid (not a valid pixel); 5 no plane (a, b, c or h is not
+ * finite); 1 ground (fabsf(h) <= ground_tol); 4 below (h < 0); 2 obstacle (h <= max_height); 3 overhead.
+ * height float32 [B,1,H,W] (NULL: skipped) = h, 0.0f for the codes 0 and 5; codes uint8 [B,1,H,W] (NULL: skipped; not both);
+ * counts int64 [B][6] (NULL: skipped) = the pixels of each code.  One launch, plus one that clears counts when it is given. */
+int lws_ground_classify(const float *disp, const uint8_t *mask, const float *cam, const float *plane, int B, int H, int W, float min_disp,
+                        float max_depth, float ground_tol, float max_height, float *height, uint8_t *codes, int64_t *counts, void *stream);
+/* An occupancy grid seen from above.  codes and height: what lws_ground_classify wrote (height may be NULL when hmax is).  A pixel
+ * takes part iff it is valid (the rule of lws_depth_maps without a mask) and its code is below 6 with bit codes[p] of code_bits
+ * (0..63) set.  Its cell, with X and Z of lws_depth_maps; x_min finite, cell finite and > 0, in metres; Gx, Gz in 1..4096:
+ *   u = (X - x_min) / cell;   v = Z / cell;   kept iff u >= 0 && u < (float)Gx && v >= 0 && v < (float)Gz
+ *   ix = (int)floorf(u);   iz = (int)floorf(v)          (after the compares: a huge or NaN coordinate is never converted)
+ * count uint32 [B,Gz,Gx] (NULL: skipped) = the pixels of the cell; hmax float32 [B,Gz,Gx] (NULL: skipped; not both) = the largest
+ * height in the cell, +0.0f for an empty one -- the unsigned maximum of the heights' bit patterns, which is their maximum because
+ * they are positive: a code_bits with one of the bits 0, 1, 4, 5 set is refused when hmax is requested.  The call clears both
+ * grids itself.  Two launches: clear, scatter (atomic add and atomic unsigned max). */
+int lws_bev_grid(const float *disp, const float *cam, const uint8_t *codes, const float *height, int B, int H, int W, float min_disp,
+                 float max_depth, int code_bits, float x_min, float cell, int Gx, int Gz, uint32_t *count, float *hmax, void *stream);
+
 /* ---- speckle filter: connected components of a disparity map (additive after v8) ---- */
 /* bytes of device workspace lws_speckle_filter needs for this geometry: per pixel one int32 parent word and one int32 size word
  * (8 bytes), plus three int32 per row for the counts, each part rounded up to 256 bytes */

@@ -58,6 +58,11 @@ PROTOTYPES = {
     "lws_surface_normals": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp]),
     "lws_surface_mesh_workspace": (ctypes.c_int64, [_i, _i]),
     "lws_surface_mesh": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lws_vdisparity": (_i, [_vp, _vp, _i, _i, _i, _f, _i, _i, _vp, _vp]),
+    "lws_ground_workspace": (ctypes.c_int64, [_i, _i, _i]),
+    "lws_ground_fit": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp]),
+    "lws_ground_classify": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
+    "lws_bev_grid": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _f, _f, _i, _i, _vp, _vp, _vp]),
     "lws_speckle_workspace": (ctypes.c_int64, [_i, _i, _i]),
     "lws_speckle_filter": (_i, [_vp, _vp, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lws_wmedian_filter": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),

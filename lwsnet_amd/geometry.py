@@ -77,6 +77,32 @@ def camera_rows(cameras, B):
     return np.stack([c.check().row() for c in cams])
 
 
+@dataclass(frozen=True)
+class GroundPlane:
+    """The road of lwsnet_amd.ops.ground_fit as the camera sees it: its `height` over the road in metres, `pitch_deg` (> 0: the
+    camera looks down, the horizon lies above the principal point), `roll_deg` (> 0: the road's normal leans towards +x) and the
+    unit `normal` (nx, ny, nz) of the plane nx*X + ny*Y + nz*Z = height in camera coordinates (x right, y down, z forward)."""
+    height: float
+    pitch_deg: float
+    roll_deg: float
+    normal: tuple
+
+    @classmethod
+    def from_plane(cls, plane, camera):
+        """plane: a row {a, b, c, ...} of ground_fit's output, the road's disparity d = a*x + b*y + c in the pixel coordinates of
+        `camera` (a Camera, cropped as the map is).  Host float64: (nx, ny, nz) = (a*fx, b*fy, a*cx + b*cy + c), the plane is
+        nx*X + ny*Y + nz*Z = fb.  None for a plane that is not finite (no ground, degenerate) or has no normal."""
+        a, b, c = (float(v) for v in np.asarray(plane, np.float64).reshape(-1)[:3])
+        cam = camera.check()
+        n = np.array([a * float(cam.fx), b * float(cam.fy), a * float(cam.cx) + b * float(cam.cy) + c])
+        length = float(np.sqrt(n @ n))
+        if not (np.isfinite(length) and length > 0.0):
+            return None
+        n = n / length
+        return cls(float(cam.fb) / length, float(np.degrees(np.arctan2(n[2], np.hypot(n[0], n[1])))),
+                   float(np.degrees(np.arctan2(n[0], n[1]))), tuple(float(v) for v in n))
+
+
 def _read_kitti_values(path):
     """key -> list of floats for every `key: v v v` line of a KITTI calibration file (lines without numbers are skipped)."""
     mats = {}

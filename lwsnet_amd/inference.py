@@ -40,6 +40,13 @@ points need a camera: `--calib` (a KITTI calibration file, or in directory mode 
 (default 1), so no triangle spans a depth discontinuity.  Both need a camera and the sequential mode, as `--save_ply` does, and keep
 the pixels it keeps.
 
+`--ground [--ground_tol M] [--max_height M] [--save_ground]`: the road under each map, on the device (lwsnet_amd.ops.ground: lws_vdisparity,
+lws_ground_fit, lws_ground_classify, lws_bev_grid) -- one log line with the fit's status, the camera's height over the road, its pitch
+and roll, the share of inliers and the pixels per code (invalid, ground, obstacle, overhead, below, no plane).  `--save_ground` also
+writes `<stem>_ground.png`, the codes through a fixed six-colour table averaged with the left image's grey, and `<stem>_bev.png`, the
+largest obstacle height per 0.2 m cell of a grid 40 m wide and 60 m deep as rint(min(h / max_height, 1) * 255), row 0 the farthest.
+Both need a camera and the sequential mode, as `--save_ply` does, and take the code map it takes.
+
 `--speckle SIZE [--speckle_diff D] [--speckle_fill]`: the connected blobs of at most SIZE pixels (4-neighbours joined when their
 disparities differ by <= D, default 1) are removed from the stage maps on the device (lws_speckle_filter) before the colour, 16-bit
 and point-cloud files are written, and each colour file gets a grey code map `<stem>_sp.png` beside it (kept 255, speckle 64, the
@@ -138,7 +145,7 @@ def add_conf_arguments(p):
 
 def _geometry_requested(args):
     """One of the files _save_geometry writes is asked for."""
-    return any(getattr(args, flag, False) for flag in ("save_disp16", "save_depth", "save_ply", "save_normals", "save_mesh"))
+    return any(getattr(args, flag, False) for flag in ("save_disp16", "save_depth", "save_ply", "save_normals", "save_mesh", "ground", "save_ground"))
 
 
 def conf_requested(args):
@@ -244,6 +251,16 @@ def add_geometry_arguments(p):
                    help="write <stem>_mesh.ply, a binary triangle mesh of the kept pixels with vertex normals; needs a camera")
     p.add_argument("--max_jump", type=float, default=argparse.SUPPRESS, metavar="J",
                    help="normals and mesh: the largest disparity step between two neighbouring pixels of one surface (default 1)")
+    # the ground flags likewise
+    p.add_argument("--ground", action="store_true", default=argparse.SUPPRESS,
+                   help="fit the road's plane and log camera height, pitch, roll and the pixels per code for each map; needs a camera")
+    p.add_argument("--save_ground", action="store_true", default=argparse.SUPPRESS,
+                   help="--ground, and write <stem>_ground.png (the codes in colour over the left image's grey) and <stem>_bev.png (the "
+                        "obstacles' heights seen from above)")
+    p.add_argument("--ground_tol", type=float, default=argparse.SUPPRESS, metavar="M",
+                   help="ground: a pixel within M metres of the plane is road (default 0.2)")
+    p.add_argument("--max_height", type=float, default=argparse.SUPPRESS, metavar="M",
+                   help="ground: a pixel up to M metres above the road is an obstacle, above that overhead (default 3)")
 
 
 def _list_pairs(args):
@@ -271,8 +288,13 @@ def check_geometry_arguments(p, args):
     from .geometry import Camera
     args.save_normals, args.save_mesh = getattr(args, "save_normals", False), getattr(args, "save_mesh", False)
     args.max_jump = getattr(args, "max_jump", 1.0)
+    args.save_ground = getattr(args, "save_ground", False)
+    args.ground = getattr(args, "ground", False) or args.save_ground
+    args.ground_tol, args.max_height = getattr(args, "ground_tol", 0.2), getattr(args, "max_height", 3.0)
     surface = args.save_normals or args.save_mesh
     outputs = args.save_disp16 or args.save_depth or args.save_ply or surface
+    if not (np.isfinite(args.ground_tol) and np.isfinite(args.max_height) and 0 <= args.ground_tol <= args.max_height):
+        p.error(f"--ground_tol and --max_height must be finite with 0 <= ground_tol <= max_height, got {args.ground_tol} and {args.max_height}")
     if not (np.isfinite(args.max_jump) and args.max_jump >= 0):
         p.error(f"--max_jump must be finite and >= 0, got {args.max_jump}")
     if not (np.isfinite(args.min_disp) and args.min_disp > 0):
@@ -281,6 +303,10 @@ def check_geometry_arguments(p, args):
         p.error(f"--max_depth must be > 0, got {args.max_depth}")
     if (args.save_depth or args.save_ply or surface) and args.calib is None and args.camera is None and getattr(args, "rectify", None) is None:
         p.error("--save_depth, --save_ply, --save_normals and --save_mesh need a camera: --calib PATH or --camera FX FY CX CY BASELINE")
+    if args.ground and args.calib is None and args.camera is None and getattr(args, "rectify", None) is None:
+        p.error("--ground and --save_ground need a camera: --calib PATH or --camera FX FY CX CY BASELINE")
+    if args.ground and args.workers > 0:
+        p.error("--ground / --save_ground run in the sequential mode only: use --workers 0")
     if outputs and args.workers > 0:
         p.error("--save_disp16 / --save_depth / --save_ply / --save_normals / --save_mesh run in the sequential mode only: use --workers 0")
     if args.camera is not None:
@@ -604,7 +630,8 @@ def _frame_camera(args, left_path, h, w):
 
 def _save_geometry(path, disp, mask, cam, left_rgb, args, log):
     """The geometry files of the map written to `path`, beside it: <stem>_disp16.png, <stem>_depth16.png, <stem>.ply,
-    <stem>_normals.png, <stem>_mesh.ply.  mask: the left-right check's codes (only code-1 pixels kept) or None."""
+    <stem>_normals.png, <stem>_mesh.ply, <stem>_ground.png, <stem>_bev.png; with --ground the road's log line.  mask: the left-right
+    check's codes (only code-1 pixels kept) or None."""
     import torch
 
     from . import ops
@@ -638,6 +665,50 @@ def _save_geometry(path, disp, mask, cam, left_rgb, args, log):
         write_mesh_ply(stem + "_mesh.ply", mesh.points[0, :n].cpu().numpy(), n, mesh.faces[0, :m].cpu().numpy(), mesh.vnormals[0, :n].cpu().numpy())
         written.append(stem + "_mesh.ply")
         log.info("Save mesh ({} vertices, {} faces) = {}".format(n, m, stem + "_mesh.ply"))
+    if getattr(args, "ground", False):
+        written.extend(_ground(stem, disp, mask, cam, left_rgb, args, log))
+    return written
+
+
+GROUND_COLOURS = np.array([[0, 0, 0], [0, 200, 0], [255, 0, 0], [0, 128, 255], [255, 0, 255], [128, 128, 128]], np.uint8)   # by code
+
+
+def ground_to_rgb(codes, left_rgb):
+    """<stem>_ground.png: the colour of each pixel's code (GROUND_COLOURS: invalid black, ground green, obstacle red, overhead blue,
+    below magenta, no plane grey) averaged with the left image's grey, (77 r + 150 g + 29 b + 128) >> 8; integers throughout."""
+    rgb = np.asarray(left_rgb).astype(np.uint32)
+    grey = (77 * rgb[..., 0] + 150 * rgb[..., 1] + 29 * rgb[..., 2] + 128) >> 8
+    return ((GROUND_COLOURS[np.asarray(codes)].astype(np.uint32) + grey[..., None] + 1) >> 1).astype(np.uint8)
+
+
+def bev_to_u8(hmax, max_height):
+    """<stem>_bev.png: [Gz,Gx] largest heights -> rint(min(h / max_height, 1) * 255), 0 for an empty cell, row 0 the farthest."""
+    h = np.asarray(hmax, np.float64)[::-1]
+    with np.errstate(all="ignore"):
+        v = np.where(h > 0, np.minimum(h / float(max_height), 1.0), 0.0)
+    return np.rint(v * 255.0).astype(np.uint8)
+
+
+def _ground(stem, disp, mask, cam, left_rgb, args, log):
+    """--ground: the road of one map (ops.ground) as a log line; --save_ground: <stem>_ground.png and <stem>_bev.png."""
+    from . import ops
+    from .geometry import GroundPlane
+    res = ops.ground(disp, cam, mask, args.min_disp, args.max_depth, maxdisp=args.max_disparity, ground_tol=args.ground_tol,
+                     max_height=args.max_height)
+    info, counts = res.info[0].cpu().tolist(), res.counts[0].cpu().tolist()
+    gp = GroundPlane.from_plane(res.plane[0].cpu().numpy(), cam) if info[0] == 0 else None
+    pose = "height = {:.3f} m, pitch = {:.2f} deg, roll = {:.2f} deg".format(gp.height, gp.pitch_deg, gp.roll_deg) if gp else "no plane"
+    valid = max(sum(counts[1:]), 1)
+    log.info("Ground: status = {}, {}, inliers = {:.4f} of the valid pixels, {}".format(
+        ops.GROUND_STATUS[info[0]], pose, info[4] / valid, ", ".join("{} = {}".format(n, c) for n, c in zip(ops.GROUND_CODES, counts))))
+    written = []
+    if getattr(args, "save_ground", False):
+        left = left_rgb[0].cpu().numpy() if not isinstance(left_rgb, np.ndarray) else left_rgb
+        io.save_png(stem + "_ground.png", ground_to_rgb(res.codes[0, 0].cpu().numpy(), left))
+        with open(stem + "_bev.png", "wb") as f:
+            f.write(io.encode_png_gray(bev_to_u8(res.bev_hmax[0].cpu().numpy(), args.max_height)))
+        written += [stem + "_ground.png", stem + "_bev.png"]
+        log.info("Save ground codes = {}, bird's-eye heights = {}".format(stem + "_ground.png", stem + "_bev.png"))
     return written
 
 

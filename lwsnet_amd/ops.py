@@ -582,6 +582,190 @@ def surface_mesh(disp, cameras, mask=None, rgb=None, min_disp=1.0, max_depth=flo
     return SurfaceMesh(points, vn, faces, index, counts)
 
 
+GROUND_STATUS = ("ok", "no ground", "degenerate")                     # info[b, 0] of ground_fit
+GROUND_CODES = ("invalid", "ground", "obstacle", "overhead", "below", "no plane")      # the codes of ground_classify
+
+
+def _int_in(name, v, lo, hi):
+    if isinstance(v, bool) or int(v) != v or not lo <= v <= hi:
+        raise ValueError(f"{name} must be an integer in {lo} .. {hi}, got {v}")
+    return int(v)
+
+
+def _finite_nonneg(name, v):
+    import math
+    if not (math.isfinite(v) and v >= 0):
+        raise ValueError(f"{name} must be finite and >= 0, got {v}")
+    return float(v)
+
+
+def _hist_args(min_disp, sub, nbins, maxdisp):
+    """(min_disp, sub, nbins) of vdisparity / ground_fit; nbins None: min(1024, sub * maxdisp)."""
+    import math
+    if not (math.isfinite(min_disp) and min_disp > 0):
+        raise ValueError(f"min_disp must be finite and > 0, got {min_disp}")
+    sub = _int_in("sub", sub, 1, 16)
+    if nbins is None:
+        nbins = min(1024, sub * _int_in("maxdisp", maxdisp, 1, 1 << 20), 256 * sub)
+    return float(min_disp), sub, _int_in("nbins", nbins, 1, min(4096, 256 * sub))
+
+
+def vdisparity(disp, mask=None, min_disp=1.0, sub=4, nbins=None, maxdisp=192):
+    """The v-disparity image of disparity maps: per row, a histogram of the disparities in bins of 1 / sub pixels
+    (include/lwsnet_hip.h, lws_vdisparity).  disp [B,1,H,W] float32; mask: None or the uint8 code map (only code-1 pixels count);
+    nbins: None for min(1024, sub * maxdisp).  Returns hist uint32 [B,H,nbins]."""
+    min_disp, sub, nbins = _hist_args(min_disp, sub, nbins, maxdisp)
+    d = _disp_map(disp, "disp")
+    mask = _code_map(mask, d)
+    B, _, H, W = d.shape
+    hist = torch.empty((B, H, nbins), device=d.device, dtype=torch.uint32)
+    with torch.cuda.device(d.device):
+        _lib.check(_lib.load().lws_vdisparity(_ptr(d), _ptr(mask), B, H, W, min_disp, sub, nbins, _ptr(hist), _stream()), "lws_vdisparity")
+    return hist
+
+
+def ground_fit(disp, hist, mask=None, min_disp=1.0, sub=4, yh_range=None, qb_range=None, tol_bins=1, min_score=0, tol0=1.0, tol=1.0,
+               iters=3):
+    """The road's plane d = a*x + b*y + c of disparity maps: a Hough vote on their v-disparity image `hist` (vdisparity with the same
+    mask, min_disp and sub), then iters + 1 least-squares passes on the maps (include/lwsnet_hip.h, lws_ground_fit).  yh_range: the
+    horizon rows tried, (lo, hi), None for H/4 .. 3H/4; qb_range: the bottom row's bins tried, None for the upper two thirds of the
+    bins; tol0 / tol: the inlier tolerance in pixels of pass 0 (against the voted line) and of the later passes.  Returns
+    (plane float32 [B,4] = {a, b, c, 0}, NaN unless info[b,0] is 0; info int32 [B,8] = {status, yh, qB, score, inliers, 0, 0, 0}),
+    both on the device; status: GROUND_STATUS."""
+    if not isinstance(hist, torch.Tensor) or hist.dtype != torch.uint32 or hist.dim() != 3:
+        raise ValueError("hist must be the uint32 [B,H,nbins] tensor vdisparity returns")
+    nbins = int(hist.shape[2])
+    min_disp, sub, nbins = _hist_args(min_disp, sub, nbins, 1)
+    H = int(hist.shape[1])
+    if yh_range is None:
+        yh_hi = min(3 * H // 4, H - 2)
+        yh_range = (min(H // 4, yh_hi), yh_hi)
+    if qb_range is None:
+        qb_range = (max(1, nbins // 3), nbins - 1)
+    yh_lo, yh_hi = (_int_in("yh_range", v, -65536, H - 2) for v in yh_range)
+    qb_lo, qb_hi = (_int_in("qb_range", v, 1, nbins - 1) for v in qb_range)
+    if yh_lo > yh_hi or qb_lo > qb_hi:
+        raise ValueError(f"yh_range {tuple(yh_range)} and qb_range {tuple(qb_range)} must each be (lo, hi) with lo <= hi")
+    if (yh_hi - yh_lo + 1) * (qb_hi - qb_lo + 1) > 1 << 22:
+        raise ValueError("yh_range x qb_range holds more than 2^22 candidates")
+    tol_bins, iters = _int_in("tol_bins", tol_bins, 0, 8), _int_in("iters", iters, 0, 8)
+    min_score = _int_in("min_score", min_score, 0, 2 ** 31 - 1)
+    tol0, tol = _finite_nonneg("tol0", tol0), _finite_nonneg("tol", tol)
+    d = _disp_map(disp, "disp")
+    mask = _code_map(mask, d)
+    B, _, _, W = d.shape
+    if tuple(hist.shape[:2]) != (B, d.shape[2]) or hist.device != d.device:
+        raise ValueError(f"hist must be [{B},{d.shape[2]},nbins] on {d.device}; got {tuple(hist.shape)} on {hist.device}")
+    hist = hist.contiguous()
+    lib = _lib.load()
+    work = _workspace(lib, "lws_ground_workspace", d.device, B, H, nbins)
+    plane = torch.empty((B, 4), device=d.device, dtype=torch.float32)
+    info = torch.empty((B, 8), device=d.device, dtype=torch.int32)
+    with torch.cuda.device(d.device):
+        _lib.check(lib.lws_ground_fit(_ptr(d), _ptr(mask), _ptr(hist), B, H, W, min_disp, sub, nbins, yh_lo, yh_hi, qb_lo, qb_hi, tol_bins,
+                                      min_score, tol0, tol, iters, _ptr(work), _ptr(plane), _ptr(info), _stream()), "lws_ground_fit")
+    return plane, info
+
+
+def _heights(ground_tol, max_height):
+    ground_tol, max_height = _finite_nonneg("ground_tol", ground_tol), _finite_nonneg("max_height", max_height)
+    if ground_tol > max_height:
+        raise ValueError(f"ground_tol {ground_tol} must be <= max_height {max_height}")
+    return ground_tol, max_height
+
+
+def ground_classify(disp, cameras, plane, mask=None, min_disp=1.0, max_depth=float("inf"), ground_tol=0.2, max_height=3.0, height=True,
+                    codes=True, counts=True):
+    """The height of every valid pixel's point over the plane and a code per pixel (include/lwsnet_hip.h, lws_ground_classify;
+    GROUND_CODES).  plane: the float32 [B,4] device tensor ground_fit returns; ground_tol, max_height in metres.  Returns
+    (height float32 [B,1,H,W], codes uint8 [B,1,H,W], counts int64 [B,6]), each None where not asked for."""
+    if not (height or codes):
+        raise ValueError("ground_classify: ask for at least one of height, codes")
+    if cameras is None:
+        raise ValueError("ground_classify needs cameras")
+    ground_tol, max_height = _heights(ground_tol, max_height)
+    d, mask, cam = _geometry_inputs(disp, mask, cameras, min_disp, max_depth)
+    B, _, H, W = d.shape
+    if not isinstance(plane, torch.Tensor) or plane.dtype != torch.float32 or tuple(plane.shape) != (B, 4) or plane.device != d.device:
+        raise ValueError(f"plane must be a float32 {(B, 4)} tensor on {d.device} (what ground_fit returns)")
+    plane = plane.contiguous()
+    h = torch.empty(d.shape, device=d.device, dtype=torch.float32) if height else None
+    c = torch.empty(d.shape, device=d.device, dtype=torch.uint8) if codes else None
+    n = torch.empty((B, 6), device=d.device, dtype=torch.int64) if counts else None
+    with torch.cuda.device(d.device):
+        _lib.check(_lib.load().lws_ground_classify(_ptr(d), _ptr(mask), _ptr(cam), _ptr(plane), B, H, W, float(min_disp), float(max_depth),
+                                                   ground_tol, max_height, _ptr(h), _ptr(c), _ptr(n), _stream()), "lws_ground_classify")
+    return h, c, n
+
+
+def _bev_args(code_bits, x_min, cell, grid, hmax):
+    import math
+    code_bits = _int_in("code_bits", code_bits, 0, 63)
+    if hmax and code_bits & 0x33:
+        raise ValueError(f"code_bits {code_bits} selects a code other than 2 and 3, whose heights are not positive: ask for no hmax")
+    if not math.isfinite(x_min):
+        raise ValueError(f"x_min must be finite, got {x_min}")
+    if not (math.isfinite(cell) and cell > 0):
+        raise ValueError(f"cell must be finite and > 0, got {cell}")
+    if len(grid) != 2:
+        raise ValueError(f"grid must be (Gx, Gz), got {grid}")
+    return code_bits, float(x_min), float(cell), _int_in("grid", grid[0], 1, 4096), _int_in("grid", grid[1], 1, 4096)
+
+
+def bev_grid(disp, cameras, codes, height=None, min_disp=1.0, max_depth=float("inf"), code_bits=1 << 2, x_min=-20.0, cell=0.2,
+             grid=(200, 300), count=True, hmax=True):
+    """An occupancy grid seen from above (include/lwsnet_hip.h, lws_bev_grid): the valid pixels whose code's bit is set in code_bits
+    (default: obstacles), dropped into cells of `cell` metres; grid = (Gx, Gz): Gx cells across from x_min, Gz cells deep from the
+    camera.  codes, height: what ground_classify returns.  Returns (count uint32 [B,Gz,Gx], hmax float32 [B,Gz,Gx] -- the largest
+    height in the cell, 0 for an empty one), each None where not asked for."""
+    if not (count or hmax):
+        raise ValueError("bev_grid: ask for at least one of count, hmax")
+    if cameras is None:
+        raise ValueError("bev_grid needs cameras")
+    if hmax and height is None:
+        raise ValueError("bev_grid: hmax needs height")
+    code_bits, x_min, cell, Gx, Gz = _bev_args(code_bits, x_min, cell, grid, hmax)
+    d, _, cam = _geometry_inputs(disp, None, cameras, min_disp, max_depth)
+    B, _, H, W = d.shape
+    if not isinstance(codes, torch.Tensor) or codes.dtype != torch.uint8 or tuple(codes.shape) != tuple(d.shape) or codes.device != d.device:
+        raise ValueError(f"codes must be a uint8 {tuple(d.shape)} tensor on {d.device} (what ground_classify returns)")
+    codes = codes.contiguous()
+    if height is not None:
+        height = _disp_map(height, "height")
+        if tuple(height.shape) != tuple(d.shape) or height.device != d.device:
+            raise ValueError(f"height must be {tuple(d.shape)} on {d.device}")
+    n = torch.empty((B, Gz, Gx), device=d.device, dtype=torch.uint32) if count else None
+    top = torch.empty((B, Gz, Gx), device=d.device, dtype=torch.float32) if hmax else None
+    with torch.cuda.device(d.device):
+        _lib.check(_lib.load().lws_bev_grid(_ptr(d), _ptr(cam), _ptr(codes), _ptr(height if hmax else None), B, H, W, float(min_disp),
+                                            float(max_depth), code_bits, x_min, cell, Gx, Gz, _ptr(n), _ptr(top), _stream()), "lws_bev_grid")
+    return n, top
+
+
+GroundResult = namedtuple("GroundResult", ["hist", "plane", "info", "height", "codes", "counts", "bev_count", "bev_hmax"])
+GroundResult.__doc__ = """What ground returns, all on the device: hist uint32 [B,H,nbins] (vdisparity), plane float32 [B,4] and info
+int32 [B,8] (ground_fit), height float32 [B,1,H,W], codes uint8 [B,1,H,W] and counts int64 [B,6] (ground_classify), bev_count uint32
+and bev_hmax float32 [B,Gz,Gx] (bev_grid)."""
+
+
+def ground(disp, cameras, mask=None, min_disp=1.0, max_depth=float("inf"), maxdisp=192, sub=4, nbins=None, yh_range=None, qb_range=None,
+           tol_bins=1, min_score=0, tol0=1.0, tol=1.0, iters=3, ground_tol=0.2, max_height=3.0, code_bits=1 << 2, x_min=-20.0, cell=0.2,
+           grid=(200, 300)):
+    """Where the road is and what stands on it: vdisparity, ground_fit, ground_classify and bev_grid on the current stream, nothing
+    read back in between.  Defaults: bins of a quarter pixel up to min(1024, 4 * maxdisp), horizon rows H/4 .. 3H/4, three passes
+    after the voted line at 1 px, ground within 0.2 m, obstacles up to 3 m, a grid of 0.2 m cells 40 m wide and 60 m deep.
+    Returns a GroundResult; lwsnet_amd.geometry.GroundPlane turns a plane row into camera height, pitch and roll."""
+    if cameras is None:
+        raise ValueError("ground needs cameras")
+    _heights(ground_tol, max_height)
+    _bev_args(code_bits, x_min, cell, grid, True)
+    hist = vdisparity(disp, mask, min_disp, sub, nbins, maxdisp)
+    plane, info = ground_fit(disp, hist, mask, min_disp, sub, yh_range, qb_range, tol_bins, min_score, tol0, tol, iters)
+    height, codes, counts = ground_classify(disp, cameras, plane, mask, min_disp, max_depth, ground_tol, max_height)
+    n, top = bev_grid(disp, cameras, codes, height, min_disp, max_depth, code_bits, x_min, cell, grid)
+    return GroundResult(hist, plane, info, height, codes, counts, n, top)
+
+
 SpeckleResult = namedtuple("SpeckleResult", ["disp", "mask", "labels", "counts"])
 SpeckleResult.__doc__ = """What speckle_filter returns: the filtered (filled if asked) maps float32 [B,1,H,W], the uint8 code map (1 kept,
 3 speckle, the input code or 0 for an invalid pixel), labels int32 [B,1,H,W] (None unless want_labels) and counts, an int64
