@@ -6,7 +6,8 @@
  * entry point names the reference lines it replaces.  Plain pointers and sizes
  * only; all tensors are float32, contiguous, NCHW, in DEVICE memory unless the
  * parameter is called `host`.  `stream` is a hipStream_t passed as void*
- * (NULL = the default stream).  Calls are asynchronous on that stream.
+ * (NULL = the default stream).  Calls are asynchronous on that stream, with one exception: at batch 1 lws_forward and
+ * lws_forward_conf may hold the calling thread at their three cross-stream joins (option "host_joins" below).
  *
  * Every function returns 0 on success or a negative lws_status; the message of
  * the last failure on the calling thread is lws_last_error().
@@ -599,6 +600,26 @@ int lws_photometric(const float *const disp[4], int nmaps, const uint8_t *left, 
  *   "fuse_ref_last"  -1 (default: batch 1 only) / 0 / 1: refinement2's last depthwise-separable block (dilation 1), the 32 -> 1
  *                    convolution and "+ pred3" in one launch (k_ref_dws_last: the block recomputed on the one-pixel ring the
  *                    convolution needs) instead of k_ref_dws + k_ref_last
+ *   "host_joins"     -1 (default: automatic) / 0 / 1: the three joins of lws_forward -- the 1/4 feature map before stage 2, the
+ *                    1/2 map before stage 3, refinement1_left before the refinement -- are resolved by the HOST: it polls
+ *                    hipEventQuery on the side stream's event, and once it has seen the event complete it queues nothing (every
+ *                    later launch on the caller's stream is then ordered behind the side work).  A wait queued on an event that
+ *                    is not yet complete costs the chain 5 to 7 us even when the side work finished long before the queue gets
+ *                    there, which is every join of a batch-1 throughput loop.  0 = hipStreamWaitEvent always.  Automatic = on
+ *                    when the batch is 1 AND the calling thread's previous forward ran on this same handle: a thread that
+ *                    feeds several handles in turn is never held (its first forward, and every forward after a change of
+ *                    handle, queues its waits).  Ignored (no polling) with "side_streams" = 0, which has no joins, and while
+ *                    `stream` is being captured into a hipGraph, where the waits are the graph's edges.  The capture check
+ *                    looks at `stream` only: a caller that captures ANOTHER stream of the process in global capture mode
+ *                    while it runs eager forwards (hipEventQuery is not allowed then), must set 0 for the duration.
+ *                    WHAT CHANGES FOR THE CALLER: with host joins on, lws_forward / lws_forward_conf may hold the
+ *                    calling thread until the device has reached roughly the middle of THAT forward (the end of the side
+ *                    stream's refinement1_left); it stays asynchronous with respect to the forward's tail, the refinement.
+ *                    lws_pool sets 0 on its workers' clones whatever the source handle says: a worker issues for a queue of jobs.
+ *   "host_join_budget_us"  900 (default), 0..1000000: how long a join polls before it falls back to hipStreamWaitEvent; 0 =
+ *                    every join falls back at once.  After the first fallback the forward's remaining joins queue without
+ *                    polling, so one forward spins for one budget at the most.  The budget never changes a result, only
+ *                    where the host waits.
  *   "device"         the HIP device the handle belongs to; settable only before lws_finalize / lws_reserve allocate
  * Unknown names and out-of-range values return LWS_ERR_INVALID.
  * hipGraph capture: lws_reserve first (nothing may allocate while capturing), then capture lws_forward on a non-default
@@ -662,6 +683,12 @@ int lws_clock_read(lws_handle h, double *ghz);
  * poison for fresh memory.  Must NOT be called while `stream` is being captured into a hipGraph (a replay would poison the
  * slab under whatever runs then), nor while a forward of this handle is in flight on another stream. */
 int lws_debug_fill_workspace(lws_handle h, uint32_t word, void *stream);
+/* Measurement hook (additive after v8): what the joins of lws_forward / lws_forward_conf did on this handle since the last reset.
+ * out (optional) receives 3 x 4 values, joins in chain order (the 1/4 map, the 1/2 map, refinement1_left): {joins the host saw
+ * complete, joins queued with hipStreamWaitEvent, host nanoseconds spent polling in total, the longest single poll}.  reset != 0
+ * clears the counters afterwards.  Host-side only: no GPU call, any current device.  Forwards with "side_streams" = 0 count
+ * nothing (they have no joins). */
+int lws_join_stats(lws_handle h, int64_t *out, int reset);
 
 /* ---- several forwards in flight (no counterpart in the reference: inference.py:105-109 is one thread, one stream) ---- */
 /* A second handle for the same model on the same device: shares src's (read-only) parameter slab, owns its workspace,

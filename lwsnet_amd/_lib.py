@@ -78,6 +78,7 @@ PROTOTYPES = {
     "lws_clock_stamp": (_i, [_vp, _i]),
     "lws_clock_read": (_i, [_vp, ctypes.POINTER(ctypes.c_double)]),
     "lws_debug_fill_workspace": (_i, [_vp, ctypes.c_uint32, _vp]),
+    "lws_join_stats": (_i, [_vp, c_int64_p, _i]),
     "lws_clone": (_i, [_vp, ctypes.POINTER(_vp)]),
     "lws_pool_create": (_i, [_vp, _i, _i, ctypes.POINTER(_vp)]),
     "lws_pool_destroy": (_i, [_vp]),

@@ -115,6 +115,8 @@ static int *option_slot(lws_ctx *h, const char *name)
                                                      {"fuse_last1", &h->opt.fuse_last1},
                                                      {"fork2_after", &h->opt.fork2_after},
                                                      {"fuse_ref_last", &h->opt.fuse_ref_last},
+                                                     {"host_joins", &h->opt.host_joins},
+                                                     {"host_join_budget_us", &h->opt.host_join_budget_us},
                                                      {"device", &h->device}};
     for (auto &e : tab)
         if (strcmp(e.name, name) == 0) return e.slot;
@@ -131,8 +133,10 @@ int lws_set_option(lws_handle h, const char *name, int value)
         LWS_CHECK_ARG(value >= 0 && value <= 7, "lws_set_option: split_bf16 is a bit mask in 0..7 (got %d)", value);
     else if (strcmp(name, "fuse_first") == 0)
         LWS_CHECK_ARG(value >= 0 && value <= 3, "lws_set_option: fuse_first is a bit mask in 0..3 (got %d)", value);
-    else if (strcmp(name, "ref_pipe") == 0 || strcmp(name, "fuse_ref_last") == 0)
+    else if (strcmp(name, "ref_pipe") == 0 || strcmp(name, "fuse_ref_last") == 0 || strcmp(name, "host_joins") == 0)
         LWS_CHECK_ARG(value >= -1 && value <= 1, "lws_set_option: %s is out of range (got %d)", name, value);
+    else if (strcmp(name, "host_join_budget_us") == 0)
+        LWS_CHECK_ARG(value >= 0 && value <= 1000000, "lws_set_option: host_join_budget_us must be in 0..1000000 (got %d)", value);
     else if (strcmp(name, "ref_chunk_mb") == 0)
         LWS_CHECK_ARG(value >= 0 && value <= 4096, "lws_set_option: ref_chunk_mb must be in 0..4096 (got %d)", value);
     else if (strcmp(name, "device") == 0) {
@@ -212,6 +216,21 @@ int lws_profile_read_class(lws_handle h, int kernel_class, float *ms_out, int ca
         ++n;
     }
     *count = n;
+    return LWS_OK;
+}
+
+int lws_join_stats(lws_handle h, int64_t *out, int reset)
+{
+    LWS_CHECK_ARG(h, "lws_join_stats: null handle");
+    for (int i = 0; i < 3 && out != nullptr; ++i) {
+        const lws_join_stat &j = h->join_stat[i];
+        out[4 * i] = j.host;
+        out[4 * i + 1] = j.queued;
+        out[4 * i + 2] = j.wait_ns;
+        out[4 * i + 3] = j.max_ns;
+    }
+    if (reset)
+        for (lws_join_stat &j : h->join_stat) j = lws_join_stat();
     return LWS_OK;
 }
 

@@ -233,6 +233,12 @@ struct Net2d {
 
 }  // namespace lws
 
+// one join of lws_forward since the last reset: how often the host saw the event complete / a wait was queued, and the
+// host time spent polling (both outcomes)
+struct lws_join_stat {
+    int64_t host = 0, queued = 0, wait_ns = 0, max_ns = 0;
+};
+
 struct lws_prof_rec {
     int kc;
     hipEvent_t t0, t1;
@@ -252,7 +258,10 @@ struct lws_ctx {
         int fork2_after = -1;      // the second fork: 0 = behind stage 1's last Conv3D layer, k = behind its k-th middle layer, -1 = automatic (the last middle layer)
         int fuse_ref_last = -1;    // refinement2's last block + the 32 -> 1 convolution + pred3 in one launch: -1 = batch 1 only, 0 / 1
         int ref_chunk_mb = 72;     // refinement in chunks of pairs whose maps are at most this many MB each (0 = one chunk); see refine_chunk (lws_forward.hip)
+        int host_joins = -1;       // the three joins of lws_forward resolved by the host (hipEventQuery) instead of a wait on the caller's queue: -1 = batch 1 and the thread's previous forward on this same handle, 0 / 1; see host_join (lws_forward.hip)
+        int host_join_budget_us = 900;    // how long one join polls before it falls back to hipStreamWaitEvent (0 = at once)
     } opt;
+    lws_join_stat join_stat[3];              // lws_join_stats: the joins of lws_forward in chain order (f4, f2, refinement1_left)
     unsigned prof_mask = 0;                  // kernel classes being timed in the current call
     unsigned prof_mask_cfg = 0;              // ... as configured by lws_profile_enable
     int prof_every = 1;                      // lws_profile_sample: lws_forward records events on every n-th call only

@@ -1,6 +1,7 @@
 // Running the network: the workspace layout, the built-in profiler's event pairs, the launch plan of LWSNet.forward
 // (models/models.py:106-164 of the reference) and the entry points that execute it on a handle.
 #include <algorithm>
+#include <chrono>
 
 #include "lws_common.h"
 
@@ -492,6 +493,51 @@ static int ensure_streams(lws_ctx *h)
     return LWS_OK;
 }
 
+// A join of lws_forward: everything queued on `st` from here on runs after `ev` (recorded on the side stream) is complete.
+// hipStreamWaitEvent on an event that is NOT complete when the host calls it puts a wait on st's queue, which costs the chain
+// 5 to 7 us even when the event has long completed by the time the queue reaches it; on an event that IS complete the runtime
+// queues nothing (tools/micro/event_cost.hip; profiles/NOTES.md, "host-resolved joins").  host: poll the event first.  Once the
+// host has seen it complete, every later launch on st is ordered behind the side work and nothing is queued at all.  The poll is
+// bounded by option "host_join_budget_us"; when that runs out (or is 0) the wait is queued as before, so the budget decides
+// where the host spends its time and never what is computed -- and `host` is cleared: the caller's stream is backed up, the
+// forward's later joins would run out as well, so they queue at once and one forward spins for one budget at the most.
+// Never under hipGraph capture (the caller passes host = false): an event query is illegal there, and a captured graph needs
+// the wait as an edge.
+static int host_join(lws_ctx *h, int which, hipEvent_t ev, hipStream_t st, bool &host)
+{
+    lws_join_stat &js = h->join_stat[which];
+    if (host && h->opt.host_join_budget_us > 0) {
+        typedef std::chrono::steady_clock clk;
+        const clk::time_point t0 = clk::now(), t_end = t0 + std::chrono::microseconds(h->opt.host_join_budget_us);
+        clk::time_point t = t0;
+        hipError_t e;
+        do {
+            e = hipEventQuery(ev);
+            t = clk::now();
+        } while (e == hipErrorNotReady && t < t_end);
+        const int64_t ns = std::chrono::duration_cast<std::chrono::nanoseconds>(t - t0).count();
+        js.wait_ns += ns;
+        js.max_ns = std::max(js.max_ns, ns);
+        if (e == hipSuccess) {
+            ++js.host;
+            return LWS_OK;
+        }
+        if (e != hipErrorNotReady) {
+            set_error("hipEventQuery failed at join %d of the forward: %s", which, hipGetErrorString(e));
+            return LWS_ERR_HIP;
+        }
+        host = false;
+    }
+    ++js.queued;
+    LWS_HIP(hipStreamWaitEvent(st, ev, 0));
+    return LWS_OK;
+}
+
+// Which handle ran the latest forward on this thread (automatic "host_joins"): a thread that feeds several handles in turn
+// (bench.py --streams N) must not be held at a join of one while the others have nothing queued.  Compared, never
+// dereferenced: a handle destroyed since, or a new one at its address, costs at most one forward on the other plan.
+static thread_local const lws_ctx *tl_last_forward = nullptr;
+
 }  // namespace lws
 
 using namespace lws;
@@ -620,7 +666,8 @@ static int run_forward(lws_ctx *h, const char *what, const float *left, const fl
     //   caller's stream: feature head -> stage 1 -> stage 2 -> stage 3 -> refinement1_disp, refinement2
     //   fork 1, behind the feature head:                    conv5 (-> the 1/4 map of stage 2)
     //   fork 2, behind stage 1's last middle Conv3D layer:  conv6 + classif1 (-> the 1/2 map of stage 3), refinement1_left
-    //   joins: the 1/4 map before stage 2, the 1/2 map before stage 3, refinement1_left before the refinement.
+    //   joins: the 1/4 map before stage 2, the 1/2 map before stage 3, refinement1_left before the refinement (host_join:
+    //   at batch 1 the host resolves them, option "host_joins").
     // refinement1_left is HBM-bound work beside stages 2 and 3, whose MFMA kernels keep their weights in registers and do not
     // mind; beside stage 1 it would slow k_conv3d_mid16, which streams its weights from L2.
     const bool multi = h->opt.side_streams != 0;
@@ -630,6 +677,12 @@ static int run_forward(lws_ctx *h, const char *what, const float *left, const fl
     }
     hipStream_t side = multi ? h->side : st;
     const bool ext = multi && !capturing;       // forks ride on their producer kernel's completion signal (StopArm)
+    // automatic: batch 1 only -- from batch 2 up a queued wait is under 0.3 % of the step and blocking the caller buys nothing --
+    // and only when this thread's previous forward ran on this same handle (one handle, one stream: the host has nothing else
+    // to issue while it waits; rotating handles measured 2,374 against 2,612 pairs/s with the host held at the joins)
+    const bool same_handle = tl_last_forward == h;
+    tl_last_forward = h;
+    bool hj = !capturing && (h->opt.host_joins >= 0 ? h->opt.host_joins != 0 : B == 1 && same_handle);
     float *f8 = h->ws + L.fe_f8, *f4 = h->ws + L.fe_f4, *f2 = h->ws + L.fe_f2;
     rc = feature_head(h, left, right, B, B, H, W, L, f8, st, Fork{multi ? h->ev_feat[0] : nullptr, 0, ext});   // models.py:110-111
     if (rc) return rc;
@@ -649,7 +702,10 @@ static int run_forward(lws_ctx *h, const char *what, const float *left, const fl
     const bool ref_evaluates = (h->opt.fuse_first & 1) && ref_first_dws_can_fuse(h->net2d.r1[1][0], 1);
     StageMap map[3] = {{pred_out[0]}, {pred_out[1]}, {pred_out[2]}};
     for (int s = 0; s < 3; ++s) {                                                                   // :115-156
-        if (multi && s > 0) LWS_HIP(hipStreamWaitEvent(st, h->ev_feat[s], 0));    // joins: f4 before stage 2, f2 before stage 3
+        if (multi && s > 0) {                                                     // joins: f4 before stage 2, f2 before stage 3
+            rc = host_join(h, s - 1, h->ev_feat[s], st, hj);
+            if (rc) return rc;
+        }
         const bool defer = co == nullptr && defers(h, s, B, H, W, s < 2 || ref_evaluates);
         const StageDims d = stage_dims(h, s, H, W);
         bool fused;
@@ -679,7 +735,10 @@ static int run_forward(lws_ctx *h, const char *what, const float *left, const fl
             if (rc) return rc;
         }
     }
-    if (multi) LWS_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
+    if (multi) {
+        rc = host_join(h, 2, h->ev_join, st, hj);
+        if (rc) return rc;
+    }
     return refine_rest(h, map[2], B, H, W, L, pred_out[3], st);                                        // :159-162
 }
 

@@ -193,6 +193,8 @@ int lws_pool_create(lws_handle src, int workers, int flags, lws_pool_handle *out
         p->workers.push_back(h);
         // one stream = one hardware queue per worker unless the caller asks for the per-handle side streams too
         h->opt.side_streams = (flags & LWS_POOL_SIDE_STREAMS) ? 1 : 0;
+        // a worker issues for a queue of jobs: it never blocks inside a forward (with LWS_POOL_SIDE_STREAMS its joins stay on the queue)
+        h->opt.host_joins = 0;
         // several forwards share the CUs: no residency cap on k_conv3d_mid8q (a capped workgroup holds a third of a CU's LDS
         // idle, which the kernels of the other workers' forwards could use)
         h->mid8_balance = 0;
