@@ -339,7 +339,7 @@ int lws_surface_mesh(const float *disp, const uint8_t *mask, const uint8_t *rgb,
                      int W, float min_disp, float max_depth, float max_jump, void *workspace, void *points, void *vnormals,
                      int32_t *faces, int32_t *index, int64_t *counts, void *stream);
 
-/* ---- the road under a disparity map: v-disparity, ground plane, obstacle codes, bird's-eye grid (additive after v8) ---- */
+/* ---- the road under a disparity map: v-disparity, ground plane, obstacle codes, bird's-eye grid, stixels (additive after v8) ---- */
 /* disp, mask, cam, min_disp, max_depth: as lws_depth_maps, with its validity rule, its P = (X, Y, Z) and its u16() unchanged.  One
  * IEEE operation per step in the order written, no fma: float32 per pixel, float64 for the plane, integers for every sum.  What
  * crosses lanes or workgroups is an integer add or an integer max, whose order cannot show, so every output is a pure function
@@ -349,8 +349,7 @@ int lws_surface_mesh(const float *disp, const uint8_t *mask, const uint8_t *rgb,
  * hipGraph.  No scratch memory.
  * Limits, stated and left as they are: the fit starts from a line without roll.  On synthetic roads a roll of 2 degrees at 96 x 160
  * and of 1.5 degrees at KITTI size is recovered within three passes; a roll of 3 degrees with a pitch of 2 degrees is not (the
- * inliers of pass 0 then lie on one side of the image, and the passes do not leave it).  u-disparity, stixels and tracking over
- * frames are not here. */
+ * inliers of pass 0 then lie on one side of the image, and the passes do not leave it).  Tracking over frames is not here. */
 /* Row histograms of a disparity map (the v-disparity image).  sub in 1..16: bins per pixel of disparity; nbins in 1..4096 and
  * <= 256 * sub (disparities below 256 px: the 64-bit sums of lws_ground_fit stay in range).  Per pixel, d = disp[b,0,y,x]:
  *   t = floorf(d * (float)sub);   counted = ok_mask && isfinite(d) && d >= min_disp && t < (float)nbins;   q = (int)t
@@ -414,6 +413,35 @@ int lws_ground_classify(const float *disp, const uint8_t *mask, const float *cam
  * grids itself.  Two launches: clear, scatter (atomic add and atomic unsigned max). */
 int lws_bev_grid(const float *disp, const float *cam, const uint8_t *codes, const float *height, int B, int H, int W, float min_disp,
                  float max_depth, int code_bits, float x_min, float cell, int Gx, int Gz, uint32_t *count, float *hmax, void *stream);
+/* Stixels and the u-disparity of the obstacle columns: per strip of `width` columns, where the road ends, how far away what stands
+ * there is and how tall.  codes and height: what lws_ground_classify wrote for the same map, both required; there is no mask (an
+ * invalid pixel has code 0).  H, W <= 16384; width in 1..64; sub in 1..16 and nbins in 1..4096, <= 256 * sub, as for lws_vdisparity;
+ * tol_bins in 0..8; min_count >= 1; min_row >= 1; max_gap >= 0; layers in 1..4; code_bits in 0..63 with none of the bits 0, 1, 4, 5
+ * (the maximum below relies on positive heights, as hmax of lws_bev_grid does).  S = ceil(W / width) strips; strip s holds the columns
+ * x0 = s*width .. x1 = min(x0 + width, W) - 1 of every row.  Per image and strip:
+ *   take(p), d = disp[p]:  valid (the rule of lws_depth_maps without a mask) && codes[p] < 6 with bit codes[p] of code_bits set &&
+ *            t = floorf(d * (float)sub) < (float)nbins;   q = (int)t (the compare is on the float);   Q = (int)u16(d) as in lws_ground_fit
+ *   U[k] = the taking pixels of the strip with q == k.  udisp uint32 [B,S,nbins] (NULL: skipped) = U, every bin written.
+ * Layers j = 0 .. layers - 1, nearest first, kmax_0 = nbins - 1; layer j searches the bins 0 .. kmax_j:
+ *   Wn(k)  = the sum of U[max(k - tol_bins, 0) .. min(k + tol_bins, kmax_j)]
+ *   k_near = the largest k <= kmax_j with Wn(k) >= min_count; none (or kmax_j < 0): this layer and all later ones are empty, k_peak = -1
+ *   k_peak = the bin of the largest U within max(k_near - tol_bins, 0) .. min(k_near + tol_bins, kmax_j); the larger k wins a tie
+ *   kmax_{j+1} = k_peak - tol_bins - 1, whatever follows
+ *   members: the taking pixels with |q - k_peak| <= tol_bins and q <= kmax_j;   r[y] = the members in row y;   f[y] = r[y] >= min_row
+ *   y_base = the largest flagged row; none: the slot is a hole, {0, -1, -1, k_peak} and zeros, and the next layer still runs (slots
+ *            are not compacted)
+ *   y_top: y_top = y_base, gap = 0; for y = y_base - 1 down to 0: a flagged row sets y_top = y, gap = 0; any other row does ++gap,
+ *            and the walk stops once gap > max_gap
+ *   over the members in the rows y_top .. y_base: n = their count, SQ = the int64 sum of Q, hb = the unsigned maximum of the bit
+ *            patterns of height
+ *   d_st = (float)(((double)SQ / (double)n) / 256.0);   z = fb / d_st;   xc = (float)(x0 + x1) * 0.5f;   X = ((xc - cx) * z) / fx
+ * rows int32 [B,S,layers,4] = {n, y_top, y_base, k_peak}; vals float32 [B,S,layers,4] = {d_st, z, X, the height of bits hb}; an empty
+ * slot is {0, -1, -1, k_peak or -1} and four +0.0f.  Every element is written: the caller clears nothing.  No workspace.  One
+ * launch, one workgroup per strip and image: the histogram and r[y] live in LDS (adds), n, SQ and hb are wave and LDS reductions
+ * (adds, unsigned max); no global atomic. */
+int lws_stixels(const float *disp, const float *cam, const uint8_t *codes, const float *height, int B, int H, int W, float min_disp,
+                float max_depth, int code_bits, int width, int sub, int nbins, int tol_bins, int min_count, int min_row, int max_gap,
+                int layers, int32_t *rows, float *vals, uint32_t *udisp, void *stream);
 
 /* ---- speckle filter: connected components of a disparity map (additive after v8) ---- */
 /* bytes of device workspace lws_speckle_filter needs for this geometry: per pixel one int32 parent word and one int32 size word

@@ -63,6 +63,7 @@ PROTOTYPES = {
     "lws_ground_fit": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp]),
     "lws_ground_classify": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "lws_bev_grid": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _f, _f, _i, _i, _vp, _vp, _vp]),
+    "lws_stixels": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "lws_speckle_workspace": (ctypes.c_int64, [_i, _i, _i]),
     "lws_speckle_filter": (_i, [_vp, _vp, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lws_wmedian_filter": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),

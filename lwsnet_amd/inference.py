@@ -47,6 +47,13 @@ writes `<stem>_ground.png`, the codes through a fixed six-colour table averaged 
 largest obstacle height per 0.2 m cell of a grid 40 m wide and 60 m deep as rint(min(h / max_height, 1) * 255), row 0 the farthest.
 Both need a camera and the sequential mode, as `--save_ply` does, and take the code map it takes.
 
+`--stixels [--stixel_width N] [--stixel_layers N] [--save_stixels]`: the stixel world of each map, on the device (lwsnet_amd.ops.stixels:
+lws_stixels on the codes and heights of `--ground`, which it implies) -- per strip of N columns (default 8) and per layer (default 2,
+nearest first) the obstacle that stands there; one log line with the number of stixels and the nearest one's depth z and lateral
+position X.  `--save_stixels` also writes `<stem>_stixels.png`, the left image's grey with each stixel's rectangle tinted by a fixed
+depth ramp (near red, far blue, 60 m and beyond the same), and `<stem>_stixels.csv`, one line per stixel:
+strip,layer,x0,x1,y_top,y_base,n,disparity,z,x,height.  Camera and mode as for `--ground`.
+
 `--speckle SIZE [--speckle_diff D] [--speckle_fill]`: the connected blobs of at most SIZE pixels (4-neighbours joined when their
 disparities differ by <= D, default 1) are removed from the stage maps on the device (lws_speckle_filter) before the colour, 16-bit
 and point-cloud files are written, and each colour file gets a grey code map `<stem>_sp.png` beside it (kept 255, speckle 64, the
@@ -145,7 +152,7 @@ def add_conf_arguments(p):
 
 def _geometry_requested(args):
     """One of the files _save_geometry writes is asked for."""
-    return any(getattr(args, flag, False) for flag in ("save_disp16", "save_depth", "save_ply", "save_normals", "save_mesh", "ground", "save_ground"))
+    return any(getattr(args, flag, False) for flag in ("save_disp16", "save_depth", "save_ply", "save_normals", "save_mesh", "ground", "save_ground", "stixels", "save_stixels"))
 
 
 def conf_requested(args):
@@ -261,6 +268,13 @@ def add_geometry_arguments(p):
                    help="ground: a pixel within M metres of the plane is road (default 0.2)")
     p.add_argument("--max_height", type=float, default=argparse.SUPPRESS, metavar="M",
                    help="ground: a pixel up to M metres above the road is an obstacle, above that overhead (default 3)")
+    # the stixel flags likewise
+    p.add_argument("--stixels", action="store_true", default=argparse.SUPPRESS,
+                   help="--ground, and log the number of stixels (obstacles per column strip) and the nearest one's depth and lateral position")
+    p.add_argument("--save_stixels", action="store_true", default=argparse.SUPPRESS,
+                   help="--stixels, and write <stem>_stixels.png (the stixels tinted by depth over the left image's grey) and <stem>_stixels.csv")
+    p.add_argument("--stixel_width", type=int, default=argparse.SUPPRESS, metavar="N", help="stixels: columns per strip, 1 .. 64 (default 8)")
+    p.add_argument("--stixel_layers", type=int, default=argparse.SUPPRESS, metavar="N", help="stixels: obstacles per strip, nearest first, 1 .. 4 (default 2)")
 
 
 def _list_pairs(args):
@@ -289,7 +303,10 @@ def check_geometry_arguments(p, args):
     args.save_normals, args.save_mesh = getattr(args, "save_normals", False), getattr(args, "save_mesh", False)
     args.max_jump = getattr(args, "max_jump", 1.0)
     args.save_ground = getattr(args, "save_ground", False)
-    args.ground = getattr(args, "ground", False) or args.save_ground
+    args.save_stixels = getattr(args, "save_stixels", False)
+    args.stixels = getattr(args, "stixels", False) or args.save_stixels
+    args.stixel_width, args.stixel_layers = getattr(args, "stixel_width", 8), getattr(args, "stixel_layers", 2)
+    args.ground = getattr(args, "ground", False) or args.save_ground or args.stixels
     args.ground_tol, args.max_height = getattr(args, "ground_tol", 0.2), getattr(args, "max_height", 3.0)
     surface = args.save_normals or args.save_mesh
     outputs = args.save_disp16 or args.save_depth or args.save_ply or surface
@@ -303,6 +320,14 @@ def check_geometry_arguments(p, args):
         p.error(f"--max_depth must be > 0, got {args.max_depth}")
     if (args.save_depth or args.save_ply or surface) and args.calib is None and args.camera is None and getattr(args, "rectify", None) is None:
         p.error("--save_depth, --save_ply, --save_normals and --save_mesh need a camera: --calib PATH or --camera FX FY CX CY BASELINE")
+    if not 1 <= args.stixel_width <= 64:
+        p.error(f"--stixel_width must be in 1 .. 64, got {args.stixel_width}")
+    if not 1 <= args.stixel_layers <= 4:
+        p.error(f"--stixel_layers must be in 1 .. 4, got {args.stixel_layers}")
+    if args.stixels and args.calib is None and args.camera is None and getattr(args, "rectify", None) is None:
+        p.error("--stixels and --save_stixels need a camera: --calib PATH or --camera FX FY CX CY BASELINE")
+    if args.stixels and args.workers > 0:
+        p.error("--stixels / --save_stixels run in the sequential mode only: use --workers 0")
     if args.ground and args.calib is None and args.camera is None and getattr(args, "rectify", None) is None:
         p.error("--ground and --save_ground need a camera: --calib PATH or --camera FX FY CX CY BASELINE")
     if args.ground and args.workers > 0:
@@ -630,7 +655,8 @@ def _frame_camera(args, left_path, h, w):
 
 def _save_geometry(path, disp, mask, cam, left_rgb, args, log):
     """The geometry files of the map written to `path`, beside it: <stem>_disp16.png, <stem>_depth16.png, <stem>.ply,
-    <stem>_normals.png, <stem>_mesh.ply, <stem>_ground.png, <stem>_bev.png; with --ground the road's log line.  mask: the left-right
+    <stem>_normals.png, <stem>_mesh.ply, <stem>_ground.png, <stem>_bev.png, <stem>_stixels.png, <stem>_stixels.csv; with --ground the
+    road's log line, with --stixels the stixels'.  mask: the left-right
     check's codes (only code-1 pixels kept) or None."""
     import torch
 
@@ -666,7 +692,10 @@ def _save_geometry(path, disp, mask, cam, left_rgb, args, log):
         written.append(stem + "_mesh.ply")
         log.info("Save mesh ({} vertices, {} faces) = {}".format(n, m, stem + "_mesh.ply"))
     if getattr(args, "ground", False):
-        written.extend(_ground(stem, disp, mask, cam, left_rgb, args, log))
+        ground = []
+        written.extend(_ground(stem, disp, mask, cam, left_rgb, args, log, ground))
+        if getattr(args, "stixels", False):
+            written.extend(_stixels(stem, disp, cam, ground[0], left_rgb, args, log))
     return written
 
 
@@ -689,12 +718,15 @@ def bev_to_u8(hmax, max_height):
     return np.rint(v * 255.0).astype(np.uint8)
 
 
-def _ground(stem, disp, mask, cam, left_rgb, args, log):
-    """--ground: the road of one map (ops.ground) as a log line; --save_ground: <stem>_ground.png and <stem>_bev.png."""
+def _ground(stem, disp, mask, cam, left_rgb, args, log, result=None):
+    """--ground: the road of one map (ops.ground) as a log line; --save_ground: <stem>_ground.png and <stem>_bev.png.  result: a list
+    that receives the GroundResult."""
     from . import ops
     from .geometry import GroundPlane
     res = ops.ground(disp, cam, mask, args.min_disp, args.max_depth, maxdisp=args.max_disparity, ground_tol=args.ground_tol,
                      max_height=args.max_height)
+    if result is not None:
+        result.append(res)
     info, counts = res.info[0].cpu().tolist(), res.counts[0].cpu().tolist()
     gp = GroundPlane.from_plane(res.plane[0].cpu().numpy(), cam) if info[0] == 0 else None
     pose = "height = {:.3f} m, pitch = {:.2f} deg, roll = {:.2f} deg".format(gp.height, gp.pitch_deg, gp.roll_deg) if gp else "no plane"
@@ -709,6 +741,72 @@ def _ground(stem, disp, mask, cam, left_rgb, args, log):
             f.write(io.encode_png_gray(bev_to_u8(res.bev_hmax[0].cpu().numpy(), args.max_height)))
         written += [stem + "_ground.png", stem + "_bev.png"]
         log.info("Save ground codes = {}, bird's-eye heights = {}".format(stem + "_ground.png", stem + "_bev.png"))
+    return written
+
+
+STIXEL_COLOUR_DEPTH = 60.0          # metres: the far end of the depth ramp of <stem>_stixels.png
+
+
+def stixels_to_rgb(rows, vals, left_rgb, width, max_depth_for_colour):
+    """<stem>_stixels.png: the left image's grey, (77 r + 150 g + 29 b + 128) >> 8, with each stixel's rectangle x0 .. x1 by y_top ..
+    y_base averaged with the colour of its depth: t = min(z / max_depth_for_colour, 1), (r, g, b) = rint(255 * (1 - t, 2 min(t, 1 - t),
+    t)) -- near red, far blue.  rows, vals: one image's [S,layers,4]; the layers are drawn far to near, so the nearest shows."""
+    rgb = np.asarray(left_rgb).astype(np.uint32)
+    grey = (77 * rgb[..., 0] + 150 * rgb[..., 1] + 29 * rgb[..., 2] + 128) >> 8
+    out = np.repeat(grey[..., None], 3, axis=2)
+    rows, vals = np.asarray(rows), np.asarray(vals, np.float64)
+    W = grey.shape[1]
+    for layer in range(rows.shape[1] - 1, -1, -1):
+        for s in range(rows.shape[0]):
+            n, y_top, y_base, _ = (int(v) for v in rows[s, layer])
+            if n <= 0:
+                continue
+            t = min(max(vals[s, layer, 1] / float(max_depth_for_colour), 0.0), 1.0)
+            colour = np.rint(255.0 * np.array([1.0 - t, 2.0 * min(t, 1.0 - t), t])).astype(np.uint32)
+            x0, x1 = s * width, min((s + 1) * width, W) - 1
+            out[y_top:y_base + 1, x0:x1 + 1] = (colour + grey[y_top:y_base + 1, x0:x1 + 1, None] + 1) >> 1
+    return out.astype(np.uint8)
+
+
+STIXEL_CSV_HEADER = "strip,layer,x0,x1,y_top,y_base,n,disparity,z,x,height"
+
+
+def stixels_to_csv(rows, vals, width, W):
+    """<stem>_stixels.csv as a string: STIXEL_CSV_HEADER, then one line per non-empty slot of one image's [S,layers,4] rows and vals,
+    strips left to right, layers nearest first; the four values with six decimals."""
+    rows, vals = np.asarray(rows), np.asarray(vals)
+    lines = [STIXEL_CSV_HEADER]
+    for s in range(rows.shape[0]):
+        for layer in range(rows.shape[1]):
+            n, y_top, y_base, _ = (int(v) for v in rows[s, layer])
+            if n > 0:
+                x0, x1 = s * width, min((s + 1) * width, W) - 1
+                lines.append(",".join([str(v) for v in (s, layer, x0, x1, y_top, y_base, n)] + ["{:.6f}".format(float(v)) for v in vals[s, layer]]))
+    return "\n".join(lines) + "\n"
+
+
+def _stixels(stem, disp, cam, ground, left_rgb, args, log):
+    """--stixels: the stixels of one map (ops.stixels on the codes and heights of its GroundResult) as a log line; --save_stixels:
+    <stem>_stixels.png and <stem>_stixels.csv."""
+    from . import ops
+    res = ops.stixels(disp, cam, ground.codes, ground.height, args.min_disp, args.max_depth, width=args.stixel_width,
+                      maxdisp=args.max_disparity, layers=args.stixel_layers)
+    rows, vals = res.rows[0].cpu().numpy(), res.vals[0].cpu().numpy()
+    found = rows[..., 0] > 0
+    nearest = "none"
+    if found.any():
+        s, layer = np.unravel_index(np.argmin(np.where(found, vals[..., 1], np.inf)), found.shape)
+        nearest = "z = {:.2f} m, X = {:.2f} m".format(float(vals[s, layer, 1]), float(vals[s, layer, 2]))
+    log.info("Stixels: {} in {} strips of {} columns x {} layers, nearest: {}".format(int(found.sum()), rows.shape[0], args.stixel_width,
+                                                                                     rows.shape[1], nearest))
+    written = []
+    if getattr(args, "save_stixels", False):
+        left = left_rgb[0].cpu().numpy() if not isinstance(left_rgb, np.ndarray) else left_rgb
+        io.save_png(stem + "_stixels.png", stixels_to_rgb(rows, vals, left, args.stixel_width, STIXEL_COLOUR_DEPTH))
+        with open(stem + "_stixels.csv", "w", encoding="ascii", newline="") as f:
+            f.write(stixels_to_csv(rows, vals, args.stixel_width, disp.shape[3]))
+        written += [stem + "_stixels.png", stem + "_stixels.csv"]
+        log.info("Save stixels = {}, {}".format(stem + "_stixels.png", stem + "_stixels.csv"))
     return written
 
 

@@ -766,6 +766,59 @@ def ground(disp, cameras, mask=None, min_disp=1.0, max_depth=float("inf"), maxdi
     return GroundResult(hist, plane, info, height, codes, counts, n, top)
 
 
+StixelResult = namedtuple("StixelResult", ["rows", "vals", "udisp"])
+StixelResult.__doc__ = """What stixels returns, all on the device, S = ceil(W / width) strips: rows int32 [B,S,layers,4] = {n, y_top,
+y_base, k_peak}, vals float32 [B,S,layers,4] = {disparity, z, X, height}, udisp uint32 [B,S,nbins] (None unless asked for).  A slot
+with n = 0 is empty: y_top = y_base = -1 and four zeros."""
+
+
+def _stixel_args(min_disp, code_bits, width, maxdisp, sub, nbins, tol_bins, min_count, min_row, max_gap, layers):
+    """The validated scalar arguments of stixels, defaults resolved: min_count None is 2 * width, min_row None max(1, width // 2)."""
+    min_disp, sub, nbins = _hist_args(min_disp, sub, nbins, maxdisp)
+    code_bits = _int_in("code_bits", code_bits, 0, 63)
+    if code_bits & 0x33:
+        raise ValueError(f"code_bits {code_bits} selects a code other than 2 and 3, whose heights are not positive")
+    width = _int_in("width", width, 1, 64)
+    top = 2 ** 31 - 1
+    min_count = _int_in("min_count", 2 * width if min_count is None else min_count, 1, top)
+    min_row = _int_in("min_row", max(1, width // 2) if min_row is None else min_row, 1, top)
+    return (min_disp, code_bits, width, sub, nbins, _int_in("tol_bins", tol_bins, 0, 8), min_count, min_row,
+            _int_in("max_gap", max_gap, 0, top), _int_in("layers", layers, 1, 4))
+
+
+def stixels(disp, cameras, codes, height, min_disp=1.0, max_depth=float("inf"), code_bits=1 << 2, width=8, maxdisp=192, sub=4, nbins=None,
+            tol_bins=1, min_count=None, min_row=None, max_gap=2, layers=2, udisp=False):
+    """The stixel world of disparity maps (include/lwsnet_hip.h, lws_stixels): per strip of `width` columns and per layer, nearest
+    first, the obstacle that stands there -- its rows, disparity, depth z, lateral position X and height -- from the u-disparity
+    histogram of the strip's pixels whose code's bit is set in code_bits (default: obstacles).  codes, height: what ground_classify
+    (or ground) returns for the same maps.  Bins of 1 / sub pixels, nbins None for min(1024, sub * maxdisp) as in vdisparity; a layer is
+    the nearest bin whose window of +-tol_bins holds min_count pixels (None: 2 * width); a row belongs to it with min_row members
+    (None: max(1, width // 2)), and it ends above the first max_gap + 1 rows without.  Returns a StixelResult."""
+    if cameras is None:
+        raise ValueError("stixels needs cameras")
+    min_disp, code_bits, width, sub, nbins, tol_bins, min_count, min_row, max_gap, layers = _stixel_args(
+        min_disp, code_bits, width, maxdisp, sub, nbins, tol_bins, min_count, min_row, max_gap, layers)
+    d, _, cam = _geometry_inputs(disp, None, cameras, min_disp, max_depth)
+    B, _, H, W = d.shape
+    if H > 16384 or W > 16384:
+        raise ValueError(f"disp is {H}x{W}: stixels takes maps up to 16384x16384")
+    if not isinstance(codes, torch.Tensor) or codes.dtype != torch.uint8 or tuple(codes.shape) != tuple(d.shape) or codes.device != d.device:
+        raise ValueError(f"codes must be a uint8 {tuple(d.shape)} tensor on {d.device} (what ground_classify returns)")
+    codes = codes.contiguous()
+    height = _disp_map(height, "height")
+    if tuple(height.shape) != tuple(d.shape) or height.device != d.device:
+        raise ValueError(f"height must be {tuple(d.shape)} on {d.device}")
+    S = -(-W // width)
+    rows = torch.empty((B, S, layers, 4), device=d.device, dtype=torch.int32)
+    vals = torch.empty((B, S, layers, 4), device=d.device, dtype=torch.float32)
+    u = torch.empty((B, S, nbins), device=d.device, dtype=torch.uint32) if udisp else None
+    with torch.cuda.device(d.device):
+        _lib.check(_lib.load().lws_stixels(_ptr(d), _ptr(cam), _ptr(codes), _ptr(height), B, H, W, min_disp, float(max_depth), code_bits, width,
+                                           sub, nbins, tol_bins, min_count, min_row, max_gap, layers, _ptr(rows), _ptr(vals), _ptr(u), _stream()),
+                   "lws_stixels")
+    return StixelResult(rows, vals, u)
+
+
 SpeckleResult = namedtuple("SpeckleResult", ["disp", "mask", "labels", "counts"])
 SpeckleResult.__doc__ = """What speckle_filter returns: the filtered (filled if asked) maps float32 [B,1,H,W], the uint8 code map (1 kept,
 3 speckle, the input code or 0 for an invalid pixel), labels int32 [B,1,H,W] (None unless want_labels) and counts, an int64
