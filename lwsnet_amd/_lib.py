@@ -1,4 +1,10 @@
-"""ctypes binding of liblwsnet_hip.so (include/lwsnet_hip.h).
+"""ctypes binding of liblwsnet_hip.so.  include/lwsnet_hip.h is the only statement of the C ABI: PROTOTYPES and the LWS_*
+constants are read from it when this module is imported (tests/test_abi_cpu.py has a C++ compiler check the reading).
+
+The header cannot say which pointers are host pointers, so every pointer but `const char *` is c_void_p: the 20 host-pointer
+parameters -- lws_set_tensor's data and shape, the mean / std arrays, lws_profile_read*, lws_clock_read, lws_join_stats, the
+handle out-parameters and lws_create's config -- carry no POINTER(...) type.  ctypes converts byref(x), arrays and typed pointer
+objects to c_void_p parameters, so callers pass what they always passed.
 
 There is no CPU fallback: if the library is missing or a call fails this module raises.
 """
@@ -6,11 +12,11 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblwsnet_hip.so")
-
-LWS_OK, LWS_ERR_INVALID, LWS_ERR_HIP, LWS_ERR_STATE, LWS_ERR_NOMEM = 0, -1, -2, -3, -4
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "lwsnet_hip.h")
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
@@ -22,79 +28,83 @@ class LwsConfig(ctypes.Structure):
                 ("feature_fp16", ctypes.c_int32), ("interp_align_mode", ctypes.c_int32)]
 
 
-# name -> (restype, argtypes); exactly the functions include/lwsnet_hip.h declares
-_vp, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-PROTOTYPES = {
-    "lws_abi_version": (_i, []),
-    "lws_last_error": (ctypes.c_char_p, []),
-    "lws_device_count": (_i, []),
-    "lws_create": (_i, [ctypes.POINTER(LwsConfig), ctypes.POINTER(_vp)]),
-    "lws_destroy": (_i, [_vp]),
-    "lws_set_tensor": (_i, [_vp, ctypes.c_char_p, c_float_p, c_int64_p, _i]),
-    "lws_finalize": (_i, [_vp]),
-    "lws_reserve": (_i, [_vp, _i, _i, _i]),
-    "lws_volume_l1_shift": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "lws_volume_l1_warp": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "lws_conv3d_stack": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "lws_softargmin": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp]),
-    "lws_upsample_add": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "lws_disparity_stages": (_i, [_vp, _vp * 3, _vp * 3, _i, _i, _i, _vp * 3, _vp]),
-    "lws_feature_extraction": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "lws_refine": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    "lws_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp * 4, _vp]),
-    "lws_softargmin_conf": (_i, [_vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "lws_forward_conf": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp * 4, _vp * 3, _vp * 3, _vp]),
-    "lws_preprocess_rgb8": (_i, [_vp, _vp, _i, _i, _i, c_float_p, c_float_p, _vp]),
-    "lws_apply_lut8": (_i, [_vp, _vp, _vp, ctypes.c_int64, _vp]),
-    "lws_stage_metrics_workspace": (ctypes.c_int64, [_i, _i, _i]),
-    "lws_stage_metrics": (_i, [_vp * 4, _i, _i, _i, _i, _vp, _i, _f, _i, _vp, _vp, _vp, _vp]),
-    "lws_sparsification": (_i, [_vp * 4, _vp * 4, _i, _i, _i, _i, _i, _i, _vp, _i, _f, _i, _vp, _vp]),
-    "lws_lr_pairs": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
-    "lws_lr_check": (_i, [_vp * 4, _vp * 4, _i, _i, _i, _i, _f, _i, _vp * 4, _vp * 4, _vp * 4, _vp, _vp]),
-    "lws_occlusion_check": (_i, [_vp * 4, _i, _i, _i, _i, _f, _i, _vp * 4, _vp * 4, _vp * 4, _vp, _vp]),
-    "lws_depth_maps": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp]),
-    "lws_point_cloud_workspace": (ctypes.c_int64, [_i, _i]),
-    "lws_point_cloud": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp]),
-    "lws_surface_normals": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp]),
-    "lws_surface_mesh_workspace": (ctypes.c_int64, [_i, _i]),
-    "lws_surface_mesh": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "lws_vdisparity": (_i, [_vp, _vp, _i, _i, _i, _f, _i, _i, _vp, _vp]),
-    "lws_ground_workspace": (ctypes.c_int64, [_i, _i, _i]),
-    "lws_ground_fit": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp]),
-    "lws_ground_classify": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
-    "lws_bev_grid": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _f, _f, _i, _i, _vp, _vp, _vp]),
-    "lws_stixels": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "lws_speckle_workspace": (ctypes.c_int64, [_i, _i, _i]),
-    "lws_speckle_filter": (_i, [_vp, _vp, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "lws_wmedian_filter": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "lws_rectify_pair": (_i, [_vp * 2, _vp, _i, _i, _i, _i, _i, _i, _i, _i, c_float_p, c_float_p, _vp * 2, _vp * 2, _vp * 2, _vp * 2, _vp]),
-    "lws_photometric": (_i, [_vp * 4, _i, _vp, _vp, _vp * 4, _vp, _i, _i, _i, _f, _vp * 4, _vp * 4, _vp * 4, _vp, _vp]),
-    "lws_set_option": (_i, [_vp, ctypes.c_char_p, _i]),
-    "lws_get_option": (_i, [_vp, ctypes.c_char_p, ctypes.POINTER(_i)]),
-    "lws_profile_enable": (_i, [_vp, _i]),
-    "lws_profile_sample": (_i, [_vp, _i]),
-    "lws_profile_read": (_i, [_vp, ctypes.POINTER(ctypes.c_double), c_int64_p]),
-    "lws_profile_read_class": (_i, [_vp, _i, c_float_p, _i, ctypes.POINTER(_i)]),
-    "lws_kernel_class_name": (ctypes.c_char_p, [_i]),
-    "lws_clock_stamp": (_i, [_vp, _i]),
-    "lws_clock_read": (_i, [_vp, ctypes.POINTER(ctypes.c_double)]),
-    "lws_debug_fill_workspace": (_i, [_vp, ctypes.c_uint32, _vp]),
-    "lws_join_stats": (_i, [_vp, c_int64_p, _i]),
-    "lws_clone": (_i, [_vp, ctypes.POINTER(_vp)]),
-    "lws_pool_create": (_i, [_vp, _i, _i, ctypes.POINTER(_vp)]),
-    "lws_pool_destroy": (_i, [_vp]),
-    "lws_pool_workers": (_i, [_vp]),
-    "lws_pool_reserve": (_i, [_vp, _i, _i, _i]),
-    "lws_pool_submit": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp * 4, _vp, c_int64_p]),
-    "lws_pool_wait": (_i, [_vp, ctypes.c_int64]),
-    "lws_pool_wait_all": (_i, [_vp]),
-    "lws_pool_clear_error": (_i, [_vp]),
-    "lws_pool_profile_enable": (_i, [_vp, _i, _i]),
-    "lws_pool_profile_read": (_i, [_vp, ctypes.POINTER(ctypes.c_double), c_int64_p]),
-}
-LWS_POOL_SIDE_STREAMS = 1
-LWS_KC_COUNT = 14
-LWS_SPARS_BINS = 1026
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32,
+            "float": ctypes.c_float, "double": ctypes.c_double}
+_HANDLES = ("lws_handle", "lws_pool_handle")
+
+
+def _ctype(decl, named):
+    """One parameter (`named`) or return type as written in C -> (ctypes type, the C spelling without the name, such as
+    `const float *` or `float *const [4]`).  What the rules of parse_header do not cover raises ValueError."""
+    m = re.fullmatch(r"(.*?)(\w+)\s*(?:\[\s*(\d+)\s*\])?" if named else r"(.*)()()", decl.strip(), re.S)      # type, name, [N]
+    tokens = re.findall(r"\w+|\*|\S", m[1]) if m else []
+    base = [t for t in tokens if t not in ("const", "*")]
+    if len(base) != 1 or not re.fullmatch(r"\w+", base[0]):
+        raise ValueError(f"cannot read `{' '.join(decl.split())}` as a type{' and a name' if named else ''}")
+    base, stars, n = base[0], tokens.count("*"), m[3]
+    spelling = " ".join(tokens).replace("* ", "*") + (f" [{n}]" if n else "")
+    if stars > 1:
+        raise ValueError(f"`{spelling}` is a pointer to a pointer")
+    if n:
+        if not stars:
+            raise ValueError(f"`{spelling}` is an array of non-pointers")
+        return ctypes.c_void_p * int(n), spelling
+    if stars:
+        return (ctypes.c_char_p if tokens[:2] == ["const", "char"] else ctypes.c_void_p), spelling
+    if base in _HANDLES:
+        return ctypes.c_void_p, spelling
+    if base not in _SCALARS:
+        raise ValueError(f"unknown type name `{base}`")
+    return _SCALARS[base], spelling
+
+
+def parse_header(text, where="header"):
+    """Reads a C header written like include/lwsnet_hip.h.  Returns (prototypes, spellings, constants):
+    prototypes {function: (restype, [argtypes])}, spellings {function: (return type, [parameter types])} as C text, constants
+    {name: int} from `#define NAME <integer>` and enum entries `NAME = <integer>`.  Scalars map by name (int, int32_t, int64_t,
+    uint32_t, float, double); lws_handle, lws_pool_handle and every pointer map to c_void_p, except `const char *`: c_char_p;
+    `T *name[N]` and `T *const name[N]` map to c_void_p * N.  Anything else -- an unknown type name, an array of non-pointers,
+    a pointer to a pointer -- raises ValueError naming the function and the parameter: nothing defaults to int."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    consts = {m[1]: int(m[2]) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(-?\d+)[ \t]*$", text, re.M)}
+    for body in re.findall(r"\benum\b[^{;]*\{(.*?)\}", text, re.S):
+        for entry in filter(None, (e.strip() for e in body.split(","))):
+            m = re.fullmatch(r"(\w+)\s*=\s*(-?\d+)", entry)
+            if not m:
+                raise ValueError(f"{where}: enum entry `{entry}` has no integer value written out")
+            consts[m[1]] = int(m[2])
+    text = re.sub(r"^[ \t]*#[^\n]*$", " ", text, flags=re.M)                   # preprocessor lines
+    text = re.sub(r"extern\s*\"C\"\s*\{|\{[^{}]*\}|\}", " ", text)             # the extern "C" braces, struct and enum bodies
+    protos, spellings = {}, {}
+    for stmt in filter(None, (s.strip() for s in text.split(";"))):
+        if stmt.startswith("typedef"):
+            continue
+        m = re.fullmatch(r"(.*?)\b(\w+)\s*\((.*)\)", stmt, re.S)
+        if not m:
+            raise ValueError(f"{where}: cannot read `{' '.join(stmt.split())}` as a function declaration")
+        name, params = m[2], [] if m[3].strip() == "void" else m[3].split(",")
+        try:
+            res = _ctype(m[1], False)
+        except ValueError as e:
+            raise ValueError(f"{where}: {name}: return type: {e}") from None
+        args = []
+        for i, p in enumerate(params):
+            try:
+                args.append(_ctype(p, True))
+            except ValueError as e:
+                pname = re.findall(r"[A-Za-z_]\w*", p)[-1:] or [f"#{i + 1}"]
+                raise ValueError(f"{where}: {name}: parameter `{pname[0]}`: {e}") from None
+        protos[name] = (res[0], [a[0] for a in args])
+        spellings[name] = (res[1], [a[1] for a in args])
+    return protos, spellings, consts
+
+
+# name -> (restype, argtypes) and name -> (C return type, C parameter types): exactly the functions the header declares
+with open(HEADER_PATH) as _f:
+    PROTOTYPES, C_SPELLINGS, _CONSTANTS = parse_header(_f.read(), HEADER_PATH)
+(LWS_ABI_VERSION, LWS_OK, LWS_ERR_INVALID, LWS_ERR_HIP, LWS_ERR_STATE, LWS_ERR_NOMEM, LWS_KC_COUNT, LWS_SPARS_BINS,
+ LWS_POOL_SIDE_STREAMS) = (_CONSTANTS[k] for k in ("LWS_ABI_VERSION", "LWS_OK", "LWS_ERR_INVALID", "LWS_ERR_HIP", "LWS_ERR_STATE",
+                                                   "LWS_ERR_NOMEM", "LWS_KC_COUNT", "LWS_SPARS_BINS", "LWS_POOL_SIDE_STREAMS"))
 
 _lib = None
 
@@ -124,7 +134,7 @@ def load():
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
-    if lib.lws_abi_version() != 8:
+    if lib.lws_abi_version() != LWS_ABI_VERSION:
         raise RuntimeError("liblwsnet_hip.so ABI version mismatch; rebuild the extension")
     _lib = lib
     return lib
@@ -137,3 +147,16 @@ def check(rc, what=""):
     if rc == LWS_ERR_INVALID:
         raise ValueError(msg or what)
     raise RuntimeError(f"{what}: {msg} (status {rc})")
+
+
+def call(name, *args):
+    """The library's function `name` on args; a status other than LWS_OK raises (check).  The one place a name is given."""
+    check(getattr(load(), name)(*args), name)
+
+
+def nbytes(name, *dims):
+    """What a *_workspace function answers for dims: a byte count; a negative answer is a status and raises (check)."""
+    n = getattr(load(), name)(*dims)
+    if n < 0:
+        check(n, name)
+    return n

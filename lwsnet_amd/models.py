@@ -108,7 +108,7 @@ class LWSNet:
         self._training = False
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device()) \
             if torch.cuda.is_available() else None
-        lib = _lib.load()                                         # raises if the HIP extension is missing
+        _lib.load()                                               # raises if the HIP extension is missing
         self.feature_fp16 = bool(getattr(args, "feature_fp16", False))     # BASELINE config 5 (not in the reference)
         # which source index the reference's four F.interpolate calls use (models.py:119,146,154,161): 0 = half-pixel centres
         # (this build's reading of Paddle 2.0rc0), 1 = src = ratio * dst; not in the reference's namespace
@@ -119,7 +119,7 @@ class LWSNet:
                              (ctypes.c_int32 * 3)(*self.growth_rate), 1 if self.feature_fp16 else 0, self.interp_align_mode)
         self._h = ctypes.c_void_p()
         with self._device_ctx():
-            _lib.check(lib.lws_create(ctypes.byref(cfg), ctypes.byref(self._h)), "lws_create")
+            _lib.call("lws_create", ctypes.byref(cfg), ctypes.byref(self._h))
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -160,14 +160,12 @@ class LWSNet:
         missing = [k for k in self._spec if k not in sd]
         if missing:
             raise KeyError(f"state dict is missing {len(missing)} entries, e.g. {missing[:3]}")
-        lib = _lib.load()
         with self._device_ctx():
             for k, v in sd.items():
                 shape = (ctypes.c_int64 * v.ndim)(*v.shape)
-                _lib.check(lib.lws_set_tensor(self._h, k.encode(), v.ctypes.data_as(_lib.c_float_p), shape, v.ndim),
-                           "lws_set_tensor")
+                _lib.call("lws_set_tensor", self._h, k.encode(), v.ctypes.data_as(_lib.c_float_p), shape, v.ndim)
             if self.device is not None:
-                _lib.check(lib.lws_finalize(self._h), "lws_finalize")
+                _lib.call("lws_finalize", self._h)
                 self._params = True
         self._sd = sd
         return self
@@ -176,12 +174,12 @@ class LWSNet:
 
     def set_option(self, name, value):
         """Launch-plan option of the HIP library (include/lwsnet_hip.h: lws_set_option); results never change."""
-        _lib.check(_lib.load().lws_set_option(self._h, name.encode(), int(value)), "lws_set_option")
+        _lib.call("lws_set_option", self._h, name.encode(), int(value))
         return self
 
     def get_option(self, name):
         v = ctypes.c_int(0)
-        _lib.check(_lib.load().lws_get_option(self._h, name.encode(), ctypes.byref(v)), "lws_get_option")
+        _lib.call("lws_get_option", self._h, name.encode(), ctypes.byref(v))
         return v.value
 
     # ---- several forwards in flight (include/lwsnet_hip.h: lws_pool_*) --------------------------
@@ -297,13 +295,12 @@ class ForwardPool:
         self._shape = None
         self._live = {}                         # ticket -> (left, right, outs) of jobs that may still be running
         with torch.cuda.device(model.device):
-            _lib.check(self._lib.lws_pool_create(model._h, workers, _lib.LWS_POOL_SIDE_STREAMS if side_streams else 0,
-                                                 ctypes.byref(self._p)), "lws_pool_create")
+            _lib.call("lws_pool_create", model._h, workers, _lib.LWS_POOL_SIDE_STREAMS if side_streams else 0, ctypes.byref(self._p))
         self.workers = workers
 
     def reserve(self, B, H, W):
         with torch.cuda.device(self._model.device):
-            _lib.check(self._lib.lws_pool_reserve(self._p, int(B), int(H), int(W)), "lws_pool_reserve")
+            _lib.call("lws_pool_reserve", self._p, int(B), int(H), int(W))
         self._shape = (B, H, W)
         return self
 
@@ -317,8 +314,8 @@ class ForwardPool:
                 self.reserve(B, H, W)            # first use / new geometry: allocate before anything is in flight
             ptrs = (ctypes.c_void_p * 4)(*[o.data_ptr() for o in outs])
             after = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            _lib.check(self._lib.lws_pool_submit(self._p, ctypes.c_void_p(left.data_ptr()), ctypes.c_void_p(right.data_ptr()),
-                                                 B, H, W, ptrs, after, ctypes.byref(ticket)), "lws_pool_submit")
+            _lib.call("lws_pool_submit", self._p, ctypes.c_void_p(left.data_ptr()), ctypes.c_void_p(right.data_ptr()), B, H, W, ptrs, after,
+                      ctypes.byref(ticket))
         # the pool itself keeps the inputs and outputs alive until the ticket has completed: a job object dropped without
         # result() must not hand its tensors back to the caching allocator while a worker's stream still uses them.
         # lws_pool_submit recycles the slot of ticket t - 4 x workers only after hipEventSynchronize on that job, so every
@@ -332,31 +329,31 @@ class ForwardPool:
 
     def _wait(self, ticket):
         try:
-            _lib.check(self._lib.lws_pool_wait(self._p, ctypes.c_int64(ticket)), "lws_pool_wait")
+            _lib.call("lws_pool_wait", self._p, ctypes.c_int64(ticket))
         finally:
             self._live.pop(ticket, None)
 
     def wait_all(self):
         try:
-            _lib.check(self._lib.lws_pool_wait_all(self._p), "lws_pool_wait_all")
+            _lib.call("lws_pool_wait_all", self._p)
         finally:
             self._live.clear()
 
     def profile(self, class_mask, every_n=1):
         """Per-class kernel timing on every worker (lws_pool_profile_enable); call with nothing in flight."""
-        _lib.check(self._lib.lws_pool_profile_enable(self._p, int(class_mask), int(every_n)), "lws_pool_profile_enable")
+        _lib.call("lws_pool_profile_enable", self._p, int(class_mask), int(every_n))
 
     def profile_read(self):
         """(total_ms[class], launches[class]) summed over the workers; call with nothing in flight."""
         tot = (ctypes.c_double * _lib.LWS_KC_COUNT)()
         cnt = (ctypes.c_int64 * _lib.LWS_KC_COUNT)()
         with torch.cuda.device(self._model.device):
-            _lib.check(self._lib.lws_pool_profile_read(self._p, tot, cnt), "lws_pool_profile_read")
+            _lib.call("lws_pool_profile_read", self._p, tot, cnt)
         return list(tot), list(cnt)
 
     def clear_error(self):
         """Clears the pool's sticky first-failure status (lws_pool_clear_error) so that submits are accepted again."""
-        _lib.check(self._lib.lws_pool_clear_error(self._p), "lws_pool_clear_error")
+        _lib.call("lws_pool_clear_error", self._p)
 
     def close(self):
         if self._p:

@@ -7,6 +7,7 @@ tensors must live on a HIP device.
 from __future__ import annotations
 
 import ctypes
+import math
 from collections import namedtuple
 
 import torch
@@ -30,9 +31,16 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
-def _arr4(ts):
-    """The device pointers of up to four tensors as the void *[4] of the C ABI (missing entries: NULL)."""
-    return (ctypes.c_void_p * 4)(*[t.data_ptr() for t in ts])
+def _arr(ts, n=4):
+    """The device pointers of up to n tensors as the void *[n] of the C ABI (a None and the missing entries: NULL)."""
+    return (ctypes.c_void_p * n)(*[t.data_ptr() if t is not None else None for t in ts])
+
+
+def _call(name, dev, *args):
+    """The library's `name` on device `dev` and torch's current stream there, which goes last: a tensor or None among args becomes
+    its device pointer, everything else passes through unchanged."""
+    with torch.cuda.device(dev):
+        _lib.call(name, *[_ptr(a) if a is None or isinstance(a, torch.Tensor) else a for a in args], _stream())
 
 
 def _imagenet_stats():
@@ -70,29 +78,59 @@ def _check_outputs(n, shape, dev, want_right):
     return out, mask, right, torch.empty((n, shape[0], shape[2]), device=dev, dtype=torch.int32)
 
 
+def _tensor_of(t, name, dt, shape, device, tail=""):
+    """t made contiguous: it must be a tensor of dtype dt and exactly `shape` on `device`; `tail` ends the message."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != tuple(shape) or t.device != device:
+        raise ValueError(f"{name} must be a {str(dt).split('.')[-1]} {tuple(shape)} tensor on {device}{tail}")
+    return t.contiguous()
+
+
 def _code_map(mask, d):
     """mask: None, or the uint8 code map of the maps d (same shape and device), made contiguous."""
-    if mask is None:
-        return None
-    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or tuple(mask.shape) != tuple(d.shape) or mask.device != d.device:
-        raise ValueError(f"mask must be a uint8 {tuple(d.shape)} tensor on {d.device} (the lws_lr_check code map)")
-    return mask.contiguous()
+    return None if mask is None else _tensor_of(mask, "mask", torch.uint8, d.shape, d.device, " (the lws_lr_check code map)")
 
 
 def _guide(rgb, d):
     """rgb: the uint8 [B,H,W,3] images that go with the maps d [B,1,H,W], made contiguous."""
     B, _, H, W = d.shape
-    if not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8 or tuple(rgb.shape) != (B, H, W, 3) or rgb.device != d.device:
-        raise ValueError(f"rgb must be a uint8 {(B, H, W, 3)} tensor on {d.device}")
-    return rgb.contiguous()
+    return _tensor_of(rgb, "rgb", torch.uint8, (B, H, W, 3), d.device)
 
 
-def _workspace(lib, name, device, *dims):
+def _ground_codes(codes, d):
+    """codes: the uint8 codes ground_classify returns for the maps d (same shape and device), made contiguous."""
+    return _tensor_of(codes, "codes", torch.uint8, d.shape, d.device, " (what ground_classify returns)")
+
+
+def _height_map(height, d):
+    """height: the float32 heights ground_classify returns for the maps d (same shape and device), made contiguous."""
+    height = _disp_map(height, "height")
+    if tuple(height.shape) != tuple(d.shape) or height.device != d.device:
+        raise ValueError(f"height must be {tuple(d.shape)} on {d.device}")
+    return height
+
+
+def _int_in(name, v, lo, hi, what=None):
+    """v as an int that must lie in lo .. hi; `what` words the range where the default wording does not serve."""
+    if isinstance(v, bool) or int(v) != v or not lo <= v <= hi:
+        raise ValueError(f"{name} must be {what or f'an integer in {lo} .. {hi}'}, got {v}")
+    return int(v)
+
+
+def _finite_nonneg(name, v):
+    if not (math.isfinite(v) and v >= 0):
+        raise ValueError(f"{name} must be finite and >= 0, got {v}")
+    return float(v)
+
+
+def _finite_pos(name, v):
+    if not (math.isfinite(v) and v > 0):
+        raise ValueError(f"{name} must be finite and > 0, got {v}")
+    return float(v)
+
+
+def _workspace(name, device, *dims):
     """The uint8 workspace of the size the library's `name`(*dims) asks for."""
-    nbytes = int(getattr(lib, name)(*dims))
-    if nbytes < 0:
-        _lib.check(nbytes, name)
-    return torch.empty((nbytes,), device=device, dtype=torch.uint8)
+    return torch.empty((_lib.nbytes(name, *dims),), device=device, dtype=torch.uint8)
 
 
 def volume_l1_shift(feat_l, feat_r, maxdisp):
@@ -102,10 +140,7 @@ def volume_l1_shift(feat_l, feat_r, maxdisp):
         raise ValueError(f"feat_l/feat_r must both be [B,C,h,w]; got {tuple(L.shape)} and {tuple(R.shape)}")
     B, C, h, w = L.shape
     cost = torch.empty((B, maxdisp, h, w), device=L.device, dtype=torch.float32)
-    lib = _lib.load()
-    with torch.cuda.device(L.device):
-        _lib.check(lib.lws_volume_l1_shift(_ptr(L), _ptr(R), _ptr(cost), B, C, h, w, int(maxdisp), _stream()),
-                   "lws_volume_l1_shift")
+    _call("lws_volume_l1_shift", L.device, L, R, cost, B, C, h, w, int(maxdisp))
     return cost
 
 
@@ -120,10 +155,7 @@ def volume_l1_warp(feat_l, feat_r, prev_disp, maxdisp, return_wflow=False):
     H, W = P.shape[2], P.shape[3]
     cost = torch.empty((B, 2 * maxdisp - 1, h, w), device=L.device, dtype=torch.float32)
     wflow = torch.empty((B, h, w), device=L.device, dtype=torch.float32) if return_wflow else None
-    lib = _lib.load()
-    with torch.cuda.device(L.device):
-        _lib.check(lib.lws_volume_l1_warp(_ptr(L), _ptr(R), _ptr(P), _ptr(cost), _ptr(wflow), B, C, h, w, H, W,
-                                          int(maxdisp), _stream()), "lws_volume_l1_warp")
+    _call("lws_volume_l1_warp", L.device, L, R, P, cost, wflow, B, C, h, w, H, W, int(maxdisp))
     return (cost, wflow) if return_wflow else cost
 
 
@@ -134,10 +166,7 @@ def conv3d_stack(handle, stage, cost):
         raise ValueError(f"cost must be [B,D,h,w]; got {tuple(c.shape)}")
     B, D, h, w = c.shape
     out = torch.empty_like(c)
-    lib = _lib.load()
-    with torch.cuda.device(c.device):
-        _lib.check(lib.lws_conv3d_stack(handle, int(stage), _ptr(c), _ptr(out), B, D, h, w, _stream()),
-                   "lws_conv3d_stack")
+    _call("lws_conv3d_stack", c.device, handle, int(stage), c, out, B, D, h, w)
     return out
 
 
@@ -146,9 +175,7 @@ def softargmin(cost, start):
     c = _dev(cost, "cost")
     B, D, h, w = c.shape
     low = torch.empty((B, h, w), device=c.device, dtype=torch.float32)
-    lib = _lib.load()
-    with torch.cuda.device(c.device):
-        _lib.check(lib.lws_softargmin(_ptr(c), _ptr(low), B, D, h, w, float(start), _stream()), "lws_softargmin")
+    _call("lws_softargmin", c.device, c, low, B, D, h, w, float(start))
     return low
 
 
@@ -165,10 +192,7 @@ def softargmin_conf(cost, start, H, W, disp_low=True, peak_low=True, sigma_low=T
     B, D, h, w = c.shape
     outs = [torch.empty((B, h, w), device=c.device, dtype=torch.float32) if on else None for on in (disp_low, peak_low, sigma_low)]
     outs += [torch.empty((B, 1, int(H), int(W)), device=c.device, dtype=torch.float32) if on else None for on in (conf, sigma)]
-    lib = _lib.load()
-    with torch.cuda.device(c.device):
-        _lib.check(lib.lws_softargmin_conf(_ptr(c), B, D, h, w, float(start), int(H), int(W), *[_ptr(t) for t in outs], _stream()),
-                   "lws_softargmin_conf")
+    _call("lws_softargmin_conf", c.device, c, B, D, h, w, float(start), int(H), int(W), *outs)
     return SoftargminConf(*outs)
 
 
@@ -178,10 +202,7 @@ def upsample_add(disp_low, prev, H, W):
     B, h, w = low.shape
     prev = _dev(prev, "prev") if prev is not None else None
     out = torch.empty((B, 1, H, W), device=low.device, dtype=torch.float32)
-    lib = _lib.load()
-    with torch.cuda.device(low.device):
-        _lib.check(lib.lws_upsample_add(_ptr(low), _ptr(prev), _ptr(out), B, h, w, int(H), int(W), _stream()),
-                   "lws_upsample_add")
+    _call("lws_upsample_add", low.device, low, prev, out, B, h, w, int(H), int(W))
     return out
 
 
@@ -198,12 +219,7 @@ def disparity_stages(handle, feats_l, feats_r, H, W):
         if tuple(fl[i].shape) != want[i] or tuple(fr[i].shape) != want[i]:
             raise ValueError(f"stage {i + 1} features must be {want[i]}; got {tuple(fl[i].shape)} / {tuple(fr[i].shape)}")
     preds = [torch.empty((B, 1, H, W), device=fl[0].device, dtype=torch.float32) for _ in range(3)]
-    arr = ctypes.c_void_p * 3
-    lib = _lib.load()
-    with torch.cuda.device(fl[0].device):
-        _lib.check(lib.lws_disparity_stages(handle, arr(*[t.data_ptr() for t in fl]), arr(*[t.data_ptr() for t in fr]),
-                                            B, int(H), int(W), arr(*[t.data_ptr() for t in preds]), _stream()),
-                   "lws_disparity_stages")
+    _call("lws_disparity_stages", fl[0].device, handle, _arr(fl, 3), _arr(fr, 3), B, int(H), int(W), _arr(preds, 3))
     return preds
 
 
@@ -217,10 +233,7 @@ def feature_extraction(handle, img):
     f8 = torch.empty((N, 16, h2 // 4, w2 // 4), device=x.device, dtype=torch.float32)
     f4 = torch.empty((N, 16, h2 // 2, w2 // 2), device=x.device, dtype=torch.float32)
     f2 = torch.empty((N, 8, h2, w2), device=x.device, dtype=torch.float32)
-    lib = _lib.load()
-    with torch.cuda.device(x.device):
-        _lib.check(lib.lws_feature_extraction(handle, _ptr(x), N, H, W, _ptr(f8), _ptr(f4), _ptr(f2), _stream()),
-                   "lws_feature_extraction")
+    _call("lws_feature_extraction", x.device, handle, x, N, H, W, f8, f4, f2)
     return [f8, f4, f2]
 
 
@@ -231,9 +244,7 @@ def refine(handle, left, pred3):
     if tuple(p3.shape) != (B, 1, H, W):
         raise ValueError(f"pred3 must be {(B, 1, H, W)}; got {tuple(p3.shape)}")
     out = torch.empty_like(p3)
-    lib = _lib.load()
-    with torch.cuda.device(l.device):
-        _lib.check(lib.lws_refine(handle, _ptr(l), _ptr(p3), B, H, W, _ptr(out), _stream()), "lws_refine")
+    _call("lws_refine", l.device, handle, l, p3, B, H, W, out)
     return out
 
 
@@ -262,11 +273,7 @@ def forward(handle, left, right, out=None):
     l, r = _dev(left, "left"), _dev(right, "right")
     B, _, H, W = l.shape
     preds = stage_outputs(out, B, H, W, l.device)
-    arr = ctypes.c_void_p * 4
-    lib = _lib.load()
-    with torch.cuda.device(l.device):
-        _lib.check(lib.lws_forward(handle, _ptr(l), _ptr(r), B, H, W, arr(*[t.data_ptr() for t in preds]), _stream()),
-                   "lws_forward")
+    _call("lws_forward", l.device, handle, l, r, B, H, W, _arr(preds))
     return preds
 
 
@@ -277,12 +284,7 @@ def forward_conf(handle, left, right, conf=True, sigma=True):
     B, _, H, W = l.shape
     preds = stage_outputs(None, B, H, W, l.device)
     cs, ss = ([torch.empty((B, 1, H, W), device=l.device, dtype=torch.float32) for _ in range(3)] if on else None for on in (conf, sigma))
-    arr4, arr3 = ctypes.c_void_p * 4, ctypes.c_void_p * 3
-    lib = _lib.load()
-    with torch.cuda.device(l.device):
-        _lib.check(lib.lws_forward_conf(handle, _ptr(l), _ptr(r), B, H, W, arr4(*[t.data_ptr() for t in preds]),
-                                        arr3(*[t.data_ptr() for t in cs]) if cs else arr3(),
-                                        arr3(*[t.data_ptr() for t in ss]) if ss else arr3(), _stream()), "lws_forward_conf")
+    _call("lws_forward_conf", l.device, handle, l, r, B, H, W, _arr(preds), _arr(cs or [], 3), _arr(ss or [], 3))
     return preds, cs, ss
 
 
@@ -328,8 +330,7 @@ def preprocess_rgb8(rgb_u8, out=None):
     elif tuple(out.shape) != (B, 3, H, W) or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
         raise ValueError("out must be a contiguous [B,3,H,W] float32 device tensor")
     mean, std = _imagenet_stats()
-    with torch.cuda.device(rgb_u8.device):
-        _lib.check(_lib.load().lws_preprocess_rgb8(_ptr(rgb_u8), _ptr(out), B, H, W, mean, std, _stream()), "lws_preprocess_rgb8")
+    _call("lws_preprocess_rgb8", rgb_u8.device, rgb_u8, out, B, H, W, mean, std)
     return out
 
 
@@ -343,9 +344,7 @@ def apply_lut8(disp, lut_dev, out=None):
         out = torch.empty(tuple(d.shape) + (3,), device=d.device, dtype=torch.uint8)
     elif out.numel() != 3 * d.numel() or out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
         raise ValueError("out must be a contiguous uint8 device tensor with 3 bytes per disparity value")
-    with torch.cuda.device(d.device):
-        _lib.check(_lib.load().lws_apply_lut8(_ptr(d), _ptr(lut_dev.contiguous()), _ptr(out), ctypes.c_int64(d.numel()), _stream()),
-                   "lws_apply_lut8")
+    _call("lws_apply_lut8", d.device, d, lut_dev.contiguous(), out, ctypes.c_int64(d.numel()))
     return out
 
 
@@ -377,14 +376,11 @@ def stage_metrics(preds, gt, row_offset, maxdisp, mode):
         raise ValueError("preds must be the four stage maps")
     mode, g, row_offset, (ps,) = _gt_maps(gt, row_offset, mode, preds=preds)
     B, Hg, W = g.shape
-    lib = _lib.load()
-    work = _workspace(lib, "lws_stage_metrics_workspace", g.device, B, Hg, W)
+    work = _workspace("lws_stage_metrics_workspace", g.device, B, Hg, W)
     counts = torch.empty((4, B, 2), device=g.device, dtype=torch.int64)
     abs_sum = torch.empty((4, B), device=g.device, dtype=torch.float64)
-    with torch.cuda.device(g.device):
-        _lib.check(lib.lws_stage_metrics(_arr4(ps), B, Hg + row_offset, W, row_offset, _ptr(g), Hg,
-                                         float(maxdisp), int(mode), _ptr(work), _ptr(counts), _ptr(abs_sum), _stream()),
-                   "lws_stage_metrics")
+    _call("lws_stage_metrics", g.device, _arr(ps), B, Hg + row_offset, W, row_offset, g, Hg, float(maxdisp), int(mode), work, counts,
+          abs_sum)
     return counts, abs_sum
 
 
@@ -405,12 +401,8 @@ def sparsification(preds, unc, gt, row_offset, maxdisp, mode, kind):
     mode, g, row_offset, (ps, us) = _gt_maps(gt, row_offset, mode, preds=preds, unc=unc)
     B, Hg, W = g.shape
     hist = torch.empty((len(ps), B, 2, _lib.LWS_SPARS_BINS, 3), device=g.device, dtype=torch.int64)
-    pad = [None] * (4 - len(ps))
-    arr = ctypes.c_void_p * 4
-    with torch.cuda.device(g.device):
-        _lib.check(_lib.load().lws_sparsification(arr(*[t.data_ptr() for t in ps], *pad), arr(*[t.data_ptr() for t in us], *pad), len(ps),
-                                                  int(kind), B, Hg + row_offset, W, row_offset, _ptr(g), Hg, float(maxdisp), int(mode),
-                                                  _ptr(hist), _stream()), "lws_sparsification")
+    _call("lws_sparsification", g.device, _arr(ps), _arr(us), len(ps), int(kind), B, Hg + row_offset, W, row_offset, g, Hg,
+          float(maxdisp), int(mode), hist)
     return hist
 
 
@@ -423,8 +415,7 @@ def lr_pairs(left, right):
     B, _, H, W = l.shape
     left2 = torch.empty((2 * B, 3, H, W), device=l.device, dtype=torch.float32)
     right2 = torch.empty_like(left2)
-    with torch.cuda.device(l.device):
-        _lib.check(_lib.load().lws_lr_pairs(_ptr(l), _ptr(r), _ptr(left2), _ptr(right2), B, H, W, _stream()), "lws_lr_pairs")
+    _call("lws_lr_pairs", l.device, l, r, left2, right2, B, H, W)
     return left2, right2
 
 
@@ -438,9 +429,8 @@ def lr_check(dl, drm, tau, fill, want_right=True):
     (ls, rs), shape, dev = _stage_maps(dl=dl, drm=drm)
     B, _, H, W = shape
     out, mask, right, row_kept = _check_outputs(len(ls), shape, dev, want_right)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().lws_lr_check(_arr4(ls), _arr4(rs), len(ls), B, H, W, float(tau), int(bool(fill)), _arr4(out), _arr4(mask),
-                                            _arr4(right or []), _ptr(row_kept), _stream()), "lws_lr_check")
+    _call("lws_lr_check", dev, _arr(ls), _arr(rs), len(ls), B, H, W, float(tau), int(bool(fill)), _arr(out), _arr(mask), _arr(right or []),
+          row_kept)
     return out, mask, right, row_kept
 
 
@@ -455,22 +445,18 @@ def occlusion_check(dl, tau, fill, want_right=True):
     (ls,), shape, dev = _stage_maps(dl=dl)
     B, _, H, W = shape
     out, mask, right, row_kept = _check_outputs(len(ls), shape, dev, want_right)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().lws_occlusion_check(_arr4(ls), len(ls), B, H, W, float(tau), int(bool(fill)), _arr4(out), _arr4(mask),
-                                                   _arr4(right or []), _ptr(row_kept), _stream()), "lws_occlusion_check")
+    _call("lws_occlusion_check", dev, _arr(ls), len(ls), B, H, W, float(tau), int(bool(fill)), _arr(out), _arr(mask), _arr(right or []),
+          row_kept)
     return out, mask, right, row_kept
 
 
 def _geometry_inputs(disp, mask, cameras, min_disp, max_depth):
     """Shared checks of depth_maps / point_cloud: disp [B,1,H,W] float32, mask None or uint8 of that shape, cameras (None, one
     Camera or a list of B) -> (disp, mask, cam [B,5] float32 device tensor or None)."""
-    import math
-
     from .geometry import camera_rows
     d = _disp_map(disp, "disp")
     mask = _code_map(mask, d)
-    if not (math.isfinite(min_disp) and min_disp > 0):
-        raise ValueError(f"min_disp must be finite and > 0, got {min_disp}")
+    _finite_pos("min_disp", min_disp)
     if not max_depth > 0:
         raise ValueError(f"max_depth must be > 0 (inf allowed), got {max_depth}")
     cam = None
@@ -492,9 +478,7 @@ def depth_maps(disp, cameras=None, mask=None, min_disp=1.0, max_depth=float("inf
     outs = [torch.empty(d.shape, device=d.device, dtype=dt) if want else None
             for want, dt in ((depth, torch.float32), (depth16, torch.uint16), (disp16, torch.uint16))]
     B, _, H, W = d.shape
-    with torch.cuda.device(d.device):
-        _lib.check(_lib.load().lws_depth_maps(_ptr(d), _ptr(mask), _ptr(cam), B, H, W, float(min_disp), float(max_depth), *map(_ptr, outs),
-                                              _stream()), "lws_depth_maps")
+    _call("lws_depth_maps", d.device, d, mask, cam, B, H, W, float(min_disp), float(max_depth), *outs)
     return tuple(outs)
 
 
@@ -509,21 +493,11 @@ def point_cloud(disp, cameras, mask=None, rgb=None, min_disp=1.0, max_depth=floa
     B, _, H, W = d.shape
     if rgb is not None:
         rgb = _guide(rgb, d)
-    lib = _lib.load()
-    work = _workspace(lib, "lws_point_cloud_workspace", d.device, B, H)
+    work = _workspace("lws_point_cloud_workspace", d.device, B, H)
     points = torch.empty((B, H * W, 16), device=d.device, dtype=torch.uint8)
     counts = torch.empty((B,), device=d.device, dtype=torch.int64)
-    with torch.cuda.device(d.device):
-        _lib.check(lib.lws_point_cloud(_ptr(d), _ptr(mask), _ptr(rgb), _ptr(cam), B, H, W, float(min_disp), float(max_depth), _ptr(work),
-                                       _ptr(points), _ptr(counts), _stream()), "lws_point_cloud")
+    _call("lws_point_cloud", d.device, d, mask, rgb, cam, B, H, W, float(min_disp), float(max_depth), work, points, counts)
     return points, counts
-
-
-def _max_jump(max_jump):
-    import math
-    if not (math.isfinite(max_jump) and max_jump >= 0):
-        raise ValueError(f"max_jump must be finite and >= 0, got {max_jump}")
-    return float(max_jump)
 
 
 def surface_normals(disp, cameras, mask=None, min_disp=1.0, max_depth=float("inf"), max_jump=1.0, normals=True, normals8=False):
@@ -540,9 +514,8 @@ def surface_normals(disp, cameras, mask=None, min_disp=1.0, max_depth=float("inf
     B, _, H, W = d.shape
     n = torch.empty((B, 3, H, W), device=d.device, dtype=torch.float32) if normals else None
     n8 = torch.empty((B, H, W, 3), device=d.device, dtype=torch.uint8) if normals8 else None
-    with torch.cuda.device(d.device):
-        _lib.check(_lib.load().lws_surface_normals(_ptr(d), _ptr(mask), _ptr(cam), B, H, W, float(min_disp), float(max_depth),
-                                                   _max_jump(max_jump), _ptr(n), _ptr(n8), _stream()), "lws_surface_normals")
+    max_jump = _finite_nonneg("max_jump", max_jump)
+    _call("lws_surface_normals", d.device, d, mask, cam, B, H, W, float(min_disp), float(max_depth), max_jump, n, n8)
     return n, n8
 
 
@@ -564,21 +537,18 @@ def surface_mesh(disp, cameras, mask=None, rgb=None, min_disp=1.0, max_depth=flo
     B, _, H, W = d.shape
     if rgb is not None:
         rgb = _guide(rgb, d)
-    lib = _lib.load()
     dev = d.device
-    work = _workspace(lib, "lws_surface_mesh_workspace", dev, B, H)
+    work = _workspace("lws_surface_mesh_workspace", dev, B, H)
     n = torch.empty((B, 3, H, W), device=dev, dtype=torch.float32) if with_normals else None
     vn = torch.empty((B, H * W, 4), device=dev, dtype=torch.float32) if with_normals else None
     points = torch.empty((B, H * W, 16), device=dev, dtype=torch.uint8)
     faces = torch.empty((B, max(1, 2 * (H - 1) * (W - 1)), 3), device=dev, dtype=torch.int32)
     index = torch.empty((B, 1, H, W), device=dev, dtype=torch.int32) if want_index else None
     counts = torch.empty((B, 2), device=dev, dtype=torch.int64)
-    args = (B, H, W, float(min_disp), float(max_depth), _max_jump(max_jump))
-    with torch.cuda.device(dev):
-        if with_normals:
-            _lib.check(lib.lws_surface_normals(_ptr(d), _ptr(mask), _ptr(cam), *args, _ptr(n), _ptr(None), _stream()), "lws_surface_normals")
-        _lib.check(lib.lws_surface_mesh(_ptr(d), _ptr(mask), _ptr(rgb), _ptr(cam), _ptr(n), *args, _ptr(work), _ptr(points), _ptr(vn),
-                                        _ptr(faces), _ptr(index), _ptr(counts), _stream()), "lws_surface_mesh")
+    args = (B, H, W, float(min_disp), float(max_depth), _finite_nonneg("max_jump", max_jump))
+    if with_normals:
+        _call("lws_surface_normals", dev, d, mask, cam, *args, n, None)
+    _call("lws_surface_mesh", dev, d, mask, rgb, cam, n, *args, work, points, vn, faces, index, counts)
     return SurfaceMesh(points, vn, faces, index, counts)
 
 
@@ -586,28 +556,12 @@ GROUND_STATUS = ("ok", "no ground", "degenerate")                     # info[b, 
 GROUND_CODES = ("invalid", "ground", "obstacle", "overhead", "below", "no plane")      # the codes of ground_classify
 
 
-def _int_in(name, v, lo, hi):
-    if isinstance(v, bool) or int(v) != v or not lo <= v <= hi:
-        raise ValueError(f"{name} must be an integer in {lo} .. {hi}, got {v}")
-    return int(v)
-
-
-def _finite_nonneg(name, v):
-    import math
-    if not (math.isfinite(v) and v >= 0):
-        raise ValueError(f"{name} must be finite and >= 0, got {v}")
-    return float(v)
-
-
 def _hist_args(min_disp, sub, nbins, maxdisp):
     """(min_disp, sub, nbins) of vdisparity / ground_fit; nbins None: min(1024, sub * maxdisp)."""
-    import math
-    if not (math.isfinite(min_disp) and min_disp > 0):
-        raise ValueError(f"min_disp must be finite and > 0, got {min_disp}")
-    sub = _int_in("sub", sub, 1, 16)
+    min_disp, sub = _finite_pos("min_disp", min_disp), _int_in("sub", sub, 1, 16)
     if nbins is None:
         nbins = min(1024, sub * _int_in("maxdisp", maxdisp, 1, 1 << 20), 256 * sub)
-    return float(min_disp), sub, _int_in("nbins", nbins, 1, min(4096, 256 * sub))
+    return min_disp, sub, _int_in("nbins", nbins, 1, min(4096, 256 * sub))
 
 
 def vdisparity(disp, mask=None, min_disp=1.0, sub=4, nbins=None, maxdisp=192):
@@ -619,8 +573,7 @@ def vdisparity(disp, mask=None, min_disp=1.0, sub=4, nbins=None, maxdisp=192):
     mask = _code_map(mask, d)
     B, _, H, W = d.shape
     hist = torch.empty((B, H, nbins), device=d.device, dtype=torch.uint32)
-    with torch.cuda.device(d.device):
-        _lib.check(_lib.load().lws_vdisparity(_ptr(d), _ptr(mask), B, H, W, min_disp, sub, nbins, _ptr(hist), _stream()), "lws_vdisparity")
+    _call("lws_vdisparity", d.device, d, mask, B, H, W, min_disp, sub, nbins, hist)
     return hist
 
 
@@ -657,13 +610,11 @@ def ground_fit(disp, hist, mask=None, min_disp=1.0, sub=4, yh_range=None, qb_ran
     if tuple(hist.shape[:2]) != (B, d.shape[2]) or hist.device != d.device:
         raise ValueError(f"hist must be [{B},{d.shape[2]},nbins] on {d.device}; got {tuple(hist.shape)} on {hist.device}")
     hist = hist.contiguous()
-    lib = _lib.load()
-    work = _workspace(lib, "lws_ground_workspace", d.device, B, H, nbins)
+    work = _workspace("lws_ground_workspace", d.device, B, H, nbins)
     plane = torch.empty((B, 4), device=d.device, dtype=torch.float32)
     info = torch.empty((B, 8), device=d.device, dtype=torch.int32)
-    with torch.cuda.device(d.device):
-        _lib.check(lib.lws_ground_fit(_ptr(d), _ptr(mask), _ptr(hist), B, H, W, min_disp, sub, nbins, yh_lo, yh_hi, qb_lo, qb_hi, tol_bins,
-                                      min_score, tol0, tol, iters, _ptr(work), _ptr(plane), _ptr(info), _stream()), "lws_ground_fit")
+    _call("lws_ground_fit", d.device, d, mask, hist, B, H, W, min_disp, sub, nbins, yh_lo, yh_hi, qb_lo, qb_hi, tol_bins, min_score, tol0, tol,
+          iters, work, plane, info)
     return plane, info
 
 
@@ -686,30 +637,24 @@ def ground_classify(disp, cameras, plane, mask=None, min_disp=1.0, max_depth=flo
     ground_tol, max_height = _heights(ground_tol, max_height)
     d, mask, cam = _geometry_inputs(disp, mask, cameras, min_disp, max_depth)
     B, _, H, W = d.shape
-    if not isinstance(plane, torch.Tensor) or plane.dtype != torch.float32 or tuple(plane.shape) != (B, 4) or plane.device != d.device:
-        raise ValueError(f"plane must be a float32 {(B, 4)} tensor on {d.device} (what ground_fit returns)")
-    plane = plane.contiguous()
+    plane = _tensor_of(plane, "plane", torch.float32, (B, 4), d.device, " (what ground_fit returns)")
     h = torch.empty(d.shape, device=d.device, dtype=torch.float32) if height else None
     c = torch.empty(d.shape, device=d.device, dtype=torch.uint8) if codes else None
     n = torch.empty((B, 6), device=d.device, dtype=torch.int64) if counts else None
-    with torch.cuda.device(d.device):
-        _lib.check(_lib.load().lws_ground_classify(_ptr(d), _ptr(mask), _ptr(cam), _ptr(plane), B, H, W, float(min_disp), float(max_depth),
-                                                   ground_tol, max_height, _ptr(h), _ptr(c), _ptr(n), _stream()), "lws_ground_classify")
+    _call("lws_ground_classify", d.device, d, mask, cam, plane, B, H, W, float(min_disp), float(max_depth), ground_tol, max_height, h, c, n)
     return h, c, n
 
 
 def _bev_args(code_bits, x_min, cell, grid, hmax):
-    import math
     code_bits = _int_in("code_bits", code_bits, 0, 63)
     if hmax and code_bits & 0x33:
         raise ValueError(f"code_bits {code_bits} selects a code other than 2 and 3, whose heights are not positive: ask for no hmax")
     if not math.isfinite(x_min):
         raise ValueError(f"x_min must be finite, got {x_min}")
-    if not (math.isfinite(cell) and cell > 0):
-        raise ValueError(f"cell must be finite and > 0, got {cell}")
+    cell = _finite_pos("cell", cell)
     if len(grid) != 2:
         raise ValueError(f"grid must be (Gx, Gz), got {grid}")
-    return code_bits, float(x_min), float(cell), _int_in("grid", grid[0], 1, 4096), _int_in("grid", grid[1], 1, 4096)
+    return code_bits, float(x_min), cell, _int_in("grid", grid[0], 1, 4096), _int_in("grid", grid[1], 1, 4096)
 
 
 def bev_grid(disp, cameras, codes, height=None, min_disp=1.0, max_depth=float("inf"), code_bits=1 << 2, x_min=-20.0, cell=0.2,
@@ -727,18 +672,13 @@ def bev_grid(disp, cameras, codes, height=None, min_disp=1.0, max_depth=float("i
     code_bits, x_min, cell, Gx, Gz = _bev_args(code_bits, x_min, cell, grid, hmax)
     d, _, cam = _geometry_inputs(disp, None, cameras, min_disp, max_depth)
     B, _, H, W = d.shape
-    if not isinstance(codes, torch.Tensor) or codes.dtype != torch.uint8 or tuple(codes.shape) != tuple(d.shape) or codes.device != d.device:
-        raise ValueError(f"codes must be a uint8 {tuple(d.shape)} tensor on {d.device} (what ground_classify returns)")
-    codes = codes.contiguous()
+    codes = _ground_codes(codes, d)
     if height is not None:
-        height = _disp_map(height, "height")
-        if tuple(height.shape) != tuple(d.shape) or height.device != d.device:
-            raise ValueError(f"height must be {tuple(d.shape)} on {d.device}")
+        height = _height_map(height, d)
     n = torch.empty((B, Gz, Gx), device=d.device, dtype=torch.uint32) if count else None
     top = torch.empty((B, Gz, Gx), device=d.device, dtype=torch.float32) if hmax else None
-    with torch.cuda.device(d.device):
-        _lib.check(_lib.load().lws_bev_grid(_ptr(d), _ptr(cam), _ptr(codes), _ptr(height if hmax else None), B, H, W, float(min_disp),
-                                            float(max_depth), code_bits, x_min, cell, Gx, Gz, _ptr(n), _ptr(top), _stream()), "lws_bev_grid")
+    _call("lws_bev_grid", d.device, d, cam, codes, height if hmax else None, B, H, W, float(min_disp), float(max_depth), code_bits, x_min, cell,
+          Gx, Gz, n, top)
     return n, top
 
 
@@ -802,20 +742,13 @@ def stixels(disp, cameras, codes, height, min_disp=1.0, max_depth=float("inf"), 
     B, _, H, W = d.shape
     if H > 16384 or W > 16384:
         raise ValueError(f"disp is {H}x{W}: stixels takes maps up to 16384x16384")
-    if not isinstance(codes, torch.Tensor) or codes.dtype != torch.uint8 or tuple(codes.shape) != tuple(d.shape) or codes.device != d.device:
-        raise ValueError(f"codes must be a uint8 {tuple(d.shape)} tensor on {d.device} (what ground_classify returns)")
-    codes = codes.contiguous()
-    height = _disp_map(height, "height")
-    if tuple(height.shape) != tuple(d.shape) or height.device != d.device:
-        raise ValueError(f"height must be {tuple(d.shape)} on {d.device}")
+    codes, height = _ground_codes(codes, d), _height_map(height, d)
     S = -(-W // width)
     rows = torch.empty((B, S, layers, 4), device=d.device, dtype=torch.int32)
     vals = torch.empty((B, S, layers, 4), device=d.device, dtype=torch.float32)
     u = torch.empty((B, S, nbins), device=d.device, dtype=torch.uint32) if udisp else None
-    with torch.cuda.device(d.device):
-        _lib.check(_lib.load().lws_stixels(_ptr(d), _ptr(cam), _ptr(codes), _ptr(height), B, H, W, min_disp, float(max_depth), code_bits, width,
-                                           sub, nbins, tol_bins, min_count, min_row, max_gap, layers, _ptr(rows), _ptr(vals), _ptr(u), _stream()),
-                   "lws_stixels")
+    _call("lws_stixels", d.device, d, cam, codes, height, B, H, W, min_disp, float(max_depth), code_bits, width, sub, nbins, tol_bins, min_count,
+          min_row, max_gap, layers, rows, vals, u)
     return StixelResult(rows, vals, u)
 
 
@@ -831,23 +764,17 @@ def speckle_filter(disp, max_size, max_diff=1.0, mask=None, fill=False, want_lab
     torch.cat them along B, every image is filtered on its own); mask: None or the uint8 lws_lr_check code map (only code-1
     pixels are valid); fill: give the removed and invalid pixels the background value of their row.  The workspace (8 bytes per
     pixel) and the outputs are allocated per call on the current stream.  Returns a SpeckleResult."""
-    import math
     d = _disp_map(disp, "disp")
     mask = _code_map(mask, d)
-    if not (math.isfinite(max_diff) and max_diff >= 0):
-        raise ValueError(f"max_diff must be finite and >= 0, got {max_diff}")
-    if int(max_size) != max_size or max_size < 0 or max_size >= 2 ** 31:
-        raise ValueError(f"max_size must be an integer in 0 .. 2^31 - 1, got {max_size}")
+    max_diff = _finite_nonneg("max_diff", max_diff)
+    max_size = _int_in("max_size", max_size, 0, 2 ** 31 - 1, "an integer in 0 .. 2^31 - 1")
     B, _, H, W = d.shape
-    lib = _lib.load()
-    work = _workspace(lib, "lws_speckle_workspace", d.device, B, H, W)
+    work = _workspace("lws_speckle_workspace", d.device, B, H, W)
     out = torch.empty_like(d)
     mask_out = torch.empty(d.shape, device=d.device, dtype=torch.uint8)
     labels = torch.empty(d.shape, device=d.device, dtype=torch.int32) if want_labels else None
     counts = torch.empty((B, 3), device=d.device, dtype=torch.int64)
-    with torch.cuda.device(d.device):
-        _lib.check(lib.lws_speckle_filter(_ptr(d), _ptr(mask), B, H, W, float(max_diff), int(max_size), int(bool(fill)), _ptr(work),
-                                          _ptr(out), _ptr(mask_out), _ptr(labels), _ptr(counts), _stream()), "lws_speckle_filter")
+    _call("lws_speckle_filter", d.device, d, mask, B, H, W, max_diff, max_size, int(bool(fill)), work, out, mask_out, labels, counts)
     return SpeckleResult(out, mask_out, labels, counts)
 
 
@@ -858,8 +785,6 @@ def wmedian_lut(sigma, scale=4096):
     """The weight table of wmedian_filter: numpy uint16 [766], wlut[s] = rint(scale * exp(-s / (3 * sigma))) in float64, s the sum
     of the absolute colour differences to the window's centre (so sigma is in grey levels per channel).  sigma finite and > 0,
     scale an integer in 1 .. 65535 (the weight of equal colours).  The only transcendental of the filter: the table is data."""
-    import math
-
     import numpy as np
     if isinstance(sigma, bool) or not isinstance(sigma, (int, float, np.integer, np.floating)) or not (math.isfinite(sigma) and sigma > 0):
         raise ValueError(f"sigma must be finite and > 0, got {sigma!r}")
@@ -884,10 +809,8 @@ def wmedian_filter(disp, radius, rgb=None, wlut=None, mask=None, fill_min=0):
     never).  The outputs are allocated per call on the current stream.  Returns a WMedianResult."""
     import numpy as np
     d = _disp_map(disp, "disp")
-    if isinstance(radius, bool) or int(radius) != radius or not 1 <= radius <= 3:
-        raise ValueError(f"radius must be 1, 2 or 3, got {radius!r}")
-    if isinstance(fill_min, bool) or int(fill_min) != fill_min or fill_min < 0 or fill_min >= 2 ** 31:
-        raise ValueError(f"fill_min must be an integer in 0 .. 2^31 - 1, got {fill_min!r}")
+    radius = _int_in("radius", radius, 1, 3, "1, 2 or 3")
+    fill_min = _int_in("fill_min", fill_min, 0, 2 ** 31 - 1, "an integer in 0 .. 2^31 - 1")
     B, _, H, W = d.shape
     mask = _code_map(mask, d)
     if rgb is None:
@@ -905,9 +828,7 @@ def wmedian_filter(disp, radius, rgb=None, wlut=None, mask=None, fill_min=0):
         wlut = wlut.contiguous()
     out = torch.empty_like(d)
     counts = torch.empty((B, 2), device=d.device, dtype=torch.int64)
-    with torch.cuda.device(d.device):
-        _lib.check(_lib.load().lws_wmedian_filter(_ptr(d), _ptr(mask), _ptr(rgb), _ptr(wlut), B, H, W, int(radius), int(fill_min), _ptr(out),
-                                                  _ptr(counts), _stream()), "lws_wmedian_filter")
+    _call("lws_wmedian_filter", d.device, d, mask, rgb, wlut, B, H, W, radius, fill_min, out, counts)
     return WMedianResult(out, counts)
 
 
@@ -943,8 +864,7 @@ def rectify_pair(raw_left, raw_right, params, out_hw, origin=(0, 0), border=0, w
         raise ValueError(f"params must be [{B},2,18] or [2,18]; got {tuple(params.shape)}")
     params = params.contiguous()
     (H, W), (y0, x0) = (int(v) for v in out_hw), (int(v) for v in origin)
-    if isinstance(border, bool) or int(border) != border or not 0 <= border <= 255:
-        raise ValueError(f"border must be an integer in 0 .. 255, got {border!r}")
+    border = _int_in("border", border, 0, 255)
     if H < 1 or W < 1:
         raise ValueError(f"out_hw must be positive, got {(H, W)}")
     res, arrays = {}, []
@@ -953,12 +873,9 @@ def rectify_pair(raw_left, raw_right, params, out_hw, origin=(0, 0), border=0, w
         pair = torch.empty((2, B) + shape, device=dev, dtype=dt) if want else None     # one allocation for both cameras
         if want:
             res[key] = (pair[0], pair[1])
-        arrays.append((ctypes.c_void_p * 2)(*[pair[c].data_ptr() if want else None for c in range(2)]))
+        arrays.append(_arr(res.get(key, ()), 2))
     mean, std = _imagenet_stats()
-    raws = (ctypes.c_void_p * 2)(raw_left.data_ptr(), raw_right.data_ptr())
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().lws_rectify_pair(raws, _ptr(params), B, Hs, Ws, H, W, x0, y0, int(border), mean, std, *arrays, _stream()),
-                   "lws_rectify_pair")
+    _call("lws_rectify_pair", dev, _arr([raw_left, raw_right], 2), params, B, Hs, Ws, H, W, x0, y0, border, mean, std, *arrays)
     return res
 
 
@@ -976,7 +893,6 @@ def photometric(disp, left_u8, right_u8, mask=None, rvalid=None, alpha=0.85, wan
     lws_lr_check code map for every map, or a list with one (or None) per map: only code-1 pixels are scored; rvalid: None or the
     uint8 [B,1,H,W] valid map of the right camera (rectify_pair): a tap outside it cannot be used; alpha in [0, 1].  The outputs are
     allocated per call on the current stream.  Returns a PhotometricResult."""
-    import math
     single = isinstance(disp, torch.Tensor)
     maps = [disp] if single else disp
     if not isinstance(maps, (list, tuple)) or not 1 <= len(maps) <= 4:
@@ -997,11 +913,8 @@ def photometric(disp, left_u8, right_u8, mask=None, rvalid=None, alpha=0.85, wan
     scored = [torch.empty(shape, device=dev, dtype=torch.uint8) for _ in range(n)] if want_scored else None
     warped = [torch.empty((B, H, W, 3), device=dev, dtype=torch.uint8) for _ in range(n)] if want_warped else None
     sums = torch.empty((n, B, 4), device=dev, dtype=torch.int64)
-    arr = ctypes.c_void_p * 4
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().lws_photometric(_arr4(ds), n, _ptr(left), _ptr(right), arr(*[k.data_ptr() if k is not None else None for k in masks]),
-                                               _ptr(rvalid), B, H, W, float(alpha), _arr4(err or []), _arr4(scored or []), _arr4(warped or []),
-                                               _ptr(sums), _stream()), "lws_photometric")
+    _call("lws_photometric", dev, _arr(ds), n, left, right, _arr(masks), rvalid, B, H, W, float(alpha), _arr(err or []), _arr(scored or []),
+          _arr(warped or []), sums)
     if single:
         err, scored, warped = (v[0] if v is not None else None for v in (err, scored, warped))
     return PhotometricResult(err, scored, warped, sums)

@@ -1,9 +1,14 @@
 """The C-ABI library builds for gfx950, loads without a GPU and exports every symbol
 include/lwsnet_hip.h declares; host-side argument / state errors behave like the
-reference's Python exceptions (ValueError for bad shapes, RuntimeError otherwise)."""
+reference's Python exceptions (ValueError for bad shapes, RuntimeError otherwise).
+lwsnet_amd._lib reads its prototypes and constants from that header: its reading is held to a C++ compiler, to hand-written
+expectations and, on small header texts, to every rule it states."""
 import ctypes
+import importlib.util
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -21,6 +26,184 @@ def _declared():
 
 def test_header_and_prototypes_agree():
     assert _declared() == sorted(_lib.PROTOTYPES)
+
+
+# ---- the reader of include/lwsnet_hip.h (lwsnet_amd._lib.parse_header) ----
+VP, I, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+
+
+def _host_compiler():
+    """g++, or the clang++ of the toolchain hipcc belongs to; a box that builds the library has one of them."""
+    from lwsnet_amd import build
+    cands = [shutil.which("g++"), shutil.which("clang++")]
+    try:
+        rocm = os.path.dirname(os.path.dirname(os.path.realpath(build._hipcc())))
+        cands += [os.path.join(rocm, "llvm", "bin", "clang++"), os.path.join(rocm, "lib", "llvm", "bin", "clang++")]
+    except RuntimeError:
+        pass
+    found = [c for c in cands if c and os.path.isfile(c)]
+    assert found, f"no host C++ compiler among {cands}: the reading of the header cannot be checked"
+    return found[0]
+
+
+def _assert_line(name, spelling):
+    ret, params = spelling
+    return f'static_assert(std::is_same_v<decltype(&{name}), {ret} (*)({", ".join(params)})>, "{name}");\n'
+
+
+def _syntax_only(cxx, path, lines):
+    with open(path, "w") as f:
+        f.write('#include <cstddef>\n#include <type_traits>\n#include "lwsnet_hip.h"\n' + "".join(lines))
+    return subprocess.run([cxx, "-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(path)], capture_output=True, text=True)
+
+
+def test_a_compiler_agrees_with_the_reading(tmp_path):
+    """Per declared function, the parameter and return types the reader kept, as C text, are the function's type to a C++
+    compiler; one scalar misread fails the compile and names the function; LwsConfig has lws_config's size and offsets."""
+    cxx = _host_compiler()
+    assert sorted(_lib.C_SPELLINGS) == _declared() and len(_lib.C_SPELLINGS) == 66
+    lines = {name: _assert_line(name, sp) for name, sp in _lib.C_SPELLINGS.items()}
+    config = [f'static_assert(sizeof(lws_config) == {ctypes.sizeof(_lib.LwsConfig)}, "sizeof(lws_config)");\n']
+    for field, _ in _lib.LwsConfig._fields_:
+        d = getattr(_lib.LwsConfig, field)
+        config.append(f'static_assert(offsetof(lws_config, {field}) == {d.offset} && sizeof(lws_config::{field}) == {d.size}, "{field}");\n')
+    assert len(config) == 7
+    ok = _syntax_only(cxx, tmp_path / "abi.cpp", list(lines.values()) + config)
+    assert ok.returncode == 0, ok.stderr
+    # lws_softargmin(const float *, float *, int, int, int, int, float, void *): its fourth int read as float
+    ret, params = _lib.C_SPELLINGS["lws_softargmin"]
+    assert params[5] == "int" and params[6] == "float"
+    flipped = dict(lines, lws_softargmin=_assert_line("lws_softargmin", (ret, params[:5] + ["float"] + params[6:])))
+    bad = _syntax_only(cxx, tmp_path / "abi_flipped.cpp", list(flipped.values()) + config)
+    assert bad.returncode != 0 and '"lws_softargmin"' in bad.stderr, bad.stderr
+    assert bad.stderr.count("error:") == 1, bad.stderr
+    # ... and a field of the structure moved by four bytes
+    moved = _syntax_only(cxx, tmp_path / "abi_moved.cpp", [config[2].replace("== 12 ", "== 16 ")])
+    assert "== 16 " in config[2].replace("== 12 ", "== 16 ") and moved.returncode != 0 and "layers_3d" in moved.stderr, moved.stderr
+
+
+# written by hand from the header, not from the reader: every parameter kind, the two longest lists, the three return types
+EXPECTED = {
+    "lws_ground_fit": (I, [VP, VP, VP, I, I, I, F, I, I, I, I, I, I, I, I, F, F, I, VP, VP, VP, VP]),
+    "lws_stixels": (I, [VP, VP, VP, VP, I, I, I, F, F, I, I, I, I, I, I, I, I, I, VP, VP, VP, VP]),
+    "lws_rectify_pair": (I, [VP * 2, VP, I, I, I, I, I, I, I, I, VP, VP, VP * 2, VP * 2, VP * 2, VP * 2, VP]),
+    "lws_photometric": (I, [VP * 4, I, VP, VP, VP * 4, VP, I, I, I, F, VP * 4, VP * 4, VP * 4, VP, VP]),
+    "lws_softargmin_conf": (I, [VP, I, I, I, I, F, I, I, VP, VP, VP, VP, VP, VP]),
+    "lws_stage_metrics_workspace": (ctypes.c_int64, [I, I, I]),
+    "lws_pool_submit": (I, [VP, VP, VP, I, I, I, VP * 4, VP, VP]),
+    "lws_last_error": (ctypes.c_char_p, []),
+    # the scalar kinds the eight above do not hold: int64_t and uint32_t by value, const char * as a parameter
+    "lws_apply_lut8": (I, [VP, VP, VP, ctypes.c_int64, VP]),
+    "lws_debug_fill_workspace": (I, [VP, ctypes.c_uint32, VP]),
+    "lws_set_tensor": (I, [VP, ctypes.c_char_p, VP, VP, I]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(EXPECTED))
+def test_prototypes_against_hand_written_expectations(name):
+    assert _lib.PROTOTYPES[name] == EXPECTED[name]
+    assert len(EXPECTED["lws_ground_fit"][1]) == len(EXPECTED["lws_stixels"][1]) == 22 == max(len(a) for _, a in _lib.PROTOTYPES.values())
+
+
+def test_constants_come_from_the_header():
+    assert _lib.LWS_ABI_VERSION == 8 and _lib.LWS_KC_COUNT == 14 and _lib.LWS_SPARS_BINS == 1026 and _lib.LWS_POOL_SIDE_STREAMS == 1
+    assert (_lib.LWS_OK, _lib.LWS_ERR_INVALID, _lib.LWS_ERR_HIP, _lib.LWS_ERR_STATE, _lib.LWS_ERR_NOMEM) == (0, -1, -2, -3, -4)
+    assert _lib.c_float_p is ctypes.POINTER(ctypes.c_float) and _lib.c_int64_p is ctypes.POINTER(ctypes.c_int64)
+
+
+SMALL_HEADER = """
+/* a comment that looks like a call: lws_x(left, right -> out) */
+#ifndef SMALL_H
+#define SMALL_H
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define LWS_ANSWER 42
+#define LWS_NEGATIVE -7
+typedef enum { LWS_A = 0,   /* lws_y( */
+               LWS_B = -3 } lws_letters;
+typedef struct { int32_t v[3]; /* lws_z(int) */ } lws_thing;
+typedef struct lws_ctx *lws_handle;      // lws_w(void)
+typedef struct lws_pool *lws_pool_handle;
+int lws_none(void);
+const char *lws_text(int which, const char *key);
+int64_t lws_scalars(int a, int32_t b, int64_t c, uint32_t d, float e, double f);
+int lws_handles(lws_handle h, lws_pool_handle p, lws_handle *out, lws_pool_handle *pool_out);
+int lws_pointers(const float *in, float *out, const uint8_t *bytes, uint16_t *words, const lws_thing *cfg, double *ms, void *stream);
+int lws_arrays(const float *const maps[4], float *const out[3], uint8_t *raw[2]);
+int lws_three_lines(const float *disp,   // the map
+                    int B, int H,
+                    int W, void *stream);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+def test_reader_maps_every_kind_of_parameter():
+    protos, spellings, consts = _lib.parse_header(SMALL_HEADER)
+    assert consts == {"LWS_ANSWER": 42, "LWS_NEGATIVE": -7, "LWS_A": 0, "LWS_B": -3}
+    assert list(protos) == ["lws_none", "lws_text", "lws_scalars", "lws_handles", "lws_pointers", "lws_arrays", "lws_three_lines"]
+    assert protos["lws_none"] == (I, []) and spellings["lws_none"] == ("int", [])
+    assert protos["lws_text"] == (ctypes.c_char_p, [I, ctypes.c_char_p]) and spellings["lws_text"] == ("const char *", ["int", "const char *"])
+    assert protos["lws_scalars"] == (ctypes.c_int64, [I, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, F, ctypes.c_double])
+    assert protos["lws_handles"] == (I, [VP] * 4) and spellings["lws_handles"][1] == ["lws_handle", "lws_pool_handle", "lws_handle *", "lws_pool_handle *"]
+    assert protos["lws_pointers"] == (I, [VP] * 7)
+    assert spellings["lws_pointers"][1] == ["const float *", "float *", "const uint8_t *", "uint16_t *", "const lws_thing *", "double *", "void *"]
+    assert protos["lws_arrays"] == (I, [VP * 4, VP * 3, VP * 2])
+    assert spellings["lws_arrays"][1] == ["const float *const [4]", "float *const [3]", "uint8_t * [2]"]
+    assert protos["lws_three_lines"] == (I, [VP, I, I, I, VP])
+
+
+@pytest.mark.parametrize("decl,words", [
+    ("int lws_f(int B, unsigned n);", ("lws_f", "`n`", "unknown type name `unsigned`")),        # nothing defaults to int
+    ("int lws_f(const float *disp, size_t n, void *stream);", ("lws_f", "`n`", "unknown type name `size_t`")),
+    ("int lws_f(float *out, int dims[3]);", ("lws_f", "`dims`", "array of non-pointers")),
+    # a pointer to a pointer is refused, not mapped: the handle out-parameters are `lws_handle *`, one star
+    ("int lws_f(lws_handle h, float **out);", ("lws_f", "`out`", "pointer to a pointer")),
+    ("int lws_f(lws_handle **out);", ("lws_f", "`out`", "pointer to a pointer")),
+    ("void lws_f(int B);", ("lws_f", "return type", "unknown type name `void`")),
+    ("int lws_f(int);", ("lws_f", "cannot read `int`")),
+    ("typedef enum { LWS_A, LWS_B } lws_e;", ("enum entry `LWS_A`",)),
+    ("static const int lws_table[3];", ("cannot read `static const int lws_table[3]` as a function declaration",)),
+])
+def test_reader_refuses_what_it_cannot_map(decl, words):
+    with pytest.raises(ValueError) as e:
+        _lib.parse_header(decl, "small.h")
+    assert str(e.value).startswith("small.h: ")
+    for w in words:
+        assert w in str(e.value), str(e.value)
+
+
+def test_import_without_the_header_names_the_missing_path(tmp_path):
+    """_lib.py in a tree without include/lwsnet_hip.h: importing it raises and names the path; no empty table is left behind."""
+    (tmp_path / "pkg").mkdir()
+    shutil.copy(_lib.__file__, tmp_path / "pkg" / "_lib.py")
+    spec = importlib.util.spec_from_file_location("lib_without_header", tmp_path / "pkg" / "_lib.py")
+    with pytest.raises(FileNotFoundError, match=re.escape(str(tmp_path / "include" / "lwsnet_hip.h"))):
+        spec.loader.exec_module(importlib.util.module_from_spec(spec))
+    assert os.path.samefile(_lib.HEADER_PATH, os.path.join(ROOT, "include", "lwsnet_hip.h"))
+
+
+def test_call_names_the_function_once(hip_lib):
+    """_lib.call: the status is checked under the name it was called by; _lib.nbytes: a negative size is a status."""
+    rc, h = _create(hip_lib)
+    assert rc == 0
+    _lib.call("lws_set_option", h, b"fork2_after", 2)
+    v = ctypes.c_int(0)
+    _lib.call("lws_get_option", h, b"fork2_after", ctypes.byref(v))
+    assert v.value == 2
+    with pytest.raises(ValueError, match="unknown option"):
+        _lib.call("lws_set_option", h, b"bogus", 1)
+    with pytest.raises(RuntimeError, match=r"^lws_finalize: .* \(status -3\)$"):
+        _lib.call("lws_finalize", h)
+    with pytest.raises(AttributeError):
+        _lib.call("lws_no_such_function", h)
+    _lib.call("lws_destroy", h)
+    assert _lib.nbytes("lws_surface_mesh_workspace", 1, 1) == 512
+    with pytest.raises(ValueError, match="surface_mesh_workspace: bad shape B=0 H=368"):
+        _lib.nbytes("lws_surface_mesh_workspace", 0, 368)
 
 
 def test_library_exports_every_symbol(hip_lib):

@@ -106,3 +106,19 @@ def test_chain_with_every_stage_off(model, batch):
     got = run_chain(model, left, right, Options())
     assert_maps(got.disp, model(left, right), "stage map")
     assert got[1:] == (None,) * 6, "no stage ran: no codes, no density, no counts"
+
+
+def test_ops_call_runs_on_the_current_stream(dev, hip_lib):
+    """ops._call, the one path every wrapper takes into the library: the launch goes to the stream that is current at the call, on
+    the tensor's device, and a None argument arrives as NULL (prev).  The result of a fresh stream is complete once THAT stream
+    is synchronised -- nothing device-wide is waited for, so an output computed on another stream would be read early."""
+    from lwsnet_amd import ops
+    low = torch.tensor([[[0.5, 1.25, 2.0], [3.0, 0.75, 1.5]]], device=dev)
+    want = host(ops.upsample_add(low, None, 4, 6))                          # default stream; the copy waits for it, and for `low`
+    assert want.shape == (1, 1, 4, 6) and want.min() > 0
+    s = torch.cuda.Stream(device=dev)
+    with torch.cuda.stream(s):
+        got = ops.upsample_add(low, None, 4, 6)
+        got_host = got.cpu()                                                # queued on s, behind the launch if the launch is on s
+    s.synchronize()
+    G.assert_bits(got_host, want, "upsample_add on a fresh stream")
