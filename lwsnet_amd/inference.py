@@ -18,7 +18,8 @@ slot, and the same workers PNG-encode them (the processes, the slots and the one
 The files written are byte-identical to the sequential loop's (tests/test_gpu_parity.py::test_cli_directory_pipeline_writes_identical_files);
 the end-to-end rate and where the time goes are logged and returned (profiles/r06/e2e_cli.txt).
 
-The flags below are not in the reference and run in the sequential mode only.  `--lr_check` (or `--occ_check`), `--speckle` and `--wmedian` are the
+The flags below are not in the reference and run in the sequential mode only; their files are written by lwsnet_amd/outputs.py, one
+writer per group of files, in the order of its write_stage.  `--lr_check` (or `--occ_check`), `--speckle` and `--wmedian` are the
 post-processing chain; the order of its steps, which step fills, and which code map the median and the geometry files are given
 are stated once, in the docstring of lwsnet_amd/postprocess.py.
 
@@ -103,8 +104,11 @@ import time
 import numpy as np
 
 from . import imageio as io
+from . import outputs as out
 from . import pipeline
 from . import postprocess as post
+from .outputs import (STIXEL_COLOUR_DEPTH, bev_to_u8, conf_to_u8, ground_to_rgb, photo_to_u8, sigma_to_u8, stixels_to_csv,  # noqa: F401
+                      stixels_to_rgb, geometry_requested as _geometry_requested)      # these stay this module's names
 from .postprocess import (add_lr_arguments, add_occ_arguments, add_speckle_arguments, add_wmedian_arguments, check_lr_arguments,
                           check_occ_arguments, check_speckle_arguments, check_wmedian_arguments)
 
@@ -150,24 +154,19 @@ def add_conf_arguments(p):
                    help="--save_disp16 / --save_depth / --save_ply / --save_normals / --save_mesh keep only the pixels whose disparity sigma is <= S pixels")
 
 
-def _geometry_requested(args):
-    """One of the files _save_geometry writes is asked for."""
-    return any(getattr(args, flag, False) for flag in ("save_disp16", "save_depth", "save_ply", "save_normals", "save_mesh", "ground", "save_ground", "stixels", "save_stixels"))
-
-
 def conf_requested(args):
     return bool(getattr(args, "save_conf", False)) or getattr(args, "conf_min", None) is not None or getattr(args, "sigma_max_keep", None) is not None
 
 
+CONF_DEFAULTS = dict(save_conf=False, sigma_max=8.0, conf_min=None, sigma_max_keep=None)
+
+
 def check_conf_arguments(p, args):
     """Rejects what the confidence outputs do not support, before any model or GPU work; sets the flags' defaults (--sigma_max: 8)."""
-    args.save_conf = getattr(args, "save_conf", False)
-    for flag in ("sigma_max", "conf_min", "sigma_max_keep"):
-        setattr(args, flag, getattr(args, flag, None))
-    if args.sigma_max is not None and not args.save_conf:
+    sigma_max_given = getattr(args, "sigma_max", None) is not None
+    post.set_defaults(args, **CONF_DEFAULTS)
+    if sigma_max_given and not args.save_conf:
         p.error("--sigma_max needs --save_conf")
-    if args.sigma_max is None:
-        args.sigma_max = 8.0
     if not (np.isfinite(args.sigma_max) and args.sigma_max > 0):
         p.error(f"--sigma_max MAX must be finite and > 0, got {args.sigma_max}")
     for flag in ("conf_min", "sigma_max_keep"):
@@ -179,20 +178,9 @@ def check_conf_arguments(p, args):
     flags = "--save_conf / --conf_min / --sigma_max_keep"
     if args.lr_check is not None or getattr(args, "occ_check", None) is not None:
         p.error(f"{flags} use the network's own confidence and do not combine with --lr_check or --occ_check")
-    if args.workers > 0:
-        p.error(f"{flags} run in the sequential mode only: use --workers 0")
+    post.sequential_only(p, args, flags, "run")
     if (args.conf_min is not None or args.sigma_max_keep is not None) and not _geometry_requested(args):
         p.error("--conf_min and --sigma_max_keep mask --save_disp16 / --save_depth / --save_ply / --save_normals / --save_mesh: give one of them")
-
-
-def conf_to_u8(conf):
-    """[H,W] confidence -> the bytes of <stem>_conf.png: rint(clip(conf, 0, 1) * 255)."""
-    return np.rint(np.clip(np.asarray(conf, np.float64), 0.0, 1.0) * 255.0).astype(np.uint8)
-
-
-def sigma_to_u8(sigma, sigma_max):
-    """[H,W] sigma in pixels -> the bytes of <stem>_sigma.png: rint(min(sigma, MAX) * 255 / MAX)."""
-    return np.rint(np.minimum(np.asarray(sigma, np.float64), float(sigma_max)) * 255.0 / float(sigma_max)).astype(np.uint8)
 
 
 class _ConfModel:
@@ -223,19 +211,8 @@ def check_rectify_arguments(p, args):
         if args.save_rect:
             p.error("--save_rect needs --rectify PATH")
         return
-    if args.workers > 0:
-        p.error("--rectify runs in the sequential mode only: use --workers 0")
-    if os.path.isdir(args.rectify):
-        if args.left_img:
-            p.error("--rectify: a folder of calibration files needs directory mode (--img_path); give a file with --left_img")
-        paths = [_frame_file(args.rectify, li) for li in _list_pairs(args)[0]]
-    else:
-        paths = [args.rectify]
-    for path in paths:
-        try:
-            RectifyCalib.from_kitti(path)
-        except (OSError, ValueError) as e:
-            p.error(f"--rectify: cannot read {path}: {e}")
+    post.sequential_only(p, args, "--rectify")
+    _check_calibration_files(p, args, "rectify", args.rectify, RectifyCalib.from_kitti)
 
 
 def add_geometry_arguments(p):
@@ -293,21 +270,39 @@ def _frame_file(path, left_path):
     return os.path.join(path, os.path.splitext(os.path.basename(left_path))[0].split("_")[0] + ".txt")
 
 
-def _calib_path(args, left_path):
-    return _frame_file(args.calib, left_path)
+def _geometry_defaults(args):
+    """The surface, stixel and ground flags' defaults, in the order in which the log's argument lines have shown them; --save_stixels
+    implies --stixels, and both and --save_ground imply --ground."""
+    post.set_defaults(args, save_normals=False, save_mesh=False, max_jump=1.0, save_ground=False, save_stixels=False, stixels=False,
+                      stixel_width=8, stixel_layers=2, ground=False, ground_tol=0.2, max_height=3.0)
+    args.stixels = args.stixels or args.save_stixels
+    args.ground = args.ground or args.save_ground or args.stixels
+
+
+def _check_calibration_files(p, args, flag, path, read):
+    """--calib / --rectify PATH: a parser error unless `read` reads the file or, for a folder, the file of every frame."""
+    paths = [path]
+    if os.path.isdir(path):
+        if args.left_img:
+            p.error(f"--{flag}: a folder of calibration files needs directory mode (--img_path); give a file with --left_img")
+        paths = [_frame_file(path, li) for li in _list_pairs(args)[0]]
+    for f in paths:
+        try:
+            read(f)
+        except (OSError, ValueError) as e:
+            p.error(f"--{flag}: cannot read {f}: {e}")
+
+
+def _needs_camera(p, args, flags):
+    """A parser error for `flags` (their names as the sentence's subject) when nothing gives a camera: --calib, --camera or --rectify."""
+    if args.calib is None and args.camera is None and getattr(args, "rectify", None) is None:
+        p.error(f"{flags} need a camera: --calib PATH or --camera FX FY CX CY BASELINE")
 
 
 def check_geometry_arguments(p, args):
     """Rejects what the geometry outputs do not support, before any model or GPU work; reads every calibration file."""
     from .geometry import Camera
-    args.save_normals, args.save_mesh = getattr(args, "save_normals", False), getattr(args, "save_mesh", False)
-    args.max_jump = getattr(args, "max_jump", 1.0)
-    args.save_ground = getattr(args, "save_ground", False)
-    args.save_stixels = getattr(args, "save_stixels", False)
-    args.stixels = getattr(args, "stixels", False) or args.save_stixels
-    args.stixel_width, args.stixel_layers = getattr(args, "stixel_width", 8), getattr(args, "stixel_layers", 2)
-    args.ground = getattr(args, "ground", False) or args.save_ground or args.stixels
-    args.ground_tol, args.max_height = getattr(args, "ground_tol", 0.2), getattr(args, "max_height", 3.0)
+    _geometry_defaults(args)
     surface = args.save_normals or args.save_mesh
     outputs = args.save_disp16 or args.save_depth or args.save_ply or surface
     if not (np.isfinite(args.ground_tol) and np.isfinite(args.max_height) and 0 <= args.ground_tol <= args.max_height):
@@ -318,39 +313,25 @@ def check_geometry_arguments(p, args):
         p.error(f"--min_disp must be finite and > 0, got {args.min_disp}")
     if not args.max_depth > 0:
         p.error(f"--max_depth must be > 0, got {args.max_depth}")
-    if (args.save_depth or args.save_ply or surface) and args.calib is None and args.camera is None and getattr(args, "rectify", None) is None:
-        p.error("--save_depth, --save_ply, --save_normals and --save_mesh need a camera: --calib PATH or --camera FX FY CX CY BASELINE")
+    if args.save_depth or args.save_ply or surface:
+        _needs_camera(p, args, "--save_depth, --save_ply, --save_normals and --save_mesh")
     if not 1 <= args.stixel_width <= 64:
         p.error(f"--stixel_width must be in 1 .. 64, got {args.stixel_width}")
     if not 1 <= args.stixel_layers <= 4:
         p.error(f"--stixel_layers must be in 1 .. 4, got {args.stixel_layers}")
-    if args.stixels and args.calib is None and args.camera is None and getattr(args, "rectify", None) is None:
-        p.error("--stixels and --save_stixels need a camera: --calib PATH or --camera FX FY CX CY BASELINE")
-    if args.stixels and args.workers > 0:
-        p.error("--stixels / --save_stixels run in the sequential mode only: use --workers 0")
-    if args.ground and args.calib is None and args.camera is None and getattr(args, "rectify", None) is None:
-        p.error("--ground and --save_ground need a camera: --calib PATH or --camera FX FY CX CY BASELINE")
-    if args.ground and args.workers > 0:
-        p.error("--ground / --save_ground run in the sequential mode only: use --workers 0")
-    if outputs and args.workers > 0:
-        p.error("--save_disp16 / --save_depth / --save_ply / --save_normals / --save_mesh run in the sequential mode only: use --workers 0")
+    for name in ("stixels", "ground"):
+        if getattr(args, name):
+            _needs_camera(p, args, f"--{name} and --save_{name}")
+            post.sequential_only(p, args, f"--{name} / --save_{name}", "run")
+    if outputs:
+        post.sequential_only(p, args, "--save_disp16 / --save_depth / --save_ply / --save_normals / --save_mesh", "run")
     if args.camera is not None:
         try:
             Camera(*args.camera).check()
         except ValueError as e:
             p.error(f"--camera: {e}")
     if args.calib is not None:
-        if os.path.isdir(args.calib):
-            if args.left_img:
-                p.error("--calib: a folder of calibration files needs directory mode (--img_path); give a file with --left_img")
-            paths = [_calib_path(args, li) for li in _list_pairs(args)[0]]
-        else:
-            paths = [args.calib]
-        for path in paths:
-            try:
-                Camera.from_kitti(path)
-            except (OSError, ValueError) as e:
-                p.error(f"--calib: cannot read {path}: {e}")
+        _check_calibration_files(p, args, "calib", args.calib, Camera.from_kitti)
 
 
 def add_model_arguments(p):
@@ -522,62 +503,36 @@ def inference_pipelined(model, left_imgs, right_imgs, args, log):
     return paths, stats
 
 
+def default_arguments(args):
+    """The defaults that main()'s check_* calls write, in their order, for a namespace that did not go through them (build_parser()'s
+    own, or one made by hand): the code below main() reads every flag as args.flag."""
+    post.set_defaults(args, rectify=None, save_rect=False, **post.OCC_DEFAULTS)
+    _geometry_defaults(args)
+    post.set_defaults(args, **CONF_DEFAULTS)
+    post.photometric_defaults(args, save=True)
+
+
 def inference(model, left_imgs, right_imgs, args, log):
     """inference.py:78-138."""
     import torch
-    written = []
-    warm = False
+    default_arguments(args)
+    written, warm = [], False
     opts = post.Options.from_args(args)
     geo = _geometry_requested(args)
-    rc = getattr(args, "rectify", None) is not None
     conf_on = conf_requested(args)
-    conf_mask = conf_on and (args.conf_min is not None or args.sigma_max_keep is not None)
     chain_model = _ConfModel(model) if conf_on else model
-    photo_on, save_photo = getattr(args, "photometric", False), getattr(args, "save_photo", False)
-
-    def save(path, color, stage):                                       # the colour file, then the mask and geometry files beside it
-        io.save_png(path, color)
-        written.append(path)
-        log.info("{}\t\tSave img = {}".format(ss, path))
-        if res.lr_masks is not None:
-            written.append(_save_lr_mask(path, res.lr_masks[stage], log))
-        if res.occ_masks is not None:
-            written.append(_save_occ_mask(path, res.occ_masks[stage], log))
-        if res.speckle_masks is not None:
-            written.append(_save_sp_mask(path, res.speckle_masks[stage], log))
-        if conf_on and args.save_conf and (stage == 2 or not args.left_img):    # --left_img: beside 3.png, the stage they belong to
-            written.extend(_save_conf(path, chain_model.last, args.sigma_max, log))
-        if geo:
-            keep = res.keep[stage] if res.keep is not None else None
-            if conf_mask:                                               # each map by its own stage's confidence, the refined one by stage 3's
-                from . import ops
-                low = ops.confidence_codes(chain_model.last.conf, chain_model.last.sigma, args.conf_min, args.sigma_max_keep, stages=(min(stage, 2),))
-                keep = low if keep is None else torch.where(low == 0, torch.zeros_like(keep), keep)
-            if rc:                                                      # a pixel sampled outside the raw left image: out of view
-                keep = valid_left if keep is None else torch.where(valid_left == 0, torch.full_like(keep, 2), keep)
-            written.extend(_save_geometry(path, res.disp[stage], keep, cam, left, args, log))
-        if photo_on and save_photo:
-            written.extend(_save_photo(path, photo.err[stage], photo.warped[stage], log))
-
     for li, ri in zip(left_imgs, right_imgs):
-        full = io.load_rgb(li)
-        if rc:
-            front = _rectify_frame(args, li, full, io.load_rgb(ri), model.device, geo, written, log)
-            if front is None:
-                continue
-            l_in, r_in, left, valid_left, cam, right, valid_right = front
-        else:
-            left = io.crop_bottom_right(full)
-            right = io.crop_bottom_right(io.load_rgb(ri))
-            if left is None or right is None:                           # :96-97
-                continue
-            cam = _frame_camera(args, li, *full.shape[:2]) if geo else None
-            l_in, r_in = io.to_input(left)[None], io.to_input(right)[None]
+        frame = _load_frame(args, li, ri, model.device, geo, log)
+        if frame is None:
+            continue
+        if args.rectify is not None and args.save_rect:
+            folder = os.path.dirname(args.left_img) if args.left_img else args.save_path
+            written += out.save_rect(frame, os.path.join(folder, os.path.splitext(os.path.basename(frame.path))[0]), args, log)
         for _ in range(1 if warm else 2):                   # the first frame runs twice: one warm-up in all (the reference times its first call)
             torch.cuda.synchronize(model.device)
             t0 = time.time()
-            guide = _rgb_on_device(left, model.device) if opts.needs_guide else None
-            res = post.run_chain(chain_model, l_in, r_in, opts, guide)
+            guide = out.rgb_on_device(frame.left, model.device) if opts.needs_guide else None
+            res = post.run_chain(chain_model, frame.l_in, frame.r_in, opts, guide)
             torch.cuda.synchronize(model.device)
             cost = time.time() - t0
         warm = True
@@ -586,33 +541,36 @@ def inference(model, left_imgs, right_imgs, args, log):
             for stage, (changed, refilled) in enumerate(res.wmedian_counts[:, 0].cpu().tolist()):
                 log.info("Weighted median (radius {}, sigma {:g}, fill {}): stage {} changed = {}, filled = {}".format(
                     opts.wmedian, opts.wmedian_sigma, opts.wmedian_fill, stage + 1, changed, refilled))
-        if photo_on:
-            photo = _photometric(res, left, right, valid_left if rc else None, valid_right if rc else None, getattr(args, "photo_alpha", 0.85),
-                                 save_photo, model.device, log)
-        color = None
+        conf = chain_model.last if conf_on else None
+        photo = out.photometric(frame, res, args, log) if args.photometric else None
         for stage in range(4):
             disp = res.disp[stage].squeeze(axis=[0, 1]).numpy()         # :114 (the uint8 cast is inside disparity_to_color)
             color = io.disparity_to_color(disp)
             if args.left_img:                                           # :117-122
-                save(os.path.join(os.path.dirname(args.left_img), str(stage + 1) + ".png"), color, stage)
+                written += out.write_stage(os.path.join(os.path.dirname(args.left_img), str(stage + 1) + ".png"), color, ss, frame, stage, args, log, res, conf, photo)
         if not args.left_img:                                           # :133-137 (stage-4 map only)
-            save(os.path.join(args.save_path, os.path.basename(li)), color, 3)
+            written += out.write_stage(os.path.join(args.save_path, os.path.basename(frame.path)), color, ss, frame, 3, args, log, res, conf, photo)
     return written
 
 
-def _rgb_on_device(rgb, device):
-    """A uint8 [H,W,3] image (numpy) or [1,H,W,3] device tensor as the [1,H,W,3] device tensor the kernels take."""
-    import torch
-    if isinstance(rgb, torch.Tensor):
-        return rgb
-    return torch.from_numpy(np.ascontiguousarray(rgb)[None]).to(device)
+def _load_frame(args, left_path, right_path, device, geo, log):
+    """One pair decoded and cropped (inference.py:90-103) or, with --rectify, rectified on the device, as the Frame of
+    lwsnet_amd/outputs.py; None when the frame is skipped (:96-97).  geo: a geometry output is on, so the frame needs its camera."""
+    full = io.load_rgb(left_path)
+    if args.rectify is not None:
+        return _rectify_frame(args, left_path, full, io.load_rgb(right_path), device, geo, log)
+    left = io.crop_bottom_right(full)
+    right = io.crop_bottom_right(io.load_rgb(right_path))
+    if left is None or right is None:                                   # :96-97
+        return None
+    cam = _frame_camera(args, left_path, *full.shape[:2]) if geo else None
+    return out.Frame(left_path, io.to_input(left)[None], io.to_input(right)[None], left, right, cam=cam)
 
 
-def _rectify_frame(args, left_path, raw_left, raw_right, device, geo, written, log):
-    """--rectify: one raw pair -> (left input, right input, rectified left crop uint8 [1,H,W,3], valid map of the left view, camera
-    of the crop or None), all on the device; None when the frame is skipped (rectified frame smaller than the crop) or in error
-    (image size other than the calibration's).  --save_rect: the two crops are written and their paths appended to `written`.
-    Behind the five, for --photometric: the rectified right crop and the valid map of the right view."""
+def _rectify_frame(args, left_path, raw_left, raw_right, device, geo, log):
+    """--rectify: one raw pair -> the Frame of its rectified crops, all on the device (network inputs, uint8 crops [1,H,W,3], valid
+    maps of the two views, camera of the crop or None); None when the frame is skipped (rectified frame smaller than the crop) or in
+    error (image size other than the calibration's)."""
     import torch
     from . import ops
     from .geometry import RectifyCalib
@@ -627,264 +585,21 @@ def _rectify_frame(args, left_path, raw_left, raw_right, device, geo, written, l
         return None
     raws = [torch.from_numpy(np.ascontiguousarray(img)[None]).to(device) for img in (raw_left, raw_right)]
     with torch.cuda.device(device):
-        out = ops.rectify_pair(raws[0], raws[1], calib.params(), (io.CROP_H, io.CROP_W), origin=(hr - io.CROP_H, wr - io.CROP_W))
-    cam = None
-    if geo:
-        cam = _frame_camera(args, left_path, hr, wr) or calib.camera().crop_bottom_right(hr, wr, io.CROP_H, io.CROP_W)
-    if args.save_rect:
-        folder = os.path.dirname(args.left_img) if args.left_img else args.save_path
-        stem = os.path.join(folder, os.path.splitext(os.path.basename(left_path))[0])
-        for side, img in zip(("left", "right"), out["rect"]):
-            io.save_png(f"{stem}_rect_{side}.png", img[0].cpu().numpy())
-            written.append(f"{stem}_rect_{side}.png")
-            log.info("Save rectified %s image = %s_rect_%s.png", side, stem, side)
-    return out["input"][0], out["input"][1], out["rect"][0], out["valid"][0], cam, out["rect"][1], out["valid"][1]
+        r = ops.rectify_pair(raws[0], raws[1], calib.params(), (io.CROP_H, io.CROP_W), origin=(hr - io.CROP_H, wr - io.CROP_W))
+    cam = (_frame_camera(args, left_path, hr, wr) or calib.camera().crop_bottom_right(hr, wr, io.CROP_H, io.CROP_W)) if geo else None
+    return out.Frame(left_path, *r["input"], *r["rect"], *r["valid"], cam)
 
 
 def _frame_camera(args, left_path, h, w):
     """The camera of a frame's cropped maps (None without --calib / --camera)."""
     from .geometry import Camera
     if args.calib is not None:
-        cam = Camera.from_kitti(_calib_path(args, left_path))
+        cam = Camera.from_kitti(_frame_file(args.calib, left_path))
     elif args.camera is not None:
         cam = Camera(*args.camera)
     else:
         return None
     return cam.crop_bottom_right(h, w, io.CROP_H, io.CROP_W)
-
-
-def _save_geometry(path, disp, mask, cam, left_rgb, args, log):
-    """The geometry files of the map written to `path`, beside it: <stem>_disp16.png, <stem>_depth16.png, <stem>.ply,
-    <stem>_normals.png, <stem>_mesh.ply, <stem>_ground.png, <stem>_bev.png, <stem>_stixels.png, <stem>_stixels.csv; with --ground the
-    road's log line, with --stixels the stixels'.  mask: the left-right
-    check's codes (only code-1 pixels kept) or None."""
-    import torch
-
-    from . import ops
-    from .geometry import write_mesh_ply, write_ply
-    stem = os.path.splitext(path)[0]
-    written = []
-    if args.save_disp16 or args.save_depth:
-        _, depth16, disp16 = ops.depth_maps(disp, cam, mask, args.min_disp, args.max_depth, depth=False, depth16=args.save_depth,
-                                            disp16=args.save_disp16)
-        for t, suffix in ((disp16, "_disp16.png"), (depth16, "_depth16.png")):
-            if t is not None:
-                io.save_png_gray16(stem + suffix, t[0, 0].cpu().numpy())
-                written.append(stem + suffix)
-                log.info("Save {} = {}".format(suffix[1:-4], stem + suffix))
-    if args.save_ply:
-        rgb = _rgb_on_device(left_rgb, disp.device)
-        points, counts = ops.point_cloud(disp, cam, mask, rgb, args.min_disp, args.max_depth)
-        n = int(counts[0])
-        write_ply(stem + ".ply", points[0, :n].cpu().numpy(), n)
-        written.append(stem + ".ply")
-        log.info("Save point cloud ({} points) = {}".format(n, stem + ".ply"))
-    if getattr(args, "save_normals", False):
-        _, n8 = ops.surface_normals(disp, cam, mask, args.min_disp, args.max_depth, args.max_jump, normals=False, normals8=True)
-        io.save_png(stem + "_normals.png", n8[0].cpu().numpy())
-        written.append(stem + "_normals.png")
-        log.info("Save normal map = {}".format(stem + "_normals.png"))
-    if getattr(args, "save_mesh", False):
-        rgb = _rgb_on_device(left_rgb, disp.device)
-        mesh = ops.surface_mesh(disp, cam, mask, rgb, args.min_disp, args.max_depth, args.max_jump)
-        n, m = (int(v) for v in mesh.counts[0].cpu())
-        write_mesh_ply(stem + "_mesh.ply", mesh.points[0, :n].cpu().numpy(), n, mesh.faces[0, :m].cpu().numpy(), mesh.vnormals[0, :n].cpu().numpy())
-        written.append(stem + "_mesh.ply")
-        log.info("Save mesh ({} vertices, {} faces) = {}".format(n, m, stem + "_mesh.ply"))
-    if getattr(args, "ground", False):
-        ground = []
-        written.extend(_ground(stem, disp, mask, cam, left_rgb, args, log, ground))
-        if getattr(args, "stixels", False):
-            written.extend(_stixels(stem, disp, cam, ground[0], left_rgb, args, log))
-    return written
-
-
-GROUND_COLOURS = np.array([[0, 0, 0], [0, 200, 0], [255, 0, 0], [0, 128, 255], [255, 0, 255], [128, 128, 128]], np.uint8)   # by code
-
-
-def ground_to_rgb(codes, left_rgb):
-    """<stem>_ground.png: the colour of each pixel's code (GROUND_COLOURS: invalid black, ground green, obstacle red, overhead blue,
-    below magenta, no plane grey) averaged with the left image's grey, (77 r + 150 g + 29 b + 128) >> 8; integers throughout."""
-    rgb = np.asarray(left_rgb).astype(np.uint32)
-    grey = (77 * rgb[..., 0] + 150 * rgb[..., 1] + 29 * rgb[..., 2] + 128) >> 8
-    return ((GROUND_COLOURS[np.asarray(codes)].astype(np.uint32) + grey[..., None] + 1) >> 1).astype(np.uint8)
-
-
-def bev_to_u8(hmax, max_height):
-    """<stem>_bev.png: [Gz,Gx] largest heights -> rint(min(h / max_height, 1) * 255), 0 for an empty cell, row 0 the farthest."""
-    h = np.asarray(hmax, np.float64)[::-1]
-    with np.errstate(all="ignore"):
-        v = np.where(h > 0, np.minimum(h / float(max_height), 1.0), 0.0)
-    return np.rint(v * 255.0).astype(np.uint8)
-
-
-def _ground(stem, disp, mask, cam, left_rgb, args, log, result=None):
-    """--ground: the road of one map (ops.ground) as a log line; --save_ground: <stem>_ground.png and <stem>_bev.png.  result: a list
-    that receives the GroundResult."""
-    from . import ops
-    from .geometry import GroundPlane
-    res = ops.ground(disp, cam, mask, args.min_disp, args.max_depth, maxdisp=args.max_disparity, ground_tol=args.ground_tol,
-                     max_height=args.max_height)
-    if result is not None:
-        result.append(res)
-    info, counts = res.info[0].cpu().tolist(), res.counts[0].cpu().tolist()
-    gp = GroundPlane.from_plane(res.plane[0].cpu().numpy(), cam) if info[0] == 0 else None
-    pose = "height = {:.3f} m, pitch = {:.2f} deg, roll = {:.2f} deg".format(gp.height, gp.pitch_deg, gp.roll_deg) if gp else "no plane"
-    valid = max(sum(counts[1:]), 1)
-    log.info("Ground: status = {}, {}, inliers = {:.4f} of the valid pixels, {}".format(
-        ops.GROUND_STATUS[info[0]], pose, info[4] / valid, ", ".join("{} = {}".format(n, c) for n, c in zip(ops.GROUND_CODES, counts))))
-    written = []
-    if getattr(args, "save_ground", False):
-        left = left_rgb[0].cpu().numpy() if not isinstance(left_rgb, np.ndarray) else left_rgb
-        io.save_png(stem + "_ground.png", ground_to_rgb(res.codes[0, 0].cpu().numpy(), left))
-        with open(stem + "_bev.png", "wb") as f:
-            f.write(io.encode_png_gray(bev_to_u8(res.bev_hmax[0].cpu().numpy(), args.max_height)))
-        written += [stem + "_ground.png", stem + "_bev.png"]
-        log.info("Save ground codes = {}, bird's-eye heights = {}".format(stem + "_ground.png", stem + "_bev.png"))
-    return written
-
-
-STIXEL_COLOUR_DEPTH = 60.0          # metres: the far end of the depth ramp of <stem>_stixels.png
-
-
-def stixels_to_rgb(rows, vals, left_rgb, width, max_depth_for_colour):
-    """<stem>_stixels.png: the left image's grey, (77 r + 150 g + 29 b + 128) >> 8, with each stixel's rectangle x0 .. x1 by y_top ..
-    y_base averaged with the colour of its depth: t = min(z / max_depth_for_colour, 1), (r, g, b) = rint(255 * (1 - t, 2 min(t, 1 - t),
-    t)) -- near red, far blue.  rows, vals: one image's [S,layers,4]; the layers are drawn far to near, so the nearest shows."""
-    rgb = np.asarray(left_rgb).astype(np.uint32)
-    grey = (77 * rgb[..., 0] + 150 * rgb[..., 1] + 29 * rgb[..., 2] + 128) >> 8
-    out = np.repeat(grey[..., None], 3, axis=2)
-    rows, vals = np.asarray(rows), np.asarray(vals, np.float64)
-    W = grey.shape[1]
-    for layer in range(rows.shape[1] - 1, -1, -1):
-        for s in range(rows.shape[0]):
-            n, y_top, y_base, _ = (int(v) for v in rows[s, layer])
-            if n <= 0:
-                continue
-            t = min(max(vals[s, layer, 1] / float(max_depth_for_colour), 0.0), 1.0)
-            colour = np.rint(255.0 * np.array([1.0 - t, 2.0 * min(t, 1.0 - t), t])).astype(np.uint32)
-            x0, x1 = s * width, min((s + 1) * width, W) - 1
-            out[y_top:y_base + 1, x0:x1 + 1] = (colour + grey[y_top:y_base + 1, x0:x1 + 1, None] + 1) >> 1
-    return out.astype(np.uint8)
-
-
-STIXEL_CSV_HEADER = "strip,layer,x0,x1,y_top,y_base,n,disparity,z,x,height"
-
-
-def stixels_to_csv(rows, vals, width, W):
-    """<stem>_stixels.csv as a string: STIXEL_CSV_HEADER, then one line per non-empty slot of one image's [S,layers,4] rows and vals,
-    strips left to right, layers nearest first; the four values with six decimals."""
-    rows, vals = np.asarray(rows), np.asarray(vals)
-    lines = [STIXEL_CSV_HEADER]
-    for s in range(rows.shape[0]):
-        for layer in range(rows.shape[1]):
-            n, y_top, y_base, _ = (int(v) for v in rows[s, layer])
-            if n > 0:
-                x0, x1 = s * width, min((s + 1) * width, W) - 1
-                lines.append(",".join([str(v) for v in (s, layer, x0, x1, y_top, y_base, n)] + ["{:.6f}".format(float(v)) for v in vals[s, layer]]))
-    return "\n".join(lines) + "\n"
-
-
-def _stixels(stem, disp, cam, ground, left_rgb, args, log):
-    """--stixels: the stixels of one map (ops.stixels on the codes and heights of its GroundResult) as a log line; --save_stixels:
-    <stem>_stixels.png and <stem>_stixels.csv."""
-    from . import ops
-    res = ops.stixels(disp, cam, ground.codes, ground.height, args.min_disp, args.max_depth, width=args.stixel_width,
-                      maxdisp=args.max_disparity, layers=args.stixel_layers)
-    rows, vals = res.rows[0].cpu().numpy(), res.vals[0].cpu().numpy()
-    found = rows[..., 0] > 0
-    nearest = "none"
-    if found.any():
-        s, layer = np.unravel_index(np.argmin(np.where(found, vals[..., 1], np.inf)), found.shape)
-        nearest = "z = {:.2f} m, X = {:.2f} m".format(float(vals[s, layer, 1]), float(vals[s, layer, 2]))
-    log.info("Stixels: {} in {} strips of {} columns x {} layers, nearest: {}".format(int(found.sum()), rows.shape[0], args.stixel_width,
-                                                                                     rows.shape[1], nearest))
-    written = []
-    if getattr(args, "save_stixels", False):
-        left = left_rgb[0].cpu().numpy() if not isinstance(left_rgb, np.ndarray) else left_rgb
-        io.save_png(stem + "_stixels.png", stixels_to_rgb(rows, vals, left, args.stixel_width, STIXEL_COLOUR_DEPTH))
-        with open(stem + "_stixels.csv", "w", encoding="ascii", newline="") as f:
-            f.write(stixels_to_csv(rows, vals, args.stixel_width, disp.shape[3]))
-        written += [stem + "_stixels.png", stem + "_stixels.csv"]
-        log.info("Save stixels = {}, {}".format(stem + "_stixels.png", stem + "_stixels.csv"))
-    return written
-
-
-def photo_to_u8(err):
-    """[H,W] photometric error in [0, 1] -> the bytes of <stem>_pe.png: rint(pe * 255)."""
-    return np.rint(np.asarray(err, np.float64) * 255.0).astype(np.uint8)
-
-
-def _photometric(res, left, right, valid_left, valid_right, alpha, want_maps, device, log):
-    """--photometric: ops.photometric on the chain's four final maps of one frame, masked by the codes the geometry files keep (with
-    --rectify: merged with the left valid map as for them; the right valid map is rvalid); logs the frame's line.  left, right: the
-    uint8 crops (numpy [H,W,3] or device [1,H,W,3])."""
-    import torch
-
-    from . import ops
-    from .metrics import photometric_means
-    keep = list(res.keep) if res.keep is not None else None
-    if valid_left is not None:
-        keep = [valid_left if k is None else torch.where(valid_left == 0, torch.full_like(k, 2), k) for k in (keep or [None] * 4)]
-    with torch.cuda.device(device):
-        photo = ops.photometric(list(res.disp), _rgb_on_device(left, device), _rgb_on_device(right, device), mask=keep, rvalid=valid_right,
-                                alpha=alpha, want_err=want_maps, want_warped=want_maps)
-    H, W = res.disp[0].shape[2:]
-    m = photometric_means(photo.sums, H * W)
-    log.info("Photometric (alpha = {:g}): ".format(alpha) + ", ".join(
-        "Stage {} = {} (density {:.4f})".format(s + 1, "none" if e is None else "{:.4f}".format(e), d)
-        for s, (e, d) in enumerate(zip(m["pe"], m["density"]))))
-    return photo
-
-
-def _save_photo(path, err, warped, log):
-    """The photometric error and the warped right image of the map written to `path`, as <stem>_pe.png and <stem>_warp.png."""
-    stem = os.path.splitext(path)[0]
-    with open(stem + "_pe.png", "wb") as f:
-        f.write(io.encode_png_gray(photo_to_u8(err[0, 0].cpu().numpy())))
-    io.save_png(stem + "_warp.png", warped[0].cpu().numpy())
-    log.info("Save photometric maps = {}_pe.png, {}_warp.png".format(stem, stem))
-    return [stem + "_pe.png", stem + "_warp.png"]
-
-
-def _save_conf(path, result, sigma_max, log):
-    """The finest stage's confidence and sigma of the pair whose map was written to `path`, as <stem>_conf.png and <stem>_sigma.png."""
-    stem = os.path.splitext(path)[0]
-    conf, sigma = result.conf[2][0, 0].cpu().numpy(), result.sigma[2][0, 0].cpu().numpy()
-    for suffix, img in (("_conf.png", conf_to_u8(conf)), ("_sigma.png", sigma_to_u8(sigma, sigma_max))):
-        with open(stem + suffix, "wb") as f:
-            f.write(io.encode_png_gray(img))
-    log.info("Confidence: mean = {:.4f}, sigma: median = {:.3f} px\t\tSave maps = {}_conf.png, {}_sigma.png".format(
-        float(conf.mean()), float(np.median(sigma)), stem, stem))
-    return [stem + "_conf.png", stem + "_sigma.png"]
-
-
-def _save_lr_mask(path, mask, log):
-    """The left-right check codes of the map written to `path`, as the grey PNG <stem>_lr.png next to it."""
-    code = mask[0, 0].cpu().numpy()
-    mpath = os.path.splitext(path)[0] + "_lr.png"
-    io.save_lr_mask_png(mpath, code)
-    log.info("LR check: density = {:.4f}\t\tSave mask = {}".format(float((code == 1).mean()), mpath))
-    return mpath
-
-
-def _save_occ_mask(path, mask, log):
-    """The occlusion check codes of the map written to `path`, as the grey PNG <stem>_occ.png next to it."""
-    code = mask[0, 0].cpu().numpy()
-    mpath = os.path.splitext(path)[0] + "_occ.png"
-    io.save_lr_mask_png(mpath, code)
-    log.info("Occlusion check: density = {:.4f}\t\tSave mask = {}".format(float((code == 1).mean()), mpath))
-    return mpath
-
-
-def _save_sp_mask(path, mask, log):
-    """The speckle filter's codes of the map written to `path`, as the grey PNG <stem>_sp.png next to it."""
-    code = mask[0, 0].cpu().numpy()
-    mpath = os.path.splitext(path)[0] + "_sp.png"
-    io.save_lr_mask_png(mpath, code)
-    log.info("Speckle filter: kept = {:.4f}, removed = {:.4f}\t\tSave codes = {}".format(float((code == 1).mean()),
-                                                                                      float((code == 3).mean()), mpath))
-    return mpath
 
 
 def main(argv=None):

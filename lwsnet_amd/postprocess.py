@@ -225,10 +225,17 @@ def add_wmedian_arguments(p):
                         "(default 0 = holes are not filled)")
 
 
-def sequential_only(p, args, flag):
-    """The stages run in the CLIs' sequential mode: a parser error for `flag` with --workers N > 0."""
+def sequential_only(p, args, flag, verb="runs"):
+    """The stages run in the CLIs' sequential mode: a parser error for `flag` (several flags: verb="run") with --workers N > 0."""
     if args.workers > 0:
-        p.error(f"{flag} runs in the sequential mode only: use --workers 0")
+        p.error(f"{flag} {verb} in the sequential mode only: use --workers 0")
+
+
+def set_defaults(args, **defaults):
+    """Writes the default of every flag that the parser left out of the namespace (argparse.SUPPRESS) or at None."""
+    for flag, value in defaults.items():
+        if getattr(args, flag, None) is None:
+            setattr(args, flag, value)
 
 
 # main flag -> (the flags that depend on it, the error when one of them comes without it)
@@ -261,9 +268,12 @@ def check_lr_arguments(p, args):
     _check_stage(p, args, "lr_check")
 
 
+OCC_DEFAULTS = dict(occ_check=None, occ_fill=False)
+
+
 def check_occ_arguments(p, args):
     """Rejects what the occlusion check does not support, --lr_check beside it included; sets the flags' defaults."""
-    args.occ_check, args.occ_fill = getattr(args, "occ_check", None), getattr(args, "occ_fill", False)
+    set_defaults(args, **OCC_DEFAULTS)
     if args.occ_check is not None and getattr(args, "lr_check", None) is not None:
         p.error("--occ_check and --lr_check are alternatives: give one of them")
     _check_stage(p, args, "occ_check")
@@ -294,16 +304,17 @@ def add_photometric_arguments(p, save=False):
                        help="with --photometric: write <stem>_pe.png, the error map as rint(pe * 255), and <stem>_warp.png, the warped right image")
 
 
+def photometric_defaults(args, save=False):
+    set_defaults(args, photometric=False, **({"save_photo": False} if save else {}), photo_alpha=0.85)
+
+
 def check_photometric_arguments(p, args, save=False):
     """Rejects what the photometric error does not support, before any model or GPU work; sets the flags' defaults (False, 0.85
     and, for the CLI that has --save_photo, False)."""
-    args.photometric = getattr(args, "photometric", False)
-    alpha = getattr(args, "photo_alpha", None)
-    if save:
-        args.save_photo = getattr(args, "save_photo", False)
-    if not args.photometric and (alpha is not None or (save and args.save_photo)):
+    alpha_given = getattr(args, "photo_alpha", None) is not None
+    photometric_defaults(args, save)
+    if not args.photometric and (alpha_given or (save and args.save_photo)):
         p.error("--photo_alpha and --save_photo need --photometric" if save else "--photo_alpha needs --photometric")
-    args.photo_alpha = 0.85 if alpha is None else alpha
     if not 0.0 <= args.photo_alpha <= 1.0:                              # (false for NaN)
         p.error(f"--photo_alpha A must be in [0, 1], got {args.photo_alpha}")
     if args.photometric:

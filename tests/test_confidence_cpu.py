@@ -164,3 +164,31 @@ def test_cli_png_encodings():
     sigma = np.array([[0.0, 1.0, 4.0, 8.0, 9.0, 0.1]], F)
     assert inference.sigma_to_u8(sigma, 8.0).tolist() == [[0, 32, 128, 255, 255, 3]]
     assert inference.conf_to_u8(conf).dtype == np.uint8
+
+
+CONF_FLAGS = "--save_conf / --conf_min / --sigma_max_keep"
+OUTPUT_FLAGS = "--save_disp16 / --save_depth / --save_ply / --save_normals / --save_mesh"
+
+
+@pytest.mark.parametrize("extra,text", [
+    (["--sigma_max", "4"], "--sigma_max needs --save_conf"),
+    (["--save_conf", "--sigma_max", "0"], "--sigma_max MAX must be finite and > 0, got 0.0"),
+    (["--save_conf", "--sigma_max", "inf"], "--sigma_max MAX must be finite and > 0, got inf"),
+    (["--conf_min", "nan"], "--conf_min must be a number, got nan"),
+    (["--sigma_max_keep", "nan"], "--sigma_max_keep must be a number, got nan"),
+    (["--save_conf", "--occ_check", "1"], CONF_FLAGS + " use the network's own confidence and do not combine with --lr_check or --occ_check"),
+    (["--save_conf", "--workers", "2"], CONF_FLAGS + " run in the sequential mode only: use --workers 0"),
+    (["--conf_min", "0.5"], "--conf_min and --sigma_max_keep mask " + OUTPUT_FLAGS + ": give one of them"),
+    # two apply: the earlier check wins
+    (["--sigma_max", "0", "--conf_min", "nan"], "--sigma_max needs --save_conf"),
+    (["--save_conf", "--sigma_max", "0", "--conf_min", "nan"], "--sigma_max MAX must be finite and > 0, got 0.0"),
+    (["--conf_min", "nan", "--lr_check", "1"], "--conf_min must be a number, got nan"),
+    (["--conf_min", "0.5", "--lr_check", "1", "--workers", "2"], "--lr_check runs in the sequential mode only: use --workers 0"),
+    (["--sigma_max_keep", "2", "--workers", "2"], CONF_FLAGS + " run in the sequential mode only: use --workers 0"),
+])
+def test_cli_conf_error_texts(extra, text, capsys):
+    from lwsnet_amd import inference
+    with pytest.raises(SystemExit) as e:
+        inference.main(["--left_img", "nowhere/left_test.png", "--synthetic_weights", *extra])
+    assert e.value.code == 2
+    assert capsys.readouterr().err.endswith(": error: " + text + "\n")

@@ -298,3 +298,95 @@ def test_geometry_flags_default_off():
     a = inference.build_parser().parse_args([])
     assert (a.calib, a.camera, a.save_disp16, a.save_depth, a.save_ply) == (None, None, False, False, False)
     assert a.min_disp == 1.0 and a.max_depth == float("inf")
+
+
+CAMERA = ["--camera", "700", "700", "600", "180", "0.5"]
+NEEDS_CAMERA = " need a camera: --calib PATH or --camera FX FY CX CY BASELINE"
+SEQUENTIAL = " in the sequential mode only: use --workers 0"
+OUTPUTS_SEQUENTIAL = "--save_disp16 / --save_depth / --save_ply / --save_normals / --save_mesh run" + SEQUENTIAL
+OUTPUTS_CAMERA = "--save_depth, --save_ply, --save_normals and --save_mesh" + NEEDS_CAMERA
+GROUND_HEIGHTS = "--ground_tol and --max_height must be finite with 0 <= ground_tol <= max_height, got -1.0 and 3.0"
+
+
+def _error(argv, capsys):
+    """The message of the parser error `argv` ends in: argparse's last line without its "prog: error: "."""
+    err = _refused(argv, capsys)
+    assert err.endswith("\n") and ": error: " in err
+    return err[:-1].split(": error: ", 1)[1]
+
+
+@pytest.mark.parametrize("argv,text", [
+    (["--save_ply", "--min_disp", "0"], "--min_disp must be finite and > 0, got 0.0"),
+    (["--save_ply", "--min_disp", "inf"], "--min_disp must be finite and > 0, got inf"),
+    (["--save_ply", "--max_depth", "-1"], "--max_depth must be > 0, got -1.0"),
+    (["--max_depth", "nan"], "--max_depth must be > 0, got nan"),
+    (["--save_depth"], OUTPUTS_CAMERA),
+    (["--save_ply"], OUTPUTS_CAMERA),
+    (["--save_normals"], OUTPUTS_CAMERA),
+    (["--save_disp16", "--workers", "2"], OUTPUTS_SEQUENTIAL),
+    (["--save_mesh", "--workers", "1"] + CAMERA, OUTPUTS_SEQUENTIAL),
+    (["--camera", "0", "700", "600", "180", "0.5"], "--camera: camera needs finite values with fx, fy, baseline > 0; got Camera(fx=0.0, fy=700.0, cx=600.0, cy=180.0, baseline=0.5)"),
+    (["--left_img", "nowhere/left_test.png", "--calib", "."], "--calib: a folder of calibration files needs directory mode (--img_path); give a file with --left_img"),
+])
+def test_cli_geometry_error_texts(argv, text, capsys):
+    assert _error(argv, capsys) == text
+
+
+def test_cli_calib_error_text_names_the_file(tmp_path, capsys):
+    missing = str(tmp_path / "missing.txt")
+    assert _error(["--calib", missing], capsys).startswith(f"--calib: cannot read {missing}: [Errno 2] ")
+
+
+@pytest.mark.parametrize("argv,text", [
+    (["--ground_tol", "-1", "--max_jump", "-1"], GROUND_HEIGHTS),
+    (["--max_jump", "-1", "--min_disp", "0"], "--max_jump must be finite and >= 0, got -1.0"),
+    (["--min_disp", "0", "--max_depth", "-1"], "--min_disp must be finite and > 0, got 0.0"),
+    (["--max_depth", "-1", "--save_ply"], "--max_depth must be > 0, got -1.0"),
+    (["--save_ply", "--stixel_width", "0"], OUTPUTS_CAMERA),
+    (["--stixel_width", "0", "--stixel_layers", "0"], "--stixel_width must be in 1 .. 64, got 0"),
+    (["--stixel_layers", "0", "--stixels"], "--stixel_layers must be in 1 .. 4, got 0"),
+    (["--stixels", "--workers", "2"], "--stixels and --save_stixels" + NEEDS_CAMERA),
+    (["--stixels", "--workers", "2"] + CAMERA, "--stixels / --save_stixels run" + SEQUENTIAL),
+    (["--ground", "--workers", "2"], "--ground and --save_ground" + NEEDS_CAMERA),
+    (["--ground", "--save_disp16", "--workers", "2"] + CAMERA, "--ground / --save_ground run" + SEQUENTIAL),
+    (["--save_disp16", "--workers", "2", "--camera", "0", "700", "600", "180", "0.5"], OUTPUTS_SEQUENTIAL),
+    (["--save_disp16", "--lr_check", "1", "--workers", "2"], "--lr_check runs" + SEQUENTIAL),
+    (["--save_disp16", "--workers", "2", "--rectify", "nowhere.txt"], OUTPUTS_SEQUENTIAL),
+    (["--save_rect", "--save_conf", "--lr_check", "1"], "--save_rect needs --rectify PATH"),
+    (["--save_conf", "--lr_check", "1", "--photo_alpha", "0.5"],
+     "--save_conf / --conf_min / --sigma_max_keep use the network's own confidence and do not combine with --lr_check or --occ_check"),
+])
+def test_cli_earlier_check_wins(argv, text, capsys):
+    """Two errors apply to each line: the one whose check comes first is reported (the checks of check_geometry_arguments in their
+    order, then the order of main()'s check_* calls)."""
+    assert _error(argv, capsys) == text
+
+
+DEFAULT_NAMESPACE = {"max_disparity": 192, "img_path": "dataset/kitti2015/testing/", "left_img": "",
+                     "model": "results/finetune/checkpoint.pdparams", "save_path": "results/inference", "maxdisplist": [24, 5, 5],
+                     "channels_3d": 8, "layers_3d": 4, "growth_rate": [4, 1, 1], "gpu_id": 0, "synthetic_weights": False, "vis": False,
+                     "split_bf16": False, "workers": 0, "gpu_workers": 3, "lr_check": None, "lr_fill": False, "speckle": None,
+                     "speckle_diff": None, "speckle_fill": False, "wmedian": None, "wmedian_sigma": None, "wmedian_fill": None,
+                     "calib": None, "camera": None, "min_disp": 1.0, "max_depth": float("inf"), "save_disp16": False,
+                     "save_depth": False, "save_ply": False, "rectify": None, "save_rect": False}
+
+
+@pytest.mark.parametrize("argv,changed", [
+    ([], {}),
+    (["--lr_check", "1", "--lr_fill"], dict(lr_check=1.0, lr_fill=True)),
+    (["--occ_check", "0.5", "--occ_fill"], dict(occ_check=0.5, occ_fill=True)),
+    (["--speckle", "60", "--speckle_diff", "0.5", "--speckle_fill"], dict(speckle=60, speckle_diff=0.5, speckle_fill=True)),
+    (["--wmedian", "2", "--wmedian_sigma", "4", "--wmedian_fill", "3"], dict(wmedian=2, wmedian_sigma=4.0, wmedian_fill=3)),
+    (["--save_disp16", "--save_depth", "--save_ply", "--min_disp", "0.5", "--max_depth", "80"] + CAMERA,
+     dict(save_disp16=True, save_depth=True, save_ply=True, min_disp=0.5, max_depth=80.0, camera=[700.0, 700.0, 600.0, 180.0, 0.5])),
+    (["--save_normals", "--save_mesh", "--max_jump", "2", "--calib", "c.txt"], dict(save_normals=True, save_mesh=True, max_jump=2.0, calib="c.txt")),
+    (["--ground", "--save_ground", "--ground_tol", "0.3", "--max_height", "2"], dict(ground=True, save_ground=True, ground_tol=0.3, max_height=2.0)),
+    (["--stixels", "--save_stixels", "--stixel_width", "4", "--stixel_layers", "3"], dict(stixels=True, save_stixels=True, stixel_width=4, stixel_layers=3)),
+    (["--rectify", "r.txt", "--save_rect", "--workers", "2", "--gpu_workers", "1"], dict(rectify="r.txt", save_rect=True, workers=2, gpu_workers=1)),
+    (["--save_conf", "--sigma_max", "4", "--conf_min", "0.3", "--sigma_max_keep", "2"], dict(save_conf=True, sigma_max=4.0, conf_min=0.3, sigma_max_keep=2.0)),
+    (["--photometric", "--photo_alpha", "0.5", "--save_photo"], dict(photometric=True, photo_alpha=0.5, save_photo=True)),
+])
+def test_command_lines_parse_to_the_same_namespaces(argv, changed):
+    """What build_parser() alone makes of a command line, before any check_* writes a default: the flags given and no others."""
+    from lwsnet_amd import inference
+    assert vars(inference.build_parser().parse_args(argv)) == {**DEFAULT_NAMESPACE, **changed}

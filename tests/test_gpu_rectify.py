@@ -325,3 +325,50 @@ def test_inference_cli_rectify(dev, model, tmp_path):
     for n_ in ("left_test.png", "right_test.png"):
         Image.fromarray(raw[0][0, :370]).save(small / n_)
     assert inference.main(["--left_img", str(small / "left_test.png"), "--synthetic_weights", "--rectify", path]) == []
+
+
+GEOMETRY = [("--save_disp16", "_disp16.png", "Save disp16"), ("--save_depth", "_depth16.png", "Save depth16"), ("--save_ply", ".ply", "Save point"),
+            ("--save_normals", "_normals.png", "Save normal"), ("--save_mesh", "_mesh.ply", "Save mesh"), ("--save_ground", "_ground.png", "Ground: status"),
+            (None, "_bev.png", "Save ground"), ("--save_stixels", "_stixels.png", "Stixels: "), (None, "_stixels.csv", "Save stixels")]
+CHAIN = ["--save_rect", "--speckle", "60", "--wmedian", "2", "--photometric", "--save_photo"]
+
+
+def _chain_case(check, suffix, words, without=()):
+    geo = [g for g in GEOMETRY if g[0] not in without]
+    return (CHAIN + check + [g[0] for g in geo if g[0]],
+            ["_rect_left.png", "_rect_right.png", ".png", suffix, "_sp.png"] + [g[1] for g in geo] + ["_pe.png", "_warp.png"],
+            ["Save rectified", "Save rectified"] + ["Weighted median"] * 4 + ["Photometric (", "Inference 4", words, "Speckle filter:"]
+            + [g[2] for g in geo] + ["Save photometric"])
+
+
+# With --lr_check 1 --speckle 60 no pixel of this pair survives, and an empty point cloud cannot be written (ply_bytes refuses a
+# view with a zero in its shape), so that line goes without the two PLY files; they are in the other two lines.
+CASES = {"lr": _chain_case(["--lr_check", "1"], "_lr.png", "LR check:", without=("--save_ply", "--save_mesh")),
+         "occ": _chain_case(["--occ_check", "1"], "_occ.png", "Occlusion check:"),
+         "confidence": (["--save_conf", "--conf_min", "0.3", "--sigma_max_keep", "4"] + [g[0] for g in GEOMETRY if g[0]],
+                        [".png", "_conf.png", "_sigma.png"] + [g[1] for g in GEOMETRY], ["Inference 4", "Confidence: "] + [g[2] for g in GEOMETRY])}
+
+
+@pytest.mark.parametrize("extra,files,lines", list(CASES.values()), ids=list(CASES))
+def test_inference_cli_every_output_in_order(extra, files, lines, tmp_path, caplog):
+    """One raw frame in directory mode with every output that combines switched on: the names and the order of the returned paths,
+    and the order of the log lines between "Begin inference!" and "End inference!" by their leading words.  (What each file
+    holds is the business of its feature's own test.)"""
+    import logging
+
+    from lwsnet_amd import inference
+    src = os.path.join(ROOT, "tests", "golden", "kitti_pair")
+    for folder, name in (("image_2", "left_test.png"), ("image_3", "right_test.png")):
+        os.makedirs(tmp_path / "kitti" / folder)
+        shutil.copy(os.path.join(src, name), tmp_path / "kitti" / folder / "000007_10.png")
+    path = R.write_kitti(tmp_path / "calib_cam_to_cam.txt", R.kitti_like_calib((375, 1242))[0])
+    with caplog.at_level(logging.INFO, logger="lwsnet_amd.inference"):
+        written = inference.main(["--img_path", str(tmp_path / "kitti"), "--save_path", str(tmp_path / "out"), "--synthetic_weights", "--rectify", path,
+                                  "--camera", "721.5", "721.5", "609.5", "172.8", "0.54", *extra])
+    assert written == [str(tmp_path / "out" / ("000007_10" + f)) for f in files]
+    assert all(os.path.getsize(w) > 0 for w in written)
+    messages = [r.getMessage() for r in caplog.records if r.name == "lwsnet_amd.inference"]
+    messages = messages[messages.index("Begin inference!") + 1:messages.index("End inference!")]
+    assert len(messages) == len(lines), messages
+    for message, words in zip(messages, lines):
+        assert message.startswith(words), (message, words)

@@ -359,3 +359,15 @@ def test_ground_png_helpers():
     bev = inference.bev_to_u8(np.array([[0.0, 1.5], [3.0, 4.0]], F), 3.0)
     assert bev.tolist() == [[255, 255], [0, 128]]                               # row 0 the farthest; rint(127.5) = 128
     assert inference.bev_to_u8(np.array([[0.0, 1.0]], F), 0.0).tolist() == [[0, 255]]
+
+
+@pytest.mark.parametrize("flag", ["--ground", "--save_ground"])
+def test_cli_ground_error_texts(flag, capsys):
+    assert _cli_refused([flag], capsys).endswith(": error: --ground and --save_ground need a camera: --calib PATH or --camera FX FY CX CY BASELINE\n")
+    assert _cli_refused([flag, "--workers", "2"], capsys).endswith("--camera FX FY CX CY BASELINE\n"), "the camera comes before the mode"
+    assert _cli_refused([flag, "--workers", "2"] + CAMERA, capsys).endswith(
+        ": error: --ground / --save_ground run in the sequential mode only: use --workers 0\n")
+    assert _cli_refused([flag, "--ground_tol", "4"] + CAMERA, capsys).endswith(
+        ": error: --ground_tol and --max_height must be finite with 0 <= ground_tol <= max_height, got 4.0 and 3.0\n")
+    assert _cli_refused([flag, "--max_height", "inf", "--max_jump", "-1"], capsys).endswith(
+        ": error: --ground_tol and --max_height must be finite with 0 <= ground_tol <= max_height, got 0.2 and inf\n"), "the heights come first"

@@ -357,3 +357,16 @@ def test_surface_flags_default_off():
     a = p.parse_args(["--save_normals", "--save_mesh", "--max_jump", "2.5"] + CAMERA)
     inference.check_geometry_arguments(p, a)
     assert (a.save_normals, a.save_mesh, a.max_jump) == (True, True, 2.5)
+
+
+@pytest.mark.parametrize("value,shown", [("-1", "-1.0"), ("nan", "nan"), ("inf", "inf")])
+def test_cli_max_jump_error_text(value, shown, capsys):
+    assert _refused(["--max_jump", value], capsys).endswith(f": error: --max_jump must be finite and >= 0, got {shown}\n")
+
+
+def test_cli_surface_error_texts(capsys):
+    camera = ": error: --save_depth, --save_ply, --save_normals and --save_mesh need a camera: --calib PATH or --camera FX FY CX CY BASELINE\n"
+    assert _refused(["--save_mesh"], capsys).endswith(camera)
+    assert _refused(["--save_normals", "--workers", "2"], capsys).endswith(camera), "the camera comes before the mode"
+    assert _refused(["--save_normals", "--workers", "2"] + CAMERA, capsys).endswith(
+        ": error: --save_disp16 / --save_depth / --save_ply / --save_normals / --save_mesh run in the sequential mode only: use --workers 0\n")

@@ -312,3 +312,25 @@ def test_cli_defaults_are_unchanged(tmp_path):
     a = p.parse_args(["--rectify", R.write_kitti(tmp_path / "c.txt", R.kitti_like_calib()[0]), "--save_rect", "--save_ply"])
     inference.check_geometry_arguments(p, a)            # the calibration brings its own camera
     inference.check_rectify_arguments(p, a)
+
+
+def test_cli_rectify_error_texts(tmp_path, capsys):
+    from lwsnet_amd import inference
+
+    def error(argv):
+        with pytest.raises(SystemExit) as e:
+            inference.main(["--synthetic_weights"] + argv)
+        assert e.value.code == 2
+        return capsys.readouterr().err.rstrip("\n").split(": error: ", 1)[1]
+
+    calib = R.write_kitti(tmp_path / "calib.txt", R.kitti_like_calib()[0])
+    missing = str(tmp_path / "missing.txt")
+    assert error(["--save_rect"]) == "--save_rect needs --rectify PATH"
+    assert error(["--rectify", calib, "--workers", "4"]) == "--rectify runs in the sequential mode only: use --workers 0"
+    assert error(["--rectify", missing, "--workers", "4"]) == "--rectify runs in the sequential mode only: use --workers 0", "the mode before the file"
+    assert error(["--rectify", str(tmp_path), "--left_img", "nowhere/left_test.png"]) == (
+        "--rectify: a folder of calibration files needs directory mode (--img_path); give a file with --left_img")
+    assert error(["--rectify", missing]).startswith(f"--rectify: cannot read {missing}: [Errno 2] ")
+    # the geometry check runs first and takes the calibration's camera on trust; the confidence check runs after the rectify check
+    assert error(["--rectify", missing, "--save_ply", "--max_depth", "0"]) == "--max_depth must be > 0, got 0.0"
+    assert error(["--rectify", missing, "--sigma_max", "4"]).startswith("--rectify: cannot read ")

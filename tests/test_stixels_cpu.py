@@ -320,3 +320,14 @@ def test_stixel_file_helpers():
     assert rgb[1, 0].tolist() == rgb[3, 1].tolist() == [(223 + 100 + 1) >> 1, (64 + 100 + 1) >> 1, (32 + 100 + 1) >> 1]   # z = 7.5 of 60: t = 0.125
     assert rgb[0, 4].tolist() == [(191 + 100 + 1) >> 1, (128 + 100 + 1) >> 1, (64 + 100 + 1) >> 1]                       # t = 0.25
     assert rgb[3, 4].tolist() == [50, 50, 178]                                  # t = 1: blue
+
+
+@pytest.mark.parametrize("flag", ["--stixels", "--save_stixels"])
+def test_cli_stixel_error_texts(flag, capsys):
+    camera = ": error: --stixels and --save_stixels need a camera: --calib PATH or --camera FX FY CX CY BASELINE\n"
+    assert _cli_refused([flag], capsys).endswith(camera)
+    assert _cli_refused([flag, "--workers", "2"], capsys).endswith(camera), "the camera comes before the mode, the stixels' before the ground's"
+    assert _cli_refused([flag, "--workers", "2"] + CAMERA, capsys).endswith(
+        ": error: --stixels / --save_stixels run in the sequential mode only: use --workers 0\n")
+    assert _cli_refused([flag, "--stixel_width", "65"], capsys).endswith(": error: --stixel_width must be in 1 .. 64, got 65\n"), "sizes before the camera"
+    assert _cli_refused([flag, "--stixel_layers", "5"] + CAMERA, capsys).endswith(": error: --stixel_layers must be in 1 .. 4, got 5\n")
