@@ -138,6 +138,17 @@ __device__ __forceinline__ void store_act4(float *p, float4 v, int wt)
 }
 static inline int use_wt_stores(size_t out_bytes) { return out_bytes <= ((size_t)40 << 20) ? 1 : 0; }
 
+// The shader-clock counter (s_memtime) and the 100 MHz wall clock (s_memrealtime), read back to back and waited for once: the
+// clock a stretch of code really ran at is d shader / d wall x 100 MHz.
+__device__ __forceinline__ void clock_pair(unsigned long long &shader, unsigned long long &wall)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(shader), "=s"(wall)::"memory");
+#else
+    shader = wall = 0;
+#endif
+}
+
 // Diagnostic builds only (LWS_EXTRA_FLAGS="-DLWS_STAMPS=<kernel id>"; tools/stamps.py): every workgroup of the selected
 // kernel stores s_memtime stamps of its phases (slots 0..5) and the s_memrealtime (100 MHz) of its first and latest stamp
 // (slots 6, 7: the in-kernel clock = d s_memtime / d s_memrealtime x 100 MHz) in a per-translation-unit buffer.  The shipped library compiles
@@ -150,7 +161,7 @@ static inline int use_wt_stores(size_t out_bytes) { return out_bytes <= ((size_t
     {                                                                                                              \
         __builtin_amdgcn_sched_barrier(0);                                                                         \
         unsigned long long t_, r_;                                                                                 \
-        asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_), "=s"(r_)::"memory");  \
+        clock_pair(t_, r_);                                                                                        \
         __builtin_amdgcn_sched_barrier(0);                                                                         \
         const unsigned bid = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);                       \
         if (threadIdx.x == 0 && threadIdx.y == 0 && bid < 4096) {                                                  \

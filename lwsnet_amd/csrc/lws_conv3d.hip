@@ -10,10 +10,12 @@
 // every output is ONE float32 fma chain from 0 over taps (kd,kh,kw) outer, input channel inner, ascending.
 // v_mfma_f32_16x16x4_f32 computes exactly such a k-ordered chain, so the MFMA kernels keep that contract.
 //
-//   k_conv3d_first8 / k_conv3d_first16   cin = 1 -> C3   fp32 MFMA (K = 27 taps)
+//   k_conv3d_first8 / k_conv3d_first16   cin = 1 -> C3   fp32 MFMA (K = 27 taps); first16 can also build the stage-1 volume
 //   k_conv3d_mid16  C3 % 16 == 0     fp32 MFMA implicit GEMM, M = cout tile, N = 16 voxels along x
+//   k_conv3d_mid16x C3 == 32         the same tile on split-bf16 operands (option split_bf16 bit 0; NOT the oracle's chain)
 //   k_conv3d_mid8q  C3 == 8          v_mfma_f32_4x4x1_16B_f32 with A-block broadcast: 4 couts x 64 voxels, no padding
-//   k_conv3d_last   C3 -> 1 + skip   VALU (K = 27*C3)
+//   k_conv3d_mid8x  C3 == 8          parity-row tile on split-bf16 operands (option split_bf16 bit 1; NOT the oracle's chain)
+//   k_conv3d_last   C3 -> 1 + skip   VALU (K = 27*C3), optionally + soft-argmin over D
 #include <hip/hip_ext.h>
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
@@ -27,6 +29,11 @@ namespace lws {
 LWS_DEFINE_STAMPS(conv3d)
 
 __device__ __forceinline__ float bn_relu(float x, float s, float t) { return fmaxf(fmaf(x, s, t), 0.0f); }
+// the epilogue of every layer but the last: the NEXT layer's BatchNorm + ReLU on the 4 output channels a lane holds
+__device__ __forceinline__ float4 bn_relu4(const floatx4 &acc, const float4 &s, const float4 &t)
+{
+    return make_float4(bn_relu(acc[0], s.x, t.x), bn_relu(acc[1], s.y, t.y), bn_relu(acc[2], s.z, t.z), bn_relu(acc[3], s.w, t.w));
+}
 
 // tile index (already XCD-contiguous, xcd_tile) -> tile coordinates: d fastest, then x, then y -- the tiles that share halo
 // planes along d (2 of the 5 planes a 3-deep tile reads) and along y are then neighbours in an XCD's run and co-resident, so
@@ -38,6 +45,21 @@ __device__ __forceinline__ void tile_coords(int tile, int tiles_x, int tiles_d, 
     tile /= tiles_d;
     tx = tile % tiles_x;
     ty = tile / tiles_x;
+}
+
+// One staging item of a halo tile: voxel v of the HY x HX halo (x fastest, one voxel of border) around the output tile that starts
+// at (d0, y0, x0).  Returns whether the item holds data -- `item` (the caller's surplus-item test, it differs per kernel) and the
+// voxel inside the volume; outside is the convolution's zero padding -- and yields its element offset in a channels-last
+// [D, h, w, C] array, voxel * C + sub, or 0: callers load unconditionally (padding and surplus items read element 0, no branch
+// per load) and write the zero into LDS.
+template <int HY, int HX>
+__device__ __forceinline__ bool halo_item(int v, int item, int items, int d0, int y0, int x0, int D, int h, int w, int C, int sub, int64_t &off)
+{
+    const int hx = v % HX, t2 = v / HX, hy = t2 % HY, hd = t2 / HY;
+    const int gd = d0 + hd - 1, gy = y0 + hy - 1, gx = x0 + hx - 1;
+    const bool ok = item < items && gd >= 0 && gd < D && gy >= 0 && gy < h && gx >= 0 && gx < w;
+    off = ok ? (((int64_t)gd * h + gy) * w + gx) * C + sub : 0;
+    return ok;
 }
 
 // compile-time component select (j is always a constant after unrolling)
@@ -63,51 +85,46 @@ __device__ __forceinline__ float f4(const float4 &v, int j) { return j == 0 ? v.
 // of every workgroup reads the same 27*C3*C3*4 bytes, so they stay L2/L1-resident.
 // Each wave owns TD*TY/4 rows x all C3/16 output-channel tiles: (TD*TY/4)*(C3/16) independent
 // accumulator chains, which covers the 40-cycle dependent-issue latency of the 32-cycle MFMA.
+// (8-wave workgroups, the output-channel tiles split over two groups of waves, measured within 1 % of this split in round 1 --
+// profiles/NOTES.md -- and the two template parameters that expressed them are gone.)
 // =============================================================================================
-constexpr bool MID16_INTERLEAVE = true;   // see the inner loop of k_conv3d_mid16
-
-template <int C3, int TD, int TY, int WR, int WM>
+template <int C3, int TD, int TY>
 struct Mid16Cfg {
-    static constexpr int MT = C3 / 16;          // output-channel tiles of the layer
+    static constexpr int MT = C3 / 16;          // output-channel tiles of the layer (every wave computes all of them)
     static constexpr int Q = C3 / 16;           // input-channel groups per tap
-    static constexpr int NW = WR * WM;          // waves per workgroup
-    static constexpr int NT = 64 * NW;
+    static constexpr int NW = 4, NT = 64 * NW;
     static constexpr int ROWS = TD * TY;
-    static constexpr int RW = ROWS / WR;        // rows per wave
-    static constexpr int MTW = MT / WM;         // output-channel tiles per wave
+    static constexpr int RW = ROWS / NW;        // rows per wave
     static constexpr int HD = TD + 2, HY = TY + 2, HX = 18;
     static constexpr int VS = C3 + 4;           // LDS voxel stride in dwords
     static constexpr int NVOX = HD * HY * HX;
     static constexpr int ITEMS = NVOX * Q;      // staging items: (voxel, 16-channel group)
     static constexpr int SITER = (ITEMS + NT - 1) / NT;
     static constexpr int LDS_BYTES = NVOX * VS * 4;
-    static_assert(NW == 4 || NW == 8, "4 or 8 waves per workgroup");
-    static_assert(ROWS % WR == 0 && MT % WM == 0, "tile must split evenly over the waves");
-    static_assert(RW * MTW >= 2 || NW == 8, "need >= 2 independent accumulator chains per SIMD");
+    static_assert(ROWS % NW == 0, "rows must split evenly over the waves");
+    static_assert(RW * MT >= 2, "need >= 2 independent accumulator chains per SIMD");
 };
 
-template <int C3, int TD, int TY, int WR, int WM>
-__global__ __launch_bounds__(64 * WR * WM) void k_conv3d_mid16(const float *__restrict__ in,     // [B,D,h,w,C3]
-                                                              const float4 *__restrict__ wpk,   // packed A fragments
-                                                              const float *__restrict__ bn_s,   // next layer BN [C3]
-                                                              const float *__restrict__ bn_t,
-                                                              float *__restrict__ out, int D, int h, int w,
-                                                              int tiles_x, int tiles_y, int wt, int tiles_d,
-                                                              unsigned long long *__restrict__ clk)
+template <int C3, int TD, int TY>
+__global__ __launch_bounds__(256) void k_conv3d_mid16(const float *__restrict__ in,     // [B,D,h,w,C3]
+                                                      const float4 *__restrict__ wpk,   // packed A fragments
+                                                      const float *__restrict__ bn_s,   // next layer BN [C3]
+                                                      const float *__restrict__ bn_t,
+                                                      float *__restrict__ out, int D, int h, int w,
+                                                      int tiles_x, int tiles_y, int tiles_d,
+                                                      unsigned long long *__restrict__ clk)
 {
     // clk != nullptr (lws_clock_stamp only; kernel-uniform, so a scalar branch): the first 64 workgroups leave the shader-clock
     // counter (s_memtime) and the 100 MHz wall clock (s_memrealtime) of their first and last instruction -- the clock this
     // kernel really ran at is d s_memtime / d s_memrealtime x 100 MHz (bench.py: roofline.clock_ghz)
     unsigned long long clk_c0 = 0, clk_r0 = 0;
-    if (clk != nullptr)
-        asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(clk_c0), "=s"(clk_r0)::"memory");
-    using Cfg = Mid16Cfg<C3, TD, TY, WR, WM>;
-    constexpr int MT = Cfg::MT, Q = Cfg::Q, RW = Cfg::RW, MTW = Cfg::MTW, HY = Cfg::HY, HX = Cfg::HX, VS = Cfg::VS;
+    if (clk != nullptr) clock_pair(clk_c0, clk_r0);
+    using Cfg = Mid16Cfg<C3, TD, TY>;
+    constexpr int MT = Cfg::MT, Q = Cfg::Q, RW = Cfg::RW, HY = Cfg::HY, HX = Cfg::HX, VS = Cfg::VS;
     constexpr int NT = Cfg::NT, SITER = Cfg::SITER;
     extern __shared__ __attribute__((aligned(16))) float lds[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wr = wave / WM, wm = wave % WM;     // this wave's row group / output-channel group
     const int n = lane & 15, g = lane >> 4;
     int tx, ty, td;
     tile_coords(xcd_tile(blockIdx.x, gridDim.x), tiles_x, tiles_d, tx, ty, td);
@@ -152,40 +169,40 @@ __global__ __launch_bounds__(64 * WR * WM) void k_conv3d_mid16(const float *__re
     };
     // next layer's BatchNorm of this lane's output channels: loaded here, behind the halo loads, so that the epilogue
     // does not start with an exposed L2 round trip
-    float4 es[MTW], et[MTW];
+    float4 es[MT], et[MT];
 #pragma unroll
-    for (int mt = 0; mt < MTW; ++mt) {
-        es[mt] = *reinterpret_cast<const float4 *>(bn_s + (wm * MTW + mt) * 16 + 4 * g);
-        et[mt] = *reinterpret_cast<const float4 *>(bn_t + (wm * MTW + mt) * 16 + 4 * g);
+    for (int mt = 0; mt < MT; ++mt) {
+        es[mt] = *reinterpret_cast<const float4 *>(bn_s + mt * 16 + 4 * g);
+        et[mt] = *reinterpret_cast<const float4 *>(bn_t + mt * 16 + 4 * g);
     }
 #pragma unroll
     for (int i = 0; i < P1; ++i) stage_write(i);
 
-    // weights of this wave: [tap][q][mt][lane] float4, mt in [wm*MTW, (wm+1)*MTW); the packed array holds two
-    // extra all-zero taps so that the two-taps-ahead prefetch never needs a bounds check
-    const float4 *wp = wpk + (wm * MTW) * 64 + lane;
-    float4 wbuf[3][Q][MTW];                         // ring over kw: tap kw of the current (kd,kh) lives in wbuf[kw]
+    // weights: [tap][q][mt][lane] float4; the packed array holds two extra all-zero taps so that the two-taps-ahead
+    // prefetch never needs a bounds check
+    const float4 *wp = wpk + lane;
+    float4 wbuf[3][Q][MT];                          // ring over kw: tap kw of the current (kd,kh) lives in wbuf[kw]
 #pragma unroll
     for (int q = 0; q < Q; ++q)
 #pragma unroll
-        for (int mt = 0; mt < MTW; ++mt) {
+        for (int mt = 0; mt < MT; ++mt) {
             wbuf[0][q][mt] = wp[(q * MT + mt) * 64];
             wbuf[1][q][mt] = wp[((Q + q) * MT + mt) * 64];     // the stream runs two taps ahead of the MFMAs
         }
     __syncthreads();
     LWS_STAMPK(1, 1);
 
-    floatx4 acc[RW][MTW];
+    floatx4 acc[RW][MT];
 #pragma unroll
     for (int r = 0; r < RW; ++r)
 #pragma unroll
-        for (int mt = 0; mt < MTW; ++mt) acc[r][mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
+        for (int mt = 0; mt < MT; ++mt) acc[r][mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
 
     // per-row LDS base of this lane: voxel (rd, ry, n) of the halo tile, channel quad g
     const float *rptr[RW];
 #pragma unroll
     for (int r = 0; r < RW; ++r) {
-        const int row = wr * RW + r;
+        const int row = wave * RW + r;
         const int rd = row / TY, ry = row % TY;
         rptr[r] = lds + ((rd * HY + ry) * HX + n) * VS + 4 * g;
     }
@@ -231,9 +248,8 @@ __global__ __launch_bounds__(64 * WR * WM) void k_conv3d_mid16(const float *__re
 #pragma unroll
                     for (int r = 0; r < RW; ++r)
 #pragma unroll
-                        for (int mt = 0; mt < MTW; ++mt)
+                        for (int mt = 0; mt < MT; ++mt)
                             acc[r][mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(f4(wbuf[kw][q][mt], j), f4(bc[r], j), acc[r][mt], 0, 0, 0);
-                    if (!MID16_INTERLEAVE) __builtin_amdgcn_sched_barrier(0);
                     // prefetch slice j: one activation fragment per slice, then (on the first channel group of a tap)
                     // the weights of the next tap
                     if (j < RW) bn[j] = *reinterpret_cast<const float4 *>(rptr[j] + off_n);
@@ -243,30 +259,28 @@ __global__ __launch_bounds__(64 * WR * WM) void k_conv3d_mid16(const float *__re
                     }
                     if (q == 0 && j >= 1) {
                         // tap t+2 -> wbuf[(kw+2)%3] (the slot of tap t-1): two taps = 4 steps = ~3k cycles of lead over
-                        // the L2 latency; Q*MTW loads spread over slices 1..3
-                        constexpr int NL = Q * MTW;
+                        // the L2 latency; Q*MT loads spread over slices 1..3
+                        constexpr int NL = Q * MT;
 #pragma unroll
                         for (int l = 0; l < NL; ++l)
                             if (l % 3 == j - 1) {
-                                const int q2 = l / MTW, mt2 = l % MTW;
+                                const int q2 = l / MT, mt2 = l % MT;
                                 wbuf[(kw + 2) % 3][q2][mt2] = wtap[((kw + 2) * Q + q2) * MT * 64 + mt2 * 64];
                             }
                     }
-                    if (MID16_INTERLEAVE) {
-                        // one prefetch instruction per MFMA gap instead of all of them behind the group: an MFMA leaves
-                        // ~24 issue cycles free, a ds_read plus two global loads plus their address adds need ~50
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
-                        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);   // VALU (address)
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // DS read
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // VMEM read
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    }
+                    // one prefetch instruction per MFMA gap instead of all of them behind the group: an MFMA leaves
+                    // ~24 issue cycles free, a ds_read plus two global loads plus their address adds need ~50
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
+                    __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);   // VALU (address)
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // DS read
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // VMEM read
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 if (Q % 2 != 0) {
@@ -279,32 +293,27 @@ __global__ __launch_bounds__(64 * WR * WM) void k_conv3d_mid16(const float *__re
 
     LWS_STAMPK(1, 2);
     // ---- epilogue: D[i][j]: row i = 4*(lane>>4) + reg = output channel in the tile, col j = lane&15 = voxel.
-    //      Apply the NEXT layer's BatchNorm + ReLU and store 4 consecutive channels of one voxel (16 B).
+    //      Apply the NEXT layer's BatchNorm + ReLU and store 4 consecutive channels of one voxel (16 B), write-back like every
+    //      activation store of this file: write-through stores (store_act4) were measured a loss here (26.3 -> 27.6 us at
+    //      B = 1) -- the next layer re-reads these activations at once and finds them in the XCD's L2 only when they were
+    //      stored write-back.
     float *outb = out + (int64_t)b * D * h * w * C3;
     const int gx = x0 + n;
 #pragma unroll
     for (int r = 0; r < RW; ++r) {
-        const int row = wr * RW + r;
+        const int row = wave * RW + r;
         const int gd = d0 + row / TY, gy = y0 + row % TY;
         if (gd < D && gy < h && gx < w) {
             float *o = outb + (((int64_t)gd * h + gy) * w + gx) * C3;
 #pragma unroll
-            for (int mt = 0; mt < MTW; ++mt) {
-                const int cb = (wm * MTW + mt) * 16 + 4 * g;
-                const float4 s = es[mt], t = et[mt];
-                float4 v;
-                v.x = bn_relu(acc[r][mt][0], s.x, t.x);
-                v.y = bn_relu(acc[r][mt][1], s.y, t.y);
-                v.z = bn_relu(acc[r][mt][2], s.z, t.z);
-                v.w = bn_relu(acc[r][mt][3], s.w, t.w);
-                store_act4(o + cb, v, wt);
-            }
+            for (int mt = 0; mt < MT; ++mt)
+                *reinterpret_cast<float4 *>(o + mt * 16 + 4 * g) = bn_relu4(acc[r][mt], es[mt], et[mt]);
         }
     }
     LWS_STAMPK(1, 3);
     if (clk != nullptr) {
         unsigned long long c1, r1;
-        asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(c1), "=s"(r1)::"memory");
+        clock_pair(c1, r1);
         const unsigned bid = blockIdx.x + gridDim.x * blockIdx.y;
         if (threadIdx.x == 0 && bid < 64) {
             clk[4 * bid + 0] = clk_c0;
@@ -507,15 +516,8 @@ __global__ __launch_bounds__(256) void k_conv3d_mid16x(const float *__restrict__
         if (gd < D && gy < h && gx < w) {
             float *o = outb + (((int64_t)gd * h + gy) * w + gx) * C3;
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                const float4 s = es[mt], t = et[mt];
-                float4 v;
-                v.x = bn_relu(acc[r][mt][0], s.x, t.x);
-                v.y = bn_relu(acc[r][mt][1], s.y, t.y);
-                v.z = bn_relu(acc[r][mt][2], s.z, t.z);
-                v.w = bn_relu(acc[r][mt][3], s.w, t.w);
-                store_act4(o + mt * 16 + 4 * g, v, 0);
-            }
+            for (int mt = 0; mt < MT; ++mt)
+                *reinterpret_cast<float4 *>(o + mt * 16 + 4 * g) = bn_relu4(acc[r][mt], es[mt], et[mt]);
         }
     }
     LWS_STAMPK(19, 3);
@@ -680,14 +682,8 @@ __global__ __launch_bounds__(256) void k_conv3d_mid8x(const float *__restrict__ 
     for (int r = 0; r < RW; ++r) {
         const int row = wave * RW + r;
         const int gd = d0 + row / TY, gy = y0 + row % TY;
-        if (gd < D && gy < h && gx < w) {
-            float4 v;
-            v.x = bn_relu(acc[r][0], es8.x, et8.x);
-            v.y = bn_relu(acc[r][1], es8.y, et8.y);
-            v.z = bn_relu(acc[r][2], es8.z, et8.z);
-            v.w = bn_relu(acc[r][3], es8.w, et8.w);
-            store_act4(outb + (((int64_t)gd * h + gy) * w + gx) * 8 + cb8, v, 0);
-        }
+        if (gd < D && gy < h && gx < w)
+            *reinterpret_cast<float4 *>(outb + (((int64_t)gd * h + gy) * w + gx) * 8 + cb8) = bn_relu4(acc[r], es8, et8);
     }
     LWS_STAMPK(20, 3);
 }
@@ -735,7 +731,7 @@ __global__ __launch_bounds__((Mid8qCfg<TD, TY>::NT)) void k_conv3d_mid8q(const f
                                                                         const float *__restrict__ bn_s,    // next layer BN [8]
                                                                         const float *__restrict__ bn_t,
                                                                         float *__restrict__ out, int D, int h, int w,
-                                                                        int tiles_x, int tiles_y, int wt, int tiles_d)
+                                                                        int tiles_x, int tiles_y, int tiles_d)
 {
     using Cfg = Mid8qCfg<TD, TY>;
     constexpr int HY = Cfg::HY, HX = Cfg::HX, NP = Cfg::NP;
@@ -829,17 +825,8 @@ __global__ __launch_bounds__((Mid8qCfg<TD, TY>::NT)) void k_conv3d_mid8q(const f
     const int gd = d0 + pd, gy = y0 + ly, gx = x0 + lx;
     if (gd < D && gy < h && gx < w) {
         float *o = out + (int64_t)b * D * h * w * 8 + (((int64_t)gd * h + gy) * w + gx) * 8;
-        float4 v;
-        v.x = bn_relu(lo[0], s_lo.x, t_lo.x);
-        v.y = bn_relu(lo[1], s_lo.y, t_lo.y);
-        v.z = bn_relu(lo[2], s_lo.z, t_lo.z);
-        v.w = bn_relu(lo[3], s_lo.w, t_lo.w);
-        store_act4(o, v, wt);
-        v.x = bn_relu(hi[0], s_hi.x, t_hi.x);
-        v.y = bn_relu(hi[1], s_hi.y, t_hi.y);
-        v.z = bn_relu(hi[2], s_hi.z, t_hi.z);
-        v.w = bn_relu(hi[3], s_hi.w, t_hi.w);
-        store_act4(o + 4, v, wt);
+        *reinterpret_cast<float4 *>(o) = bn_relu4(lo, s_lo, t_lo);
+        *reinterpret_cast<float4 *>(o + 4) = bn_relu4(hi, s_hi, t_hi);
     }
     LWS_STAMPK(18, 3);
 }
@@ -875,10 +862,9 @@ __global__ __launch_bounds__(256) void k_conv3d_first8(const float *__restrict__
 #pragma unroll
     for (int i = 0; i < SITER; ++i) {
         const int v = tid + i * 256;
-        const int hx = v % HX, t2 = v / HX, hy = t2 % HY, hd = t2 / HY;
-        const int gd = d0 + hd - 1, gy = y0 + hy - 1, gx = x0 + hx - 1;
-        okv[i] = v < NVOX && gd >= 0 && gd < D && gy >= 0 && gy < h && gx >= 0 && gx < w;
-        c[i] = cb[okv[i] ? ((int64_t)gd * h + gy) * w + gx : 0];
+        int64_t off;
+        okv[i] = halo_item<HY, HX>(v, v, NVOX, d0, y0, x0, D, h, w, 1, 0, off);
+        c[i] = cb[off];
     }
     const float s0 = bn0_s[0], t0 = bn0_t[0];
     const int xpar = g >> 1, cbo = 4 * (g & 1);
@@ -914,14 +900,8 @@ __global__ __launch_bounds__(256) void k_conv3d_first8(const float *__restrict__
     for (int r = 0; r < RW; ++r) {
         const int row = wave * RW + r;
         const int gd = d0 + row / TY, gy = y0 + row % TY;
-        if (gd < D && gy < h && gx < w) {
-            float4 v;
-            v.x = bn_relu(acc[r][0], es.x, et.x);
-            v.y = bn_relu(acc[r][1], es.y, et.y);
-            v.z = bn_relu(acc[r][2], es.z, et.z);
-            v.w = bn_relu(acc[r][3], es.w, et.w);
-            *reinterpret_cast<float4 *>(outb + (((int64_t)gd * h + gy) * w + gx) * 8 + cbo) = v;
-        }
+        if (gd < D && gy < h && gx < w)
+            *reinterpret_cast<float4 *>(outb + (((int64_t)gd * h + gy) * w + gx) * 8 + cbo) = bn_relu4(acc[r], es, et);
     }
 }
 
@@ -1010,10 +990,9 @@ __global__ __launch_bounds__(256) void k_conv3d_first16(float *__restrict__ cost
 #pragma unroll
         for (int i = 0; i < SITER; ++i) {
             const int v = tid + i * 256;
-            const int hx = v % HX, t2 = v / HX, hy = t2 % HY, hd = t2 / HY;
-            const int gd = d0 + hd - 1, gy = y0 + hy - 1, gx = x0 + hx - 1;
-            okv[i] = v < NVOX && gd >= 0 && gd < D && gy >= 0 && gy < h && gx >= 0 && gx < w;
-            c[i] = cb[okv[i] ? ((int64_t)gd * h + gy) * w + gx : 0];
+            int64_t off;
+        okv[i] = halo_item<HY, HX>(v, v, NVOX, d0, y0, x0, D, h, w, 1, 0, off);
+            c[i] = cb[off];
         }
     }
     const float s0 = bn0_s[0], t0 = bn0_t[0];
@@ -1063,14 +1042,8 @@ __global__ __launch_bounds__(256) void k_conv3d_first16(float *__restrict__ cost
         if (gd < D && gy < h && gx < w) {
             float *o = outb + (((int64_t)gd * h + gy) * w + gx) * C3;
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                float4 v;
-                v.x = bn_relu(acc[r][mt][0], es[mt].x, et[mt].x);
-                v.y = bn_relu(acc[r][mt][1], es[mt].y, et[mt].y);
-                v.z = bn_relu(acc[r][mt][2], es[mt].z, et[mt].z);
-                v.w = bn_relu(acc[r][mt][3], es[mt].w, et[mt].w);
-                *reinterpret_cast<float4 *>(o + mt * 16 + 4 * g) = v;
-            }
+            for (int mt = 0; mt < MT; ++mt)
+                *reinterpret_cast<float4 *>(o + mt * 16 + 4 * g) = bn_relu4(acc[r][mt], es[mt], et[mt]);
         }
     }
 }
@@ -1138,11 +1111,10 @@ __global__ __launch_bounds__((LastCfg<C3, TD, TY, TX, FUSE>::NT)) void k_conv3d_
 #pragma unroll
         for (int i = 0; i < SITER; ++i) {
             const int it = tid + i * NT;
-            const int c4 = it % C4, v = it / C4;
-            const int hx = v % HX, t2 = v / HX, hy = t2 % HY, hd = t2 / HY;
-            const int gd = d0 + hd - 1, gy = y0 + hy - 1, gx = x0 + hx - 1;
-            const bool ok = it < Cfg::ITEMS && gd >= 0 && gd < D && gy >= 0 && gy < h && gx >= 0 && gx < w;
-            c[i] = *reinterpret_cast<const float4 *>(ab + (ok ? (((int64_t)gd * h + gy) * w + gx) * C3 + c4 * 4 : 0));
+            const int c4 = it % C4;
+            int64_t off;
+            const bool ok = halo_item<HY, HX>(it / C4, it, Cfg::ITEMS, d0, y0, x0, D, h, w, C3, c4 * 4, off);
+            c[i] = *reinterpret_cast<const float4 *>(ab + off);
             if (!ok) c[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
 #pragma unroll
@@ -1280,9 +1252,60 @@ void pack_mid_weights(const float *w, int c3, float *out)
                     }
 }
 
+// ---- what every launcher below shares ----
+// the tile counts of a [D, h, w] volume (the kernels decode blockIdx.x with tile_coords) and the grid: x = tiles, y = samples
+struct TileGrid {
+    int tiles_x, tiles_y, tiles_d;
+    dim3 grid;
+};
+static TileGrid tile_grid(int B, int D, int h, int w, int TX, int TY, int TD)
+{
+    const int tiles_x = cdiv(w, TX), tiles_y = cdiv(h, TY), tiles_d = cdiv(D, TD);
+    return {tiles_x, tiles_y, tiles_d, dim3(tiles_x * tiles_y * tiles_d, B)};
+}
+
+// lets `Kernel` be launched with `bytes` of dynamic LDS (ensure_dyn_lds; the per-device mask is per kernel)
+template <auto Kernel>
+static int allow_dyn_lds(int bytes)
+{
+    static std::atomic<uint64_t> attr_done{0};
+    return ensure_dyn_lds(attr_done, reinterpret_cast<const void *>(Kernel), bytes);
+}
+
+static int unsupported_c3(const char *who, int c3, const char *also = "")
+{
+    set_error("%s: unsupported channel count %d (8, 16, 32)%s", who, c3, also);
+    return LWS_ERR_INVALID;
+}
+
 bool shift_first_can_fuse(const Stage3d &s, int C)
 {
     return C == 16 && (s.c3 == 16 || s.c3 == 32) && !s.layers.empty() && s.layers[0].w_mfma != nullptr;
+}
+
+// k_conv3d_first16 for c3 = 16 / 32.  shift 0: `cost` is read (L, R unused); 1 / 2 (features rounded to fp16): it is built from
+// the features L, R and written
+static int first16_launch(const Stage3d &s, int shift, float *cost, const float *L, const float *R, float *act_out, int B, int D,
+                          int h, int w, hipStream_t st)
+{
+    constexpr int TD = 3, TY = 4;
+    const TileGrid t = tile_grid(B, D, h, w, 16, TY, TD);
+    auto launch = [&](auto c3, auto sh) {
+        hipLaunchKernelGGL((k_conv3d_first16<decltype(c3)::value, TD, TY, decltype(sh)::value>), t.grid, dim3(256), 0, st, cost, L, R,
+                           s.layers[0].w_mfma, s.layers[0].bn_s, s.layers[0].bn_t, s.layers[1].bn_s, s.layers[1].bn_t, act_out, D, h,
+                           w, t.tiles_x, t.tiles_y, t.tiles_d);
+    };
+    auto with_c3 = [&](auto sh) {
+        if (s.c3 == 32) launch(std::integral_constant<int, 32>{}, sh);
+        else launch(std::integral_constant<int, 16>{}, sh);
+    };
+    switch (shift) {
+        case 0: with_c3(std::integral_constant<int, 0>{}); break;
+        case 1: with_c3(std::integral_constant<int, 1>{}); break;
+        default: with_c3(std::integral_constant<int, 2>{}); break;
+    }
+    LWS_LAUNCH_CHECK();
+    return LWS_OK;
 }
 
 // stage-1 volume (written to `cost`: the stack's skip input) + first Conv3D layer in one launch
@@ -1293,23 +1316,7 @@ int launch_shift_first(const Stage3d &s, const float *L, const float *R, float *
         set_error("shift_first: unsupported channels C=%d c3=%d", C, s.c3);
         return LWS_ERR_INVALID;
     }
-    constexpr int TD = 3, TY = 4;
-    const int tiles_x = cdiv(w, 16), tiles_y = cdiv(h, TY), tiles_d = cdiv(D, TD);
-    dim3 grid(tiles_x * tiles_y * tiles_d, B), block(256);
-#define LWS_SF(C3v, SH)                                                                                               \
-    hipLaunchKernelGGL((k_conv3d_first16<C3v, TD, TY, SH>), grid, block, 0, st, cost, L, R, s.layers[0].w_mfma,        \
-                       s.layers[0].bn_s, s.layers[0].bn_t, s.layers[1].bn_s, s.layers[1].bn_t, act_out, D, h, w,      \
-                       tiles_x, tiles_y, tiles_d)
-    if (s.c3 == 32) {
-        if (q16) LWS_SF(32, 2);
-        else LWS_SF(32, 1);
-    } else {
-        if (q16) LWS_SF(16, 2);
-        else LWS_SF(16, 1);
-    }
-#undef LWS_SF
-    LWS_LAUNCH_CHECK();
-    return LWS_OK;
+    return first16_launch(s, q16 ? 2 : 1, cost, L, R, act_out, B, D, h, w, st);
 }
 
 int launch_conv3d_first(const Stage3d &s, const float *cost, float *act_out, int B, int D, int h, int w,
@@ -1317,60 +1324,35 @@ int launch_conv3d_first(const Stage3d &s, const float *cost, float *act_out, int
 {
     if (s.c3 == 8 && s.layers[0].w_mfma != nullptr) {
         constexpr int TD = 3, TY = 4;
-        const int tiles_x = cdiv(w, 32), tiles_y = cdiv(h, TY), tiles_d = cdiv(D, TD);
-        dim3 grid(tiles_x * tiles_y * tiles_d, B), block(256);
-        hipLaunchKernelGGL((k_conv3d_first8<TD, TY>), grid, block, 0, st, cost, s.layers[0].w_mfma, s.layers[0].bn_s,
-                           s.layers[0].bn_t, s.layers[1].bn_s, s.layers[1].bn_t, act_out, D, h, w, tiles_x, tiles_y,
-                           tiles_d);
+        const TileGrid t = tile_grid(B, D, h, w, 32, TY, TD);
+        hipLaunchKernelGGL((k_conv3d_first8<TD, TY>), t.grid, dim3(256), 0, st, cost, s.layers[0].w_mfma, s.layers[0].bn_s,
+                           s.layers[0].bn_t, s.layers[1].bn_s, s.layers[1].bn_t, act_out, D, h, w, t.tiles_x, t.tiles_y,
+                           t.tiles_d);
         LWS_LAUNCH_CHECK();
         return LWS_OK;
     }
-    if ((s.c3 == 16 || s.c3 == 32) && s.layers[0].w_mfma != nullptr) {
-        constexpr int TD = 3, TY = 4;
-        const int tiles_x = cdiv(w, 16), tiles_y = cdiv(h, TY), tiles_d = cdiv(D, TD);
-        dim3 grid(tiles_x * tiles_y * tiles_d, B), block(256);
-        float *cin = const_cast<float *>(cost);     // SHIFT = 0: read only
-        const float *nofeat = nullptr;
-        if (s.c3 == 32)
-            hipLaunchKernelGGL((k_conv3d_first16<32, TD, TY, 0>), grid, block, 0, st, cin, nofeat, nofeat, s.layers[0].w_mfma,
-                               s.layers[0].bn_s, s.layers[0].bn_t, s.layers[1].bn_s, s.layers[1].bn_t, act_out, D, h, w,
-                               tiles_x, tiles_y, tiles_d);
-        else
-            hipLaunchKernelGGL((k_conv3d_first16<16, TD, TY, 0>), grid, block, 0, st, cin, nofeat, nofeat, s.layers[0].w_mfma,
-                               s.layers[0].bn_s, s.layers[0].bn_t, s.layers[1].bn_s, s.layers[1].bn_t, act_out, D, h, w,
-                               tiles_x, tiles_y, tiles_d);
-        LWS_LAUNCH_CHECK();
-        return LWS_OK;
-    }
-    set_error("conv3d_first: unsupported channel count %d (8, 16, 32) or weights not packed", s.c3);
-    return LWS_ERR_INVALID;
+    if ((s.c3 == 16 || s.c3 == 32) && s.layers[0].w_mfma != nullptr)
+        return first16_launch(s, 0, const_cast<float *>(cost), nullptr, nullptr, act_out, B, D, h, w, st);
+    return unsupported_c3("conv3d_first", s.c3, " or weights not packed");
 }
 
-template <int C3, int TD, int TY, int WR, int WM>
+template <int C3, int TD, int TY>
 static int mid16_launch(const Stage3d &s, int layer, const float *in, float *out, int B, int D, int h, int w,
                         hipStream_t st, hipEvent_t e0, hipEvent_t e1)
 {
-    using Cfg = Mid16Cfg<C3, TD, TY, WR, WM>;
-    static std::atomic<uint64_t> attr_done{0};
-    {
-        const int rc_ = ensure_dyn_lds(attr_done, reinterpret_cast<const void *>(&k_conv3d_mid16<C3, TD, TY, WR, WM>), Cfg::LDS_BYTES);
-        if (rc_) return rc_;
-    }
-    const int tiles_x = cdiv(w, 16), tiles_y = cdiv(h, TY), tiles_d = cdiv(D, TD);
-    dim3 grid(tiles_x * tiles_y * tiles_d, B), block(256);
-    block = dim3(Cfg::NT);
-    // write-through stores were measured a loss here (26.3 -> 27.6 us at B = 1): the next layer re-reads these
-    // activations at once and finds them in the XCD's L2 only when they were stored write-back
-    const int wt = 0;
+    using Cfg = Mid16Cfg<C3, TD, TY>;
+    if (const int rc = allow_dyn_lds<&k_conv3d_mid16<C3, TD, TY>>(Cfg::LDS_BYTES)) return rc;
+    const TileGrid t = tile_grid(B, D, h, w, 16, TY, TD);
+    const dim3 block(Cfg::NT);
     if (e0 != nullptr) {
         // profiler on: the events carry the kernel's own begin / end timestamps (no dispatch latency in between)
-        hipExtLaunchKernelGGL((k_conv3d_mid16<C3, TD, TY, WR, WM>), grid, block, Cfg::LDS_BYTES, st, e0, e1, 0, in,
+        hipExtLaunchKernelGGL((k_conv3d_mid16<C3, TD, TY>), t.grid, block, Cfg::LDS_BYTES, st, e0, e1, 0, in,
                               reinterpret_cast<const float4 *>(s.layers[layer].w), s.layers[layer + 1].bn_s,
-                              s.layers[layer + 1].bn_t, out, D, h, w, tiles_x, tiles_y, wt, tiles_d, s.clk);
+                              s.layers[layer + 1].bn_t, out, D, h, w, t.tiles_x, t.tiles_y, t.tiles_d, s.clk);
     } else {
-        LWS_LAUNCH_STOP((k_conv3d_mid16<C3, TD, TY, WR, WM>), grid, block, Cfg::LDS_BYTES, st, in,
+        LWS_LAUNCH_STOP((k_conv3d_mid16<C3, TD, TY>), t.grid, block, Cfg::LDS_BYTES, st, in,
                         reinterpret_cast<const float4 *>(s.layers[layer].w), s.layers[layer + 1].bn_s,
-                        s.layers[layer + 1].bn_t, out, D, h, w, tiles_x, tiles_y, wt, tiles_d, s.clk);
+                        s.layers[layer + 1].bn_t, out, D, h, w, t.tiles_x, t.tiles_y, t.tiles_d, s.clk);
     }
     LWS_LAUNCH_CHECK();
     return LWS_OK;
@@ -1381,20 +1363,16 @@ static int mid16x_launch(const Stage3d &s, int layer, const float *in, float *ou
                          hipEvent_t e0, hipEvent_t e1)
 {
     using Cfg = Mid16xCfg<TD, TY>;
-    static std::atomic<uint64_t> attr_done{0};
-    {
-        const int rc_ = ensure_dyn_lds(attr_done, reinterpret_cast<const void *>(&k_conv3d_mid16x<TD, TY>), Cfg::LDS_BYTES);
-        if (rc_) return rc_;
-    }
-    const int tiles_x = cdiv(w, 16), tiles_y = cdiv(h, TY), tiles_d = cdiv(D, TD);
-    dim3 grid(tiles_x * tiles_y * tiles_d, B), block(Cfg::NT);
+    if (const int rc = allow_dyn_lds<&k_conv3d_mid16x<TD, TY>>(Cfg::LDS_BYTES)) return rc;
+    const TileGrid t = tile_grid(B, D, h, w, 16, TY, TD);
+    const dim3 block(Cfg::NT);
     const uint4 *wx = reinterpret_cast<const uint4 *>(s.layers[layer].w + (size_t)29 * 32 * 32);
     if (e0 != nullptr)
-        hipExtLaunchKernelGGL((k_conv3d_mid16x<TD, TY>), grid, block, Cfg::LDS_BYTES, st, e0, e1, 0, in, wx, s.layers[layer + 1].bn_s,
-                              s.layers[layer + 1].bn_t, out, D, h, w, tiles_x, tiles_y, tiles_d);
+        hipExtLaunchKernelGGL((k_conv3d_mid16x<TD, TY>), t.grid, block, Cfg::LDS_BYTES, st, e0, e1, 0, in, wx, s.layers[layer + 1].bn_s,
+                              s.layers[layer + 1].bn_t, out, D, h, w, t.tiles_x, t.tiles_y, t.tiles_d);
     else
-        hipLaunchKernelGGL((k_conv3d_mid16x<TD, TY>), grid, block, Cfg::LDS_BYTES, st, in, wx, s.layers[layer + 1].bn_s,
-                           s.layers[layer + 1].bn_t, out, D, h, w, tiles_x, tiles_y, tiles_d);
+        hipLaunchKernelGGL((k_conv3d_mid16x<TD, TY>), t.grid, block, Cfg::LDS_BYTES, st, in, wx, s.layers[layer + 1].bn_s,
+                           s.layers[layer + 1].bn_t, out, D, h, w, t.tiles_x, t.tiles_y, t.tiles_d);
     LWS_LAUNCH_CHECK();
     return LWS_OK;
 }
@@ -1405,15 +1383,12 @@ template <int TD, int TY>
 static int mid8q_launch(const Stage3d &s, int layer, const float *in, float *out, int B, int D, int h, int w, hipStream_t st)
 {
     using Cfg = Mid8qCfg<TD, TY>;
-    static std::atomic<uint64_t> attr_done{0};
-    if (Cfg::LDS_BYTES > 48 * 1024) {
-        const int rc_ = ensure_dyn_lds(attr_done, reinterpret_cast<const void *>(&k_conv3d_mid8q<TD, TY>), kCuLdsBytes);
-        if (rc_) return rc_;
+    if (Cfg::LDS_BYTES > 48 * 1024) {   // the CU's whole LDS, not only this tile's
+        if (const int rc = allow_dyn_lds<&k_conv3d_mid8q<TD, TY>>(kCuLdsBytes)) return rc;
     }
-    const int tiles_x = cdiv(w, 32), tiles_y = cdiv(h, TY), tiles_d = cdiv(D, TD);
-    dim3 grid(tiles_x * tiles_y * tiles_d, B), block(Cfg::NT);
-    hipLaunchKernelGGL((k_conv3d_mid8q<TD, TY>), grid, block, Cfg::LDS_BYTES, st, in, s.layers[layer].w,
-                       s.layers[layer + 1].bn_s, s.layers[layer + 1].bn_t, out, D, h, w, tiles_x, tiles_y, /*wt=*/0, tiles_d);
+    const TileGrid t = tile_grid(B, D, h, w, 32, TY, TD);
+    hipLaunchKernelGGL((k_conv3d_mid8q<TD, TY>), t.grid, dim3(Cfg::NT), Cfg::LDS_BYTES, st, in, s.layers[layer].w,
+                       s.layers[layer + 1].bn_s, s.layers[layer + 1].bn_t, out, D, h, w, t.tiles_x, t.tiles_y, t.tiles_d);
     LWS_LAUNCH_CHECK();
     return LWS_OK;
 }
@@ -1422,14 +1397,11 @@ template <int TD, int TY>
 static int mid8x_launch(const Stage3d &s, int layer, const float *in, float *out, int B, int D, int h, int w, hipStream_t st)
 {
     using Cfg = Mid8xCfg<TD, TY>;
-    static std::atomic<uint64_t> attr_done{0};
-    const int rc_ = ensure_dyn_lds(attr_done, reinterpret_cast<const void *>(&k_conv3d_mid8x<TD, TY>), Cfg::LDS_BYTES);
-    if (rc_) return rc_;
-    const int tiles_x = cdiv(w, 32), tiles_y = cdiv(h, TY), tiles_d = cdiv(D, TD);
-    dim3 grid(tiles_x * tiles_y * tiles_d, B), block(Cfg::NT);
-    hipLaunchKernelGGL((k_conv3d_mid8x<TD, TY>), grid, block, Cfg::LDS_BYTES, st, in,
+    if (const int rc = allow_dyn_lds<&k_conv3d_mid8x<TD, TY>>(Cfg::LDS_BYTES)) return rc;
+    const TileGrid t = tile_grid(B, D, h, w, 32, TY, TD);
+    hipLaunchKernelGGL((k_conv3d_mid8x<TD, TY>), t.grid, dim3(Cfg::NT), Cfg::LDS_BYTES, st, in,
                        reinterpret_cast<const uint4 *>(s.layers[layer].w + 28 * 64), s.layers[layer + 1].bn_s,
-                       s.layers[layer + 1].bn_t, out, D, h, w, tiles_x, tiles_y, tiles_d);
+                       s.layers[layer + 1].bn_t, out, D, h, w, t.tiles_x, t.tiles_y, t.tiles_d);
     LWS_LAUNCH_CHECK();
     return LWS_OK;
 }
@@ -1459,12 +1431,12 @@ int launch_conv3d_mid(const Stage3d &s, int layer, const float *act_in, float *a
             if (big_tiles >= 192 && !small_wins) return mid8q_launch<3, 8>(s, layer, act_in, act_out, B, D, h, w, st);
             return mid8q_launch<3, 2>(s, layer, act_in, act_out, B, D, h, w, st);
         }
-        case 16: return mid16_launch<16, 3, 4, 4, 1>(s, layer, act_in, act_out, B, D, h, w, st, e0, e1);
+        case 16: return mid16_launch<16, 3, 4>(s, layer, act_in, act_out, B, D, h, w, st, e0, e1);
         case 32: {
             if (s.mid16_split) return mid16x_launch<3, 4>(s, layer, act_in, act_out, B, D, h, w, st, e0, e1);
-            return mid16_launch<32, 3, 4, 4, 1>(s, layer, act_in, act_out, B, D, h, w, st, e0, e1);
+            return mid16_launch<32, 3, 4>(s, layer, act_in, act_out, B, D, h, w, st, e0, e1);
         }
-        default: set_error("conv3d: unsupported channel count %d (8, 16, 32)", s.c3); return LWS_ERR_INVALID;
+        default: return unsupported_c3("conv3d", s.c3);
     }
 }
 
@@ -1473,15 +1445,12 @@ static int last_launch(const Stage3d &s, const float *act, const float *skip, fl
                        int B, int D, int h, int w, hipStream_t st)
 {
     using Cfg = LastCfg<C3, TD, TY, TX, FUSE>;
-    static std::atomic<uint64_t> attr_done{0};
     if (Cfg::LDS_BYTES > 48 * 1024) {
-        const int rc_ = ensure_dyn_lds(attr_done, reinterpret_cast<const void *>(&k_conv3d_last<C3, TD, TY, TX, FUSE>), Cfg::LDS_BYTES);
-        if (rc_) return rc_;
+        if (const int rc = allow_dyn_lds<&k_conv3d_last<C3, TD, TY, TX, FUSE>>(Cfg::LDS_BYTES)) return rc;
     }
-    const int tiles_x = cdiv(w, TX), tiles_y = cdiv(h, TY), tiles_d = cdiv(D, TD);
-    dim3 grid(tiles_x * tiles_y * tiles_d, B), block(Cfg::NT);
-    LWS_LAUNCH_STOP((k_conv3d_last<C3, TD, TY, TX, FUSE>), grid, block, Cfg::LDS_BYTES, st, act, s.layers.back().w,
-                    skip, cost_out, low, start, D, h, w, tiles_x, tiles_y, tiles_d);
+    const TileGrid t = tile_grid(B, D, h, w, TX, TY, TD);
+    LWS_LAUNCH_STOP((k_conv3d_last<C3, TD, TY, TX, FUSE>), t.grid, dim3(Cfg::NT), Cfg::LDS_BYTES, st, act, s.layers.back().w,
+                    skip, cost_out, low, start, D, h, w, t.tiles_x, t.tiles_y, t.tiles_d);
     LWS_LAUNCH_CHECK();
     return LWS_OK;
 }
@@ -1493,7 +1462,7 @@ int launch_conv3d_last(const Stage3d &s, const float *act_in, const float *cost_
         case 8: return last_launch<8, 3, 4, 16, false>(s, act_in, cost_skip, cost_out, nullptr, 0.f, B, D, h, w, st);
         case 16: return last_launch<16, 3, 4, 16, false>(s, act_in, cost_skip, cost_out, nullptr, 0.f, B, D, h, w, st);
         case 32: return last_launch<32, 3, 4, 16, false>(s, act_in, cost_skip, cost_out, nullptr, 0.f, B, D, h, w, st);
-        default: set_error("conv3d: unsupported channel count %d (8, 16, 32)", s.c3); return LWS_ERR_INVALID;
+        default: return unsupported_c3("conv3d", s.c3);
     }
 }
 

@@ -912,24 +912,37 @@ def test_second_state_dict_rebuilds_the_parameters(dev, hip_lib):
     assert all((a != b).any() for a, b in zip(*preds))
 
 
-@pytest.mark.parametrize("mdl,l3,c3,gr", [((24, 5, 5), 4, 8, (1, 1, 1)), ((16, 2, 6), 2, 8, (4, 2, 1)), ((8, 1, 1), 1, 16, (1, 1, 1)),
-                                          ((24, 5, 5), 1, 8, (4, 1, 1)), ((12, 4, 2), 3, 8, (2, 2, 2)), ((24, 7, 9), 4, 8, (4, 1, 1)),
-                                          ((30, 5, 5), 4, 8, (4, 4, 4))])
-def test_forward_constructor_sweep(dev, hip_lib, mdl, l3, c3, gr):
+# (maxdisplist, layers_3d, channels_3d, growth_rate, feature_fp16, (H, W)); the ids of the first seven are the ones pytest gave them
+# when the first four were the only parameters
+CONSTRUCTOR_SWEEP = [((24, 5, 5), 4, 8, (1, 1, 1), False, (64, 256)), ((16, 2, 6), 2, 8, (4, 2, 1), False, (64, 256)),
+                     ((8, 1, 1), 1, 16, (1, 1, 1), False, (64, 256)), ((24, 5, 5), 1, 8, (4, 1, 1), False, (64, 256)),
+                     ((12, 4, 2), 3, 8, (2, 2, 2), False, (64, 256)), ((24, 7, 9), 4, 8, (4, 1, 1), False, (64, 256)),
+                     ((30, 5, 5), 4, 8, (4, 4, 4), False, (64, 256)),
+                     # 16 channels with D = 9 at stages 2 and 3 (the fused last layer k_conv3d_last<16, 9, 2, 16, true>), then the same
+                     # with fp16-rounded features (k_conv3d_first16<16, 3, 4, 2>), at stage sizes 5 x 33, 10 x 66 and 20 x 132: no
+                     # multiple of a tile edge, so every face of the halo is padding somewhere
+                     ((24, 5, 5), 2, 8, (2, 2, 2), False, (40, 264)), ((24, 5, 5), 2, 8, (2, 2, 2), True, (40, 264))]
+
+
+@pytest.mark.parametrize("mdl,l3,c3,gr,fp16,size", CONSTRUCTOR_SWEEP,
+                         ids=[f"mdl{i}-{c[1]}-{c[2]}-gr{i}" + (f"-{c[5][0]}x{c[5][1]}" if c[5] != (64, 256) else "") + ("-fp16" if c[4] else "")
+                              for i, c in enumerate(CONSTRUCTOR_SWEEP)])
+def test_forward_constructor_sweep(dev, hip_lib, mdl, l3, c3, gr, fp16, size):
     """The constructor's degrees of freedom (models/models.py:8-22) beyond the CLI defaults: every channel count the library
     accepts (8 / 16 / 32) at every stage, 1-4 middle layers, hypothesis counts from D = 1 (maxdisplist entry 1: a single
     residual hypothesis, the soft-argmin of one value) through 3, 7, 11, 13, 17 to 30 -- last layers fused with the soft-argmin
-    or not, every Conv3D kernel family on every stage.  Two pairs at 64x256, all four stage maps bit for bit the C oracle's."""
+    or not, every Conv3D kernel family on every stage.  Two pairs at 64x256 (the last two cases: 40x264), all four stage maps bit
+    for bit the C oracle's."""
     from lwsnet_amd.models import LWSNet
     from oracle import c_oracle as C
-    args = default_args(maxdisplist=mdl, layers_3d=l3, channels_3d=c3, growth_rate=gr)
+    args = default_args(maxdisplist=mdl, layers_3d=l3, channels_3d=c3, growth_rate=gr, feature_fp16=fp16)
     sd = make_state_dict(13, args, calibrated=False)
     m = LWSNet(args, device=dev).set_state_dict(sd).eval()
-    left, right = make_batch(2, 64, 256, 4)
+    left, right = make_batch(2, *size, 4)
     pred = m(left, right)
-    want = C.forward(left, right, sd, maxdisplist=mdl)
+    want = C.forward(left, right, sd, maxdisplist=mdl, feature_fp16=fp16)
     for s in range(4):
-        assert_bits(pred[s], want[s], f"maxdisplist={mdl} layers_3d={l3} channels_3d={c3} growth_rate={gr} stage {s + 1}")
+        assert_bits(pred[s], want[s], f"maxdisplist={mdl} layers_3d={l3} channels_3d={c3} growth_rate={gr} fp16={fp16} stage {s + 1}")
 
 
 def test_forward_matches_literal_oracle(dev, model):
