@@ -442,6 +442,7 @@ int lws_bev_grid(const float *disp, const float *cam, const uint8_t *codes, cons
 int lws_stixels(const float *disp, const float *cam, const uint8_t *codes, const float *height, int B, int H, int W, float min_disp,
                 float max_depth, int code_bits, int width, int sub, int nbins, int tol_bins, int min_count, int min_row, int max_gap,
                 int layers, int32_t *rows, float *vals, uint32_t *udisp, void *stream);
+/* Obstacle objects -- the connected components of udisp, with pixel labels and boxes -- are declared in lwsnet_objects.h. */
 
 /* ---- speckle filter: connected components of a disparity map (additive after v8) ---- */
 /* bytes of device workspace lws_speckle_filter needs for this geometry: per pixel one int32 parent word and one int32 size word

@@ -1,5 +1,6 @@
-"""ctypes binding of liblwsnet_hip.so.  include/lwsnet_hip.h is the only statement of the C ABI: PROTOTYPES and the LWS_*
-constants are read from it when this module is imported (tests/test_abi_cpu.py has a C++ compiler check the reading).
+"""ctypes binding of liblwsnet_hip.so.  include/lwsnet_hip.h is the statement of the C ABI: PROTOTYPES and the LWS_*
+constants are read from it when this module is imported (tests/test_abi_cpu.py has a C++ compiler check the reading).  The entry
+points added behind ABI v8 in headers of their own (include/lwsnet_objects.h) are read the same way into EXTENSION_PROTOTYPES.
 
 The header cannot say which pointers are host pointers, so every pointer but `const char *` is c_void_p: the 20 host-pointer
 parameters -- lws_set_tensor's data and shape, the mean / std arrays, lws_profile_read*, lws_clock_read, lws_join_stats, the
@@ -17,6 +18,7 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblwsnet_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "lwsnet_hip.h")
+EXTENSION_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "lwsnet_objects.h"),)
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
@@ -106,6 +108,14 @@ with open(HEADER_PATH) as _f:
  LWS_POOL_SIDE_STREAMS) = (_CONSTANTS[k] for k in ("LWS_ABI_VERSION", "LWS_OK", "LWS_ERR_INVALID", "LWS_ERR_HIP", "LWS_ERR_STATE",
                                                    "LWS_ERR_NOMEM", "LWS_KC_COUNT", "LWS_SPARS_BINS", "LWS_POOL_SIDE_STREAMS"))
 
+# the same two tables for the headers that extend the ABI: exactly the functions those headers declare
+EXTENSION_PROTOTYPES, EXTENSION_SPELLINGS = {}, {}
+for _path in EXTENSION_HEADER_PATHS:
+    with open(_path) as _f:
+        _protos, _spellings, _ = parse_header(_f.read(), _path)
+    EXTENSION_PROTOTYPES.update(_protos)
+    EXTENSION_SPELLINGS.update(_spellings)
+
 _lib = None
 
 
@@ -130,7 +140,7 @@ def load():
             f"{LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python -m lwsnet_amd.build`); there is no CPU fallback for the disparity path")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in PROTOTYPES.items():
+    for name, (res, args) in {**PROTOTYPES, **EXTENSION_PROTOTYPES}.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

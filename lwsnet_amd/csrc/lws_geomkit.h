@@ -1,5 +1,5 @@
 // What the geometry translation units share (lws_geometry.hip: depth maps and the point cloud; lws_mesh.hip: surface normals and the
-// triangle mesh; lws_ground.hip: ground plane, obstacle codes and the bird's-eye grid; lws_stixels.hip: stixels): the camera row, the quad loads of a disparity row and its code map, the validity rule and the argument checks, so
+// triangle mesh; lws_ground.hip: ground plane, obstacle codes and the bird's-eye grid; lws_stixels.hip: stixels; lws_objects.hip: obstacle objects): the camera row, the quad loads of a disparity row and its code map, the validity rule and the argument checks, so
 // that "a valid pixel" is written once.  Contract: include/lwsnet_hip.h, lws_depth_maps.
 #pragma once
 #include "lws_common.h"
@@ -50,7 +50,7 @@ __device__ __forceinline__ void load_ok(const uint8_t *__restrict__ m, int x, in
 }
 
 // The validity rule shared by lws_depth_maps, lws_point_cloud, lws_surface_normals, lws_surface_mesh, lws_ground_classify,
-// lws_bev_grid and lws_stixels; z = fb / d is returned for every pixel.
+// lws_bev_grid, lws_stixels and lws_objects; z = fb / d is returned for every pixel.
 __device__ __forceinline__ bool valid_z(float d, bool ok, float fb, float min_disp, float max_depth, float &z)
 {
     z = fb / d;

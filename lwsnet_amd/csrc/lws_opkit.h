@@ -1,4 +1,4 @@
-// The toolkit of the post-network ops (lws_metrics, lws_lrcheck, lws_occlusion, lws_geometry, lws_mesh, lws_ground, lws_stixels, lws_speckle, lws_wmedian, lws_rectify,
+// The toolkit of the post-network ops (lws_metrics, lws_lrcheck, lws_occlusion, lws_geometry, lws_mesh, lws_ground, lws_stixels, lws_objects, lws_speckle, lws_wmedian, lws_rectify,
 // lws_confidence, lws_sparsification, lws_photometric; lws_rowkit.h builds on it).  An op is its own arithmetic and its own limits between these
 // pieces.  Host half: the argument checks their entry points share, under the caller's name `who`, so that a text is written once.
 // Device half: the 64-lane sum, the four-wave combine in its fixed order, and the ground-truth contract of the evaluation kernels.

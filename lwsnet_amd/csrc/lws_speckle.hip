@@ -10,9 +10,10 @@
 //   k_sp_apply    one workgroup per row: codes, out (with the row fill of lws_rowkit.h), labels, per-row counts
 //   k_sp_counts   (counts != NULL) one workgroup per image: the per-row counts summed in a fixed order
 //
-// The invariant every loop rests on: parent[p] <= p in raster order, always (a root is the FIRST pixel of its set, a union hangs
-// the later root under the earlier one with an atomic min).  A find walk therefore strictly decreases and ends after at most p
-// steps whatever other workgroups do meanwhile; no loop waits for another thread's progress.
+// The invariant every loop rests on (lws_cclkit.h holds the union-find and its termination arguments): parent[p] <= p in raster
+// order, always (a root is the FIRST pixel of its set, a union hangs the later root under the earlier one with an atomic min).  A
+// find walk therefore strictly decreases and ends after at most p steps whatever other workgroups do meanwhile; no loop waits for
+// another thread's progress.
 // Words shared between workgroups inside a launch (parent[] in k_sp_border and k_sp_flatten, size[] in k_sp_flatten) are touched
 // through relaxed agent-scope atomics only (each word stands for itself: there is no payload to publish behind it); everything
 // else crosses between workgroups at kernel boundaries.  Only ROOTS are ever re-parented, so a non-root pixel keeps the parent
@@ -20,6 +21,7 @@
 // Sizes: counted per tile in LDS (one add per wave for the wave's leading root, an LDS add for the other lanes), then ONE integer
 // atomic add per tile-local component to its global root: a 450 k-pixel component costs a few hundred adds on its word, not 450 k.
 // Integer atomics only, so the result does not depend on their order.  0 bytes of scratch.
+#include "lws_cclkit.h"
 #include "lws_common.h"
 #include "lws_rowkit.h"
 
@@ -29,6 +31,7 @@ namespace {
 
 using namespace rowkit;                                     // kThreads, kWaves, kMaxW and the pieces of k_sp_apply
 using namespace opkit;
+using namespace cclkit;                                    // lds_find, lds_unite, ld_agent, g_find, g_unite
 constexpr int kTH = 32, kTW = 64;                           // the tile of k_sp_tile
 constexpr int kTile = kTH * kTW;
 constexpr int kQuadsPerThread = kTile / 4 / kThreads;       // 2
@@ -46,61 +49,6 @@ __device__ __forceinline__ void store_quad_i(int *__restrict__ p, int x, int W, 
 #pragma unroll
         for (int i = 0; i < 4; ++i)
             if (x + i < W) p[x + i] = v[i];
-    }
-}
-
-// ---- union-find in LDS (one tile) ----
-// par[i] <= i: the walk strictly decreases, so it ends.
-__device__ __forceinline__ int lds_find(const volatile int *par, int i)
-{
-    for (int n = par[i]; n != i; n = par[i]) i = n;
-    return i;
-}
-
-// Every round ends the call or strictly lowers max(a, b) (the atomic min hangs the later root a under the earlier one b; when
-// another thread re-parented a first, its old parent `o` < a takes a's place and the union goes on as (o, b)), so the loop ends.
-__device__ __forceinline__ void lds_unite(int *par, int a, int b)
-{
-    for (;;) {
-        a = lds_find(par, a);
-        b = lds_find(par, b);
-        if (a == b) return;
-        if (a < b) {
-            const int s = a;
-            a = b;
-            b = s;
-        }
-        const int o = atomicMin(&par[a], b);
-        if (o == a) return;
-        a = o;
-    }
-}
-
-// ---- union-find in global memory across workgroups: agent-scope atomics only ----
-__device__ __forceinline__ int ld_agent(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// par[i] <= i, and a parent only ever decreases: the walk strictly decreases, so it ends (after at most i steps).
-__device__ __forceinline__ int g_find(const int *par, int i)
-{
-    for (int n = ld_agent(par + i); n != i; n = ld_agent(par + i)) i = n;
-    return i;
-}
-
-// As lds_unite: every round returns or strictly lowers max(a, b); it never waits for another workgroup.
-__device__ __forceinline__ void g_unite(int *par, int a, int b)
-{
-    for (;;) {
-        a = g_find(par, a);
-        b = g_find(par, b);
-        if (a == b) return;
-        if (a < b) {
-            const int s = a;
-            a = b;
-            b = s;
-        }
-        const int o = __hip_atomic_fetch_min(par + a, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (o == a) return;
-        a = o;                                              // a had been hung under o < a meanwhile: o and b are still to be joined
     }
 }
 

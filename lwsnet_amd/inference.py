@@ -55,6 +55,14 @@ position X.  `--save_stixels` also writes `<stem>_stixels.png`, the left image's
 depth ramp (near red, far blue, 60 m and beyond the same), and `<stem>_stixels.csv`, one line per stixel:
 strip,layer,x0,x1,y_top,y_base,n,disparity,z,x,height.  Camera and mode as for `--ground`.
 
+`--objects [--object_min_pixels N] [--save_objects]`: the obstacle objects of each map, on the device (lwsnet_amd.ops.objects: lws_objects
+on the codes of `--ground` and the u-disparity histogram of `--stixels`, which it implies) -- the connected cells of that histogram
+that hold at least a strip's row of pixels, each pixel mapped back to its cell's object, objects of fewer than N pixels (default 64)
+dropped; one log line with the number of objects, components and member pixels and the nearest object's depth z, lateral extent and
+size.  `--save_objects` also writes `<stem>_objects.png`, the left image's grey with each object's pixels tinted with a fixed palette
+colour by its number and its pixel box outlined, and `<stem>_objects.csv`, one line per object, nearest first:
+object,n,x_min,x_max,y_min,y_max,k_min,k_max,cells,disparity,z,X_min,X_max,Y_min,Y_max,Z_min,Z_max.  Camera and mode as for `--ground`.
+
 `--speckle SIZE [--speckle_diff D] [--speckle_fill]`: the connected blobs of at most SIZE pixels (4-neighbours joined when their
 disparities differ by <= D, default 1) are removed from the stage maps on the device (lws_speckle_filter) before the colour, 16-bit
 and point-cloud files are written, and each colour file gets a grey code map `<stem>_sp.png` beside it (kept 255, speckle 64, the
@@ -107,8 +115,8 @@ from . import imageio as io
 from . import outputs as out
 from . import pipeline
 from . import postprocess as post
-from .outputs import (STIXEL_COLOUR_DEPTH, bev_to_u8, conf_to_u8, ground_to_rgb, photo_to_u8, sigma_to_u8, stixels_to_csv,  # noqa: F401
-                      stixels_to_rgb, geometry_requested as _geometry_requested)      # these stay this module's names
+from .outputs import (STIXEL_COLOUR_DEPTH, bev_to_u8, conf_to_u8, ground_to_rgb, objects_to_csv, objects_to_rgb, photo_to_u8,  # noqa: F401
+                      sigma_to_u8, stixels_to_csv, stixels_to_rgb, geometry_requested as _geometry_requested)      # these stay this module's names
 from .postprocess import (add_lr_arguments, add_occ_arguments, add_speckle_arguments, add_wmedian_arguments, check_lr_arguments,
                           check_occ_arguments, check_speckle_arguments, check_wmedian_arguments)
 
@@ -252,6 +260,14 @@ def add_geometry_arguments(p):
                    help="--stixels, and write <stem>_stixels.png (the stixels tinted by depth over the left image's grey) and <stem>_stixels.csv")
     p.add_argument("--stixel_width", type=int, default=argparse.SUPPRESS, metavar="N", help="stixels: columns per strip, 1 .. 64 (default 8)")
     p.add_argument("--stixel_layers", type=int, default=argparse.SUPPRESS, metavar="N", help="stixels: obstacles per strip, nearest first, 1 .. 4 (default 2)")
+    # the object flags likewise
+    p.add_argument("--objects", action="store_true", default=argparse.SUPPRESS,
+                   help="--stixels, and log the number of objects (connected obstacles in strip and disparity) and the nearest one's depth, lateral "
+                        "extent and size")
+    p.add_argument("--save_objects", action="store_true", default=argparse.SUPPRESS,
+                   help="--objects, and write <stem>_objects.png (each object's pixels tinted and its box outlined over the left image's grey) and "
+                        "<stem>_objects.csv")
+    p.add_argument("--object_min_pixels", type=int, default=argparse.SUPPRESS, metavar="N", help="objects: the fewest pixels of an object (default 64)")
 
 
 def _list_pairs(args):
@@ -271,11 +287,13 @@ def _frame_file(path, left_path):
 
 
 def _geometry_defaults(args):
-    """The surface, stixel and ground flags' defaults, in the order in which the log's argument lines have shown them; --save_stixels
-    implies --stixels, and both and --save_ground imply --ground."""
+    """The surface, stixel, ground and object flags' defaults, in the order in which the log's argument lines have shown them;
+    --save_objects implies --objects, both and --save_stixels imply --stixels, and those and --save_ground imply --ground."""
     post.set_defaults(args, save_normals=False, save_mesh=False, max_jump=1.0, save_ground=False, save_stixels=False, stixels=False,
-                      stixel_width=8, stixel_layers=2, ground=False, ground_tol=0.2, max_height=3.0)
-    args.stixels = args.stixels or args.save_stixels
+                      stixel_width=8, stixel_layers=2, ground=False, ground_tol=0.2, max_height=3.0, save_objects=False, objects=False,
+                      object_min_pixels=64)
+    args.objects = args.objects or args.save_objects
+    args.stixels = args.stixels or args.save_stixels or args.objects
     args.ground = args.ground or args.save_ground or args.stixels
 
 
@@ -319,7 +337,9 @@ def check_geometry_arguments(p, args):
         p.error(f"--stixel_width must be in 1 .. 64, got {args.stixel_width}")
     if not 1 <= args.stixel_layers <= 4:
         p.error(f"--stixel_layers must be in 1 .. 4, got {args.stixel_layers}")
-    for name in ("stixels", "ground"):
+    if args.object_min_pixels < 1:
+        p.error(f"--object_min_pixels must be >= 1, got {args.object_min_pixels}")
+    for name in ("objects", "stixels", "ground"):
         if getattr(args, name):
             _needs_camera(p, args, f"--{name} and --save_{name}")
             post.sequential_only(p, args, f"--{name} / --save_{name}", "run")

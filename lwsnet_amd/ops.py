@@ -752,6 +752,58 @@ def stixels(disp, cameras, codes, height, min_disp=1.0, max_depth=float("inf"), 
     return StixelResult(rows, vals, u)
 
 
+ObjectResult = namedtuple("ObjectResult", ["rows", "vals", "labels", "info"])
+ObjectResult.__doc__ = """What objects returns, all on the device: rows int32 [B,max_objects,8] = {n, x_min, x_max, y_min, y_max, k_min, k_max,
+cells}, vals float32 [B,max_objects,8] = {disparity, z, X_min, X_max, Y_min, Y_max, Z_min, Z_max}, labels int32 [B,1,H,W] (the object's
+number per pixel, -1 for none; None unless asked for) and info int32 [B,4] = {occupied cells, components, kept components, member
+pixels of the kept ones}.  A slot with n = 0 is empty: -1 in the boxes and eight zeros."""
+
+
+def _object_args(min_disp, code_bits, width, sub, min_count, min_pixels, max_objects):
+    """The validated scalar arguments of objects, defaults resolved: min_count None is width."""
+    min_disp = _finite_pos("min_disp", min_disp)
+    width = _int_in("width", width, 1, 64)
+    top = 2 ** 31 - 1
+    return (min_disp, _int_in("code_bits", code_bits, 0, 63), width, _int_in("sub", sub, 1, 16),
+            _int_in("min_count", width if min_count is None else min_count, 1, top), _int_in("min_pixels", min_pixels, 1, top),
+            _int_in("max_objects", max_objects, 1, 65536))
+
+
+def objects(disp, cameras, codes, udisp, min_disp=1.0, max_depth=float("inf"), code_bits=1 << 2, width=8, sub=4, min_count=None,
+            min_pixels=64, max_objects=256, labels=True):
+    """The obstacle objects of disparity maps (include/lwsnet_objects.h, lws_objects): the connected components (8-neighbours) of the
+    cells of the u-disparity image that hold at least min_count pixels, each pixel mapped back to its cell's component, and per
+    component of at least min_pixels pixels -- nearest first -- its pixel box, bins, disparity, depth and box in camera coordinates.
+    codes: what ground_classify (or ground) returns for the same maps; udisp: what stixels(udisp=True) returns for them with the same
+    min_disp, max_depth, code_bits, width and sub (nbins is udisp.shape[2]).  min_count None means width: a cell counts once it holds
+    as many pixels as one row of its strip.  That default and min_pixels = 64 were chosen on synthetic road scenes only; they have
+    not met real data.  Returns an ObjectResult."""
+    if cameras is None:
+        raise ValueError("objects needs cameras")
+    min_disp, code_bits, width, sub, min_count, min_pixels, max_objects = _object_args(min_disp, code_bits, width, sub, min_count, min_pixels,
+                                                                                      max_objects)
+    d, _, cam = _geometry_inputs(disp, None, cameras, min_disp, max_depth)
+    B, _, H, W = d.shape
+    if H > 16384 or W > 16384:
+        raise ValueError(f"disp is {H}x{W}: objects takes maps up to 16384x16384")
+    S = -(-W // width)
+    if not isinstance(udisp, torch.Tensor) or udisp.dim() != 3:
+        raise ValueError("udisp must be a uint32 [B,S,nbins] tensor (what stixels(udisp=True) returns)")
+    nbins = _int_in("nbins = udisp.shape[2]", udisp.shape[2], 1, min(4096, 256 * sub))
+    if S * nbins > 1 << 22:
+        raise ValueError(f"{S} strips x {nbins} bins: objects takes up to 2^22 cells")
+    codes = _ground_codes(codes, d)
+    udisp = _tensor_of(udisp, "udisp", torch.uint32, (B, S, nbins), d.device, " (what stixels(udisp=True) returns)")
+    work = _workspace("lws_objects_workspace", d.device, B, W, width, nbins)
+    rows = torch.empty((B, max_objects, 8), device=d.device, dtype=torch.int32)
+    vals = torch.empty((B, max_objects, 8), device=d.device, dtype=torch.float32)
+    lab = torch.empty(d.shape, device=d.device, dtype=torch.int32) if labels else None
+    info = torch.empty((B, 4), device=d.device, dtype=torch.int32)
+    _call("lws_objects", d.device, d, cam, codes, udisp, B, H, W, min_disp, float(max_depth), code_bits, width, sub, nbins, min_count,
+          min_pixels, max_objects, work, rows, vals, lab, info)
+    return ObjectResult(rows, vals, lab, info)
+
+
 SpeckleResult = namedtuple("SpeckleResult", ["disp", "mask", "labels", "counts"])
 SpeckleResult.__doc__ = """What speckle_filter returns: the filtered (filled if asked) maps float32 [B,1,H,W], the uint8 code map (1 kept,
 3 speckle, the input code or 0 for an invalid pixel), labels int32 [B,1,H,W] (None unless want_labels) and counts, an int64

@@ -129,6 +129,45 @@ def stixels_to_csv(rows, vals, width, W):
     return "\n".join(lines) + "\n"
 
 
+# by object number, cycled: distinct hues that stay apart from the grey underneath
+OBJECT_COLOURS = np.array([[230, 25, 75], [60, 180, 75], [255, 225, 25], [0, 130, 200], [245, 130, 48], [145, 30, 180], [70, 240, 240],
+                           [240, 50, 230], [210, 245, 60], [250, 190, 212], [0, 128, 128], [170, 110, 40]], np.uint8)
+
+
+def objects_to_rgb(rows, labels, left_rgb):
+    """<stem>_objects.png: the left image's grey (_grey) with each object's pixels averaged with the colour of its number
+    (OBJECT_COLOURS, cycled) and its pixel box x_min .. x_max by y_min .. y_max outlined in that colour.  rows: one image's [N,8];
+    labels: its [H,W]; the boxes are drawn far to near, so the nearest shows."""
+    grey = _grey(left_rgb)
+    out = np.repeat(grey[..., None], 3, axis=2)
+    rows, labels = np.asarray(rows), np.asarray(labels)
+    colours = OBJECT_COLOURS.astype(np.uint32)
+    member = labels >= 0
+    out[member] = (colours[labels[member] % len(colours)] + grey[member][:, None] + 1) >> 1
+    for j in range(rows.shape[0] - 1, -1, -1):
+        n, x_min, x_max, y_min, y_max = (int(v) for v in rows[j, :5])
+        if n <= 0:
+            continue
+        colour = colours[j % len(colours)]
+        out[[y_min, y_max], x_min:x_max + 1] = colour
+        out[y_min:y_max + 1, [x_min, x_max]] = colour
+    return out.astype(np.uint8)
+
+
+OBJECT_CSV_HEADER = "object,n,x_min,x_max,y_min,y_max,k_min,k_max,cells,disparity,z,X_min,X_max,Y_min,Y_max,Z_min,Z_max"
+
+
+def objects_to_csv(rows, vals):
+    """<stem>_objects.csv as a string: OBJECT_CSV_HEADER, then one line per non-empty slot of one image's [N,8] rows and vals, nearest
+    first; the eight values with six decimals."""
+    rows, vals = np.asarray(rows), np.asarray(vals)
+    lines = [OBJECT_CSV_HEADER]
+    for j in range(rows.shape[0]):
+        if rows[j, 0] > 0:
+            lines.append(",".join([str(j)] + [str(int(v)) for v in rows[j]] + ["{:.6f}".format(float(v)) for v in vals[j]]))
+    return "\n".join(lines) + "\n"
+
+
 # ---- the writers ----
 def save_png_gray8(path, img):
     with open(path, "wb") as f:
@@ -205,7 +244,7 @@ def _save_mesh(frame, stage, stem, args, log, disp, mask):
 
 def _save_ground(frame, stage, stem, args, log, disp, mask):
     """--ground: the road of one map (ops.ground) as a log line; --save_ground: <stem>_ground.png and <stem>_bev.png; --stixels: the
-    stixels of the same map behind them, on this GroundResult."""
+    stixels of the same map behind them, on this GroundResult; --objects: the objects behind those, on the stixels' histogram."""
     from . import ops
     from .geometry import GroundPlane
     res = ops.ground(disp, frame.cam, mask, args.min_disp, args.max_depth, maxdisp=args.max_disparity, ground_tol=args.ground_tol,
@@ -223,16 +262,19 @@ def _save_ground(frame, stage, stem, args, log, disp, mask):
         written += [stem + "_ground.png", stem + "_bev.png"]
         log.info("Save ground codes = {}, bird's-eye heights = {}".format(stem + "_ground.png", stem + "_bev.png"))
     if args.stixels:
-        written += _save_stixels(frame, stage, stem, args, log, disp, res)
+        paths, stixels = _save_stixels(frame, stage, stem, args, log, disp, res)
+        written += paths
+        if args.objects:
+            written += _save_objects(frame, stage, stem, args, log, disp, res, stixels)
     return written
 
 
 def _save_stixels(frame, stage, stem, args, log, disp, ground):
     """--stixels: the stixels of one map (ops.stixels on the codes and heights of its GroundResult) as a log line; --save_stixels:
-    <stem>_stixels.png and <stem>_stixels.csv."""
+    <stem>_stixels.png and <stem>_stixels.csv.  Returns the paths and the StixelResult (with --objects: its u-disparity histogram)."""
     from . import ops
     res = ops.stixels(disp, frame.cam, ground.codes, ground.height, args.min_disp, args.max_depth, width=args.stixel_width,
-                      maxdisp=args.max_disparity, layers=args.stixel_layers)
+                      maxdisp=args.max_disparity, layers=args.stixel_layers, udisp=args.objects)
     rows, vals = res.rows[0].cpu().numpy(), res.vals[0].cpu().numpy()
     found = rows[..., 0] > 0
     nearest = "none"
@@ -242,16 +284,37 @@ def _save_stixels(frame, stage, stem, args, log, disp, ground):
     log.info("Stixels: {} in {} strips of {} columns x {} layers, nearest: {}".format(int(found.sum()), rows.shape[0], args.stixel_width,
                                                                                      rows.shape[1], nearest))
     if not args.save_stixels:
-        return []
+        return [], res
     io.save_png(stem + "_stixels.png", stixels_to_rgb(rows, vals, _rgb_on_host(frame.left), args.stixel_width, STIXEL_COLOUR_DEPTH))
     with open(stem + "_stixels.csv", "w", encoding="ascii", newline="") as f:
         f.write(stixels_to_csv(rows, vals, args.stixel_width, disp.shape[3]))
     log.info("Save stixels = {}, {}".format(stem + "_stixels.png", stem + "_stixels.csv"))
-    return [stem + "_stixels.png", stem + "_stixels.csv"]
+    return [stem + "_stixels.png", stem + "_stixels.csv"], res
+
+
+def _save_objects(frame, stage, stem, args, log, disp, ground, stixels):
+    """--objects: the objects of one map (ops.objects on the codes of its GroundResult and the histogram of its StixelResult) as a
+    log line; --save_objects: <stem>_objects.png and <stem>_objects.csv."""
+    from . import ops
+    res = ops.objects(disp, frame.cam, ground.codes, stixels.udisp, args.min_disp, args.max_depth, width=args.stixel_width,
+                      min_pixels=args.object_min_pixels, labels=args.save_objects)
+    rows, vals, info = res.rows[0].cpu().numpy(), res.vals[0].cpu().numpy(), res.info[0].cpu().tolist()
+    nearest = "none"
+    if rows[0, 0] > 0:                                      # object 0 is the one whose nearest cell is nearest
+        nearest = "z = {:.2f} m, X = {:.2f} .. {:.2f} m, {} pixels in {} cells".format(float(vals[0, 1]), float(vals[0, 2]), float(vals[0, 3]),
+                                                                                      int(rows[0, 0]), int(rows[0, 7]))
+    log.info("Objects: {} of {} components in {} cells, {} member pixels, nearest: {}".format(info[2], info[1], info[0], info[3], nearest))
+    if not args.save_objects:
+        return []
+    io.save_png(stem + "_objects.png", objects_to_rgb(rows, res.labels[0, 0].cpu().numpy(), _rgb_on_host(frame.left)))
+    with open(stem + "_objects.csv", "w", encoding="ascii", newline="") as f:
+        f.write(objects_to_csv(rows, vals))
+    log.info("Save objects = {}, {}".format(stem + "_objects.png", stem + "_objects.csv"))
+    return [stem + "_objects.png", stem + "_objects.csv"]
 
 
 # the geometry outputs in the order they are written: (the flags that ask for one, its writer); --save_ground, --stixels and
-# --save_stixels imply --ground, whose writer makes their files
+# --save_stixels imply --ground, whose writer makes their files; --objects and --save_objects imply --stixels and ride on it
 GEOMETRY = ((("save_disp16", "save_depth"), _save_depth_maps), (("save_ply",), _save_ply), (("save_normals",), _save_normals),
             (("save_mesh",), _save_mesh), (("ground", "save_ground", "stixels", "save_stixels"), _save_ground))
 
@@ -263,8 +326,8 @@ def geometry_requested(args):
 
 def save_geometry(frame, stage, stem, args, log, disp, mask):
     """The geometry files of one map, <stem>_disp16.png, <stem>_depth16.png, <stem>.ply, <stem>_normals.png, <stem>_mesh.ply,
-    <stem>_ground.png, <stem>_bev.png, <stem>_stixels.png, <stem>_stixels.csv; with --ground the road's log line, with --stixels the
-    stixels'.  mask: the code map of merge_keep (only code-1 pixels kept) or None."""
+    <stem>_ground.png, <stem>_bev.png, <stem>_stixels.png, <stem>_stixels.csv, <stem>_objects.png, <stem>_objects.csv; with --ground the
+    road's log line, with --stixels the stixels', with --objects the objects'.  mask: the code map of merge_keep (only code-1 pixels kept) or None."""
     written = []
     for flags, writer in GEOMETRY:
         if any(getattr(args, flag) for flag in flags):
