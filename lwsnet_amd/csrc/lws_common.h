@@ -119,6 +119,13 @@ static inline int ensure_dyn_lds(std::atomic<uint64_t> &done, const void *fn, in
     if (bit != 0) done.fetch_or(bit, std::memory_order_release);
     return LWS_OK;
 }
+// lets `Kernel` be launched with `bytes` of dynamic LDS (ensure_dyn_lds; the per-device mask is per kernel)
+template <auto Kernel>
+static int allow_dyn_lds(int bytes)
+{
+    static std::atomic<uint64_t> attr_done{0};
+    return ensure_dyn_lds(attr_done, reinterpret_cast<const void *>(Kernel), bytes);
+}
 
 // 16-byte activation store.  wt (wave-uniform) selects a write-through store (sc0 sc1): the line does not stay dirty in
 // the XCD's L2, so the end-of-kernel release has less to write back.  It pays for small outputs and costs for large ones

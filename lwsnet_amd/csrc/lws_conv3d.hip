@@ -1264,14 +1264,6 @@ static TileGrid tile_grid(int B, int D, int h, int w, int TX, int TY, int TD)
     return {tiles_x, tiles_y, tiles_d, dim3(tiles_x * tiles_y * tiles_d, B)};
 }
 
-// lets `Kernel` be launched with `bytes` of dynamic LDS (ensure_dyn_lds; the per-device mask is per kernel)
-template <auto Kernel>
-static int allow_dyn_lds(int bytes)
-{
-    static std::atomic<uint64_t> attr_done{0};
-    return ensure_dyn_lds(attr_done, reinterpret_cast<const void *>(Kernel), bytes);
-}
-
 static int unsupported_c3(const char *who, int c3, const char *also = "")
 {
     set_error("%s: unsupported channel count %d (8, 16, 32)%s", who, c3, also);

@@ -315,11 +315,8 @@ static int conv2d_pair_launch(const Conv2dLayer &a, const Conv2dLayer &b, const 
         return LWS_ERR_STATE;
     }
     const size_t lds = (size_t)Cfg::LDS_FLOATS * sizeof(float);
-    static std::atomic<uint64_t> attr_done{0};
-    if (lds > 48 * 1024) {
-        const int rc_ = ensure_dyn_lds(attr_done, reinterpret_cast<const void *>(&k_conv2d_pair<CIN, CM, COUT, SA, DA, DB, NW>), (int)lds);
-        if (rc_) return rc_;
-    }
+    if (lds > 48 * 1024)
+        if (const int rc = allow_dyn_lds<&k_conv2d_pair<CIN, CM, COUT, SA, DA, DB, NW>>((int)lds)) return rc;
     dim3 grid(cdiv(WA, 8), cdiv(HA, 8), N), block(Cfg::NT);
     hipLaunchKernelGGL((k_conv2d_pair<CIN, CM, COUT, SA, DA, DB, NW>), grid, block, lds, st, in, in2, n1, a.w_pair, a.bn_s,
                        a.bn_t, a.relu ? 1 : 0, b.w_pair, b.bn_s, b.bn_t, res, b.relu ? 1 : 0, out, H, W, HA, WA);

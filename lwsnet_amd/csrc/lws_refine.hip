@@ -87,7 +87,7 @@ struct RefTile {
 // r03 and removed: XCD-contiguous runs of that list, and the phase slowest inside an XCD's run -- 66.0 vs 69.3 / 67.2 us per
 // k_ref_dws launch at 8 x 256x512 (profiles/r03/experiments/rbench_b8_ref_order.txt): the halo re-reads already hit L2 / the
 // Infinity Cache (tools/micro/copybw.hip: a phase-grid copy costs the same with and without the halo).
-__device__ __forceinline__ RefTile ref_tile(int dil, int nbx, int nby, int tile_rows = RT_Y)
+__device__ __forceinline__ RefTile ref_tile(int dil, int nbx, int nby)
 {
     int bid = blockIdx.x;
     const int d2 = dil * dil;
@@ -98,9 +98,80 @@ __device__ __forceinline__ RefTile ref_tile(int dil, int nbx, int nby, int tile_
     const int by = bid % nby;
     RefTile t;
     t.b = bid / nby;
-    t.Y0 = by * tile_rows * dil + phase / dil;
+    t.Y0 = by * RT_Y * dil + phase / dil;
     t.X0 = bx * RT_X * dil + phase % dil;
     return t;
+}
+
+// Staging of a dense 32-channel halo tile of HY x HX pixels that starts PAD pixels before the tile origin (Y0, X0): item = (halo
+// pixel hp, 4-channel group c4), hp = (tid >> 3) + 32 i.  Unconditional clamped loads, all in flight; okv[i] = the item exists
+// and lies in the image.
+constexpr int halo32_iters(int npx) { return (npx * 8 + 255) / 256; }
+template <int HY, int HX, int PAD>
+__device__ __forceinline__ void halo32_loads(const float *inb, int Y0, int X0, int H, int W, int tid,
+                                             float4 (&c)[halo32_iters(HY * HX)], bool (&okv)[halo32_iters(HY * HX)])
+{
+    const int c4 = tid & 7;
+#pragma unroll
+    for (int i = 0; i < halo32_iters(HY * HX); ++i) {
+        const int hp = (tid >> 3) + 32 * i;
+        const int hy = hp / HX, hx = hp - hy * HX;
+        const int gy = Y0 + (hy - PAD), gx = X0 + (hx - PAD);
+        okv[i] = hp < HY * HX && gy >= 0 && gy < H && gx >= 0 && gx < W;
+        const int off = okv[i] ? (gy * W + gx) * 32 + c4 * 4 : 0;      // one image < 2^31 floats
+        c[i] = *reinterpret_cast<const float4 *>(inb + off);
+    }
+}
+
+// Per-thread weights of a depthwise-separable block: the pointwise A fragments and this thread's depthwise taps (its channel
+// group c4 is fixed)
+__device__ __forceinline__ void dws_weights(const float4 *pwpk, const float *dw, int lane, int c4, float4 (&aw)[2][2], float4 (&wd)[9])
+{
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) aw[q][mt] = pwpk[(q * 2 + mt) * 64 + lane];
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) wd[tap] = *reinterpret_cast<const float4 *>(dw + tap * 32 + c4 * 4);
+}
+
+// Pointwise 32 -> 32 on fp32 MFMA: Out^T[cout, pixel] = W[cout, cin] * X[cin, pixel] for NTW N-tiles of 16 pixels (bv[r][q]: the
+// B operand of tile r, channels 16q ..) x both output-channel tiles, K = 32 = 8 MFMAs per accumulator, channels ascending
+template <int NTW>
+__device__ __forceinline__ void pointwise32_mfma(const float4 (&aw)[2][2], const float4 (&bv)[NTW][2], floatx4 (&acc)[NTW][2])
+{
+#pragma unroll
+    for (int r = 0; r < NTW; ++r)
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) acc[r][mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int r = 0; r < NTW; ++r)
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt)
+                    acc[r][mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(f4c(aw[q][mt], j), f4c(bv[r][q], j), acc[r][mt], 0, 0, 0);
+}
+
+// Output store of a phase-grid tile (refinement2[0], both forms): this wave's R tile rows from row0 on, both output-channel
+// tiles; lane (n, g) holds channels 16mt + 4g .. +3 of pixel (row, n).  outb: the image's map [H,W,32].
+template <int R>
+__device__ __forceinline__ void store_tile_rows(float *outb, const RefTile t, int row0, const floatx4 (&acc)[R][2], int H, int W,
+                                                int dil, int n, int g, int wt)
+{
+    const int gx = t.X0 + n * dil;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int gy = t.Y0 + (row0 + r) * dil;
+        if (gy < H && gx < W) {
+            float *o = outb + ((int64_t)gy * W + gx) * 32;
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+                store_act4(o + mt * 16 + 4 * g, make_float4(acc[r][mt][0], acc[r][mt][1], acc[r][mt][2], acc[r][mt][3]), wt);
+        }
+    }
 }
 
 // =============================================================================================
@@ -203,6 +274,8 @@ __global__ __launch_bounds__(256, 4) void k_ref_dws(const float *__restrict__ in
     const float4 t4 = *reinterpret_cast<const float4 *>(bn_t + c4 * 4);
 
     // 1. stage: item = (halo pixel hp, 4-channel group c4); hp = (tid >> 3) + 32 i.  Unconditional clamped loads first.
+    //    (The FIRST == 0 loads are halo32_loads with a dilation, and the store below is store_tile_rows with a 32-bit pixel index;
+    //    both keep their own lines, which hold this kernel's machine code where it was -- profiles/NOTES.md, "Refinement file pass".)
     constexpr int NPX = RH_Y * RH_X, SITER = (NPX * 8 + 255) / 256;
     float4 c[SITER];
     bool okv[SITER];
@@ -272,15 +345,8 @@ __global__ __launch_bounds__(256, 4) void k_ref_dws(const float *__restrict__ in
             c[i] = *reinterpret_cast<const float4 *>(inb + off);
         }
     }
-    // pointwise A fragments and this thread's depthwise weights (its channel group is fixed)
-    float4 aw[2][2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) aw[q][mt] = pwpk[(q * 2 + mt) * 64 + lane];
-    float4 wd[9];
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) wd[tap] = *reinterpret_cast<const float4 *>(dw + tap * 32 + c4 * 4);
+    float4 aw[2][2], wd[9];
+    dws_weights(pwpk, dw, lane, c4, aw, wd);
     if (FIRST == 0) {
 #pragma unroll
         for (int i = 0; i < SITER; ++i) {
@@ -333,24 +399,12 @@ __global__ __launch_bounds__(256, 4) void k_ref_dws(const float *__restrict__ in
     // 3. pointwise MFMA: wave handles tile rows 2*wave, 2*wave+1 x both output-channel tiles
     const int n = lane & 15, g = lane >> 4;
     floatx4 acc[2][2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) acc[r][mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
     float4 bv[2][2];
 #pragma unroll
     for (int r = 0; r < 2; ++r)
 #pragma unroll
         for (int q = 0; q < 2; ++q) bv[r][q] = sB[(4 * q + g) * DWS_SB + (2 * wave + r) * RT_X + n];
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 2; ++r)
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-                    acc[r][mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(f4c(aw[q][mt], j), f4c(bv[r][q], j), acc[r][mt], 0, 0, 0);
+    pointwise32_mfma(aw, bv, acc);
 
     LWS_STAMPK(5, 3);
     // 4. store: lane (n, g) holds channels 16mt + 4g .. +3 of pixel (row, n)
@@ -374,41 +428,60 @@ __global__ __launch_bounds__(256, 4) void k_ref_dws(const float *__restrict__ in
 // channels-last maps are staged side by side.  fp32-MFMA implicit GEMM, K = 9 taps x 64 channels = 144 MFMAs per
 // accumulator; weights streamed from L2 in fragment order one step ahead (same scheme as k_conv3d_mid16).
 // =============================================================================================
-template <int TY, int NW>   // tile rows, waves per workgroup (TY/NW rows each)
-__global__ __launch_bounds__(64 * NW) void k_ref_conv64(const float *__restrict__ inL, const float *__restrict__ inD,
-                                                    const float *__restrict__ bn_s, const float *__restrict__ bn_t,   // [64]
-                                                    const float4 *__restrict__ wpk,   // [tap][qq][mt][lane]
-                                                    float *__restrict__ out, int H, int W, int dil, int nbx, int nby, int wt)
+constexpr int C64X_VSB = 208;                        // split-bf16 form: LDS pixel stride in bytes, 3 variants x 64 B + 16 B
+constexpr int C64X_STEP_U4 = 2 * 3 * 64;             // ... and uint4 per (tap, tensor) step of its packed weights
+
+// Both forms: the RT_Y x RT_X tile of k_ref_dws, NW waves of RW rows each; staging item = (tensor, halo pixel, 16-channel
+// group) = 64 bytes of the concat, it = 2 (tensor * NPX + halo pixel) + group
+struct Conv64Cfg {
+    static constexpr int NW = 4, NT = 64 * NW, RW = RT_Y / NW, NPX = RH_Y * RH_X;
+    static constexpr int ITEMS = 2 * NPX * 2, SITER = (ITEMS + NT - 1) / NT;
+    static constexpr int LDS_BYTES = 2 * NPX * C64X_VSB;      // k_ref_conv64x only
+    static_assert(RW == 2, "sub-steps j < RW of k_ref_conv64's step prefetch the fragments, the other two the weights");
+};
+
+// Staging loads of the concat [inL, inD], both forms: unconditional, clamped loads first (see k_ref_dws)
+__device__ __forceinline__ void conv64_stage_loads(const float *__restrict__ inL, const float *__restrict__ inD, const RefTile t,
+                                                   int H, int W, int dil, int tid, float4 (&c)[Conv64Cfg::SITER][4],
+                                                   bool (&okv)[Conv64Cfg::SITER])
 {
-    constexpr int HY = TY + 2, NPX = HY * RH_X, RW = TY / NW, NT = 64 * NW;
-    static_assert(TY % NW == 0 && RW >= 1 && RW <= 4, "rows must split evenly over the waves");
+    using Cfg = Conv64Cfg;
+#pragma unroll
+    for (int i = 0; i < Cfg::SITER; ++i) {
+        const int it = tid + i * Cfg::NT;
+        const int q = it & 1, hp = (it >> 1) % Cfg::NPX, ten = (it >> 1) / Cfg::NPX;
+        const int hy = hp / RH_X, hx = hp % RH_X;
+        const int gy = t.Y0 + (hy - 1) * dil, gx = t.X0 + (hx - 1) * dil;
+        okv[i] = it < Cfg::ITEMS && gy >= 0 && gy < H && gx >= 0 && gx < W;
+        const float *base = (ten == 1 && it < Cfg::ITEMS ? inD : inL) + (int64_t)t.b * H * W * 32;
+        const float4 *src = reinterpret_cast<const float4 *>(base + (okv[i] ? ((int64_t)gy * W + gx) * 32 + q * 16 : 0));
+#pragma unroll
+        for (int k = 0; k < 4; ++k) c[i][k] = src[k];
+    }
+}
+
+__global__ __launch_bounds__(Conv64Cfg::NT) void k_ref_conv64(const float *__restrict__ inL, const float *__restrict__ inD,
+                                                              const float *__restrict__ bn_s, const float *__restrict__ bn_t,   // [64]
+                                                              const float4 *__restrict__ wpk,   // [tap][qq][mt][lane]
+                                                              float *__restrict__ out, int H, int W, int dil, int nbx, int nby, int wt)
+{
+    using Cfg = Conv64Cfg;
+    constexpr int NPX = Cfg::NPX, RW = Cfg::RW, NT = Cfg::NT, SITER = Cfg::SITER;
     __shared__ __attribute__((aligned(16))) float sA[2 * NPX * RVS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const RefTile t = ref_tile(dil, nbx, nby, TY);
+    const RefTile t = ref_tile(dil, nbx, nby);
     const int n = lane & 15, g = lane >> 4;
     LWS_STAMPK(6, 0);
 
-    // stage: item = (tensor, halo pixel, 16-channel group) = 64 bytes
-    constexpr int ITEMS = 2 * NPX * 2, SITER = (ITEMS + NT - 1) / NT;
+    // stage: BN + ReLU of the loaded items (zeros outside the image), into the two LDS images
     {
         float4 c[SITER][4];
         bool okv[SITER];
-#pragma unroll
-        for (int i = 0; i < SITER; ++i) {          // unconditional, clamped loads first (see k_ref_dws)
-            const int it = tid + i * NT;
-            const int q = it & 1, hp = (it >> 1) % NPX, ten = (it >> 1) / NPX;
-            const int hy = hp / RH_X, hx = hp % RH_X;
-            const int gy = t.Y0 + (hy - 1) * dil, gx = t.X0 + (hx - 1) * dil;
-            okv[i] = it < ITEMS && gy >= 0 && gy < H && gx >= 0 && gx < W;
-            const float *base = (ten == 1 && it < ITEMS ? inD : inL) + (int64_t)t.b * H * W * 32;
-            const float4 *src = reinterpret_cast<const float4 *>(base + (okv[i] ? ((int64_t)gy * W + gx) * 32 + q * 16 : 0));
-#pragma unroll
-            for (int k = 0; k < 4; ++k) c[i][k] = src[k];
-        }
+        conv64_stage_loads(inL, inD, t, H, W, dil, tid, c, okv);
 #pragma unroll
         for (int i = 0; i < SITER; ++i) {
             const int it = tid + i * NT;
-            if (it < ITEMS) {
+            if (it < Cfg::ITEMS) {
                 const int q = it & 1, hp = (it >> 1) % NPX, ten = (it >> 1) / NPX;
                 const float4 *sp = reinterpret_cast<const float4 *>(bn_s + ten * 32 + q * 16);
                 const float4 *tp = reinterpret_cast<const float4 *>(bn_t + ten * 32 + q * 16);
@@ -468,8 +541,8 @@ __global__ __launch_bounds__(64 * NW) void k_ref_conv64(const float *__restrict_
                         acc[r][mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(f4c(wbuf[0][qq][mt], j), f4c(bc[r], j), acc[r][mt], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
                 if (j < RW) bn[j] = qq < 3 ? frag(j, tap, qq + 1) : frag(j, tn, 0);
-                if (j >= 2) {      // next tap's 8 weight fragments: one per (qq, j in {2,3})
-                    const int l = qq * 2 + (j - 2);
+                else {             // next tap's 8 weight fragments: one per (qq, j in {2,3})
+                    const int l = qq * 2 + (j - RW);
                     wbuf[1][l >> 1][l & 1] = wp[(((tap + 1) * 4 + (l >> 1)) * 2 + (l & 1)) * 64];
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -481,18 +554,7 @@ __global__ __launch_bounds__(64 * NW) void k_ref_conv64(const float *__restrict_
             for (int mt = 0; mt < 2; ++mt) wbuf[0][qq][mt] = wbuf[1][qq][mt];
     }
     LWS_STAMPK(6, 2);
-    float *outb = out + (int64_t)t.b * H * W * 32;
-    const int gx = t.X0 + n * dil;
-#pragma unroll
-    for (int r = 0; r < RW; ++r) {
-        const int gy = t.Y0 + (RW * wave + r) * dil;
-        if (gy < H && gx < W) {
-            float *o = outb + ((int64_t)gy * W + gx) * 32;
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-                store_act4(o + mt * 16 + 4 * g, make_float4(acc[r][mt][0], acc[r][mt][1], acc[r][mt][2], acc[r][mt][3]), wt);
-        }
-    }
+    store_tile_rows(out + (int64_t)t.b * H * W * 32, t, RW * wave, acc, H, W, dil, n, g, wt);
     LWS_STAMPK(6, 3);
 }
 
@@ -505,29 +567,17 @@ __global__ __launch_bounds__(64 * NW) void k_ref_conv64(const float *__restrict_
 // the host into A fragments [step][mt][variant][lane][8] (pack_conv64_bf16x3) and streamed two steps ahead through a
 // three-slot register ring; activation fragments are double-buffered by step parity.
 // =============================================================================================
-constexpr int C64X_VSB = 208;                        // LDS pixel stride in bytes: 3 variants x 64 B + 16 B
-constexpr int C64X_STEP_U4 = 2 * 3 * 64;             // uint4 per (tap, tensor) step of the packed weights
-
-template <int TY, int NW>
-struct Conv64xCfg {
-    static constexpr int HY = TY + 2, NPX = HY * RH_X, RW = TY / NW, NT = 64 * NW;
-    static constexpr int ITEMS = 2 * NPX * 2, SITER = (ITEMS + NT - 1) / NT;
-    static constexpr int LDS_BYTES = 2 * NPX * C64X_VSB;
-    static_assert(TY % NW == 0 && RW >= 1 && RW <= 4, "rows must split evenly over the waves");
-};
-
-template <int TY, int NW>
-__global__ __launch_bounds__(64 * NW) void k_ref_conv64x(const float *__restrict__ inL, const float *__restrict__ inD,
-                                                     const float *__restrict__ bn_s, const float *__restrict__ bn_t,   // [64]
-                                                     const uint4 *__restrict__ wpk,   // [20][2][3][64] x 8 bf16
-                                                     float *__restrict__ out, int H, int W, int dil, int nbx, int nby, int wt)
+__global__ __launch_bounds__(Conv64Cfg::NT) void k_ref_conv64x(const float *__restrict__ inL, const float *__restrict__ inD,
+                                                               const float *__restrict__ bn_s, const float *__restrict__ bn_t,   // [64]
+                                                               const uint4 *__restrict__ wpk,   // [20][2][3][64] x 8 bf16
+                                                               float *__restrict__ out, int H, int W, int dil, int nbx, int nby, int wt)
 {
-    using Cfg = Conv64xCfg<TY, NW>;
+    using Cfg = Conv64Cfg;
     constexpr int NPX = Cfg::NPX, RW = Cfg::RW, NT = Cfg::NT, SITER = Cfg::SITER, VSB = C64X_VSB;
     extern __shared__ __attribute__((aligned(16))) float lds64x[];
     unsigned char *ldsb = reinterpret_cast<unsigned char *>(lds64x);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const RefTile t = ref_tile(dil, nbx, nby, TY);
+    const RefTile t = ref_tile(dil, nbx, nby);
     const int n = lane & 15, g = lane >> 4;
     LWS_STAMPK(21, 0);
 
@@ -535,18 +585,7 @@ __global__ __launch_bounds__(64 * NW) void k_ref_conv64x(const float *__restrict
     {
         float4 c[SITER][4];
         bool okv[SITER];
-#pragma unroll
-        for (int i = 0; i < SITER; ++i) {
-            const int it = tid + i * NT;
-            const int q = it & 1, hp = (it >> 1) % NPX, ten = (it >> 1) / NPX;
-            const int hy = hp / RH_X, hx = hp % RH_X;
-            const int gy = t.Y0 + (hy - 1) * dil, gx = t.X0 + (hx - 1) * dil;
-            okv[i] = it < Cfg::ITEMS && gy >= 0 && gy < H && gx >= 0 && gx < W;
-            const float *base = (ten == 1 && it < Cfg::ITEMS ? inD : inL) + (int64_t)t.b * H * W * 32;
-            const float4 *src = reinterpret_cast<const float4 *>(base + (okv[i] ? ((int64_t)gy * W + gx) * 32 + q * 16 : 0));
-#pragma unroll
-            for (int k = 0; k < 4; ++k) c[i][k] = src[k];
-        }
+        conv64_stage_loads(inL, inD, t, H, W, dil, tid, c, okv);
 #pragma unroll
         for (int i = 0; i < SITER; ++i) {
             const int it = tid + i * NT;
@@ -632,18 +671,7 @@ __global__ __launch_bounds__(64 * NW) void k_ref_conv64x(const float *__restrict
                 }
     }
     LWS_STAMPK(21, 2);
-    float *outb = out + (int64_t)t.b * H * W * 32;
-    const int gx = t.X0 + n * dil;
-#pragma unroll
-    for (int r = 0; r < RW; ++r) {
-        const int gy = t.Y0 + (RW * wave + r) * dil;
-        if (gy < H && gx < W) {
-            float *o = outb + ((int64_t)gy * W + gx) * 32;
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-                store_act4(o + mt * 16 + 4 * g, make_float4(acc[r][mt][0], acc[r][mt][1], acc[r][mt][2], acc[r][mt][3]), wt);
-        }
-    }
+    store_tile_rows(out + (int64_t)t.b * H * W * 32, t, RW * wave, acc, H, W, dil, n, g, wt);
     LWS_STAMPK(21, 3);
 }
 
@@ -667,14 +695,7 @@ __global__ __launch_bounds__(256) void k_ref_last(const float *__restrict__ in, 
     const int c4 = tid & 7;
     float4 c[SITER];
     bool okv[SITER];
-#pragma unroll
-    for (int i = 0; i < SITER; ++i) {
-        const int hp = (tid >> 3) + 32 * i;
-        const int hy = hp / LAST_HX, hx = hp - hy * LAST_HX;
-        const int gy = y0 + hy - 1, gx = x0 + hx - 1;
-        okv[i] = hp < LAST_NPX && gy >= 0 && gy < H && gx >= 0 && gx < W;
-        c[i] = *reinterpret_cast<const float4 *>(inb + (okv[i] ? (gy * W + gx) * 32 + c4 * 4 : 0));
-    }
+    halo32_loads<LAST_HY, LAST_HX, 1>(inb, y0, x0, H, W, tid, c, okv);
 #pragma unroll
     for (int i = 0; i < SITER; ++i) {
         const int hp = (tid >> 3) + 32 * i;
@@ -745,22 +766,9 @@ __global__ __launch_bounds__(256, 2) void k_ref_dws_last(const float *__restrict
     constexpr int SITER = (FL_NIN * 8 + 255) / 256;
     float4 c[SITER];
     bool okv[SITER];
-#pragma unroll
-    for (int i = 0; i < SITER; ++i) {
-        const int hp = (tid >> 3) + 32 * i;
-        const int hy = hp / FL_IX, hx = hp - hy * FL_IX;
-        const int gy = t.Y0 + hy - 2, gx = t.X0 + hx - 2;
-        okv[i] = hp < FL_NIN && gy >= 0 && gy < H && gx >= 0 && gx < W;
-        c[i] = *reinterpret_cast<const float4 *>(inb + (okv[i] ? (gy * W + gx) * 32 + c4 * 4 : 0));
-    }
-    float4 aw[2][2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) aw[q][mt] = pwpk[(q * 2 + mt) * 64 + lane];
-    float4 wd[9];
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) wd[tap] = *reinterpret_cast<const float4 *>(dw + tap * 32 + c4 * 4);
+    halo32_loads<FL_IY, FL_IX, 2>(inb, t.Y0, t.X0, H, W, tid, c, okv);
+    float4 aw[2][2], wd[9];
+    dws_weights(pwpk, dw, lane, c4, aw, wd);
 #pragma unroll
     for (int i = 0; i < SITER; ++i) {
         const int hp = (tid >> 3) + 32 * i;
@@ -802,21 +810,10 @@ __global__ __launch_bounds__(256, 2) void k_ref_dws_last(const float *__restrict
         floatx4 acc[NTW][2];
         float4 bv[NTW][2];
 #pragma unroll
-        for (int r = 0; r < NTW; ++r) {
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) acc[r][mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
+        for (int r = 0; r < NTW; ++r)
 #pragma unroll
             for (int q = 0; q < 2; ++q) bv[r][q] = sB[(4 * q + g) * FL_SB + (wave * NTW + r) * 16 + n];
-        }
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int r = 0; r < NTW; ++r)
-#pragma unroll
-                    for (int mt = 0; mt < 2; ++mt)
-                        acc[r][mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(f4c(aw[q][mt], j), f4c(bv[r][q], j), acc[r][mt], 0, 0, 0);
+        pointwise32_mfma(aw, bv, acc);
         // lane (n, g) holds channels 16 mt + 4 g .. + 3 of ring pixel p -> plane 4 mt + g of sC; zeros outside the image
 #pragma unroll
         for (int r = 0; r < NTW; ++r) {
@@ -877,33 +874,32 @@ int launch_ref_first(const float *in, int cin, const float *w, float *out, int B
     return LWS_OK;
 }
 
-// Launch geometry of the phase-grid kernels (ref_tile): image blocks of (tile_rows * dil) x (RT_X * dil) pixels, dil * dil phases
+// Launch geometry of the phase-grid kernels (ref_tile): image blocks of (RT_Y * dil) x (RT_X * dil) pixels, dil * dil phases
 // of each, B images.
 struct RefGrid {
     int nbx, nby;
     dim3 grid;
 };
-static RefGrid ref_grid(int B, int H, int W, int dil, int tile_rows = RT_Y)
+static RefGrid ref_grid(int B, int H, int W, int dil)
 {
-    const int nbx = cdiv(W, RT_X * dil), nby = cdiv(H, tile_rows * dil);
+    const int nbx = cdiv(W, RT_X * dil), nby = cdiv(H, RT_Y * dil);
     return {nbx, nby, dim3(nbx * nby * dil * dil * B)};
 }
 
-// One k_ref_dws launch.  wfrag: the fused first convolution's fragments (FIRST != 0); plow, ph, pw, pmat: the deferred disparity
-// map a FIRST == 1 block may read and write out -- by default there is none.
-template <int FIRST>
-static void ref_dws_launch(const RefDws &l, const float *in, const float *wfrag, float *out, int B, int H, int W, hipStream_t st,
-                           float ioff, const float *plow = nullptr, int ph = 0, int pw = 0, float *pmat = nullptr)
+// One k_ref_dws launch.  kernel: k_ref_dws<FIRST>; wfrag: the fused first convolution's fragments (FIRST != 0); def: the
+// deferred disparity map a FIRST == 1 block reads and writes out, or nullptr.
+static void ref_dws_launch(decltype(&k_ref_dws<0>) kernel, const RefDws &l, const float *in, const float *wfrag, float *out, int B,
+                           int H, int W, hipStream_t st, float ioff, const StageMap *def = nullptr)
 {
     const RefGrid g = ref_grid(B, H, W, l.dil);
-    hipLaunchKernelGGL(k_ref_dws<FIRST>, g.grid, dim3(256), 0, st, in, wfrag, l.bn_s, l.bn_t, l.dw,
-                       reinterpret_cast<const float4 *>(l.pw), out, H, W, l.dil, g.nbx, g.nby, use_wt_stores((size_t)B * H * W * 128),
-                       plow, ph, pw, pmat, ioff);
+    hipLaunchKernelGGL(kernel, g.grid, dim3(256), 0, st, in, wfrag, l.bn_s, l.bn_t, l.dw, reinterpret_cast<const float4 *>(l.pw), out,
+                       H, W, l.dil, g.nbx, g.nby, use_wt_stores((size_t)B * H * W * 128), def ? def->low : nullptr, def ? def->h : 0,
+                       def ? def->w : 0, def ? def->mem : nullptr, ioff);
 }
 
 int launch_ref_dws(const RefDws &l, const float *in, float *out, int B, int H, int W, hipStream_t st)
 {
-    ref_dws_launch<0>(l, in, nullptr, out, B, H, W, st, 0.5f);
+    ref_dws_launch(k_ref_dws<0>, l, in, nullptr, out, B, H, W, st, 0.5f);
     LWS_LAUNCH_CHECK();
     return LWS_OK;
 }
@@ -941,12 +937,7 @@ int launch_ref_first_dws(const RefDws &l, StageMap &in, int cin, const float *wf
     if (rc) return rc;
     const bool def = !in.written;      // (the kernel writes a deferred map out: its tiles partition the image)
     const float *img = def ? in.prev->mem : in.mem;
-    if (cin == 3)
-        ref_dws_launch<3>(l, img, wfrag, out, B, H, W, st, ioff);
-    else if (def)
-        ref_dws_launch<1>(l, img, wfrag, out, B, H, W, st, ioff, in.low, in.h, in.w, in.mem);
-    else
-        ref_dws_launch<1>(l, img, wfrag, out, B, H, W, st, ioff);
+    ref_dws_launch(cin == 3 ? k_ref_dws<3> : k_ref_dws<1>, l, img, wfrag, out, B, H, W, st, ioff, def ? &in : nullptr);
     LWS_LAUNCH_CHECK();
     in.written = true;
     return LWS_OK;
@@ -956,20 +947,18 @@ int launch_ref_conv64(const RefConv64 &l, const float *inL, const float *inD, fl
                       hipStream_t st)
 {
     const int dil = 8, wt = use_wt_stores((size_t)B * H * W * 128);
-    const RefGrid g = ref_grid(B, H, W, dil, 8);      // both forms: 8-row tiles, 4 waves x 2 rows
+    using Cfg = Conv64Cfg;                        // both forms: 8-row tiles, 4 waves x 2 rows
+    const RefGrid g = ref_grid(B, H, W, dil);
     if (l.form == 1) {
         // split-bf16 form: 73 KB of LDS (2 workgroups per CU)
-        using Cfg = Conv64xCfg<8, 4>;
-        static std::atomic<uint64_t> attr_done{0};
-        const int rc_ = ensure_dyn_lds(attr_done, reinterpret_cast<const void *>(&k_ref_conv64x<8, 4>), Cfg::LDS_BYTES);
-        if (rc_ != LWS_OK) return rc_;
-        hipLaunchKernelGGL((k_ref_conv64x<8, 4>), g.grid, dim3(Cfg::NT), Cfg::LDS_BYTES, st, inL, inD, l.bn_s, l.bn_t,
+        if (const int rc = allow_dyn_lds<&k_ref_conv64x>(Cfg::LDS_BYTES)) return rc;
+        hipLaunchKernelGGL(k_ref_conv64x, g.grid, dim3(Cfg::NT), Cfg::LDS_BYTES, st, inL, inD, l.bn_s, l.bn_t,
                            reinterpret_cast<const uint4 *>(l.wx), out, H, W, dil, g.nbx, g.nby, wt);
     } else {
         // 46 KB LDS (3 workgroups per CU): 50.5 / 349 us at B = 1 / 8 (r01, 256x512; the floor is 31 / 246 us of fp32 MFMA
         // issue).  Measured and dropped: 4-row tiles x 4 waves 54.3 / 390 us, 4-row x 2 waves 66.2 / 403 us, 2-row x 1 wave
         // 53.8 / 408 us.
-        hipLaunchKernelGGL((k_ref_conv64<8, 4>), g.grid, dim3(64 * 4), 0, st, inL, inD, l.bn_s, l.bn_t,
+        hipLaunchKernelGGL(k_ref_conv64, g.grid, dim3(Cfg::NT), 0, st, inL, inD, l.bn_s, l.bn_t,
                            reinterpret_cast<const float4 *>(l.w), out, H, W, dil, g.nbx, g.nby, wt);
     }
     LWS_LAUNCH_CHECK();
