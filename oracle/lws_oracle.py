@@ -31,13 +31,18 @@ EPS = 1e-5
 #   scalar_div   "reciprocal": tensor / python_scalar is a scale op by fp32(1/c)
 #                "divide":     a true elementwise division
 VARIANT = {"align_mode": 0, "grid_unnorm": "cuda", "scalar_div": "reciprocal"}
+# One more switch that is no reading of Paddle's defaults, so VARIANT holds it only while `variant(split_bf16=mask)` is entered
+# (absent = 0: every convolution is one F.conv of the dtype).  A bit mask, the one of the HIP option of the same name, for float32
+# runs only (float64 ignores it): 1 = the 32 -> 32 Conv3D middle layers, 2 = the 8 -> 8 ones, 4 = refinement2.0.2 run by
+# `split_conv` -- the ARITHMETIC of the opt-in numerics mode (k_conv3d_mid16x, k_conv3d_mid8x, k_ref_conv64x), not its summation order
+SET_ONLY_WHILE_ENTERED = {"split_bf16"}
 
 
 class variant:
     """with variant(align_mode=1): ...  -- run the restatement under another reading of Paddle's defaults."""
 
     def __init__(self, **kw):
-        unknown = set(kw) - set(VARIANT)
+        unknown = set(kw) - set(VARIANT) - SET_ONLY_WHILE_ENTERED
         if unknown:
             raise KeyError(f"unknown oracle variant switch(es): {sorted(unknown)}")
         self.kw = kw
@@ -93,6 +98,36 @@ def grid_sample_bilinear(x, grid, unnorm="cuda"):
         tap = flat.gather(2, idx).reshape(out.shape)
         out = out + tap * (wgt * ok.to(x.dtype)).unsqueeze(1)
     return out
+
+
+def split_bf16x3(x):
+    """float32 x -> (hi, mid, lo), each a bf16 value held in float32, by round to nearest even: hi = bf16(x), mid = bf16(x - hi),
+    lo = bf16(x - hi - mid); every subtraction is exact and hi + mid + lo == x (split_bf16x3 of lws_device_math.h)."""
+    assert x.dtype == torch.float32, x.dtype
+    hi = x.to(torch.bfloat16).to(torch.float32)
+    r1 = x - hi
+    mid = r1.to(torch.bfloat16).to(torch.float32)
+    lo = (r1 - mid).to(torch.bfloat16).to(torch.float32)
+    return {"hi": hi, "mid": mid, "lo": lo}
+
+
+# weight part * input part, smallest first: the six cross terms of total order <= 2 that mfma_split_bf16_term sums (T = 0 .. 5)
+SPLIT_TERMS = (("lo", "hi"), ("hi", "lo"), ("mid", "mid"), ("mid", "hi"), ("hi", "mid"), ("hi", "hi"))
+
+
+def split_conv(x, w, conv):
+    """conv(x, w) on split-bf16 operands: input and weight as three bf16 values each, every term of SPLIT_TERMS one float32
+    convolution (its products are exact in float32), the terms summed in float32 in the order of the table."""
+    xs, ws = split_bf16x3(x), split_bf16x3(w)
+    acc = None
+    for wpart, xpart in SPLIT_TERMS:
+        term = conv(xs[xpart], ws[wpart])
+        acc = term if acc is None else acc + term
+    return acc
+
+
+def _split(bit, dtype):
+    return dtype == torch.float32 and (VARIANT.get("split_bf16", 0) & bit) != 0
 
 
 def _t(sd, key, dtype):
@@ -204,7 +239,12 @@ def post_3dconvs(cost5, sd, stage, dtype=torch.float32):
     while f"volume_postprocess.{stage}.{j}.2.weight" in sd:
         p = f"volume_postprocess.{stage}.{j}"
         y = F.relu(_bn(y, sd, p + ".0", dtype))
-        y = F.conv3d(y, _t(sd, p + ".2.weight", dtype), None, 1, 1)
+        wgt = _t(sd, p + ".2.weight", dtype)
+        c3 = wgt.shape[0]
+        if wgt.shape[1] == c3 and c3 in (32, 8) and _split(1 if c3 == 32 else 2, dtype):        # a C3 -> C3 middle layer
+            y = split_conv(y, wgt, lambda a, b: F.conv3d(a, b, None, 1, 1))
+        else:
+            y = F.conv3d(y, wgt, None, 1, 1)
         j += 1
     return y
 
@@ -268,7 +308,10 @@ def refinement1(x, sd, name, dtype=torch.float32):
 
 def refinement2(x, sd, dtype=torch.float32):
     x = F.relu(_bn(x, sd, "refinement2.0.0", dtype))
-    x = F.conv2d(x, _t(sd, "refinement2.0.2.weight", dtype), None, 1, 8, 8)
+    if _split(4, dtype):
+        x = split_conv(x, _t(sd, "refinement2.0.2.weight", dtype), lambda a, b: F.conv2d(a, b, None, 1, 8, 8))
+    else:
+        x = F.conv2d(x, _t(sd, "refinement2.0.2.weight", dtype), None, 1, 8, 8)
     for i, k in enumerate(reversed(range(4))):
         x = _dws_block(x, sd, f"refinement2.{i + 1}", 2 ** k, dtype)
     return F.conv2d(x, _t(sd, "refinement2.5.weight", dtype), None, 1, 1)

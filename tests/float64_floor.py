@@ -11,7 +11,9 @@ float32 run, never the code under test.
 
 Also here, because the CPU test, the GPU test and the tool share them: the seeded inputs and literal references of every per-op
 case (`case`, one per entry of `CASES`), the C restatement's runners (`C_RUNNERS`), and the distribution gates of the end-to-end
-stage maps (`assert_e2e_distribution`) on the committed tests/golden/ref_source_*.npz fixtures.  Plain numpy / torch-CPU."""
+stage maps (`assert_e2e_distribution`) on the committed tests/golden/ref_source_*.npz fixtures; and the cases of the split-bf16
+kernels (`SPLIT_CASES`: the same references, the same factors) with the CPU emulation of their arithmetic (`split_emulation`;
+tests/test_float64_floor_cpu.py part D, tools/noise_budget.py --split).  Plain numpy / torch-CPU."""
 import os
 from collections import namedtuple
 
@@ -167,6 +169,47 @@ CASES = {
     "align1_stage1": [(2, 63, 255)],        # ... under align mode 1: the one way to the HIP resize of that mode, which only a handle carries
 }
 FAMILY_SEED = {name: i + 1 for i, name in enumerate(CASES)}
+
+# The split-bf16 kernels (option "split_bf16": 1 = k_conv3d_mid16x, 2 = k_conv3d_mid8x, 4 = k_ref_conv64x), a dict of their own:
+# the C restatement has no split form, so nothing that iterates CASES may meet them.  family -> [(mask, params of `case`)]: the
+# references are those of the exact cases (the same Case object where the parameters coincide) -- the mode claims the float32
+# chain's accuracy, so its yardstick is the float32 chain's.
+#   mask 1, stage 0 (C3 = 32; the tile is 3 x 4 x 16): the seven stage-0 shapes of CASES["conv3d_stack"]
+#   mask 2, stages 1 and 2 (C3 = 8; the tile is 3 x 4 x 32 and the kernel runs from 256 tiles per sample), each shape under both
+#           stages' weights: 288 tiles with every extent one past a tile edge and an odd width; batch 2 at 396 tiles; exactly 256
+#           tiles; 240 tiles (stays on the exact kernel)
+#   mask 4: the six shapes of CASES["refine"]
+MID8X_SHAPES = ((1, 7, 45, 225), (2, 9, 41, 353), (1, 4, 64, 256), (1, 4, 60, 256))
+SPLIT_CASES = {
+    "conv3d_stack": ([(1, (0, shape, None, True)) for shape in ((1, 1, 1, 1), (2, 1, 5, 1), (1, 4, 9, 31), (2, 9, 30, 70), (1, 24, 8, 32),
+                                                               (1, 32, 9, 48), (1, 9, 17, 33))]
+                     + [(2, (stage, shape, None, True)) for stage in (1, 2) for shape in MID8X_SHAPES]),
+    "refine": [(4, params) for params in CASES["refine"]],
+}
+# the shapes whose map exceeds the contraction's footprint and that run a split kernel: there the GPU tests assert that the
+# result differs in bits from the exact kernel's ...
+SPLIT_LARGE = {
+    "conv3d_stack": [(2, 9, 30, 70), (1, 24, 8, 32), (1, 32, 9, 48), (1, 9, 17, 33), (1, 7, 45, 225), (2, 9, 41, 353), (1, 4, 64, 256)],
+    "refine": [(1, 33, 47), (1, 63, 255)],
+}
+# ... and the cases on which a restatement that loses one 2^-16-order cross term leaves the floor (tests/test_float64_floor_cpu.py part D
+# asserts it): those shapes, the 8 -> 8 ones under stage 2's weights only (under stage 1's the float32 floor is 1e-7 of the scale
+# and `tiny` is most of the gate: see test_five_terms_leave_the_floor)
+SPLIT_TEETH = {
+    "conv3d_stack": [(0, shape, None, True) for shape in SPLIT_LARGE["conv3d_stack"][:4]]
+                    + [(2, shape, None, True) for shape in SPLIT_LARGE["conv3d_stack"][4:]],
+    "refine": list(SPLIT_LARGE["refine"]),
+}
+MID8X_MIN_TILES = 256        # launch_conv3d_mid (lws_conv3d.hip): k_conv3d_mid8x from this many 3 x 4 x 32 tiles per SAMPLE
+
+
+def mid8x_tiles(shape):
+    _, D, h, w = shape
+    return -(-w // 32) * -(-h // 4) * -(-D // 3)
+
+
+def split_id(family, mask, params):
+    return f"mask{mask}-{case_id(family, params)}"
 
 
 def case_id(family, params):
@@ -384,6 +427,49 @@ def format_row(c, label, r):
     def v(x):
         return "   -" if x is None else f"{x:4.2f}"
     return f"{c.family:19s} {c.id:28s} {label:18s} max {v(r.max)} mean {v(r.mean)} | ring max {v(r.ring_max)} mean {v(r.ring_mean)}"
+
+
+# ------------------------------------------------------------------------------------------------
+# the split-bf16 arithmetic, restated (oracle.lws_oracle.split_conv behind VARIANT["split_bf16"]); leaving a term out is test-side
+# ------------------------------------------------------------------------------------------------
+class split_terms_without:
+    """with split_terms_without("mid*mid"): ... -- the restatement's split convolutions sum five terms, the named one ("weight
+    part*input part") left out: the planted defect of the teeth checks.  None leaves the six."""
+
+    def __init__(self, term):
+        self.term = None if term is None else tuple(term.split("*"))
+
+    def __enter__(self):
+        from oracle import lws_oracle as O
+        self.saved = O.SPLIT_TERMS
+        if self.term is not None:
+            assert self.term in O.SPLIT_TERMS, self.term
+            O.SPLIT_TERMS = tuple(t for t in O.SPLIT_TERMS if t != self.term)
+        return self
+
+    def __exit__(self, *a):
+        from oracle import lws_oracle as O
+        O.SPLIT_TERMS = self.saved
+
+
+ORDER2_TERMS = ("lo*hi", "hi*lo", "mid*mid")          # weight part * input part: the three cross terms of order 2^-16
+
+
+def split_emulation(c, mask, without=None):
+    """The outputs of case `c` from the literal restatement in float32 with its split convolutions on (`mask`), as `check` takes
+    them; `without`: one term of ORDER2_TERMS left out."""
+    from oracle import lws_oracle as O
+
+    def T(a):
+        return torch.as_tensor(np.asarray(a), dtype=torch.float32)
+
+    _, sd = state_dict(*c.params[2:4]) if c.family == "conv3d_stack" else state_dict()
+    with torch.no_grad(), O.variant(split_bf16=mask), split_terms_without(without):
+        if c.family == "conv3d_stack":
+            cost = T(c.inputs["cost"])[:, None]
+            return {"cost_out": (O.post_3dconvs(cost, sd, c.params[0], torch.float32) + cost)[:, 0].numpy()}
+        assert c.family == "refine", c.family
+        return {"pred4": O.refine(T(c.inputs["left"]), T(c.inputs["pred3"]), sd, torch.float32).numpy()}
 
 
 # ------------------------------------------------------------------------------------------------

@@ -7,7 +7,12 @@ that shape.  References are computed once per case and shared (FF.case); never m
 Two things the per-op entry points cannot be given, both by their own contract: lws_volume_l1_shift rejects a map narrower than
 the number of hypotheses (the (2, 8, 4, 3), D = 5 case: the rejection is asserted instead), and lws_volume_l1_warp /
 lws_upsample_add carry no handle and so resize under align mode 0 only -- align mode 1 is reached through a model built with
-interp_align_mode = 1: stage 1 of lws_disparity_stages per op (`align1_stage1`), the warps in the end-to-end gates below."""
+interp_align_mode = 1: stage 1 of lws_disparity_stages per op (`align1_stage1`), the warps in the end-to-end gates below.
+
+The split-bf16 kernels (option "split_bf16": k_conv3d_mid16x, k_conv3d_mid8x, k_ref_conv64x) are NOT the C restatement's bits, so
+here the tolerance does all the work: FF.SPLIT_CASES under the same gate with the same factors (the mode claims the float32
+chain's accuracy, so it gets the float32 chain's gate), what tests/test_float64_floor_cpu.py (part D) shows a kernel that loses one of its
+2^-16-order terms would miss; then the bits across batch sizes, calls and refinement chunks, and the end-to-end distributions."""
 import numpy as np
 import pytest
 
@@ -147,12 +152,115 @@ def test_stage1_through_a_configured_model(dev, hip_lib, family):
     FF.check(c, {"pred1": host(ops.disparity_stages(m._h, fl, fr, c.meta["H"], c.meta["W"])[0])}, show=print)
 
 
+# ------------------------------------------------------------------ per op, split-bf16
+def split_ids(family, keep=lambda mask, p: True):
+    cases = [(mask, p) for mask, p in FF.SPLIT_CASES[family] if keep(mask, p)]
+    return pytest.mark.parametrize("mask,params", cases, ids=[FF.split_id(family, mask, p) for mask, p in cases])
+
+
+def with_split(m, mask, fn):
+    """fn() under option split_bf16 = mask, the option restored whatever happens."""
+    m.set_option("split_bf16", mask)
+    try:
+        return fn()
+    finally:
+        m.set_option("split_bf16", 0)
+
+
+@split_ids("conv3d_stack")
+def test_conv3d_stack_split(dev, hip_lib, mask, params):
+    """k_conv3d_mid16x (mask 1, stage 0) and k_conv3d_mid8x (mask 2, stages 1 and 2, from 256 tiles per sample) on the float32
+    floor at FF.MAX_FACTOR / FF.MEAN_FACTOR, whole tensor and ring; on the large maps the bits differ from the exact kernel's (the
+    split kernel really ran); the 240-tile sample stays on the exact kernel (the C restatement's bits with the option on); the
+    exact form comes back bit for bit."""
+    from lwsnet_amd import ops
+    from oracle import c_oracle as C
+    stage, shape, _, _ = params
+    c = FF.case("conv3d_stack", params)
+    m, x = model(dev), cu(c.inputs["cost"], dev)
+    assert m.get_option("split_bf16") == 0
+    exact = host(ops.conv3d_stack(m._h, stage, x))
+    got = with_split(m, mask, lambda: host(ops.conv3d_stack(m._h, stage, x)))
+    after = host(ops.conv3d_stack(m._h, stage, x))
+    FF.check(c, {"cost_out": got}, show=print)
+    assert np.array_equal(after.view(np.uint32), exact.view(np.uint32)), "the exact form did not come back"
+    runs_split = mask == 1 or FF.mid8x_tiles(shape) >= FF.MID8X_MIN_TILES
+    if not runs_split:
+        assert np.array_equal(got.view(np.uint32), C.conv3d_stack(c.inputs["cost"], FF.state_dict()[1], stage).view(np.uint32))
+    elif shape in FF.SPLIT_LARGE["conv3d_stack"]:
+        assert not np.array_equal(got, exact), "the option did not select the split kernel"
+
+
+@split_ids("refine")
+def test_refine_split(dev, hip_lib, mask, params):
+    """k_ref_conv64x (mask 4) on the float32 floor at FF.MAX_FACTOR / FF.MEAN_FACTOR: whole tensor, ring, and both again with the
+    150-px carrier removed; on the maps larger than the dilation-8 footprint the bits differ from the exact kernel's; the exact
+    form comes back bit for bit."""
+    from lwsnet_amd import ops
+    c = FF.case("refine", params)
+    m, left, pred3 = model(dev), cu(c.inputs["left"], dev), cu(c.inputs["pred3"], dev)
+    assert m.get_option("split_bf16") == 0
+    exact = host(ops.refine(m._h, left, pred3))
+    got = with_split(m, mask, lambda: host(ops.refine(m._h, left, pred3)))
+    after = host(ops.refine(m._h, left, pred3))
+    FF.check(c, {"pred4": got}, show=print)
+    assert np.array_equal(after.view(np.uint32), exact.view(np.uint32)), "the exact form did not come back"
+    if params in FF.SPLIT_LARGE["refine"]:
+        assert not np.array_equal(got, exact), "the option did not select the split kernel"
+
+
+@pytest.mark.parametrize("family,mask,params", [("conv3d_stack", 1, (0, (2, 9, 30, 70), None, True)), ("conv3d_stack", 2, (1, (2, 9, 41, 353), None, True)),
+                                                ("conv3d_stack", 2, (2, (2, 9, 41, 353), None, True)), ("refine", 4, (3, 5, 70)), ("refine", 4, (2, 17, 15)),
+                                                ("refine", 4, (2, 63, 65))],
+                         ids=lambda v: FF.case_id("", v) if isinstance(v, tuple) else str(v))
+def test_split_bits_do_not_depend_on_the_batch_the_call_or_the_chunk(dev, hip_lib, family, mask, params):
+    """In split mode too (launch_conv3d_mid's comment: the one mode whose candidate kernels differ in bits): sample b of a batch is
+    the bits of the same sample run alone, a second call repeats the first, and the refinement under ref_chunk_mb = 1 is the
+    refinement under 72 -- (2,63,65) is there for that: its [H,W,32] map is 0.52 MB a pair, so 1 MB really makes chunks of one pair
+    (the two small maps fit one chunk either way)."""
+    from lwsnet_amd import ops
+    c = FF.case(family, params)
+    m = model(dev)
+    names = ["cost"] if family == "conv3d_stack" else ["left", "pred3"]
+
+    def run(sel=slice(None)):
+        args = [cu(c.inputs[n][sel], dev) for n in names]
+        return host(ops.conv3d_stack(m._h, params[0], *args) if family == "conv3d_stack" else ops.refine(m._h, *args))
+
+    def all_of_it():
+        whole = run()
+        out = {"whole": whole, "again": run(), "alone": [run(slice(b, b + 1)) for b in range(whole.shape[0])]}
+        if family == "refine":
+            m.set_option("ref_chunk_mb", 1)
+            try:
+                out["chunked"] = run()
+            finally:
+                m.set_option("ref_chunk_mb", 72)
+        return out
+
+    exact = run()
+    out = with_split(m, mask, all_of_it)
+    whole = out["whole"].view(np.uint32)
+    assert np.array_equal(out["again"].view(np.uint32), whole), "a second call gave other bits"
+    for b, alone in enumerate(out["alone"]):
+        assert np.array_equal(alone.view(np.uint32), whole[b:b + 1]), f"sample {b} alone differs from sample {b} of the batch"
+    if family == "refine":
+        assert np.array_equal(out["chunked"].view(np.uint32), whole), "ref_chunk_mb = 1 differs from 72"
+    else:
+        assert not np.array_equal(out["whole"], exact), "the option did not select the split kernel"
+
+
 # ------------------------------------------------------------------ end to end
-def forward(dev, name):
+def forward(dev, name, split_bf16=(0,)):
+    """The fixture and the stage maps of one model's forward (under each mask of option split_bf16, if more than the default)."""
     from lwsnet_amd.models import LWSNet
     g, args, sd, _ = FF.ref_source_case(name)               # args carries the fixture's align mode
-    pred = LWSNet(args, device=dev).set_state_dict(sd).eval()(g["left"], g["right"])
-    return g, [host(p) for p in pred]
+    m = LWSNet(args, device=dev).set_state_dict(sd).eval()
+    preds = []
+    for mask in split_bf16:
+        m.set_option("split_bf16", mask)
+        preds.append([host(p) for p in m(g["left"], g["right"])])
+    return (g, *preds)
 
 
 def show_e2e(name, s, st):
@@ -175,3 +283,16 @@ def test_e2e_medians_on_the_chaotic_fixtures(dev, hip_lib, name):
     g, pred = forward(dev, name)
     for s in range(4):
         show_e2e(name, s, FF.assert_e2e_distribution(pred[s], g[f"pred{s}"], g[f"pred64_{s}"], f"{name} stage {s + 1}", **FF.E2E_CHAOTIC_GATES))
+
+
+@pytest.mark.parametrize("name", FF.E2E_SMOOTH)
+def test_e2e_distributions_split(dev, hip_lib, name):
+    """The smooth fixtures through a model with split_bf16 = 7 under the gates of the exact build (FF.E2E_SMOOTH_GATES: mean 1.3,
+    median 1.35, bias 0.3 x the reference's own float32).  At these sizes bits 1 and 4 are live (stage 3 has 96 tiles per sample:
+    its 8 -> 8 layers stay exact), so stage 4 is not the exact build's bits.  The bias gate is the one that would catch a device
+    split that truncates where it should round to nearest: every operand then errs to the same side."""
+    g, exact, pred = forward(dev, name, split_bf16=(0, 7))
+    for s in range(4):
+        show_e2e(name + " split", s, FF.assert_e2e_distribution(pred[s], g[f"pred{s}"], g[f"pred64_{s}"], f"{name} split_bf16 = 7 stage {s + 1}",
+                                                               **FF.E2E_SMOOTH_GATES))
+    assert not np.array_equal(pred[3], exact[3]), "split_bf16 = 7 gave the exact build's stage 4"

@@ -745,7 +745,8 @@ def test_split_bf16_forward_on_the_float32_noise_floor(dev, hip_lib):
     float64), so it is asserted on aggregates over six pairs (five seeded smooth pairs and the white-noise pair) against
     the float64 literal oracle, for each option alone and for all three: per stage, mean |split - fp64| <= 1.15 x mean |exact -
     fp64| and max <= 1.5 x max (+1e-4 px).  Measured r03 (tools/split_bf16_numerics.py, 8 pairs, mid16_form): means
-    3.16e-5 / 8.64e-5 / 2.82e-4 / 3.46e-4 px against the exact build's 3.14e-5 / 8.84e-5 / 2.97e-4 / 3.63e-4 at 64x256."""
+    3.16e-5 / 8.64e-5 / 2.82e-4 / 3.46e-4 px against the exact build's 3.14e-5 / 8.84e-5 / 2.97e-4 / 3.63e-4 at 64x256.
+    The per-op gate of these kernels, with a ring gate and ragged shapes: tests/test_gpu_float64_floor.py::test_*_split."""
     from lwsnet_amd.models import LWSNet
     from lwsnet_amd.synth import make_noise_pair, make_pair
     from oracle import lws_oracle
@@ -787,7 +788,8 @@ def test_split_bf16_forward_on_the_float32_noise_floor(dev, hip_lib):
 def test_split_bf16_refine_close_to_the_exact_chain(dev, model, B, H, W):
     """lws_refine with split_bf16 = 4 (k_ref_conv64x) against the C oracle's exact chain: the refined map moves by
     float32 rounding noise only (a 576-term contraction, then four depthwise-separable blocks and the last convolution),
-    including ragged tiles and image borders of the dilation-8 phase grid; the exact form comes back bit for bit."""
+    including ragged tiles and image borders of the dilation-8 phase grid; the exact form comes back bit for bit.
+    The tight gate (this one lets a kernel without a 2^-16-order term through): tests/test_gpu_float64_floor.py::test_refine_split."""
     from lwsnet_amd import ops
     from oracle import c_oracle as C
     rng = np.random.default_rng(9)
@@ -814,7 +816,8 @@ def test_split_bf16_stack_close_to_the_exact_chain(dev, model, stage, option, va
     """lws_conv3d_stack with the split-bf16 middle layers (stage 1: k_conv3d_mid16x, C3 = 32; stages 2-3: k_conv3d_mid8x,
     C3 = 8) against the C oracle's exact chain: float32-level agreement (six layers deep; tools/micro/split_bf16.hip measures
     3.2e-6 vs 2.7e-6 from float64 for one layer at output scale 4.7), on ragged shapes too (tile edges in x, y and d, odd
-    widths for the parity rows); the exact form comes back bit for bit."""
+    widths for the parity rows); the exact form comes back bit for bit.
+    The tight gate (this one lets a kernel without a 2^-16-order term through): tests/test_gpu_float64_floor.py::test_conv3d_stack_split."""
     from lwsnet_amd import ops
     from oracle import c_oracle as C
     default = model.get_option(option)

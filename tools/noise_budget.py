@@ -7,6 +7,8 @@ reference algorithm's own noise floor.  Usage: python tools/noise_budget.py [--s
 --per-op: instead, every per-op case of tests/float64_floor.py through the C restatement (oracle/lws_oracle.c, whose bits are the
 HIP kernels' bits) against the literal oracle in float32 and float64, one line of ratios per gate and the worst per op: the
 per-op table of DESIGN.md section 2.  --e2e: the end-to-end table beside it, from the committed tests/golden/ref_source_*.npz.
+--split: the split-bf16 arithmetic restated on the CPU (oracle.lws_oracle.split_conv) on FF.SPLIT_CASES, six terms and each of
+the three five-term forms: the emulation's lines of the same section (tests/test_float64_floor_cpu.py, part D, asserts them).
 """
 import argparse
 import os
@@ -77,6 +79,29 @@ def per_op():
         print(f"{family:19s} {r.max:5.2f} {r.mean:5.2f} {r.ring_max:9.2f} {r.ring_mean:10.2f}")
 
 
+def split():
+    """Ratios to the float32 floor of the six-term restatement and of the three five-term forms (ungated here), per split case."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import float64_floor as FF
+    inf = float("inf")
+    six, five = [], []
+    for family, cases in FF.SPLIT_CASES.items():
+        for mask, params in cases:
+            c = FF.case(family, params)
+            six += [(family, label, r) for label, r in FF.check(c, FF.split_emulation(c, mask), show=lambda line: print("six terms       " + line, flush=True))]
+            for term in FF.ORDER2_TERMS:
+                rows = FF.check(c, FF.split_emulation(c, mask, term), max_factor=inf, mean_factor=inf,
+                                show=lambda line: print(f"without {term:8s}" + line, flush=True))
+                if params in FF.SPLIT_TEETH[family]:
+                    five += [(family, label, r) for label, r in rows]
+    print(f"\n{'CPU emulation':32s} {'max':>5s} {'mean':>5s} {'ring max':>9s} {'ring mean':>10s}   (gates: {FF.MAX_FACTOR} / {FF.MEAN_FACTOR})")
+    for family, r in FF.worst_per_family(six).items():
+        print(f"{family + ', six terms, worst':32s} {r.max:5.2f} {r.mean:5.2f} {r.ring_max:9.2f} {r.ring_mean:10.2f}")
+    for family in FF.SPLIT_TEETH:
+        cols = [min(v for v in col if v is not None) for col in zip(*[r for f, _, r in five if f == family])]
+        print(f"{family + ', five terms, smallest':32s} {cols[0]:5.2f} {cols[1]:5.2f} {cols[2]:9.2f} {cols[3]:10.2f}   (the cases of FF.SPLIT_TEETH)")
+
+
 def e2e():
     """The distribution statistics of the C restatement's stage maps on the six reference-source fixtures."""
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -100,11 +125,14 @@ def main():
     ap.add_argument("--threads", type=int, default=8)
     ap.add_argument("--per-op", action="store_true", help="the per-op ratio table of the C restatement (tests/float64_floor.py)")
     ap.add_argument("--e2e", action="store_true", help="the end-to-end distribution table of the C restatement")
+    ap.add_argument("--split", action="store_true", help="the split-bf16 emulation's ratio table (tests/float64_floor.py SPLIT_CASES)")
     a = ap.parse_args()
     torch.set_num_threads(a.threads)
-    if a.per_op or a.e2e:
+    if a.per_op or a.e2e or a.split:
         if a.per_op:
             per_op()
+        if a.split:
+            split()
         if a.e2e:
             e2e()
         return
