@@ -103,6 +103,40 @@ class GroundPlane:
                    float(np.degrees(np.arctan2(n[0], n[1]))), tuple(float(v) for v in n))
 
 
+def read_kitti_poses(path):
+    """The poses of a KITTI odometry `poses.txt`: float64 (N,3,4), line i the row-major [R|t] that maps a point of the left camera's
+    frame at time i into the world (camera-to-world).  Every line holds 12 numbers; empty lines are skipped."""
+    rows = []
+    with open(path, encoding="utf-8") as f:
+        for n, line in enumerate(f, 1):
+            if not line.strip():
+                continue
+            try:
+                v = [float(t) for t in line.split()]
+            except ValueError:
+                raise ValueError(f"{path}:{n}: not a line of numbers") from None
+            if len(v) != 12 or not np.isfinite(v).all():
+                raise ValueError(f"{path}:{n}: a pose is 12 finite numbers (a row-major 3x4 [R|t]), got {len(v)}")
+            rows.append(v)
+    return np.asarray(rows, np.float64).reshape(-1, 3, 4)
+
+
+def _pose44(T, name):
+    T = np.asarray(T, np.float64)
+    if T.shape != (3, 4) or not np.isfinite(T).all():
+        raise ValueError(f"{name} must be a finite 3x4 [R|t], got shape {T.shape}")
+    return np.vstack([T, [0.0, 0.0, 0.0, 1.0]])
+
+
+def relative_pose(T_prev, T_cur):
+    """The `pose` rows of lwsnet_amd.ops.temporal_step for one image, float32 [2][12]: inv(T_cur) . T_prev, which maps a point of
+    the previous camera's frame into the current one, and its inverse inv(T_prev) . T_cur, both from camera-to-world 3x4 poses
+    (read_kitti_poses) and computed in float64."""
+    a, b = _pose44(T_prev, "T_prev"), _pose44(T_cur, "T_cur")
+    fwd, back = np.linalg.solve(b, a), np.linalg.solve(a, b)
+    return np.stack([fwd[:3].reshape(12), back[:3].reshape(12)]).astype(np.float32)
+
+
 def _read_kitti_values(path):
     """key -> list of floats for every `key: v v v` line of a KITTI calibration file (lines without numbers are skipped)."""
     mats = {}

@@ -99,6 +99,16 @@ Only the pixels the chain's codes keep are scored, under the rule of the geometr
 filled); with `--rectify` the left valid map merges into those codes as it does for the geometry files, and a right tap outside the
 right valid map cannot be used.  `--save_photo` writes two files beside each colour file: `<stem>_pe.png`, the error map as 8-bit
 grey rint(pe * 255) (0 where the pixel is not scored), and `<stem>_warp.png`, the warped right image.
+
+`--temporal --poses PATH [--temporal_gate G] [--temporal_q Q] [--temporal_sigma S|net] [--temporal_hold] [--save_temporal]`: directory
+mode only; the frames are a sequence in sorted order and line i of PATH (a KITTI odometry `poses.txt`: 12 numbers, camera-to-world) is
+the pose of pair i; fewer lines than pairs is an error.  The stage-4 map of each frame goes through lwsnet_amd.temporal.TemporalFilter
+(lws_temporal_step) behind the post-processing chain, with the chain's `keep` codes as the filter's mask, so `--temporal_hold` fills
+what the checks dropped with what earlier frames saw; the fused map is what the colour file and every geometry or ground step
+receive.  The measurement's sigma is the constant S px (default 0.5) or, with `net`, LWSNet.forward_conf's stage-3 sigma.  One log
+line per frame gives the pixels per code (nothing, new, fused, reset, held).  `--save_temporal` writes `<stem>_tcode.png`, the codes
+through a fixed five-colour table, and `<stem>_tsigma.png`, sqrt of the fused variance scaled as `--save_conf`'s sigma image.  Needs a
+camera; the poses are taken as the left camera's.
 """
 import argparse
 import contextlib
@@ -145,6 +155,7 @@ def build_parser():
     add_rectify_arguments(p)
     add_conf_arguments(p)
     post.add_photometric_arguments(p, save=True)
+    add_temporal_arguments(p)
     return p
 
 
@@ -189,6 +200,70 @@ def check_conf_arguments(p, args):
     post.sequential_only(p, args, flags, "run")
     if (args.conf_min is not None or args.sigma_max_keep is not None) and not _geometry_requested(args):
         p.error("--conf_min and --sigma_max_keep mask --save_disp16 / --save_depth / --save_ply / --save_normals / --save_mesh: give one of them")
+
+
+def add_temporal_arguments(p):
+    """--temporal and its flags (not in the reference): lwsnet_amd.temporal.TemporalFilter behind the chain.  A command line without
+    them parses to the namespace it parsed to before they existed (argparse.SUPPRESS); check_temporal_arguments writes their defaults."""
+    S = argparse.SUPPRESS
+    p.add_argument("--temporal", action="store_true", default=S,
+                   help="fuse the stage-4 maps of the sequence over time with the poses of --poses (directory mode, sequential only; "
+                        "needs a camera; not in the reference)")
+    p.add_argument("--poses", type=str, default=S, metavar="PATH",
+                   help="with --temporal: a KITTI odometry poses.txt, 12 numbers per line (camera-to-world), line i for the i-th pair in sorted order")
+    p.add_argument("--temporal_gate", type=float, default=S, metavar="G", help="temporal: the gate in standard deviations (default 3)")
+    p.add_argument("--temporal_q", type=float, default=S, metavar="Q", help="temporal: process noise in px^2 per frame (default 0)")
+    p.add_argument("--temporal_sigma", type=str, default=S, metavar="S|net",
+                   help="temporal: the measurement's sigma in px (default 0.5), or `net` for the network's own stage-3 sigma")
+    p.add_argument("--temporal_hold", action="store_true", default=S,
+                   help="temporal: a pixel the checks dropped holds what was seen there in earlier frames")
+    p.add_argument("--save_temporal", action="store_true", default=S,
+                   help="--temporal, and write <stem>_tcode.png (the codes in colour) and <stem>_tsigma.png (the fused sigma, scaled as --save_conf's)")
+
+
+TEMPORAL_DEFAULTS = dict(temporal=False, poses=None, temporal_gate=3.0, temporal_q=0.0, temporal_sigma="0.5", temporal_hold=False,
+                         save_temporal=False)
+
+
+def temporal_sigma(args):
+    """--temporal_sigma as (the scalar sigma0 in px, or None for the network's stage-3 sigma)."""
+    return None if args.temporal_sigma == "net" else float(args.temporal_sigma)
+
+
+def check_temporal_arguments(p, args):
+    """Rejects what the temporal filter does not support, before any model or GPU work; reads the poses file; sets the defaults."""
+    from .geometry import read_kitti_poses
+    given = [f for f in ("temporal_gate", "temporal_q", "temporal_sigma", "temporal_hold") if getattr(args, f, None) not in (None, False)]
+    post.set_defaults(args, **TEMPORAL_DEFAULTS)
+    args.temporal = args.temporal or args.save_temporal
+    if not args.temporal:
+        if given or args.poses is not None:
+            p.error("--poses, --temporal_gate, --temporal_q, --temporal_sigma and --temporal_hold need --temporal")
+        return
+    if args.poses is None:
+        p.error("--temporal needs --poses PATH, the camera-to-world pose of every pair")
+    _needs_camera(p, args, "--temporal and --save_temporal")
+    post.sequential_only(p, args, "--temporal / --save_temporal", "run")
+    if args.left_img:
+        p.error("--temporal fuses a sequence: use directory mode (--img_path), not --left_img")
+    try:
+        if temporal_sigma(args) is not None and not (np.isfinite(temporal_sigma(args)) and temporal_sigma(args) >= 0):
+            raise ValueError
+    except ValueError:
+        p.error(f"--temporal_sigma must be a finite number of pixels >= 0 or `net`, got {args.temporal_sigma}")
+    if temporal_sigma(args) is None and (args.lr_check is not None or getattr(args, "occ_check", None) is not None):
+        p.error("--temporal_sigma net uses the network's own sigma and does not combine with --lr_check or --occ_check")
+    if not (np.isfinite(args.temporal_gate) and args.temporal_gate > 0):
+        p.error(f"--temporal_gate must be finite and > 0, got {args.temporal_gate}")
+    if not (np.isfinite(args.temporal_q) and args.temporal_q >= 0):
+        p.error(f"--temporal_q must be finite and >= 0, got {args.temporal_q}")
+    try:
+        n = len(read_kitti_poses(args.poses))
+    except (OSError, ValueError) as e:
+        p.error(f"--poses: cannot read {args.poses}: {e}")
+    pairs = len(_list_pairs(args)[0])
+    if n < pairs:
+        p.error(f"--poses: {args.poses} holds {n} poses for {pairs} pairs (line i belongs to the i-th pair in sorted order)")
 
 
 class _ConfModel:
@@ -536,12 +611,14 @@ def inference(model, left_imgs, right_imgs, args, log):
     """inference.py:78-138."""
     import torch
     default_arguments(args)
+    post.set_defaults(args, **TEMPORAL_DEFAULTS)            # (check_temporal_arguments' defaults, for a namespace that skipped it)
     written, warm = [], False
     opts = post.Options.from_args(args)
-    geo = _geometry_requested(args)
-    conf_on = conf_requested(args)
+    geo = _geometry_requested(args) or args.temporal
+    conf_on = conf_requested(args) or (args.temporal and temporal_sigma(args) is None)
     chain_model = _ConfModel(model) if conf_on else model
-    for li, ri in zip(left_imgs, right_imgs):
+    sequence = _Sequence(args) if args.temporal else None
+    for index, (li, ri) in enumerate(zip(left_imgs, right_imgs)):
         frame = _load_frame(args, li, ri, model.device, geo, log)
         if frame is None:
             continue
@@ -562,6 +639,7 @@ def inference(model, left_imgs, right_imgs, args, log):
                 log.info("Weighted median (radius {}, sigma {:g}, fill {}): stage {} changed = {}, filled = {}".format(
                     opts.wmedian, opts.wmedian_sigma, opts.wmedian_fill, stage + 1, changed, refilled))
         conf = chain_model.last if conf_on else None
+        fused, res = sequence.step(index, frame, res, conf, log) if sequence else (None, res)
         photo = out.photometric(frame, res, args, log) if args.photometric else None
         for stage in range(4):
             disp = res.disp[stage].squeeze(axis=[0, 1]).numpy()         # :114 (the uint8 cast is inside disparity_to_color)
@@ -569,8 +647,41 @@ def inference(model, left_imgs, right_imgs, args, log):
             if args.left_img:                                           # :117-122
                 written += out.write_stage(os.path.join(os.path.dirname(args.left_img), str(stage + 1) + ".png"), color, ss, frame, stage, args, log, res, conf, photo)
         if not args.left_img:                                           # :133-137 (stage-4 map only)
-            written += out.write_stage(os.path.join(args.save_path, os.path.basename(frame.path)), color, ss, frame, 3, args, log, res, conf, photo)
+            written += out.write_stage(os.path.join(args.save_path, os.path.basename(frame.path)), color, ss, frame, 3, args, log, res, conf, photo, fused)
     return written
+
+
+class _Sequence:
+    """--temporal: the filter of the run and the poses of its frames.  step() fuses one frame's stage-4 map behind the chain -- the
+    chain's `keep` codes are the filter's mask, so --temporal_hold fills what the checks dropped -- and puts the fused map in the
+    chain's place: every later writer and geometry step receives the ChainResult step() returns, whose stage-4 map is the fused one
+    and whose stage-4 `keep` (where the chain handed one on) is 1 where the filter left a value.  A frame that was skipped is
+    bridged: the pose is the one between the two frames fused."""
+
+    def __init__(self, args):
+        from .geometry import read_kitti_poses
+        self.args, self.poses, self.filter, self.last = args, read_kitti_poses(args.poses), None, None
+
+    def step(self, index, frame, res, conf, log):
+        import torch
+        from .geometry import relative_pose
+        from .models import DisparityTensor
+        from .temporal import TemporalFilter
+        a = self.args
+        sigma0 = temporal_sigma(a)
+        if self.filter is None:
+            self.filter = TemporalFilter(frame.cam, gate=a.temporal_gate, q=a.temporal_q, sigma0=0.5 if sigma0 is None else sigma0,
+                                         hold=a.temporal_hold, min_disp=a.min_disp)
+        disp = res.disp[3].as_subclass(torch.Tensor)
+        pose = None if self.last is None else relative_pose(self.poses[self.last], self.poses[index])
+        with torch.cuda.device(disp.device):
+            out_ = self.filter.step(disp, pose, sigma=conf.sigma[2] if sigma0 is None else None, mask=res.keep[3] if res.keep is not None else None)
+        self.last = index
+        log.info("Temporal: " + ", ".join("{} = {}".format(n, c) for n, c in zip(out.TEMPORAL_CODES, out_.counts[0].cpu().tolist())))
+        disps = list(res.disp[:3]) + [DisparityTensor.wrap(out_.disp)]
+        keep = None if res.keep is None else list(res.keep[:3]) + [(out_.code != 0).to(torch.uint8)]
+        return out_, post.ChainResult(disps, res.lr_masks, res.speckle_masks, keep, res.lr_density, res.speckle_counts, res.wmedian_counts,
+                                      res.occ_masks, res.occ_density)
 
 
 def _load_frame(args, left_path, right_path, device, geo, log):
@@ -633,6 +744,7 @@ def main(argv=None):
     check_rectify_arguments(parser, args)
     check_conf_arguments(parser, args)
     post.check_photometric_arguments(parser, args, save=True)
+    check_temporal_arguments(parser, args)
     log = start_logging("lwsnet_amd.inference", args)
     model = load_model(args, log)
     if getattr(args, "split_bf16", False):

@@ -804,6 +804,82 @@ def objects(disp, cameras, codes, udisp, min_disp=1.0, max_depth=float("inf"), c
     return ObjectResult(rows, vals, lab, info)
 
 
+TemporalResult = namedtuple("TemporalResult", ["disp", "var", "age", "code", "counts"])
+TemporalResult.__doc__ = """What temporal_step returns: the new state -- disp float32 [B,1,H,W] the fused disparity, var float32 its variance
+in px^2, age uint16 the frames fused (0: no state) --, code uint8 [B,1,H,W] (0 nothing, 1 new, 2 fused, 3 reset by the gate, 4 held)
+and counts, an int64 [B,5] device tensor of the pixels per code (None unless asked for)."""
+
+
+def _temporal_args(sigma0, min_disp, sigma_min, gate, q, max_jump, hold, q_hold, max_var):
+    """The validated scalar arguments of temporal_step, in the order of the C call."""
+    if not (max_jump >= 0):
+        raise ValueError(f"max_jump must be >= 0 (inf allowed), got {max_jump}")
+    if not (max_var > 0):
+        raise ValueError(f"max_var must be > 0 (inf allowed), got {max_var}")
+    if isinstance(hold, float) or hold not in (0, 1):
+        raise ValueError(f"hold must be False or True, got {hold}")
+    return (_finite_nonneg("sigma0", sigma0), _finite_pos("min_disp", min_disp), _finite_pos("sigma_min", sigma_min), _finite_pos("gate", gate),
+            _finite_nonneg("q", q), float(max_jump), int(hold), _finite_nonneg("q_hold", q_hold), float(max_var))
+
+
+def temporal_pose_rows(pose, B):
+    """pose as the float32 [B,2,12] rows of lws_temporal_step: one [2][12] (lwsnet_amd.geometry.relative_pose) for every image, or
+    B of them."""
+    import numpy as np
+    p = np.asarray(pose.detach().cpu().numpy() if isinstance(pose, torch.Tensor) else pose, np.float32)
+    if p.shape == (2, 12):
+        p = np.broadcast_to(p, (B, 2, 12))
+    if p.shape != (B, 2, 12) or not np.isfinite(p).all():
+        raise ValueError(f"pose must be a finite float32 [2,12] or [{B},2,12] (geometry.relative_pose), got shape {p.shape}")
+    return np.array(p, np.float32, order="C")              # (a copy: a broadcast view is read-only)
+
+
+def temporal_step(disp, cameras, pose=None, prev=None, sigma=None, mask=None, sigma0=0.5, min_disp=1.0, sigma_min=0.05, gate=3.0, q=0.0,
+                  max_jump=1.0, hold=False, q_hold=0.05, max_var=4.0, counts=True, out=None):
+    """One step of the temporal filter on disparity maps (include/lwsnet_temporal.h, lws_temporal_step): the previous state is carried
+    into the current left camera with a known pose, gated against the new maps and fused with them; with hold, a pixel without a
+    measurement keeps what was seen there before.  disp [B,1,H,W] float32; cameras: one Camera or a list of B; pose: what
+    geometry.relative_pose returns, [2,12] or [B,2,12]; prev: the (disp, var, age) of the previous step's TemporalResult, or None on
+    the first frame (pose is then not read); sigma: None (sigma0 px everywhere) or float32 [B,1,H,W] in px; mask: None or the uint8
+    lws_lr_check code map (only code-1 pixels are measurements).  The defaults of gate, q, sigma0, sigma_min, max_jump, q_hold and
+    max_var were chosen on a synthetic scene only; they have not met real data.  out: None (new tensors) or the four tensors (disp, var, age, code) to write, which may not be
+    prev's.  Returns a TemporalResult."""
+    if cameras is None:
+        raise ValueError("temporal_step needs cameras")
+    scalars = _temporal_args(sigma0, min_disp, sigma_min, gate, q, max_jump, hold, q_hold, max_var)
+    if prev is not None and (len(prev) != 3 or any(t is None for t in prev)):
+        raise ValueError("prev must be the (disp, var, age) of the previous step, or None")
+    if prev is not None and pose is None:
+        raise ValueError("temporal_step: a previous state needs pose")
+    d, mask, cam = _geometry_inputs(disp, mask, cameras, scalars[1], float("inf"))
+    B, _, H, W = d.shape
+    if H * W >= 1 << 31:
+        raise ValueError(f"disp is {H}x{W}: temporal_step takes maps of fewer than 2^31 pixels")
+    if sigma is not None:
+        sigma = _disp_map(sigma, "sigma")
+        if tuple(sigma.shape) != tuple(d.shape) or sigma.device != d.device:
+            raise ValueError(f"sigma must be {tuple(d.shape)} on {d.device}")
+    pose_dev = None
+    if prev is not None:
+        prev = (_tensor_of(prev[0], "prev disp", torch.float32, d.shape, d.device), _tensor_of(prev[1], "prev var", torch.float32, d.shape, d.device),
+                _tensor_of(prev[2], "prev age", torch.uint16, d.shape, d.device))
+        pose_dev = torch.from_numpy(temporal_pose_rows(pose, B)).to(d.device)
+    else:
+        prev = (None, None, None)
+    hold = scalars[6]
+    work = _workspace("lws_temporal_workspace", d.device, B, H, W, hold) if hold else None
+    dts = (torch.float32, torch.float32, torch.uint16, torch.uint8)
+    if out is None:
+        out = [torch.empty(d.shape, device=d.device, dtype=dt) for dt in dts]
+    elif len(out) != 4:
+        raise ValueError("out must be four tensors (disp, var, age, code)")
+    else:
+        out = [_tensor_of(t, f"out[{i}]", dt, d.shape, d.device) for i, (t, dt) in enumerate(zip(out, dts))]
+    cnt =torch.empty((B, 5), device=d.device, dtype=torch.int64) if counts else None
+    _call("lws_temporal_step", d.device, d, sigma, mask, cam, pose_dev, *prev, B, H, W, *scalars, work, *out, cnt)
+    return TemporalResult(*out, cnt)
+
+
 SpeckleResult = namedtuple("SpeckleResult", ["disp", "mask", "labels", "counts"])
 SpeckleResult.__doc__ = """What speckle_filter returns: the filtered (filled if asked) maps float32 [B,1,H,W], the uint8 code map (1 kept,
 3 speckle, the input code or 0 for an invalid pixel), labels int32 [B,1,H,W] (None unless want_labels) and counts, an int64

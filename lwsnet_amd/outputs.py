@@ -366,16 +366,36 @@ def save_photo(frame, stage, stem, args, log, photo):
     return [stem + "_pe.png", stem + "_warp.png"]
 
 
+TEMPORAL_CODES = ("nothing", "new", "fused", "reset", "held")                     # lws_temporal_step's codes 0 .. 4
+TEMPORAL_COLOURS = np.array([[0, 0, 0], [0, 130, 200], [60, 180, 75], [230, 25, 75], [255, 225, 25]], np.uint8)   # by code
+
+
+def temporal_to_rgb(code):
+    """<stem>_tcode.png: the colour of each pixel's temporal code (TEMPORAL_COLOURS: nothing black, new blue, fused green, reset by
+    the gate red, held yellow)."""
+    return TEMPORAL_COLOURS[np.asarray(code)]
+
+
+def save_temporal(frame, stage, stem, args, log, fused):
+    """--save_temporal: the temporal filter's codes and fused sigma of one frame (an ops.TemporalResult) as <stem>_tcode.png and
+    <stem>_tsigma.png = sigma_to_u8(sqrt(var), --sigma_max)."""
+    io.save_png(stem + "_tcode.png", temporal_to_rgb(fused.code[0, 0].cpu().numpy()))
+    save_png_gray8(stem + "_tsigma.png", sigma_to_u8(np.sqrt(fused.var[0, 0].cpu().numpy().astype(np.float64)), args.sigma_max))
+    log.info("Save temporal codes = {}_tcode.png, fused sigma = {}_tsigma.png".format(stem, stem))
+    return [stem + "_tcode.png", stem + "_tsigma.png"]
+
+
 # the code maps beside a colour file: (the ChainResult's field, suffix, log line, the codes whose shares it gives)
 CODE_MASKS = (("lr_masks", "_lr.png", "LR check: density = {:.4f}\t\tSave mask = {}", (1,)),
               ("occ_masks", "_occ.png", "Occlusion check: density = {:.4f}\t\tSave mask = {}", (1,)),
               ("speckle_masks", "_sp.png", "Speckle filter: kept = {:.4f}, removed = {:.4f}\t\tSave codes = {}", (1, 3)))
 
 
-def write_stage(path, color, cost_line, frame, stage, args, log, res, conf=None, photo=None):
+def write_stage(path, color, cost_line, frame, stage, args, log, res, conf=None, photo=None, temporal=None):
     """One colour file and everything beside it: the colour-mapped map `color` of stage `stage` to `path`, then the lr, occ and
-    speckle code maps, the confidence maps, the geometry files and the photometric maps that are on.  res: the ChainResult; conf:
-    the ConfResult of the same forward when a confidence flag is on; photo: the result of photometric().  Returns the paths."""
+    speckle code maps, the confidence maps, the geometry files, the photometric maps and the temporal maps that are on.  res: the
+    ChainResult; conf: the ConfResult of the same forward when a confidence flag is on; photo: the result of photometric();
+    temporal: the frame's ops.TemporalResult with --temporal.  Returns the paths."""
     io.save_png(path, color)
     log.info("{}\t\tSave img = {}".format(cost_line, path))
     written, stem = [path], os.path.splitext(path)[0]
@@ -393,4 +413,6 @@ def write_stage(path, color, cost_line, frame, stage, args, log, res, conf=None,
         written += save_geometry(frame, stage, stem, args, log, res.disp[stage], keep)
     if photo is not None and args.save_photo:
         written += save_photo(frame, stage, stem, args, log, photo)
+    if temporal is not None and args.save_temporal and stage == 3:      # the filter runs on the stage-4 map
+        written += save_temporal(frame, stage, stem, args, log, temporal)
     return written
