@@ -121,6 +121,17 @@ def read_kitti_poses(path):
     return np.asarray(rows, np.float64).reshape(-1, 3, 4)
 
 
+def write_kitti_poses(path, poses):
+    """Writes camera-to-world poses, float64 (N,3,4), as a KITTI odometry `poses.txt`: line i the 12 numbers of the row-major [R|t]
+    of frame i, each with the digits that read back to the same float64 (read_kitti_poses returns exactly `poses`)."""
+    p = np.asarray(poses, np.float64)
+    if p.ndim != 3 or p.shape[1:] != (3, 4) or not np.isfinite(p).all():
+        raise ValueError(f"poses must be finite (N,3,4) camera-to-world [R|t], got shape {p.shape}")
+    with open(path, "w", encoding="utf-8") as f:
+        for row in p.reshape(-1, 12):
+            f.write(" ".join(repr(float(v)) for v in row) + "\n")
+
+
 def _pose44(T, name):
     T = np.asarray(T, np.float64)
     if T.shape != (3, 4) or not np.isfinite(T).all():

@@ -109,6 +109,18 @@ receive.  The measurement's sigma is the constant S px (default 0.5) or, with `n
 line per frame gives the pixels per code (nothing, new, fused, reset, held).  `--save_temporal` writes `<stem>_tcode.png`, the codes
 through a fixed five-colour table, and `<stem>_tsigma.png`, sqrt of the fused variance scaled as `--save_conf`'s sigma image.  Needs a
 camera; the poses are taken as the left camera's.
+
+`--egomotion [--ego_levels N] [--ego_iters N] [--ego_huber K] [--save_poses PATH] [--save_ego]`: directory mode only, sequential, needs
+a camera; the frames are a sequence in sorted order.  The motion of the left camera from each frame to the next is estimated by dense
+direct alignment (lwsnet_amd.egomotion.Odometry, lws_egomotion) from the previous frame's left crop, the chain's own stage-4 map and
+`keep` codes of that frame (not a fused state) and the current left crop.  One log line per frame gives the translation in metres, the
+rotation in degrees, the pixels used, the rms residual in grey levels and the status bits.  `--save_poses PATH` writes the accumulated
+camera-to-world poses as a KITTI odometry `poses.txt` (line 0 the identity); `--save_ego` writes `<stem>_ego.png`, the magnitude of
+the residual at the final pose as 8-bit grey (all 0 for the first frame): what does not move with the scene shows there.  A pair that
+is skipped keeps its line of the poses file (line i belongs to pair i): it repeats the pose before it, with a warning, and the next
+estimate spans the gap.  The op reads nothing back; the CLI reads the estimate's pose, info and status back once per frame.  With
+`--temporal`, the filter takes its pose from the estimate and `--poses` may not be given; an estimate whose status says it is not to
+be trusted (bit 3) resets the filter for that frame, with a warning.
 """
 import argparse
 import contextlib
@@ -156,6 +168,7 @@ def build_parser():
     add_conf_arguments(p)
     post.add_photometric_arguments(p, save=True)
     add_temporal_arguments(p)
+    add_egomotion_arguments(p)
     return p
 
 
@@ -240,7 +253,10 @@ def check_temporal_arguments(p, args):
         if given or args.poses is not None:
             p.error("--poses, --temporal_gate, --temporal_q, --temporal_sigma and --temporal_hold need --temporal")
         return
-    if args.poses is None:
+    ego = bool(getattr(args, "egomotion", False))
+    if ego and args.poses is not None:
+        p.error("--temporal --egomotion takes the filter's poses from the estimate: do not give --poses as well")
+    if args.poses is None and not ego:
         p.error("--temporal needs --poses PATH, the camera-to-world pose of every pair")
     _needs_camera(p, args, "--temporal and --save_temporal")
     post.sequential_only(p, args, "--temporal / --save_temporal", "run")
@@ -257,6 +273,8 @@ def check_temporal_arguments(p, args):
         p.error(f"--temporal_gate must be finite and > 0, got {args.temporal_gate}")
     if not (np.isfinite(args.temporal_q) and args.temporal_q >= 0):
         p.error(f"--temporal_q must be finite and >= 0, got {args.temporal_q}")
+    if ego:
+        return
     try:
         n = len(read_kitti_poses(args.poses))
     except (OSError, ValueError) as e:
@@ -264,6 +282,45 @@ def check_temporal_arguments(p, args):
     pairs = len(_list_pairs(args)[0])
     if n < pairs:
         p.error(f"--poses: {args.poses} holds {n} poses for {pairs} pairs (line i belongs to the i-th pair in sorted order)")
+
+
+def add_egomotion_arguments(p):
+    """--egomotion and its flags (not in the reference): lwsnet_amd.egomotion.Odometry beside the chain.  A command line without them
+    parses to the namespace it parsed to before they existed (argparse.SUPPRESS); check_egomotion_arguments writes their defaults."""
+    S = argparse.SUPPRESS
+    p.add_argument("--egomotion", action="store_true", default=S,
+                   help="estimate the left camera's motion from frame to frame by dense direct alignment (directory mode, sequential "
+                        "only; needs a camera; not in the reference)")
+    p.add_argument("--ego_levels", type=int, default=S, metavar="N", help="egomotion: pyramid levels, 1 .. 8 (default 4)")
+    p.add_argument("--ego_iters", type=int, default=S, metavar="N", help="egomotion: Gauss-Newton steps per level, 1 .. 64 (default 8)")
+    p.add_argument("--ego_huber", type=float, default=S, metavar="K", help="egomotion: the Huber threshold in grey levels (default 10)")
+    p.add_argument("--save_poses", type=str, default=S, metavar="PATH",
+                   help="egomotion: write the accumulated camera-to-world poses as a KITTI odometry poses.txt")
+    p.add_argument("--save_ego", action="store_true", default=S,
+                   help="egomotion: write <stem>_ego.png, the magnitude of the residual at the final pose")
+
+
+EGO_DEFAULTS = dict(egomotion=False, ego_levels=4, ego_iters=8, ego_huber=10.0, save_poses=None, save_ego=False)
+
+
+def check_egomotion_arguments(p, args):
+    """Rejects what the ego-motion estimate does not support, before any model or GPU work; sets the defaults."""
+    given = [f for f in ("ego_levels", "ego_iters", "ego_huber", "save_poses", "save_ego") if hasattr(args, f)]   # (SUPPRESS: there only if given)
+    post.set_defaults(args, **EGO_DEFAULTS)
+    if not args.egomotion:
+        if given:
+            p.error("--ego_levels, --ego_iters, --ego_huber, --save_poses and --save_ego need --egomotion")
+        return
+    _needs_camera(p, args, "--egomotion and --save_ego")
+    post.sequential_only(p, args, "--egomotion / --save_ego", "run")
+    if args.left_img:
+        p.error("--egomotion follows a sequence: use directory mode (--img_path), not --left_img")
+    if not 1 <= args.ego_levels <= 8:
+        p.error(f"--ego_levels must be in 1 .. 8, got {args.ego_levels}")
+    if not 1 <= args.ego_iters <= 64:
+        p.error(f"--ego_iters must be in 1 .. 64, got {args.ego_iters}")
+    if not (np.isfinite(args.ego_huber) and args.ego_huber > 0):
+        p.error(f"--ego_huber must be finite and > 0, got {args.ego_huber}")
 
 
 class _ConfModel:
@@ -612,15 +669,19 @@ def inference(model, left_imgs, right_imgs, args, log):
     import torch
     default_arguments(args)
     post.set_defaults(args, **TEMPORAL_DEFAULTS)            # (check_temporal_arguments' defaults, for a namespace that skipped it)
+    post.set_defaults(args, **EGO_DEFAULTS)
     written, warm = [], False
     opts = post.Options.from_args(args)
-    geo = _geometry_requested(args) or args.temporal
+    geo = _geometry_requested(args) or args.temporal or args.egomotion
     conf_on = conf_requested(args) or (args.temporal and temporal_sigma(args) is None)
     chain_model = _ConfModel(model) if conf_on else model
     sequence = _Sequence(args) if args.temporal else None
+    odometry = _Odometry(args) if args.egomotion else None
     for index, (li, ri) in enumerate(zip(left_imgs, right_imgs)):
         frame = _load_frame(args, li, ri, model.device, geo, log)
         if frame is None:
+            if odometry:
+                odometry.skip(li, log)
             continue
         if args.rectify is not None and args.save_rect:
             folder = os.path.dirname(args.left_img) if args.left_img else args.save_path
@@ -639,7 +700,8 @@ def inference(model, left_imgs, right_imgs, args, log):
                 log.info("Weighted median (radius {}, sigma {:g}, fill {}): stage {} changed = {}, filled = {}".format(
                     opts.wmedian, opts.wmedian_sigma, opts.wmedian_fill, stage + 1, changed, refilled))
         conf = chain_model.last if conf_on else None
-        fused, res = sequence.step(index, frame, res, conf, log) if sequence else (None, res)
+        ego = odometry.step(frame, res, log) if odometry else None     # on the chain's own map and codes, ahead of the filter
+        fused, res = sequence.step(index, frame, res, conf, log, ego) if sequence else (None, res)
         photo = out.photometric(frame, res, args, log) if args.photometric else None
         for stage in range(4):
             disp = res.disp[stage].squeeze(axis=[0, 1]).numpy()         # :114 (the uint8 cast is inside disparity_to_color)
@@ -648,7 +710,54 @@ def inference(model, left_imgs, right_imgs, args, log):
                 written += out.write_stage(os.path.join(os.path.dirname(args.left_img), str(stage + 1) + ".png"), color, ss, frame, stage, args, log, res, conf, photo)
         if not args.left_img:                                           # :133-137 (stage-4 map only)
             written += out.write_stage(os.path.join(args.save_path, os.path.basename(frame.path)), color, ss, frame, 3, args, log, res, conf, photo, fused)
+            if odometry and args.save_ego:
+                written += out.save_ego(os.path.splitext(os.path.join(args.save_path, os.path.basename(frame.path)))[0], frame, log, ego)
+    if odometry and args.save_poses is not None:
+        odometry.write_poses(args.save_poses)
+        log.info("Save poses = {}".format(args.save_poses))
+        written.append(args.save_poses)
     return written
+
+
+class _Odometry:
+    """--egomotion: the Odometry of the run.  step() estimates the motion from the previous frame to this one from the chain's own
+    stage-4 map and `keep` codes and returns the ops.EgoResult (None on the first frame).  The op itself reads nothing back; this
+    class does, once per frame: the pose, info and status of the estimate, for the log line, the accumulated poses and the
+    filter's reset.  A pair that was skipped is bridged -- the next estimate spans the gap -- and keeps its line in the poses file
+    (line i belongs to pair i, as geometry.read_kitti_poses' users expect): it repeats the pose of the last pair before it, the
+    identity where there is none, and a warning says so."""
+
+    def __init__(self, args):
+        self.args, self.odometry = args, None
+        self.lines = []            # per pair: the index of its pose among the Odometry's, -1 before the first processed pair
+
+    def skip(self, left_path, log):
+        log.warning("Egomotion: %s was skipped; its line of the poses file repeats the pose of the pair before it", left_path)
+        self.lines.append(self.lines[-1] if self.lines else -1)
+
+    def write_poses(self, path):
+        from .geometry import write_kitti_poses
+        identity = np.hstack([np.eye(3), np.zeros((3, 1))])
+        poses = self.odometry.poses() if self.odometry is not None else np.zeros((0, 3, 4))
+        write_kitti_poses(path, np.stack([poses[i] if i >= 0 else identity for i in self.lines]) if self.lines else poses)
+
+    def step(self, frame, res, log):
+        import torch
+        from .egomotion import Odometry, motion_summary
+        a = self.args
+        if self.odometry is None:
+            self.odometry = Odometry(frame.cam, levels=a.ego_levels, iters=a.ego_iters, huber=a.ego_huber, min_disp=a.min_disp)
+        disp = res.disp[3].as_subclass(torch.Tensor)
+        with torch.cuda.device(disp.device):
+            ego = self.odometry.step(out.rgb_on_device(frame.left, disp.device), disp, res.keep[3] if res.keep is not None else None,
+                                     resid=a.save_ego)
+        self.lines.append(len(self.odometry.poses()) - 1)
+        if ego is not None:
+            t, deg = motion_summary(ego.pose[0, 0].cpu().numpy())
+            n, rms = ego.info[0, :2].cpu().tolist()
+            log.info("Egomotion: t = {:.4f} m, rotation = {:.4f} deg, pixels = {}, rms = {:.3f}, status = {}".format(
+                t, deg, int(n), rms, int(self.odometry.status[-1][0])))
+        return ego
 
 
 class _Sequence:
@@ -660,10 +769,12 @@ class _Sequence:
 
     def __init__(self, args):
         from .geometry import read_kitti_poses
-        self.args, self.poses, self.filter, self.last = args, read_kitti_poses(args.poses), None, None
+        self.args, self.filter, self.last = args, None, None
+        self.poses = None if args.egomotion else read_kitti_poses(args.poses)      # --egomotion: the pose comes with every frame
 
-    def step(self, index, frame, res, conf, log):
+    def step(self, index, frame, res, conf, log, ego=None):
         import torch
+        from . import ops
         from .geometry import relative_pose
         from .models import DisparityTensor
         from .temporal import TemporalFilter
@@ -673,7 +784,16 @@ class _Sequence:
             self.filter = TemporalFilter(frame.cam, gate=a.temporal_gate, q=a.temporal_q, sigma0=0.5 if sigma0 is None else sigma0,
                                          hold=a.temporal_hold, min_disp=a.min_disp)
         disp = res.disp[3].as_subclass(torch.Tensor)
-        pose = None if self.last is None else relative_pose(self.poses[self.last], self.poses[index])
+        if self.poses is not None:
+            pose = None if self.last is None else relative_pose(self.poses[self.last], self.poses[index])
+        elif ego is None:
+            pose = None
+        elif int(ego.status[0]) & ops.EGO_UNTRUSTED:
+            log.warning("Temporal: the ego-motion estimate of %s is not to be trusted (status %d): the filter starts anew", frame.path,
+                        int(ego.status[0]))
+            pose = None
+        else:
+            pose = ego.pose
         with torch.cuda.device(disp.device):
             out_ = self.filter.step(disp, pose, sigma=conf.sigma[2] if sigma0 is None else None, mask=res.keep[3] if res.keep is not None else None)
         self.last = index
@@ -744,6 +864,7 @@ def main(argv=None):
     check_rectify_arguments(parser, args)
     check_conf_arguments(parser, args)
     post.check_photometric_arguments(parser, args, save=True)
+    check_egomotion_arguments(parser, args)
     check_temporal_arguments(parser, args)
     log = start_logging("lwsnet_amd.inference", args)
     model = load_model(args, log)

@@ -839,7 +839,7 @@ def temporal_step(disp, cameras, pose=None, prev=None, sigma=None, mask=None, si
     """One step of the temporal filter on disparity maps (include/lwsnet_temporal.h, lws_temporal_step): the previous state is carried
     into the current left camera with a known pose, gated against the new maps and fused with them; with hold, a pixel without a
     measurement keeps what was seen there before.  disp [B,1,H,W] float32; cameras: one Camera or a list of B; pose: what
-    geometry.relative_pose returns, [2,12] or [B,2,12]; prev: the (disp, var, age) of the previous step's TemporalResult, or None on
+    geometry.relative_pose returns, [2,12] or [B,2,12], or the float32 [B,2,12] device tensor egomotion returns; prev: the (disp, var, age) of the previous step's TemporalResult, or None on
     the first frame (pose is then not read); sigma: None (sigma0 px everywhere) or float32 [B,1,H,W] in px; mask: None or the uint8
     lws_lr_check code map (only code-1 pixels are measurements).  The defaults of gate, q, sigma0, sigma_min, max_jump, q_hold and
     max_var were chosen on a synthetic scene only; they have not met real data.  out: None (new tensors) or the four tensors (disp, var, age, code) to write, which may not be
@@ -863,7 +863,10 @@ def temporal_step(disp, cameras, pose=None, prev=None, sigma=None, mask=None, si
     if prev is not None:
         prev = (_tensor_of(prev[0], "prev disp", torch.float32, d.shape, d.device), _tensor_of(prev[1], "prev var", torch.float32, d.shape, d.device),
                 _tensor_of(prev[2], "prev age", torch.uint16, d.shape, d.device))
-        pose_dev = torch.from_numpy(temporal_pose_rows(pose, B)).to(d.device)
+        if isinstance(pose, torch.Tensor) and pose.is_cuda:  # egomotion's pose block: it stays on the device, nothing is read back
+            pose_dev = _tensor_of(pose, "pose", torch.float32, (B, 2, 12), d.device)
+        else:
+            pose_dev = torch.from_numpy(temporal_pose_rows(pose, B)).to(d.device)
     else:
         prev = (None, None, None)
     hold = scalars[6]
@@ -878,6 +881,91 @@ def temporal_step(disp, cameras, pose=None, prev=None, sigma=None, mask=None, si
     cnt =torch.empty((B, 5), device=d.device, dtype=torch.int64) if counts else None
     _call("lws_temporal_step", d.device, d, sigma, mask, cam, pose_dev, *prev, B, H, W, *scalars, work, *out, cnt)
     return TemporalResult(*out, cnt)
+
+
+EgoResult = namedtuple("EgoResult", ["pose", "status", "info", "trace", "resid"])
+EgoResult.__doc__ = """What egomotion returns, all on the device: pose float32 [B,2,12], the block temporal_step reads (pose[b][0] maps the
+previous camera's frame into the current one, pose[b][1] is its inverse); status int32 [B], a bit set (1 a level had too few pixels,
+2 a singular step, 4 a non-finite step, 8 the final linearisation had too few pixels: do not trust the pose, 16 a step below the
+pose's float32 resolution was not taken); info float64 [B,4]: pixels used and weighted rms residual at level 0 for the final pose,
+|delta| of the last step taken, steps taken; trace float64 [B,levels*iters,48] and resid float32 [B,1,H,W] (None unless asked for)."""
+EGO_UNTRUSTED = 8                                           # the status bit that says the pose is not to be trusted
+
+
+def ego_args(levels, iters, min_disp, max_jump, huber, damping, min_pixels):
+    """The validated scalar arguments of egomotion, in the order of the C call (lwsnet_amd.egomotion.Odometry checks its own with it)."""
+    if not (max_jump >= 0):
+        raise ValueError(f"max_jump must be >= 0 (inf allowed), got {max_jump}")
+    return (_int_in("levels", levels, 1, 8), _int_in("iters", iters, 1, 64), _finite_pos("min_disp", min_disp), float(max_jump),
+            _finite_pos("huber", huber), _finite_nonneg("damping", damping), _int_in("min_pixels", min_pixels, 1, (1 << 31) - 1))
+
+
+def _motion_rows(M, B, name, dt):
+    """M as [B,12] rows of numpy dtype dt: one row-major 3 x 4 [R|t] (12 numbers or 3 x 4) for every image, or B of them."""
+    import numpy as np
+    m = np.asarray(M.detach().cpu().numpy() if isinstance(M, torch.Tensor) else M, np.float64)
+    if m.shape in ((12,), (3, 4)):
+        m = np.broadcast_to(m.reshape(1, 12), (B, 12))
+    elif m.shape == (B, 3, 4):
+        m = m.reshape(B, 12)
+    if m.shape != (B, 12) or not np.isfinite(m).all():
+        raise ValueError(f"{name} must be a finite [12] or [{B},12] (row-major 3x4 [R|t]), got shape {m.shape}")
+    return np.array(m, dt, order="C")
+
+
+def ego_normal(grey_ref, disp_ref, grey_cur, cameras, M, level=0, mask=None, min_disp=1.0, huber=10.0, terms=False):
+    """One linearisation of the photometric error at one pyramid level (include/lwsnet_egomotion.h, lws_ego_normal).  grey_ref,
+    disp_ref, grey_cur float32 [B,1,H,W], the images of this level (disp_ref in full-resolution pixels); cameras: the full-resolution
+    Camera or a list of B; M: the motion to linearise at, [12] or [B,12] (float64); level 0..7 scales the camera; mask: None or the
+    uint8 lws_lr_check code map.  Returns (sums float64 [B,29], terms float32 [B,H,W,8] or None)."""
+    if cameras is None:
+        raise ValueError("ego_normal needs cameras")
+    level = _int_in("level", level, 0, 7)
+    huber = _finite_pos("huber", huber)
+    d, mask, cam = _geometry_inputs(disp_ref, mask, cameras, min_disp, float("inf"))
+    B, _, H, W = d.shape
+    if H * W >= 1 << 31:
+        raise ValueError(f"disp_ref is {H}x{W}: ego_normal takes maps of fewer than 2^31 pixels")
+    g0, g1 = (_tensor_of(g, name, torch.float32, d.shape, d.device) for g, name in ((grey_ref, "grey_ref"), (grey_cur, "grey_cur")))
+    m_dev = torch.from_numpy(_motion_rows(M, B, "M", "float64")).to(d.device)
+    work = _workspace("lws_egomotion_workspace", d.device, B, H, W, 1)
+    sums = torch.empty((B, 29), device=d.device, dtype=torch.float64)
+    tm = torch.empty((B, H, W, 8), device=d.device, dtype=torch.float32) if terms else None
+    _call("lws_ego_normal", d.device, g0, d, mask, g1, cam, m_dev, B, H, W, level, float(min_disp), huber, work, sums, tm)
+    return sums, tm
+
+
+def egomotion(rgb_ref, disp_ref, rgb_cur, cameras, mask=None, init=None, levels=4, iters=8, min_disp=1.0, max_jump=1.0, huber=10.0,
+              damping=0.0, min_pixels=256, trace=False, resid=False):
+    """The motion of the camera between two frames by dense direct alignment (include/lwsnet_egomotion.h, lws_egomotion): the pixels
+    of the previous left image, with their disparity, are warped into the current one and the intensity difference is minimised over
+    the six motion parameters, coarse to fine.  rgb_ref, rgb_cur uint8 [B,H,W,3], the previous and the current left image; disp_ref
+    float32 [B,1,H,W] and mask (None or the uint8 lws_lr_check code map) the previous frame's disparity; cameras: one Camera or a
+    list of B; init: None (the identity), a float32 [B,12] device tensor (such as pose[:, 0] of the previous estimate) or [12] /
+    [B,12] host numbers.  The defaults of levels, iters, huber, max_jump and min_pixels were chosen on a synthetic scene only; they
+    have not met real data.  Returns an EgoResult; nothing is read back, and its pose is what temporal_step takes as `pose`."""
+    if cameras is None:
+        raise ValueError("egomotion needs cameras")
+    scalars = ego_args(levels, iters, min_disp, max_jump, huber, damping, min_pixels)
+    d, mask, cam = _geometry_inputs(disp_ref, mask, cameras, scalars[2], float("inf"))
+    B, _, H, W = d.shape
+    if H * W >= 1 << 31:
+        raise ValueError(f"disp_ref is {H}x{W}: egomotion takes maps of fewer than 2^31 pixels")
+    r0, r1 = (_tensor_of(r, name, torch.uint8, (B, H, W, 3), d.device) for r, name in ((rgb_ref, "rgb_ref"), (rgb_cur, "rgb_cur")))
+    if init is not None:
+        if isinstance(init, torch.Tensor) and init.is_cuda:
+            init = _tensor_of(init, "init", torch.float32, (B, 12), d.device)
+        else:
+            init = torch.from_numpy(_motion_rows(init, B, "init", "float32")).to(d.device)
+    levels, iters = scalars[:2]
+    work = _workspace("lws_egomotion_workspace", d.device, B, H, W, levels)
+    pose = torch.empty((B, 2, 12), device=d.device, dtype=torch.float32)
+    status = torch.empty((B,), device=d.device, dtype=torch.int32)
+    info = torch.empty((B, 4), device=d.device, dtype=torch.float64)
+    tr = torch.empty((B, levels * iters, 48), device=d.device, dtype=torch.float64) if trace else None
+    rs = torch.empty(d.shape, device=d.device, dtype=torch.float32) if resid else None
+    _call("lws_egomotion", d.device, r0, d, mask, r1, cam, init, B, H, W, *scalars, work, pose, status, info, tr, rs)
+    return EgoResult(pose, status, info, tr, rs)
 
 
 SpeckleResult = namedtuple("SpeckleResult", ["disp", "mask", "labels", "counts"])

@@ -385,6 +385,20 @@ def save_temporal(frame, stage, stem, args, log, fused):
     return [stem + "_tcode.png", stem + "_tsigma.png"]
 
 
+def ego_to_u8(resid):
+    """[H,W] residual of lws_egomotion in grey levels -> the bytes of <stem>_ego.png: min(rint(|r|), 255)."""
+    return np.minimum(np.rint(np.abs(np.asarray(resid, np.float64))), 255.0).astype(np.uint8)
+
+
+def save_ego(stem, frame, log, ego):
+    """--save_ego: <stem>_ego.png, the residual magnitude at the final pose of the frame's ops.EgoResult; all 0 for a first frame
+    (ego None), which has no previous frame to align with."""
+    h, w = _rgb_on_host(frame.left).shape[:2]
+    save_png_gray8(stem + "_ego.png", np.zeros((h, w), np.uint8) if ego is None else ego_to_u8(ego.resid[0, 0].cpu().numpy()))
+    log.info("Save ego-motion residual = {}_ego.png".format(stem))
+    return [stem + "_ego.png"]
+
+
 # the code maps beside a colour file: (the ChainResult's field, suffix, log line, the codes whose shares it gives)
 CODE_MASKS = (("lr_masks", "_lr.png", "LR check: density = {:.4f}\t\tSave mask = {}", (1,)),
               ("occ_masks", "_occ.png", "Occlusion check: density = {:.4f}\t\tSave mask = {}", (1,)),
