@@ -1,7 +1,7 @@
 """ctypes binding of liblwsnet_hip.so.  include/lwsnet_hip.h is the statement of the C ABI: PROTOTYPES and the LWS_*
 constants are read from it when this module is imported (tests/test_abi_cpu.py has a C++ compiler check the reading).  The entry
 points added behind ABI v8 in headers of their own (include/lwsnet_objects.h) are read the same way into EXTENSION_PROTOTYPES, include/lwsnet_temporal.h into TEMPORAL_PROTOTYPES and
-include/lwsnet_egomotion.h into EGOMOTION_PROTOTYPES.
+include/lwsnet_egomotion.h into EGOMOTION_PROTOTYPES and include/lwsnet_tsdf.h into TSDF_PROTOTYPES.
 
 The header cannot say which pointers are host pointers, so every pointer but `const char *` is c_void_p: the 20 host-pointer
 parameters -- lws_set_tensor's data and shape, the mean / std arrays, lws_profile_read*, lws_clock_read, lws_join_stats, the
@@ -22,6 +22,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "lwsnet_hip.h")
 EXTENSION_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "lwsnet_objects.h"),)
 TEMPORAL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "lwsnet_temporal.h")
 EGOMOTION_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "lwsnet_egomotion.h")
+TSDF_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "lwsnet_tsdf.h")
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
@@ -127,6 +128,10 @@ with open(TEMPORAL_HEADER_PATH) as _f:
 with open(EGOMOTION_HEADER_PATH) as _f:
     EGOMOTION_PROTOTYPES, EGOMOTION_SPELLINGS, _ = parse_header(_f.read(), EGOMOTION_HEADER_PATH)
 
+# and for the TSDF volume's header: exactly the functions include/lwsnet_tsdf.h declares
+with open(TSDF_HEADER_PATH) as _f:
+    TSDF_PROTOTYPES, TSDF_SPELLINGS, _ = parse_header(_f.read(), TSDF_HEADER_PATH)
+
 _lib = None
 
 
@@ -151,7 +156,7 @@ def load():
             f"{LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python -m lwsnet_amd.build`); there is no CPU fallback for the disparity path")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in {**PROTOTYPES, **EXTENSION_PROTOTYPES, **TEMPORAL_PROTOTYPES, **EGOMOTION_PROTOTYPES}.items():
+    for name, (res, args) in {**PROTOTYPES, **EXTENSION_PROTOTYPES, **TEMPORAL_PROTOTYPES, **EGOMOTION_PROTOTYPES, **TSDF_PROTOTYPES}.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

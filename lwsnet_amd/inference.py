@@ -121,6 +121,19 @@ is skipped keeps its line of the poses file (line i belongs to pair i): it repea
 estimate spans the gap.  The op reads nothing back; the CLI reads the estimate's pose, info and status back once per frame.  With
 `--temporal`, the filter takes its pose from the estimate and `--poses` may not be given; an estimate whose status says it is not to
 be trusted (bit 3) resets the filter for that frame, with a warning.
+
+`--tsdf [--tsdf_voxel V] [--tsdf_extent X0 X1 Y0 Y1 Z0 Z1] [--tsdf_trunc MU0] [--tsdf_trunc_px MU_D] [--tsdf_weight unit|sigma]
+[--tsdf_sdf plane|ray] [--save_tsdf_ply PATH] [--save_tsdf]`: directory mode only, sequential, needs a camera and the pose of every
+pair, from `--poses PATH` or `--egomotion`.  The stage-4 map of each frame -- with `--temporal` the fused map and its sigma -- is
+integrated behind the chain into a dense TSDF volume (lwsnet_amd.tsdf.TsdfVolume, lws_tsdf_integrate) under the chain's `keep` codes
+and with the left crop's colours.  The volume's frame is the first camera integrated (y down, z forward); the extent is in metres
+there, the voxel V metres wide (default 0.2 over -12.8 12.8 -3.2 3.2 0 51.2).  `plane` (the default) measures the distance to each
+pixel's tangent plane, with the normals of lws_surface_normals at `--max_jump`; `ray` measures it along the ray, which starves a road
+seen at a grazing angle of updates.  One log line per frame gives the voxels updated.  `--save_tsdf` writes `<stem>_tsdf.png`, the
+volume ray-cast into the frame's own pose and coloured as the stage maps: the denoised model view of that frame.  At the end
+`--save_tsdf_ply PATH` writes the volume's zero crossings as a PLY of vertices with normals and colours and logs their number.  A
+volume that does not fit the device's free memory is an error before the first frame.  What leaves the volume is not mapped; movers
+smear; the poses are taken as given.
 """
 import argparse
 import contextlib
@@ -169,6 +182,7 @@ def build_parser():
     post.add_photometric_arguments(p, save=True)
     add_temporal_arguments(p)
     add_egomotion_arguments(p)
+    add_tsdf_arguments(p)
     return p
 
 
@@ -250,7 +264,7 @@ def check_temporal_arguments(p, args):
     post.set_defaults(args, **TEMPORAL_DEFAULTS)
     args.temporal = args.temporal or args.save_temporal
     if not args.temporal:
-        if given or args.poses is not None:
+        if given or (args.poses is not None and not getattr(args, "tsdf", False)):
             p.error("--poses, --temporal_gate, --temporal_q, --temporal_sigma and --temporal_hold need --temporal")
         return
     ego = bool(getattr(args, "egomotion", False))
@@ -321,6 +335,83 @@ def check_egomotion_arguments(p, args):
         p.error(f"--ego_iters must be in 1 .. 64, got {args.ego_iters}")
     if not (np.isfinite(args.ego_huber) and args.ego_huber > 0):
         p.error(f"--ego_huber must be finite and > 0, got {args.ego_huber}")
+
+
+def add_tsdf_arguments(p):
+    """--tsdf and its flags (not in the reference): lwsnet_amd.tsdf.TsdfVolume behind the chain.  A command line without them parses
+    to the namespace it parsed to before they existed (argparse.SUPPRESS); check_tsdf_arguments writes their defaults."""
+    S = argparse.SUPPRESS
+    p.add_argument("--tsdf", action="store_true", default=S,
+                   help="integrate the stage-4 maps of the sequence into a TSDF volume with the poses of --poses or --egomotion (directory "
+                        "mode, sequential only; needs a camera; not in the reference)")
+    p.add_argument("--tsdf_voxel", type=float, default=S, metavar="V", help="tsdf: the voxel's side in metres (default 0.2)")
+    p.add_argument("--tsdf_extent", type=float, nargs=6, default=S, metavar=("X0", "X1", "Y0", "Y1", "Z0", "Z1"),
+                   help="tsdf: the volume's extent in metres in the first camera's frame, y down, z forward (default -12.8 12.8 -3.2 3.2 0 51.2)")
+    p.add_argument("--tsdf_trunc", type=float, default=S, metavar="MU0", help="tsdf: the truncation band in metres (default 3 voxels)")
+    p.add_argument("--tsdf_trunc_px", type=float, default=S, metavar="MU_D",
+                   help="tsdf: the band in pixels of disparity, so that it grows as z^2: max(MU0, MU_D * z^2 / fb) (default 0)")
+    p.add_argument("--tsdf_weight", type=str, default=S, choices=("unit", "sigma"),
+                   help="tsdf: a frame counts 1, or 1 / sigma_z^2 with the sigma of --temporal (0.5 px without it) (default unit)")
+    p.add_argument("--tsdf_sdf", type=str, default=S, choices=("plane", "ray"),
+                   help="tsdf: the distance to the pixel's tangent plane (surface normals with --max_jump) or along the ray (default plane)")
+    p.add_argument("--save_tsdf_ply", type=str, default=S, metavar="PATH",
+                   help="tsdf: at the end, write the volume's zero crossings as a binary PLY of vertices with normals and colours")
+    p.add_argument("--save_tsdf", action="store_true", default=S,
+                   help="tsdf: write <stem>_tsdf.png, the volume ray-cast into the frame's own pose, coloured as the stage maps")
+
+
+TSDF_DEFAULTS = dict(tsdf=False, tsdf_voxel=0.2, tsdf_extent=(-12.8, 12.8, -3.2, 3.2, 0.0, 51.2), tsdf_trunc=None, tsdf_trunc_px=0.0,
+                     tsdf_weight="unit", tsdf_sdf="plane", save_tsdf_ply=None, save_tsdf=False)
+TSDF_MAX_POINTS = 1 << 22                                   # the capacity of --save_tsdf_ply, in records of 32 bytes
+
+
+def tsdf_grid(args):
+    """(origin, dims) of the volume --tsdf_extent and --tsdf_voxel describe: voxel centres from X0, Y0, Z0 on, as many as reach the
+    far ends."""
+    e, v = args.tsdf_extent, args.tsdf_voxel
+    return (e[0], e[2], e[4]), tuple(int(np.floor((e[2 * k + 1] - e[2 * k]) / v + 0.5)) + 1 for k in range(3))
+
+
+def check_tsdf_arguments(p, args):
+    """Rejects what the volume does not support, before any model or GPU work; sets the defaults."""
+    from . import ops
+    given = [f for f in TSDF_DEFAULTS if f != "tsdf" and hasattr(args, f)]      # (SUPPRESS: there only if given)
+    post.set_defaults(args, **TSDF_DEFAULTS)
+    if not args.tsdf:
+        if given:
+            p.error("--tsdf_voxel, --tsdf_extent, --tsdf_trunc, --tsdf_trunc_px, --tsdf_weight, --tsdf_sdf, --save_tsdf_ply and --save_tsdf need --tsdf")
+        return
+    _needs_camera(p, args, "--tsdf and --save_tsdf")
+    post.sequential_only(p, args, "--tsdf / --save_tsdf", "run")
+    if args.left_img:
+        p.error("--tsdf maps a sequence: use directory mode (--img_path), not --left_img")
+    if getattr(args, "poses", None) is None and not getattr(args, "egomotion", False):
+        p.error("--tsdf needs the pose of every pair: --poses PATH or --egomotion")
+    if not (np.isfinite(args.tsdf_voxel) and args.tsdf_voxel > 0):
+        p.error(f"--tsdf_voxel must be finite and > 0, got {args.tsdf_voxel}")
+    e = args.tsdf_extent
+    if not (np.isfinite(e).all() and e[0] < e[1] and e[2] < e[3] and e[4] < e[5]):
+        p.error(f"--tsdf_extent must be finite X0 < X1, Y0 < Y1, Z0 < Z1, got {' '.join(str(v) for v in e)}")
+    try:
+        ops.tsdf_volume_args(tsdf_grid(args)[0], args.tsdf_voxel, tsdf_grid(args)[1])
+    except ValueError as err:
+        p.error(f"--tsdf_extent / --tsdf_voxel: {err}")
+    if args.tsdf_trunc is None:
+        args.tsdf_trunc = 3.0 * args.tsdf_voxel
+    if not (np.isfinite(args.tsdf_trunc) and args.tsdf_trunc > 0):
+        p.error(f"--tsdf_trunc must be finite and > 0, got {args.tsdf_trunc}")
+    if not (np.isfinite(args.tsdf_trunc_px) and args.tsdf_trunc_px >= 0):
+        p.error(f"--tsdf_trunc_px must be finite and >= 0, got {args.tsdf_trunc_px}")
+    if getattr(args, "temporal", False) or getattr(args, "egomotion", False):
+        return                                              # check_temporal_arguments read the poses file, or there is none
+    from .geometry import read_kitti_poses
+    try:
+        n = len(read_kitti_poses(args.poses))
+    except (OSError, ValueError) as err:
+        p.error(f"--poses: cannot read {args.poses}: {err}")
+    pairs = len(_list_pairs(args)[0])
+    if n < pairs:
+        p.error(f"--poses: {args.poses} holds {n} poses for {pairs} pairs (line i belongs to the i-th pair in sorted order)")
 
 
 class _ConfModel:
@@ -670,13 +761,15 @@ def inference(model, left_imgs, right_imgs, args, log):
     default_arguments(args)
     post.set_defaults(args, **TEMPORAL_DEFAULTS)            # (check_temporal_arguments' defaults, for a namespace that skipped it)
     post.set_defaults(args, **EGO_DEFAULTS)
+    post.set_defaults(args, **TSDF_DEFAULTS)
     written, warm = [], False
     opts = post.Options.from_args(args)
-    geo = _geometry_requested(args) or args.temporal or args.egomotion
+    geo = _geometry_requested(args) or args.temporal or args.egomotion or args.tsdf
     conf_on = conf_requested(args) or (args.temporal and temporal_sigma(args) is None)
     chain_model = _ConfModel(model) if conf_on else model
     sequence = _Sequence(args) if args.temporal else None
     odometry = _Odometry(args) if args.egomotion else None
+    volume = _Volume(args, model.device, log) if args.tsdf else None
     for index, (li, ri) in enumerate(zip(left_imgs, right_imgs)):
         frame = _load_frame(args, li, ri, model.device, geo, log)
         if frame is None:
@@ -702,6 +795,7 @@ def inference(model, left_imgs, right_imgs, args, log):
         conf = chain_model.last if conf_on else None
         ego = odometry.step(frame, res, log) if odometry else None     # on the chain's own map and codes, ahead of the filter
         fused, res = sequence.step(index, frame, res, conf, log, ego) if sequence else (None, res)
+        view = volume.step(index, frame, res, fused, odometry, log) if volume else None       # on what the filter left, where it runs
         photo = out.photometric(frame, res, args, log) if args.photometric else None
         for stage in range(4):
             disp = res.disp[stage].squeeze(axis=[0, 1]).numpy()         # :114 (the uint8 cast is inside disparity_to_color)
@@ -712,10 +806,15 @@ def inference(model, left_imgs, right_imgs, args, log):
             written += out.write_stage(os.path.join(args.save_path, os.path.basename(frame.path)), color, ss, frame, 3, args, log, res, conf, photo, fused)
             if odometry and args.save_ego:
                 written += out.save_ego(os.path.splitext(os.path.join(args.save_path, os.path.basename(frame.path)))[0], frame, log, ego)
+            if view is not None:
+                written += out.save_tsdf(os.path.splitext(os.path.join(args.save_path, os.path.basename(frame.path)))[0], log, view)
     if odometry and args.save_poses is not None:
         odometry.write_poses(args.save_poses)
         log.info("Save poses = {}".format(args.save_poses))
         written.append(args.save_poses)
+    if volume and args.save_tsdf_ply is not None:
+        log.info("Save TSDF points = {}, vertices = {}".format(args.save_tsdf_ply, volume.write_ply(args.save_tsdf_ply)))
+        written.append(args.save_tsdf_ply)
     return written
 
 
@@ -758,6 +857,54 @@ class _Odometry:
             log.info("Egomotion: t = {:.4f} m, rotation = {:.4f} deg, pixels = {}, rms = {:.3f}, status = {}".format(
                 t, deg, int(n), rms, int(self.odometry.status[-1][0])))
         return ego
+
+
+class _Volume:
+    """--tsdf: the TsdfVolume of the run.  step() integrates one frame's stage-4 map behind the chain -- the fused map and its sigma
+    with --temporal -- under the chain's `keep` codes, with the pose of --poses or the accumulated one of --egomotion, expressed in
+    the frame of the first camera integrated; with --save_tsdf it returns the volume ray-cast into the frame's own pose.  A volume
+    that does not fit the device's free memory is an error before the first frame."""
+
+    def __init__(self, args, device, log):
+        import torch
+        from .geometry import read_kitti_poses
+        from .tsdf import TsdfVolume, volume_bytes
+        self.args, self.first = args, None
+        self.poses = None if args.egomotion else read_kitti_poses(args.poses)
+        origin, dims = tsdf_grid(args)
+        need, free = volume_bytes(dims, colour=True), torch.cuda.mem_get_info(device)[0]
+        if need > free:
+            raise RuntimeError(f"--tsdf: a volume of {dims[0]} x {dims[1]} x {dims[2]} voxels takes {need} bytes, the device has {free} free "
+                               "(a larger --tsdf_voxel or a smaller --tsdf_extent)")
+        self.volume = TsdfVolume(origin, args.tsdf_voxel, dims, mu0=args.tsdf_trunc, mu_d=args.tsdf_trunc_px, weight=args.tsdf_weight, colour=True,
+                                 min_disp=args.min_disp, max_depth=args.max_depth, device=device)
+        log.info("TSDF: volume {} x {} x {} voxels of {:g} m from ({:g}, {:g}, {:g}), {} bytes".format(*dims, args.tsdf_voxel, *origin, need))
+
+    def step(self, index, frame, res, fused, odometry, log):
+        import torch
+        from . import ops
+        a = self.args
+        pose = np.vstack([self.poses[index] if self.poses is not None else odometry.odometry.poses()[-1], [0.0, 0.0, 0.0, 1.0]])
+        if self.first is None:
+            self.first = pose
+        pose = np.linalg.solve(self.first, pose)[:3]        # camera -> the first camera integrated
+        disp = res.disp[3].as_subclass(torch.Tensor)
+        keep = out.merge_keep(res.keep[3] if res.keep is not None else None, frame.valid_left)
+        with torch.cuda.device(disp.device):
+            normals = None
+            if a.tsdf_sdf == "plane":
+                normals = ops.surface_normals(disp, frame.cam, mask=keep, min_disp=a.min_disp, max_depth=a.max_depth, max_jump=a.max_jump)[0]
+            sigma = None if fused is None else torch.sqrt(fused.var)
+            updated = self.volume.integrate(disp, frame.cam, pose, sigma=sigma, mask=keep, normals=normals,
+                                            rgb=out.rgb_on_device(frame.left, disp.device))
+            log.info("TSDF: voxels updated = {}".format(int(updated[0])))
+            if not a.save_tsdf:
+                return None
+            h, w = disp.shape[2:]
+            return self.volume.raycast(frame.cam, pose, h, w, z_near=max(a.tsdf_voxel, 0.5), weight=False, normals=False)
+
+    def write_ply(self, path):
+        return self.volume.write_ply(path, max_points=TSDF_MAX_POINTS)
 
 
 class _Sequence:
@@ -866,6 +1013,7 @@ def main(argv=None):
     post.check_photometric_arguments(parser, args, save=True)
     check_egomotion_arguments(parser, args)
     check_temporal_arguments(parser, args)
+    check_tsdf_arguments(parser, args)
     log = start_logging("lwsnet_amd.inference", args)
     model = load_model(args, log)
     if getattr(args, "split_bf16", False):

@@ -968,6 +968,174 @@ def egomotion(rgb_ref, disp_ref, rgb_cur, cameras, mask=None, init=None, levels=
     return EgoResult(pose, status, info, tr, rs)
 
 
+TSDF_WEIGHTS = {"unit": 0, "sigma": 1}                      # wmode of lws_tsdf_integrate
+
+
+def tsdf_volume_args(origin, voxel, dims):
+    """The validated (Gx, Gy, Gz, ox, oy, oz, vs) of a volume, in the order of the C calls: origin three finite numbers (the centre
+    of voxel (0, 0, 0)), voxel finite and > 0, dims = (Gx, Gy, Gz), each in 2 .. 4096 with a product below 2^31."""
+    if len(origin) != 3 or not all(math.isfinite(v) for v in origin):
+        raise ValueError(f"origin must be three finite numbers, got {origin}")
+    if len(dims) != 3:
+        raise ValueError(f"dims must be (Gx, Gy, Gz), got {dims}")
+    g = [_int_in(f"dims[{i}]", v, 2, 4096) for i, v in enumerate(dims)]
+    if g[0] * g[1] * g[2] >= 1 << 31:
+        raise ValueError(f"dims {tuple(g)}: a volume holds fewer than 2^31 voxels")
+    return (*g, *(float(v) for v in origin), _finite_pos("voxel", voxel))
+
+
+def tsdf_pose_rows(poses_c2w, B):
+    """Camera-to-world poses, float64 [3,4] (one for every image) or [B,3,4] -> the float32 [B,2,12] rows of lws_tsdf_integrate and
+    lws_tsdf_raycast: world -> camera, the inverse taken in float64 as geometry.relative_pose takes it, and camera -> world."""
+    import numpy as np
+    p = np.asarray(poses_c2w, np.float64)
+    if p.shape == (3, 4):
+        p = np.broadcast_to(p, (B, 3, 4))
+    if p.shape != (B, 3, 4) or not np.isfinite(p).all():
+        raise ValueError(f"poses must be finite camera-to-world [3,4] or [{B},3,4] float64 [R|t], got shape {p.shape}")
+    m = np.concatenate([p, np.broadcast_to(np.array([0.0, 0.0, 0.0, 1.0]), (B, 1, 4))], axis=1)
+    inv = np.stack([np.linalg.solve(m[b], np.eye(4)) for b in range(B)])
+    return np.stack([inv[:, :3].reshape(B, 12), m[:, :3].reshape(B, 12)], axis=1).astype(np.float32)
+
+
+def _tsdf_pose(pose, B, device):
+    if isinstance(pose, torch.Tensor) and pose.is_cuda:
+        return _tensor_of(pose, "pose", torch.float32, (B, 2, 12), device)
+    import numpy as np
+    p = np.asarray(pose.detach().cpu().numpy() if isinstance(pose, torch.Tensor) else pose)
+    if p.dtype != np.float32 or p.shape != (B, 2, 12) or not np.isfinite(p).all():
+        raise ValueError(f"pose must be the finite float32 [{B},2,12] of tsdf_pose_rows, got {p.dtype} {p.shape}")
+    return torch.from_numpy(np.ascontiguousarray(p)).to(device)
+
+
+def _tsdf_volume(T, Wt, C, g):
+    """The tensors of a volume of g = (Gx, Gy, Gz): T, Wt float32 [Gz,Gy,Gx], C None or uint8 [Gz,Gy,Gx,4], contiguous on one HIP
+    device (the calls write them in place, so nothing is copied)."""
+    shape = (g[2], g[1], g[0])
+    for name, t, dt, sh in (("T", T, torch.float32, shape), ("Wt", Wt, torch.float32, shape), ("C", C, torch.uint8, (*shape, 4))):
+        if t is None and name == "C":
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{name} must be a torch tensor on a HIP device (the volume has no CPU fallback)")
+        if t.dtype != dt or tuple(t.shape) != sh or not t.is_contiguous() or t.device != T.device:
+            raise ValueError(f"{name} must be a contiguous {str(dt).split('.')[-1]} {sh} tensor on {T.device}")
+    return T.device
+
+
+def _tsdf_integrate_args(sigma0, min_disp, max_depth, mu0, mu_d, sigma_min, weight, w_max):
+    """The validated scalar arguments of tsdf_integrate, in the order of the C call."""
+    if not (max_depth > 0):
+        raise ValueError(f"max_depth must be > 0 (inf allowed), got {max_depth}")
+    if not (w_max > 0):
+        raise ValueError(f"w_max must be > 0 (inf allowed), got {w_max}")
+    if weight not in TSDF_WEIGHTS:
+        raise ValueError(f"weight must be one of {sorted(TSDF_WEIGHTS)}, got {weight!r}")
+    return (_finite_nonneg("sigma0", sigma0), _finite_pos("min_disp", min_disp), float(max_depth), _finite_pos("mu0", mu0), _finite_nonneg("mu_d", mu_d),
+            _finite_pos("sigma_min", sigma_min), TSDF_WEIGHTS[weight], float(w_max))
+
+
+def tsdf_integrate(T, Wt, origin, voxel, disp, cameras, pose, C=None, sigma=None, mask=None, normals=None, rgb=None, sigma0=0.5, min_disp=1.0,
+                   max_depth=float("inf"), mu0=0.25, mu_d=0.0, sigma_min=0.05, weight="unit", w_max=float("inf"), updated=True):
+    """Integrates B frames into a TSDF volume, in place (include/lwsnet_tsdf.h, lws_tsdf_integrate).  T, Wt float32 [Gz,Gy,Gx] and
+    C uint8 [Gz,Gy,Gx,4] or None: the volume, whose voxel (0, 0, 0) has its centre at `origin` and whose voxels are `voxel` metres
+    wide; disp [B,1,H,W] float32; cameras: one Camera or a list of B; pose: tsdf_pose_rows(camera-to-world poses, B), or that block
+    as a float32 [B,2,12] device tensor; sigma: None (sigma0 px everywhere) or float32 [B,1,H,W]; mask: None or the uint8
+    lws_lr_check code map; normals: None (the distance along the ray) or the float32 [B,3,H,W] of surface_normals (the distance to
+    the pixel's tangent plane); rgb: the uint8 [B,H,W,3] images, required iff C is given.  Returns the voxels taken per frame, an
+    int64 [B] device tensor (None unless asked for)."""
+    if cameras is None:
+        raise ValueError("tsdf_integrate needs cameras")
+    g = tsdf_volume_args(origin, voxel, T.shape[::-1] if isinstance(T, torch.Tensor) and T.dim() == 3 else ())
+    scalars = _tsdf_integrate_args(sigma0, min_disp, max_depth, mu0, mu_d, sigma_min, weight, w_max)
+    dev = _tsdf_volume(T, Wt, C, g)
+    if (C is None) != (rgb is None):
+        raise ValueError("tsdf_integrate: rgb and C go together (a volume with colour needs the images, one without takes none)")
+    d, mask, cam = _geometry_inputs(disp, mask, cameras, scalars[1], scalars[2])
+    if d.device != dev:
+        raise ValueError(f"disp is on {d.device}, the volume on {dev}")
+    B, _, H, W = d.shape
+    if H * W >= 1 << 31 or max(H, W) > 1 << 24:
+        raise ValueError(f"disp is {H}x{W}: tsdf_integrate takes maps of fewer than 2^31 pixels and at most 2^24 a side")
+    if sigma is not None:
+        sigma = _tensor_of(sigma, "sigma", torch.float32, d.shape, dev)
+    if normals is not None:
+        normals = _tensor_of(normals, "normals", torch.float32, (B, 3, H, W), dev, " (what surface_normals returns)")
+    if rgb is not None:
+        rgb = _guide(rgb, d)
+    pose = _tsdf_pose(pose, B, dev)
+    upd = torch.empty((B,), device=dev, dtype=torch.int64) if updated else None
+    _call("lws_tsdf_integrate", dev, d, sigma, mask, normals, rgb, cam, pose, B, H, W, T, Wt, C, *g, *scalars, upd)
+    return upd
+
+
+TsdfView = namedtuple("TsdfView", ["disp", "weight", "normals"])
+TsdfView.__doc__ = """What tsdf_raycast returns: disp float32 [B,1,H,W], the disparity of the surface the pixel's ray meets, 0 where it
+meets none; weight float32 [B,1,H,W], the volume's weight there; normals float32 [B,3,H,W] in the camera's frame, the convention of
+surface_normals (weight and normals: None unless asked for)."""
+
+
+def _tsdf_w_min(w_min):
+    return _finite_nonneg("w_min", w_min)
+
+
+def tsdf_raycast(T, Wt, origin, voxel, cameras, pose, H, W, z_near=0.5, step=None, nsteps=None, z_far=None, w_min=0.0, weight=True, normals=True):
+    """Casts B views of H x W from a TSDF volume (include/lwsnet_tsdf.h, lws_tsdf_raycast).  cameras: one Camera or a list of B
+    (B = 1 for one Camera and one pose); pose as tsdf_integrate takes it; the rays are sampled at the camera depths
+    z_near + k * step, k < nsteps.  step defaults to half a voxel; nsteps to what reaches z_far, and z_far to z_near plus the volume's
+    diagonal, which no ray that starts inside the volume outruns.  Returns a TsdfView."""
+    import numpy as np
+    from .geometry import Camera, camera_rows
+    g = tsdf_volume_args(origin, voxel, T.shape[::-1] if isinstance(T, torch.Tensor) and T.dim() == 3 else ())
+    dev = _tsdf_volume(T, Wt, None, g)
+    if cameras is None:
+        raise ValueError("tsdf_raycast needs cameras")
+    if isinstance(pose, torch.Tensor) or (isinstance(pose, np.ndarray) and pose.ndim == 3):
+        B = int(pose.shape[0])
+    else:
+        raise ValueError("pose must be the float32 [B,2,12] of tsdf_pose_rows")
+    if not isinstance(cameras, Camera) and len(cameras) != B:
+        raise ValueError(f"cameras must be one Camera or a list of {B}")
+    B = _int_in("B", B, 1, 65535)
+    H, W = _int_in("H", H, 1, 1 << 24), _int_in("W", W, 1, 1 << 24)
+    if H * W >= 1 << 31:
+        raise ValueError(f"{H}x{W}: tsdf_raycast takes views of fewer than 2^31 pixels")
+    z_near = _finite_pos("z_near", z_near)
+    step = _finite_pos("step", 0.5 * g[6] if step is None else step)
+    if nsteps is None:
+        far = z_near + g[6] * math.sqrt(sum((n - 1) ** 2 for n in g[:3])) if z_far is None else _finite_pos("z_far", z_far)
+        nsteps = min(max(int(math.ceil((far - z_near) / step)) + 1, 2), 65535)
+    nsteps = _int_in("nsteps", nsteps, 2, 65535)
+    w_min = _tsdf_w_min(w_min)
+    cam = torch.from_numpy(camera_rows(cameras, B)).to(dev)
+    pose = _tsdf_pose(pose, B, dev)
+    d = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32)
+    wt = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32) if weight else None
+    n = torch.empty((B, 3, H, W), device=dev, dtype=torch.float32) if normals else None
+    _call("lws_tsdf_raycast", dev, T, Wt, *g, cam, pose, B, H, W, z_near, step, nsteps, w_min, d, wt, n)
+    return TsdfView(d, wt, n)
+
+
+TsdfPoints = namedtuple("TsdfPoints", ["points", "vnormals", "counts"])
+TsdfPoints.__doc__ = """What tsdf_points returns: points uint8 [max_points,16], the records of point_cloud (geometry.POINT_DTYPE) in world
+coordinates; vnormals float32 [max_points,4] {n.x, n.y, n.z, 0} (None unless asked for); counts, an int64 [1] device tensor: the
+crossings found, of which the first min(counts, max_points) records are written and the rest is unwritten."""
+
+
+def tsdf_points(T, Wt, origin, voxel, max_points, C=None, w_min=0.0, with_normals=True):
+    """The zero crossings of a TSDF volume on the edges of its voxel grid as oriented, coloured points in a fixed order
+    (include/lwsnet_tsdf.h, lws_tsdf_points).  max_points: the capacity in records.  Returns a TsdfPoints."""
+    g = tsdf_volume_args(origin, voxel, T.shape[::-1] if isinstance(T, torch.Tensor) and T.dim() == 3 else ())
+    max_points = _int_in("max_points", max_points, 1, (1 << 31) - 1)
+    w_min = _tsdf_w_min(w_min)
+    dev = _tsdf_volume(T, Wt, C, g)
+    work = _workspace("lws_tsdf_points_workspace", dev, g[1], g[2])
+    points = torch.empty((max_points, 16), device=dev, dtype=torch.uint8)
+    vn = torch.empty((max_points, 4), device=dev, dtype=torch.float32) if with_normals else None
+    counts = torch.empty((1,), device=dev, dtype=torch.int64)
+    _call("lws_tsdf_points", dev, T, Wt, C, *g, w_min, ctypes.c_int64(max_points), work, points, vn, counts)
+    return TsdfPoints(points, vn, counts)
+
+
 SpeckleResult = namedtuple("SpeckleResult", ["disp", "mask", "labels", "counts"])
 SpeckleResult.__doc__ = """What speckle_filter returns: the filtered (filled if asked) maps float32 [B,1,H,W], the uint8 code map (1 kept,
 3 speckle, the input code or 0 for an invalid pixel), labels int32 [B,1,H,W] (None unless want_labels) and counts, an int64

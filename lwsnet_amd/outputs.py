@@ -399,6 +399,13 @@ def save_ego(stem, frame, log, ego):
     return [stem + "_ego.png"]
 
 
+def save_tsdf(stem, log, view):
+    """--save_tsdf: <stem>_tsdf.png, the volume ray-cast into the frame's own pose (an ops.TsdfView), coloured as the stage maps."""
+    io.save_png(stem + "_tsdf.png", io.disparity_to_color(view.disp[0, 0].cpu().numpy()))
+    log.info("Save TSDF view = {}_tsdf.png".format(stem))
+    return [stem + "_tsdf.png"]
+
+
 # the code maps beside a colour file: (the ChainResult's field, suffix, log line, the codes whose shares it gives)
 CODE_MASKS = (("lr_masks", "_lr.png", "LR check: density = {:.4f}\t\tSave mask = {}", (1,)),
               ("occ_masks", "_occ.png", "Occlusion check: density = {:.4f}\t\tSave mask = {}", (1,)),
