@@ -30,7 +30,6 @@ constexpr int kTile = kThreads * kPerThread;                // pixels of a workg
 constexpr int kSums = 29;
 constexpr int kState = 16;                                  // doubles per image: M[12], |delta| of the last step taken, steps taken, status
 constexpr int kTrace = 48;
-constexpr int kMaxDim = 1 << 24;                            // (float)(W - 2) and (float)(H - 2) are exact
 constexpr int kMaxLevels = 8;
 constexpr double kSeriesBelow = 0.05;
 constexpr double kMinStep2 = 0x1p-46;
@@ -110,10 +109,7 @@ __global__ __launch_bounds__(kThreads) void k_ego_down(DownArgs a)
         bool ok = !m || (m[0] == 1 && m[1] == 1 && m[a.Ws] == 1 && m[a.Ws + 1] == 1);
         ok = ok && __builtin_isfinite(t00) && t00 >= a.min_disp && __builtin_isfinite(t01) && t01 >= a.min_disp &&
              __builtin_isfinite(t10) && t10 >= a.min_disp && __builtin_isfinite(t11) && t11 >= a.min_disp;
-        float mx = t00, mn = t00;
-        mx = t01 > mx ? t01 : mx, mx = t10 > mx ? t10 : mx, mx = t11 > mx ? t11 : mx;
-        mn = t01 < mn ? t01 : mn, mn = t10 < mn ? t10 : mn, mn = t11 < mn ? t11 : mn;
-        out = ok && mx - mn <= a.max_jump ? mean : 0.0f;
+        out = ok && jump4(t00, t01, t10, t11) <= a.max_jump ? mean : 0.0f;
     }
     a.dst[which][(int64_t)b * Hd * Wd + p] = out;
 }
@@ -133,9 +129,7 @@ struct NormalArgs {
 template <typename Fn>
 __device__ __forceinline__ float blend(Fn f, int j0, int i0, float a, float b)
 {
-    const float t00 = f(j0, i0), t01 = f(j0, i0 + 1), t10 = f(j0 + 1, i0), t11 = f(j0 + 1, i0 + 1);
-    const float top = t00 + a * (t01 - t00), bot = t10 + a * (t11 - t10);
-    return top + b * (bot - top);
+    return blend4(f(j0, i0), f(j0, i0 + 1), f(j0 + 1, i0), f(j0 + 1, i0 + 1), a, b);
 }
 
 // grid (ceil(H * W / 1024), B): thread t takes the pixels tile * 1024 + k * 256 + t, k = 0 .. 3
@@ -144,9 +138,8 @@ __global__ __launch_bounds__(kThreads) void k_ego_normal(NormalArgs a)
     __shared__ double s_w[kThreads / 64][kSums];
     const int b = blockIdx.y, t = threadIdx.x, H = a.H, W = a.W;
     const int64_t npix = (int64_t)H * W, img = (int64_t)b * npix;
-    const Cam c0 = load_cam(a.cam, b);
-    const float fx = c0.fx * a.scale, fy = c0.fy * a.scale;
-    const float cx = (c0.cx + 0.5f) * a.scale - 0.5f, cy = (c0.cy + 0.5f) * a.scale - 0.5f, fb = c0.fb;
+    const Cam c0 = load_cam(a.cam, b);                      // the full-resolution camera; c: this level's
+    const Cam c = {c0.fx * a.scale, c0.fy * a.scale, (c0.cx + 0.5f) * a.scale - 0.5f, (c0.cy + 0.5f) * a.scale - 0.5f, c0.fb};
     float Mf[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i) Mf[i] = (float)a.M[(int64_t)a.m_stride * b + i];
@@ -164,13 +157,12 @@ __global__ __launch_bounds__(kThreads) void k_ego_normal(NormalArgs a)
         bool use = (!a.mask || a.mask[img + p] == 1) && __builtin_isfinite(d) && d >= a.min_disp;
         float r = 0.0f, w = 0.0f, J[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
         if (use) {
-            const float z = fb / d;
-            const float X = (((float)x - cx) * z) / fx, Y = (((float)y - cy) * z) / fy;
-            const float Qx = ((Mf[0] * X + Mf[1] * Y) + Mf[2] * z) + Mf[3];
-            const float Qy = ((Mf[4] * X + Mf[5] * Y) + Mf[6] * z) + Mf[7];
-            const float Qz = ((Mf[8] * X + Mf[9] * Y) + Mf[10] * z) + Mf[11];
-            const float u = (fx * Qx) / Qz + cx, v = (fy * Qy) / Qz + cy;
-            use = Qz > 0.0f && big && u >= 1.0f && u <= (float)(W - 2) && v >= 1.0f && v <= (float)(H - 2);
+            const float z = c.fb / d;
+            const float X = back_x(c, x, z), Y = back_y(c, y, z);
+            const float Qx = row_dot(Mf, 0, X, Y, z), Qy = row_dot(Mf, 1, X, Y, z), Qz = row_dot(Mf, 2, X, Y, z);
+            float u, v;
+            const bool inside = project(c, Qx, Qy, Qz, H, W, 1, u, v);      // margin 1: the taps' central differences lie inside
+            use = Qz > 0.0f && big && inside;
             if (use) {
                 const int i0 = min((int)floorf(u), W - 3), j0 = min((int)floorf(v), H - 3);      // 1 <= i0 <= W - 3, 1 <= j0 <= H - 3
                 const float fa = u - (float)i0, fbl = v - (float)j0;
@@ -180,7 +172,7 @@ __global__ __launch_bounds__(kThreads) void k_ego_normal(NormalArgs a)
                 const float rr = Ic - a.grey_ref[img + p];
                 const float ar = fabsf(rr);
                 const float ww = ar <= a.huber ? 1.0f : a.huber / ar;
-                const float ju = (gx * fx) / Qz, jv = (gy * fy) / Qz;
+                const float ju = (gx * c.fx) / Qz, jv = (gy * c.fy) / Qz;
                 const float jz = -((ju * Qx + jv * Qy) / Qz);
                 const float j3 = jz * Qy - jv * Qz, j4 = ju * Qz - jz * Qx, j5 = jv * Qx - ju * Qy;
                 use = __builtin_isfinite(rr) && __builtin_isfinite(gx) && __builtin_isfinite(gy) && __builtin_isfinite(ju) &&
@@ -210,13 +202,8 @@ __global__ __launch_bounds__(kThreads) void k_ego_normal(NormalArgs a)
         }
         if (a.resid) a.resid[img + p] = r;
     }
-    wave_sum_n(acc);
-    if ((t & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < kSums; ++k) s_w[t >> 6][k] = acc[k];
-    }
-    __syncthreads();
-    if (t < kSums) a.partials[((int64_t)b * gridDim.x + blockIdx.x) * kSums + t] = sum4(s_w[0][t], s_w[1][t], s_w[2][t], s_w[3][t]);
+    block_sum_n(acc, s_w);
+    if (t < kSums) a.partials[((int64_t)b * gridDim.x + blockIdx.x) * kSums + t] = block_total(s_w, t);
 }
 
 struct SolveArgs {
@@ -247,14 +234,9 @@ __global__ __launch_bounds__(kThreads) void k_ego_solve(SolveArgs a)
 #pragma unroll
         for (int k = 0; k < kSums; ++k) acc[k] += part[(int64_t)j * kSums + k];
     }
-    wave_sum_n(acc);
-    if ((t & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < kSums; ++k) s_w[t >> 6][k] = acc[k];
-    }
-    __syncthreads();
+    block_sum_n(acc, s_w);
     if (t < kSums) {
-        const double v = sum4(s_w[0][t], s_w[1][t], s_w[2][t], s_w[3][t]);
+        const double v = block_total(s_w, t);
         s_s[t] = v;
         if (a.mode == kModeSums) a.sums[(int64_t)b * kSums + t] = v;
     }
@@ -270,11 +252,11 @@ __global__ __launch_bounds__(kThreads) void k_ego_solve(SolveArgs a)
         a.status[b] = status;
         double *info = a.info + 4 * (int64_t)b;
         info[0] = n, info[1] = n > 0.0 ? sqrt(s_s[27] / n) : 0.0, info[2] = st[12], info[3] = st[13];
-        float *po = a.pose + 24 * (int64_t)b;
+        float *po = a.pose + kPoseFloats * (int64_t)b, *pi = po + kPoseInverse;
         for (int i = 0; i < 12; ++i) po[i] = (float)s_M[i];
         for (int i = 0; i < 3; ++i) {                       // the inverse: R^T, 0 - R^T t (so that a zero t gives +0, not -0)
-            for (int j = 0; j < 3; ++j) po[12 + 4 * i + j] = (float)s_M[4 * j + i];
-            po[12 + 4 * i + 3] = (float)(0.0 - ((s_M[i] * s_M[3] + s_M[4 + i] * s_M[7]) + s_M[8 + i] * s_M[11]));
+            for (int j = 0; j < 3; ++j) pi[4 * i + j] = (float)s_M[4 * j + i];
+            pi[4 * i + 3] = (float)(0.0 - ((s_M[i] * s_M[3] + s_M[4 + i] * s_M[7]) + s_M[8 + i] * s_M[11]));
         }
         return;
     }
@@ -381,20 +363,11 @@ __global__ __launch_bounds__(kThreads) void k_ego_solve(SolveArgs a)
     }
 }
 
-int check_shape(const char *who, int B, int H, int W)
-{
-    LWS_CHECK_RC(check_image_shape(who, B, H, W, 31));
-    LWS_CHECK_ARG(H <= kMaxDim && W <= kMaxDim, "%s: H=%d W=%d exceed %d (pixel coordinates are exact floats)", who, H, W, kMaxDim);
-    return LWS_OK;
-}
-
 int check_levels(const char *who, int levels)
 {
     LWS_CHECK_ARG(levels >= 1 && levels <= kMaxLevels, "%s: levels %d outside 1..%d", who, levels, kMaxLevels);
     return LWS_OK;
 }
-
-bool finite_pos(float x) { return x > 0.0f && finite_nonneg(x); }
 
 int launch_normal(const NormalArgs &n, int B, hipStream_t st)
 {
@@ -416,7 +389,7 @@ extern "C" {
 int64_t lws_egomotion_workspace(int B, int H, int W, int levels)
 {
     const char *who = "egomotion_workspace";
-    LWS_CHECK_RC(check_shape(who, B, H, W));
+    LWS_CHECK_RC(check_view_shape(who, B, H, W));
     LWS_CHECK_RC(check_levels(who, levels));
     return layout_of(B, H, W, levels).total;
 }
@@ -428,7 +401,7 @@ int lws_ego_normal(const float *grey_ref, const float *disp_ref, const uint8_t *
     const char *who = "ego_normal";
     LWS_CHECK_ARG(grey_ref && disp_ref && grey_cur && cam && M, "%s: grey_ref, disp_ref, grey_cur, cam and M must not be null", who);
     LWS_CHECK_ARG(workspace && sums, "%s: workspace and sums must not be null", who);
-    LWS_CHECK_RC(check_shape(who, B, H, W));
+    LWS_CHECK_RC(check_view_shape(who, B, H, W));
     LWS_CHECK_ARG(level >= 0 && level < kMaxLevels, "%s: level %d outside 0..%d", who, level, kMaxLevels - 1);
     LWS_CHECK_ARG(aligned(grey_ref, 4) && aligned(disp_ref, 4) && aligned(grey_cur, 4) && aligned(cam, 4) && aligned(terms, 4) &&
                       aligned(M, 8) && aligned(sums, 8) && aligned(workspace, 8),
@@ -462,7 +435,7 @@ int lws_egomotion(const uint8_t *rgb_ref, const float *disp_ref, const uint8_t *
     const char *who = "egomotion";
     LWS_CHECK_ARG(rgb_ref && disp_ref && rgb_cur && cam, "%s: rgb_ref, disp_ref, rgb_cur and cam must not be null", who);
     LWS_CHECK_ARG(workspace && pose && status && info, "%s: workspace, pose, status and info must not be null", who);
-    LWS_CHECK_RC(check_shape(who, B, H, W));
+    LWS_CHECK_RC(check_view_shape(who, B, H, W));
     LWS_CHECK_RC(check_levels(who, levels));
     LWS_CHECK_ARG(iters >= 1 && iters <= 64, "%s: iters %d outside 1..64", who, iters);
     LWS_CHECK_ARG(aligned(disp_ref, 4) && aligned(cam, 4) && aligned(init, 4) && aligned(pose, 4) && aligned(status, 4) && aligned(resid, 4) &&

@@ -4,14 +4,14 @@
 // Determinism: no atomics; the point cloud is packed in raster order by a per-row count, a per-image scan and a per-row scatter
 // whose ranks come from wave ballots, so an image gives the same bytes in any batch.  0 bytes of scratch.
 #include "lws_geomkit.h"
+#include "lws_packkit.h"
 
 namespace lws {
 
 namespace {
 
 using namespace geomkit;
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
+using namespace packkit;                                    // kThreads, kWaves
 
 // KITTI's 16-bit PNG value of v (> 0): v * 256 rounded half to even, clamped to 0 .. 65535
 __device__ __forceinline__ uint16_t to_u16x256(float v)
@@ -113,51 +113,29 @@ __global__ __launch_bounds__(kThreads) void k_pc_count(const float *__restrict__
         float d[4], z[4];
         n += __builtin_popcount(quad_valid(dp, mk, vd, vm, q, W, c, min_disp, max_depth, d, z));
     }
-    n = wave_sum(n);
-    if ((t & 63) == 0) s_n[t >> 6] = n;
-    __syncthreads();
-    if (t == 0) row_count[(int64_t)b * H + y] = sum4(s_n[0], s_n[1], s_n[2], s_n[3]);
+    n = block_sum(n, s_n);
+    if (t == 0) row_count[(int64_t)b * H + y] = n;
 }
 
-// grid (B), 256 threads: row_count[b][.] -> its exclusive scan, in place; counts[b] = the total.
+// grid (B), 256 threads: row_count[b][.] -> its exclusive scan, in place (packkit::row_scan); counts[b] = the total.
 __global__ __launch_bounds__(kThreads) void k_pc_scan(int *__restrict__ row, int H, int64_t *__restrict__ counts)
 {
     __shared__ int s_w[kWaves];
-    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    int *r = row + (int64_t)b * H;
-    int carry = 0;                                          // uniform: the rows before the chunk
-    for (int64_t y0 = 0; y0 < H; y0 += kThreads) {
-        const int64_t y = y0 + t;
-        const int v = y < H ? r[y] : 0;
-        int inc = v;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int u = __shfl_up(inc, o, 64);
-            inc += lane >= o ? u : 0;
-        }
-        if (lane == 63) s_w[wave] = inc;
-        __syncthreads();
-        int before = carry, total = carry;
-        for (int w = 0; w < kWaves; ++w) {
-            before += w < wave ? s_w[w] : 0;
-            total += s_w[w];
-        }
-        if (y < H) r[y] = before + inc - v;
-        carry = total;
-        __syncthreads();                                    // s_w is rewritten by the next chunk
-    }
-    if (t == 0) counts[b] = carry;
+    const int b = blockIdx.x;
+    const int total = row_scan(row + (int64_t)b * H, H, s_w);
+    if (threadIdx.x == 0) counts[b] = total;
 }
 
 // grid (H, B), 256 threads: the valid pixels of row y of image b, in raster order, to points + (b * H * W + row_off[b][y]) * 16 B.
-// A chunk is 256 quads; in it, the rank of pixel i of quad q is the valid pixels of the chunk's earlier quads (four wave ballots,
-// one per pixel slot, plus popcounts; the earlier waves' totals through LDS) plus the valid pixels of q before i.
+// A chunk is 256 quads; in it, the rank of pixel i of quad q is the valid pixels of the chunk's earlier quads (packkit::block_rank,
+// one bit slot per pixel) plus the valid pixels of q before i.
 __global__ __launch_bounds__(kThreads) void k_pc_scatter(const float *__restrict__ disp, const uint8_t *__restrict__ mask,
                                                         const uint8_t *__restrict__ rgb, const float *__restrict__ cam, int H, int W,
                                                         float min_disp, float max_depth, const int *__restrict__ row_off,
                                                         uint4 *__restrict__ points)
 {
     __shared__ int s_w[kWaves];
-    const int y = blockIdx.x, b = blockIdx.y, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int y = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
     const int64_t row = ((int64_t)b * H + y) * W;
     const float *dp = disp + row;
     const uint8_t *mk = mask ? mask + row : nullptr;
@@ -165,29 +143,13 @@ __global__ __launch_bounds__(kThreads) void k_pc_scatter(const float *__restrict
     const bool vd = aligned(dp, 16), vm = aligned(mk, 4), vc = aligned(cp, 4);
     const Cam c = load_cam(cam, b);
     uint4 *out = points + (int64_t)b * H * W + row_off[(int64_t)b * H + y];
-    const unsigned long long below = (1ull << lane) - 1ull;
-    const float fy = (float)y - c.cy;
     const int nq = (W + 3) >> 2;
     int carry = 0;                                          // uniform: the valid pixels of the earlier chunks
     for (int q0 = 0; q0 < nq; q0 += kThreads) {
         const int q = q0 + t;
         float d[4], z[4];
         const unsigned bits = q < nq ? quad_valid(dp, mk, vd, vm, q, W, c, min_disp, max_depth, d, z) : 0u;
-        int rank = 0, wave_n = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const unsigned long long m = __ballot((bits >> i) & 1u);
-            rank += __popcll(m & below);
-            wave_n += __popcll(m);
-        }
-        if (lane == 0) s_w[wave] = wave_n;
-        __syncthreads();
-        int total = carry;
-        for (int w = 0; w < kWaves; ++w) {
-            rank += w < wave ? s_w[w] : 0;
-            total += s_w[w];
-        }
-        rank += carry;
+        int rank = block_rank<4>(bits, s_w, carry);
         if (bits) {
             const int x = 4 * q;
             uint8_t px[12];
@@ -206,14 +168,12 @@ __global__ __launch_bounds__(kThreads) void k_pc_scatter(const float *__restrict
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 if (!((bits >> i) & 1u)) continue;
-                const float X = (((float)(x + i) - c.cx) * z[i]) / c.fx;
-                const float Y = (fy * z[i]) / c.fy;
+                const float X = back_x(c, x + i, z[i]), Y = back_y(c, y, z[i]);
                 const unsigned col = (unsigned)px[3 * i] | ((unsigned)px[3 * i + 1] << 8) | ((unsigned)px[3 * i + 2] << 16) | (255u << 24);
                 out[rank] = make_uint4(__float_as_uint(X), __float_as_uint(Y), __float_as_uint(z[i]), col);
                 ++rank;
             }
         }
-        carry = total;
         __syncthreads();                                    // s_w is rewritten by the next chunk
     }
 }

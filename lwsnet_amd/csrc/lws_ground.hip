@@ -420,7 +420,7 @@ int check_hist_args(const char *who, const float *disp, int B, int H, int W, flo
 {
     LWS_CHECK_ARG(disp, "%s: disp is null", who);
     LWS_CHECK_RC(check_image_shape(who, B, H, W, 31));
-    LWS_CHECK_ARG(min_disp > 0.0f && finite_nonneg(min_disp), "%s: min_disp must be finite and > 0, got %g", who, (double)min_disp);
+    LWS_CHECK_ARG(finite_pos(min_disp), "%s: min_disp must be finite and > 0, got %g", who, (double)min_disp);
     LWS_CHECK_ARG(sub >= 1 && sub <= kMaxSub, "%s: sub %d outside 1..%d", who, sub, kMaxSub);
     LWS_CHECK_ARG(nbins >= 1 && nbins <= kMaxBins && nbins <= 256 * sub, "%s: nbins %d outside 1..min(%d, 256 * sub = %d)", who, nbins,
                   kMaxBins, 256 * sub);
@@ -547,7 +547,7 @@ int lws_bev_grid(const float *disp, const float *cam, const uint8_t *codes, cons
     LWS_CHECK_ARG(!hmax || (code_bits & 0x33) == 0,
                   "bev_grid: code_bits %d selects a code other than 2 and 3, whose heights are not positive; hmax cannot be requested", code_bits);
     LWS_CHECK_ARG(x_min >= -3.4028234663852886e38f && x_min <= 3.4028234663852886e38f, "bev_grid: x_min must be finite, got %g", (double)x_min);
-    LWS_CHECK_ARG(cell > 0.0f && finite_nonneg(cell), "bev_grid: cell must be finite and > 0, got %g", (double)cell);
+    LWS_CHECK_ARG(finite_pos(cell), "bev_grid: cell must be finite and > 0, got %g", (double)cell);
     LWS_CHECK_ARG(Gx >= 1 && Gx <= kMaxGrid && Gz >= 1 && Gz <= kMaxGrid, "bev_grid: grid Gx=%d Gz=%d outside 1..%d", Gx, Gz, kMaxGrid);
     const int64_t px = (int64_t)B * H * W, cells = (int64_t)B * Gz * Gx;
     const Buf bufs[] = {{count, 4 * cells, "count"}, {hmax, 4 * cells, "hmax"}, {disp, 4 * px, "disp"}, {cam, 20 * (int64_t)B, "cam"},

@@ -10,14 +10,14 @@
 //   k_mesh_scatter  one workgroup per row y: ranks the pixels of rows y and y + 1 and the faces of cell row y, writes row y's records
 // 0 bytes of scratch.
 #include "lws_geomkit.h"
+#include "lws_packkit.h"
 
 namespace lws {
 
 namespace {
 
 using namespace geomkit;
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
+using namespace packkit;                // kThreads, kWaves
 constexpr int kTW = 64;                 // tile width: one wave = 64 consecutive pixels of a row
 constexpr int kTH = 16;                 // tile height: four rows per wave
 constexpr int kPW = kTW + 2;            // the tile and its halo
@@ -55,8 +55,8 @@ __global__ __launch_bounds__(kThreads) void k_normals(const float *__restrict__ 
         const bool ok = in && (!mk || mk[pix] == 1);
         float z;
         const bool v = valid_z(d, ok, c.fb, min_disp, max_depth, z);
-        s_x[i] = (((float)x - c.cx) * z) / c.fx;
-        s_y[i] = (((float)y - c.cy) * z) / c.fy;
+        s_x[i] = back_x(c, x, z);
+        s_y[i] = back_y(c, y, z);
         s_z[i] = z;
         s_d[i] = v ? d : nan;
     }
@@ -194,30 +194,12 @@ __device__ __forceinline__ unsigned cell_faces(const float t[5], const float u[5
     return f;
 }
 
-// The rank of a thread's first set bit among the set bits of the workgroup's threads in thread order (N bit slots per thread: one
-// wave ballot per slot, the earlier waves' totals through LDS row s_w[kWaves]), plus `carry`; total = carry + all of them.  Every
-// thread of the workgroup calls it; the caller synchronises before s_w is reused.
-template <int N>
-__device__ __forceinline__ int wave_rank(unsigned bits, int lane, int &wave_n)
-{
-    const unsigned long long below = (1ull << lane) - 1ull;
-    int rank = 0;
-    wave_n = 0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const unsigned long long m = __ballot((bits >> i) & 1u);
-        rank += __popcll(m & below);
-        wave_n += __popcll(m);
-    }
-    return rank;
-}
-
 // grid (H, B), 256 threads: vertices of row y -> rows[0][b * H + y], faces of cell row y -> rows[1][b * H + y].
 __global__ __launch_bounds__(kThreads) void k_mesh_count(const float *__restrict__ disp, const uint8_t *__restrict__ mask,
                                                         const float *__restrict__ cam, int H, int W, float min_disp, float max_depth,
                                                         float max_jump, int *__restrict__ vrow, int *__restrict__ frow)
 {
-    __shared__ int s_n[2][kWaves];
+    __shared__ int s_n[kWaves][2];
     const int y = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
     const RowPair r = row_pair(disp, mask, b, y, H, W);
     const Cam c = load_cam(cam, b);
@@ -230,40 +212,18 @@ __global__ __launch_bounds__(kThreads) void k_mesh_count(const float *__restrict
         penta(r.d1, r.m1, r.vd1, r.vm1, q, W, c, min_disp, max_depth, d1, z);
         n[1] += __builtin_popcount(cell_faces(d0, d1, max_jump, diag));
     }
-    wave_sum_n(n);
-    if ((t & 63) == 0) s_n[0][t >> 6] = n[0], s_n[1][t >> 6] = n[1];
-    __syncthreads();
-    if (t < 2) (t ? frow : vrow)[(int64_t)b * H + y] = sum4(s_n[t][0], s_n[t][1], s_n[t][2], s_n[t][3]);
+    block_sum_n(n, s_n);
+    if (t < 2) (t ? frow : vrow)[(int64_t)b * H + y] = block_total(s_n, t);
 }
 
-// grid (B, 2), 256 threads: the row counts of image b (blockIdx.y: 0 = vertices, 1 = faces) -> their exclusive scan, in place;
-// counts[b][blockIdx.y] = the total.
+// grid (B, 2), 256 threads: the row counts of image b (blockIdx.y: 0 = vertices, 1 = faces) -> their exclusive scan, in place
+// (packkit::row_scan); counts[b][blockIdx.y] = the total.
 __global__ __launch_bounds__(kThreads) void k_mesh_scan(int *__restrict__ vrow, int *__restrict__ frow, int H, int64_t *__restrict__ counts)
 {
     __shared__ int s_w[kWaves];
-    const int b = blockIdx.x, which = blockIdx.y, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    int *r = (which ? frow : vrow) + (int64_t)b * H;
-    int carry = 0;                                          // uniform: the rows before the chunk
-    for (int64_t y0 = 0; y0 < H; y0 += kThreads) {
-        const int64_t y = y0 + t;
-        const int v = y < H ? r[y] : 0;
-        int inc = v;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int u = __shfl_up(inc, o, 64);
-            inc += lane >= o ? u : 0;
-        }
-        if (lane == 63) s_w[wave] = inc;
-        __syncthreads();
-        int before = carry, total = carry;
-        for (int w = 0; w < kWaves; ++w) {
-            before += w < wave ? s_w[w] : 0;
-            total += s_w[w];
-        }
-        if (y < H) r[y] = before + inc - v;
-        carry = total;
-        __syncthreads();                                    // s_w is rewritten by the next chunk
-    }
-    if (t == 0) counts[2 * (int64_t)b + which] = carry;
+    const int b = blockIdx.x, which = blockIdx.y;
+    const int total = row_scan((which ? frow : vrow) + (int64_t)b * H, H, s_w);
+    if (threadIdx.x == 0) counts[2 * (int64_t)b + which] = total;
 }
 
 struct MeshOut {
@@ -297,7 +257,6 @@ __global__ __launch_bounds__(kThreads) void k_mesh_scatter(const float *__restri
     uint4 *pts = o.points + b * plane;
     float4 *vnr = o.vnormals ? o.vnormals + b * plane : nullptr;
     int32_t *fc = o.faces + ((int64_t)b * 2 * (H - 1) * (W - 1) + frow[brow]) * 3;
-    const float fy = (float)y - c.cy;
     const int nq = (W + 3) >> 2;
     int carry[3] = {voff0, voff1, 0};                       // uniform: the index of the chunk's first vertex of each row, its first face
     for (int q0 = 0; q0 < nq; q0 += kThreads) {
@@ -310,21 +269,13 @@ __global__ __launch_bounds__(kThreads) void k_mesh_scatter(const float *__restri
             fbits = cell_faces(d0, d1, max_jump, diag);
         }
         int wn[3], rank[3];
-        rank[0] = wave_rank<4>(bits0, lane, wn[0]);
-        rank[1] = wave_rank<4>(bits1, lane, wn[1]);
-        rank[2] = wave_rank<8>(fbits, lane, wn[2]);
+        rank[0] = wave_rank<4>(bits0, wn[0]);
+        rank[1] = wave_rank<4>(bits1, wn[1]);
+        rank[2] = wave_rank<8>(fbits, wn[2]);
         if (lane == 0) s_w[0][wave] = wn[0], s_w[1][wave] = wn[1], s_w[2][wave] = wn[2];
-        __syncthreads();
+        __syncthreads();                                    // (one barrier for the three ranks)
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            int total = carry[k];
-            rank[k] += carry[k];
-            for (int w = 0; w < kWaves; ++w) {
-                rank[k] += w < wave ? s_w[k][w] : 0;
-                total += s_w[k][w];
-            }
-            carry[k] = total;
-        }
+        for (int k = 0; k < 3; ++k) rank[k] = add_earlier_waves(rank[k], s_w[k], carry[k]);
         const int x = 4 * q;
         if (q < nq && ix) {
             int v[4];
@@ -361,8 +312,7 @@ __global__ __launch_bounds__(kThreads) void k_mesh_scatter(const float *__restri
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 if (!((bits0 >> i) & 1u)) continue;
-                const float X = (((float)(x + i) - c.cx) * z[i]) / c.fx;
-                const float Y = (fy * z[i]) / c.fy;
+                const float X = back_x(c, x + i, z[i]), Y = back_y(c, y, z[i]);
                 const unsigned col = (unsigned)px[3 * i] | ((unsigned)px[3 * i + 1] << 8) | ((unsigned)px[3 * i + 2] << 16) | (255u << 24);
                 pts[at] = make_uint4(__float_as_uint(X), __float_as_uint(Y), __float_as_uint(z[i]), col);
                 if (np) vnr[at] = make_float4(n3[0][i], n3[1][i], n3[2][i], 0.0f);

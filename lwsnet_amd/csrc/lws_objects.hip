@@ -30,7 +30,7 @@
 
 #include "lws_cclkit.h"
 #include "lws_geomkit.h"
-#include "lws_opkit.h"
+#include "lws_packkit.h"
 #include "lws_takekit.h"
 
 namespace lws {
@@ -40,8 +40,7 @@ namespace {
 using namespace geomkit;
 using namespace takekit;                    // the limits, Item / load_item, Rule / bin_of, u16f
 using namespace cclkit;
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
+using namespace packkit;                    // kThreads, kWaves, block_scan
 constexpr int kTK = 32, kTS = 64;           // the tile of k_ob_tile: rows (bins) x columns (strips)
 constexpr int kTile = kTK * kTS;
 constexpr int kMaxCells = 1 << 22;          // S * nbins: the workspace stays below 286 MB per image
@@ -54,16 +53,7 @@ enum { R_N = 0, R_X0, R_X1, R_Y0, R_Y1, R_CELLS, R_SQ, R_KEY = 8, R_KR = 14, R_N
 typedef unsigned long long u64;
 typedef unsigned u32;
 
-// The monotone key of a float: a < b as floats (-0.0f < +0.0f) iff key(a) < key(b) as unsigned; no NaN comes here.
-__device__ __forceinline__ u32 key_of(float v)
-{
-    const u32 b = __float_as_uint(v);
-    return b & 0x80000000u ? ~b : b | 0x80000000u;
-}
-
-__device__ __forceinline__ float float_of(u32 k) { return __uint_as_float(k & 0x80000000u ? k ^ 0x80000000u : ~k); }
-
-// What a set of member pixels adds to a record.  key[]: X_min, X_max, Y_min, Y_max, Z_min, Z_max
+// What a set of member pixels adds to a record.  key[]: X_min, X_max, Y_min, Y_max, Z_min, Z_max as opkit::key_of words (no NaN comes here)
 struct Acc {
     u32 n;
     int x0, x1, y0, y1;
@@ -265,7 +255,7 @@ __global__ __launch_bounds__(kThreads) void k_ob_pixels(const float *__restrict_
                 if (q < 0 || !((s_occ[q >> 5] >> (q & 31)) & 1u)) continue;
                 const int x = x0 + xs + j;
                 const float z = c.fb / it.d[j];
-                const float X = (((float)x - c.cx) * z) / c.fx, Y = (((float)y - c.cy) * z) / c.fy;
+                const float X = back_x(c, x, z), Y = back_y(c, y, z);
                 const u32 kx = key_of(X), ky = key_of(Y), kz = key_of(z);
                 a[j] = Acc{1u, x, x, y, y, (u64)(int)u16f(it.d[j]), {kx, kx, ky, ky, kz, kz}};
                 cell[j] = (nbins - 1 - q) * S + s;
@@ -328,40 +318,18 @@ __device__ __forceinline__ unsigned kept_roots(const int *__restrict__ par, cons
     return keep;
 }
 
-// The exclusive scan of `mine` over the workgroup's 256 threads in thread order, and the workgroup's total: a wave scan, the four
-// waves' totals in LDS (s_w: kWaves words; two barriers, so that the next call may write them again).
-__device__ __forceinline__ int block_scan(int mine, int *s_w, int &total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = mine;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-    }
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    int before = incl - mine;
-    total = 0;
-    for (int w = 0; w < kWaves; ++w) before += w < wave ? s_w[w] : 0, total += s_w[w];
-    __syncthreads();
-    return before;
-}
-
 // The numbering is the three-launch scan of lws_point_cloud over the cells in c order, in blocks of 2048 cells (8 consecutive cells
 // per thread): per-block counts, a per-image exclusive scan of them, a ranked write.
 // grid (nblk, B), 256 threads: cnt[b][blk] = {kept roots, occupied cells, components, member pixels of the kept roots} of the block.
 __global__ __launch_bounds__(kThreads) void k_ob_count(const int *__restrict__ parent, const u32 *__restrict__ rec, int N, int min_pixels,
                                                       int *__restrict__ cnt)
 {
-    __shared__ int s_n[4][kWaves];
+    __shared__ int s_n[kWaves][4];
     const int blk = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
     int sums[4] = {0, 0, 0, 0};
     sums[0] = __popc(kept_roots(parent + (int64_t)b * N, rec + (int64_t)b * N * kRec, (blk * kThreads + t) * kPer, N, min_pixels, sums + 1));
-    wave_sum_n(sums);
-    if ((t & 63) == 0)
-        for (int i = 0; i < 4; ++i) s_n[i][t >> 6] = sums[i];
-    __syncthreads();
-    if (t < 4) cnt[4 * ((int64_t)b * gridDim.x + blk) + t] = sum4(s_n[t][0], s_n[t][1], s_n[t][2], s_n[t][3]);
+    block_sum_n(sums, s_n);
+    if (t < 4) cnt[4 * ((int64_t)b * gridDim.x + blk) + t] = block_total(s_n, t);
 }
 
 // grid (B), 256 threads: cnt[b][blk][0] becomes the kept roots before the block (an exclusive scan over the image's blocks, 256 a
@@ -370,36 +338,28 @@ __global__ __launch_bounds__(kThreads) void k_ob_scan(int *__restrict__ cnt, int
                                                      float *__restrict__ vals, int32_t *__restrict__ info)
 {
     __shared__ int s_w[kWaves];
-    __shared__ int s_n[3][kWaves];
+    __shared__ int s_n[kWaves][3];
     const int b = blockIdx.x, t = threadIdx.x;
     int *c = cnt + 4 * (int64_t)b * nblk;
     int before = 0, sums[3] = {0, 0, 0};
     for (int i0 = 0; i0 < nblk; i0 += kThreads) {
         const int i = i0 + t;
-        int total;
-        const int mine = i < nblk ? c[4 * i] : 0;
-        const int at = before + block_scan(mine, s_w, total);
+        const int at = block_scan(i < nblk ? c[4 * i] : 0, s_w, before);
         if (i < nblk) {
             c[4 * i] = at;
             for (int j = 0; j < 3; ++j) sums[j] += c[4 * i + 1 + j];
         }
-        before += total;
+        __syncthreads();                                    // s_w is rewritten by the next round
     }
     const int none[8] = {0, -1, -1, -1, -1, -1, -1, 0};
     const float zero[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     int32_t *orow = rows + (int64_t)b * max_objects * 8;
     float *oval = vals + (int64_t)b * max_objects * 8;
     for (int j = min(before, max_objects) + t; j < max_objects; j += kThreads) store_object(orow + 8 * (int64_t)j, oval + 8 * (int64_t)j, none, zero);
-    wave_sum_n(sums);
-    if ((t & 63) == 0)
-        for (int i = 0; i < 3; ++i) s_n[i][t >> 6] = sums[i];
-    __syncthreads();
+    block_sum_n(sums, s_n);
     if (t == 0) {
         int32_t *o = info + 4 * (int64_t)b;
-        o[0] = sum4(s_n[0][0], s_n[0][1], s_n[0][2], s_n[0][3]);
-        o[1] = sum4(s_n[1][0], s_n[1][1], s_n[1][2], s_n[1][3]);
-        o[2] = before;
-        o[3] = sum4(s_n[2][0], s_n[2][1], s_n[2][2], s_n[2][3]);
+        o[0] = block_total(s_n, 0), o[1] = block_total(s_n, 1), o[2] = before, o[3] = block_total(s_n, 2);
     }
 }
 
@@ -418,8 +378,8 @@ __global__ __launch_bounds__(kThreads) void k_ob_write(const int *__restrict__ p
     const float fb = load_cam(cam, b).fb;
     const int cb = (blk * kThreads + t) * kPer;
     const unsigned keep = kept_roots(parent + (int64_t)b * N, r_img, cb, N, min_pixels, nullptr);
-    int total;
-    int j = cnt[4 * ((int64_t)b * gridDim.x + blk)] + block_scan(__popc(keep), s_w, total);
+    int before = cnt[4 * ((int64_t)b * gridDim.x + blk)];
+    int j = block_scan((int)__popc(keep), s_w, before);
     for (int i = 0; i < kPer; ++i) {
         if (!((keep >> i) & 1u)) continue;
         u32 *r = r_img + (int64_t)(cb + i) * kRec;
@@ -428,8 +388,8 @@ __global__ __launch_bounds__(kThreads) void k_ob_write(const int *__restrict__ p
             const u64 sq = *reinterpret_cast<const u64 *>(r + R_SQ);
             const float d = (float)(((double)sq / (double)n) / 256.0);
             const int ri[8] = {n, (int)r[R_X0], (int)r[R_X1], (int)r[R_Y0], (int)r[R_Y1], k_min, k_max, (int)r[R_CELLS] + 1};
-            const float vf[8] = {d, fb / d, float_of(r[R_KEY]), float_of(r[R_KEY + 1]), float_of(r[R_KEY + 2]), float_of(r[R_KEY + 3]),
-                                 float_of(r[R_KEY + 4]), float_of(r[R_KEY + 5])};
+            const float vf[8] = {d, fb / d, unkey(r[R_KEY]), unkey(r[R_KEY + 1]), unkey(r[R_KEY + 2]), unkey(r[R_KEY + 3]),
+                                 unkey(r[R_KEY + 4]), unkey(r[R_KEY + 5])};
             store_object(orow + 8 * (int64_t)j, oval + 8 * (int64_t)j, ri, vf);
             r[R_NUM] = (u32)j;
         }

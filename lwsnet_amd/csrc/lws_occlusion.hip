@@ -13,6 +13,8 @@ namespace lws {
 namespace {
 
 using namespace rowkit;                                     // kThreads, kWaves, kMaxW: dL row + z-buffer row, 64 KiB of LDS at most
+using opkit::key_of;                                        // 0 is no splatted value's key: an empty z-buffer word
+using opkit::unkey;
 constexpr int kTailWords = 3 * kWaves;                      // the fill's two per-wave aggregates and the kept counts
 
 struct OccMaps {                                            // the nmaps stage maps of one call, by value in the kernel arguments
@@ -21,16 +23,6 @@ struct OccMaps {                                            // the nmaps stage m
     uint8_t *mask[4];
     float *right[4];
 };
-
-// The order-preserving word of a float: unsigned compare of keys == float compare of values (-0.0 below +0.0).  0 is no float's
-// key but a NaN's (bits 0xffffffff), and NaNs are never keyed: 0 means "empty".
-__device__ __forceinline__ unsigned key_of(float d)
-{
-    const unsigned u = __float_as_uint(d);
-    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
-}
-
-__device__ __forceinline__ float unkey(unsigned k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
 
 // words of LDS behind the staged row: the z-buffer (4 nq), which the fill's index arrays (2 nq) and the kTailWords reuse
 __host__ __device__ constexpr int z_words(int nq) { return 4 * nq > 2 * nq + kTailWords ? 4 * nq : 2 * nq + kTailWords; }

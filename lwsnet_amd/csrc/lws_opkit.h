@@ -1,7 +1,9 @@
-// The toolkit of the post-network ops (lws_metrics, lws_lrcheck, lws_occlusion, lws_geometry, lws_mesh, lws_ground, lws_stixels, lws_objects, lws_speckle, lws_wmedian, lws_rectify,
-// lws_confidence, lws_sparsification, lws_photometric; lws_rowkit.h builds on it).  An op is its own arithmetic and its own limits between these
-// pieces.  Host half: the argument checks their entry points share, under the caller's name `who`, so that a text is written once.
-// Device half: the 64-lane sum, the four-wave combine in its fixed order, and the ground-truth contract of the evaluation kernels.
+// The toolkit of the post-network ops (lws_metrics, lws_lrcheck, lws_occlusion, lws_geometry, lws_mesh, lws_ground, lws_stixels,
+// lws_objects, lws_temporal, lws_egomotion, lws_tsdf, lws_speckle, lws_wmedian, lws_rectify, lws_confidence, lws_sparsification,
+// lws_photometric; lws_rowkit.h, lws_geomkit.h and lws_packkit.h build on it).  An op is its own arithmetic and its own limits
+// between these pieces.  Host half: the argument checks their entry points share, under the caller's name `who`, so that a text is
+// written once.  Device half: the 64-lane sum, the four-wave combine in its fixed order, the workgroup's sum made of the two, the
+// monotone key of a float, and the ground-truth contract of the evaluation kernels.
 // The translation units of the forward (feature2d, refine, conv3d, volume, regress, forward, params, api, pool) do not include this header.
 #pragma once
 #include "lws_common.h"
@@ -52,7 +54,10 @@ static inline int check_image_shape(const char *who, int B, int H, int W, int pi
     return LWS_OK;
 }
 
-static inline bool finite_nonneg(float x) { return x >= 0.0f && x <= 3.4028234663852886e38f; }   // (false for NaN)
+constexpr float kFloatMax = 3.4028234663852886e38f;
+static inline bool finite_nonneg(float x) { return x >= 0.0f && x <= kFloatMax; }   // (false for NaN)
+static inline bool finite_pos(float x) { return x > 0.0f && x <= kFloatMax; }
+static inline bool finite_any(float x) { return x >= -kFloatMax && x <= kFloatMax; }
 
 static inline int check_fill(const char *who, int fill)
 {
@@ -116,6 +121,41 @@ __device__ __forceinline__ void wave_sum_n(T (&v)[N])
 // The sums of the four waves of a 256-thread workgroup, in the one fixed order
 template <typename T>
 __device__ __forceinline__ T sum4(const T &w0, const T &w1, const T &w2, const T &w3) { return (w0 + w1) + (w2 + w3); }
+
+// The sum of v over the 256 threads of a workgroup in that fixed order: wave_sum, one word per wave in s[0 .. 4) (the caller's LDS),
+// a barrier, sum4.  Every thread calls it and every thread holds the result; the caller synchronises before s is written again.
+template <typename T>
+__device__ __forceinline__ T block_sum(T v, T *s)
+{
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return sum4(s[0], s[1], s[2], s[3]);
+}
+
+// N sums side by side: the waves' sums to s[wave][j] and a barrier; sum j is then block_total(s, j) in every thread
+// (rowkit::wave_sums / row_total are this layout for int, with the barrier left to the row kernel, which has one anyway)
+template <typename T, int N>
+__device__ __forceinline__ void block_sum_n(T (&v)[N], T (*s)[N])
+{
+    wave_sum_n(v);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) s[threadIdx.x >> 6][j] = v[j];
+    }
+    __syncthreads();
+}
+template <typename T, int N>
+__device__ __forceinline__ T block_total(const T (*s)[N], int j) { return sum4(s[0][j], s[1][j], s[2][j], s[3][j]); }
+
+// The order-preserving word of a float: unsigned compare of keys == float compare of values (-0.0 below +0.0).  0 is no float's
+// key but a NaN's (bits 0xffffffff), and NaNs are never keyed, so a caller may let 0 mean "empty".
+__device__ __forceinline__ unsigned key_of(float d)
+{
+    const unsigned u = __float_as_uint(d);
+    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+}
+__device__ __forceinline__ float unkey(unsigned k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
 
 // One pixel against its ground truth g, the reference's float32 numpy: valid = the mask of the mode (0 = KITTI: 0 < g < md,
 // 1 = EPE: g < md), e = |p - g|, bad = valid & e > 3 & e / g > 0.05.  One IEEE float32 operation each; the ordered compares are

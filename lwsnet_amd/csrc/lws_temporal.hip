@@ -14,11 +14,12 @@
 //                is 0 -- on a map of which the checks kept 90 % nine atomics in ten never leave the CU
 //   k_tp_hold    (hold) one thread per quad: a code-0 pixel with a non-empty word takes the state of the source the word names
 // The per-code counts are taken by the last kernel of the list: per thread in two packed words, per wave by shuffles, per
-// workgroup through LDS, then one 64-bit integer atomic per workgroup and non-zero counter.
+// workgroup through LDS (opkit::block_sum_n), then one 64-bit integer atomic per workgroup and non-zero counter.
 // Determinism: what crosses threads is the integer max of the z-buffer words (agent scope, relaxed; the word holds the key of dn
 // and the source index, so the winner is a function of the inputs) and the integer adds of the counts; a workgroup works on one
 // image, so an image gives the same bytes in any batch, at any position, on every run.  0 bytes of scratch.
 #include "lws_geomkit.h"
+#include "lws_rowkit.h"
 
 namespace lws {
 
@@ -27,29 +28,8 @@ namespace {
 using namespace geomkit;
 using u64 = unsigned long long;
 constexpr int kThreads = 256;
-constexpr int kMaxDim = 1 << 24;                            // (float)(W - 1) and (float)(H - 1) are exact
-
-// (lws_occlusion.hip's key: unsigned compare of keys == float compare of values; 0 is no non-NaN float's key)
-__device__ __forceinline__ unsigned key_of(float d)
-{
-    const unsigned u = __float_as_uint(d);
-    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
-}
-__device__ __forceinline__ float unkey(unsigned k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
-
-// row r of the 3 x 4 matrix m applied to (X, Y, Z)
-__device__ __forceinline__ float row_dot(const float *__restrict__ m, int r, float X, float Y, float Z)
-{
-    return ((m[4 * r] * X + m[4 * r + 1] * Y) + m[4 * r + 2] * Z) + m[4 * r + 3];
-}
-
-// the pixel (u, v) of a point with Pz > 0, and whether it lies in the image
-__device__ __forceinline__ bool project(const Cam &c, float Px, float Py, float Pz, int H, int W, float &u, float &v)
-{
-    u = (c.fx * Px) / Pz + c.cx;
-    v = (c.fy * Py) / Pz + c.cy;
-    return u >= 0.0f && u <= (float)(W - 1) && v >= 0.0f && v <= (float)(H - 1);
-}
+using rowkit::store_codes;
+using rowkit::store_quad;
 
 struct TpArgs {                                             // by value in the kernel arguments
     const float *meas, *sigma;
@@ -75,42 +55,16 @@ __device__ __forceinline__ void store_ages(uint16_t *p, int x, int W, const unsi
     }
 }
 
-__device__ __forceinline__ void store_floats(float *p, int x, int W, const float v[4])
-{
-    if (x + 4 <= W && aligned(p + x, 16)) {
-        *reinterpret_cast<float4 *>(p + x) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if (x + i < W) p[x + i] = v[i];
-    }
-}
-
-__device__ __forceinline__ void store_code_quad(uint8_t *p, int x, int W, const int c[4])
-{
-    if (x + 4 <= W && aligned(p + x, 4)) {
-        *reinterpret_cast<uchar4 *>(p + x) = make_uchar4((uint8_t)c[0], (uint8_t)c[1], (uint8_t)c[2], (uint8_t)c[3]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if (x + i < W) p[x + i] = (uint8_t)c[i];
-    }
-}
-
 // The workgroup's pixels per code, packed[k / 3] holding code k in bits 10 (k % 3) .. (at most 4 per thread, 256 per wave), added
 // to counts[b][0..4].  Called by all kThreads threads.
 __device__ __forceinline__ void add_counts(unsigned (&packed)[2], u64 *__restrict__ counts, int b)
 {
-    __shared__ int s_c[5][kThreads / 64];
+    __shared__ unsigned s_p[kThreads / 64][2];
     const int t = threadIdx.x;
-    wave_sum_n(packed);
-    if ((t & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 5; ++k) s_c[k][t >> 6] = (int)((packed[k / 3] >> (10 * (k % 3))) & 1023u);
-    }
-    __syncthreads();
+    block_sum_n(packed, s_p);
     if (t < 5) {
-        const int n = sum4(s_c[t][0], s_c[t][1], s_c[t][2], s_c[t][3]);
+        unsigned n = 0;                                     // (a wave's field is at most 256; four of them may need an 11th bit)
+        for (int w = 0; w < kThreads / 64; ++w) n += (s_p[w][t / 3] >> (10 * (t % 3))) & 1023u;
         if (n) __hip_atomic_fetch_add(counts + 5 * (int64_t)b + t, (u64)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
@@ -148,11 +102,10 @@ __global__ __launch_bounds__(kThreads) void k_tp_fuse(TpArgs a)
         load_ok(mk, x, W, aligned(mk, 4), ok);
         const Cam c = load_cam(a.cam, b);
         const bool prev = a.Dp != nullptr;
-        const float *p0 = a.pose + 24 * (int64_t)b, *p1 = p0 + 12;
+        const float *p0 = pose_of(a.pose, b), *p1 = inverse_of(a.pose, b);
         const float *Dp = a.Dp + img, *Vp = a.Vp + img;
         const uint16_t *Ap = a.Ap + img;
         const float gg = a.gate * a.gate;
-        const float fy = (float)y - c.cy;
         float Do[4], Vo[4];
         unsigned Ao[4];
         int co[4];
@@ -165,10 +118,10 @@ __global__ __launch_bounds__(kThreads) void k_tp_fuse(TpArgs a)
             unsigned Af = 0u;
             if (valid && prev) {
                 const float z = c.fb / m[i];
-                const float X = (((float)(x + i) - c.cx) * z) / c.fx, Y = (fy * z) / c.fy;
+                const float X = back_x(c, x + i, z), Y = back_y(c, y, z);
                 const float Qx = row_dot(p1, 0, X, Y, z), Qy = row_dot(p1, 1, X, Y, z), Qz = row_dot(p1, 2, X, Y, z);
                 float u, v;
-                if (Qz > 0.0f && project(c, Qx, Qy, Qz, H, W, u, v)) {
+                if (Qz > 0.0f && project(c, Qx, Qy, Qz, H, W, 0, u, v)) {
                     const float dexp = c.fb / Qz;
                     const int i0 = (int)floorf(u), i1 = min(i0 + 1, W - 1), j0 = (int)floorf(v), j1 = min(j0 + 1, H - 1);
                     const float fa = u - (float)i0, fb_ = v - (float)j0;
@@ -176,13 +129,9 @@ __global__ __launch_bounds__(kThreads) void k_tp_fuse(TpArgs a)
                     const unsigned a00 = Ap[t00], a01 = Ap[t01], a10 = Ap[t10], a11 = Ap[t11];
                     if (a00 > 0u && a01 > 0u && a10 > 0u && a11 > 0u) {
                         const float d00 = Dp[t00], d01 = Dp[t01], d10 = Dp[t10], d11 = Dp[t11];
-                        float mx = d00, mn = d00;
-                        mx = d01 > mx ? d01 : mx, mx = d10 > mx ? d10 : mx, mx = d11 > mx ? d11 : mx;
-                        mn = d01 < mn ? d01 : mn, mn = d10 < mn ? d10 : mn, mn = d11 < mn ? d11 : mn;
-                        if (mx - mn <= a.max_jump) {
-                            const float v00 = Vp[t00], v01 = Vp[t01], v10 = Vp[t10], v11 = Vp[t11];
-                            const float dtop = d00 + fa * (d01 - d00), dbot = d10 + fa * (d11 - d10), ds = dtop + fb_ * (dbot - dtop);
-                            const float vtop = v00 + fa * (v01 - v00), vbot = v10 + fa * (v11 - v10), vs = vtop + fb_ * (vbot - vtop);
+                        if (jump4(d00, d01, d10, d11) <= a.max_jump) {
+                            const float ds = blend4(d00, d01, d10, d11, fa, fb_);
+                            const float vs = blend4(Vp[t00], Vp[t01], Vp[t10], Vp[t11], fa, fb_);
                             const unsigned ag = min(min(a00, a01), min(a10, a11));
                             const float k = dexp / ds;
                             const float Zn = row_dot(p0, 2, Qx * k, Qy * k, Qz * k);
@@ -205,10 +154,10 @@ __global__ __launch_bounds__(kThreads) void k_tp_fuse(TpArgs a)
             Ao[i] = !valid ? 0u : pass ? Af : 1u;
             if (x + i < W) packed[co[i] / 3] += 1u << (10 * (co[i] % 3));
         }
-        store_floats(a.D + row, x, W, Do);
-        store_floats(a.V + row, x, W, Vo);
+        store_quad(a.D + row, x, W, aligned(a.D + row, 16), Do[0], Do[1], Do[2], Do[3]);
+        store_quad(a.V + row, x, W, aligned(a.V + row, 16), Vo[0], Vo[1], Vo[2], Vo[3]);
         store_ages(a.A + row, x, W, Ao);
-        store_code_quad(a.code + row, x, W, co);
+        store_codes(a.code + row, x, W, aligned(a.code + row, 4), co);
         if (HOLD) {
             u64 *zb = a.zbuf + row;
 #pragma unroll
@@ -230,13 +179,13 @@ __global__ __launch_bounds__(kThreads) void k_tp_splat(TpArgs a)
     if (a.Ap[img + s] == 0) return;
     const int y = (int)(s / W), x = (int)(s - (int64_t)y * W);
     const Cam c = load_cam(a.cam, b);
-    const float *p0 = a.pose + 24 * (int64_t)b;
+    const float *p0 = pose_of(a.pose, b);
     const float d = a.Dp[img + s];
     const float z = c.fb / d;
-    const float X = (((float)x - c.cx) * z) / c.fx, Y = (((float)y - c.cy) * z) / c.fy;
+    const float X = back_x(c, x, z), Y = back_y(c, y, z);
     const float Px = row_dot(p0, 0, X, Y, z), Py = row_dot(p0, 1, X, Y, z), Pz = row_dot(p0, 2, X, Y, z);
     float u, v;
-    if (!(Pz > 0.0f && project(c, Px, Py, Pz, H, W, u, v))) return;
+    if (!(Pz > 0.0f && project(c, Px, Py, Pz, H, W, 0, u, v))) return;
     const float dn = c.fb / Pz;
     const int64_t tgt = img + (int64_t)((int)rintf(v)) * W + (int)rintf(u);     // in the image: 0 <= u <= W - 1, 0 <= v <= H - 1
     if (a.code[tgt] != 0) return;
@@ -292,8 +241,7 @@ __global__ __launch_bounds__(kThreads) void k_tp_hold(TpArgs a)
 
 int check_shape(const char *who, int B, int H, int W, int hold)
 {
-    LWS_CHECK_RC(check_image_shape(who, B, H, W, 31));
-    LWS_CHECK_ARG(H <= kMaxDim && W <= kMaxDim, "%s: H=%d W=%d exceed %d (pixel coordinates are exact floats)", who, H, W, kMaxDim);
+    LWS_CHECK_RC(check_view_shape(who, B, H, W));
     LWS_CHECK_ARG(hold == 0 || hold == 1, "%s: hold %d (0 = off, 1 = hold what was seen before)", who, hold);
     return LWS_OK;
 }
@@ -329,9 +277,9 @@ int lws_temporal_step(const float *meas, const float *sigma, const uint8_t *mask
                       aligned(D, 4) && aligned(V, 4) && aligned(Ap, 2) && aligned(A, 2) && aligned(counts, 8) && aligned(workspace, 8),
                   "%s: meas / sigma / cam / pose / Dp / Vp / D / V must be 4-byte, Ap / A 2-byte, counts / workspace 8-byte aligned", who);
     LWS_CHECK_ARG(sigma || finite_nonneg(sigma0), "%s: sigma0 must be finite and >= 0 where sigma is null, got %g", who, (double)sigma0);
-    LWS_CHECK_ARG(min_disp > 0.0f && finite_nonneg(min_disp), "%s: min_disp must be finite and > 0, got %g", who, (double)min_disp);
-    LWS_CHECK_ARG(sigma_min > 0.0f && finite_nonneg(sigma_min), "%s: sigma_min must be finite and > 0, got %g", who, (double)sigma_min);
-    LWS_CHECK_ARG(gate > 0.0f && finite_nonneg(gate), "%s: gate must be finite and > 0, got %g", who, (double)gate);
+    LWS_CHECK_ARG(finite_pos(min_disp), "%s: min_disp must be finite and > 0, got %g", who, (double)min_disp);
+    LWS_CHECK_ARG(finite_pos(sigma_min), "%s: sigma_min must be finite and > 0, got %g", who, (double)sigma_min);
+    LWS_CHECK_ARG(finite_pos(gate), "%s: gate must be finite and > 0, got %g", who, (double)gate);
     LWS_CHECK_ARG(finite_nonneg(q), "%s: q must be finite and >= 0, got %g", who, (double)q);
     LWS_CHECK_ARG(max_jump >= 0.0f, "%s: max_jump must be >= 0 (+inf allowed), got %g", who, (double)max_jump);      // (false for NaN)
     LWS_CHECK_ARG(finite_nonneg(q_hold), "%s: q_hold must be finite and >= 0, got %g", who, (double)q_hold);

@@ -14,34 +14,21 @@
 //                        the projection of a row would have to hold under float32 rounding of u and v, which was not shown.
 //   lws_tsdf_raycast     k_ts_raycast  one thread per pixel; a step gathers the eight taps of Wt and, where all are known, of T.
 //                        Neighbouring rays walk neighbouring cells, so a wave's taps share cache lines.
-//   lws_tsdf_points      k_ts_count, k_ts_scan, k_ts_scatter: lws_point_cloud's form with an x-row of the volume in the place
-//                        of an image row, 64-bit offsets (a volume has up to 3 * 2^31 edges) and a capacity.
+//   lws_tsdf_points      k_ts_count, k_ts_scan, k_ts_scatter: lws_point_cloud's form (lws_packkit.h) with an x-row of the volume in
+//                        the place of an image row, 64-bit offsets (a volume has up to 3 * 2^31 edges) and a capacity.
 // Determinism: a voxel, a pixel and a record belong to one thread; what crosses threads is the integer add of `updated` and the
 // ballots of the scatter.  0 bytes of scratch.
 #include "lws_geomkit.h"
+#include "lws_packkit.h"
 
 namespace lws {
 
 namespace {
 
 using namespace geomkit;
+using namespace packkit;                                    // kThreads, kWaves
 using u64 = unsigned long long;
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kMaxDim = 1 << 24;                            // (float)(W - 1) and (float)(H - 1) are exact
 constexpr int kMaxGrid = 4096;
-
-// row r of the 3 x 4 matrix m applied to (X, Y, Z); rot_dot: its rotation alone
-__device__ __forceinline__ float row_dot(const float *__restrict__ m, int r, float X, float Y, float Z)
-{
-    return ((m[4 * r] * X + m[4 * r + 1] * Y) + m[4 * r + 2] * Z) + m[4 * r + 3];
-}
-__device__ __forceinline__ float rot_dot(const float *__restrict__ m, int r, float X, float Y, float Z)
-{
-    return (m[4 * r] * X + m[4 * r + 1] * Y) + m[4 * r + 2] * Z;
-}
-
-__device__ __forceinline__ float lerp(float p, float q, float s) { return p + s * (q - p); }
 
 // g / |g| as lws_surface_normals normalises, zero where the length is not finite or not > 0
 __device__ __forceinline__ void normalise(float gx, float gy, float gz, float n[3])
@@ -111,16 +98,15 @@ __global__ __launch_bounds__(kThreads) void k_ts_integrate(IntArgs a)
         int n_taken = 0;
         if (active) {
             const Cam c = load_cam(a.cam, b);
-            const float *p0 = a.pose + 24 * (int64_t)b;
+            const float *p0 = pose_of(a.pose, b);
             const int64_t img = (int64_t)b * plane;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 if (x + i >= a.Gx) continue;
                 const float xw = a.ox + (float)(x + i) * a.vs;
                 const float Px = row_dot(p0, 0, xw, yw, zw), Py = row_dot(p0, 1, xw, yw, zw), Pz = row_dot(p0, 2, xw, yw, zw);
-                if (!(Pz > 0.0f)) continue;
-                const float u = (c.fx * Px) / Pz + c.cx, v = (c.fy * Py) / Pz + c.cy;
-                if (!(u >= 0.0f && u <= (float)(W - 1) && v >= 0.0f && v <= (float)(H - 1))) continue;
+                float u, v;
+                if (!(Pz > 0.0f && project(c, Px, Py, Pz, H, W, 0, u, v))) continue;
                 const int iu = (int)rintf(u), iv = (int)rintf(v);       // in the image: 0 <= u <= W - 1, 0 <= v <= H - 1
                 const int64_t px = img + (int64_t)iv * W + iu;
                 const float d = a.disp[px];
@@ -136,7 +122,7 @@ __global__ __launch_bounds__(kThreads) void k_ts_integrate(IntArgs a)
                     const float *np = a.normals + 3 * img + (int64_t)iv * W + iu;
                     const float nx = np[0], ny = np[plane], nz = np[2 * plane];
                     if (nx != 0.0f || ny != 0.0f || nz != 0.0f) {
-                        const float X = (((float)iu - c.cx) * z) / c.fx, Y = (((float)iv - c.cy) * z) / c.fy;
+                        const float X = back_x(c, iu, z), Y = back_y(c, iv, z);
                         sdf = -(((X - Px) * nx + (Y - Py) * ny) + (z - Pz) * nz);
                     }
                 }
@@ -191,13 +177,8 @@ __global__ __launch_bounds__(kThreads) void k_ts_integrate(IntArgs a)
             }
         }
         if (a.updated) {                                    // (uniform)
-            const int n = wave_sum(n_taken);
-            if ((t & 63) == 0) s_n[b & 1][t >> 6] = n;
-            __syncthreads();                                // one barrier per frame: the next frame writes the other half of s_n
-            if (t == 0) {
-                const int total = sum4(s_n[b & 1][0], s_n[b & 1][1], s_n[b & 1][2], s_n[b & 1][3]);
-                if (total) __hip_atomic_fetch_add(a.updated + b, (u64)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            const int total = block_sum(n_taken, s_n[b & 1]);   // one barrier per frame: the next frame writes the other half of s_n
+            if (t == 0 && total) __hip_atomic_fetch_add(a.updated + b, (u64)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
     if (!touched) return;
@@ -243,12 +224,12 @@ __device__ __forceinline__ Sample sample(const Vol &v, float px, float py, float
         known = known && observed(w[k], v.w_min);
     }
     s.known = known;
-    if (WANT_W) s.wf = lerp(lerp(lerp(w[0], w[1], ax), lerp(w[2], w[3], ax), ay), lerp(lerp(w[4], w[5], ax), lerp(w[6], w[7], ax), ay), az);
+    if (WANT_W) s.wf = lerp(blend4(w[0], w[1], w[2], w[3], ax, ay), blend4(w[4], w[5], w[6], w[7], ax, ay), az);
     if (known) {
         float f[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) f[k] = v.T[o[k]];
-        s.f = lerp(lerp(lerp(f[0], f[1], ax), lerp(f[2], f[3], ax), ay), lerp(lerp(f[4], f[5], ax), lerp(f[6], f[7], ax), ay), az);
+        s.f = lerp(blend4(f[0], f[1], f[2], f[3], ax, ay), blend4(f[4], f[5], f[6], f[7], ax, ay), az);
     }
     return s;
 }
@@ -263,7 +244,7 @@ __global__ __launch_bounds__(kThreads) void k_ts_raycast(Vol v, const float *__r
     if (s >= plane) return;
     const int y = (int)(s / W), x = (int)(s - (int64_t)y * W);
     const Cam c = load_cam(cam, b);
-    const float *p0 = pose + 24 * (int64_t)b, *p1 = p0 + 12;
+    const float *p0 = pose_of(pose, b), *p1 = inverse_of(pose, b);
     const float xn = ((float)x - c.cx) / c.fx, yn = ((float)y - c.cy) / c.fy;
     bool pk = false, hit = false;
     float fp = 0.0f, zp = 0.0f, zs = 0.0f;
@@ -341,38 +322,16 @@ __global__ __launch_bounds__(kThreads) void k_ts_count(Vol v, int64_t *__restric
         float Ta, Tb[3];
         n += __builtin_popcount(edge_bits(v, ix, iy, iz, Ta, Tb));
     }
-    n = wave_sum(n);
-    if ((t & 63) == 0) s_n[t >> 6] = n;
-    __syncthreads();
-    if (t == 0) row_count[(int64_t)iz * v.Gy + iy] = sum4(s_n[0], s_n[1], s_n[2], s_n[3]);
+    n = block_sum(n, s_n);
+    if (t == 0) row_count[(int64_t)iz * v.Gy + iy] = n;
 }
 
-// grid (1), 256 threads: row_count[0 .. R) -> its exclusive scan, in place; counts[0] = the total (k_pc_scan with 64-bit sums).
+// grid (1), 256 threads: row_count[0 .. R) -> its exclusive scan, in place (packkit::row_scan with 64-bit sums); counts[0] = the total.
 __global__ __launch_bounds__(kThreads) void k_ts_scan(int64_t *__restrict__ r, int R, int64_t *__restrict__ counts)
 {
     __shared__ int64_t s_w[kWaves];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    int64_t carry = 0;                                      // uniform: the rows before the chunk
-    for (int y0 = 0; y0 < R; y0 += kThreads) {
-        const int y = y0 + t;
-        const int64_t val = y < R ? r[y] : 0;
-        int64_t inc = val;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int64_t u = __shfl_up(inc, o, 64);
-            inc += lane >= o ? u : 0;
-        }
-        if (lane == 63) s_w[wave] = inc;
-        __syncthreads();
-        int64_t before = carry, total = carry;
-        for (int w = 0; w < kWaves; ++w) {
-            before += w < wave ? s_w[w] : 0;
-            total += s_w[w];
-        }
-        if (y < R) r[y] = before + inc - val;
-        carry = total;
-        __syncthreads();                                    // s_w is rewritten by the next chunk
-    }
-    if (t == 0) counts[0] = carry;
+    const int64_t total = row_scan(r, R, s_w);
+    if (threadIdx.x == 0) counts[0] = total;
 }
 
 // the central difference of T over the six neighbours of voxel (ix, iy, iz), normalised; zero unless all six are inside and observed
@@ -389,37 +348,22 @@ __device__ __forceinline__ void voxel_normal(const Vol &v, int ix, int iy, int i
 }
 
 // grid (Gy, Gz), 256 threads: the crossings of the x-row in the order (ix, axis) to the records row_off[iz * Gy + iy] ..; a chunk
-// is 256 voxels, the rank of (voxel, axis) in it the crossings of the chunk's earlier voxels (three wave ballots, one per axis,
-// plus popcounts; the earlier waves' totals through LDS) plus the crossings of the voxel on its earlier axes.
+// is 256 voxels, the rank of (voxel, axis) in it the crossings of the chunk's earlier voxels (packkit::block_rank, one bit slot per
+// axis) plus the crossings of the voxel on its earlier axes.
 __global__ __launch_bounds__(kThreads) void k_ts_scatter(Vol v, const unsigned *__restrict__ C, const int64_t *__restrict__ row_off,
                                                         int64_t max_points, uint4 *__restrict__ points, float4 *__restrict__ vnormals)
 {
     __shared__ int s_w[kWaves];
-    const int iy = blockIdx.x, iz = blockIdx.y, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int iy = blockIdx.x, iz = blockIdx.y, t = threadIdx.x;
     const int64_t first = row_off[(int64_t)iz * v.Gy + iy];
     if (first >= max_points) return;                        // (uniform) nothing of this row fits
-    const unsigned long long below = (1ull << lane) - 1ull;
     const float yw = v.oy + (float)iy * v.vs, zw = v.oz + (float)iz * v.vs;
     int carry = 0;                                          // uniform: the crossings of the earlier chunks
     for (int x0 = 0; x0 < v.Gx; x0 += kThreads) {
         const int ix = x0 + t;
         float Ta = 0.0f, Tb[3] = {0.0f, 0.0f, 0.0f};
         const unsigned bits = ix < v.Gx ? edge_bits(v, ix, iy, iz, Ta, Tb) : 0u;
-        int rank = 0, wave_n = 0;
-#pragma unroll
-        for (int e = 0; e < 3; ++e) {
-            const unsigned long long m = __ballot((bits >> e) & 1u);
-            rank += __popcll(m & below);
-            wave_n += __popcll(m);
-        }
-        if (lane == 0) s_w[wave] = wave_n;
-        __syncthreads();
-        int total = carry;
-        for (int w = 0; w < kWaves; ++w) {
-            rank += w < wave ? s_w[w] : 0;
-            total += s_w[w];
-        }
-        rank += carry;
+        int rank = block_rank<3>(bits, s_w, carry);
         if (bits) {
             const float xw = v.ox + (float)ix * v.vs;
 #pragma unroll
@@ -442,23 +386,20 @@ __global__ __launch_bounds__(kThreads) void k_ts_scatter(Vol v, const unsigned *
                 }
             }
         }
-        carry = total;
         __syncthreads();                                    // s_w is rewritten by the next chunk
     }
 }
 
 // ---- host ----
-static inline bool finite_f(float x) { return x >= -3.4028234663852886e38f && x <= 3.4028234663852886e38f; }   // (false for NaN)
-
 int check_volume(const char *who, const float *T, const float *Wt, int Gx, int Gy, int Gz, float ox, float oy, float oz, float vs)
 {
     LWS_CHECK_ARG(T && Wt, "%s: T and Wt must not be null", who);
     LWS_CHECK_ARG(Gx >= 2 && Gx <= kMaxGrid && Gy >= 2 && Gy <= kMaxGrid && Gz >= 2 && Gz <= kMaxGrid,
                   "%s: bad volume Gx=%d Gy=%d Gz=%d (each in 2..%d)", who, Gx, Gy, Gz, kMaxGrid);
     LWS_CHECK_ARG((int64_t)Gx * Gy * Gz < ((int64_t)1 << 31), "%s: Gx*Gy*Gz = %dx%dx%d must be < 2^31", who, Gx, Gy, Gz);
-    LWS_CHECK_ARG(finite_f(ox) && finite_f(oy) && finite_f(oz), "%s: the origin (%g, %g, %g) must be finite", who, (double)ox, (double)oy,
+    LWS_CHECK_ARG(finite_any(ox) && finite_any(oy) && finite_any(oz), "%s: the origin (%g, %g, %g) must be finite", who, (double)ox, (double)oy,
                   (double)oz);
-    LWS_CHECK_ARG(vs > 0.0f && finite_nonneg(vs), "%s: vs must be finite and > 0, got %g", who, (double)vs);
+    LWS_CHECK_ARG(finite_pos(vs), "%s: vs must be finite and > 0, got %g", who, (double)vs);
     LWS_CHECK_ARG(aligned(T, 4) && aligned(Wt, 4), "%s: T / Wt must be 4-byte aligned", who);
     return LWS_OK;
 }
@@ -466,8 +407,7 @@ int check_volume(const char *who, const float *T, const float *Wt, int Gx, int G
 int check_views(const char *who, const float *cam, const float *pose, int B, int H, int W)
 {
     LWS_CHECK_ARG(cam && pose, "%s: cam and pose must not be null", who);
-    LWS_CHECK_RC(check_image_shape(who, B, H, W, 31));
-    LWS_CHECK_ARG(H <= kMaxDim && W <= kMaxDim, "%s: H=%d W=%d exceed %d (pixel coordinates are exact floats)", who, H, W, kMaxDim);
+    LWS_CHECK_RC(check_view_shape(who, B, H, W));
     LWS_CHECK_ARG(aligned(cam, 4) && aligned(pose, 4), "%s: cam / pose must be 4-byte aligned", who);
     return LWS_OK;
 }
@@ -492,12 +432,12 @@ int lws_tsdf_integrate(const float *disp, const float *sigma, const uint8_t *mas
     LWS_CHECK_ARG((rgb != nullptr) == (C != nullptr), "%s: rgb and C must be given together (rgb colours C; both null: no colour)", who);
     LWS_CHECK_ARG(aligned(disp, 4) && aligned(sigma, 4) && aligned(normals, 4) && aligned(C, 4) && aligned(updated, 8),
                   "%s: disp / sigma / normals / C must be 4-byte, updated 8-byte aligned", who);
-    LWS_CHECK_ARG(min_disp > 0.0f && finite_nonneg(min_disp), "%s: min_disp must be finite and > 0, got %g", who, (double)min_disp);
+    LWS_CHECK_ARG(finite_pos(min_disp), "%s: min_disp must be finite and > 0, got %g", who, (double)min_disp);
     LWS_CHECK_ARG(max_depth > 0.0f, "%s: max_depth must be > 0 (+inf allowed), got %g", who, (double)max_depth);           // (false for NaN)
-    LWS_CHECK_ARG(mu0 > 0.0f && finite_nonneg(mu0), "%s: mu0 must be finite and > 0, got %g", who, (double)mu0);
+    LWS_CHECK_ARG(finite_pos(mu0), "%s: mu0 must be finite and > 0, got %g", who, (double)mu0);
     LWS_CHECK_ARG(finite_nonneg(mu_d), "%s: mu_d must be finite and >= 0, got %g", who, (double)mu_d);
     LWS_CHECK_ARG(sigma || finite_nonneg(sigma0), "%s: sigma0 must be finite and >= 0 where sigma is null, got %g", who, (double)sigma0);
-    LWS_CHECK_ARG(sigma_min > 0.0f && finite_nonneg(sigma_min), "%s: sigma_min must be finite and > 0, got %g", who, (double)sigma_min);
+    LWS_CHECK_ARG(finite_pos(sigma_min), "%s: sigma_min must be finite and > 0, got %g", who, (double)sigma_min);
     LWS_CHECK_ARG(wmode == 0 || wmode == 1, "%s: wmode %d (0 = unit weights, 1 = 1 / sigma_z^2)", who, wmode);
     LWS_CHECK_ARG(w_max > 0.0f, "%s: w_max must be > 0 (+inf allowed), got %g", who, (double)w_max);                       // (false for NaN)
     const int64_t px = (int64_t)B * H * W, vox = (int64_t)Gx * Gy * Gz;
@@ -532,8 +472,8 @@ int lws_tsdf_raycast(const float *T, const float *Wt, int Gx, int Gy, int Gz, fl
     LWS_CHECK_RC(check_views(who, cam, pose, B, H, W));
     LWS_CHECK_ARG(disp, "%s: disp is null", who);
     LWS_CHECK_ARG(aligned(disp, 4) && aligned(weight, 4) && aligned(normals, 4), "%s: disp / weight / normals must be 4-byte aligned", who);
-    LWS_CHECK_ARG(z_near > 0.0f && finite_nonneg(z_near), "%s: z_near must be finite and > 0, got %g", who, (double)z_near);
-    LWS_CHECK_ARG(step > 0.0f && finite_nonneg(step), "%s: step must be finite and > 0, got %g", who, (double)step);
+    LWS_CHECK_ARG(finite_pos(z_near), "%s: z_near must be finite and > 0, got %g", who, (double)z_near);
+    LWS_CHECK_ARG(finite_pos(step), "%s: step must be finite and > 0, got %g", who, (double)step);
     LWS_CHECK_ARG(nsteps >= 2 && nsteps <= 65535, "%s: nsteps %d outside 2..65535", who, nsteps);
     LWS_CHECK_ARG(finite_nonneg(w_min), "%s: w_min must be finite and >= 0, got %g", who, (double)w_min);
     const int64_t px = (int64_t)B * H * W, vox = (int64_t)Gx * Gy * Gz;

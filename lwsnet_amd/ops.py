@@ -128,6 +128,21 @@ def _finite_pos(name, v):
     return float(v)
 
 
+def _int_indexed(H, W, name, op, what="maps", sides=False):
+    """Refuses images of 2^31 pixels or more, which the kernels of `op` index with an int; with `sides`, also a side above 2^24."""
+    if H * W >= 1 << 31 or (sides and max(H, W) > 1 << 24):
+        raise ValueError(f"{name + ' is ' if name else ''}{H}x{W}: {op} takes {what} of fewer than 2^31 pixels"
+                         f"{' and at most 2^24 a side' if sides else ''}")
+
+
+def _device_rows(t, name, shape, device, host_rows):
+    """t as a float32 device tensor of `shape`: a device tensor (egomotion's pose block, say) is taken as it is and nothing is read
+    back; anything else is what host_rows() makes of it, the op's own reading of host numbers as a numpy array, uploaded."""
+    if isinstance(t, torch.Tensor) and t.is_cuda:
+        return _tensor_of(t, name, torch.float32, shape, device)
+    return torch.from_numpy(host_rows()).to(device)
+
+
 def _workspace(name, device, *dims):
     """The uint8 workspace of the size the library's `name`(*dims) asks for."""
     return torch.empty((_lib.nbytes(name, *dims),), device=device, dtype=torch.uint8)
@@ -853,8 +868,7 @@ def temporal_step(disp, cameras, pose=None, prev=None, sigma=None, mask=None, si
         raise ValueError("temporal_step: a previous state needs pose")
     d, mask, cam = _geometry_inputs(disp, mask, cameras, scalars[1], float("inf"))
     B, _, H, W = d.shape
-    if H * W >= 1 << 31:
-        raise ValueError(f"disp is {H}x{W}: temporal_step takes maps of fewer than 2^31 pixels")
+    _int_indexed(H, W, "disp", "temporal_step")
     if sigma is not None:
         sigma = _disp_map(sigma, "sigma")
         if tuple(sigma.shape) != tuple(d.shape) or sigma.device != d.device:
@@ -863,10 +877,7 @@ def temporal_step(disp, cameras, pose=None, prev=None, sigma=None, mask=None, si
     if prev is not None:
         prev = (_tensor_of(prev[0], "prev disp", torch.float32, d.shape, d.device), _tensor_of(prev[1], "prev var", torch.float32, d.shape, d.device),
                 _tensor_of(prev[2], "prev age", torch.uint16, d.shape, d.device))
-        if isinstance(pose, torch.Tensor) and pose.is_cuda:  # egomotion's pose block: it stays on the device, nothing is read back
-            pose_dev = _tensor_of(pose, "pose", torch.float32, (B, 2, 12), d.device)
-        else:
-            pose_dev = torch.from_numpy(temporal_pose_rows(pose, B)).to(d.device)
+        pose_dev = _device_rows(pose, "pose", (B, 2, 12), d.device, lambda: temporal_pose_rows(pose, B))
     else:
         prev = (None, None, None)
     hold = scalars[6]
@@ -924,8 +935,7 @@ def ego_normal(grey_ref, disp_ref, grey_cur, cameras, M, level=0, mask=None, min
     huber = _finite_pos("huber", huber)
     d, mask, cam = _geometry_inputs(disp_ref, mask, cameras, min_disp, float("inf"))
     B, _, H, W = d.shape
-    if H * W >= 1 << 31:
-        raise ValueError(f"disp_ref is {H}x{W}: ego_normal takes maps of fewer than 2^31 pixels")
+    _int_indexed(H, W, "disp_ref", "ego_normal")
     g0, g1 = (_tensor_of(g, name, torch.float32, d.shape, d.device) for g, name in ((grey_ref, "grey_ref"), (grey_cur, "grey_cur")))
     m_dev = torch.from_numpy(_motion_rows(M, B, "M", "float64")).to(d.device)
     work = _workspace("lws_egomotion_workspace", d.device, B, H, W, 1)
@@ -949,14 +959,10 @@ def egomotion(rgb_ref, disp_ref, rgb_cur, cameras, mask=None, init=None, levels=
     scalars = ego_args(levels, iters, min_disp, max_jump, huber, damping, min_pixels)
     d, mask, cam = _geometry_inputs(disp_ref, mask, cameras, scalars[2], float("inf"))
     B, _, H, W = d.shape
-    if H * W >= 1 << 31:
-        raise ValueError(f"disp_ref is {H}x{W}: egomotion takes maps of fewer than 2^31 pixels")
+    _int_indexed(H, W, "disp_ref", "egomotion")
     r0, r1 = (_tensor_of(r, name, torch.uint8, (B, H, W, 3), d.device) for r, name in ((rgb_ref, "rgb_ref"), (rgb_cur, "rgb_cur")))
     if init is not None:
-        if isinstance(init, torch.Tensor) and init.is_cuda:
-            init = _tensor_of(init, "init", torch.float32, (B, 12), d.device)
-        else:
-            init = torch.from_numpy(_motion_rows(init, B, "init", "float32")).to(d.device)
+        init = _device_rows(init, "init", (B, 12), d.device, lambda: _motion_rows(init, B, "init", "float32"))
     levels, iters = scalars[:2]
     work = _workspace("lws_egomotion_workspace", d.device, B, H, W, levels)
     pose = torch.empty((B, 2, 12), device=d.device, dtype=torch.float32)
@@ -999,13 +1005,13 @@ def tsdf_pose_rows(poses_c2w, B):
 
 
 def _tsdf_pose(pose, B, device):
-    if isinstance(pose, torch.Tensor) and pose.is_cuda:
-        return _tensor_of(pose, "pose", torch.float32, (B, 2, 12), device)
-    import numpy as np
-    p = np.asarray(pose.detach().cpu().numpy() if isinstance(pose, torch.Tensor) else pose)
-    if p.dtype != np.float32 or p.shape != (B, 2, 12) or not np.isfinite(p).all():
-        raise ValueError(f"pose must be the finite float32 [{B},2,12] of tsdf_pose_rows, got {p.dtype} {p.shape}")
-    return torch.from_numpy(np.ascontiguousarray(p)).to(device)
+    def host_rows():
+        import numpy as np
+        p = np.asarray(pose.detach().cpu().numpy() if isinstance(pose, torch.Tensor) else pose)
+        if p.dtype != np.float32 or p.shape != (B, 2, 12) or not np.isfinite(p).all():
+            raise ValueError(f"pose must be the finite float32 [{B},2,12] of tsdf_pose_rows, got {p.dtype} {p.shape}")
+        return np.ascontiguousarray(p)
+    return _device_rows(pose, "pose", (B, 2, 12), device, host_rows)
 
 
 def _tsdf_volume(T, Wt, C, g):
@@ -1054,8 +1060,7 @@ def tsdf_integrate(T, Wt, origin, voxel, disp, cameras, pose, C=None, sigma=None
     if d.device != dev:
         raise ValueError(f"disp is on {d.device}, the volume on {dev}")
     B, _, H, W = d.shape
-    if H * W >= 1 << 31 or max(H, W) > 1 << 24:
-        raise ValueError(f"disp is {H}x{W}: tsdf_integrate takes maps of fewer than 2^31 pixels and at most 2^24 a side")
+    _int_indexed(H, W, "disp", "tsdf_integrate", sides=True)
     if sigma is not None:
         sigma = _tensor_of(sigma, "sigma", torch.float32, d.shape, dev)
     if normals is not None:
@@ -1097,8 +1102,7 @@ def tsdf_raycast(T, Wt, origin, voxel, cameras, pose, H, W, z_near=0.5, step=Non
         raise ValueError(f"cameras must be one Camera or a list of {B}")
     B = _int_in("B", B, 1, 65535)
     H, W = _int_in("H", H, 1, 1 << 24), _int_in("W", W, 1, 1 << 24)
-    if H * W >= 1 << 31:
-        raise ValueError(f"{H}x{W}: tsdf_raycast takes views of fewer than 2^31 pixels")
+    _int_indexed(H, W, "", "tsdf_raycast", what="views")
     z_near = _finite_pos("z_near", z_near)
     step = _finite_pos("step", 0.5 * g[6] if step is None else step)
     if nsteps is None:

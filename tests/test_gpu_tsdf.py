@@ -247,9 +247,10 @@ def points_buffers(dev, dims, cap, put, T, Wt, C):
                 counts=torch.full((1,), 77, dtype=torch.int64, device=dev))
 
 
-@pytest.mark.parametrize("dims", [(5, 3, 2), (33, 4, 5), (65, 7, 9), (300, 3, 2)])
+@pytest.mark.parametrize("dims", [(5, 3, 2), (33, 4, 5), (65, 7, 9), (300, 3, 2), *R.POINTS_CHUNKED])
 def test_points_bitexact_order_included(dev, hip_lib, dims):
-    """300 x 3 x 2: a row of more than one chunk of 256 voxels.  Then with a w_min, without C and normals, and with a capacity
+    """300 x 3 x 2: a row of more than one chunk of 256 voxels; R.POINTS_CHUNKED: 256, 258 and 520 rows, where the scan of the row
+    counts carries from chunk to chunk.  Then with a w_min, without C and normals, and with a capacity
     smaller than the count: counts is the full number, the first max_points records are equal, what lies behind is untouched."""
     T, Wt, C, origin, vs = R.points_volume(dims, 1)
     g = grid(dims, origin, vs)

@@ -106,6 +106,24 @@ def test_the_points_cases_cross_on_every_axis_both_ways(dims):
     assert (xyz >= lo).all() and (xyz <= lo + F(vs) * (np.array(dims, F) - 1)).all()
 
 
+@pytest.mark.parametrize("dims", list(R.POINTS_CHUNKED))
+def test_the_chunked_points_cases_cross_on_both_sides_of_every_carry(dims):
+    """The x-row of a crossing on an x-edge can be read off its y and z, which are voxel centres: rows on both sides of every
+    chunk boundary of the scan hold records, so a wrong carry moves records that the bit-exact comparison sees."""
+    T, Wt, C, origin, vs = R.points_volume(dims, 1)
+    xyz, rgba, nrm, e, up = R.points(T, Wt, C, origin, vs)
+    assert len(xyz) == R.POINTS_CHUNKED[dims]
+    xs, ys, zs = R.centres(origin, vs, dims)
+    on_x = xyz[e == 0]
+    iy, iz = np.searchsorted(ys, on_x[:, 1]), np.searchsorted(zs, on_x[:, 2])
+    assert (ys[iy] == on_x[:, 1]).all() and (zs[iz] == on_x[:, 2]).all()
+    row, rows = iz * dims[1] + iy, dims[1] * dims[2]
+    for edge in range(256, rows + 256, 256):                 # the chunk [edge - 256, edge) and, if any row follows it, what follows
+        assert ((row >= edge - 256) & (row < edge)).any(), edge
+        assert (row >= edge).any() == (rows > edge), edge
+    assert (rows - 1) // 256 == {(6, 16, 16): 0, (5, 3, 86): 1, (9, 20, 26): 2}[dims]      # the carries of the scan
+
+
 def test_the_exact_wall():
     for frames in (1, 5):
         w = wall_volume(frames)

@@ -257,6 +257,9 @@ def records(xyz, rgba):
 
 # ---- the cases of the tests: tests/test_tsdf_cpu.py asserts what they reach, tests/test_gpu_tsdf.py runs them on the device ----
 VOLUMES, MAPS, BATCHES = ((5, 3, 2), (33, 4, 5), (65, 7, 9)), ((5, 7), (48, 96)), (1, 3)
+# lws_tsdf_points scans its Gy * Gz row counts in chunks of 256 with a carry: volumes (for points_volume(dims, 1)) of exactly 256
+# rows, of 258 rows and of 520 rows (two carries), with 972, 728 and 2919 crossings
+POINTS_CHUNKED = {(6, 16, 16): 972, (5, 3, 86): 728, (9, 20, 26): 2919}
 # camera-to-world motions (temporal_reference.forward_pose: dz, yaw, dx); the last one puts part of every volume behind the camera
 MOTIONS = {"identity": (0.0, 0.0, 0.0), "yaw_and_step": (0.3, 0.05, 0.2), "backward": (11.8, 0.0, 0.0)}
 _CASES = {}
