@@ -1,7 +1,7 @@
 """ctypes binding of liblwsnet_hip.so.  include/lwsnet_hip.h is the statement of the C ABI: PROTOTYPES and the LWS_*
 constants are read from it when this module is imported (tests/test_abi_cpu.py has a C++ compiler check the reading).  The entry
-points added behind ABI v8 in headers of their own (include/lwsnet_objects.h) are read the same way into EXTENSION_PROTOTYPES, include/lwsnet_temporal.h into TEMPORAL_PROTOTYPES and
-include/lwsnet_egomotion.h into EGOMOTION_PROTOTYPES and include/lwsnet_tsdf.h into TSDF_PROTOTYPES.
+points added behind ABI v8 live in headers of their own, named in HEADERS; each is read the same way into ABI[header name], and a
+new header is one more name there.
 
 The header cannot say which pointers are host pointers, so every pointer but `const char *` is c_void_p: the 20 host-pointer
 parameters -- lws_set_tensor's data and shape, the mean / std arrays, lws_profile_read*, lws_clock_read, lws_join_stats, the
@@ -18,11 +18,9 @@ import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblwsnet_hip.so")
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "lwsnet_hip.h")
-EXTENSION_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), "include", "lwsnet_objects.h"),)
-TEMPORAL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "lwsnet_temporal.h")
-EGOMOTION_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "lwsnet_egomotion.h")
-TSDF_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "lwsnet_tsdf.h")
+INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
+HEADERS = ("lwsnet_hip.h", "lwsnet_objects.h", "lwsnet_temporal.h", "lwsnet_egomotion.h", "lwsnet_tsdf.h")      # the base header first
+HEADER_PATH = os.path.join(INCLUDE, HEADERS[0])
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
@@ -105,32 +103,32 @@ def parse_header(text, where="header"):
     return protos, spellings, consts
 
 
-# name -> (restype, argtypes) and name -> (C return type, C parameter types): exactly the functions the header declares
-with open(HEADER_PATH) as _f:
-    PROTOTYPES, C_SPELLINGS, _CONSTANTS = parse_header(_f.read(), HEADER_PATH)
+def merge_headers(tables):
+    """{header name: prototypes} -> the one table load() binds, {function: (restype, argtypes)}; a function that two headers
+    declare raises ValueError naming it and both headers."""
+    merged, origin = {}, {}
+    for header, protos in tables.items():
+        for name in protos:
+            if name in origin:
+                raise ValueError(f"{name} is declared by {origin[name]} and by {header}")
+            origin[name] = header
+        merged.update(protos)
+    return merged
+
+
+# header name -> (prototypes, spellings, path): name -> (restype, argtypes) and name -> (C return type, C parameter types), exactly
+# the functions that header declares; PROTOTYPES, C_SPELLINGS and the constants are the base header's
+ABI = {}
+for _name in HEADERS:
+    with open(os.path.join(INCLUDE, _name)) as _f:
+        _protos, _spellings, _consts = parse_header(_f.read(), _f.name)
+    ABI[_name] = (_protos, _spellings, _f.name)
+    if _name == HEADERS[0]:
+        PROTOTYPES, C_SPELLINGS, _CONSTANTS = _protos, _spellings, _consts
 (LWS_ABI_VERSION, LWS_OK, LWS_ERR_INVALID, LWS_ERR_HIP, LWS_ERR_STATE, LWS_ERR_NOMEM, LWS_KC_COUNT, LWS_SPARS_BINS,
  LWS_POOL_SIDE_STREAMS) = (_CONSTANTS[k] for k in ("LWS_ABI_VERSION", "LWS_OK", "LWS_ERR_INVALID", "LWS_ERR_HIP", "LWS_ERR_STATE",
                                                    "LWS_ERR_NOMEM", "LWS_KC_COUNT", "LWS_SPARS_BINS", "LWS_POOL_SIDE_STREAMS"))
-
-# the same two tables for the headers that extend the ABI: exactly the functions those headers declare
-EXTENSION_PROTOTYPES, EXTENSION_SPELLINGS = {}, {}
-for _path in EXTENSION_HEADER_PATHS:
-    with open(_path) as _f:
-        _protos, _spellings, _ = parse_header(_f.read(), _path)
-    EXTENSION_PROTOTYPES.update(_protos)
-    EXTENSION_SPELLINGS.update(_spellings)
-
-# and for the temporal filter's header: exactly the functions include/lwsnet_temporal.h declares
-with open(TEMPORAL_HEADER_PATH) as _f:
-    TEMPORAL_PROTOTYPES, TEMPORAL_SPELLINGS, _ = parse_header(_f.read(), TEMPORAL_HEADER_PATH)
-
-# and for the ego-motion header: exactly the functions include/lwsnet_egomotion.h declares
-with open(EGOMOTION_HEADER_PATH) as _f:
-    EGOMOTION_PROTOTYPES, EGOMOTION_SPELLINGS, _ = parse_header(_f.read(), EGOMOTION_HEADER_PATH)
-
-# and for the TSDF volume's header: exactly the functions include/lwsnet_tsdf.h declares
-with open(TSDF_HEADER_PATH) as _f:
-    TSDF_PROTOTYPES, TSDF_SPELLINGS, _ = parse_header(_f.read(), TSDF_HEADER_PATH)
+ALL_PROTOTYPES = merge_headers({name: table[0] for name, table in ABI.items()})
 
 _lib = None
 
@@ -156,7 +154,7 @@ def load():
             f"{LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python -m lwsnet_amd.build`); there is no CPU fallback for the disparity path")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in {**PROTOTYPES, **EXTENSION_PROTOTYPES, **TEMPORAL_PROTOTYPES, **EGOMOTION_PROTOTYPES, **TSDF_PROTOTYPES}.items():
+    for name, (res, args) in ALL_PROTOTYPES.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

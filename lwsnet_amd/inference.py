@@ -137,12 +137,12 @@ smear; the poses are taken as given.
 """
 import argparse
 import contextlib
-import glob
 import logging
 import os
 import shutil
 import sys
 import time
+import types
 
 import numpy as np
 
@@ -150,10 +150,13 @@ from . import imageio as io
 from . import outputs as out
 from . import pipeline
 from . import postprocess as post
+from . import sequence as seq
 from .outputs import (STIXEL_COLOUR_DEPTH, bev_to_u8, conf_to_u8, ground_to_rgb, objects_to_csv, objects_to_rgb, photo_to_u8,  # noqa: F401
                       sigma_to_u8, stixels_to_csv, stixels_to_rgb, geometry_requested as _geometry_requested)      # these stay this module's names
 from .postprocess import (add_lr_arguments, add_occ_arguments, add_speckle_arguments, add_wmedian_arguments, check_lr_arguments,
                           check_occ_arguments, check_speckle_arguments, check_wmedian_arguments)
+from .sequence import (TSDF_DEFAULTS, check_egomotion_arguments, check_temporal_arguments, check_tsdf_arguments,  # noqa: F401
+                       list_pairs as _list_pairs, temporal_sigma, tsdf_grid)
 
 
 def build_parser():
@@ -180,9 +183,7 @@ def build_parser():
     add_rectify_arguments(p)
     add_conf_arguments(p)
     post.add_photometric_arguments(p, save=True)
-    add_temporal_arguments(p)
-    add_egomotion_arguments(p)
-    add_tsdf_arguments(p)
+    seq.add_sequence_arguments(p)
     return p
 
 
@@ -213,8 +214,7 @@ def check_conf_arguments(p, args):
     post.set_defaults(args, **CONF_DEFAULTS)
     if sigma_max_given and not args.save_conf:
         p.error("--sigma_max needs --save_conf")
-    if not (np.isfinite(args.sigma_max) and args.sigma_max > 0):
-        p.error(f"--sigma_max MAX must be finite and > 0, got {args.sigma_max}")
+    post.in_range(p.error, "--sigma_max MAX", args.sigma_max, strict=True)
     for flag in ("conf_min", "sigma_max_keep"):
         v = getattr(args, flag)
         if v is not None and np.isnan(v):
@@ -227,191 +227,6 @@ def check_conf_arguments(p, args):
     post.sequential_only(p, args, flags, "run")
     if (args.conf_min is not None or args.sigma_max_keep is not None) and not _geometry_requested(args):
         p.error("--conf_min and --sigma_max_keep mask --save_disp16 / --save_depth / --save_ply / --save_normals / --save_mesh: give one of them")
-
-
-def add_temporal_arguments(p):
-    """--temporal and its flags (not in the reference): lwsnet_amd.temporal.TemporalFilter behind the chain.  A command line without
-    them parses to the namespace it parsed to before they existed (argparse.SUPPRESS); check_temporal_arguments writes their defaults."""
-    S = argparse.SUPPRESS
-    p.add_argument("--temporal", action="store_true", default=S,
-                   help="fuse the stage-4 maps of the sequence over time with the poses of --poses (directory mode, sequential only; "
-                        "needs a camera; not in the reference)")
-    p.add_argument("--poses", type=str, default=S, metavar="PATH",
-                   help="with --temporal: a KITTI odometry poses.txt, 12 numbers per line (camera-to-world), line i for the i-th pair in sorted order")
-    p.add_argument("--temporal_gate", type=float, default=S, metavar="G", help="temporal: the gate in standard deviations (default 3)")
-    p.add_argument("--temporal_q", type=float, default=S, metavar="Q", help="temporal: process noise in px^2 per frame (default 0)")
-    p.add_argument("--temporal_sigma", type=str, default=S, metavar="S|net",
-                   help="temporal: the measurement's sigma in px (default 0.5), or `net` for the network's own stage-3 sigma")
-    p.add_argument("--temporal_hold", action="store_true", default=S,
-                   help="temporal: a pixel the checks dropped holds what was seen there in earlier frames")
-    p.add_argument("--save_temporal", action="store_true", default=S,
-                   help="--temporal, and write <stem>_tcode.png (the codes in colour) and <stem>_tsigma.png (the fused sigma, scaled as --save_conf's)")
-
-
-TEMPORAL_DEFAULTS = dict(temporal=False, poses=None, temporal_gate=3.0, temporal_q=0.0, temporal_sigma="0.5", temporal_hold=False,
-                         save_temporal=False)
-
-
-def temporal_sigma(args):
-    """--temporal_sigma as (the scalar sigma0 in px, or None for the network's stage-3 sigma)."""
-    return None if args.temporal_sigma == "net" else float(args.temporal_sigma)
-
-
-def check_temporal_arguments(p, args):
-    """Rejects what the temporal filter does not support, before any model or GPU work; reads the poses file; sets the defaults."""
-    from .geometry import read_kitti_poses
-    given = [f for f in ("temporal_gate", "temporal_q", "temporal_sigma", "temporal_hold") if getattr(args, f, None) not in (None, False)]
-    post.set_defaults(args, **TEMPORAL_DEFAULTS)
-    args.temporal = args.temporal or args.save_temporal
-    if not args.temporal:
-        if given or (args.poses is not None and not getattr(args, "tsdf", False)):
-            p.error("--poses, --temporal_gate, --temporal_q, --temporal_sigma and --temporal_hold need --temporal")
-        return
-    ego = bool(getattr(args, "egomotion", False))
-    if ego and args.poses is not None:
-        p.error("--temporal --egomotion takes the filter's poses from the estimate: do not give --poses as well")
-    if args.poses is None and not ego:
-        p.error("--temporal needs --poses PATH, the camera-to-world pose of every pair")
-    _needs_camera(p, args, "--temporal and --save_temporal")
-    post.sequential_only(p, args, "--temporal / --save_temporal", "run")
-    if args.left_img:
-        p.error("--temporal fuses a sequence: use directory mode (--img_path), not --left_img")
-    try:
-        if temporal_sigma(args) is not None and not (np.isfinite(temporal_sigma(args)) and temporal_sigma(args) >= 0):
-            raise ValueError
-    except ValueError:
-        p.error(f"--temporal_sigma must be a finite number of pixels >= 0 or `net`, got {args.temporal_sigma}")
-    if temporal_sigma(args) is None and (args.lr_check is not None or getattr(args, "occ_check", None) is not None):
-        p.error("--temporal_sigma net uses the network's own sigma and does not combine with --lr_check or --occ_check")
-    if not (np.isfinite(args.temporal_gate) and args.temporal_gate > 0):
-        p.error(f"--temporal_gate must be finite and > 0, got {args.temporal_gate}")
-    if not (np.isfinite(args.temporal_q) and args.temporal_q >= 0):
-        p.error(f"--temporal_q must be finite and >= 0, got {args.temporal_q}")
-    if ego:
-        return
-    try:
-        n = len(read_kitti_poses(args.poses))
-    except (OSError, ValueError) as e:
-        p.error(f"--poses: cannot read {args.poses}: {e}")
-    pairs = len(_list_pairs(args)[0])
-    if n < pairs:
-        p.error(f"--poses: {args.poses} holds {n} poses for {pairs} pairs (line i belongs to the i-th pair in sorted order)")
-
-
-def add_egomotion_arguments(p):
-    """--egomotion and its flags (not in the reference): lwsnet_amd.egomotion.Odometry beside the chain.  A command line without them
-    parses to the namespace it parsed to before they existed (argparse.SUPPRESS); check_egomotion_arguments writes their defaults."""
-    S = argparse.SUPPRESS
-    p.add_argument("--egomotion", action="store_true", default=S,
-                   help="estimate the left camera's motion from frame to frame by dense direct alignment (directory mode, sequential "
-                        "only; needs a camera; not in the reference)")
-    p.add_argument("--ego_levels", type=int, default=S, metavar="N", help="egomotion: pyramid levels, 1 .. 8 (default 4)")
-    p.add_argument("--ego_iters", type=int, default=S, metavar="N", help="egomotion: Gauss-Newton steps per level, 1 .. 64 (default 8)")
-    p.add_argument("--ego_huber", type=float, default=S, metavar="K", help="egomotion: the Huber threshold in grey levels (default 10)")
-    p.add_argument("--save_poses", type=str, default=S, metavar="PATH",
-                   help="egomotion: write the accumulated camera-to-world poses as a KITTI odometry poses.txt")
-    p.add_argument("--save_ego", action="store_true", default=S,
-                   help="egomotion: write <stem>_ego.png, the magnitude of the residual at the final pose")
-
-
-EGO_DEFAULTS = dict(egomotion=False, ego_levels=4, ego_iters=8, ego_huber=10.0, save_poses=None, save_ego=False)
-
-
-def check_egomotion_arguments(p, args):
-    """Rejects what the ego-motion estimate does not support, before any model or GPU work; sets the defaults."""
-    given = [f for f in ("ego_levels", "ego_iters", "ego_huber", "save_poses", "save_ego") if hasattr(args, f)]   # (SUPPRESS: there only if given)
-    post.set_defaults(args, **EGO_DEFAULTS)
-    if not args.egomotion:
-        if given:
-            p.error("--ego_levels, --ego_iters, --ego_huber, --save_poses and --save_ego need --egomotion")
-        return
-    _needs_camera(p, args, "--egomotion and --save_ego")
-    post.sequential_only(p, args, "--egomotion / --save_ego", "run")
-    if args.left_img:
-        p.error("--egomotion follows a sequence: use directory mode (--img_path), not --left_img")
-    if not 1 <= args.ego_levels <= 8:
-        p.error(f"--ego_levels must be in 1 .. 8, got {args.ego_levels}")
-    if not 1 <= args.ego_iters <= 64:
-        p.error(f"--ego_iters must be in 1 .. 64, got {args.ego_iters}")
-    if not (np.isfinite(args.ego_huber) and args.ego_huber > 0):
-        p.error(f"--ego_huber must be finite and > 0, got {args.ego_huber}")
-
-
-def add_tsdf_arguments(p):
-    """--tsdf and its flags (not in the reference): lwsnet_amd.tsdf.TsdfVolume behind the chain.  A command line without them parses
-    to the namespace it parsed to before they existed (argparse.SUPPRESS); check_tsdf_arguments writes their defaults."""
-    S = argparse.SUPPRESS
-    p.add_argument("--tsdf", action="store_true", default=S,
-                   help="integrate the stage-4 maps of the sequence into a TSDF volume with the poses of --poses or --egomotion (directory "
-                        "mode, sequential only; needs a camera; not in the reference)")
-    p.add_argument("--tsdf_voxel", type=float, default=S, metavar="V", help="tsdf: the voxel's side in metres (default 0.2)")
-    p.add_argument("--tsdf_extent", type=float, nargs=6, default=S, metavar=("X0", "X1", "Y0", "Y1", "Z0", "Z1"),
-                   help="tsdf: the volume's extent in metres in the first camera's frame, y down, z forward (default -12.8 12.8 -3.2 3.2 0 51.2)")
-    p.add_argument("--tsdf_trunc", type=float, default=S, metavar="MU0", help="tsdf: the truncation band in metres (default 3 voxels)")
-    p.add_argument("--tsdf_trunc_px", type=float, default=S, metavar="MU_D",
-                   help="tsdf: the band in pixels of disparity, so that it grows as z^2: max(MU0, MU_D * z^2 / fb) (default 0)")
-    p.add_argument("--tsdf_weight", type=str, default=S, choices=("unit", "sigma"),
-                   help="tsdf: a frame counts 1, or 1 / sigma_z^2 with the sigma of --temporal (0.5 px without it) (default unit)")
-    p.add_argument("--tsdf_sdf", type=str, default=S, choices=("plane", "ray"),
-                   help="tsdf: the distance to the pixel's tangent plane (surface normals with --max_jump) or along the ray (default plane)")
-    p.add_argument("--save_tsdf_ply", type=str, default=S, metavar="PATH",
-                   help="tsdf: at the end, write the volume's zero crossings as a binary PLY of vertices with normals and colours")
-    p.add_argument("--save_tsdf", action="store_true", default=S,
-                   help="tsdf: write <stem>_tsdf.png, the volume ray-cast into the frame's own pose, coloured as the stage maps")
-
-
-TSDF_DEFAULTS = dict(tsdf=False, tsdf_voxel=0.2, tsdf_extent=(-12.8, 12.8, -3.2, 3.2, 0.0, 51.2), tsdf_trunc=None, tsdf_trunc_px=0.0,
-                     tsdf_weight="unit", tsdf_sdf="plane", save_tsdf_ply=None, save_tsdf=False)
-TSDF_MAX_POINTS = 1 << 22                                   # the capacity of --save_tsdf_ply, in records of 32 bytes
-
-
-def tsdf_grid(args):
-    """(origin, dims) of the volume --tsdf_extent and --tsdf_voxel describe: voxel centres from X0, Y0, Z0 on, as many as reach the
-    far ends."""
-    e, v = args.tsdf_extent, args.tsdf_voxel
-    return (e[0], e[2], e[4]), tuple(int(np.floor((e[2 * k + 1] - e[2 * k]) / v + 0.5)) + 1 for k in range(3))
-
-
-def check_tsdf_arguments(p, args):
-    """Rejects what the volume does not support, before any model or GPU work; sets the defaults."""
-    from . import ops
-    given = [f for f in TSDF_DEFAULTS if f != "tsdf" and hasattr(args, f)]      # (SUPPRESS: there only if given)
-    post.set_defaults(args, **TSDF_DEFAULTS)
-    if not args.tsdf:
-        if given:
-            p.error("--tsdf_voxel, --tsdf_extent, --tsdf_trunc, --tsdf_trunc_px, --tsdf_weight, --tsdf_sdf, --save_tsdf_ply and --save_tsdf need --tsdf")
-        return
-    _needs_camera(p, args, "--tsdf and --save_tsdf")
-    post.sequential_only(p, args, "--tsdf / --save_tsdf", "run")
-    if args.left_img:
-        p.error("--tsdf maps a sequence: use directory mode (--img_path), not --left_img")
-    if getattr(args, "poses", None) is None and not getattr(args, "egomotion", False):
-        p.error("--tsdf needs the pose of every pair: --poses PATH or --egomotion")
-    if not (np.isfinite(args.tsdf_voxel) and args.tsdf_voxel > 0):
-        p.error(f"--tsdf_voxel must be finite and > 0, got {args.tsdf_voxel}")
-    e = args.tsdf_extent
-    if not (np.isfinite(e).all() and e[0] < e[1] and e[2] < e[3] and e[4] < e[5]):
-        p.error(f"--tsdf_extent must be finite X0 < X1, Y0 < Y1, Z0 < Z1, got {' '.join(str(v) for v in e)}")
-    try:
-        ops.tsdf_volume_args(tsdf_grid(args)[0], args.tsdf_voxel, tsdf_grid(args)[1])
-    except ValueError as err:
-        p.error(f"--tsdf_extent / --tsdf_voxel: {err}")
-    if args.tsdf_trunc is None:
-        args.tsdf_trunc = 3.0 * args.tsdf_voxel
-    if not (np.isfinite(args.tsdf_trunc) and args.tsdf_trunc > 0):
-        p.error(f"--tsdf_trunc must be finite and > 0, got {args.tsdf_trunc}")
-    if not (np.isfinite(args.tsdf_trunc_px) and args.tsdf_trunc_px >= 0):
-        p.error(f"--tsdf_trunc_px must be finite and >= 0, got {args.tsdf_trunc_px}")
-    if getattr(args, "temporal", False) or getattr(args, "egomotion", False):
-        return                                              # check_temporal_arguments read the poses file, or there is none
-    from .geometry import read_kitti_poses
-    try:
-        n = len(read_kitti_poses(args.poses))
-    except (OSError, ValueError) as err:
-        p.error(f"--poses: cannot read {args.poses}: {err}")
-    pairs = len(_list_pairs(args)[0])
-    if n < pairs:
-        p.error(f"--poses: {args.poses} holds {n} poses for {pairs} pairs (line i belongs to the i-th pair in sorted order)")
 
 
 class _ConfModel:
@@ -493,15 +308,6 @@ def add_geometry_arguments(p):
     p.add_argument("--object_min_pixels", type=int, default=argparse.SUPPRESS, metavar="N", help="objects: the fewest pixels of an object (default 64)")
 
 
-def _list_pairs(args):
-    """The (left, right) image paths of directory mode (inference.py:50-60)."""
-    if os.path.isdir(args.img_path):
-        return (sorted(glob.glob(os.path.join(args.img_path, "image_2/*.png"))),
-                sorted(glob.glob(os.path.join(args.img_path, "image_3/*.png"))))
-    base, name = os.path.dirname(os.path.dirname(args.img_path)), os.path.basename(args.img_path)
-    return [os.path.join(base, "image_2", name)], [os.path.join(base, "image_3", name)]
-
-
 def _frame_file(path, left_path):
     """The calibration file of a frame: `path` itself, or for a folder the KITTI naming 000123_10.png -> 000123.txt."""
     if not os.path.isdir(path):
@@ -534,12 +340,6 @@ def _check_calibration_files(p, args, flag, path, read):
             p.error(f"--{flag}: cannot read {f}: {e}")
 
 
-def _needs_camera(p, args, flags):
-    """A parser error for `flags` (their names as the sentence's subject) when nothing gives a camera: --calib, --camera or --rectify."""
-    if args.calib is None and args.camera is None and getattr(args, "rectify", None) is None:
-        p.error(f"{flags} need a camera: --calib PATH or --camera FX FY CX CY BASELINE")
-
-
 def check_geometry_arguments(p, args):
     """Rejects what the geometry outputs do not support, before any model or GPU work; reads every calibration file."""
     from .geometry import Camera
@@ -548,23 +348,19 @@ def check_geometry_arguments(p, args):
     outputs = args.save_disp16 or args.save_depth or args.save_ply or surface
     if not (np.isfinite(args.ground_tol) and np.isfinite(args.max_height) and 0 <= args.ground_tol <= args.max_height):
         p.error(f"--ground_tol and --max_height must be finite with 0 <= ground_tol <= max_height, got {args.ground_tol} and {args.max_height}")
-    if not (np.isfinite(args.max_jump) and args.max_jump >= 0):
-        p.error(f"--max_jump must be finite and >= 0, got {args.max_jump}")
-    if not (np.isfinite(args.min_disp) and args.min_disp > 0):
-        p.error(f"--min_disp must be finite and > 0, got {args.min_disp}")
+    post.in_range(p.error, "--max_jump", args.max_jump)
+    post.in_range(p.error, "--min_disp", args.min_disp, strict=True)
     if not args.max_depth > 0:
         p.error(f"--max_depth must be > 0, got {args.max_depth}")
     if args.save_depth or args.save_ply or surface:
-        _needs_camera(p, args, "--save_depth, --save_ply, --save_normals and --save_mesh")
-    if not 1 <= args.stixel_width <= 64:
-        p.error(f"--stixel_width must be in 1 .. 64, got {args.stixel_width}")
-    if not 1 <= args.stixel_layers <= 4:
-        p.error(f"--stixel_layers must be in 1 .. 4, got {args.stixel_layers}")
+        post.needs_camera(p, args, "--save_depth, --save_ply, --save_normals and --save_mesh")
+    post.in_range(p.error, "--stixel_width", args.stixel_width, 1, 64)
+    post.in_range(p.error, "--stixel_layers", args.stixel_layers, 1, 4)
     if args.object_min_pixels < 1:
         p.error(f"--object_min_pixels must be >= 1, got {args.object_min_pixels}")
     for name in ("objects", "stixels", "ground"):
         if getattr(args, name):
-            _needs_camera(p, args, f"--{name} and --save_{name}")
+            post.needs_camera(p, args, f"--{name} and --save_{name}")
             post.sequential_only(p, args, f"--{name} / --save_{name}", "run")
     if outputs:
         post.sequential_only(p, args, "--save_disp16 / --save_depth / --save_ply / --save_normals / --save_mesh", "run")
@@ -755,26 +551,21 @@ def default_arguments(args):
     post.photometric_defaults(args, save=True)
 
 
-def inference(model, left_imgs, right_imgs, args, log):
-    """inference.py:78-138."""
+def inference(model, left_imgs, right_imgs, args, log, poses=None):
+    """inference.py:78-138.  poses: the file of --poses as main()'s checks read it."""
     import torch
     default_arguments(args)
-    post.set_defaults(args, **TEMPORAL_DEFAULTS)            # (check_temporal_arguments' defaults, for a namespace that skipped it)
-    post.set_defaults(args, **EGO_DEFAULTS)
-    post.set_defaults(args, **TSDF_DEFAULTS)
     written, warm = [], False
     opts = post.Options.from_args(args)
-    geo = _geometry_requested(args) or args.temporal or args.egomotion or args.tsdf
+    source, stages = seq.begin(args, min(len(left_imgs), len(right_imgs)), model.device, log, poses)
+    geo = _geometry_requested(args) or bool(stages)
     conf_on = conf_requested(args) or (args.temporal and temporal_sigma(args) is None)
     chain_model = _ConfModel(model) if conf_on else model
-    sequence = _Sequence(args) if args.temporal else None
-    odometry = _Odometry(args) if args.egomotion else None
-    volume = _Volume(args, model.device, log) if args.tsdf else None
     for index, (li, ri) in enumerate(zip(left_imgs, right_imgs)):
         frame = _load_frame(args, li, ri, model.device, geo, log)
         if frame is None:
-            if odometry:
-                odometry.skip(li, log)
+            for st in stages:
+                st.skip(li, log)
             continue
         if args.rectify is not None and args.save_rect:
             folder = os.path.dirname(args.left_img) if args.left_img else args.save_path
@@ -793,9 +584,11 @@ def inference(model, left_imgs, right_imgs, args, log):
                 log.info("Weighted median (radius {}, sigma {:g}, fill {}): stage {} changed = {}, filled = {}".format(
                     opts.wmedian, opts.wmedian_sigma, opts.wmedian_fill, stage + 1, changed, refilled))
         conf = chain_model.last if conf_on else None
-        ego = odometry.step(frame, res, log) if odometry else None     # on the chain's own map and codes, ahead of the filter
-        fused, res = sequence.step(index, frame, res, conf, log, ego) if sequence else (None, res)
-        view = volume.step(index, frame, res, fused, odometry, log) if volume else None       # on what the filter left, where it runs
+        step = types.SimpleNamespace(index=index, frame=frame, res=res, conf=conf, ego=None, fused=None, view=None)   # (lwsnet_amd/sequence.py)
+        source.frame(index)
+        for st in stages:                                   # ego-motion on the chain's own map and codes, the filter, the volume on what it left
+            st.step(step, log)
+        res = step.res
         photo = out.photometric(frame, res, args, log) if args.photometric else None
         for stage in range(4):
             disp = res.disp[stage].squeeze(axis=[0, 1]).numpy()         # :114 (the uint8 cast is inside disparity_to_color)
@@ -803,152 +596,13 @@ def inference(model, left_imgs, right_imgs, args, log):
             if args.left_img:                                           # :117-122
                 written += out.write_stage(os.path.join(os.path.dirname(args.left_img), str(stage + 1) + ".png"), color, ss, frame, stage, args, log, res, conf, photo)
         if not args.left_img:                                           # :133-137 (stage-4 map only)
-            written += out.write_stage(os.path.join(args.save_path, os.path.basename(frame.path)), color, ss, frame, 3, args, log, res, conf, photo, fused)
-            if odometry and args.save_ego:
-                written += out.save_ego(os.path.splitext(os.path.join(args.save_path, os.path.basename(frame.path)))[0], frame, log, ego)
-            if view is not None:
-                written += out.save_tsdf(os.path.splitext(os.path.join(args.save_path, os.path.basename(frame.path)))[0], log, view)
-    if odometry and args.save_poses is not None:
-        odometry.write_poses(args.save_poses)
-        log.info("Save poses = {}".format(args.save_poses))
-        written.append(args.save_poses)
-    if volume and args.save_tsdf_ply is not None:
-        log.info("Save TSDF points = {}, vertices = {}".format(args.save_tsdf_ply, volume.write_ply(args.save_tsdf_ply)))
-        written.append(args.save_tsdf_ply)
+            path = os.path.join(args.save_path, os.path.basename(frame.path))
+            written += out.write_stage(path, color, ss, frame, 3, args, log, res, conf, photo, step.fused)
+            for st in stages:
+                written += st.save(step, os.path.splitext(path)[0], log)
+    for st in stages:
+        written += st.finish(log)
     return written
-
-
-class _Odometry:
-    """--egomotion: the Odometry of the run.  step() estimates the motion from the previous frame to this one from the chain's own
-    stage-4 map and `keep` codes and returns the ops.EgoResult (None on the first frame).  The op itself reads nothing back; this
-    class does, once per frame: the pose, info and status of the estimate, for the log line, the accumulated poses and the
-    filter's reset.  A pair that was skipped is bridged -- the next estimate spans the gap -- and keeps its line in the poses file
-    (line i belongs to pair i, as geometry.read_kitti_poses' users expect): it repeats the pose of the last pair before it, the
-    identity where there is none, and a warning says so."""
-
-    def __init__(self, args):
-        self.args, self.odometry = args, None
-        self.lines = []            # per pair: the index of its pose among the Odometry's, -1 before the first processed pair
-
-    def skip(self, left_path, log):
-        log.warning("Egomotion: %s was skipped; its line of the poses file repeats the pose of the pair before it", left_path)
-        self.lines.append(self.lines[-1] if self.lines else -1)
-
-    def write_poses(self, path):
-        from .geometry import write_kitti_poses
-        identity = np.hstack([np.eye(3), np.zeros((3, 1))])
-        poses = self.odometry.poses() if self.odometry is not None else np.zeros((0, 3, 4))
-        write_kitti_poses(path, np.stack([poses[i] if i >= 0 else identity for i in self.lines]) if self.lines else poses)
-
-    def step(self, frame, res, log):
-        import torch
-        from .egomotion import Odometry, motion_summary
-        a = self.args
-        if self.odometry is None:
-            self.odometry = Odometry(frame.cam, levels=a.ego_levels, iters=a.ego_iters, huber=a.ego_huber, min_disp=a.min_disp)
-        disp = res.disp[3].as_subclass(torch.Tensor)
-        with torch.cuda.device(disp.device):
-            ego = self.odometry.step(out.rgb_on_device(frame.left, disp.device), disp, res.keep[3] if res.keep is not None else None,
-                                     resid=a.save_ego)
-        self.lines.append(len(self.odometry.poses()) - 1)
-        if ego is not None:
-            t, deg = motion_summary(ego.pose[0, 0].cpu().numpy())
-            n, rms = ego.info[0, :2].cpu().tolist()
-            log.info("Egomotion: t = {:.4f} m, rotation = {:.4f} deg, pixels = {}, rms = {:.3f}, status = {}".format(
-                t, deg, int(n), rms, int(self.odometry.status[-1][0])))
-        return ego
-
-
-class _Volume:
-    """--tsdf: the TsdfVolume of the run.  step() integrates one frame's stage-4 map behind the chain -- the fused map and its sigma
-    with --temporal -- under the chain's `keep` codes, with the pose of --poses or the accumulated one of --egomotion, expressed in
-    the frame of the first camera integrated; with --save_tsdf it returns the volume ray-cast into the frame's own pose.  A volume
-    that does not fit the device's free memory is an error before the first frame."""
-
-    def __init__(self, args, device, log):
-        import torch
-        from .geometry import read_kitti_poses
-        from .tsdf import TsdfVolume, volume_bytes
-        self.args, self.first = args, None
-        self.poses = None if args.egomotion else read_kitti_poses(args.poses)
-        origin, dims = tsdf_grid(args)
-        need, free = volume_bytes(dims, colour=True), torch.cuda.mem_get_info(device)[0]
-        if need > free:
-            raise RuntimeError(f"--tsdf: a volume of {dims[0]} x {dims[1]} x {dims[2]} voxels takes {need} bytes, the device has {free} free "
-                               "(a larger --tsdf_voxel or a smaller --tsdf_extent)")
-        self.volume = TsdfVolume(origin, args.tsdf_voxel, dims, mu0=args.tsdf_trunc, mu_d=args.tsdf_trunc_px, weight=args.tsdf_weight, colour=True,
-                                 min_disp=args.min_disp, max_depth=args.max_depth, device=device)
-        log.info("TSDF: volume {} x {} x {} voxels of {:g} m from ({:g}, {:g}, {:g}), {} bytes".format(*dims, args.tsdf_voxel, *origin, need))
-
-    def step(self, index, frame, res, fused, odometry, log):
-        import torch
-        from . import ops
-        a = self.args
-        pose = np.vstack([self.poses[index] if self.poses is not None else odometry.odometry.poses()[-1], [0.0, 0.0, 0.0, 1.0]])
-        if self.first is None:
-            self.first = pose
-        pose = np.linalg.solve(self.first, pose)[:3]        # camera -> the first camera integrated
-        disp = res.disp[3].as_subclass(torch.Tensor)
-        keep = out.merge_keep(res.keep[3] if res.keep is not None else None, frame.valid_left)
-        with torch.cuda.device(disp.device):
-            normals = None
-            if a.tsdf_sdf == "plane":
-                normals = ops.surface_normals(disp, frame.cam, mask=keep, min_disp=a.min_disp, max_depth=a.max_depth, max_jump=a.max_jump)[0]
-            sigma = None if fused is None else torch.sqrt(fused.var)
-            updated = self.volume.integrate(disp, frame.cam, pose, sigma=sigma, mask=keep, normals=normals,
-                                            rgb=out.rgb_on_device(frame.left, disp.device))
-            log.info("TSDF: voxels updated = {}".format(int(updated[0])))
-            if not a.save_tsdf:
-                return None
-            h, w = disp.shape[2:]
-            return self.volume.raycast(frame.cam, pose, h, w, z_near=max(a.tsdf_voxel, 0.5), weight=False, normals=False)
-
-    def write_ply(self, path):
-        return self.volume.write_ply(path, max_points=TSDF_MAX_POINTS)
-
-
-class _Sequence:
-    """--temporal: the filter of the run and the poses of its frames.  step() fuses one frame's stage-4 map behind the chain -- the
-    chain's `keep` codes are the filter's mask, so --temporal_hold fills what the checks dropped -- and puts the fused map in the
-    chain's place: every later writer and geometry step receives the ChainResult step() returns, whose stage-4 map is the fused one
-    and whose stage-4 `keep` (where the chain handed one on) is 1 where the filter left a value.  A frame that was skipped is
-    bridged: the pose is the one between the two frames fused."""
-
-    def __init__(self, args):
-        from .geometry import read_kitti_poses
-        self.args, self.filter, self.last = args, None, None
-        self.poses = None if args.egomotion else read_kitti_poses(args.poses)      # --egomotion: the pose comes with every frame
-
-    def step(self, index, frame, res, conf, log, ego=None):
-        import torch
-        from . import ops
-        from .geometry import relative_pose
-        from .models import DisparityTensor
-        from .temporal import TemporalFilter
-        a = self.args
-        sigma0 = temporal_sigma(a)
-        if self.filter is None:
-            self.filter = TemporalFilter(frame.cam, gate=a.temporal_gate, q=a.temporal_q, sigma0=0.5 if sigma0 is None else sigma0,
-                                         hold=a.temporal_hold, min_disp=a.min_disp)
-        disp = res.disp[3].as_subclass(torch.Tensor)
-        if self.poses is not None:
-            pose = None if self.last is None else relative_pose(self.poses[self.last], self.poses[index])
-        elif ego is None:
-            pose = None
-        elif int(ego.status[0]) & ops.EGO_UNTRUSTED:
-            log.warning("Temporal: the ego-motion estimate of %s is not to be trusted (status %d): the filter starts anew", frame.path,
-                        int(ego.status[0]))
-            pose = None
-        else:
-            pose = ego.pose
-        with torch.cuda.device(disp.device):
-            out_ = self.filter.step(disp, pose, sigma=conf.sigma[2] if sigma0 is None else None, mask=res.keep[3] if res.keep is not None else None)
-        self.last = index
-        log.info("Temporal: " + ", ".join("{} = {}".format(n, c) for n, c in zip(out.TEMPORAL_CODES, out_.counts[0].cpu().tolist())))
-        disps = list(res.disp[:3]) + [DisparityTensor.wrap(out_.disp)]
-        keep = None if res.keep is None else list(res.keep[:3]) + [(out_.code != 0).to(torch.uint8)]
-        return out_, post.ChainResult(disps, res.lr_masks, res.speckle_masks, keep, res.lr_density, res.speckle_counts, res.wmedian_counts,
-                                      res.occ_masks, res.occ_density)
 
 
 def _load_frame(args, left_path, right_path, device, geo, log):
@@ -1012,8 +666,8 @@ def main(argv=None):
     check_conf_arguments(parser, args)
     post.check_photometric_arguments(parser, args, save=True)
     check_egomotion_arguments(parser, args)
-    check_temporal_arguments(parser, args)
-    check_tsdf_arguments(parser, args)
+    poses = check_temporal_arguments(parser, args)
+    alone = check_tsdf_arguments(parser, args)              # the file of --poses comes from the one of the two checks that read it
     log = start_logging("lwsnet_amd.inference", args)
     model = load_model(args, log)
     if getattr(args, "split_bf16", False):
@@ -1032,7 +686,7 @@ def main(argv=None):
         written, stats = inference_pipelined(model, lefts, rights, args, log)
         main.last_stats = stats
     else:
-        written = inference(model, lefts, rights, args, log)
+        written = inference(model, lefts, rights, args, log, alone if poses is None else poses)
     log.info("End inference!")
     return written
 

@@ -53,23 +53,20 @@ class Options:
 
     def check(self):
         """Raises ValueError for every value a stage that is on does not support."""
-        if self.lr_check is not None and not (np.isfinite(self.lr_check) and self.lr_check >= 0):
-            raise ValueError(f"--lr_check TAU must be finite and >= 0, got {self.lr_check}")
+        if self.lr_check is not None:
+            in_range(_invalid, "--lr_check TAU", self.lr_check)
         if self.occ_check is not None:
-            if not (np.isfinite(self.occ_check) and self.occ_check >= 0):
-                raise ValueError(f"--occ_check TAU must be finite and >= 0, got {self.occ_check}")
+            in_range(_invalid, "--occ_check TAU", self.occ_check)
             if self.lr_check is not None:
                 raise ValueError("--occ_check and --lr_check are alternatives: give one of them")
         if self.speckle is not None:
             if self.speckle <= 0 or self.speckle >= 2 ** 31:
                 raise ValueError(f"--speckle SIZE must be an integer > 0, got {self.speckle}")
-            if not np.isfinite(self.speckle_diff) or self.speckle_diff < 0:
-                raise ValueError(f"--speckle_diff D must be finite and >= 0, got {self.speckle_diff}")
+            in_range(_invalid, "--speckle_diff D", self.speckle_diff)
         if self.wmedian is not None:
             if not 1 <= self.wmedian <= 3:
                 raise ValueError(f"--wmedian R must be 1, 2 or 3, got {self.wmedian}")
-            if not np.isfinite(self.wmedian_sigma) or self.wmedian_sigma < 0:
-                raise ValueError(f"--wmedian_sigma S must be finite and >= 0, got {self.wmedian_sigma}")
+            in_range(_invalid, "--wmedian_sigma S", self.wmedian_sigma)
             if self.wmedian_fill < 0 or self.wmedian_fill >= 2 ** 31:
                 raise ValueError(f"--wmedian_fill N must be an integer >= 0, got {self.wmedian_fill}")
 
@@ -127,6 +124,12 @@ class ChainResult(namedtuple("ChainResult", ["disp", "lr_masks", "speckle_masks"
         self = super().__new__(cls, disp, lr_masks, speckle_masks, keep, lr_density, speckle_counts, wmedian_counts)
         self.occ_masks, self.occ_density = occ_masks, occ_density
         return self
+
+    def with_stage4(self, disp, keep):
+        """This result with another stage-4 map and, where there are `keep` codes, another stage-4 code map."""
+        new = self._replace(disp=list(self.disp[:3]) + [disp], keep=None if self.keep is None else list(self.keep[:3]) + [keep])
+        new.occ_masks, new.occ_density = self.occ_masks, self.occ_density      # (_replace copies the tuple's seven only)
+        return new
 
 
 def run_chain(model, left, right, options, guide=None):
@@ -229,6 +232,26 @@ def sequential_only(p, args, flag, verb="runs"):
     """The stages run in the CLIs' sequential mode: a parser error for `flag` (several flags: verb="run") with --workers N > 0."""
     if args.workers > 0:
         p.error(f"{flag} {verb} in the sequential mode only: use --workers 0")
+
+
+def needs_camera(p, args, flags):
+    """A parser error for `flags` (their names as the sentence's subject) when nothing gives a camera: --calib, --camera or --rectify."""
+    if args.calib is None and args.camera is None and getattr(args, "rectify", None) is None:
+        p.error(f"{flags} need a camera: --calib PATH or --camera FX FY CX CY BASELINE")
+
+
+def in_range(fail, name, v, lo=0, hi=None, strict=False):
+    """The one wording of a flag's range: fail(sentence) -- a parser's error, or _invalid -- unless v is finite and >= lo (> lo
+    when strict) or, with hi, in lo .. hi."""
+    if hi is not None:
+        if not lo <= v <= hi:
+            fail(f"{name} must be in {lo} .. {hi}, got {v}")
+    elif not (np.isfinite(v) and (v > lo if strict else v >= lo)):
+        fail(f"{name} must be finite and {'>' if strict else '>='} {lo}, got {v}")
+
+
+def _invalid(sentence):
+    raise ValueError(sentence)
 
 
 def set_defaults(args, **defaults):

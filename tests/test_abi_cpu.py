@@ -51,16 +51,16 @@ def _assert_line(name, spelling):
     return f'static_assert(std::is_same_v<decltype(&{name}), {ret} (*)({", ".join(params)})>, "{name}");\n'
 
 
-def _syntax_only(cxx, path, lines):
+def compiles(header, path, lines):
+    """The host compiler's run over `lines` behind an include of `header`, syntax only."""
     with open(path, "w") as f:
-        f.write('#include <cstddef>\n#include <type_traits>\n#include "lwsnet_hip.h"\n' + "".join(lines))
-    return subprocess.run([cxx, "-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(path)], capture_output=True, text=True)
+        f.write(f'#include <cstddef>\n#include <type_traits>\n#include "{header}"\n' + "".join(lines))
+    return subprocess.run([_host_compiler(), "-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(path)], capture_output=True, text=True)
 
 
 def test_a_compiler_agrees_with_the_reading(tmp_path):
     """Per declared function, the parameter and return types the reader kept, as C text, are the function's type to a C++
     compiler; one scalar misread fails the compile and names the function; LwsConfig has lws_config's size and offsets."""
-    cxx = _host_compiler()
     assert sorted(_lib.C_SPELLINGS) == _declared() and len(_lib.C_SPELLINGS) == 66
     lines = {name: _assert_line(name, sp) for name, sp in _lib.C_SPELLINGS.items()}
     config = [f'static_assert(sizeof(lws_config) == {ctypes.sizeof(_lib.LwsConfig)}, "sizeof(lws_config)");\n']
@@ -68,17 +68,17 @@ def test_a_compiler_agrees_with_the_reading(tmp_path):
         d = getattr(_lib.LwsConfig, field)
         config.append(f'static_assert(offsetof(lws_config, {field}) == {d.offset} && sizeof(lws_config::{field}) == {d.size}, "{field}");\n')
     assert len(config) == 7
-    ok = _syntax_only(cxx, tmp_path / "abi.cpp", list(lines.values()) + config)
+    ok = compiles("lwsnet_hip.h", tmp_path / "abi.cpp", list(lines.values()) + config)
     assert ok.returncode == 0, ok.stderr
     # lws_softargmin(const float *, float *, int, int, int, int, float, void *): its fourth int read as float
     ret, params = _lib.C_SPELLINGS["lws_softargmin"]
     assert params[5] == "int" and params[6] == "float"
     flipped = dict(lines, lws_softargmin=_assert_line("lws_softargmin", (ret, params[:5] + ["float"] + params[6:])))
-    bad = _syntax_only(cxx, tmp_path / "abi_flipped.cpp", list(flipped.values()) + config)
+    bad = compiles("lwsnet_hip.h", tmp_path / "abi_flipped.cpp", list(flipped.values()) + config)
     assert bad.returncode != 0 and '"lws_softargmin"' in bad.stderr, bad.stderr
     assert bad.stderr.count("error:") == 1, bad.stderr
     # ... and a field of the structure moved by four bytes
-    moved = _syntax_only(cxx, tmp_path / "abi_moved.cpp", [config[2].replace("== 12 ", "== 16 ")])
+    moved = compiles("lwsnet_hip.h", tmp_path / "abi_moved.cpp", [config[2].replace("== 12 ", "== 16 ")])
     assert "== 16 " in config[2].replace("== 12 ", "== 16 ") and moved.returncode != 0 and "layers_3d" in moved.stderr, moved.stderr
 
 
@@ -109,6 +109,90 @@ def test_constants_come_from_the_header():
     assert _lib.LWS_ABI_VERSION == 8 and _lib.LWS_KC_COUNT == 14 and _lib.LWS_SPARS_BINS == 1026 and _lib.LWS_POOL_SIDE_STREAMS == 1
     assert (_lib.LWS_OK, _lib.LWS_ERR_INVALID, _lib.LWS_ERR_HIP, _lib.LWS_ERR_STATE, _lib.LWS_ERR_NOMEM) == (0, -1, -2, -3, -4)
     assert _lib.c_float_p is ctypes.POINTER(ctypes.c_float) and _lib.c_int64_p is ctypes.POINTER(ctypes.c_int64)
+
+
+# ---- the headers behind include/lwsnet_hip.h (lwsnet_amd._lib.ABI) ----
+I64 = ctypes.c_int64
+# written by hand from each header, not from the reader.  source: the file of lwsnet_amd.build.SOURCES that defines its functions;
+# protos: every function's (restype, argtypes); lengths: the long parameter lists, counted; spelled: (function, position) -> the C
+# text of that parameter; flip: the (function, position) of an int that a compiler must refuse to take for a float
+EXTENSIONS = {
+    "lwsnet_objects.h": dict(
+        source="lws_objects.hip",
+        protos={"lws_objects": (I, [VP, VP, VP, VP, I, I, I, F, F, I, I, I, I, I, I, I, VP, VP, VP, VP, VP, VP]),
+                "lws_objects_workspace": (I64, [I, I, I, I])},
+        lengths={"lws_objects": 22}, flip=("lws_objects", 6), spelled={("lws_objects", 6): "int", ("lws_objects", 7): "float"}),
+    "lwsnet_temporal.h": dict(
+        source="lws_temporal.hip",
+        protos={"lws_temporal_step": (I, [VP] * 8 + [I, I, I] + [F] * 6 + [I, F, F] + [VP] * 7), "lws_temporal_workspace": (I64, [I, I, I, I])},
+        lengths={"lws_temporal_step": 27}, flip=("lws_temporal_step", 17),
+        spelled={("lws_temporal_step", 16): "float", ("lws_temporal_step", 17): "int", ("lws_temporal_step", 18): "float"}),      # max_jump, hold, q_hold
+    "lwsnet_egomotion.h": dict(
+        source="lws_egomotion.hip",
+        protos={"lws_ego_normal": (I, [VP] * 6 + [I, I, I, I, F, F] + [VP] * 4), "lws_egomotion": (I, [VP] * 6 + [I] * 5 + [F] * 4 + [I] + [VP] * 7),
+                "lws_egomotion_workspace": (I64, [I, I, I, I])},
+        lengths={"lws_egomotion": 23, "lws_ego_normal": 16}, flip=("lws_egomotion", 15),
+        spelled={("lws_egomotion", 14): "float", ("lws_egomotion", 15): "int", ("lws_egomotion", 16): "void *",                 # damping, min_pixels, workspace
+                 ("lws_ego_normal", 5): "const double *"}),
+    "lwsnet_tsdf.h": dict(
+        source="lws_tsdf.hip",
+        protos={"lws_tsdf_integrate": (I, [VP] * 7 + [I] * 3 + [VP] * 3 + [I] * 3 + [F] * 10 + [I, F, VP, VP]),
+                "lws_tsdf_raycast": (I, [VP, VP] + [I] * 3 + [F] * 4 + [VP, VP] + [I] * 3 + [F, F, I, F] + [VP] * 4),
+                "lws_tsdf_points": (I, [VP] * 3 + [I] * 3 + [F] * 5 + [I64] + [VP] * 5), "lws_tsdf_points_workspace": (I64, [I, I])},
+        lengths={}, flip=("lws_tsdf_integrate", 26),
+        spelled={("lws_tsdf_integrate", 26): "int", ("lws_tsdf_integrate", 27): "float", ("lws_tsdf_integrate", 28): "int64_t *",  # wmode, w_max, updated
+                 ("lws_tsdf_points", 11): "int64_t"}),
+}
+
+
+def test_every_header_is_in_the_table_and_none_declares_what_another_does():
+    assert _lib.HEADERS == ("lwsnet_hip.h", *EXTENSIONS) == tuple(_lib.ABI) and _lib.ABI["lwsnet_hip.h"][0] is _lib.PROTOTYPES
+    assert len(_lib.PROTOTYPES) == 66 and _lib.ABI["lwsnet_hip.h"][1] is _lib.C_SPELLINGS
+    assert len(_lib.ALL_PROTOTYPES) == sum(len(protos) for protos, _, _ in _lib.ABI.values()) == 66 + sum(len(e["protos"]) for e in EXTENSIONS.values())
+
+
+def test_a_function_declared_by_two_headers_is_refused():
+    one = _lib.parse_header("int lws_a(int B);\nint lws_twice(const float *x, void *stream);\n", "one.h")[0]
+    two = _lib.parse_header("int64_t lws_twice(int B);\nint lws_b(void);\n", "two.h")[0]
+    assert list(_lib.merge_headers({"one.h": one, "other.h": {"lws_b": two["lws_b"]}})) == ["lws_a", "lws_twice", "lws_b"]
+    with pytest.raises(ValueError, match=r"^lws_twice is declared by one\.h and by two\.h$"):
+        _lib.merge_headers({"one.h": one, "two.h": two})
+
+
+@pytest.mark.parametrize("header", sorted(EXTENSIONS))
+def test_prototypes_of_an_extension_header(header, hip_lib):
+    """The entry points of a header behind include/lwsnet_hip.h, which lwsnet_amd._lib reads into ABI[header]: exactly its functions,
+    each as written by hand, bound that way on the loaded library; the table of include/lwsnet_hip.h is what it was."""
+    want = EXTENSIONS[header]
+    protos, spellings, path = _lib.ABI[header]
+    assert sorted(protos) == sorted(spellings) == sorted(want["protos"])
+    assert os.path.samefile(path, os.path.join(ROOT, "include", header))
+    for name, (res, args) in want["protos"].items():
+        fn = getattr(hip_lib, name)
+        assert protos[name] == (res, args) and fn.argtypes == args and fn.restype is res, name
+    for name, n in want["lengths"].items():
+        assert len(protos[name][1]) == n, name
+    assert hip_lib.lws_abi_version() == 8
+    from lwsnet_amd import build
+    assert want["source"] in build.SOURCES
+
+
+@pytest.mark.parametrize("header", sorted(EXTENSIONS))
+def test_a_compiler_agrees_with_the_reading_of_an_extension_header(header, tmp_path):
+    """As above for include/lwsnet_hip.h: per function of the header, the types the reader kept, as C text, are the function's type
+    to a C++ compiler; one int read as float fails the compile and names the function."""
+    want, spellings = EXTENSIONS[header], _lib.ABI[header][1]
+    lines = {name: _assert_line(name, sp) for name, sp in spellings.items()}
+    ok = compiles(header, tmp_path / "ext.cpp", lines.values())
+    assert ok.returncode == 0, ok.stderr
+    for (name, k), text in want["spelled"].items():
+        assert spellings[name][1][k] == text, (name, k)
+    name, k = want["flip"]
+    ret, params = spellings[name]
+    assert params[k] == "int"
+    flipped = dict(lines, **{name: _assert_line(name, (ret, params[:k] + ["float"] + params[k + 1:]))})
+    bad = compiles(header, tmp_path / "ext_flipped.cpp", flipped.values())
+    assert bad.returncode != 0 and f'"{name}"' in bad.stderr and bad.stderr.count("error:") == 1, bad.stderr
 
 
 SMALL_HEADER = """

@@ -1,17 +1,16 @@
 """Ego-motion without a GPU: the numpy restatement (tests/egomotion_reference.py) recovering known motions of the textured
 road-and-wall scene, its guard against levels that are too coarse, its Jacobian against finite differences of its own residual, the
 se(3) exponential across the threshold of its series; the host pieces (the poses writer, argument errors of the C ABI, of
-ops.ego_normal / ops.egomotion and of Odometry, the inference CLI's flags); and the binding of include/lwsnet_egomotion.h."""
+ops.ego_normal / ops.egomotion and of Odometry, the inference CLI's flags); and the CLI's pose source over a stub Odometry."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import egomotion_reference as E
 import temporal_reference as T
-from conftest import ROOT
+from cli_helpers import CAMERA, cli_refused as _cli_refused, poses_file, sequence_dir as _sequence_dir
 from lwsnet_amd import _lib
 
 F = np.float32
@@ -367,24 +366,7 @@ def test_ops_and_odometry_validate_before_any_gpu_call():
 
 
 # ---- the inference CLI ----
-CAMERA = ["--camera", "700", "700", "600", "180", "0.5"]
 NEW_FLAGS = ("egomotion", "ego_levels", "ego_iters", "ego_huber", "save_poses", "save_ego")
-
-
-def _cli_refused(argv, capsys):
-    from lwsnet_amd import inference
-    with pytest.raises(SystemExit) as e:
-        inference.main(argv + ["--synthetic_weights"])
-    assert e.value.code != 0
-    return capsys.readouterr().err
-
-
-def _sequence_dir(tmp_path, pairs):
-    for side in ("image_2", "image_3"):
-        os.makedirs(tmp_path / "seq" / side)
-        for k in range(pairs):
-            (tmp_path / "seq" / side / f"{k:06d}.png").write_bytes(b"")
-    return ["--img_path", str(tmp_path / "seq"), "--save_path", str(tmp_path / "out")]
 
 
 def test_egomotion_flags_default_off(tmp_path):
@@ -424,9 +406,8 @@ def test_cli_refuses_egomotion_without_what_it_needs(tmp_path, capsys):
     assert _cli_refused(ok + ["--ego_iters", "65"], capsys).endswith(": error: --ego_iters must be in 1 .. 64, got 65\n")
     assert _cli_refused(ok + ["--ego_huber", "0"], capsys).endswith(": error: --ego_huber must be finite and > 0, got 0.0\n")
     assert _cli_refused(ok + ["--ego_huber", "nan"], capsys).endswith(": error: --ego_huber must be finite and > 0, got nan\n")
-    poses = tmp_path / "poses.txt"
-    poses.write_text("".join(" ".join(str(float(v)) for v in T.forward_pose(k, 0.5).reshape(12)) + "\n" for k in range(3)))
-    assert _cli_refused(ok + ["--temporal", "--poses", str(poses)], capsys).endswith(
+    poses = poses_file(tmp_path / "poses.txt", 3)
+    assert _cli_refused(ok + ["--temporal", "--poses", poses], capsys).endswith(
         ": error: --temporal --egomotion takes the filter's poses from the estimate: do not give --poses as well\n")
     # --temporal alone keeps its text
     assert _cli_refused(seq + ["--temporal"] + CAMERA, capsys).endswith(": error: --temporal needs --poses PATH, the camera-to-world pose of every pair\n")
@@ -451,23 +432,34 @@ def test_odometry_step_refuses_a_frame_that_does_not_match_the_previous_one():
 
 
 def test_a_skipped_pair_keeps_its_line_of_the_poses_file(tmp_path, caplog):
-    """Pairs 0 and 3 of five are skipped: line i still belongs to pair i, a skipped pair repeating the pose before it (the identity
-    where there is none), and each skip is warned about."""
+    """The pose source over a stub Odometry whose poses() grows by one per processed pair.  Pairs 0 and 3 of five are skipped: line i
+    still belongs to pair i, a skipped pair repeating the pose before it (the identity where there is none), and each skip is
+    warned about.  The world pose is the latest accumulated one; the filter is handed None on the first frame and, with a warning,
+    for an estimate that is not to be trusted, else the estimate's own block."""
     import logging
-    import types
-    from lwsnet_amd import geometry, inference
+    from types import SimpleNamespace
+    from lwsnet_amd import geometry, ops, sequence
     poses = np.stack([T.forward_pose(k, 0.4, yaw=0.01) for k in range(3)])
-    o = inference._Odometry(types.SimpleNamespace())
+    done, handed, block = [], [], np.zeros((1, 2, 12), F)
+    src = sequence.PoseSource(5)
+    src.odometry = SimpleNamespace(poses=lambda: poses[:len(done)])
+    stage = sequence._Odometry(SimpleNamespace(save_poses=str(tmp_path / "p.txt")), src)
     log = logging.getLogger("test_egomotion_cpu")
     with caplog.at_level(logging.WARNING, logger=log.name):
-        o.skip("a.png", log)
-        o.odometry = types.SimpleNamespace(poses=lambda: poses)
-        o.lines += [0, 1]
-        o.skip("d.png", log)
-        o.lines += [2]
+        for index, name in enumerate(("a.png", "b.png", "c.png", "d.png", "e.png")):
+            if index in (0, 3):
+                stage.skip(name, log)
+                continue
+            done.append(index)                              # the stub's step
+            src.frame(index)
+            assert (src.world() == poses[len(done) - 1]).all()
+            ego = None if len(done) == 1 else SimpleNamespace(status=[1 | (ops.EGO_UNTRUSTED if index == 2 else 0)], pose=block)
+            handed.append(src.relative(SimpleNamespace(frame=SimpleNamespace(path=name), ego=ego), log))
+    assert handed[0] is None and handed[1] is None and handed[2] is block
+    skipped = "Egomotion: {} was skipped; its line of the poses file repeats the pose of the pair before it"
     assert [r.getMessage() for r in caplog.records] == [
-        f"Egomotion: {n} was skipped; its line of the poses file repeats the pose of the pair before it" for n in ("a.png", "d.png")]
-    o.write_poses(str(tmp_path / "p.txt"))
+        skipped.format("a.png"), "Temporal: the ego-motion estimate of c.png is not to be trusted (status 9): the filter starts anew", skipped.format("d.png")]
+    assert stage.finish(log) == [str(tmp_path / "p.txt")]
     got = geometry.read_kitti_poses(str(tmp_path / "p.txt"))
     ident = E.IDENTITY12.reshape(3, 4)
     assert got.shape == (5, 3, 4) and (got == np.stack([ident, poses[0], poses[1], poses[1], poses[2]])).all()
@@ -477,45 +469,3 @@ def test_ego_file_helper():
     from lwsnet_amd import outputs
     u8 = outputs.ego_to_u8(np.array([[0.0, -0.4, 0.6], [-12.5, 254.6, -1e9]], F))
     assert u8.dtype == np.uint8 and u8.tolist() == [[0, 0, 1], [12, 255, 255]]
-
-
-# ---- binding ----
-def test_prototypes_of_the_egomotion_header(hip_lib):
-    VP, I, Fl = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-    protos = _lib.EGOMOTION_PROTOTYPES
-    assert sorted(protos) == sorted(_lib.EGOMOTION_SPELLINGS) == ["lws_ego_normal", "lws_egomotion", "lws_egomotion_workspace"]
-    for other in (_lib.PROTOTYPES, _lib.EXTENSION_PROTOTYPES, _lib.TEMPORAL_PROTOTYPES):
-        assert not set(protos) & set(other)
-    assert len(_lib.PROTOTYPES) == 66 and sorted(_lib.TEMPORAL_PROTOTYPES) == ["lws_temporal_step", "lws_temporal_workspace"]
-    assert protos["lws_ego_normal"] == (I, [VP] * 6 + [I, I, I, I, Fl, Fl] + [VP] * 4)
-    assert protos["lws_egomotion"] == (I, [VP] * 6 + [I] * 5 + [Fl] * 4 + [I] + [VP] * 7)
-    assert hip_lib.lws_egomotion.argtypes == protos["lws_egomotion"][1] and len(protos["lws_egomotion"][1]) == 23
-    assert hip_lib.lws_ego_normal.argtypes == protos["lws_ego_normal"][1] and len(protos["lws_ego_normal"][1]) == 16
-    assert protos["lws_egomotion_workspace"] == (ctypes.c_int64, [I, I, I, I])
-    assert hip_lib.lws_egomotion_workspace.restype is ctypes.c_int64
-    assert hip_lib.lws_abi_version() == 8
-    assert os.path.samefile(_lib.EGOMOTION_HEADER_PATH, os.path.join(ROOT, "include", "lwsnet_egomotion.h"))
-    from lwsnet_amd import build
-    assert "lws_egomotion.hip" in build.SOURCES
-
-
-def test_a_compiler_agrees_with_the_reading_of_the_egomotion_header(tmp_path):
-    """As tests/test_abi_cpu.py does for include/lwsnet_hip.h: per function of include/lwsnet_egomotion.h, the types the reader kept,
-    as C text, are the function's type to a C++ compiler; one int read as float fails the compile and names the function."""
-    from test_abi_cpu import _assert_line, _host_compiler
-    cxx = _host_compiler()
-
-    def compiles(path, lines):
-        with open(path, "w") as f:
-            f.write('#include <type_traits>\n#include "lwsnet_egomotion.h"\n' + "".join(lines))
-        return subprocess.run([cxx, "-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(path)], capture_output=True, text=True)
-
-    lines = {name: _assert_line(name, sp) for name, sp in _lib.EGOMOTION_SPELLINGS.items()}
-    ok = compiles(tmp_path / "egomotion.cpp", lines.values())
-    assert ok.returncode == 0, ok.stderr
-    ret, params = _lib.EGOMOTION_SPELLINGS["lws_egomotion"]
-    assert params[14] == "float" and params[15] == "int" and params[16] == "void *"         # damping, min_pixels, workspace
-    assert _lib.EGOMOTION_SPELLINGS["lws_ego_normal"][1][5] == "const double *"
-    flipped = dict(lines, lws_egomotion=_assert_line("lws_egomotion", (ret, params[:15] + ["float"] + params[16:])))
-    bad = compiles(tmp_path / "egomotion_flipped.cpp", flipped.values())
-    assert bad.returncode != 0 and '"lws_egomotion"' in bad.stderr and bad.stderr.count("error:") == 1, bad.stderr

@@ -9,6 +9,7 @@ import pytest
 from PIL import Image
 
 import geometry_reference as G
+from cli_helpers import CAMERA, cli_refused as _refused
 from lwsnet_amd import _lib
 from lwsnet_amd.geometry import POINT_DTYPE, Camera, read_ply, write_ply
 
@@ -248,14 +249,6 @@ def test_point_cloud_rejects_bad_arguments(hip_lib):
 
 
 # ---- the inference CLI refuses before any model or GPU work ----
-def _refused(argv, capsys):
-    from lwsnet_amd import inference
-    with pytest.raises(SystemExit) as e:
-        inference.main(argv + ["--synthetic_weights"])
-    assert e.value.code != 0
-    return capsys.readouterr().err
-
-
 @pytest.mark.parametrize("flag", ["--save_depth", "--save_ply"])
 def test_cli_refuses_depth_without_camera(flag, capsys):
     assert "need a camera" in _refused([flag], capsys)
@@ -300,7 +293,6 @@ def test_geometry_flags_default_off():
     assert a.min_disp == 1.0 and a.max_depth == float("inf")
 
 
-CAMERA = ["--camera", "700", "700", "600", "180", "0.5"]
 NEEDS_CAMERA = " need a camera: --calib PATH or --camera FX FY CX CY BASELINE"
 SEQUENTIAL = " in the sequential mode only: use --workers 0"
 OUTPUTS_SEQUENTIAL = "--save_disp16 / --save_depth / --save_ply / --save_normals / --save_mesh run" + SEQUENTIAL

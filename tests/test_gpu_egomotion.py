@@ -532,3 +532,119 @@ def test_inference_cli_egomotion_files(dev, model, tmp_path):
     assert trusted_frames >= 1                              # the filter was fed an estimate at least once
     got = read_kitti_poses(str(pose_file))
     assert got.shape == (n, 3, 4) and (got[0] == world[0]).all() and (got == np.stack(world)).all()
+
+
+# ---- the CLI's three sequence stages together, over four pairs of which pair 1 is skipped ----
+@pytest.fixture(scope="module")
+def gap_sequence(dev, model, tmp_path_factory):
+    """(the CLI flags of a KITTI tree whose pair 1 is smaller than the crop, with its calibration and --occ_check 1; per processed pair
+    its index, stem, left crop, camera and the chain's stage-4 map and `keep` codes), computed once."""
+    from PIL import Image
+    from lwsnet_amd import imageio as io, postprocess as post, synth
+    from lwsnet_amd.geometry import Camera
+    base = tmp_path_factory.mktemp("gap")
+    root = str(base / "kitti")
+    synth.write_kitti_tree(root, 4)
+    for side in ("image_2", "image_3"):
+        Image.fromarray(np.zeros((io.CROP_H - 1, io.CROP_W, 3), np.uint8)).save(os.path.join(root, side, "000001_10.png"))
+    (base / "calib.txt").write_text(KITTI15_CALIB.format(fx=721.5377, cx=609.5593, cy=172.854, t3=44.85728 - 0.54 * 721.5377))
+    frames = []
+    for k, stem in ((k, f"{k:06d}_10") for k in (0, 2, 3)):
+        full = io.load_rgb(os.path.join(root, "image_2", stem + ".png"))
+        left = io.crop_bottom_right(full)
+        r_in = io.to_input(io.crop_bottom_right(io.load_rgb(os.path.join(root, "image_3", stem + ".png"))))[None]
+        res = post.run_chain(model, io.to_input(left)[None], r_in, post.Options.make(occ_check=1.0))
+        cam = Camera.from_kitti(str(base / "calib.txt")).crop_bottom_right(*full.shape[:2])
+        frames.append((k, stem, left, cam, res.disp[3].as_subclass(torch.Tensor).clone(), res.keep[3].clone()))
+    return ["--img_path", root + "/", "--synthetic_weights", "--calib", str(base / "calib.txt"), "--occ_check", "1"], frames
+
+
+def _by_hand(dev, frames, out, tmp, vol, hold, motion):
+    """The filter and the volume composed by hand over `frames`, their files compared byte for byte with the CLI's in `out`.
+    motion(k, rgb, d, keep) -> (the EgoResult or None, the filter's pose block or None, the camera-to-world pose [3,4]); the volume's
+    frame is the first camera integrated.  Returns the voxels updated per frame."""
+    from lwsnet_amd import imageio as io, ops, outputs
+    from lwsnet_amd.temporal import TemporalFilter
+    filt, first, updated, inf = None, None, [], float("inf")
+    for k, stem, left, cam, d, keep in frames:
+        filt = filt or TemporalFilter(cam, gate=3.0, q=0.0, sigma0=0.5, hold=hold, min_disp=1.0)
+        rgb = outputs.rgb_on_device(left, dev)
+        ego, pose, world = motion(k, rgb, d, keep)
+        fused = filt.step(d, pose, mask=keep)
+        kept = (fused.code != 0).to(torch.uint8)
+        world = np.vstack([world, [0.0, 0.0, 0.0, 1.0]])
+        first = world if first is None else first
+        into_first = np.linalg.solve(first, world)[:3]
+        normals = ops.surface_normals(fused.disp, cam, mask=kept, min_disp=1.0, max_depth=inf, max_jump=1.0)[0]
+        updated.append(int(vol.integrate(fused.disp, cam, into_first, sigma=torch.sqrt(fused.var), mask=kept, normals=normals, rgb=rgb)[0]))
+        view = vol.raycast(cam, into_first, *d.shape[2:], z_near=0.5, weight=False, normals=False)
+        want = {".png": (io.save_png, io.disparity_to_color(fused.disp[0, 0].cpu().numpy())),
+                "_tcode.png": (io.save_png, outputs.temporal_to_rgb(fused.code[0, 0].cpu().numpy())),
+                "_tsigma.png": (outputs.save_png_gray8, outputs.sigma_to_u8(np.sqrt(fused.var[0, 0].cpu().numpy().astype(np.float64)), 8.0)),
+                "_ego.png": (outputs.save_png_gray8, np.zeros(left.shape[:2], np.uint8) if ego is None else outputs.ego_to_u8(ego.resid[0, 0].cpu().numpy())),
+                "_tsdf.png": (io.save_png, io.disparity_to_color(view.disp[0, 0].cpu().numpy()))}
+        for suffix in (s for s in want if os.path.exists(out / (stem + s))):
+            want[suffix][0](str(tmp / "want.png"), want[suffix][1])
+            assert (out / (stem + suffix)).read_bytes() == (tmp / "want.png").read_bytes(), stem + suffix
+    return updated
+
+
+def test_inference_cli_three_stages_over_a_gap_with_estimated_poses(dev, model, gap_sequence, tmp_path, caplog):
+    """--egomotion, --temporal and --tsdf in one run: the filter takes the estimate's motion (nothing on the first frame and after an
+    estimate that is not to be trusted), the volume the accumulated pose and the filter's map and sigma.  Every file is what Odometry,
+    TemporalFilter, ops.surface_normals and TsdfVolume give composed by hand; the skipped pair keeps its line of the poses file."""
+    import logging
+    import re
+    from lwsnet_amd import inference, ops
+    from lwsnet_amd.egomotion import Odometry
+    from lwsnet_amd.geometry import read_kitti_poses, read_mesh_ply
+    from lwsnet_amd.tsdf import TsdfVolume
+    flags, frames = gap_sequence
+    out, pose_file, ply = tmp_path / "out", tmp_path / "est_poses.txt", tmp_path / "map.ply"
+    with caplog.at_level(logging.INFO, logger="lwsnet_amd.inference"):
+        written = inference.main(flags + ["--save_path", str(out), "--egomotion", "--ego_levels", "3", "--ego_iters", "4", "--save_poses", str(pose_file),
+                                          "--save_ego", "--temporal", "--save_temporal", "--tsdf", "--tsdf_voxel", "0.4", "--tsdf_extent", "-8", "8", "-3.2", "3.2",
+                                          "0", "32", "--tsdf_weight", "sigma", "--save_tsdf", "--save_tsdf_ply", str(ply)])
+    names = [stem + e for _, stem, *_ in frames for e in (".png", "_occ.png", "_tcode.png", "_tsigma.png", "_ego.png", "_tsdf.png")]
+    assert sorted(os.listdir(out)) == sorted(names) and written == [str(out / n) for n in names] + [str(pose_file), str(ply)]
+    lines = [r.getMessage() for r in caplog.records]
+    assert "TSDF: volume 41 x 17 x 81 voxels of 0.4 m from (-8, -3.2, 0), {} bytes".format(12 * 41 * 17 * 81) in lines
+    odo, world, resets = Odometry(frames[0][3], levels=3, iters=4, huber=10.0, min_disp=1.0), {}, []
+
+    def motion(k, rgb, d, keep):                            # pair 2 is aligned with pair 0: the estimate spans the gap
+        ego = odo.step(rgb, d, keep, resid=True)
+        world[k] = odo.poses()[-1]
+        trusted = ego is not None and not int(ego.status[0]) & ops.EGO_UNTRUSTED
+        resets.extend([k] * (ego is not None and not trusted))
+        return ego, ego.pose if trusted else None, world[k]
+
+    vol = TsdfVolume((-8.0, -3.2, 0.0), 0.4, (41, 17, 81), mu0=3.0 * 0.4, weight="sigma", colour=True, min_disp=1.0, max_depth=float("inf"), device=dev)
+    updated = _by_hand(dev, frames, out, tmp_path, vol, False, motion)
+    assert sum(line.startswith("Temporal: the ego-motion estimate") for line in lines) == len(resets)
+    assert [int(m[1]) for m in (re.fullmatch(r"TSDF: voxels updated = (\d+)", line) for line in lines) if m] == updated and min(updated) > 0
+    got = read_kitti_poses(str(pose_file))
+    assert got.shape == (4, 3, 4) and (got[1] == got[0]).all() and (got == np.stack([world[0], world[0], world[2], world[3]])).all()
+    n = vol.write_ply(str(tmp_path / "by_hand.ply"))
+    logged = [int(m[1]) for m in (re.fullmatch(r"Save TSDF points = .*, vertices = (\d+)", line) for line in lines) if m]
+    assert logged == [n] and len(read_mesh_ply(str(ply))[0]) == n > 0 and ply.read_bytes() == (tmp_path / "by_hand.ply").read_bytes()
+
+
+def test_inference_cli_filter_and_volume_over_a_gap_with_given_poses(dev, model, gap_sequence, tmp_path):
+    """--poses of four lines over the same tree: the third and fourth pairs take lines 2 and 3 of the file -- a pose source that
+    counted the frames processed would take lines 1 and 2 -- and the filter bridges the gap with relative_pose(line 0, line 2)."""
+    from lwsnet_amd import inference
+    from lwsnet_amd.geometry import relative_pose
+    from lwsnet_amd.tsdf import TsdfVolume
+    flags, frames = gap_sequence
+    poses = np.stack([T.forward_pose(k, 0.3, yaw=0.002) for k in range(4)])
+    pose_file, out, seen = tmp_path / "poses.txt", tmp_path / "out", []
+    pose_file.write_text("".join(" ".join(repr(float(v)) for v in p.reshape(12)) + "\n" for p in poses))
+    inference.main(flags + ["--save_path", str(out), "--poses", str(pose_file), "--temporal", "--temporal_hold", "--tsdf", "--save_tsdf"])
+    assert sorted(os.listdir(out)) == sorted(stem + e for _, stem, *_ in frames for e in (".png", "_occ.png", "_tsdf.png"))
+
+    def motion(k, rgb, d, keep):
+        seen.append(k)
+        return None, relative_pose(poses[seen[-2]], poses[k]) if len(seen) > 1 else None, poses[k]
+
+    vol = TsdfVolume((-12.8, -3.2, 0.0), 0.2, (129, 33, 257), mu0=3.0 * 0.2, colour=True, min_disp=1.0, max_depth=float("inf"), device=dev)
+    assert min(_by_hand(dev, frames, out, tmp_path, vol, True, motion)) > 0 and seen == [0, 2, 3]

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import ground_reference as G
+from cli_helpers import CAMERA, cli_refused as _cli_refused
 from lwsnet_amd import _lib
 from lwsnet_amd.geometry import Camera, GroundPlane
 
@@ -309,16 +310,7 @@ def test_ops_validate_before_any_gpu_call():
 
 
 # ---- the inference CLI ----
-CAMERA = ["--camera", "700", "700", "600", "180", "0.5"]
 NEW_FLAGS = ("ground", "save_ground", "ground_tol", "max_height")
-
-
-def _cli_refused(argv, capsys):
-    from lwsnet_amd import inference
-    with pytest.raises(SystemExit) as e:
-        inference.main(argv + ["--synthetic_weights"])
-    assert e.value.code != 0
-    return capsys.readouterr().err
 
 
 def test_ground_flags_default_off():

@@ -9,6 +9,7 @@ import pytest
 
 import geometry_reference as G
 import mesh_reference as M
+from cli_helpers import CAMERA, cli_refused as _refused
 from lwsnet_amd import _lib
 from lwsnet_amd.geometry import POINT_DTYPE, VERTEX_NORMAL_DTYPE, Camera, camera_rows, mesh_ply_bytes, read_mesh_ply, write_mesh_ply
 
@@ -314,17 +315,6 @@ def test_mesh_ply_rejects_what_it_cannot_write():
 
 
 # ---- the inference CLI refuses before any model or GPU work ----
-CAMERA = ["--camera", "700", "700", "600", "180", "0.5"]
-
-
-def _refused(argv, capsys):
-    from lwsnet_amd import inference
-    with pytest.raises(SystemExit) as e:
-        inference.main(argv + ["--synthetic_weights"])
-    assert e.value.code != 0
-    return capsys.readouterr().err
-
-
 @pytest.mark.parametrize("flag", ["--save_normals", "--save_mesh"])
 def test_cli_refuses_surface_outputs_without_camera(flag, capsys):
     assert "--save_normals and --save_mesh need a camera" in _refused([flag], capsys)

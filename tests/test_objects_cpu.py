@@ -4,13 +4,13 @@ raised before any GPU work; the CSV and PNG helpers on a two-object example."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import object_reference as O
 import stixel_reference as X
+from cli_helpers import CAMERA, cli_refused as _cli_refused
 from conftest import ROOT
 from lwsnet_amd import _lib
 from test_stixels_cpu import CAM, CAM1, scene
@@ -187,44 +187,7 @@ def test_objects_rejects_bad_arguments(hip_lib):
         assert hip_lib.lws_objects_workspace(*dims) == _lib.LWS_ERR_INVALID and hip_lib.lws_last_error() == msg
     assert hip_lib.lws_objects_workspace(3, 13, 4, 70) == (3 * 4 * 70 * 4 // 256 * 256 + 256) + 3 * 4 * 70 * 64 + 256
     assert hip_lib.lws_objects_workspace(2, 1232, 8, 768) == 2 * 154 * 768 * 68 + 2048          # 58 blocks of 2048 cells an image: 1856 bytes of counts
-
-
-def test_prototype_matches_the_library(hip_lib):
-    """The two entry points are declared in include/lwsnet_objects.h, which lwsnet_amd._lib reads into EXTENSION_PROTOTYPES; the
-    table of include/lwsnet_hip.h is what it was."""
-    VP, I, Fl = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-    protos = _lib.EXTENSION_PROTOTYPES
-    assert sorted(protos) == sorted(_lib.EXTENSION_SPELLINGS) == ["lws_objects", "lws_objects_workspace"]
-    assert not set(protos) & set(_lib.PROTOTYPES)
-    assert protos["lws_objects"] == (I, [VP, VP, VP, VP, I, I, I, Fl, Fl, I, I, I, I, I, I, I, VP, VP, VP, VP, VP, VP])
-    assert hip_lib.lws_objects.argtypes == protos["lws_objects"][1] and len(protos["lws_objects"][1]) == 22
-    assert protos["lws_objects_workspace"] == (ctypes.c_int64, [I, I, I, I])
-    assert hip_lib.lws_objects_workspace.argtypes == [I, I, I, I] and hip_lib.lws_objects_workspace.restype is ctypes.c_int64
-    assert hip_lib.lws_abi_version() == 8
-    from lwsnet_amd import build
-    assert "lws_objects.hip" in build.SOURCES
     assert tile() == (64, 32)
-
-
-def test_a_compiler_agrees_with_the_reading_of_the_extension_header(tmp_path):
-    """As tests/test_abi_cpu.py does for include/lwsnet_hip.h: per function of include/lwsnet_objects.h, the types the reader kept, as C
-    text, are the function's type to a C++ compiler; one int read as float fails the compile and names the function."""
-    from test_abi_cpu import _assert_line, _host_compiler
-    cxx = _host_compiler()
-
-    def compiles(path, lines):
-        with open(path, "w") as f:
-            f.write('#include <type_traits>\n#include "lwsnet_objects.h"\n' + "".join(lines))
-        return subprocess.run([cxx, "-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(path)], capture_output=True, text=True)
-
-    lines = {name: _assert_line(name, sp) for name, sp in _lib.EXTENSION_SPELLINGS.items()}
-    ok = compiles(tmp_path / "ext.cpp", lines.values())
-    assert ok.returncode == 0, ok.stderr
-    ret, params = _lib.EXTENSION_SPELLINGS["lws_objects"]
-    assert params[6] == "int" and params[7] == "float"
-    flipped = dict(lines, lws_objects=_assert_line("lws_objects", (ret, params[:6] + ["float"] + params[7:])))
-    bad = compiles(tmp_path / "ext_flipped.cpp", flipped.values())
-    assert bad.returncode != 0 and '"lws_objects"' in bad.stderr and bad.stderr.count("error:") == 1, bad.stderr
 
 
 def test_ops_validate_before_any_gpu_call():
@@ -245,16 +208,7 @@ def test_ops_validate_before_any_gpu_call():
 
 
 # ---- the inference CLI ----
-CAMERA = ["--camera", "700", "700", "600", "180", "0.5"]
 NEW_FLAGS = ("objects", "save_objects", "object_min_pixels")
-
-
-def _cli_refused(argv, capsys):
-    from lwsnet_amd import inference
-    with pytest.raises(SystemExit) as e:
-        inference.main(argv + ["--synthetic_weights"])
-    assert e.value.code != 0
-    return capsys.readouterr().err
 
 
 def test_object_flags_default_off():

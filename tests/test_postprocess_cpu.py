@@ -166,4 +166,7 @@ def test_check_rejects_what_the_cli_tests_reject():
                 dict(wmedian=1, wmedian_fill=2 ** 31)):
         with pytest.raises(ValueError):
             Options.make(**bad).check()
+    for flag, name in (("lr_check", "--lr_check TAU"), ("occ_check", "--occ_check TAU"), ("speckle_diff", "--speckle_diff D"), ("wmedian_sigma", "--wmedian_sigma S")):
+        with pytest.raises(ValueError, match=f"^{name} must be finite and >= 0, got -1.0$"):      # the whole sentence, which the CLIs pass on as it is
+            Options.make(**{"speckle": 5, "wmedian": 1, flag: -1}).check()
     Options.make(lr_check=0.0, speckle=2 ** 31 - 1, speckle_diff=0.0, wmedian=3, wmedian_sigma=0.0, wmedian_fill=2 ** 31 - 1).check()

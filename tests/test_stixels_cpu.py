@@ -8,6 +8,7 @@ import pytest
 
 import ground_reference as G
 import stixel_reference as X
+from cli_helpers import CAMERA, cli_refused as _cli_refused
 from lwsnet_amd import _lib
 from lwsnet_amd.geometry import Camera
 from test_gpu_ground import ROAD
@@ -259,16 +260,7 @@ def test_ops_validate_before_any_gpu_call():
 
 
 # ---- the inference CLI ----
-CAMERA = ["--camera", "700", "700", "600", "180", "0.5"]
 NEW_FLAGS = ("stixels", "save_stixels", "stixel_width", "stixel_layers")
-
-
-def _cli_refused(argv, capsys):
-    from lwsnet_amd import inference
-    with pytest.raises(SystemExit) as e:
-        inference.main(argv + ["--synthetic_weights"])
-    assert e.value.code != 0
-    return capsys.readouterr().err
 
 
 def test_stixel_flags_default_off():

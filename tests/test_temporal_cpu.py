@@ -1,16 +1,15 @@
 """The temporal filter without a GPU: the numpy restatement (tests/temporal_reference.py) on an identity pose, on a box that jumps,
 on pixels entering the view and on bad input; its noise and its hold on the synthetic road-and-wall scene, held to the conditions
 the feature was asked to meet; the host pieces (poses, argument errors of the C ABI, of ops.temporal_step, of TemporalFilter and of
-the inference CLI's flags); and the binding of include/lwsnet_temporal.h."""
+the inference CLI's flags); and the CLI's pose source over a poses file with skipped pairs."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import temporal_reference as T
-from conftest import ROOT
+from cli_helpers import CAMERA, cli_refused as _cli_refused, poses_file, sequence_dir
 from lwsnet_amd import _lib
 
 F = np.float32
@@ -268,27 +267,7 @@ def test_ops_and_filter_validate_before_any_gpu_call():
 
 
 # ---- the inference CLI ----
-CAMERA = ["--camera", "700", "700", "600", "180", "0.5"]
 NEW_FLAGS = ("temporal", "poses", "temporal_gate", "temporal_q", "temporal_sigma", "temporal_hold", "save_temporal")
-
-
-def _cli_refused(argv, capsys):
-    from lwsnet_amd import inference
-    with pytest.raises(SystemExit) as e:
-        inference.main(argv + ["--synthetic_weights"])
-    assert e.value.code != 0
-    return capsys.readouterr().err
-
-
-def _sequence_dir(tmp_path, pairs, poses):
-    """A folder with `pairs` (empty) image files per side and a poses file of `poses` lines: enough for the flag checks."""
-    for side in ("image_2", "image_3"):
-        os.makedirs(tmp_path / "seq" / side)
-        for k in range(pairs):
-            (tmp_path / "seq" / side / f"{k:06d}.png").write_bytes(b"")
-    path = tmp_path / "poses.txt"
-    path.write_text("".join(" ".join(str(float(v)) for v in T.forward_pose(k, 0.5).reshape(12)) + "\n" for k in range(poses)))
-    return ["--img_path", str(tmp_path / "seq"), "--save_path", str(tmp_path / "out")], str(path)
 
 
 def test_temporal_flags_default_off(tmp_path):
@@ -302,7 +281,7 @@ def test_temporal_flags_default_off(tmp_path):
     inference.check_geometry_arguments(p, a)
     inference.check_temporal_arguments(p, a)
     assert tuple(getattr(a, f) for f in NEW_FLAGS) == (False, None, 3.0, 0.0, "0.5", False, False)
-    seq, poses = _sequence_dir(tmp_path, 3, 3)
+    seq, poses = sequence_dir(tmp_path, 3), poses_file(tmp_path / "poses.txt", 3)
     a = p.parse_args(seq + ["--save_temporal", "--poses", poses, "--temporal_sigma", "net", "--temporal_hold"] + CAMERA)
     inference.check_occ_arguments(p, a)
     inference.check_geometry_arguments(p, a)
@@ -313,8 +292,7 @@ def test_temporal_flags_default_off(tmp_path):
 
 
 def test_cli_refuses_temporal_without_what_it_needs(tmp_path, capsys):
-    seq, poses = _sequence_dir(tmp_path, 4, 3)
-    _, enough = _sequence_dir(tmp_path / "b", 4, 4)
+    seq, poses, enough = sequence_dir(tmp_path, 4), poses_file(tmp_path / "poses.txt", 3), poses_file(tmp_path / "enough.txt", 4)
     ok = seq + ["--temporal", "--poses", enough] + CAMERA
     assert _cli_refused(seq + ["--temporal"] + CAMERA, capsys).endswith(": error: --temporal needs --poses PATH, the camera-to-world pose of every pair\n")
     assert _cli_refused(seq + ["--temporal", "--poses", enough], capsys).endswith(
@@ -345,39 +323,20 @@ def test_temporal_file_helpers():
     assert outputs.TEMPORAL_CODES == ("nothing", "new", "fused", "reset", "held")
 
 
-# ---- binding ----
-def test_prototypes_of_the_temporal_header(hip_lib):
-    VP, I, Fl = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-    protos = _lib.TEMPORAL_PROTOTYPES
-    assert sorted(protos) == sorted(_lib.TEMPORAL_SPELLINGS) == ["lws_temporal_step", "lws_temporal_workspace"]
-    assert not set(protos) & set(_lib.PROTOTYPES) and not set(protos) & set(_lib.EXTENSION_PROTOTYPES)
-    assert sorted(_lib.EXTENSION_PROTOTYPES) == ["lws_objects", "lws_objects_workspace"] and len(_lib.PROTOTYPES) == 66
-    assert protos["lws_temporal_step"] == (I, [VP] * 8 + [I, I, I] + [Fl] * 6 + [I, Fl, Fl] + [VP] * 7)
-    assert hip_lib.lws_temporal_step.argtypes == protos["lws_temporal_step"][1] and len(protos["lws_temporal_step"][1]) == 27
-    assert protos["lws_temporal_workspace"] == (ctypes.c_int64, [I, I, I, I])
-    assert hip_lib.lws_temporal_workspace.restype is ctypes.c_int64
-    assert hip_lib.lws_abi_version() == 8
-    assert os.path.samefile(_lib.TEMPORAL_HEADER_PATH, os.path.join(ROOT, "include", "lwsnet_temporal.h"))
-    from lwsnet_amd import build
-    assert "lws_temporal.hip" in build.SOURCES
-
-
-def test_a_compiler_agrees_with_the_reading_of_the_temporal_header(tmp_path):
-    """As tests/test_abi_cpu.py does for include/lwsnet_hip.h: per function of include/lwsnet_temporal.h, the types the reader kept, as
-    C text, are the function's type to a C++ compiler; one int read as float fails the compile and names the function."""
-    from test_abi_cpu import _assert_line, _host_compiler
-    cxx = _host_compiler()
-
-    def compiles(path, lines):
-        with open(path, "w") as f:
-            f.write('#include <type_traits>\n#include "lwsnet_temporal.h"\n' + "".join(lines))
-        return subprocess.run([cxx, "-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(path)], capture_output=True, text=True)
-
-    lines = {name: _assert_line(name, sp) for name, sp in _lib.TEMPORAL_SPELLINGS.items()}
-    ok = compiles(tmp_path / "temporal.cpp", lines.values())
-    assert ok.returncode == 0, ok.stderr
-    ret, params = _lib.TEMPORAL_SPELLINGS["lws_temporal_step"]
-    assert params[16] == "float" and params[17] == "int" and params[18] == "float"          # max_jump, hold, q_hold
-    flipped = dict(lines, lws_temporal_step=_assert_line("lws_temporal_step", (ret, params[:17] + ["float"] + params[18:])))
-    bad = compiles(tmp_path / "temporal_flipped.cpp", flipped.values())
-    assert bad.returncode != 0 and '"lws_temporal_step"' in bad.stderr and bad.stderr.count("error:") == 1, bad.stderr
+def test_pose_source_counts_pairs_not_processed_frames():
+    """The CLI's pose source over a poses file of five lines, pairs 1 and 3 skipped: the filter is handed nothing on the first frame,
+    then geometry.relative_pose of the two pairs it fuses, bit for bit; the world pose of pair 4 is line 4, not the third line."""
+    from types import SimpleNamespace
+    from lwsnet_amd import geometry, sequence
+    poses = np.stack([T.forward_pose(k, 0.7, yaw=0.03, dx=0.1) for k in range(5)])
+    src = sequence.PoseSource(5, poses)
+    handed = {}
+    for index in (0, 2, 4):
+        src.frame(index)
+        handed[index] = src.relative(SimpleNamespace(frame=SimpleNamespace(path=f"{index}.png"), ego=None), None)
+        assert (src.world() == poses[index]).all()
+    assert handed[0] is None and (src.world() != poses[2]).any()
+    for prev, index in ((0, 2), (2, 4)):
+        want = geometry.relative_pose(poses[prev], poses[index])
+        assert handed[index].dtype == want.dtype == np.float32 and handed[index].tobytes() == want.tobytes()
+        assert handed[index].tobytes() != geometry.relative_pose(poses[index - 1], poses[index]).tobytes()

@@ -1,9 +1,8 @@
 """The TSDF volume without a GPU: what the numpy restatement (tests/tsdf_reference.py) gives on the exact wall and on the road
 scene, that the cases of tests/test_gpu_tsdf.py reach every branch of the rules, the argument checks of the C entry points, of
-lwsnet_amd.ops.tsdf_* and of TsdfVolume, and the binding of include/lwsnet_tsdf.h."""
+lwsnet_amd.ops.tsdf_* and of TsdfVolume, and the inference CLI's flags."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,7 +10,7 @@ import pytest
 import mesh_reference as M
 import temporal_reference as TR
 import tsdf_reference as R
-from conftest import ROOT
+from cli_helpers import CAMERA, cli_refused as _cli_refused, poses_file as _poses_file, sequence_dir as _sequence_dir
 from lwsnet_amd import _lib
 
 F = np.float32
@@ -344,73 +343,8 @@ def test_ops_and_the_volume_validate_before_any_gpu_call():
     assert ops.TsdfView._fields == ("disp", "weight", "normals") and ops.TsdfPoints._fields == ("points", "vnormals", "counts")
 
 
-# ---- binding ----
-def test_prototypes_of_the_tsdf_header(hip_lib):
-    VP, I, Fl, I64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64
-    protos = _lib.TSDF_PROTOTYPES
-    assert sorted(protos) == sorted(_lib.TSDF_SPELLINGS) == ["lws_tsdf_integrate", "lws_tsdf_points", "lws_tsdf_points_workspace", "lws_tsdf_raycast"]
-    for other in (_lib.PROTOTYPES, _lib.EXTENSION_PROTOTYPES, _lib.TEMPORAL_PROTOTYPES, _lib.EGOMOTION_PROTOTYPES):
-        assert not set(protos) & set(other)
-    assert len(_lib.PROTOTYPES) == 66 and sorted(_lib.EGOMOTION_PROTOTYPES) == ["lws_ego_normal", "lws_egomotion", "lws_egomotion_workspace"]
-    assert protos["lws_tsdf_integrate"] == (I, [VP] * 7 + [I] * 3 + [VP] * 3 + [I] * 3 + [Fl] * 10 + [I, Fl, VP, VP])
-    assert protos["lws_tsdf_raycast"] == (I, [VP, VP] + [I] * 3 + [Fl] * 4 + [VP, VP] + [I] * 3 + [Fl, Fl, I, Fl] + [VP] * 4)
-    assert protos["lws_tsdf_points"] == (I, [VP] * 3 + [I] * 3 + [Fl] * 5 + [I64] + [VP] * 5)
-    assert protos["lws_tsdf_points_workspace"] == (I64, [I, I])
-    for name, (res, args) in protos.items():
-        fn = getattr(hip_lib, name)
-        assert fn.argtypes == args and fn.restype is res
-    assert hip_lib.lws_abi_version() == 8
-    assert os.path.samefile(_lib.TSDF_HEADER_PATH, os.path.join(ROOT, "include", "lwsnet_tsdf.h"))
-    from lwsnet_amd import build
-    assert "lws_tsdf.hip" in build.SOURCES
-
-
-def test_a_compiler_agrees_with_the_reading_of_the_tsdf_header(tmp_path):
-    """As tests/test_abi_cpu.py does for include/lwsnet_hip.h: per function of include/lwsnet_tsdf.h, the types the reader kept, as C
-    text, are the function's type to a C++ compiler; one int read as float fails the compile and names the function."""
-    from test_abi_cpu import _assert_line, _host_compiler
-    cxx = _host_compiler()
-
-    def compiles(path, lines):
-        with open(path, "w") as f:
-            f.write('#include <type_traits>\n#include "lwsnet_tsdf.h"\n' + "".join(lines))
-        return subprocess.run([cxx, "-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(path)], capture_output=True, text=True)
-
-    lines = {name: _assert_line(name, sp) for name, sp in _lib.TSDF_SPELLINGS.items()}
-    ok = compiles(tmp_path / "tsdf.cpp", lines.values())
-    assert ok.returncode == 0, ok.stderr
-    ret, params = _lib.TSDF_SPELLINGS["lws_tsdf_integrate"]
-    assert params[26] == "int" and params[27] == "float" and params[28] == "int64_t *"          # wmode, w_max, updated
-    assert _lib.TSDF_SPELLINGS["lws_tsdf_points"][1][11] == "int64_t"
-    flipped = dict(lines, lws_tsdf_integrate=_assert_line("lws_tsdf_integrate", (ret, params[:26] + ["float"] + params[27:])))
-    bad = compiles(tmp_path / "tsdf_flipped.cpp", flipped.values())
-    assert bad.returncode != 0 and '"lws_tsdf_integrate"' in bad.stderr and bad.stderr.count("error:") == 1, bad.stderr
-
-
 # ---- the inference CLI ----
-CAMERA = ["--camera", "700", "700", "600", "180", "0.5"]
 NEW_FLAGS = ("tsdf", "tsdf_voxel", "tsdf_extent", "tsdf_trunc", "tsdf_trunc_px", "tsdf_weight", "tsdf_sdf", "save_tsdf_ply", "save_tsdf")
-
-
-def _cli_refused(argv, capsys):
-    from lwsnet_amd import inference
-    with pytest.raises(SystemExit) as e:
-        inference.main(argv + ["--synthetic_weights"])
-    assert e.value.code != 0
-    return capsys.readouterr().err
-
-
-def _sequence_dir(tmp_path, pairs):
-    for side in ("image_2", "image_3"):
-        os.makedirs(tmp_path / "seq" / side)
-        for k in range(pairs):
-            (tmp_path / "seq" / side / f"{k:06d}.png").write_bytes(b"")
-    return ["--img_path", str(tmp_path / "seq"), "--save_path", str(tmp_path / "out")]
-
-
-def _poses_file(path, n):
-    path.write_text("".join(" ".join(str(float(v)) for v in TR.forward_pose(k, 0.5).reshape(12)) + "\n" for k in range(n)))
-    return str(path)
 
 
 def test_tsdf_flags_default_off(tmp_path):
