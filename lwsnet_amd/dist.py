@@ -234,6 +234,12 @@ class StagedGather:
             self.pending[b] = gather_async(self.staging[b], self.recv[b], dst=self.dst)
         else:
             self.recv[b][0].copy_(self.staging[b])
+            if self.on_gpu:
+                # without a process group the gather is this copy, queued on the current stream only: a step on another stream
+                # that is handed this buffer again waits for the event, as it does for a collective that has completed
+                ev = torch.cuda.Event()
+                ev.record()
+                self.free_event[b] = (ev, {torch.cuda.current_stream()})
         self.last = (b, self.fill)
         self.count += 1
         self.buf, self.fill = 1 - b, 0
