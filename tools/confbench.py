@@ -12,18 +12,10 @@ One JSON line with, from one run:
 The kernel's calls rotate over enough distinct buffer sets (> 256 MiB together) that every call streams from HBM rather than from
 the Infinity Cache; hipEvents bracket a run of back-to-back calls on one stream, the median of five runs is reported."""
 import argparse
-import ctypes
 import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-from lbench import HBM_TBS, n_sets, timed  # noqa: E402
+import benchkit
+import torch
 
 
 def bench_stage(lib, stage, B, H, W, maxdisplist, iters, dev):
@@ -32,41 +24,31 @@ def bench_stage(lib, stage, B, H, W, maxdisplist, iters, dev):
     D, start = (m, 0.0) if stage == 0 else (2 * m - 1, float(-m + 1))
     h, w = ((H + 1) // 2) // (4 >> stage), ((W + 1) // 2) // (4 >> stage)
     set_bytes = 4 * B * (D * h * w + 2 * H * W)
-    n = n_sets(set_bytes)
+    n = benchkit.n_sets(set_bytes)
     g = torch.Generator(device=dev).manual_seed(stage)
     sets = [(torch.rand((B, D, h, w), device=dev, generator=g) * 12, torch.empty((B, 1, H, W), device=dev),
              torch.empty((B, 1, H, W), device=dev)) for _ in range(n)]
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    P = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
+    st = benchkit.stream()
+    P = benchkit.ptr
 
     def call(k):
         cost, conf, sigma = sets[k % n]
         _lib.check(lib.lws_softargmin_conf(P(cost), B, D, h, w, start, H, W, None, None, None, P(conf), P(sigma), st), "lws_softargmin_conf")
 
-    for k in range(2 * n):
-        call(k)
-    torch.cuda.synchronize()
-    us, runs = timed(call, iters)
+    benchkit.warm(call, 2 * n)
+    runs = benchkit.windows(call, iters)
     return {"kernel": "lws_softargmin_conf", "stage": stage + 1, "geometry": f"{B}x{H}x{W}", "D": D, "low": f"{h}x{w}", "bytes": set_bytes,
-            "buffer_sets": n, "us_per_call": round(us, 2), "us_runs": [round(r, 2) for r in runs],
-            "tb_per_s": round(set_bytes / us / 1e6, 3), "fraction_of_hbm": round(set_bytes / us / 1e6 / HBM_TBS, 3),
-            "hbm_floor_us": round(set_bytes / HBM_TBS / 1e6, 2)}
+            "buffer_sets": n, **benchkit.per_call(runs, set_bytes)}
 
 
 def bench_forward(model, B, H, W, iters):
-    from lwsnet_amd.synth import make_batch
-    dev = model.device
-    left, right = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in make_batch(B, H, W)[:2])
+    left, right = benchkit.device_batch(B, H, W)
     cases = {"forward": lambda k: model(left, right), "forward_conf": lambda k: model.forward_conf(left, right)}
     res = {}
     for fn in cases.values():
-        for k in range(3):
-            fn(k)
-        torch.cuda.synchronize()
+        benchkit.warm(fn, 3)
     for name, fn in cases.items():
-        us, runs = timed(fn, iters)
-        res[name + "_ms"] = round(us / 1e3, 3)
-        res[name + "_ms_runs"] = [round(r / 1e3, 3) for r in runs]
+        res.update(benchkit.forward_ms(name, benchkit.windows(fn, iters)))
     res["conf_over_forward"] = round(res["forward_conf_ms"] / res["forward_ms"], 4)
     return {"geometry": f"{B}x{H}x{W}", **res}
 
@@ -76,15 +58,9 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--forward_iters", type=int, default=20)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/confbench.py needs a HIP device")
-    from lwsnet_amd import _lib, build
-    from lwsnet_amd.models import LWSNet
-    from lwsnet_amd.weights import default_args, make_state_dict
-    build.build_library()
-    lib = _lib.load()
-    dev = torch.device("cuda:0")
-    model = LWSNet(default_args(), device=dev).set_state_dict(make_state_dict(7)).eval()
+    benchkit.need_device(__file__)
+    lib, dev = benchkit.library(build=True), benchkit.DEV
+    model = benchkit.seeded_model()
     line = {"softargmin_conf": [], "forward": []}
     shapes = ((1, 368, 1232), (8, 256, 512), (8, 368, 1232))
     for B, H, W in shapes:

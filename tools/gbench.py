@@ -12,35 +12,12 @@ The inputs are model-like disparities (10 .. 150 pixels) with a code map that ke
 enough distinct buffer sets (> 256 MiB together) that every call streams from HBM rather than from the Infinity Cache; hipEvents
 bracket a run of back-to-back calls on one stream, the median of five runs is reported."""
 import argparse
-import ctypes
 import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402
+import benchkit
+import torch
 
-HBM_TBS = 6.29          # MI355X, measured float4 copy rate
 FX, BASELINE = 721.5377, 0.5327
-
-
-def timed(call, iters, runs=5):
-    out = []
-    for _ in range(runs):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for k in range(iters):
-            call(k)
-        e1.record()
-        e1.synchronize()
-        out.append(1e3 * e0.elapsed_time(e1) / iters)
-    out.sort()
-    return out[len(out) // 2], out
-
-
-def n_sets(set_bytes):
-    return max(2, -(-(512 << 20) // set_bytes))
 
 
 def inputs(B, H, W, dev, g):
@@ -49,17 +26,15 @@ def inputs(B, H, W, dev, g):
     return disp, mask
 
 
-def result(name, B, H, W, set_bytes, n, us, runs, **extra):
-    return {"kernel": name, "geometry": f"{B}x{H}x{W}", "bytes": set_bytes, "buffer_sets": n, "us_per_call": round(us, 2),
-            "us_runs": [round(r, 2) for r in runs], "tb_per_s": round(set_bytes / us / 1e6, 3),
-            "fraction_of_hbm": round(set_bytes / us / 1e6 / HBM_TBS, 3), "hbm_floor_us": round(set_bytes / HBM_TBS / 1e6, 2),
-            "over_floor": round(us / (set_bytes / HBM_TBS / 1e6), 2), **extra}
+def result(name, B, H, W, set_bytes, n, runs, **extra):
+    return {"kernel": name, "geometry": f"{B}x{H}x{W}", "bytes": set_bytes, "buffer_sets": n,
+            **benchkit.per_call(runs, set_bytes, benchkit.TRAFFIC + ("over_floor",)), **extra}
 
 
 def bench_depth(lib, B, H, W, iters, dev):
     from lwsnet_amd import _lib
     set_bytes = 13 * B * H * W
-    n = n_sets(set_bytes)
+    n = benchkit.n_sets(set_bytes)
     g = torch.Generator(device=dev).manual_seed(0)
     cam = torch.tensor([[FX, FX, 600.0, 170.0, FX * BASELINE]] * B, dtype=torch.float32, device=dev)
     sets = []
@@ -67,18 +42,16 @@ def bench_depth(lib, B, H, W, iters, dev):
         disp, mask = inputs(B, H, W, dev, g)
         outs = [torch.empty((B, 1, H, W), dtype=dt, device=dev) for dt in (torch.float32, torch.uint16, torch.uint16)]
         sets.append([disp, mask] + outs)
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = benchkit.stream()
 
     def call(k):
         disp, mask, depth, depth16, disp16 = sets[k % n]
         _lib.check(lib.lws_depth_maps(disp.data_ptr(), mask.data_ptr(), cam.data_ptr(), B, H, W, 1.0, float("inf"), depth.data_ptr(),
                                       depth16.data_ptr(), disp16.data_ptr(), st), "lws_depth_maps")
 
-    for k in range(2 * n):
-        call(k)
-    torch.cuda.synchronize()
-    us, runs = timed(call, iters)
-    return result("lws_depth_maps", B, H, W, set_bytes, n, us, runs, outputs=["depth", "depth16", "disp16"], mask=True)
+    benchkit.warm(call, 2 * n)
+    runs = benchkit.windows(call, iters)
+    return result("lws_depth_maps", B, H, W, set_bytes, n, runs, outputs=["depth", "depth16", "disp16"], mask=True)
 
 
 def bench_cloud(lib, B, H, W, iters, dev):
@@ -87,39 +60,33 @@ def bench_cloud(lib, B, H, W, iters, dev):
     cam = torch.tensor([[FX, FX, 600.0, 170.0, FX * BASELINE]] * B, dtype=torch.float32, device=dev)
     work = torch.empty((int(lib.lws_point_cloud_workspace(B, H)),), dtype=torch.uint8, device=dev)
     counts = torch.empty((B,), dtype=torch.int64, device=dev)
-    n = n_sets(26 * B * H * W)
+    n = benchkit.n_sets(26 * B * H * W)
     sets = []
     for _ in range(n):
         disp, mask = inputs(B, H, W, dev, g)
         rgb = torch.randint(0, 256, (B, H, W, 3), dtype=torch.uint8, device=dev, generator=g)
         sets.append((disp, mask, rgb, torch.empty((B, H * W, 16), dtype=torch.uint8, device=dev)))
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = benchkit.stream()
 
     def call(k):
         disp, mask, rgb, points = sets[k % n]
         _lib.check(lib.lws_point_cloud(disp.data_ptr(), mask.data_ptr(), rgb.data_ptr(), cam.data_ptr(), B, H, W, 1.0, float("inf"),
                                        work.data_ptr(), points.data_ptr(), counts.data_ptr(), st), "lws_point_cloud")
 
-    call(0)
-    torch.cuda.synchronize()
+    benchkit.warm(call, 1)
     kept = int(counts.sum())
     set_bytes = 2 * 5 * B * H * W + 3 * B * H * W + 16 * kept          # disp + mask twice, rgb once, the kept records
-    for k in range(2 * n):
-        call(k)
-    torch.cuda.synchronize()
-    us, runs = timed(call, iters)
-    return result("lws_point_cloud", B, H, W, set_bytes, n, us, runs, kept_fraction=round(kept / (B * H * W), 4), mask=True, rgb=True)
+    benchkit.warm(call, 2 * n)
+    runs = benchkit.windows(call, iters)
+    return result("lws_point_cloud", B, H, W, set_bytes, n, runs, kept_fraction=round(kept / (B * H * W), 4), mask=True, rgb=True)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=200)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/gbench.py needs a HIP device")
-    from lwsnet_amd import _lib
-    lib = _lib.load()
-    dev = torch.device("cuda:0")
+    benchkit.need_device(__file__)
+    lib, dev = benchkit.library(), benchkit.DEV
     for B, H, W in ((1, 368, 1232), (8, 368, 1232)):
         line = {"geometry": f"{B}x{H}x{W}", "depth_maps": bench_depth(lib, B, H, W, a.iters, dev),
                 "point_cloud": bench_cloud(lib, B, H, W, a.iters, dev)}

@@ -9,20 +9,14 @@ bottom bins, three passes after the voted line; and once with iters = 0, which l
 (height, codes and counts) and lws_bev_grid (200 x 300 cells, count and hmax) -- and their sum.  The inputs are a road (a plane
 in disparity with a horizon near row 165, a little roll and a quarter pixel of noise) with boxes of constant disparity standing
 on it and a code map that keeps ~80 % of the pixels; each call reads what the call before it wrote for the same buffer set.
-Buffer rotation and timing are tools/gbench.py's: more than 256 MiB of distinct buffer sets, hipEvents around back-to-back calls
+Buffer rotation and timing are tools/benchkit.py's: more than 256 MiB of distinct buffer sets, hipEvents around back-to-back calls
 on one stream, the median of five runs."""
 import argparse
-import ctypes
 import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import torch  # noqa: E402
-
-from gbench import BASELINE, FX, n_sets, timed  # noqa: E402
+import benchkit
+import torch
+from gbench import BASELINE, FX
 
 SUB, NBINS, TOL_BINS, MIN_SCORE, TOL0, TOL, ITERS = 4, 768, 1, 0, 1.0, 1.0, 3
 MIN_DISP, MAX_DEPTH, GROUND_TOL, MAX_HEIGHT = 1.0, float("inf"), 0.2, 3.0
@@ -45,12 +39,12 @@ def bench(lib, B, H, W, iters, dev):
     from lwsnet_amd import _lib
     px = B * H * W
     set_bytes = (4 + 1 + 4 + 1) * px + 4 * B * H * NBINS + 8 * B * GX * GZ
-    n = n_sets(set_bytes)
+    n = benchkit.n_sets(set_bytes)
     g = torch.Generator(device=dev).manual_seed(4)
     cam = torch.tensor([[FX, FX, 600.0, 170.0, FX * BASELINE]] * B, dtype=torch.float32, device=dev)
     work = torch.empty((int(lib.lws_ground_workspace(B, H, NBINS)),), dtype=torch.uint8, device=dev)
     yh, qb = (H // 4, min(3 * H // 4, H - 2)), (NBINS // 3, NBINS - 1)
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = benchkit.stream()
     e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)                # noqa: E731
     sets = [inputs(B, H, W, dev, g) + (e((B, H, NBINS), torch.uint32), e((B, 4), torch.float32), e((B, 8), torch.int32),
                                        e((B, 1, H, W), torch.float32), e((B, 1, H, W), torch.uint8), e((B, 6), torch.int64),
@@ -79,11 +73,8 @@ def bench(lib, B, H, W, iters, dev):
     calls = (("vdisparity", hist), ("ground_fit_iters0", lambda k: fit(k, 0)), ("ground_fit", fit), ("ground_classify", classify),
              ("bev_grid", bev))
     for name, call in calls:                                # in this order: each reads what the one before wrote
-        for k in range(2 * n):
-            call(k)
-        torch.cuda.synchronize()
-        us, runs = timed(call, iters)
-        out[name] = {"us_per_call": round(us, 2), "us_runs": [round(r, 2) for r in runs]}
+        benchkit.warm(call, 2 * n)
+        out[name] = benchkit.per_call(benchkit.windows(call, iters))
     info, counts = sets[0][4].cpu(), sets[0][7].cpu()
     out["status"], out["inlier_share"] = info[:, 0].tolist(), round(float(info[:, 4].sum()) / max(int(counts[:, 1:].sum()), 1), 4)
     out["codes"] = counts.sum(dim=0).tolist()
@@ -95,11 +86,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=200)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/groundbench.py needs a HIP device")
-    from lwsnet_amd import _lib
-    lib = _lib.load()
-    dev = torch.device("cuda:0")
+    benchkit.need_device(__file__)
+    lib, dev = benchkit.library(), benchkit.DEV
     for B, H, W in ((1, 368, 1232), (8, 368, 1232)):
         print(json.dumps(bench(lib, B, H, W, a.iters, dev)), flush=True)
         torch.cuda.empty_cache()

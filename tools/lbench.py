@@ -13,39 +13,15 @@ the Infinity Cache; hipEvents bracket a run of back-to-back calls on one stream,
 import argparse
 import ctypes
 import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-HBM_TBS = 6.29          # MI355X, measured float4 copy rate
-
-
-def timed(call, iters, runs=5):
-    out = []
-    for _ in range(runs):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for k in range(iters):
-            call(k)
-        e1.record()
-        e1.synchronize()
-        out.append(1e3 * e0.elapsed_time(e1) / iters)
-    out.sort()
-    return out[len(out) // 2], out
-
-
-def n_sets(set_bytes):
-    return max(2, -(-(512 << 20) // set_bytes))
+import benchkit
+import torch
 
 
 def bench_check(lib, B, H, W, iters, dev):
     from lwsnet_amd import _lib
     set_bytes = 17 * 4 * B * H * W
-    n = n_sets(set_bytes)
+    n = benchkit.n_sets(set_bytes)
     g = torch.Generator(device=dev).manual_seed(0)
     arr = ctypes.c_void_p * 4
     sets = []
@@ -58,64 +34,51 @@ def bench_check(lib, B, H, W, iters, dev):
         kept = torch.empty((4, B, H), dtype=torch.int32, device=dev)
         ts = dl + drm + out + right + mask + [kept]
         sets.append((ts, [arr(*[t.data_ptr() for t in x]) for x in (dl, drm, out, mask, right)], ctypes.c_void_p(kept.data_ptr())))
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = benchkit.stream()
 
     def call(k):
         _, (a_dl, a_drm, a_out, a_mask, a_right), kp = sets[k % n]
         _lib.check(lib.lws_lr_check(a_dl, a_drm, 4, B, H, W, 1.0, 1, a_out, a_mask, a_right, kp, st), "lws_lr_check")
 
-    for k in range(2 * n):
-        call(k)
-    torch.cuda.synchronize()
-    us, runs = timed(call, iters)
+    benchkit.warm(call, 2 * n)
+    runs = benchkit.windows(call, iters)
     return {"kernel": "lws_lr_check", "geometry": f"{B}x{H}x{W}", "maps": 4, "fill": 1, "right": True, "bytes": set_bytes,
-            "buffer_sets": n, "us_per_call": round(us, 2), "us_runs": [round(r, 2) for r in runs],
-            "tb_per_s": round(set_bytes / us / 1e6, 3), "fraction_of_hbm": round(set_bytes / us / 1e6 / HBM_TBS, 3),
-            "hbm_floor_us": round(set_bytes / HBM_TBS / 1e6, 2)}
+            "buffer_sets": n, **benchkit.per_call(runs, set_bytes)}
 
 
 def bench_pairs(lib, B, H, W, iters, dev):
     from lwsnet_amd import _lib
     set_bytes = 4 * 3 * B * H * W * (2 + 4)
-    n = n_sets(set_bytes)
+    n = benchkit.n_sets(set_bytes)
     g = torch.Generator(device=dev).manual_seed(1)
+    P = benchkit.ptr
     sets = []
     for _ in range(n):
         l, r = (torch.randn((B, 3, H, W), device=dev, generator=g) for _ in range(2))
         l2, r2 = (torch.empty((2 * B, 3, H, W), device=dev) for _ in range(2))
         sets.append([l, r, l2, r2])
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = benchkit.stream()
 
     def call(k):
         l, r, l2, r2 = sets[k % n]
-        _lib.check(lib.lws_lr_pairs(ctypes.c_void_p(l.data_ptr()), ctypes.c_void_p(r.data_ptr()), ctypes.c_void_p(l2.data_ptr()),
-                                    ctypes.c_void_p(r2.data_ptr()), B, H, W, st), "lws_lr_pairs")
+        _lib.check(lib.lws_lr_pairs(P(l), P(r), P(l2), P(r2), B, H, W, st), "lws_lr_pairs")
 
-    for k in range(2 * n):
-        call(k)
-    torch.cuda.synchronize()
-    us, runs = timed(call, iters)
-    return {"kernel": "lws_lr_pairs", "geometry": f"{B}x{H}x{W}", "bytes": set_bytes, "buffer_sets": n, "us_per_call": round(us, 2),
-            "us_runs": [round(r, 2) for r in runs], "tb_per_s": round(set_bytes / us / 1e6, 3),
-            "fraction_of_hbm": round(set_bytes / us / 1e6 / HBM_TBS, 3), "hbm_floor_us": round(set_bytes / HBM_TBS / 1e6, 2)}
+    benchkit.warm(call, 2 * n)
+    runs = benchkit.windows(call, iters)
+    return {"kernel": "lws_lr_pairs", "geometry": f"{B}x{H}x{W}", "bytes": set_bytes, "buffer_sets": n,
+            **benchkit.per_call(runs, set_bytes)}
 
 
 def bench_forward(model, B, H, W, iters):
-    from lwsnet_amd.synth import make_batch
-    dev = model.device
-    left, right = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in make_batch(B, H, W)[:2])
+    left, right = benchkit.device_batch(B, H, W)
     left2, right2 = torch.cat([left, left]), torch.cat([right, right])
     cases = {"forward_B": lambda k: model(left, right), "forward_2B": lambda k: model(left2, right2),
              "forward_lr_B": lambda k: model.forward_lr(left, right, tau=1.0, fill=True)}
     res = {}
+    for fn in cases.values():
+        benchkit.warm(fn, 3)
     for name, fn in cases.items():
-        for k in range(3):
-            fn(k)
-        torch.cuda.synchronize()
-    for name, fn in cases.items():
-        ms, runs = timed(fn, iters)
-        res[name + "_ms"] = round(ms / 1e3, 3)
-        res[name + "_ms_runs"] = [round(r / 1e3, 3) for r in runs]
+        res.update(benchkit.forward_ms(name, benchkit.windows(fn, iters)))
     res["lr_over_2B"] = round(res["forward_lr_B_ms"] / res["forward_2B_ms"], 4)
     return {"kernel": "forward_lr", "geometry": f"{B}x{H}x{W}", **res}
 
@@ -125,15 +88,9 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--forward_iters", type=int, default=20)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/lbench.py needs a HIP device")
-    from lwsnet_amd import _lib, build
-    from lwsnet_amd.models import LWSNet
-    from lwsnet_amd.weights import default_args, make_state_dict
-    build.build_library()
-    lib = _lib.load()
-    dev = torch.device("cuda:0")
-    model = LWSNet(default_args(), device=dev).set_state_dict(make_state_dict(7)).eval()
+    benchkit.need_device(__file__)
+    lib, dev = benchkit.library(build=True), benchkit.DEV
+    model = benchkit.seeded_model()
     for B, H, W in ((1, 368, 1232), (8, 368, 1232), (8, 256, 512)):
         line = {"geometry": f"{B}x{H}x{W}", "lr_check": bench_check(lib, B, H, W, a.iters, dev),
                 "lr_pairs": bench_pairs(lib, B, H, W, a.iters, dev)}

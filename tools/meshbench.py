@@ -10,20 +10,14 @@ For each geometry (1 x 368 x 1232, 8 x 368 x 1232) one JSON line:
     normals once, 4 bytes of index per pixel, 32 bytes per vertex, 12 per face; the same figures;
   - lws_point_cloud from the same run (tools/gbench.py's measurement), to set the mesh beside the cloud it extends.
 The inputs are a smooth surface (a tilted plane under a slow wave, so that neighbours are connected at max_jump = 1) with a
-code map that keeps ~80 % of the pixels.  Buffer rotation and timing are tools/gbench.py's: more than 256 MiB of distinct
+code map that keeps ~80 % of the pixels.  Buffer rotation and timing are tools/benchkit.py's: more than 256 MiB of distinct
 buffer sets, hipEvents around back-to-back calls on one stream, the median of five runs."""
 import argparse
-import ctypes
 import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import torch  # noqa: E402
-
-from gbench import BASELINE, FX, bench_cloud, n_sets, result, timed  # noqa: E402
+import benchkit
+import torch
+from gbench import BASELINE, FX, bench_cloud, result
 
 ARGS = (1.0, float("inf"), 1.0)         # min_disp, max_depth, max_jump
 
@@ -44,23 +38,21 @@ def camera(B, dev):
 def bench_normals(lib, B, H, W, iters, dev):
     from lwsnet_amd import _lib
     set_bytes = 20 * B * H * W
-    n = n_sets(set_bytes)
+    n = benchkit.n_sets(set_bytes)
     g = torch.Generator(device=dev).manual_seed(2)
     cam = camera(B, dev)
     sets = [inputs(B, H, W, dev, g) + (torch.empty((B, 3, H, W), dtype=torch.float32, device=dev),
                                        torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)) for _ in range(n)]
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = benchkit.stream()
 
     def call(k):
         disp, mask, normals, normals8 = sets[k % n]
         _lib.check(lib.lws_surface_normals(disp.data_ptr(), mask.data_ptr(), cam.data_ptr(), B, H, W, *ARGS, normals.data_ptr(),
                                            normals8.data_ptr(), st), "lws_surface_normals")
 
-    for k in range(2 * n):
-        call(k)
-    torch.cuda.synchronize()
-    us, runs = timed(call, iters)
-    return result("lws_surface_normals", B, H, W, set_bytes, n, us, runs, outputs=["normals", "normals8"], mask=True)
+    benchkit.warm(call, 2 * n)
+    runs = benchkit.windows(call, iters)
+    return result("lws_surface_normals", B, H, W, set_bytes, n, runs, outputs=["normals", "normals8"], mask=True)
 
 
 def bench_mesh(lib, B, H, W, iters, dev):
@@ -70,8 +62,8 @@ def bench_mesh(lib, B, H, W, iters, dev):
     work = torch.empty((int(lib.lws_surface_mesh_workspace(B, H)),), dtype=torch.uint8, device=dev)
     counts = torch.empty((B, 2), dtype=torch.int64, device=dev)
     px = B * H * W
-    n = n_sets(85 * px)
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    n = benchkit.n_sets(85 * px)
+    st = benchkit.stream()
     sets = []
     for _ in range(n):
         disp, mask = inputs(B, H, W, dev, g)
@@ -90,15 +82,12 @@ def bench_mesh(lib, B, H, W, iters, dev):
                                         work.data_ptr(), points.data_ptr(), vn.data_ptr(), faces.data_ptr(), index.data_ptr(),
                                         counts.data_ptr(), st), "lws_surface_mesh")
 
-    call(0)
-    torch.cuda.synchronize()
+    benchkit.warm(call, 1)
     nv, nf = (int(v) for v in counts.sum(dim=0).cpu())
     set_bytes = (2 * 5 + 3 + 12 + 4) * px + 32 * nv + 12 * nf    # disp + mask twice, rgb, normals, index; vertex and face records
-    for k in range(2 * n):
-        call(k)
-    torch.cuda.synchronize()
-    us, runs = timed(call, iters)
-    return result("lws_surface_mesh", B, H, W, set_bytes, n, us, runs, kept_fraction=round(nv / px, 4),
+    benchkit.warm(call, 2 * n)
+    runs = benchkit.windows(call, iters)
+    return result("lws_surface_mesh", B, H, W, set_bytes, n, runs, kept_fraction=round(nv / px, 4),
                   faces_per_cell=round(nf / (B * (H - 1) * (W - 1)), 4), mask=True, rgb=True, normals=True, index=True)
 
 
@@ -106,11 +95,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=200)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/meshbench.py needs a HIP device")
-    from lwsnet_amd import _lib
-    lib = _lib.load()
-    dev = torch.device("cuda:0")
+    benchkit.need_device(__file__)
+    lib, dev = benchkit.library(), benchkit.DEV
     for B, H, W in ((1, 368, 1232), (8, 368, 1232)):
         line = {"geometry": f"{B}x{H}x{W}", "surface_normals": bench_normals(lib, B, H, W, a.iters, dev),
                 "surface_mesh": bench_mesh(lib, B, H, W, a.iters, dev), "point_cloud": bench_cloud(lib, B, H, W, a.iters, dev)}

@@ -15,22 +15,16 @@ the Infinity Cache; hipEvents bracket a run of back-to-back calls on one stream,
 import argparse
 import ctypes
 import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-from lbench import HBM_TBS, bench_check, n_sets, timed  # noqa: E402
+import benchkit
+import torch
+from lbench import bench_check
 
 
 def bench_occlusion(lib, B, H, W, iters, dev):
     from lwsnet_amd import _lib
     set_bytes = 13 * 4 * B * H * W
-    n = n_sets(set_bytes)
+    n = benchkit.n_sets(set_bytes)
     g = torch.Generator(device=dev).manual_seed(0)
     arr = ctypes.c_void_p * 4
     x = torch.arange(W, device=dev, dtype=torch.float32)
@@ -46,38 +40,28 @@ def bench_occlusion(lib, B, H, W, iters, dev):
         kept = torch.empty((4, B, H), dtype=torch.int32, device=dev)
         ts = dl + out + right + mask + [kept]
         sets.append((ts, [arr(*[t.data_ptr() for t in v]) for v in (dl, out, mask, right)], ctypes.c_void_p(kept.data_ptr())))
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = benchkit.stream()
 
     def call(k):
         _, (a_dl, a_out, a_mask, a_right), kp = sets[k % n]
         _lib.check(lib.lws_occlusion_check(a_dl, 4, B, H, W, 1.0, 1, a_out, a_mask, a_right, kp, st), "lws_occlusion_check")
 
-    for k in range(2 * n):
-        call(k)
-    torch.cuda.synchronize()
-    us, runs = timed(call, iters)
+    benchkit.warm(call, 2 * n)
+    runs = benchkit.windows(call, iters)
     density = float(sum(int(t.sum()) for t in (s[0][-1] for s in sets))) / (len(sets) * 4 * B * H * W)
     return {"kernel": "lws_occlusion_check", "geometry": f"{B}x{H}x{W}", "maps": 4, "fill": 1, "right": True, "bytes": set_bytes,
-            "buffer_sets": n, "density": round(density, 4), "us_per_call": round(us, 2), "us_runs": [round(r, 2) for r in runs],
-            "tb_per_s": round(set_bytes / us / 1e6, 3), "fraction_of_hbm": round(set_bytes / us / 1e6 / HBM_TBS, 3),
-            "hbm_floor_us": round(set_bytes / HBM_TBS / 1e6, 2)}
+            "buffer_sets": n, "density": round(density, 4), **benchkit.per_call(runs, set_bytes)}
 
 
 def bench_forward(model, B, H, W, iters):
-    from lwsnet_amd.synth import make_batch
-    dev = model.device
-    left, right = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in make_batch(B, H, W)[:2])
+    left, right = benchkit.device_batch(B, H, W)
     cases = {"forward": lambda k: model(left, right), "forward_occ": lambda k: model.forward_occ(left, right, tau=1.0, fill=True),
              "forward_lr": lambda k: model.forward_lr(left, right, tau=1.0, fill=True)}
     res = {}
     for fn in cases.values():
-        for k in range(3):
-            fn(k)
-        torch.cuda.synchronize()
+        benchkit.warm(fn, 3)
     for name, fn in cases.items():
-        us, runs = timed(fn, iters)
-        res[name + "_ms"] = round(us / 1e3, 3)
-        res[name + "_ms_runs"] = [round(r / 1e3, 3) for r in runs]
+        res.update(benchkit.forward_ms(name, benchkit.windows(fn, iters)))
     res["occ_over_forward"] = round(res["forward_occ_ms"] / res["forward_ms"], 4)
     res["lr_over_forward"] = round(res["forward_lr_ms"] / res["forward_ms"], 4)
     return {"geometry": f"{B}x{H}x{W}", **res}
@@ -88,21 +72,15 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--forward_iters", type=int, default=20)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/occbench.py needs a HIP device")
-    from lwsnet_amd import _lib, build
-    from lwsnet_amd.models import LWSNet
-    from lwsnet_amd.weights import default_args, make_state_dict
-    build.build_library()
-    lib = _lib.load()
-    dev = torch.device("cuda:0")
+    benchkit.need_device(__file__)
+    lib, dev = benchkit.library(build=True), benchkit.DEV
     line = {"occlusion_check": [], "lr_check": [], "forward": []}
     for B, H, W in ((1, 368, 1232), (8, 256, 512), (8, 368, 1232)):
         line["occlusion_check"].append(bench_occlusion(lib, B, H, W, a.iters, dev))
         torch.cuda.empty_cache()
         line["lr_check"].append(bench_check(lib, B, H, W, a.iters, dev))
         torch.cuda.empty_cache()
-    model = LWSNet(default_args(), device=dev).set_state_dict(make_state_dict(7)).eval()
+    model = benchkit.seeded_model()
     for B in (1, 8):
         line["forward"].append(bench_forward(model, B, 368, 1232, a.forward_iters))
     print(json.dumps(line), flush=True)

@@ -13,22 +13,15 @@ Infinity Cache; hipEvents bracket a run of back-to-back calls on one stream, the
 import argparse
 import ctypes
 import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-from lbench import HBM_TBS, n_sets, timed  # noqa: E402
+import benchkit
+import torch
 
 
 def bench_photometric(lib, B, H, W, iters, dev, with_warped):
     from lwsnet_amd import _lib
     set_bytes = (18 if with_warped else 15) * 4 * B * H * W
-    n = n_sets(set_bytes)
+    n = benchkit.n_sets(set_bytes)
     g = torch.Generator(device=dev).manual_seed(0)
     arr = ctypes.c_void_p * 4
     x = torch.arange(W, device=dev, dtype=torch.float32)
@@ -45,32 +38,23 @@ def bench_photometric(lib, B, H, W, iters, dev, with_warped):
         sums = torch.empty((4, B, 4), dtype=torch.int64, device=dev)
         ts = disp + [left, right] + err + scored + warped + [sums]
         sets.append((ts, [arr(*[t.data_ptr() for t in v]) for v in (disp, err, scored, warped)], left.data_ptr(), right.data_ptr(), sums.data_ptr()))
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = benchkit.stream()
 
     def call(k):
         _, (a_disp, a_err, a_scored, a_warped), lp, rp, sp = sets[k % n]
         _lib.check(lib.lws_photometric(a_disp, 4, lp, rp, arr(), None, B, H, W, 0.85, a_err, a_scored, a_warped, sp, st), "lws_photometric")
 
-    for k in range(2 * n):
-        call(k)
-    torch.cuda.synchronize()
-    us, runs = timed(call, iters)
+    benchkit.warm(call, 2 * n)
+    runs = benchkit.windows(call, iters)
     density = float(sum(int(s[0][-1][:, :, 0].sum()) for s in sets)) / (len(sets) * 4 * B * H * W)
     return {"kernel": "lws_photometric", "geometry": f"{B}x{H}x{W}", "maps": 4, "with_warped": with_warped, "bytes": set_bytes,
-            "buffer_sets": n, "density": round(density, 4), "us_per_call": round(us, 2), "us_runs": [round(r, 2) for r in runs],
-            "tb_per_s": round(set_bytes / us / 1e6, 3), "fraction_of_hbm": round(set_bytes / us / 1e6 / HBM_TBS, 3),
-            "hbm_floor_us": round(set_bytes / HBM_TBS / 1e6, 2)}
+            "buffer_sets": n, "density": round(density, 4), **benchkit.per_call(runs, set_bytes)}
 
 
 def bench_forward(model, B, H, W, iters):
-    from lwsnet_amd.synth import make_batch
-    dev = model.device
-    left, right = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in make_batch(B, H, W)[:2])
-    for _ in range(3):
-        model(left, right)
-    torch.cuda.synchronize()
-    us, runs = timed(lambda k: model(left, right), iters)
-    return {"geometry": f"{B}x{H}x{W}", "forward_ms": round(us / 1e3, 3), "forward_ms_runs": [round(r / 1e3, 3) for r in runs]}
+    left, right = benchkit.device_batch(B, H, W)
+    benchkit.warm(lambda k: model(left, right), 3)
+    return {"geometry": f"{B}x{H}x{W}", **benchkit.forward_ms("forward", benchkit.windows(lambda k: model(left, right), iters))}
 
 
 def main():
@@ -78,20 +62,14 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--forward_iters", type=int, default=20)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/photobench.py needs a HIP device")
-    from lwsnet_amd import _lib, build
-    from lwsnet_amd.models import LWSNet
-    from lwsnet_amd.weights import default_args, make_state_dict
-    build.build_library()
-    lib = _lib.load()
-    dev = torch.device("cuda:0")
+    benchkit.need_device(__file__)
+    lib, dev = benchkit.library(build=True), benchkit.DEV
     line = {"photometric": [], "forward": []}
     for B, H, W in ((1, 368, 1232), (8, 368, 1232)):
         for with_warped in (False, True):
             line["photometric"].append(bench_photometric(lib, B, H, W, a.iters, dev, with_warped))
             torch.cuda.empty_cache()
-    model = LWSNet(default_args(), device=dev).set_state_dict(make_state_dict(7)).eval()
+    model = benchkit.seeded_model()
     for i, B in enumerate((1, 8)):
         f = bench_forward(model, B, 368, 1232, a.forward_iters)
         f["photometric_over_forward"] = round(line["photometric"][2 * i]["us_per_call"] / 1e3 / f["forward_ms"], 4)

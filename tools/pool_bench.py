@@ -3,13 +3,10 @@
 
     python tools/pool_bench.py [--size HxW] [--batch B] [--jobs N] [--workers 2,3,4,6] [--reps 3]"""
 import argparse
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import torch   # noqa: E402
+import benchkit
+import torch
 
 
 def main():
@@ -22,13 +19,9 @@ def main():
     ap.add_argument("--opt", action="append", default=[])
     a = ap.parse_args()
     H, W = [int(v) for v in a.size.split("x")]
-    from lwsnet_amd.models import LWSNet
     from lwsnet_amd.synth import make_batch
-    from lwsnet_amd.weights import default_args, make_state_dict
-    dev = torch.device("cuda:0")
-    m = LWSNet(default_args(), device=dev).set_state_dict(make_state_dict(7)).eval()
-    for o in a.opt:
-        m.set_option(o.split("=")[0], int(o.split("=")[1]))
+    dev = benchkit.DEV
+    m = benchkit.seeded_model(opts=a.opt)
     l, r = make_batch(a.batch, H, W, 0)
     l, r = torch.from_numpy(l).to(dev), torch.from_numpy(r).to(dev)
     ref = [p.clone() for p in m(l, r)]

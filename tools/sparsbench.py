@@ -17,15 +17,9 @@ the Infinity Cache; hipEvents bracket a run of back-to-back calls on one stream,
 import argparse
 import ctypes
 import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import torch  # noqa: E402
-
-from lbench import HBM_TBS, n_sets, timed  # noqa: E402
+import benchkit
+import torch
 
 INPUTS = (("random_sigma", 0), ("random_conf", 1), ("bin0", 0))
 
@@ -45,20 +39,16 @@ def main():
     ap.add_argument("--geometry", type=int, nargs=3, default=(8, 368, 1232), metavar=("B", "H", "W"))
     ap.add_argument("--iters", type=int, default=100)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/sparsbench.py needs a HIP device")
-    from lwsnet_amd import _lib, build
-    build.build_library()
-    lib = _lib.load()
-    dev = torch.device("cuda:0")
+    benchkit.need_device(__file__)
+    from lwsnet_amd import _lib
+    lib, dev = benchkit.library(build=True), benchkit.DEV
     B, H, W = a.geometry
     map_bytes = 4 * B * H * W
-    n = n_sets(5 * map_bytes)                               # the smaller call's reads alone exceed the Infinity Cache
+    n = benchkit.n_sets(5 * map_bytes)                               # the smaller call's reads alone exceed the Infinity Cache
     g = torch.Generator(device=dev).manual_seed(0)
     sets = [make_set(B, H, W, dev, g) for _ in range(n)]
     arr = ctypes.c_void_p * 4
-    P = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    P, st = benchkit.ptr, benchkit.stream()
     work = torch.empty((int(lib.lws_stage_metrics_workspace(B, H, W)),), device=dev, dtype=torch.uint8)
     counts = torch.empty((4, B, 2), device=dev, dtype=torch.int64)
     sums = torch.empty((4, B), device=dev, dtype=torch.float64)
@@ -77,12 +67,8 @@ def main():
         return call
 
     def run(call, nbytes):
-        for k in range(2 * n):
-            call(k)
-        torch.cuda.synchronize()
-        us, runs = timed(call, a.iters)
-        return {"bytes": nbytes, "us_per_call": round(us, 2), "us_runs": [round(r, 2) for r in runs],
-                "fraction_of_hbm": round(nbytes / us / 1e6 / HBM_TBS, 3), "hbm_floor_us": round(nbytes / HBM_TBS / 1e6, 2)}
+        benchkit.warm(call, 2 * n)
+        return {"bytes": nbytes, **benchkit.per_call(benchkit.windows(call, a.iters), nbytes, ("fraction_of_hbm", "hbm_floor_us"))}
 
     line = {"geometry": f"{B}x{H}x{W}", "buffer_sets": n, "stage_metrics": run(metrics_call, 5 * map_bytes), "sparsification": {}}
     for name, kind in INPUTS:

@@ -9,27 +9,21 @@ to k_classify and k_bev_scatter of the same run (the strip passes read from L2, 
 one JSON line with what was found, so that the trace is known to be of a scene with stixels in it."""
 import argparse
 import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import torch  # noqa: E402
-
-from gbench import BASELINE, FX  # noqa: E402
-from groundbench import inputs  # noqa: E402
+import benchkit
+import torch
+from gbench import BASELINE, FX
+from groundbench import inputs
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/stixelbench.py needs a HIP device")
+    benchkit.need_device(__file__)
     from lwsnet_amd import ops
     from lwsnet_amd.geometry import Camera
-    dev = torch.device("cuda:0")
+    dev = benchkit.DEV
     B, H, W = 1, 368, 1232
     disp, mask = inputs(B, H, W, dev, torch.Generator(device=dev).manual_seed(4))
     cam = Camera(FX, FX, 600.0, 170.0, BASELINE)

@@ -12,17 +12,11 @@ windows of N calls between two events; the median window, per call.  The forward
 the same way with fewer calls.  Prints one JSON line per batch with the times, the pixels per code and the shader clock the device
 held during the forward (lws_clock_read)."""
 import argparse
-import ctypes
 import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-from objectbench import timed  # noqa: E402
+import benchkit
+import numpy as np
+import torch
 
 
 def main():
@@ -30,36 +24,25 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--runs", type=int, default=7)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/temporalbench.py needs a HIP device")
+    benchkit.need_device(__file__)
     from lwsnet_amd import _lib, ops
     from lwsnet_amd.geometry import Camera, camera_rows, relative_pose
-    from lwsnet_amd.models import LWSNet
     from lwsnet_amd.synth import make_pair
-    from lwsnet_amd.weights import default_args, make_state_dict
-    lib = _lib.load()
-    dev = torch.device("cuda:0")
+    dev = benchkit.DEV
     H, W = 368, 1232
-    model = LWSNet(default_args(), device=dev).set_state_dict(make_state_dict(7)).eval()
-    cam1 = Camera(721.5377, 721.5377, 609.5593, 172.854, 0.54)
+    model = benchkit.seeded_model()
+    cam1 = Camera(*benchkit.KITTI)
     T0 = np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 0]], np.float64)
     T1 = T0.copy()
     T1[2, 3] = 0.3
-    P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None     # noqa: E731
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    P, stream = benchkit.ptr, benchkit.stream()
     for B in (1, 8):
         frames = []
         for k in range(2):
             left, right = (np.repeat(x[None], B, axis=0) for x in make_pair(H, W, k)[:2])
             res = model.forward_occ(left, right, tau=1.0, fill=False)
             frames.append((res.disp[3].as_subclass(torch.Tensor).contiguous(), res.mask[3].contiguous(), left, right))
-        ghz = None
-        if lib.lws_clock_stamp(model._h, 1) == _lib.LWS_OK:
-            model(frames[1][2], frames[1][3])
-            v = ctypes.c_double(0.0)
-            if lib.lws_clock_read(model._h, ctypes.byref(v)) == _lib.LWS_OK:
-                ghz = round(v.value, 3)
-            lib.lws_clock_stamp(model._h, 0)
+        ghz = benchkit.clock_ghz(model, lambda: model(frames[1][2], frames[1][3]))
         cams = [cam1] * B
         pose = relative_pose(T0, T1)
         s0 = ops.temporal_step(frames[0][0], cams, mask=frames[0][1])
@@ -75,17 +58,14 @@ def main():
 
         line = {"tool": "temporalbench", "geometry": f"{B}x{H}x{W}", "iters": a.iters, "runs": a.runs, "clock_ghz": ghz,
                 "codes_with_hold": s1.counts[0].cpu().tolist()}
-        for name, call in (("hold_off", lambda: step(0)), ("hold_off_without_counts", lambda: step(0, None)), ("hold_on", lambda: step(1)),
-                           ("hold_off_again", lambda: step(0))):
-            for _ in range(10):
-                call()
-            torch.cuda.synchronize()
-            line[name] = timed(call, a.iters, a.runs)
+        for name, call in (("hold_off", lambda k: step(0)), ("hold_off_without_counts", lambda k: step(0, None)), ("hold_on", lambda k: step(1)),
+                           ("hold_off_again", lambda k: step(0))):
+            benchkit.warm(call, 10)
+            line[name] = benchkit.summary(benchkit.windows(call, a.iters, a.runs))
         l_dev, r_dev = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in frames[1][2:])     # resident inputs: no upload in the window
-        fwd = lambda: model(l_dev, r_dev)                   # noqa: E731
-        fwd()
-        torch.cuda.synchronize()
-        line["forward"] = timed(fwd, max(1, a.iters // 20), min(a.runs, 5))
+        fwd = lambda k: model(l_dev, r_dev)                   # noqa: E731
+        benchkit.warm(fwd, 1)
+        line["forward"] = benchkit.summary(benchkit.windows(fwd, max(1, a.iters // 20), min(a.runs, 5)))
         line["hold_on_over_forward"] = round(line["hold_on"]["us"] / line["forward"]["us"], 5)
         print(json.dumps(line), flush=True)
 

@@ -15,18 +15,13 @@ on them.  Prints one JSON line with the times, the voxels taken per frame, the p
 import argparse
 import ctypes
 import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-from objectbench import timed  # noqa: E402
+import benchkit
+import numpy as np
+import torch
 
 H, W = 368, 1232
-CAM = (721.5377, 721.5377, 609.5593, 172.854, 0.54)
+CAM = benchkit.KITTI
 ORIGIN, VOXEL, DIMS, MU0 = (-12.8, -3.2, 0.0), 0.2, (129, 33, 257), 0.6
 
 
@@ -45,13 +40,12 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--runs", type=int, default=7)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/tsdfbench.py needs a HIP device")
+    benchkit.need_device(__file__)
     from lwsnet_amd import _lib, ops
     from lwsnet_amd.geometry import Camera, camera_rows
     from lwsnet_amd.tsdf import TsdfVolume
-    _lib.load()
-    dev = torch.device("cuda:0")
+    benchkit.library()
+    dev = benchkit.DEV
     cam1 = Camera(*CAM)
     n = 4
     rng = np.random.default_rng(0)
@@ -66,8 +60,7 @@ def main():
     line = {"tool": "tsdfbench", "map": f"{H}x{W}", "volume": "x".join(str(d) for d in DIMS), "voxel": VOXEL, "iters": a.iters, "runs": a.runs,
             "updated_per_frame": updated.cpu().tolist(), "pixels_hit": int((view.disp > 0).sum()), "points_found": int(pts.counts[0])}
 
-    P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None     # noqa: E731
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    P, stream = benchkit.ptr, benchkit.stream()
     cam = torch.from_numpy(camera_rows([cam1] * n, n)).to(dev)
     pose = torch.from_numpy(ops.tsdf_pose_rows(poses, n)).to(dev)
     grid = (*DIMS, *ORIGIN, VOXEL)
@@ -82,18 +75,16 @@ def main():
         _lib.call("lws_tsdf_raycast", P(vol.T), P(vol.Wt), *grid, P(cam[2:]), P(pose[2:]), 1, H, W, 0.5, 0.1, 560, 0.0, P(view.disp),
                   P(view.weight) if full else None, P(view.normals) if full else None, stream)
 
-    def points():
+    def points(k=None):
         _lib.call("lws_tsdf_points", P(vol.T), P(vol.Wt), P(vol.C), *grid, 0.0, ctypes.c_int64(1 << 22), P(work), P(pts.points), P(pts.vnormals),
                   P(pts.counts), stream)
 
-    for name, call, iters in (("integrate_1_frame", lambda: integrate(1, True), a.iters), ("integrate_1_frame_plain", lambda: integrate(1, False), a.iters),
-                              ("integrate_4_frames", lambda: integrate(4, True), a.iters), ("raycast", lambda: raycast(True), max(1, a.iters // 5)),
-                              ("raycast_disp_only", lambda: raycast(False), max(1, a.iters // 5)), ("points", points, a.iters),
-                              ("integrate_1_frame_again", lambda: integrate(1, True), a.iters)):
-        for _ in range(5):
-            call()
-        torch.cuda.synchronize()
-        line[name] = timed(call, iters, a.runs)
+    for name, call, iters in (("integrate_1_frame", lambda k: integrate(1, True), a.iters), ("integrate_1_frame_plain", lambda k: integrate(1, False), a.iters),
+                              ("integrate_4_frames", lambda k: integrate(4, True), a.iters), ("raycast", lambda k: raycast(True), max(1, a.iters // 5)),
+                              ("raycast_disp_only", lambda k: raycast(False), max(1, a.iters // 5)), ("points", points, a.iters),
+                              ("integrate_1_frame_again", lambda k: integrate(1, True), a.iters)):
+        benchkit.warm(call, 5)
+        line[name] = benchkit.summary(benchkit.windows(call, iters, a.runs))
     print(json.dumps(line), flush=True)
 
 

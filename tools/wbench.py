@@ -8,13 +8,10 @@ Prints, per stage: algorithmic bytes (read L, R, the previous map once, write th
 average launch-to-launch time of N back-to-back launches (events on the stream) and the GB/s that is.  Run it under
 `rocprofv3 --kernel-trace --stats` for kernel-only durations."""
 import argparse
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import numpy as np   # noqa: E402
-import torch         # noqa: E402
+import benchkit
+import numpy as np
+import torch
 
 
 def main():
@@ -26,8 +23,7 @@ def main():
     a = ap.parse_args()
     H, W = [int(v) for v in a.size.split("x")]
     from lwsnet_amd import _lib
-    lib = _lib.load()
-    dev = torch.device("cuda:0")
+    lib, dev = benchkit.library(), benchkit.DEV
     B = a.batch
     rng = np.random.default_rng(0)
     H2, W2 = (H + 1) // 2, (W + 1) // 2
@@ -44,20 +40,12 @@ def main():
         cost = torch.empty((B, 9, h, w), device=dev)
         st = torch.cuda.current_stream().cuda_stream
 
-        def launch():
+        def launch(k=None):
             _lib.check(lib.lws_volume_l1_warp(L.data_ptr(), R.data_ptr(), prev.data_ptr(), cost.data_ptr(), None, B, C, h, w, H, W, 5, st),
                        "lws_volume_l1_warp")
 
-        for _ in range(10):
-            launch()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.iters):
-            launch()
-        e1.record()
-        torch.cuda.synchronize()
-        us = e0.elapsed_time(e1) * 1e3 / a.iters
+        benchkit.warm(launch, 10)
+        us = benchkit.windows(launch, a.iters, runs=1, device_sync=True)[0]
         print(f"B={B} {H}x{W} {name}: [{B},{C},{h},{w}] algorithmic {nbytes_survey / 1e6:.2f} MB (SURVEY 8d; {nbytes / 1e6:.2f} MB with the "
               f"full-resolution map): {us:.2f} us per launch back to back = {nbytes_survey / us / 1e3:.0f} GB/s", flush=True)
 

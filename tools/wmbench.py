@@ -13,30 +13,14 @@ shader clock the device held during the stage-1 Conv3D layers of the forward (lw
 Prints one JSON line."""
 import argparse
 import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import benchkit
+import numpy as np
+import torch
+
+benchkit.use_tests()
 
 GEOMETRIES = ((1, 368, 1232), (8, 368, 1232))
-
-
-def timed(call, iters, runs):
-    out = []
-    for _ in range(runs):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            call()
-        e1.record()
-        e1.synchronize()
-        out.append(1e3 * e0.elapsed_time(e1) / iters)
-    out.sort()
-    return {"us": round(out[len(out) // 2], 2), "min_us": round(out[0], 2), "max_us": round(out[-1], 2)}
 
 
 def piecewise_guide(B, H, W, seed):
@@ -59,55 +43,35 @@ def filter_inputs(B, H, W, dev):
             torch.from_numpy(piecewise_guide(B, H, W, 4)).to(dev))
 
 
-def clock_ghz(model):
-    import ctypes
-    from lwsnet_amd import _lib
-    ghz = ctypes.c_double(0.0)
-    rc = _lib.load().lws_clock_read(model._h, ctypes.byref(ghz))
-    return round(ghz.value, 3) if rc == _lib.LWS_OK else None
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--forward_iters", type=int, default=10)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/wmbench.py needs a HIP device")
-    from lwsnet_amd import _lib, build, ops
-    from lwsnet_amd.models import LWSNet
-    from lwsnet_amd.synth import make_batch
-    from lwsnet_amd.weights import default_args, make_state_dict
-    build.build_library()
-    lib = _lib.load()
-    dev = torch.device("cuda:0")
-    model = LWSNet(default_args(), device=dev).set_state_dict(make_state_dict(7)).eval()
+    benchkit.need_device(__file__)
+    from lwsnet_amd import ops
+    dev = benchkit.DEV
+    model = benchkit.seeded_model(build=True)
     wlut = torch.from_numpy(ops.wmedian_lut(10.0)).to(dev)
     result = {"tool": "wmbench", "iters": a.iters, "runs": a.runs, "sigma": 10.0, "geometries": []}
     for B, H, W in GEOMETRIES:
-        left, right = (torch.from_numpy(np.ascontiguousarray(t)).to(dev) for t in make_batch(B, H, W)[:2])
-        for _ in range(3):
-            model(left, right)
-        torch.cuda.synchronize()
-        fwd = timed(lambda: model(left, right), a.forward_iters, a.runs)
-        ghz = None
-        if lib.lws_clock_stamp(model._h, 1) == _lib.LWS_OK:
-            model(left, right)
-            ghz = clock_ghz(model)
-            lib.lws_clock_stamp(model._h, 0)
+        left, right = benchkit.device_batch(B, H, W)
+        benchkit.warm(lambda k: model(left, right), 3)
+        fwd = benchkit.summary(benchkit.windows(lambda k: model(left, right), a.forward_iters, a.runs), "_us")
+        ghz = benchkit.clock_ghz(model, lambda: model(left, right))
         d, m, g = filter_inputs(B, H, W, dev)
         geo = {"geometry": f"{B}x{H}x{W}", "forward": fwd, "clock_ghz": ghz, "filter": []}
         for radius in (1, 2, 3):
             for guided in (False, True):
                 for fill_min in (0, 4):
-                    def call():
+                    def call(k=None):
                         return ops.wmedian_filter(d, radius, rgb=g if guided else None, wlut=wlut if guided else None, mask=m,
                                                   fill_min=fill_min)
                     for _ in range(5):
                         res = call()
                     torch.cuda.synchronize()
-                    t = timed(call, a.iters, a.runs)
+                    t = benchkit.summary(benchkit.windows(call, a.iters, a.runs), "_us")
                     t.update(radius=radius, guide=guided, fill_min=fill_min, over_forward=round(t["us"] / fwd["us"], 4),
                              changed_filled=res.counts.sum(dim=0).tolist())
                     geo["filter"].append(t)
