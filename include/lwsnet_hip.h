@@ -718,6 +718,33 @@ int lws_debug_fill_workspace(lws_handle h, uint32_t word, void *stream);
  * clears the counters afterwards.  Host-side only: no GPU call, any current device.  Forwards with "side_streams" = 0 count
  * nothing (they have no joins). */
 int lws_join_stats(lws_handle h, int64_t *out, int reset);
+/* Test hook (additive after v8): a late side branch.  On an idle device the side stream's work is done long before the caller's
+ * chain reaches the join that waits for it, so a missing join, a misplaced record or a stage buffer laid over one the side branch
+ * still uses gives the right bits by timing alone.  From the next lws_forward / lws_forward_conf / lws_refine of this handle on,
+ * the library queues one bounded delay kernel of `microseconds` on the handle's SIDE stream at the head of every side segment
+ * selected in `segments` -- behind the segment's own wait for its producer, in front of its first kernel.  These are all the
+ * places where the library puts work on a stream that is not the caller's (lws_pool's worker streams are the caller's stream of
+ * the workers' forwards):
+ *   LWS_DELAY_F4     (bit 0)  conv5, which writes the 1/4 map stage 2 joins on;
+ *   LWS_DELAY_F2     (bit 1)  conv6 + classif1, which write the 1/2 map stage 3 joins on;
+ *   LWS_DELAY_LEFT   (bit 2)  refinement1_left, which the refinement joins on;
+ *   LWS_DELAY_CHUNKS (bit 3)  every refinement chunk option "ref_pipe" places on the side stream (a plan without such chunks
+ *                             has no such segment and queues nothing for this bit).
+ * The kernel is one wave that reads the 100 MHz counter (s_memrealtime, the one lws_clock_stamp reads) and sleeps between reads;
+ * it stores nothing, and it leaves after a number of sleeps fixed by the request even if the counter stood still (about twice
+ * the request at the shader clocks the kernels here hold).  segments == 0 or microseconds == 0 switches the hook off, and off means nothing: no launch, no
+ * event, one host branch per segment.  With option "side_streams" = 0 there is no side stream and nothing is queued.  Under
+ * hipGraph capture the delay kernel is captured like every other launch of the side branch.  The setting is handle state that
+ * lws_clone copies as it copies the options, so a pool created from a delayed handle has delayed workers (with
+ * LWS_POOL_SIDE_STREAMS; their "host_joins" stay 0).  microseconds: 0..250000.  LWS_ERR_INVALID for a null handle, unknown
+ * bits and values out of range; the earlier setting then stays.  Host-side only: no GPU call, any current device.
+ * tests/test_gpu_side_delay.py holds every join of the forward with it. */
+#define LWS_DELAY_F4 1
+#define LWS_DELAY_F2 2
+#define LWS_DELAY_LEFT 4
+#define LWS_DELAY_CHUNKS 8
+#define LWS_DELAY_ALL 15
+int lws_debug_delay_side(lws_handle h, int segments, int microseconds);
 
 /* ---- several forwards in flight (no counterpart in the reference: inference.py:105-109 is one thread, one stream) ---- */
 /* A second handle for the same model on the same device: shares src's (read-only) parameter slab, owns its workspace,

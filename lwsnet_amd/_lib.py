@@ -128,6 +128,8 @@ for _name in HEADERS:
 (LWS_ABI_VERSION, LWS_OK, LWS_ERR_INVALID, LWS_ERR_HIP, LWS_ERR_STATE, LWS_ERR_NOMEM, LWS_KC_COUNT, LWS_SPARS_BINS,
  LWS_POOL_SIDE_STREAMS) = (_CONSTANTS[k] for k in ("LWS_ABI_VERSION", "LWS_OK", "LWS_ERR_INVALID", "LWS_ERR_HIP", "LWS_ERR_STATE",
                                                    "LWS_ERR_NOMEM", "LWS_KC_COUNT", "LWS_SPARS_BINS", "LWS_POOL_SIDE_STREAMS"))
+LWS_DELAY_F4, LWS_DELAY_F2, LWS_DELAY_LEFT, LWS_DELAY_CHUNKS, LWS_DELAY_ALL = (
+    _CONSTANTS[k] for k in ("LWS_DELAY_F4", "LWS_DELAY_F2", "LWS_DELAY_LEFT", "LWS_DELAY_CHUNKS", "LWS_DELAY_ALL"))      # lws_debug_delay_side
 ALL_PROTOTYPES = merge_headers({name: table[0] for name, table in ABI.items()})
 
 _lib = None

@@ -288,6 +288,19 @@ int lws_debug_fill_workspace(lws_handle h, uint32_t word, void *stream)
     return LWS_OK;
 }
 
+int lws_debug_delay_side(lws_handle h, int segments, int microseconds)
+{
+    LWS_CHECK_ARG(h, "lws_debug_delay_side: null handle");
+    LWS_CHECK_ARG(segments >= 0 && (segments & ~LWS_DELAY_ALL) == 0, "lws_debug_delay_side: unknown segment bits 0x%x (known: 0x%x)",
+                  segments, LWS_DELAY_ALL);
+    LWS_CHECK_ARG(microseconds >= 0 && microseconds <= 250000, "lws_debug_delay_side: microseconds must be in 0..250000 (got %d)",
+                  microseconds);
+    const bool on = segments != 0 && microseconds != 0;
+    h->opt.delay_segments = on ? segments : 0;
+    h->opt.delay_us = on ? microseconds : 0;
+    return LWS_OK;
+}
+
 const char *lws_kernel_class_name(int kc)
 {
     static const char *names[LWS_KC_COUNT] = {"volume_l1_shift", "volume_l1_warp", "conv3d_first", "conv3d_mid16",

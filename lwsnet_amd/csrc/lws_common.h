@@ -278,6 +278,9 @@ struct lws_ctx {
         int ref_chunk_mb = 72;     // refinement in chunks of pairs whose maps are at most this many MB each (0 = one chunk); see refine_chunk (lws_forward.hip)
         int host_joins = -1;       // the three joins of lws_forward resolved by the host (hipEventQuery) instead of a wait on the caller's queue: -1 = batch 1 and the thread's previous forward on this same handle, 0 / 1; see host_join (lws_forward.hip)
         int host_join_budget_us = 900;    // how long one join polls before it falls back to hipStreamWaitEvent (0 = at once)
+        // lws_debug_delay_side (no option names; here so that lws_clone copies them with the options): the side segments that
+        // begin with a delay kernel, and its length.  Both 0 = off, the state of every handle no test has touched
+        int delay_segments = 0, delay_us = 0;
     } opt;
     lws_join_stat join_stat[3];              // lws_join_stats: the joins of lws_forward in chain order (f4, f2, refinement1_left)
     unsigned prof_mask = 0;                  // kernel classes being timed in the current call

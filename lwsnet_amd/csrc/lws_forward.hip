@@ -148,6 +148,32 @@ void prof_clear(lws_ctx *h)
     h->prof.clear();
 }
 
+// lws_debug_delay_side's kernel: ONE wave that holds its stream for `ticks` ticks of the 100 MHz counter (clock_pair's wall
+// clock), asleep between two reads.  It stores nothing.  One s_sleep 127 is 127 x 64 = 8128 shader cycles: 3.4 us at the 2.4 GHz
+// peak clock, 3.9 us at the 2.1 GHz the kernels here hold, more at any lower clock.  The loop is bounded by `cap` = us / 2 + 2
+// sleeps, so a counter that did not advance ends it after at least 1.7 x the request, about 2 x at 2.1 GHz (0.5 s for the largest
+// request, 250 ms) -- and the cap can never cut a delay short while the counter runs.
+__global__ void __launch_bounds__(64) k_debug_delay(unsigned long long ticks, int cap)
+{
+    unsigned long long shader, t0, t;
+    clock_pair(shader, t0);
+    for (int i = 0; i < cap; ++i) {
+        clock_pair(shader, t);
+        if (t - t0 >= ticks) break;
+        __builtin_amdgcn_s_sleep(127);
+    }
+}
+
+// The head of side segment `bit` (LWS_DELAY_*): lws_debug_delay_side's kernel on the side stream when that segment is selected.
+// Off (every handle no test has touched) this is the one branch.  Callers pass the side stream of a multi-stream plan only.
+static inline int delay_side(const lws_ctx *h, int bit, hipStream_t side)
+{
+    if (!(h->opt.delay_segments & bit)) return LWS_OK;
+    hipLaunchKernelGGL(k_debug_delay, dim3(1), dim3(64), 0, side, (unsigned long long)h->opt.delay_us * 100ull, h->opt.delay_us / 2 + 2);
+    LWS_HIP(hipGetLastError());
+    return LWS_OK;
+}
+
 // low != nullptr: the soft-argmin is wanted too; *fused tells the caller whether it was done here.  fork: see Fork
 static int conv3d_stack(lws_ctx *h, int stage, const float *cost_in, float *cost_out, float *act_a, float *act_b,
                         int B, int D, int hh, int ww, hipStream_t st, float *low = nullptr, float start = 0.f,
@@ -362,6 +388,10 @@ static int refine_rest(lws_ctx *h, const StageMap &pred3, int B, int H, int W, c
         const RefChunk c{b0, std::min(CH, B - b0), pipe ? (k & 1) * CH : 0, (pipe && (k & 1)) ? h->side : st,
                          pipe ? h->ev_feat[k & 1] : nullptr};
         if (pipe && k > 0) LWS_HIP(hipStreamWaitEvent(c.st, h->ev_feat[(k - 1) & 1], 0));
+        if (pipe && (k & 1)) {
+            const int rc = delay_side(h, LWS_DELAY_CHUNKS, c.st);
+            if (rc) return rc;
+        }
         const int rc = refine_rest_chunk(h, pred3, c, H, W, L, pred4, fuse_last);
         if (rc) return rc;
     }
@@ -689,7 +719,11 @@ static int run_forward(lws_ctx *h, const char *what, const float *left, const fl
     const size_t n2 = (size_t)B * 8 * half_up(H) * half_up(W), n4 = n2 / 2, n8 = n2 / 8;   // 8 / 16 / 16 channels
     const float *fl[3] = {f8, f4, f2};
     const float *fr[3] = {f8 + n8, f4 + n4, f2 + n2};
-    if (multi) LWS_HIP(hipStreamWaitEvent(side, h->ev_feat[0], 0));
+    if (multi) {
+        LWS_HIP(hipStreamWaitEvent(side, h->ev_feat[0], 0));
+        rc = delay_side(h, LWS_DELAY_F4, side);
+        if (rc) return rc;
+    }
     rc = feature_tail(h, 2 * B, H, W, L, f8, f4, f2, side, multi ? h->ev_feat : nullptr, 1);          // conv5 -> f4
     if (rc) return rc;
     // where the second fork sits: option "fork2_after" (k = behind stage 1's k-th middle layer, 0 = behind its last layer,
@@ -714,9 +748,17 @@ static int run_forward(lws_ctx *h, const char *what, const float *left, const fl
         if (rc) return rc;
         if (s == 0) {
             // fork 2: the side branch starts once the event is complete (bound or recorded by conv3d_stack)
-            if (multi) LWS_HIP(hipStreamWaitEvent(side, h->ev_fork2, 0));
+            if (multi) {
+                LWS_HIP(hipStreamWaitEvent(side, h->ev_fork2, 0));
+                rc = delay_side(h, LWS_DELAY_F2, side);
+                if (rc) return rc;
+            }
             rc = feature_tail(h, 2 * B, H, W, L, f8, f4, f2, side, multi ? h->ev_feat : nullptr, 2);  // conv6, classif1 -> f2
             if (rc) return rc;
+            if (multi) {
+                rc = delay_side(h, LWS_DELAY_LEFT, side);
+                if (rc) return rc;
+            }
             rc = refine_left(h, left, B, H, W, L, side);                                               // models.py:158
             if (rc) return rc;
             if (multi) LWS_HIP(hipEventRecord(h->ev_join, side));

@@ -134,7 +134,7 @@ int lws_clone(lws_handle src, lws_handle *out)
         return LWS_ERR_NOMEM;
     }
     h->cfg = src->cfg;
-    h->opt = src->opt;
+    h->opt = src->opt;                   // (lws_debug_delay_side's setting with them: the workers of a delayed handle are delayed)
     h->device = src->device;
     h->cu_count = src->cu_count;         // (apply_options, lws_api.hip, copies it into stage[]: a clone must not fall back to the 256 default)
     h->spec = src->spec;

@@ -61,7 +61,7 @@ def compiles(header, path, lines):
 def test_a_compiler_agrees_with_the_reading(tmp_path):
     """Per declared function, the parameter and return types the reader kept, as C text, are the function's type to a C++
     compiler; one scalar misread fails the compile and names the function; LwsConfig has lws_config's size and offsets."""
-    assert sorted(_lib.C_SPELLINGS) == _declared() and len(_lib.C_SPELLINGS) == 66
+    assert sorted(_lib.C_SPELLINGS) == _declared() and len(_lib.C_SPELLINGS) == 67
     lines = {name: _assert_line(name, sp) for name, sp in _lib.C_SPELLINGS.items()}
     config = [f'static_assert(sizeof(lws_config) == {ctypes.sizeof(_lib.LwsConfig)}, "sizeof(lws_config)");\n']
     for field, _ in _lib.LwsConfig._fields_:
@@ -147,8 +147,8 @@ EXTENSIONS = {
 
 def test_every_header_is_in_the_table_and_none_declares_what_another_does():
     assert _lib.HEADERS == ("lwsnet_hip.h", *EXTENSIONS) == tuple(_lib.ABI) and _lib.ABI["lwsnet_hip.h"][0] is _lib.PROTOTYPES
-    assert len(_lib.PROTOTYPES) == 66 and _lib.ABI["lwsnet_hip.h"][1] is _lib.C_SPELLINGS
-    assert len(_lib.ALL_PROTOTYPES) == sum(len(protos) for protos, _, _ in _lib.ABI.values()) == 66 + sum(len(e["protos"]) for e in EXTENSIONS.values())
+    assert len(_lib.PROTOTYPES) == 67 and _lib.ABI["lwsnet_hip.h"][1] is _lib.C_SPELLINGS
+    assert len(_lib.ALL_PROTOTYPES) == sum(len(protos) for protos, _, _ in _lib.ABI.values()) == 67 + sum(len(e["protos"]) for e in EXTENSIONS.values())
 
 
 def test_a_function_declared_by_two_headers_is_refused():

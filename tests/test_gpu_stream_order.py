@@ -19,9 +19,8 @@ What is held:
   g. the pipelined CLIs (inference.inference_pipelined, evaluate._pipelined) with their device-side I/O kernels held back: the
      pool's jobs behind the upload stream, the read-back behind the colour map, the metric's sums behind its kernel.
 
-What this cannot force: a missing JOIN.  A join is the caller's stream waiting for the side branch, and the side stream belongs to the
-handle, so a test cannot stall it; no stall hook is added to the ABI for that.  The joins stay covered by the repeat-and-compare
-tests of tests/test_gpu_host_joins.py and tests/test_gpu_parity.py only."""
+A missing JOIN -- the caller's stream waiting for the side branch -- cannot be forced from here: the side stream belongs to the
+handle.  tests/test_gpu_side_delay.py holds the joins, with lws_debug_delay_side making the side branch late from inside."""
 import contextlib
 import ctypes
 import os
@@ -80,11 +79,16 @@ def pairs(dev):
     return cu(left, dev), cu(right, dev), left, right
 
 
+_ORACLE = []
+
+
 @pytest.fixture(scope="module")
 def oracle(net, pairs):
     """The C oracle's four stage maps of the eight pairs, [8,1,H,W] each (pairs are independent of their batch)."""
-    from oracle import c_oracle
-    return c_oracle.forward(pairs[2], pairs[3], net.state_dict())
+    if not _ORACLE:         # once per process: tests/test_gpu_side_delay.py borrows this fixture, and the pairs and weights are fixed
+        from oracle import c_oracle
+        _ORACLE.extend(c_oracle.forward(pairs[2], pairs[3], net.state_dict()))
+    return list(_ORACLE)
 
 
 def maps_of(oracle, lo, B):

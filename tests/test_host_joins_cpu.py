@@ -40,6 +40,19 @@ def test_names_defaults_and_ranges(hip_lib):
     assert hip_lib.lws_destroy(h) == 0
 
 
+def test_debug_delay_side_arguments_on_the_host(hip_lib):
+    """lws_debug_delay_side is host-side state: known bits, 0..250000 microseconds, a null handle refused."""
+    h = _create(hip_lib)
+    assert (_lib.LWS_DELAY_F4, _lib.LWS_DELAY_F2, _lib.LWS_DELAY_LEFT, _lib.LWS_DELAY_CHUNKS, _lib.LWS_DELAY_ALL) == (1, 2, 4, 8, 15)
+    for segments, us in ((0, 0), (1, 1), (15, 250000), (4, 0), (0, 50000), (8, 50000)):
+        assert hip_lib.lws_debug_delay_side(h, segments, us) == 0, (segments, us)
+    for segments, us in ((16, 50000), (-1, 50000), (31, 50000), (4, -1), (4, 250001), (1 << 30, 0)):
+        assert hip_lib.lws_debug_delay_side(h, segments, us) == _lib.LWS_ERR_INVALID, (segments, us)
+        assert b"lws_debug_delay_side" in hip_lib.lws_last_error()
+    assert hip_lib.lws_debug_delay_side(None, 4, 50000) == _lib.LWS_ERR_INVALID
+    assert hip_lib.lws_destroy(h) == 0
+
+
 def test_join_stats_on_the_host(hip_lib):
     h = _create(hip_lib)
     out = (ctypes.c_int64 * 12)(*[7] * 12)
