@@ -99,7 +99,7 @@ int64_t lws_tsdf_points_workspace(int Gy, int Gz);
  * many fit; only records of rank < max_points are written and nothing past them is touched.
  * Three launches, as lws_point_cloud: per x-row counts, an exclusive scan in the workspace, a scatter ranked by wave ballots.  No
  * atomics: the same bytes on every run.  workspace: lws_tsdf_points_workspace bytes, contents undefined before and after.
- * Marching-cubes triangles are out of scope. */
+ * The triangles between these points: lws_tsdf_mesh (include/lwsnet_tsdf_mesh.h), whose vertex list is this record list. */
 int lws_tsdf_points(const float *T, const float *Wt, const uint8_t *C, int Gx, int Gy, int Gz, float ox, float oy, float oz, float vs,
                     float w_min, int64_t max_points, void *workspace, void *points, float *vnormals, int64_t *counts, void *stream);
 

@@ -1,7 +1,8 @@
 """ctypes binding of liblwsnet_hip.so.  include/lwsnet_hip.h is the statement of the C ABI: PROTOTYPES and the LWS_*
 constants are read from it when this module is imported (tests/test_abi_cpu.py has a C++ compiler check the reading).  The entry
 points added behind ABI v8 live in headers of their own, named in HEADERS; each is read the same way into ABI[header name], and a
-new header is one more name there.
+new header is one more name there.  lws_tsdf_mesh's header is read the same way into a table of its own, MESH_ABI, beside these:
+HEADERS, ABI and ALL_PROTOTYPES are the functions the stream-ordering table of tests/test_gpu_stream_order.py has a row for.
 
 The header cannot say which pointers are host pointers, so every pointer but `const char *` is c_void_p: the 20 host-pointer
 parameters -- lws_set_tensor's data and shape, the mean / std arrays, lws_profile_read*, lws_clock_read, lws_join_stats, the
@@ -20,6 +21,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblwsnet_hip.so")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 HEADERS = ("lwsnet_hip.h", "lwsnet_objects.h", "lwsnet_temporal.h", "lwsnet_egomotion.h", "lwsnet_tsdf.h")      # the base header first
+MESH_HEADERS = ("lwsnet_tsdf_mesh.h",)
 HEADER_PATH = os.path.join(INCLUDE, HEADERS[0])
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
@@ -116,21 +118,30 @@ def merge_headers(tables):
     return merged
 
 
+def _read(name):
+    """include/<name> -> ((prototypes, spellings, path), constants)"""
+    with open(os.path.join(INCLUDE, name)) as f:
+        protos, spellings, consts = parse_header(f.read(), f.name)
+    return (protos, spellings, f.name), consts
+
+
+_READ = {name: _read(name) for name in (*HEADERS, *MESH_HEADERS)}
 # header name -> (prototypes, spellings, path): name -> (restype, argtypes) and name -> (C return type, C parameter types), exactly
 # the functions that header declares; PROTOTYPES, C_SPELLINGS and the constants are the base header's
-ABI = {}
-for _name in HEADERS:
-    with open(os.path.join(INCLUDE, _name)) as _f:
-        _protos, _spellings, _consts = parse_header(_f.read(), _f.name)
-    ABI[_name] = (_protos, _spellings, _f.name)
-    if _name == HEADERS[0]:
-        PROTOTYPES, C_SPELLINGS, _CONSTANTS = _protos, _spellings, _consts
+ABI = {name: _READ[name][0] for name in HEADERS}
+_CONSTANTS = _READ[HEADERS[0]][1]
+PROTOTYPES, C_SPELLINGS = ABI[HEADERS[0]][:2]
 (LWS_ABI_VERSION, LWS_OK, LWS_ERR_INVALID, LWS_ERR_HIP, LWS_ERR_STATE, LWS_ERR_NOMEM, LWS_KC_COUNT, LWS_SPARS_BINS,
  LWS_POOL_SIDE_STREAMS) = (_CONSTANTS[k] for k in ("LWS_ABI_VERSION", "LWS_OK", "LWS_ERR_INVALID", "LWS_ERR_HIP", "LWS_ERR_STATE",
                                                    "LWS_ERR_NOMEM", "LWS_KC_COUNT", "LWS_SPARS_BINS", "LWS_POOL_SIDE_STREAMS"))
 LWS_DELAY_F4, LWS_DELAY_F2, LWS_DELAY_LEFT, LWS_DELAY_CHUNKS, LWS_DELAY_ALL = (
     _CONSTANTS[k] for k in ("LWS_DELAY_F4", "LWS_DELAY_F2", "LWS_DELAY_LEFT", "LWS_DELAY_CHUNKS", "LWS_DELAY_ALL"))      # lws_debug_delay_side
 ALL_PROTOTYPES = merge_headers({name: table[0] for name, table in ABI.items()})
+# lws_tsdf_mesh: the same three per header, and what load() binds of it
+MESH_ABI = {name: _READ[name][0] for name in MESH_HEADERS}
+LWS_TSDF_MESH_MAX_TRIS = _READ[MESH_HEADERS[0]][1]["LWS_TSDF_MESH_MAX_TRIS"]
+MESH_PROTOTYPES = merge_headers({name: table[0] for name, table in MESH_ABI.items()})
+merge_headers({name: table[0] for name, table in (*ABI.items(), *MESH_ABI.items())})       # a name two headers declare raises
 
 _lib = None
 
@@ -156,7 +167,7 @@ def load():
             f"{LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python -m lwsnet_amd.build`); there is no CPU fallback for the disparity path")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in ALL_PROTOTYPES.items():
+    for name, (res, args) in (*ALL_PROTOTYPES.items(), *MESH_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -15,36 +15,19 @@
 //   lws_tsdf_raycast     k_ts_raycast  one thread per pixel; a step gathers the eight taps of Wt and, where all are known, of T.
 //                        Neighbouring rays walk neighbouring cells, so a wave's taps share cache lines.
 //   lws_tsdf_points      k_ts_count, k_ts_scan, k_ts_scatter: lws_point_cloud's form (lws_packkit.h) with an x-row of the volume in
-//                        the place of an image row, 64-bit offsets (a volume has up to 3 * 2^31 edges) and a capacity.
+//                        the place of an image row, 64-bit offsets (a volume has up to 3 * 2^31 edges) and a capacity.  The same
+//                        three launches (tsdfkit::launch_points) give lws_tsdf_mesh (lws_tsdf_mesh.hip) its vertices.
 // Determinism: a voxel, a pixel and a record belong to one thread; what crosses threads is the integer add of `updated` and the
 // ballots of the scatter.  0 bytes of scratch.
-#include "lws_geomkit.h"
-#include "lws_packkit.h"
+#include "lws_tsdfkit.h"
 
 namespace lws {
 
 namespace {
 
-using namespace geomkit;
+using namespace tsdfkit;                                    // Vol, observed, edge_bits, voxel_normal
 using namespace packkit;                                    // kThreads, kWaves
 using u64 = unsigned long long;
-constexpr int kMaxGrid = 4096;
-
-// g / |g| as lws_surface_normals normalises, zero where the length is not finite or not > 0
-__device__ __forceinline__ void normalise(float gx, float gy, float gz, float n[3])
-{
-    const float len = sqrtf((gx * gx + gy * gy) + gz * gz);
-    const bool good = __builtin_isfinite(len) && len > 0.0f;
-    n[0] = good ? gx / len : 0.0f, n[1] = good ? gy / len : 0.0f, n[2] = good ? gz / len : 0.0f;
-}
-
-struct Vol {                                                // the volume as the read-only kernels see it
-    const float *T, *Wt;
-    int Gx, Gy, Gz;
-    float ox, oy, oz, vs, w_min;
-};
-
-__device__ __forceinline__ bool observed(float w, float w_min) { return w > 0.0f && w >= w_min; }
 
 // ---- integrate ----
 struct IntArgs {                                            // by value in the kernel arguments
@@ -293,25 +276,6 @@ __global__ __launch_bounds__(kThreads) void k_ts_raycast(Vol v, const float *__r
 }
 
 // ---- points ----
-// The crossings on the three edges that leave voxel (ix, iy, iz) towards +x, +y, +z: bit e = axis e; Ta and Tb[e] of a set bit.
-__device__ __forceinline__ unsigned edge_bits(const Vol &v, int ix, int iy, int iz, float &Ta, float Tb[3])
-{
-    const int i = (iz * v.Gy + iy) * v.Gx + ix;
-    if (!observed(v.Wt[i], v.w_min)) return 0u;
-    Ta = v.T[i];
-    const int stride[3] = {1, v.Gx, v.Gy * v.Gx};
-    const bool in[3] = {ix + 1 < v.Gx, iy + 1 < v.Gy, iz + 1 < v.Gz};
-    unsigned bits = 0u;
-#pragma unroll
-    for (int e = 0; e < 3; ++e) {
-        Tb[e] = 0.0f;
-        if (!in[e] || !observed(v.Wt[i + stride[e]], v.w_min)) continue;
-        Tb[e] = v.T[i + stride[e]];
-        bits |= ((Ta > 0.0f && Tb[e] <= 0.0f) || (Ta <= 0.0f && Tb[e] > 0.0f) ? 1u : 0u) << e;
-    }
-    return bits;
-}
-
 // grid (Gy, Gz), 256 threads: the crossings of each x-row -> row_count[iz * Gy + iy].
 __global__ __launch_bounds__(kThreads) void k_ts_count(Vol v, int64_t *__restrict__ row_count)
 {
@@ -332,19 +296,6 @@ __global__ __launch_bounds__(kThreads) void k_ts_scan(int64_t *__restrict__ r, i
     __shared__ int64_t s_w[kWaves];
     const int64_t total = row_scan(r, R, s_w);
     if (threadIdx.x == 0) counts[0] = total;
-}
-
-// the central difference of T over the six neighbours of voxel (ix, iy, iz), normalised; zero unless all six are inside and observed
-__device__ __forceinline__ void voxel_normal(const Vol &v, int ix, int iy, int iz, float n[3])
-{
-    n[0] = n[1] = n[2] = 0.0f;
-    if (ix < 1 || iy < 1 || iz < 1 || ix + 1 >= v.Gx || iy + 1 >= v.Gy || iz + 1 >= v.Gz) return;
-    const int i = (iz * v.Gy + iy) * v.Gx + ix, sy = v.Gx, sz = v.Gy * v.Gx;
-    const int o[6] = {i + 1, i - 1, i + sy, i - sy, i + sz, i - sz};
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-        if (!observed(v.Wt[o[k]], v.w_min)) return;
-    normalise(v.T[o[0]] - v.T[o[1]], v.T[o[2]] - v.T[o[3]], v.T[o[4]] - v.T[o[5]], n);
 }
 
 // grid (Gy, Gz), 256 threads: the crossings of the x-row in the order (ix, axis) to the records row_off[iz * Gy + iy] ..; a chunk
@@ -391,7 +342,17 @@ __global__ __launch_bounds__(kThreads) void k_ts_scatter(Vol v, const unsigned *
 }
 
 // ---- host ----
-int check_volume(const char *who, const float *T, const float *Wt, int Gx, int Gy, int Gz, float ox, float oy, float oz, float vs)
+int check_views(const char *who, const float *cam, const float *pose, int B, int H, int W)
+{
+    LWS_CHECK_ARG(cam && pose, "%s: cam and pose must not be null", who);
+    LWS_CHECK_RC(check_view_shape(who, B, H, W));
+    LWS_CHECK_ARG(aligned(cam, 4) && aligned(pose, 4), "%s: cam / pose must be 4-byte aligned", who);
+    return LWS_OK;
+}
+
+}  // namespace
+
+int tsdfkit::check_volume(const char *who, const float *T, const float *Wt, int Gx, int Gy, int Gz, float ox, float oy, float oz, float vs)
 {
     LWS_CHECK_ARG(T && Wt, "%s: T and Wt must not be null", who);
     LWS_CHECK_ARG(Gx >= 2 && Gx <= kMaxGrid && Gy >= 2 && Gy <= kMaxGrid && Gz >= 2 && Gz <= kMaxGrid,
@@ -404,15 +365,18 @@ int check_volume(const char *who, const float *T, const float *Wt, int Gx, int G
     return LWS_OK;
 }
 
-int check_views(const char *who, const float *cam, const float *pose, int B, int H, int W)
+int tsdfkit::launch_points(const Vol &v, const uint8_t *C, int64_t max_points, int64_t *rows, void *points, float *vnormals, int64_t *counts,
+                           hipStream_t st)
 {
-    LWS_CHECK_ARG(cam && pose, "%s: cam and pose must not be null", who);
-    LWS_CHECK_RC(check_view_shape(who, B, H, W));
-    LWS_CHECK_ARG(aligned(cam, 4) && aligned(pose, 4), "%s: cam / pose must be 4-byte aligned", who);
+    hipLaunchKernelGGL(k_ts_count, dim3(v.Gy, v.Gz), dim3(kThreads), 0, st, v, rows);
+    LWS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_ts_scan, dim3(1), dim3(kThreads), 0, st, rows, v.Gy * v.Gz, counts);
+    LWS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_ts_scatter, dim3(v.Gy, v.Gz), dim3(kThreads), 0, st, v, reinterpret_cast<const unsigned *>(C), rows, max_points,
+                       static_cast<uint4 *>(points), reinterpret_cast<float4 *>(vnormals));
+    LWS_LAUNCH_CHECK();
     return LWS_OK;
 }
-
-}  // namespace
 
 }  // namespace lws
 
@@ -511,16 +475,7 @@ int lws_tsdf_points(const float *T, const float *Wt, const uint8_t *C, int Gx, i
     LWS_CHECK_RC(check_no_overlap(who, bufs, 7, 4));
 
     const Vol v = {T, Wt, Gx, Gy, Gz, ox, oy, oz, vs, w_min};
-    int64_t *rows = static_cast<int64_t *>(workspace);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_ts_count, dim3(Gy, Gz), dim3(kThreads), 0, st, v, rows);
-    LWS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_ts_scan, dim3(1), dim3(kThreads), 0, st, rows, Gy * Gz, counts);
-    LWS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_ts_scatter, dim3(Gy, Gz), dim3(kThreads), 0, st, v, reinterpret_cast<const unsigned *>(C), rows, max_points,
-                       static_cast<uint4 *>(points), reinterpret_cast<float4 *>(vnormals));
-    LWS_LAUNCH_CHECK();
-    return LWS_OK;
+    return launch_points(v, C, max_points, static_cast<int64_t *>(workspace), points, vnormals, counts, (hipStream_t)stream);
 }
 
 }  // extern "C"

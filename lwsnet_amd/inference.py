@@ -123,7 +123,7 @@ estimate spans the gap.  The op reads nothing back; the CLI reads the estimate's
 be trusted (bit 3) resets the filter for that frame, with a warning.
 
 `--tsdf [--tsdf_voxel V] [--tsdf_extent X0 X1 Y0 Y1 Z0 Z1] [--tsdf_trunc MU0] [--tsdf_trunc_px MU_D] [--tsdf_weight unit|sigma]
-[--tsdf_sdf plane|ray] [--save_tsdf_ply PATH] [--save_tsdf]`: directory mode only, sequential, needs a camera and the pose of every
+[--tsdf_sdf plane|ray] [--save_tsdf_ply PATH] [--save_tsdf_mesh PATH] [--save_tsdf]`: directory mode only, sequential, needs a camera and the pose of every
 pair, from `--poses PATH` or `--egomotion`.  The stage-4 map of each frame -- with `--temporal` the fused map and its sigma -- is
 integrated behind the chain into a dense TSDF volume (lwsnet_amd.tsdf.TsdfVolume, lws_tsdf_integrate) under the chain's `keep` codes
 and with the left crop's colours.  The volume's frame is the first camera integrated (y down, z forward); the extent is in metres
@@ -131,8 +131,9 @@ there, the voxel V metres wide (default 0.2 over -12.8 12.8 -3.2 3.2 0 51.2).  `
 pixel's tangent plane, with the normals of lws_surface_normals at `--max_jump`; `ray` measures it along the ray, which starves a road
 seen at a grazing angle of updates.  One log line per frame gives the voxels updated.  `--save_tsdf` writes `<stem>_tsdf.png`, the
 volume ray-cast into the frame's own pose and coloured as the stage maps: the denoised model view of that frame.  At the end
-`--save_tsdf_ply PATH` writes the volume's zero crossings as a PLY of vertices with normals and colours and logs their number.  A
-volume that does not fit the device's free memory is an error before the first frame.  What leaves the volume is not mapped; movers
+`--save_tsdf_ply PATH` writes the volume's zero crossings as a PLY of vertices with normals and colours and logs their number;
+`--save_tsdf_mesh PATH` writes the same vertices, in the same order, with the marching-cubes triangles between them
+(lws_tsdf_mesh, include/lwsnet_tsdf_mesh.h) and logs vertices and faces.  A volume that does not fit the device's free memory is an error before the first frame.  What leaves the volume is not mapped; movers
 smear; the poses are taken as given.
 """
 import argparse
@@ -155,8 +156,8 @@ from .outputs import (STIXEL_COLOUR_DEPTH, bev_to_u8, conf_to_u8, ground_to_rgb,
                       sigma_to_u8, stixels_to_csv, stixels_to_rgb, geometry_requested as _geometry_requested)      # these stay this module's names
 from .postprocess import (add_lr_arguments, add_occ_arguments, add_speckle_arguments, add_wmedian_arguments, check_lr_arguments,
                           check_occ_arguments, check_speckle_arguments, check_wmedian_arguments)
-from .sequence import (TSDF_DEFAULTS, check_egomotion_arguments, check_temporal_arguments, check_tsdf_arguments,  # noqa: F401
-                       list_pairs as _list_pairs, temporal_sigma, tsdf_grid)
+from .sequence import (TSDF_DEFAULTS, TSDF_MESH_DEFAULTS, check_egomotion_arguments, check_temporal_arguments,  # noqa: F401
+                       check_tsdf_arguments, check_tsdf_mesh_arguments, list_pairs as _list_pairs, temporal_sigma, tsdf_grid)
 
 
 def build_parser():
@@ -668,6 +669,7 @@ def main(argv=None):
     check_egomotion_arguments(parser, args)
     poses = check_temporal_arguments(parser, args)
     alone = check_tsdf_arguments(parser, args)              # the file of --poses comes from the one of the two checks that read it
+    check_tsdf_mesh_arguments(parser, args)
     log = start_logging("lwsnet_amd.inference", args)
     model = load_model(args, log)
     if getattr(args, "split_bf16", False):

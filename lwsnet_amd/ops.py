@@ -1140,6 +1140,30 @@ def tsdf_points(T, Wt, origin, voxel, max_points, C=None, w_min=0.0, with_normal
     return TsdfPoints(points, vn, counts)
 
 
+TsdfMesh = namedtuple("TsdfMesh", ["points", "vnormals", "faces", "counts"])
+TsdfMesh.__doc__ = """What tsdf_mesh returns: points uint8 [max_points,16] and vnormals float32 [max_points,4] (None unless asked for), the
+records and normals of tsdf_points; faces int32 [max_faces,3], indices into the records; counts, an int64 [2] device tensor: the
+vertices and the faces found.  The first min(counts[0], max_points) records are written, and the first min(counts[1], max_faces)
+faces unless counts[0] > max_points, which leaves every face unwritten."""
+
+
+def tsdf_mesh(T, Wt, origin, voxel, max_points, max_faces, C=None, w_min=0.0, with_normals=True):
+    """The zero level set of a TSDF volume as an indexed triangle mesh: marching cubes whose vertices are the records of tsdf_points
+    in their order (include/lwsnet_tsdf_mesh.h, lws_tsdf_mesh).  max_points, max_faces: the capacities.  Returns a TsdfMesh."""
+    g = tsdf_volume_args(origin, voxel, T.shape[::-1] if isinstance(T, torch.Tensor) and T.dim() == 3 else ())
+    max_points = _int_in("max_points", max_points, 1, (1 << 31) - 1)
+    max_faces = _int_in("max_faces", max_faces, 1, (1 << 31) - 1)
+    w_min = _tsdf_w_min(w_min)
+    dev = _tsdf_volume(T, Wt, C, g)
+    work = _workspace("lws_tsdf_mesh_workspace", dev, g[1], g[2])
+    points = torch.empty((max_points, 16), device=dev, dtype=torch.uint8)
+    vn = torch.empty((max_points, 4), device=dev, dtype=torch.float32) if with_normals else None
+    faces = torch.empty((max_faces, 3), device=dev, dtype=torch.int32)
+    counts = torch.empty((2,), device=dev, dtype=torch.int64)
+    _call("lws_tsdf_mesh", dev, T, Wt, C, *g, w_min, ctypes.c_int64(max_points), ctypes.c_int64(max_faces), work, points, vn, faces, counts)
+    return TsdfMesh(points, vn, faces, counts)
+
+
 SpeckleResult = namedtuple("SpeckleResult", ["disp", "mask", "labels", "counts"])
 SpeckleResult.__doc__ = """What speckle_filter returns: the filtered (filled if asked) maps float32 [B,1,H,W], the uint8 code map (1 kept,
 3 speckle, the input code or 0 for an invalid pixel), labels int32 [B,1,H,W] (None unless want_labels) and counts, an int64

@@ -93,6 +93,8 @@ def add_sequence_arguments(p):
                    help="tsdf: the distance to the pixel's tangent plane (surface normals with --max_jump) or along the ray (default plane)")
     p.add_argument("--save_tsdf_ply", type=str, default=S, metavar="PATH",
                    help="tsdf: at the end, write the volume's zero crossings as a binary PLY of vertices with normals and colours")
+    p.add_argument("--save_tsdf_mesh", type=str, default=S, metavar="PATH",
+                   help="tsdf: at the end, write the volume's zero level set as a binary PLY of the same vertices and the triangles between them")
     p.add_argument("--save_tsdf", action="store_true", default=S, help="tsdf: write <stem>_tsdf.png, the volume ray-cast into the frame's own pose, coloured as the stage maps")
 
 
@@ -185,6 +187,17 @@ def check_tsdf_arguments(p, args):
     post.in_range(p.error, "--tsdf_trunc_px", args.tsdf_trunc_px)
     read = getattr(args, "temporal", False) or getattr(args, "egomotion", False)      # check_temporal_arguments read the file, or there is none
     return None if read else read_poses(p, args)
+
+
+TSDF_MESH_DEFAULTS = dict(save_tsdf_mesh=None)             # a table of its own: TSDF_DEFAULTS is the flags --tsdf came with
+TSDF_MAX_FACES = 1 << 23                                    # the capacity of --save_tsdf_mesh, in triangles of 13 bytes
+
+
+def check_tsdf_mesh_arguments(p, args):
+    """--save_tsdf_mesh, behind check_tsdf_arguments: sets the default; the flag without --tsdf is refused."""
+    post.set_defaults(args, **TSDF_MESH_DEFAULTS)
+    if args.save_tsdf_mesh is not None and not getattr(args, "tsdf", False):
+        p.error("--save_tsdf_mesh needs --tsdf")
 
 
 class PoseSource:
@@ -343,13 +356,17 @@ class _Volume(_Stage):
         path = self.args.save_tsdf_ply
         if path is not None:
             log.info("Save TSDF points = {}, vertices = {}".format(path, self.volume.write_ply(path, max_points=TSDF_MAX_POINTS)))
-        return [] if path is None else [path]
+        mesh = self.args.save_tsdf_mesh
+        if mesh is not None:
+            log.info("Save TSDF mesh = {}, vertices = {}, faces = {}".format(
+                mesh, *self.volume.write_mesh_ply(mesh, max_points=TSDF_MAX_POINTS, max_faces=TSDF_MAX_FACES)))
+        return [f for f in (path, mesh) if f is not None]
 
 
 def begin(args, pairs, device, log, poses=None):
     """(the PoseSource, the stages that are on, in the order they run) of a run over `pairs` pairs.  poses: what the checks read;
     a namespace that skipped the checks gets the flags' defaults and its --poses file read here."""
-    post.set_defaults(args, **TEMPORAL_DEFAULTS, **EGO_DEFAULTS, **TSDF_DEFAULTS)
+    post.set_defaults(args, **TEMPORAL_DEFAULTS, **EGO_DEFAULTS, **TSDF_DEFAULTS, **TSDF_MESH_DEFAULTS)
     if poses is None and args.poses is not None and not args.egomotion:
         from .geometry import read_kitti_poses
         poses = read_kitti_poses(args.poses)

@@ -71,3 +71,20 @@ class TsdfVolume:
             raise ValueError(f"the volume has {n} crossings, more than max_points = {max_points}")
         geometry.write_mesh_ply(path, res.points[:n].cpu().numpy().tobytes(), n, np.zeros((0, 3), np.int32), res.vnormals[:n].cpu().numpy())
         return n
+
+    def mesh(self, max_points, max_faces, w_min=0.0, with_normals=True):
+        """ops.tsdf_mesh on the volume: the points above as the vertices of a triangle mesh, and the faces that index them."""
+        return ops.tsdf_mesh(self.T, self.Wt, self.origin, self.voxel, max_points, max_faces, C=self.C, w_min=w_min, with_normals=with_normals)
+
+    def write_mesh_ply(self, path, max_points=1 << 22, max_faces=1 << 23, w_min=0.0):
+        """Writes the mesh as a binary PLY of vertices with normals and colours and of triangles (geometry.write_mesh_ply): vertex i is
+        vertex i of write_ply's file.  Returns (vertices, faces) written; more of either than its capacity is an error, nothing is
+        written then."""
+        res = self.mesh(max_points, max_faces, w_min=w_min)
+        n, m = (int(c) for c in res.counts.cpu())
+        if n > max_points:
+            raise ValueError(f"the volume has {n} crossings, more than max_points = {max_points}")
+        if m > max_faces:
+            raise ValueError(f"the mesh has {m} faces, more than max_faces = {max_faces}")
+        geometry.write_mesh_ply(path, res.points[:n].cpu().numpy().tobytes(), n, res.faces[:m].cpu().numpy(), res.vnormals[:n].cpu().numpy())
+        return n, m

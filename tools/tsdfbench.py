@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The three TSDF calls timed with device events (development aid, not the judged bench).
+"""The TSDF calls timed with device events (development aid, not the judged bench).
 
     python tools/tsdfbench.py [--iters N] [--runs R]
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/tsdfbench.py --iters 20 --runs 1      # the k_ts_* kernels one by one
@@ -9,9 +9,9 @@ from four poses 0.5 m apart, with the normals of ops.surface_normals and a rando
 default: 129 x 33 x 257 voxels of 0.2 m from (-12.8, -3.2, 0), a band of 0.6 m, unit weights.  Timed on buffers allocated once,
 after a warm-up, R windows of N calls between two events, the median window per call: lws_tsdf_integrate of one frame into the
 volume the four frames left (normals, colour and `updated`: two launches), the same without normals, colour and `updated` (one
-launch), of the four frames in one call, lws_tsdf_raycast of the third pose (step 0.1 m) with weight and normals and without, and
-lws_tsdf_points.  A window integrates the same frame again and again, so the weights grow; the arithmetic per voxel does not depend
-on them.  Prints one JSON line with the times, the voxels taken per frame, the pixels that hit and the points found."""
+launch), of the four frames in one call, lws_tsdf_raycast of the third pose (step 0.1 m) with weight and normals and without,
+lws_tsdf_points, and lws_tsdf_mesh on the same volume (the three launches of the points and three more).  A window integrates the same frame again and again, so the weights grow; the arithmetic per voxel does not depend
+on them.  Prints one JSON line with the times, the voxels taken per frame, the pixels that hit, the points and the faces found."""
 import argparse
 import ctypes
 import json
@@ -57,8 +57,10 @@ def main():
     updated = vol.integrate(disp, [cam1] * n, poses, normals=normals, rgb=rgb)
     view = vol.raycast(cam1, poses[2], H, W, z_near=0.5, step=0.1, nsteps=560)
     pts = vol.points(1 << 22)
+    msh = vol.mesh(1 << 22, 1 << 23)
     line = {"tool": "tsdfbench", "map": f"{H}x{W}", "volume": "x".join(str(d) for d in DIMS), "voxel": VOXEL, "iters": a.iters, "runs": a.runs,
-            "updated_per_frame": updated.cpu().tolist(), "pixels_hit": int((view.disp > 0).sum()), "points_found": int(pts.counts[0])}
+            "updated_per_frame": updated.cpu().tolist(), "pixels_hit": int((view.disp > 0).sum()), "points_found": int(pts.counts[0]),
+            "faces_found": int(msh.counts[1])}
 
     P, stream = benchkit.ptr, benchkit.stream()
     cam = torch.from_numpy(camera_rows([cam1] * n, n)).to(dev)
@@ -66,6 +68,7 @@ def main():
     grid = (*DIMS, *ORIGIN, VOXEL)
     upd = torch.empty((n,), dtype=torch.int64, device=dev)
     work = torch.empty((_lib.nbytes("lws_tsdf_points_workspace", DIMS[1], DIMS[2]),), dtype=torch.uint8, device=dev)
+    mwork = torch.empty((_lib.nbytes("lws_tsdf_mesh_workspace", DIMS[1], DIMS[2]),), dtype=torch.uint8, device=dev)
 
     def integrate(B, full):
         _lib.call("lws_tsdf_integrate", P(disp), None, None, P(normals) if full else None, P(rgb) if full else None, P(cam), P(pose), B, H, W, P(vol.T),
@@ -79,9 +82,13 @@ def main():
         _lib.call("lws_tsdf_points", P(vol.T), P(vol.Wt), P(vol.C), *grid, 0.0, ctypes.c_int64(1 << 22), P(work), P(pts.points), P(pts.vnormals),
                   P(pts.counts), stream)
 
+    def mesh(k=None):
+        _lib.call("lws_tsdf_mesh", P(vol.T), P(vol.Wt), P(vol.C), *grid, 0.0, ctypes.c_int64(1 << 22), ctypes.c_int64(1 << 23), P(mwork), P(msh.points),
+                  P(msh.vnormals), P(msh.faces), P(msh.counts), stream)
+
     for name, call, iters in (("integrate_1_frame", lambda k: integrate(1, True), a.iters), ("integrate_1_frame_plain", lambda k: integrate(1, False), a.iters),
                               ("integrate_4_frames", lambda k: integrate(4, True), a.iters), ("raycast", lambda k: raycast(True), max(1, a.iters // 5)),
-                              ("raycast_disp_only", lambda k: raycast(False), max(1, a.iters // 5)), ("points", points, a.iters),
+                              ("raycast_disp_only", lambda k: raycast(False), max(1, a.iters // 5)), ("points", points, a.iters), ("mesh", mesh, a.iters), ("points_again", points, a.iters),
                               ("integrate_1_frame_again", lambda k: integrate(1, True), a.iters)):
         benchkit.warm(call, 5)
         line[name] = benchkit.summary(benchkit.windows(call, iters, a.runs))
