@@ -98,7 +98,8 @@ int lws_ego_normal(const float *grey_ref, const float *disp_ref, const uint8_t *
  * images (so `levels` launches for the pyramids, not the one or two a fused pyramid would take: a level needs the level below it
  * complete); two per step; two for the final linearisation: levels + 2 * levels * iters + 2.
  * Out of scope, stated and left as it is: movers are neither tracked nor segmented (resid only shows them); no loop closure,
- * keyframes or bundle adjustment; no geometric (disparity) error term; no photometric gain and offset; drift over long sequences
+ * keyframes or bundle adjustment; no geometric (disparity) error term here (lws_track of
+ * lwsnet_track.h has one, against the TSDF model); no photometric gain and offset; drift over long sequences
  * is not bounded; real KITTI accuracy is unknown -- the defaults of the Python layer have met a synthetic scene only. */
 int lws_egomotion(const uint8_t *rgb_ref, const float *disp_ref, const uint8_t *mask, const uint8_t *rgb_cur, const float *cam,
                   const float *init, int B, int H, int W, int levels, int iters, float min_disp, float max_jump, float huber,

@@ -1,8 +1,9 @@
 """ctypes binding of liblwsnet_hip.so.  include/lwsnet_hip.h is the statement of the C ABI: PROTOTYPES and the LWS_*
 constants are read from it when this module is imported (tests/test_abi_cpu.py has a C++ compiler check the reading).  The entry
 points added behind ABI v8 live in headers of their own, named in HEADERS; each is read the same way into ABI[header name], and a
-new header is one more name there.  lws_tsdf_mesh's header is read the same way into a table of its own, MESH_ABI, beside these:
-HEADERS, ABI and ALL_PROTOTYPES are the functions the stream-ordering table of tests/test_gpu_stream_order.py has a row for.
+new header is one more name there.  HEADERS, ABI and ALL_PROTOTYPES are the functions the stream-ordering table of
+tests/test_gpu_stream_order.py has a row for; lws_tsdf_mesh's header and lws_track's (include/lwsnet_track.h) are read the same way
+into tables of their own beside these, MESH_ABI and TRACK_ABI, and their calls' stream tests are in their own test files.
 
 The header cannot say which pointers are host pointers, so every pointer but `const char *` is c_void_p: the 20 host-pointer
 parameters -- lws_set_tensor's data and shape, the mean / std arrays, lws_profile_read*, lws_clock_read, lws_join_stats, the
@@ -22,6 +23,7 @@ LIB_PATH = os.path.join(_HERE, "liblwsnet_hip.so")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 HEADERS = ("lwsnet_hip.h", "lwsnet_objects.h", "lwsnet_temporal.h", "lwsnet_egomotion.h", "lwsnet_tsdf.h")      # the base header first
 MESH_HEADERS = ("lwsnet_tsdf_mesh.h",)
+TRACK_HEADERS = ("lwsnet_track.h",)
 HEADER_PATH = os.path.join(INCLUDE, HEADERS[0])
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
@@ -125,7 +127,7 @@ def _read(name):
     return (protos, spellings, f.name), consts
 
 
-_READ = {name: _read(name) for name in (*HEADERS, *MESH_HEADERS)}
+_READ = {name: _read(name) for name in (*HEADERS, *MESH_HEADERS, *TRACK_HEADERS)}
 # header name -> (prototypes, spellings, path): name -> (restype, argtypes) and name -> (C return type, C parameter types), exactly
 # the functions that header declares; PROTOTYPES, C_SPELLINGS and the constants are the base header's
 ABI = {name: _READ[name][0] for name in HEADERS}
@@ -141,7 +143,10 @@ ALL_PROTOTYPES = merge_headers({name: table[0] for name, table in ABI.items()})
 MESH_ABI = {name: _READ[name][0] for name in MESH_HEADERS}
 LWS_TSDF_MESH_MAX_TRIS = _READ[MESH_HEADERS[0]][1]["LWS_TSDF_MESH_MAX_TRIS"]
 MESH_PROTOTYPES = merge_headers({name: table[0] for name, table in MESH_ABI.items()})
-merge_headers({name: table[0] for name, table in (*ABI.items(), *MESH_ABI.items())})       # a name two headers declare raises
+# lws_track and lws_track_normal: likewise
+TRACK_ABI = {name: _READ[name][0] for name in TRACK_HEADERS}
+TRACK_PROTOTYPES = merge_headers({name: table[0] for name, table in TRACK_ABI.items()})
+merge_headers({name: table[0] for name, table in (*ABI.items(), *MESH_ABI.items(), *TRACK_ABI.items())})       # a name two headers declare raises
 
 _lib = None
 
@@ -167,7 +172,7 @@ def load():
             f"{LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python -m lwsnet_amd.build`); there is no CPU fallback for the disparity path")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in (*ALL_PROTOTYPES.items(), *MESH_PROTOTYPES.items()):
+    for name, (res, args) in (*ALL_PROTOTYPES.items(), *MESH_PROTOTYPES.items(), *TRACK_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

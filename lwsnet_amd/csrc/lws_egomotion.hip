@@ -17,24 +17,16 @@
 // of their workgroups; a workgroup works on one image.  The small matrices of the update live in LDS: 0 bytes of scratch.
 #include "lwsnet_egomotion.h"
 
-#include "lws_geomkit.h"
+#include "lws_motionkit.h"
 
 namespace lws {
 
 namespace {
 
-using namespace geomkit;
-constexpr int kThreads = 256;
-constexpr int kPerThread = 4;                               // pixels of a thread in k_ego_normal
-constexpr int kTile = kThreads * kPerThread;                // pixels of a workgroup
+using namespace motionkit;
 constexpr int kSums = 29;
-constexpr int kState = 16;                                  // doubles per image: M[12], |delta| of the last step taken, steps taken, status
 constexpr int kTrace = 48;
 constexpr int kMaxLevels = 8;
-constexpr double kSeriesBelow = 0.05;
-constexpr double kMinStep2 = 0x1p-46;
-enum { kCodeFew = 1, kCodeSingular = 2, kCodeNonFinite = 4, kCodeFinalFew = 8, kCodeSmall = 16 };
-enum { kModeSums = 0, kModeStep = 1, kModeFinal = 2 };
 
 // Where the pieces of the workspace lie.  Doubles first: state [B][16], partials [B][tiles of level 0][29]; then three float
 // pyramids (reference grey, current grey, reference disparity), level l of each an array [B][H_l][W_l] at cum[l] * B floats.
@@ -71,16 +63,11 @@ __global__ __launch_bounds__(kThreads) void k_ego_grey(const uint8_t *__restrict
                                                        float *__restrict__ g_cur, double *__restrict__ state)
 {
     const int b = blockIdx.y, t = threadIdx.x;
-    if (blockIdx.x == 0 && blockIdx.z == 0 && t < kState) {
-        double v = 0.0;
-        if (t < 12) v = init ? (double)init[12 * (int64_t)b + t] : (t == 0 || t == 5 || t == 10 ? 1.0 : 0.0);
-        state[kState * (int64_t)b + t] = v;
-    }
+    if (blockIdx.x == 0 && blockIdx.z == 0 && t < kState) start_state(init, b, t, state);
     const int64_t p = (int64_t)blockIdx.x * kThreads + t;
     if (p >= npix) return;
     const uint8_t *s = (blockIdx.z ? rgb_cur : rgb_ref) + 3 * ((int64_t)b * npix + p);
-    const int sum = 77 * (int)s[0] + 150 * (int)s[1] + 29 * (int)s[2];
-    (blockIdx.z ? g_cur : g_ref)[(int64_t)b * npix + p] = (float)sum / 256.0f;
+    (blockIdx.z ? g_cur : g_ref)[(int64_t)b * npix + p] = grey_rule(s);
 }
 
 struct DownArgs {
@@ -125,13 +112,6 @@ struct NormalArgs {
     float *terms, *resid;
 };
 
-// the four taps (j0, i0) .. (j0 + 1, i0 + 1) of f blended with the weights a (across) and b (down)
-template <typename Fn>
-__device__ __forceinline__ float blend(Fn f, int j0, int i0, float a, float b)
-{
-    return blend4(f(j0, i0), f(j0, i0 + 1), f(j0 + 1, i0), f(j0 + 1, i0 + 1), a, b);
-}
-
 // grid (ceil(H * W / 1024), B): thread t takes the pixels tile * 1024 + k * 256 + t, k = 0 .. 3
 __global__ __launch_bounds__(kThreads) void k_ego_normal(NormalArgs a)
 {
@@ -139,7 +119,7 @@ __global__ __launch_bounds__(kThreads) void k_ego_normal(NormalArgs a)
     const int b = blockIdx.y, t = threadIdx.x, H = a.H, W = a.W;
     const int64_t npix = (int64_t)H * W, img = (int64_t)b * npix;
     const Cam c0 = load_cam(a.cam, b);                      // the full-resolution camera; c: this level's
-    const Cam c = {c0.fx * a.scale, c0.fy * a.scale, (c0.cx + 0.5f) * a.scale - 0.5f, (c0.cy + 0.5f) * a.scale - 0.5f, c0.fb};
+    const Cam c = level_cam(c0, a.scale);
     float Mf[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i) Mf[i] = (float)a.M[(int64_t)a.m_stride * b + i];
@@ -164,31 +144,10 @@ __global__ __launch_bounds__(kThreads) void k_ego_normal(NormalArgs a)
             const bool inside = project(c, Qx, Qy, Qz, H, W, 1, u, v);      // margin 1: the taps' central differences lie inside
             use = Qz > 0.0f && big && inside;
             if (use) {
-                const int i0 = min((int)floorf(u), W - 3), j0 = min((int)floorf(v), H - 3);      // 1 <= i0 <= W - 3, 1 <= j0 <= H - 3
-                const float fa = u - (float)i0, fbl = v - (float)j0;
-                const float Ic = blend([&](int j, int i) { return I[(int64_t)j * W + i]; }, j0, i0, fa, fbl);
-                const float gx = blend([&](int j, int i) { return 0.5f * (I[(int64_t)j * W + i + 1] - I[(int64_t)j * W + i - 1]); }, j0, i0, fa, fbl);
-                const float gy = blend([&](int j, int i) { return 0.5f * (I[(int64_t)(j + 1) * W + i] - I[(int64_t)(j - 1) * W + i]); }, j0, i0, fa, fbl);
-                const float rr = Ic - a.grey_ref[img + p];
-                const float ar = fabsf(rr);
-                const float ww = ar <= a.huber ? 1.0f : a.huber / ar;
-                const float ju = (gx * c.fx) / Qz, jv = (gy * c.fy) / Qz;
-                const float jz = -((ju * Qx + jv * Qy) / Qz);
-                const float j3 = jz * Qy - jv * Qz, j4 = ju * Qz - jz * Qx, j5 = jv * Qx - ju * Qy;
-                use = __builtin_isfinite(rr) && __builtin_isfinite(gx) && __builtin_isfinite(gy) && __builtin_isfinite(ju) &&
-                      __builtin_isfinite(jv) && __builtin_isfinite(jz) && __builtin_isfinite(j3) && __builtin_isfinite(j4) &&
-                      __builtin_isfinite(j5);
+                use = photo_term(I, H, W, c, Qx, Qy, Qz, u, v, a.grey_ref[img + p], a.huber, r, w, J);
                 if (use) {
-                    r = rr, w = ww, J[0] = ju, J[1] = jv, J[2] = jz, J[3] = j3, J[4] = j4, J[5] = j5;
                     const double dw = (double)w, dr = (double)r;
-                    int n = 0;
-#pragma unroll
-                    for (int i = 0; i < 6; ++i) {
-                        const double wj = dw * (double)J[i];
-#pragma unroll
-                        for (int j = i; j < 6; ++j) acc[n++] += wj * (double)J[j];
-                        acc[21 + i] += wj * dr;
-                    }
+                    add_normal(acc, dw, dr, J);
                     acc[27] += (dw * dr) * dr;
                     acc[28] += 1.0;
                 }
@@ -224,16 +183,11 @@ struct SolveArgs {
 __global__ __launch_bounds__(kThreads) void k_ego_solve(SolveArgs a)
 {
     __shared__ double s_w[kThreads / 64][kSums];
-    __shared__ double s_s[kSums], s_A[6][6], s_L[6][6], s_y[6], s_d[6], s_E[12], s_M[12], s_N[12];
+    __shared__ double s_s[kSums];
+    __shared__ SolveLds s_m;
     const int b = blockIdx.x, t = threadIdx.x;
     double acc[kSums];
-#pragma unroll
-    for (int k = 0; k < kSums; ++k) acc[k] = 0.0;
-    const double *part = a.partials + (int64_t)b * a.tiles * kSums;
-    for (int j = t; j < a.tiles; j += kThreads) {
-#pragma unroll
-        for (int k = 0; k < kSums; ++k) acc[k] += part[(int64_t)j * kSums + k];
-    }
+    add_partials(a.partials + (int64_t)b * a.tiles * kSums, a.tiles, acc);
     block_sum_n(acc, s_w);
     if (t < kSums) {
         const double v = block_total(s_w, t);
@@ -245,23 +199,18 @@ __global__ __launch_bounds__(kThreads) void k_ego_solve(SolveArgs a)
     if (t != 0) return;
     double *st = a.state + (int64_t)kState * b;
     const double n = s_s[28];
-    for (int i = 0; i < 12; ++i) s_M[i] = st[i];
+    for (int i = 0; i < 12; ++i) s_m.M[i] = st[i];
     if (a.mode == kModeFinal) {
         int status = (int)st[14];
         if (n < (double)a.min_pixels) status |= kCodeFinalFew;
         a.status[b] = status;
         double *info = a.info + 4 * (int64_t)b;
         info[0] = n, info[1] = n > 0.0 ? sqrt(s_s[27] / n) : 0.0, info[2] = st[12], info[3] = st[13];
-        float *po = a.pose + kPoseFloats * (int64_t)b, *pi = po + kPoseInverse;
-        for (int i = 0; i < 12; ++i) po[i] = (float)s_M[i];
-        for (int i = 0; i < 3; ++i) {                       // the inverse: R^T, 0 - R^T t (so that a zero t gives +0, not -0)
-            for (int j = 0; j < 3; ++j) pi[4 * i + j] = (float)s_M[4 * j + i];
-            pi[4 * i + 3] = (float)(0.0 - ((s_M[i] * s_M[3] + s_M[4 + i] * s_M[7]) + s_M[8 + i] * s_M[11]));
-        }
+        write_pose(s_m.M, a.pose + kPoseFloats * (int64_t)b);
         return;
     }
     int code = 0;
-    for (int i = 0; i < 6; ++i) s_d[i] = 0.0;
+    for (int i = 0; i < 6; ++i) s_m.d[i] = 0.0;
     if (n < (double)a.min_pixels) {
         code = kCodeFew;
     } else {
@@ -269,96 +218,13 @@ __global__ __launch_bounds__(kThreads) void k_ego_solve(SolveArgs a)
         for (int k = 0; k < kSums; ++k) finite = finite && __builtin_isfinite(s_s[k]);
         if (!finite) code = kCodeNonFinite;
     }
-    if (code == 0) {
-        int k = 0;
-        for (int i = 0; i < 6; ++i)
-            for (int j = i; j < 6; ++j) s_A[i][j] = s_A[j][i] = s_s[k++];
-        for (int i = 0; i < 6; ++i) s_A[i][i] = s_A[i][i] + a.damping * s_A[i][i];
-        for (int j = 0; j < 6 && code == 0; ++j) {          // A = L L^T, column by column
-            double s = 0.0;
-            for (int q = 0; q < j; ++q) s += s_L[j][q] * s_L[j][q];
-            const double p = s_A[j][j] - s;
-            if (!(p > 0.0)) {
-                code = kCodeSingular;
-                break;
-            }
-            const double root = sqrt(p);
-            s_L[j][j] = root;
-            for (int i = j + 1; i < 6; ++i) {
-                double s2 = 0.0;
-                for (int q = 0; q < j; ++q) s2 += s_L[i][q] * s_L[j][q];
-                s_L[i][j] = (s_A[i][j] - s2) / root;
-            }
-        }
-    }
-    if (code == 0) {
-        for (int i = 0; i < 6; ++i) {                       // L y = -b
-            double s = 0.0;
-            for (int q = 0; q < i; ++q) s += s_L[i][q] * s_y[q];
-            s_y[i] = (-s_s[21 + i] - s) / s_L[i][i];
-        }
-        for (int i = 5; i >= 0; --i) {                      // L^T delta = y
-            double s = 0.0;
-            for (int q = i + 1; q < 6; ++q) s += s_L[q][i] * s_d[q];
-            s_d[i] = (s_y[i] - s) / s_L[i][i];
-        }
-        const double dd = ((((s_d[0] * s_d[0] + s_d[1] * s_d[1]) + s_d[2] * s_d[2]) + s_d[3] * s_d[3]) + s_d[4] * s_d[4]) + s_d[5] * s_d[5];
-        if (!__builtin_isfinite(dd)) {
-            code = kCodeNonFinite;
-            for (int i = 0; i < 6; ++i) s_d[i] = 0.0;
-        } else if (dd < kMinStep2) {
-            code = kCodeSmall;
-        } else {
-            const double ox = s_d[3], oy = s_d[4], oz = s_d[5];
-            const double t2 = (ox * ox + oy * oy) + oz * oz, th = sqrt(t2);
-            double A, Bc, C;
-            if (th < kSeriesBelow) {
-                A = 1.0 - t2 * (1.0 / 6.0 - t2 * (1.0 / 120.0 - t2 * (1.0 / 5040.0)));
-                Bc = 0.5 - t2 * (1.0 / 24.0 - t2 * (1.0 / 720.0 - t2 * (1.0 / 40320.0)));
-                C = 1.0 / 6.0 - t2 * (1.0 / 120.0 - t2 * (1.0 / 5040.0 - t2 * (1.0 / 362880.0)));
-            } else {
-                const double sn = sin(th), cs = cos(th);
-                A = sn / th, Bc = (1.0 - cs) / t2, C = (th - sn) / (t2 * th);
-            }
-            // K = [om]x and K^2 = om om^T - t2 I, written out; rows of R = I + A K + B K^2 and V = I + B K + C K^2
-            const double K[9] = {0.0, -oz, oy, oz, 0.0, -ox, -oy, ox, 0.0};
-            const double K2[9] = {ox * ox - t2, ox * oy, ox * oz, ox * oy, oy * oy - t2, oy * oz, ox * oz, oy * oz, oz * oz - t2};
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                double tv = 0.0;
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    const double id = i == j ? 1.0 : 0.0;
-                    s_E[4 * i + j] = (id + A * K[3 * i + j]) + Bc * K2[3 * i + j];
-                    tv += ((id + Bc * K[3 * i + j]) + C * K2[3 * i + j]) * s_d[j];
-                }
-                s_E[4 * i + 3] = tv;
-            }
-            bool finite = true;
-            for (int i = 0; i < 3; ++i) {                   // N = E . M
-                for (int j = 0; j < 4; ++j) {
-                    double s = (s_E[4 * i] * s_M[j] + s_E[4 * i + 1] * s_M[4 + j]) + s_E[4 * i + 2] * s_M[8 + j];
-                    if (j == 3) s += s_E[4 * i + 3];
-                    s_N[4 * i + j] = s;
-                    finite = finite && __builtin_isfinite(s);
-                }
-            }
-            if (!finite) {
-                code = kCodeNonFinite;
-                for (int i = 0; i < 6; ++i) s_d[i] = 0.0;
-            } else {
-                for (int i = 0; i < 12; ++i) st[i] = s_N[i];
-                st[12] = sqrt(dd);
-                st[13] = st[13] + 1.0;
-            }
-        }
-    }
+    if (code == 0) code = gauss_newton_step(s_s, a.damping, s_m, st);
     st[14] = (double)((int)st[14] | code);
     if (a.trace) {
         double *tr = a.trace + a.trace_stride * b;
-        for (int i = 0; i < 12; ++i) tr[i] = s_M[i];
+        for (int i = 0; i < 12; ++i) tr[i] = s_m.M[i];
         for (int k = 0; k < kSums; ++k) tr[12 + k] = s_s[k];
-        for (int i = 0; i < 6; ++i) tr[41 + i] = s_d[i];
+        for (int i = 0; i < 6; ++i) tr[41 + i] = s_m.d[i];
         tr[47] = (double)code;
     }
 }

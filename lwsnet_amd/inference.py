@@ -135,6 +135,13 @@ volume ray-cast into the frame's own pose and coloured as the stage maps: the de
 `--save_tsdf_mesh PATH` writes the same vertices, in the same order, with the marching-cubes triangles between them
 (lws_tsdf_mesh, include/lwsnet_tsdf_mesh.h) and logs vertices and faces.  A volume that does not fit the device's free memory is an error before the first frame.  What leaves the volume is not mapped; movers
 smear; the poses are taken as given.
+
+`--tsdf_track [--track_iters N] [--track_lambda L] [--track_gate G] [--save_track]`: needs `--tsdf` and `--egomotion`, refused with
+`--poses`.  Each frame's ego-motion estimate is refined against the volume (lwsnet_amd.tracking.ModelTracker, lws_track,
+include/lwsnet_track.h): the volume is ray-cast at the previous frame's tracked pose and the frame is aligned with that view by
+one joint photometric + point-to-plane cost.  While it is on, the filter, the volume and `--save_poses` get the tracked poses.  One
+log line per frame gives the terms of both kinds, their rms and the status.  `--save_track` writes `<stem>_track.png`, the
+point-to-plane residual in standard deviations (white 0, red / blue +-4, black: no model there).
 """
 import argparse
 import contextlib
@@ -157,7 +164,7 @@ from .outputs import (STIXEL_COLOUR_DEPTH, bev_to_u8, conf_to_u8, ground_to_rgb,
 from .postprocess import (add_lr_arguments, add_occ_arguments, add_speckle_arguments, add_wmedian_arguments, check_lr_arguments,
                           check_occ_arguments, check_speckle_arguments, check_wmedian_arguments)
 from .sequence import (TSDF_DEFAULTS, TSDF_MESH_DEFAULTS, check_egomotion_arguments, check_temporal_arguments,  # noqa: F401
-                       check_tsdf_arguments, check_tsdf_mesh_arguments, list_pairs as _list_pairs, temporal_sigma, tsdf_grid)
+                       check_tsdf_arguments, check_tsdf_mesh_arguments, check_track_arguments, list_pairs as _list_pairs, temporal_sigma, tsdf_grid)
 
 
 def build_parser():
@@ -585,7 +592,7 @@ def inference(model, left_imgs, right_imgs, args, log, poses=None):
                 log.info("Weighted median (radius {}, sigma {:g}, fill {}): stage {} changed = {}, filled = {}".format(
                     opts.wmedian, opts.wmedian_sigma, opts.wmedian_fill, stage + 1, changed, refilled))
         conf = chain_model.last if conf_on else None
-        step = types.SimpleNamespace(index=index, frame=frame, res=res, conf=conf, ego=None, fused=None, view=None)   # (lwsnet_amd/sequence.py)
+        step = types.SimpleNamespace(index=index, frame=frame, res=res, conf=conf, ego=None, track=None, fused=None, view=None)   # (lwsnet_amd/sequence.py)
         source.frame(index)
         for st in stages:                                   # ego-motion on the chain's own map and codes, the filter, the volume on what it left
             st.step(step, log)
@@ -670,6 +677,7 @@ def main(argv=None):
     poses = check_temporal_arguments(parser, args)
     alone = check_tsdf_arguments(parser, args)              # the file of --poses comes from the one of the two checks that read it
     check_tsdf_mesh_arguments(parser, args)
+    check_track_arguments(parser, args)
     log = start_logging("lwsnet_amd.inference", args)
     model = load_model(args, log)
     if getattr(args, "split_bf16", False):

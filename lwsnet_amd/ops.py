@@ -974,6 +974,86 @@ def egomotion(rgb_ref, disp_ref, rgb_cur, cameras, mask=None, init=None, levels=
     return EgoResult(pose, status, info, tr, rs)
 
 
+TrackResult = namedtuple("TrackResult", ["pose", "status", "info", "trace", "resid", "sums", "terms"])
+TrackResult.__doc__ = """What track and track_normal return, all on the device.  track: pose float32 [B,2,12] as egomotion's; status int32
+[B], egomotion's bits (8: do not trust the pose) and 32: the final linearisation had fewer than min_pixels geometric terms, the model
+did not constrain the pose; info float64 [B,6]: n_p, photometric rms (grey levels), n_g, geometric rms (standard deviations), |delta| of
+the last step taken, steps taken; trace float64 [B,iters,51] and resid float32 [B,2,H,W] (None unless asked for); sums, terms None.
+track_normal: sums float64 [B,32] and terms float32 [B,H,W,16] (None unless asked for); the rest None."""
+TRACK_UNTRUSTED, TRACK_NO_MODEL = 8, 32
+
+
+def track_args(min_disp, huber_p, sigma_p, huber_g, gate_g, sigma0, sigma_min, lambda_g):
+    """The validated scalars of track_normal, in the order of the C call."""
+    huber_g = _finite_pos("huber_g", huber_g)
+    if not (gate_g >= huber_g):
+        raise ValueError(f"gate_g must be >= huber_g (inf allowed), got {gate_g} < {huber_g}")
+    return (_finite_pos("min_disp", min_disp), _finite_pos("huber_p", huber_p), _finite_pos("sigma_p", sigma_p), huber_g, float(gate_g),
+            _finite_nonneg("sigma0", sigma0), _finite_pos("sigma_min", sigma_min), _finite_nonneg("lambda_g", lambda_g))
+
+
+def _track_maps(who, disp_ref, normals_ref, mask_ref, disp_cur, sigma_cur, mask_cur, cameras, min_disp):
+    """The model maps and the current maps of track / track_normal, checked: (disp_ref, normals, mask_ref, disp_cur, sigma, mask_cur, cam)."""
+    if cameras is None:
+        raise ValueError(f"{who} needs cameras")
+    d, mask_ref, cam = _geometry_inputs(disp_ref, mask_ref, cameras, min_disp, float("inf"))
+    B, _, H, W = d.shape
+    _int_indexed(H, W, "disp_ref", who, sides=True)
+    dc = _tensor_of(disp_cur, "disp_cur", torch.float32, d.shape, d.device)
+    if normals_ref is not None:
+        normals_ref = _tensor_of(normals_ref, "normals_ref", torch.float32, (B, 3, H, W), d.device, " (what tsdf_raycast returns)")
+    if sigma_cur is not None:
+        sigma_cur = _tensor_of(sigma_cur, "sigma_cur", torch.float32, d.shape, d.device)
+    if mask_cur is not None:
+        mask_cur = _tensor_of(mask_cur, "mask_cur", torch.uint8, d.shape, d.device, " (the lws_lr_check code map)")
+    return d, normals_ref, mask_ref, dc, sigma_cur, mask_cur, cam
+
+
+def track_normal(grey_ref, disp_ref, grey_cur, disp_cur, cameras, M, normals_ref=None, mask_ref=None, sigma_cur=None, mask_cur=None,
+                 min_disp=1.0, huber_p=10.0, sigma_p=4.0, huber_g=1.5, gate_g=4.0, sigma0=0.5, sigma_min=0.05, lambda_g=1.0, terms=False):
+    """One linearisation of the joint photometric + point-to-plane cost (include/lwsnet_track.h, lws_track_normal).  grey_ref,
+    grey_cur, disp_ref (the model's view), disp_cur float32 [B,1,H,W]; normals_ref float32 [B,3,H,W] or None; the masks uint8 or
+    None; sigma_cur float32 [B,1,H,W] or None; M [12] or [B,12] (float64).  Returns a TrackResult with sums and terms."""
+    scalars = track_args(min_disp, huber_p, sigma_p, huber_g, gate_g, sigma0, sigma_min, lambda_g)
+    d, nr, mr, dc, sc, mc, cam = _track_maps("track_normal", disp_ref, normals_ref, mask_ref, disp_cur, sigma_cur, mask_cur, cameras, scalars[0])
+    B, _, H, W = d.shape
+    g0, g1 = (_tensor_of(g, name, torch.float32, d.shape, d.device) for g, name in ((grey_ref, "grey_ref"), (grey_cur, "grey_cur")))
+    m_dev = torch.from_numpy(_motion_rows(M, B, "M", "float64")).to(d.device)
+    work = _workspace("lws_track_workspace", d.device, B, H, W)
+    sums = torch.empty((B, 32), device=d.device, dtype=torch.float64)
+    tm = torch.empty((B, H, W, 16), device=d.device, dtype=torch.float32) if terms else None
+    _call("lws_track_normal", d.device, g0, d, nr, mr, g1, dc, sc, mc, cam, m_dev, B, H, W, *scalars, work, sums, tm)
+    return TrackResult(None, None, None, None, None, sums, tm)
+
+
+def track(rgb_ref, disp_ref, rgb_cur, disp_cur, cameras, normals_ref=None, mask_ref=None, sigma_cur=None, mask_cur=None, init=None, iters=6,
+          min_disp=1.0, huber_p=10.0, sigma_p=4.0, huber_g=1.5, gate_g=4.0, sigma0=0.5, sigma_min=0.05, lambda_g=1.0, damping=0.0,
+          min_pixels=256, trace=False, resid=False):
+    """The motion of the camera from a reference view of the TSDF model to the current frame (include/lwsnet_track.h, lws_track):
+    `iters` Gauss-Newton steps on the joint photometric + point-to-plane cost at full resolution.  rgb_ref, rgb_cur uint8 [B,H,W,3];
+    disp_ref, normals_ref, mask_ref: the model's view in the reference camera (what tsdf_raycast returns); disp_cur, sigma_cur,
+    mask_cur: the current frame's own maps; init as egomotion takes it (the frame-to-frame estimate).  The defaults were chosen on a
+    synthetic scene only; they have not met real data.  Returns a TrackResult; nothing is read back."""
+    scalars = track_args(min_disp, huber_p, sigma_p, huber_g, gate_g, sigma0, sigma_min, lambda_g)
+    iters = _int_in("iters", iters, 1, 64)
+    damping = _finite_nonneg("damping", damping)
+    min_pixels = _int_in("min_pixels", min_pixels, 1, (1 << 31) - 1)
+    d, nr, mr, dc, sc, mc, cam = _track_maps("track", disp_ref, normals_ref, mask_ref, disp_cur, sigma_cur, mask_cur, cameras, scalars[0])
+    B, _, H, W = d.shape
+    r0, r1 = (_tensor_of(r, name, torch.uint8, (B, H, W, 3), d.device) for r, name in ((rgb_ref, "rgb_ref"), (rgb_cur, "rgb_cur")))
+    if init is not None:
+        init = _device_rows(init, "init", (B, 12), d.device, lambda: _motion_rows(init, B, "init", "float32"))
+    work = _workspace("lws_track_workspace", d.device, B, H, W)
+    pose = torch.empty((B, 2, 12), device=d.device, dtype=torch.float32)
+    status = torch.empty((B,), device=d.device, dtype=torch.int32)
+    info = torch.empty((B, 6), device=d.device, dtype=torch.float64)
+    tr = torch.empty((B, iters, 51), device=d.device, dtype=torch.float64) if trace else None
+    rs = torch.empty((B, 2, H, W), device=d.device, dtype=torch.float32) if resid else None
+    _call("lws_track", d.device, r0, d, nr, mr, r1, dc, sc, mc, cam, init, B, H, W, iters, *scalars, damping, min_pixels, work, pose, status, info,
+          tr, rs)
+    return TrackResult(pose, status, info, tr, rs, None, None)
+
+
 TSDF_WEIGHTS = {"unit": 0, "sigma": 1}                      # wmode of lws_tsdf_integrate
 
 

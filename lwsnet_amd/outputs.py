@@ -399,6 +399,30 @@ def save_ego(stem, frame, log, ego):
     return [stem + "_ego.png"]
 
 
+TRACK_FULL_SCALE = 4.0                                      # standard deviations at which <stem>_track.png saturates
+
+
+def track_to_rgb(resid_g):
+    """[H,W] point-to-plane residual of lws_track in standard deviations -> the uint8 [H,W,3] of <stem>_track.png: black where the
+    pixel carried no geometric term (0), else white at a residual near 0 running to red at +TRACK_FULL_SCALE (the model lies behind
+    the frame's surface along the normal) and to blue at -TRACK_FULL_SCALE."""
+    r = np.asarray(resid_g, np.float64)
+    t = np.clip(np.abs(r) / TRACK_FULL_SCALE, 0.0, 1.0)
+    fade = np.rint(255.0 * (1.0 - t))
+    full = np.full(r.shape, 255.0)
+    rgb = np.stack([np.where(r > 0, full, fade), fade, np.where(r < 0, full, fade)], -1)
+    return np.where((r != 0)[..., None], rgb, 0.0).astype(np.uint8)
+
+
+def save_track(stem, frame, log, track):
+    """--save_track: <stem>_track.png, the point-to-plane residual at the final pose of the frame's ops.TrackResult (track_to_rgb);
+    all black for a first frame (track None), which has no model to align with."""
+    h, w = _rgb_on_host(frame.left).shape[:2]
+    io.save_png(stem + "_track.png", np.zeros((h, w, 3), np.uint8) if track is None else track_to_rgb(track.resid[0, 1].cpu().numpy()))
+    log.info("Save tracking residual = {}_track.png".format(stem))
+    return [stem + "_track.png"]
+
+
 def save_tsdf(stem, log, view):
     """--save_tsdf: <stem>_tsdf.png, the volume ray-cast into the frame's own pose (an ops.TsdfView), coloured as the stage maps."""
     io.save_png(stem + "_tsdf.png", io.disparity_to_color(view.disp[0, 0].cpu().numpy()))

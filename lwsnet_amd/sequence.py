@@ -1,16 +1,17 @@
-"""The stages of the inference CLI that treat the frames of directory mode as a sequence -- `--egomotion`, `--temporal`, `--tsdf`
-(lwsnet_amd/inference.py's docstring describes the flags) -- and the one source of their poses.
+"""The stages of the inference CLI that treat the frames of directory mode as a sequence -- `--egomotion`, `--tsdf_track`,
+`--temporal`, `--tsdf` (lwsnet_amd/inference.py's docstring describes the flags) -- and the one source of their poses.
 
 A stage is an object with four methods, and the run's stages are a tuple that inference.inference() walks with a `for`, in the
-order ego-motion (on the chain's own map), filter, volume (on what the filter left): step(s, log) takes the record of a processed
+order ego-motion (on the chain's own map), model tracking (the estimate refined against the volume), filter, volume (on what the
+filter left): step(s, log) takes the record of a processed
 pair -- index, frame, res (the ChainResult), conf, and what the stages of this frame made so far: ego (the ops.EgoResult, None on a
-first frame), fused (the ops.TemporalResult; res then holds the fused map in the chain's place), view (the ops.TsdfView of
+first frame), track (the ops.TrackResult of --tsdf_track, None on a first frame), fused (the ops.TemporalResult; res then holds the fused map in the chain's place), view (the ops.TsdfView of
 --save_tsdf) -- and leaves what it made in it; skip(path, log) hears of a pair that was skipped; save(s, stem, log) writes the stage's own
 per-frame file beside the colour file and finish(log) the file at the end of the run, both returning the paths.  A new stage is a
 class like these, its flags' add_* / *_DEFAULTS / check_* beside it, its name in begin(), and its check called by inference.main().
 
 PoseSource is the only code that maps a pair's index to a pose and the only one that knows of skipped pairs.  It is backed by the
-file of --poses (read once, by the argument check) or by the run's Odometry, and answers what the stages ask: the camera-to-world
+file of --poses (read once, by the argument check), by the run's Odometry or, with --tsdf_track, by the run's ModelTracker, and answers what the stages ask: the camera-to-world
 pose of the current pair, the motion from the pair processed before it, the lines of --save_poses.  Each answer is computed as it
 was before there was one source -- geometry.relative_pose for the file, the estimate's own block, the Odometry's accumulated
 float64 poses -- because the files written are compared bit for bit.
@@ -96,6 +97,13 @@ def add_sequence_arguments(p):
     p.add_argument("--save_tsdf_mesh", type=str, default=S, metavar="PATH",
                    help="tsdf: at the end, write the volume's zero level set as a binary PLY of the same vertices and the triangles between them")
     p.add_argument("--save_tsdf", action="store_true", default=S, help="tsdf: write <stem>_tsdf.png, the volume ray-cast into the frame's own pose, coloured as the stage maps")
+    p.add_argument("--tsdf_track", action="store_true", default=S,
+                   help="refine each frame's --egomotion estimate against the --tsdf volume (joint photometric + point-to-plane cost); the "
+                        "filter, the volume and --save_poses then get the tracked poses (needs --tsdf and --egomotion, not --poses)")
+    p.add_argument("--track_iters", type=int, default=S, metavar="N", help="tsdf_track: Gauss-Newton steps, 1 .. 64 (default 6)")
+    p.add_argument("--track_lambda", type=float, default=S, metavar="L", help="tsdf_track: the weight of the point-to-plane term, 0 switches it off (default 1)")
+    p.add_argument("--track_gate", type=float, default=S, metavar="G", help="tsdf_track: the gate of the point-to-plane residual in standard deviations (default 4)")
+    p.add_argument("--save_track", action="store_true", default=S, help="tsdf_track: write <stem>_track.png, the point-to-plane residual at the final pose in standard deviations, coloured")
 
 
 TEMPORAL_DEFAULTS = dict(temporal=False, poses=None, temporal_gate=3.0, temporal_q=0.0, temporal_sigma="0.5", temporal_hold=False, save_temporal=False)
@@ -200,19 +208,48 @@ def check_tsdf_mesh_arguments(p, args):
         p.error("--save_tsdf_mesh needs --tsdf")
 
 
+TRACK_DEFAULTS = dict(tsdf_track=False, track_iters=6, track_lambda=1.0, track_gate=4.0, save_track=False)
+TRACK_HUBER_G = 1.5                                         # the Huber threshold of the point-to-plane term: the gate may not lie below it
+
+
+def check_track_arguments(p, args):
+    """--tsdf_track, behind check_tsdf_arguments: rejects what the tracker does not support, before any model or GPU work; sets the defaults."""
+    given = [f for f in TRACK_DEFAULTS if f != "tsdf_track" and hasattr(args, f)]      # (SUPPRESS: there only if given)
+    post.set_defaults(args, **TRACK_DEFAULTS)
+    if not args.tsdf_track:
+        if given:
+            p.error("--track_iters, --track_lambda, --track_gate and --save_track need --tsdf_track")
+        return
+    if getattr(args, "left_img", None):
+        p.error("--tsdf_track follows a sequence: use directory mode (--img_path), not --left_img")
+    if getattr(args, "poses", None) is not None:
+        p.error("--tsdf_track estimates the poses: do not give --poses as well")
+    if not getattr(args, "tsdf", False):
+        p.error("--tsdf_track needs --tsdf, the volume it tracks against")
+    if not getattr(args, "egomotion", False):
+        p.error("--tsdf_track needs --egomotion, the frame-to-frame estimate it starts from")
+    post.in_range(p.error, "--track_iters", args.track_iters, 1, 64)
+    post.in_range(p.error, "--track_lambda", args.track_lambda)
+    post.in_range(p.error, "--track_gate", args.track_gate, TRACK_HUBER_G, float("inf"))
+
+
 class PoseSource:
     """The poses of a run's pairs.  poses: the float64 [N,3,4] of --poses, line i for pair i; None: they are estimated, and `odometry`
-    is the run's egomotion.Odometry from the ego-motion stage's first frame on, its k-th pose that of the k-th pair processed.
+    is the run's egomotion.Odometry from the ego-motion stage's first frame on, its k-th pose that of the k-th pair processed; with
+    --tsdf_track, `tracker` is the run's tracking.ModelTracker from the tracking stage's first frame on, and answers in its place.
     frame(index) announces each processed pair, in order; one never announced was skipped, and the next motion spans the gap."""
 
     def __init__(self, pairs, poses=None):
         self.pairs, self.poses, self.odometry, self.seen = pairs, poses, None, []      # seen: the indices of the pairs processed so far
+        self.tracker = None
 
     def frame(self, index):
         self.seen.append(index)
 
     def world(self):
         """The camera-to-world pose [3,4] of the current pair."""
+        if self.tracker is not None:
+            return self.tracker.poses()[-1]
         return self.poses[self.seen[-1]] if self.poses is not None else self.odometry.poses()[-1]
 
     def relative(self, s, log):
@@ -221,6 +258,12 @@ class PoseSource:
         if self.poses is not None:
             from .geometry import relative_pose
             return None if len(self.seen) < 2 else relative_pose(self.poses[self.seen[-2]], self.poses[self.seen[-1]])
+        if self.tracker is not None:
+            if s.track is not None and int(s.track.status[0]) & ops.TRACK_UNTRUSTED:
+                log.warning("Temporal: the tracked pose of %s is not to be trusted (status %d): the filter starts anew", s.frame.path,
+                            int(s.track.status[0]))
+                return None
+            return None if s.track is None else s.track.pose
         if s.ego is not None and int(s.ego.status[0]) & ops.EGO_UNTRUSTED:
             log.warning("Temporal: the ego-motion estimate of %s is not to be trusted (status %d): the filter starts anew", s.frame.path,
                         int(s.ego.status[0]))
@@ -230,8 +273,9 @@ class PoseSource:
     def lines(self):
         """The float64 [pairs,3,4] of --save_poses: a skipped pair repeats the last pair processed before it, else the identity."""
         identity = np.hstack([np.eye(3), np.zeros((3, 1))])
-        poses = self.odometry.poses() if self.odometry is not None else np.zeros((0, 3, 4))
-        at = np.searchsorted(self.seen, np.arange(self.pairs), side="right") - 1       # per pair: its pose among the Odometry's, -1 before the first
+        estimator = self.tracker if self.tracker is not None else self.odometry
+        poses = estimator.poses() if estimator is not None else np.zeros((0, 3, 4))
+        at = np.searchsorted(self.seen, np.arange(self.pairs), side="right") - 1       # per pair: its pose among the estimator's, -1 before the first
         return np.stack([poses[k] if k >= 0 else identity for k in at]) if self.pairs else poses
 
 
@@ -289,6 +333,38 @@ class _Odometry(_Stage):
             write_kitti_poses(path, self.source.lines())
             log.info("Save poses = {}".format(path))
         return [] if path is None else [path]
+
+
+class _Tracker(_Stage):
+    """--tsdf_track: step() refines the frame's ego-motion estimate against the volume stage's TsdfVolume with the source's
+    ModelTracker (made on the first frame) and leaves the ops.TrackResult in s.track; it reads back, once, for the log.  The volume
+    holds the frames before this one, integrated at their tracked poses: the volume stage runs after this one."""
+    volume = None                                           # the volume stage's TsdfVolume: begin() hands it over
+
+    def skip(self, path, log):
+        log.warning("Tracking: %s was skipped; the next frame is aligned with the volume's view of the pair before it", path)
+
+    def step(self, s, log):
+        import torch
+        from . import ops
+        from .tracking import ModelTracker
+        a, src = self.args, self.source
+        disp, keep = _stage4(s.res)
+        if src.tracker is None:
+            src.tracker = ModelTracker(self.volume, s.frame.cam, iters=a.track_iters, lambda_g=a.track_lambda, gate_g=a.track_gate, huber_g=TRACK_HUBER_G,
+                                       min_disp=a.min_disp, z_near=max(a.tsdf_voxel, 0.5))
+        init = None
+        if s.ego is not None and not int(s.ego.status[0]) & ops.EGO_UNTRUSTED:
+            init = s.ego.pose[:, 0].contiguous()
+        with torch.cuda.device(disp.device):
+            s.track = src.tracker.step(out.rgb_on_device(s.frame.left, disp.device), disp, keep, init=init, resid=a.save_track)
+        if s.track is not None:
+            n_p, rms_p, n_g, rms_g = s.track.info[0, :4].cpu().tolist()
+            log.info("Tracking: photometric pixels = {}, rms = {:.3f}, model pixels = {}, rms = {:.3f} sigma, status = {}".format(
+                int(n_p), rms_p, int(n_g), rms_g, int(src.tracker.status[-1][0])))
+
+    def save(self, s, stem, log):
+        return out.save_track(stem, s.frame, log, s.track) if self.args.save_track else []
 
 
 class _Sequence(_Stage):
@@ -366,10 +442,14 @@ class _Volume(_Stage):
 def begin(args, pairs, device, log, poses=None):
     """(the PoseSource, the stages that are on, in the order they run) of a run over `pairs` pairs.  poses: what the checks read;
     a namespace that skipped the checks gets the flags' defaults and its --poses file read here."""
-    post.set_defaults(args, **TEMPORAL_DEFAULTS, **EGO_DEFAULTS, **TSDF_DEFAULTS, **TSDF_MESH_DEFAULTS)
+    post.set_defaults(args, **TEMPORAL_DEFAULTS, **EGO_DEFAULTS, **TSDF_DEFAULTS, **TSDF_MESH_DEFAULTS, **TRACK_DEFAULTS)
     if poses is None and args.poses is not None and not args.egomotion:
         from .geometry import read_kitti_poses
         poses = read_kitti_poses(args.poses)
     source = PoseSource(pairs, None if args.egomotion else poses)
-    on = ((args.egomotion, _Odometry, ()), (args.temporal, _Sequence, ()), (args.tsdf, _Volume, (device, log)))
-    return source, tuple(cls(args, source, *more) for flag, cls, more in on if flag)
+    on = ((args.egomotion, _Odometry, ()), (args.tsdf_track, _Tracker, ()), (args.temporal, _Sequence, ()), (args.tsdf, _Volume, (device, log)))
+    stages = tuple(cls(args, source, *more) for flag, cls, more in on if flag)
+    for st in stages:
+        if isinstance(st, _Tracker):
+            st.volume = next(v.volume for v in stages if isinstance(v, _Volume))
+    return source, stages
