@@ -356,12 +356,7 @@ def test_forward_repeatable_batch8(dev, model):
             assert torch.equal(one[s], ref[s][3:4])
 
 
-OPTION_PLANS = [{"fuse_first": 0}, {"fuse_first": 1}, {"fuse_first": 2}, {"defer_upsample": 0}, {"ref_chunk_mb": 0}, {"ref_chunk_mb": 1},
-                {"side_streams": 0}, {"side_streams": 0, "fuse_first": 0}, {"warp_form": 0}, {"warp_form": 0, "defer_upsample": 0},
-                {"fuse_last1": 0}, {"fuse_last1": 1, "warp_form": 0}, {"fuse_ref_last": 0}, {"fuse_ref_last": 1},
-                {"fork2_after": 0}, {"fork2_after": 2}, {"fork2_after": 1, "side_streams": 0}, {"ref_pipe": 1, "ref_chunk_mb": 1},
-                {"ref_pipe": 0, "ref_chunk_mb": 1},
-                {"fuse_first": 0, "defer_upsample": 0, "fuse_last1": 0, "fuse_ref_last": 0, "fork2_after": 0, "warp_form": 0}]
+from plan_matrix import OPTION_PLANS          # (the same 20 plans, crossed with ragged shapes in tests/test_gpu_plan_matrix.py)
 
 
 @pytest.mark.parametrize("plan", OPTION_PLANS, ids=lambda p: ",".join(f"{k}={v}" for k, v in p.items()))
