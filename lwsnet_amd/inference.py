@@ -136,6 +136,17 @@ volume ray-cast into the frame's own pose and coloured as the stage maps: the de
 (lws_tsdf_mesh, include/lwsnet_tsdf_mesh.h) and logs vertices and faces.  A volume that does not fit the device's free memory is an error before the first frame.  What leaves the volume is not mapped; movers
 smear; the poses are taken as given.
 
+`--tsdf_follow [N]`: needs `--tsdf`.  The volume follows the camera (lwsnet_amd.tsdf.TsdfVolume.follow, lws_tsdf_window,
+include/lwsnet_tsdf_window.h): before a frame is integrated, the centre of `--tsdf_extent`, carried along with the camera, is compared
+with the volume's centre, and once they are N voxels apart on some axis (default 16; at least 1 and below the smallest dimension
+minus 2) the volume moves by the rounded difference, in whole voxels.  What the move loses is extracted first -- as a mesh with
+`--save_tsdf_mesh`, else as points with `--save_tsdf_ply`, else it is dropped -- and kept on the host; one log line per move gives
+the shift, the voxels kept and the vertices and faces spilled.  At the end the volume itself is the last chunk: `--save_tsdf_ply`
+gets every chunk's vertices and `--save_tsdf_mesh` the same vertices in the same order with the faces.  Limits: a vertex on the
+seam of two chunks is in both (the total is logged); a vertex normal at a chunk's border is zero, as at any volume border; what
+re-enters the volume after leaving is mapped afresh, so a loop gives two surfaces; after a sharp turn the volume swings with the
+view, and what lies behind the camera is spilled.  Without the flag no output changes by a byte.
+
 `--tsdf_track [--track_iters N] [--track_lambda L] [--track_gate G] [--save_track]`: needs `--tsdf` and `--egomotion`, refused with
 `--poses`.  Each frame's ego-motion estimate is refined against the volume (lwsnet_amd.tracking.ModelTracker, lws_track,
 include/lwsnet_track.h): the volume is ray-cast at the previous frame's tracked pose and the frame is aligned with that view by
@@ -163,8 +174,8 @@ from .outputs import (STIXEL_COLOUR_DEPTH, bev_to_u8, conf_to_u8, ground_to_rgb,
                       sigma_to_u8, stixels_to_csv, stixels_to_rgb, geometry_requested as _geometry_requested)      # these stay this module's names
 from .postprocess import (add_lr_arguments, add_occ_arguments, add_speckle_arguments, add_wmedian_arguments, check_lr_arguments,
                           check_occ_arguments, check_speckle_arguments, check_wmedian_arguments)
-from .sequence import (TSDF_DEFAULTS, TSDF_MESH_DEFAULTS, check_egomotion_arguments, check_temporal_arguments,  # noqa: F401
-                       check_tsdf_arguments, check_tsdf_mesh_arguments, check_track_arguments, list_pairs as _list_pairs, temporal_sigma, tsdf_grid)
+from .sequence import (TSDF_DEFAULTS, TSDF_FOLLOW_DEFAULTS, TSDF_MESH_DEFAULTS, check_egomotion_arguments, check_temporal_arguments,  # noqa: F401
+                       check_tsdf_arguments, check_tsdf_follow_arguments, check_tsdf_mesh_arguments, check_track_arguments, list_pairs as _list_pairs, temporal_sigma, tsdf_grid)
 
 
 def build_parser():
@@ -677,6 +688,7 @@ def main(argv=None):
     poses = check_temporal_arguments(parser, args)
     alone = check_tsdf_arguments(parser, args)              # the file of --poses comes from the one of the two checks that read it
     check_tsdf_mesh_arguments(parser, args)
+    check_tsdf_follow_arguments(parser, args)
     check_track_arguments(parser, args)
     log = start_logging("lwsnet_amd.inference", args)
     model = load_model(args, log)

@@ -1244,6 +1244,50 @@ def tsdf_mesh(T, Wt, origin, voxel, max_points, max_faces, C=None, w_min=0.0, wi
     return TsdfMesh(points, vn, faces, counts)
 
 
+TsdfWindow = namedtuple("TsdfWindow", ["T", "Wt", "C", "counts"])
+TsdfWindow.__doc__ = """What tsdf_window returns: the second volume T, Wt float32 [Dz,Dy,Dx] and C uint8 [Dz,Dy,Dx,4] (None without colour), every
+element written; counts, an int64 [2] device tensor {live, not live} voxels (None unless asked for)."""
+TSDF_MAX_SHIFT = 4096                                       # |offset| per axis of lws_tsdf_window
+
+
+def tsdf_window_args(dims, offset, out_dims=None):
+    """The validated (Gx, Gy, Gz, sx, sy, sz, Dx, Dy, Dz) of tsdf_window: dims and out_dims (default: dims) each in 2 .. 4096 with a
+    product below 2^31, offset three integers in -4096 .. 4096."""
+    def volume(name, d):
+        if len(d) != 3:
+            raise ValueError(f"{name} must be (Gx, Gy, Gz), got {tuple(d)}")
+        g = [_int_in(f"{name}[{i}]", v, 2, 4096) for i, v in enumerate(d)]
+        if g[0] * g[1] * g[2] >= 1 << 31:
+            raise ValueError(f"{name} {tuple(g)}: a volume holds fewer than 2^31 voxels")
+        return g
+    if len(offset) != 3:
+        raise ValueError(f"offset must be (sx, sy, sz), got {tuple(offset)}")
+    g = volume("dims", dims)
+    s = [_int_in(f"offset[{i}]", v, -TSDF_MAX_SHIFT, TSDF_MAX_SHIFT) for i, v in enumerate(offset)]
+    return (*g, *s, *(g if out_dims is None else volume("out_dims", out_dims)))
+
+
+def tsdf_window(T, Wt, offset, dims=None, C=None, out=None, counts=True):
+    """A TSDF volume seen through an integer offset, written to a second volume (include/lwsnet_tsdf_window.h, lws_tsdf_window):
+    voxel (ix, iy, iz) of the result is voxel (ix, iy, iz) + offset of T, Wt, C where that lies inside them and is observed, and
+    cleared (T = Wt = 0, C = 0) elsewhere.  dims = (Dx, Dy, Dz): the result's, default the source's.  out: (T2, Wt2, C2) to write into
+    (C2 None iff C is), which must not share memory with the source; default: new tensors.  Returns a TsdfWindow."""
+    a = tsdf_window_args(T.shape[::-1] if isinstance(T, torch.Tensor) and T.dim() == 3 else (), offset, dims)
+    dev = _tsdf_volume(T, Wt, C, a[:3])
+    shape = (a[8], a[7], a[6])
+    if out is None:
+        out = (torch.empty(shape, device=dev, dtype=torch.float32), torch.empty(shape, device=dev, dtype=torch.float32),
+               None if C is None else torch.empty((*shape, 4), device=dev, dtype=torch.uint8))
+    if len(out) != 3 or (out[2] is None) != (C is None):
+        raise ValueError("out must be (T2, Wt2, C2), C2 given iff C is")
+    T2, Wt2, C2 = out
+    if _tsdf_volume(T2, Wt2, C2, a[6:]) != dev:
+        raise ValueError(f"out is on {T2.device}, the volume on {dev}")
+    n = torch.empty((2,), device=dev, dtype=torch.int64) if counts else None
+    _call("lws_tsdf_window", dev, T, Wt, C, *a[:6], T2, Wt2, C2, *a[6:], n)
+    return TsdfWindow(T2, Wt2, C2, n)
+
+
 SpeckleResult = namedtuple("SpeckleResult", ["disp", "mask", "labels", "counts"])
 SpeckleResult.__doc__ = """What speckle_filter returns: the filtered (filled if asked) maps float32 [B,1,H,W], the uint8 code map (1 kept,
 3 speckle, the input code or 0 for an invalid pixel), labels int32 [B,1,H,W] (None unless want_labels) and counts, an int64

@@ -55,6 +55,9 @@ def read_poses(p, args):
     return poses
 
 
+TSDF_FOLLOW_STEP = 16                                       # --tsdf_follow without a number, in voxels
+
+
 def add_sequence_arguments(p):
     """--temporal, --egomotion, --tsdf and their flags (not in the reference).  A command line without them parses to the namespace it
     parsed to before they existed (argparse.SUPPRESS); the check_* functions write their defaults."""
@@ -96,6 +99,11 @@ def add_sequence_arguments(p):
                    help="tsdf: at the end, write the volume's zero crossings as a binary PLY of vertices with normals and colours")
     p.add_argument("--save_tsdf_mesh", type=str, default=S, metavar="PATH",
                    help="tsdf: at the end, write the volume's zero level set as a binary PLY of the same vertices and the triangles between them")
+    p.add_argument("--tsdf_follow", type=int, nargs="?", const=TSDF_FOLLOW_STEP, default=S, metavar="N",
+                   help="tsdf: the volume follows the camera, moving by whole voxels once the view's centre is N voxels from its own (default 16; "
+                        "at least 1, below the smallest dimension minus 2); what leaves is spilled to --save_tsdf_mesh / --save_tsdf_ply in chunks "
+                        "first.  A seam vertex is in both chunks that meet there, a normal at a chunk's border is zero, what re-enters the "
+                        "volume is mapped afresh (a loop gives two surfaces), and after a sharp turn what lies behind the camera is spilled")
     p.add_argument("--save_tsdf", action="store_true", default=S, help="tsdf: write <stem>_tsdf.png, the volume ray-cast into the frame's own pose, coloured as the stage maps")
     p.add_argument("--tsdf_track", action="store_true", default=S,
                    help="refine each frame's --egomotion estimate against the --tsdf volume (joint photometric + point-to-plane cost); the "
@@ -206,6 +214,21 @@ def check_tsdf_mesh_arguments(p, args):
     post.set_defaults(args, **TSDF_MESH_DEFAULTS)
     if args.save_tsdf_mesh is not None and not getattr(args, "tsdf", False):
         p.error("--save_tsdf_mesh needs --tsdf")
+
+
+TSDF_FOLLOW_DEFAULTS = dict(tsdf_follow=None)              # a table of its own, as TSDF_MESH_DEFAULTS
+
+
+def check_tsdf_follow_arguments(p, args):
+    """--tsdf_follow, behind check_tsdf_arguments: sets the default; the flag without --tsdf or with N out of range is refused."""
+    post.set_defaults(args, **TSDF_FOLLOW_DEFAULTS)
+    if args.tsdf_follow is None:
+        return
+    if not getattr(args, "tsdf", False):
+        p.error("--tsdf_follow needs --tsdf")
+    top = min(tsdf_grid(args)[1]) - 2
+    if not 1 <= args.tsdf_follow < top:
+        p.error(f"--tsdf_follow must be at least 1 and below the volume's smallest dimension minus 2 = {top} voxels, got {args.tsdf_follow}")
 
 
 TRACK_DEFAULTS = dict(tsdf_track=False, track_iters=6, track_lambda=1.0, track_gate=4.0, save_track=False)
@@ -394,7 +417,7 @@ class _Volume(_Stage):
 
     def __init__(self, args, source, device, log):
         import torch
-        from .tsdf import TsdfVolume, volume_bytes
+        from .tsdf import MeshChunks, TsdfVolume, volume_bytes
         super().__init__(args, source)
         origin, dims = tsdf_grid(args)
         need, free = volume_bytes(dims, colour=True), torch.cuda.mem_get_info(device)[0]
@@ -404,6 +427,10 @@ class _Volume(_Stage):
         self.volume = TsdfVolume(origin, args.tsdf_voxel, dims, mu0=args.tsdf_trunc, mu_d=args.tsdf_trunc_px, weight=args.tsdf_weight, colour=True,
                                  min_disp=args.min_disp, max_depth=args.max_depth, device=device)
         log.info("TSDF: volume {} x {} x {} voxels of {:g} m from ({:g}, {:g}, {:g}), {} bytes".format(*dims, args.tsdf_voxel, *origin, need))
+        # --tsdf_follow: the volume's centre in the first camera's frame is what the volume keeps near its centre, so the first frame
+        # never moves it; the chunks that left wait on the host for finish()
+        self.anchor, self.chunks = self.volume.centre(), MeshChunks()
+        self.spill = "mesh" if args.save_tsdf_mesh is not None else "points" if args.save_tsdf_ply is not None else None
 
     def step(self, s, log):
         import torch
@@ -416,6 +443,8 @@ class _Volume(_Stage):
         disp, keep = _stage4(s.res)
         keep = out.merge_keep(keep, frame.valid_left)
         with torch.cuda.device(disp.device):
+            if a.tsdf_follow is not None:
+                self.follow(pose, log)
             kw = dict(mask=keep, min_disp=a.min_disp, max_depth=a.max_depth, max_jump=a.max_jump)
             normals = ops.surface_normals(disp, frame.cam, **kw)[0] if a.tsdf_sdf == "plane" else None
             sigma = None if s.fused is None else torch.sqrt(s.fused.var)
@@ -425,10 +454,39 @@ class _Volume(_Stage):
             if a.save_tsdf:
                 s.view = self.volume.raycast(frame.cam, pose, *disp.shape[2:], z_near=max(a.tsdf_voxel, 0.5), weight=False, normals=False)
 
+    def follow(self, pose, log):
+        """--tsdf_follow, before a frame is integrated at `pose` (camera -> the first camera): moves the volume once the anchor is N
+        voxels from its centre, keeps what the move spilled and logs the move."""
+        shift, chunks = self.volume.follow(pose, self.anchor, self.args.tsdf_follow, spill=self.spill, max_points=TSDF_MAX_POINTS,
+                                           max_faces=TSDF_MAX_FACES)
+        if not any(shift):
+            return
+        for c in chunks:
+            self.chunks.append(c)
+        log.info("TSDF: followed by ({}, {}, {}) voxels, kept = {}, spilled vertices = {}, faces = {}".format(
+            *shift, int(self.volume.kept[0]), sum(len(c.points) for c in chunks), sum(len(c.faces) for c in chunks)))
+
     def save(self, s, stem, log):
         return out.save_tsdf(stem, log, s.view) if s.view is not None else []
 
+    def finish_chunks(self, log):
+        """finish() with --tsdf_follow: the volume is the last chunk; the point file gets the chunks' vertices, the mesh file the same
+        vertices in the same order and the faces."""
+        path, mesh = self.args.save_tsdf_ply, self.args.save_tsdf_mesh
+        if self.spill is not None:
+            self.chunks.append(self.volume.chunk(self.spill, max_points=TSDF_MAX_POINTS, max_faces=TSDF_MAX_FACES))
+            pts = np.concatenate(self.chunks.points)
+            twice = len(pts) - len(np.unique(np.ascontiguousarray(pts[:, :12]).view("V12")))
+            log.info("TSDF: {} chunks, vertices at a place an earlier vertex holds (the seams) = {}".format(len(self.chunks.points), twice))
+        if path is not None:
+            log.info("Save TSDF points = {}, vertices = {}".format(path, self.chunks.write(path, faces=False)[0]))
+        if mesh is not None:
+            log.info("Save TSDF mesh = {}, vertices = {}, faces = {}".format(mesh, *self.chunks.write(mesh)))
+        return [f for f in (path, mesh) if f is not None]
+
     def finish(self, log):
+        if self.args.tsdf_follow is not None:
+            return self.finish_chunks(log)
         path = self.args.save_tsdf_ply
         if path is not None:
             log.info("Save TSDF points = {}, vertices = {}".format(path, self.volume.write_ply(path, max_points=TSDF_MAX_POINTS)))
@@ -442,7 +500,7 @@ class _Volume(_Stage):
 def begin(args, pairs, device, log, poses=None):
     """(the PoseSource, the stages that are on, in the order they run) of a run over `pairs` pairs.  poses: what the checks read;
     a namespace that skipped the checks gets the flags' defaults and its --poses file read here."""
-    post.set_defaults(args, **TEMPORAL_DEFAULTS, **EGO_DEFAULTS, **TSDF_DEFAULTS, **TSDF_MESH_DEFAULTS, **TRACK_DEFAULTS)
+    post.set_defaults(args, **TEMPORAL_DEFAULTS, **EGO_DEFAULTS, **TSDF_DEFAULTS, **TSDF_MESH_DEFAULTS, **TSDF_FOLLOW_DEFAULTS, **TRACK_DEFAULTS)
     if poses is None and args.poses is not None and not args.egomotion:
         from .geometry import read_kitti_poses
         poses = read_kitti_poses(args.poses)

@@ -11,7 +11,12 @@ after a warm-up, R windows of N calls between two events, the median window per 
 volume the four frames left (normals, colour and `updated`: two launches), the same without normals, colour and `updated` (one
 launch), of the four frames in one call, lws_tsdf_raycast of the third pose (step 0.1 m) with weight and normals and without,
 lws_tsdf_points, and lws_tsdf_mesh on the same volume (the three launches of the points and three more).  A window integrates the same frame again and again, so the weights grow; the arithmetic per voxel does not depend
-on them.  Prints one JSON line with the times, the voxels taken per frame, the pixels that hit, the points and the faces found."""
+on them.  Then lws_tsdf_window (include/lwsnet_tsdf_window.h), the move of a volume that follows the camera, into a second set of
+tensors: a volume of 128 x 32 x 256 voxels with colour cut out of the one above (rows of 512 bytes: every quad is a 16-byte word
+on both sides when sx is a multiple of 4) for sx = 16 and sx = 5, the same with every voxel observed, and the 129 x 33 x 257 volume itself for sx = 16 (rows of 516 bytes: three rows in four begin off
+a 16-byte boundary and go voxel by voxel); beside each, in the same run, plain Tensor.copy_ of the same three tensors, which moves
+the same bytes, and the window's time over the copy's.  Prints one JSON line with the times, the voxels taken per frame, the pixels
+that hit, the points and the faces found."""
 import argparse
 import ctypes
 import json
@@ -92,6 +97,31 @@ def main():
                               ("integrate_1_frame_again", lambda k: integrate(1, True), a.iters)):
         benchkit.warm(call, 5)
         line[name] = benchkit.summary(benchkit.windows(call, iters, a.runs))
+
+    # the window against a plain copy of the same tensors
+    def window_rows(tag, T, Wt, C, shifts):
+        g = T.shape[::-1]
+        out = tuple(torch.empty_like(t) for t in (T, Wt, C))
+        counts = torch.empty((2,), dtype=torch.int64, device=dev)
+
+        def copy(k=None):
+            for dst, src in zip(out, (T, Wt, C)):
+                dst.copy_(src)
+        benchkit.warm(copy, 5)
+        line["copy" + tag] = benchkit.summary(benchkit.windows(copy, a.iters, a.runs))
+        for sx in shifts:
+            def window(k=None):
+                _lib.call("lws_tsdf_window", P(T), P(Wt), P(C), *g, sx, 0, 0, P(out[0]), P(out[1]), P(out[2]), *g, P(counts), stream)
+            benchkit.warm(window, 5)
+            name = f"window{tag}_sx{sx}"
+            line[name] = benchkit.summary(benchkit.windows(window, a.iters, a.runs))
+            line[name]["live"] = int(counts[0])
+            line[name]["over_copy"] = round(line[name]["us"] / line["copy" + tag]["us"], 2)
+
+    cut = ops.tsdf_window(vol.T, vol.Wt, (0, 0, 0), (128, 32, 256), C=vol.C, counts=False)
+    window_rows("_128x32x256", cut.T, cut.Wt, cut.C, (16, 5))
+    window_rows("_128x32x256_all_observed", cut.T, torch.ones_like(cut.Wt), cut.C, (16, 5))
+    window_rows("_129x33x257", vol.T, vol.Wt, vol.C, (16,))
     print(json.dumps(line), flush=True)
 
 
