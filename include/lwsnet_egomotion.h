@@ -97,7 +97,7 @@ int lws_ego_normal(const float *grey_ref, const float *disp_ref, const uint8_t *
  * captured into a hipGraph: one kernel for both level-0 grey images and the start M; one per further level for its three
  * images (so `levels` launches for the pyramids, not the one or two a fused pyramid would take: a level needs the level below it
  * complete); two per step; two for the final linearisation: levels + 2 * levels * iters + 2.
- * Out of scope, stated and left as it is: movers are neither tracked nor segmented (resid only shows them); no loop closure,
+ * Out of scope, stated and left as it is: movers are neither tracked nor segmented (resid only shows them; include/lwsnet_movers.h segments them, given the motion); no loop closure,
  * keyframes or bundle adjustment; no geometric (disparity) error term here (lws_track of
  * lwsnet_track.h has one, against the TSDF model); no photometric gain and offset; drift over long sequences
  * is not bounded; real KITTI accuracy is unknown -- the defaults of the Python layer have met a synthetic scene only. */

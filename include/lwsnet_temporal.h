@@ -68,7 +68,8 @@ int64_t lws_temporal_workspace(int B, int H, int W, int hold);
  * integer add, whose order cannot show: an image gives the same bytes in any batch, at any position in it, on every run.  No
  * scratch memory.
  * Limits, stated and left as they are: the poses are taken as the left camera's; the rig and the static scene are assumed rigid;
- * the gate resets what moves (code 3) and does not track it; held pixels drift. */
+ * the gate resets what moves (code 3) and does not track it (include/lwsnet_movers.h
+ * segments it, for the caller's mask); held pixels drift. */
 int lws_temporal_step(const float *meas, const float *sigma, const uint8_t *mask, const float *cam, const float *pose, const float *Dp,
                       const float *Vp, const uint16_t *Ap, int B, int H, int W, float sigma0, float min_disp, float sigma_min, float gate,
                       float q, float max_jump, int hold, float q_hold, float max_var, void *workspace, float *D, float *V, uint16_t *A,

@@ -87,7 +87,7 @@ int lws_track_normal(const float *grey_ref, const float *disp_ref, const float *
  * Launches on `stream`, a list fixed by iters, never by the data, nothing read back, no scratch memory, so the call can be captured
  * into a hipGraph: one grey kernel, two per step, two for the final linearisation: 2 * iters + 3.
  * Out of scope, stated and left as it is: no pyramid for the geometric term -- the coarse-to-fine work stays in lws_egomotion, which
- * supplies init; the volume neither moves nor is hashed; no loop closure, keyframes or bundle adjustment; movers are not segmented,
+ * supplies init; the volume neither moves nor is hashed; no loop closure, keyframes or bundle adjustment; movers are not segmented here (include/lwsnet_movers.h does that),
  * the gate only drops them; no photometric gain and offset; real-data accuracy is unknown -- the defaults of the Python layer have
  * met a synthetic scene only. */
 int lws_track(const uint8_t *rgb_ref, const float *disp_ref, const float *normals_ref, const uint8_t *mask_ref, const uint8_t *rgb_cur,

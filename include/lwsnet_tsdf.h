@@ -18,7 +18,8 @@
  * bad shape or scalar, rgb without C or C without rgb, any overlap between an output, the volume or the workspace and anything
  * else -- return LWS_ERR_INVALID with a message before any GPU call.
  * Limits, stated and left as they are: a dense volume of fixed extent, what leaves it is not mapped; no voxel hashing and no moving
- * volume (include/lwsnet_tsdf_window.h moves one between calls); movers smear; the poses are taken as given. */
+ * volume (include/lwsnet_tsdf_window.h moves one between calls); movers smear unless the caller masks them (include/lwsnet_movers.h
+ * segments them); the poses are taken as given. */
 #ifndef LWSNET_TSDF_H
 #define LWSNET_TSDF_H
 #include "lwsnet_hip.h"

@@ -3,8 +3,8 @@ constants are read from it when this module is imported (tests/test_abi_cpu.py h
 points added behind ABI v8 live in headers of their own, named in HEADERS; each is read the same way into ABI[header name], and a
 new header is one more name there.  HEADERS, ABI and ALL_PROTOTYPES are the functions the stream-ordering table of
 tests/test_gpu_stream_order.py has a row for; lws_tsdf_mesh's header and lws_track's (include/lwsnet_track.h) are read the same way
-into tables of their own beside these, MESH_ABI and TRACK_ABI, as is lws_tsdf_window's (include/lwsnet_tsdf_window.h) into WINDOW_ABI,
-and their calls' stream tests are in their own test files.
+into tables of their own beside these, MESH_ABI and TRACK_ABI, as is lws_tsdf_window's (include/lwsnet_tsdf_window.h) into WINDOW_ABI
+and lws_movers' (include/lwsnet_movers.h) into MOVERS_ABI, and their calls' stream tests are in their own test files.
 
 The header cannot say which pointers are host pointers, so every pointer but `const char *` is c_void_p: the 20 host-pointer
 parameters -- lws_set_tensor's data and shape, the mean / std arrays, lws_profile_read*, lws_clock_read, lws_join_stats, the
@@ -26,6 +26,7 @@ HEADERS = ("lwsnet_hip.h", "lwsnet_objects.h", "lwsnet_temporal.h", "lwsnet_egom
 MESH_HEADERS = ("lwsnet_tsdf_mesh.h",)
 TRACK_HEADERS = ("lwsnet_track.h",)
 WINDOW_HEADERS = ("lwsnet_tsdf_window.h",)
+MOVERS_HEADERS = ("lwsnet_movers.h",)
 HEADER_PATH = os.path.join(INCLUDE, HEADERS[0])
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
@@ -129,7 +130,7 @@ def _read(name):
     return (protos, spellings, f.name), consts
 
 
-_READ = {name: _read(name) for name in (*HEADERS, *MESH_HEADERS, *TRACK_HEADERS, *WINDOW_HEADERS)}
+_READ = {name: _read(name) for name in (*HEADERS, *MESH_HEADERS, *TRACK_HEADERS, *WINDOW_HEADERS, *MOVERS_HEADERS)}
 # header name -> (prototypes, spellings, path): name -> (restype, argtypes) and name -> (C return type, C parameter types), exactly
 # the functions that header declares; PROTOTYPES, C_SPELLINGS and the constants are the base header's
 ABI = {name: _READ[name][0] for name in HEADERS}
@@ -151,7 +152,10 @@ TRACK_PROTOTYPES = merge_headers({name: table[0] for name, table in TRACK_ABI.it
 # lws_tsdf_window: likewise
 WINDOW_ABI = {name: _READ[name][0] for name in WINDOW_HEADERS}
 WINDOW_PROTOTYPES = merge_headers({name: table[0] for name, table in WINDOW_ABI.items()})
-merge_headers({name: table[0] for name, table in (*ABI.items(), *MESH_ABI.items(), *TRACK_ABI.items(), *WINDOW_ABI.items())})       # a name two headers declare raises
+# lws_movers: likewise
+MOVERS_ABI = {name: _READ[name][0] for name in MOVERS_HEADERS}
+MOVERS_PROTOTYPES = merge_headers({name: table[0] for name, table in MOVERS_ABI.items()})
+merge_headers({name: table[0] for name, table in (*ABI.items(), *MESH_ABI.items(), *TRACK_ABI.items(), *WINDOW_ABI.items(), *MOVERS_ABI.items())})       # a name two headers declare raises
 
 _lib = None
 
@@ -177,7 +181,8 @@ def load():
             f"{LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python -m lwsnet_amd.build`); there is no CPU fallback for the disparity path")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in (*ALL_PROTOTYPES.items(), *MESH_PROTOTYPES.items(), *TRACK_PROTOTYPES.items(), *WINDOW_PROTOTYPES.items()):
+    for name, (res, args) in (*ALL_PROTOTYPES.items(), *MESH_PROTOTYPES.items(), *TRACK_PROTOTYPES.items(), *WINDOW_PROTOTYPES.items(),
+                              *MOVERS_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

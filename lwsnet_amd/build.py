@@ -16,7 +16,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "liblwsnet_hip.so")
 SOURCES = ["lws_api.hip", "lws_params.hip", "lws_forward.hip", "lws_pool.hip", "lws_volume.hip", "lws_regress.hip", "lws_conv3d.hip", "lws_feature2d.hip", "lws_refine.hip", "lws_io.hip",
-           "lws_metrics.hip", "lws_lrcheck.hip", "lws_occlusion.hip", "lws_geometry.hip", "lws_mesh.hip", "lws_ground.hip", "lws_stixels.hip", "lws_objects.hip", "lws_temporal.hip", "lws_egomotion.hip", "lws_tsdf.hip", "lws_tsdf_mesh.hip", "lws_tsdf_window.hip", "lws_track.hip", "lws_speckle.hip", "lws_wmedian.hip", "lws_rectify.hip", "lws_confidence.hip", "lws_sparsification.hip", "lws_photometric.hip"]
+           "lws_metrics.hip", "lws_lrcheck.hip", "lws_occlusion.hip", "lws_geometry.hip", "lws_mesh.hip", "lws_ground.hip", "lws_stixels.hip", "lws_objects.hip", "lws_temporal.hip", "lws_egomotion.hip", "lws_tsdf.hip", "lws_tsdf_mesh.hip", "lws_tsdf_window.hip", "lws_track.hip", "lws_movers.hip", "lws_speckle.hip", "lws_wmedian.hip", "lws_rectify.hip", "lws_confidence.hip", "lws_sparsification.hip", "lws_photometric.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wall", "-Wno-unused-function"]
 
@@ -40,6 +40,7 @@ def needs_build():
                                                                os.path.join(ROOT, "include", "lwsnet_tsdf_mesh.h"),
                                                                os.path.join(ROOT, "include", "lwsnet_tsdf_window.h"),
                                                                os.path.join(ROOT, "include", "lwsnet_track.h"),
+                                                               os.path.join(ROOT, "include", "lwsnet_movers.h"),
                                                                os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > t for d in deps)
 

@@ -134,7 +134,7 @@ volume ray-cast into the frame's own pose and coloured as the stage maps: the de
 `--save_tsdf_ply PATH` writes the volume's zero crossings as a PLY of vertices with normals and colours and logs their number;
 `--save_tsdf_mesh PATH` writes the same vertices, in the same order, with the marching-cubes triangles between them
 (lws_tsdf_mesh, include/lwsnet_tsdf_mesh.h) and logs vertices and faces.  A volume that does not fit the device's free memory is an error before the first frame.  What leaves the volume is not mapped; movers
-smear; the poses are taken as given.
+smear unless `--movers` takes them out; the poses are taken as given.
 
 `--tsdf_follow [N]`: needs `--tsdf`.  The volume follows the camera (lwsnet_amd.tsdf.TsdfVolume.follow, lws_tsdf_window,
 include/lwsnet_tsdf_window.h): before a frame is integrated, the centre of `--tsdf_extent`, carried along with the camera, is compared
@@ -153,6 +153,16 @@ include/lwsnet_track.h): the volume is ray-cast at the previous frame's tracked 
 one joint photometric + point-to-plane cost.  While it is on, the filter, the volume and `--save_poses` get the tracked poses.  One
 log line per frame gives the terms of both kinds, their rms and the status.  `--save_track` writes `<stem>_track.png`, the
 point-to-plane residual in standard deviations (white 0, red / blue +-4, black: no model there).
+
+`--movers [--movers_gate G] [--movers_gate_p P] [--movers_radius R] [--movers_min_pixels N] [--movers_grow N] [--movers_uncovered]
+[--save_movers]`: needs a pose source, `--poses` or `--egomotion`.  Between tracking and the filter, each frame is compared with
+the pair processed before it under the run's motion (lwsnet_amd.movers.MoverSegmenter, lws_movers, include/lwsnet_movers.h): the
+pixels whose disparity or grey level disagrees with a rigid scene are grouped, a group of N pixels or more is a mover, and the movers
+(grown by `--movers_grow` pixels) get code 4 in the stage-4 `keep` codes, so that `--temporal` and `--tsdf` never take them; a run
+without checks gets `keep` codes where it had none.  A frame whose motion is not to be trusted is not segmented.  One log line per
+frame gives the pixels per evidence code, the movers and the nearest mover's box and depth.  `--save_movers` writes
+`<stem>_movers.png` (untested black, static grey, appeared red, uncovered blue, changed yellow, movers outlined in white) and
+`<stem>_movers.csv`, one line per mover.  A receding mover looks like a disocclusion and is found with `--movers_uncovered` only.
 """
 import argparse
 import contextlib
@@ -175,7 +185,7 @@ from .outputs import (STIXEL_COLOUR_DEPTH, bev_to_u8, conf_to_u8, ground_to_rgb,
 from .postprocess import (add_lr_arguments, add_occ_arguments, add_speckle_arguments, add_wmedian_arguments, check_lr_arguments,
                           check_occ_arguments, check_speckle_arguments, check_wmedian_arguments)
 from .sequence import (TSDF_DEFAULTS, TSDF_FOLLOW_DEFAULTS, TSDF_MESH_DEFAULTS, check_egomotion_arguments, check_temporal_arguments,  # noqa: F401
-                       check_tsdf_arguments, check_tsdf_follow_arguments, check_tsdf_mesh_arguments, check_track_arguments, list_pairs as _list_pairs, temporal_sigma, tsdf_grid)
+                       check_tsdf_arguments, check_tsdf_follow_arguments, check_tsdf_mesh_arguments, check_track_arguments, check_movers_arguments, list_pairs as _list_pairs, temporal_sigma, tsdf_grid)
 
 
 def build_parser():
@@ -603,7 +613,7 @@ def inference(model, left_imgs, right_imgs, args, log, poses=None):
                 log.info("Weighted median (radius {}, sigma {:g}, fill {}): stage {} changed = {}, filled = {}".format(
                     opts.wmedian, opts.wmedian_sigma, opts.wmedian_fill, stage + 1, changed, refilled))
         conf = chain_model.last if conf_on else None
-        step = types.SimpleNamespace(index=index, frame=frame, res=res, conf=conf, ego=None, track=None, fused=None, view=None)   # (lwsnet_amd/sequence.py)
+        step = types.SimpleNamespace(index=index, frame=frame, res=res, conf=conf, ego=None, track=None, movers=None, fused=None, view=None)   # (lwsnet_amd/sequence.py)
         source.frame(index)
         for st in stages:                                   # ego-motion on the chain's own map and codes, the filter, the volume on what it left
             st.step(step, log)
@@ -690,6 +700,7 @@ def main(argv=None):
     check_tsdf_mesh_arguments(parser, args)
     check_tsdf_follow_arguments(parser, args)
     check_track_arguments(parser, args)
+    mine = check_movers_arguments(parser, args)
     log = start_logging("lwsnet_amd.inference", args)
     model = load_model(args, log)
     if getattr(args, "split_bf16", False):
@@ -708,7 +719,7 @@ def main(argv=None):
         written, stats = inference_pipelined(model, lefts, rights, args, log)
         main.last_stats = stats
     else:
-        written = inference(model, lefts, rights, args, log, alone if poses is None else poses)
+        written = inference(model, lefts, rights, args, log, next((f for f in (poses, alone, mine) if f is not None), None))
     log.info("End inference!")
     return written
 

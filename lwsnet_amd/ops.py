@@ -1288,6 +1288,74 @@ def tsdf_window(T, Wt, offset, dims=None, C=None, out=None, counts=True):
     return TsdfWindow(T2, Wt2, C2, n)
 
 
+MoversResult = namedtuple("MoversResult", ["evidence", "mask", "labels", "rows", "vals", "info"])
+MoversResult.__doc__ = """What movers returns, all on the device and in the current frame: evidence uint8 [B,1,H,W] (MOVER_EVIDENCE: 0 untested,
+1 static, 2 appeared, 3 uncovered, 4 changed); mask uint8 [B,1,H,W], the current code map with MOVER_CODE = 4 on every mover and
+`grow` pixels around it; labels int32 [B,1,H,W] (None unless asked for), the mover's number or -1; rows int32 [B,max_movers,8] =
+{n, x_min, x_max, y_min, y_max, n2, n3, n4}; vals float32 [B,max_movers,2] = {disparity, depth}; info int32 [B,8] = {tested, static,
+appeared, uncovered, changed pixels, components, movers before the cap, pixels of code 4 in mask}."""
+MOVER_EVIDENCE = ("untested", "static", "appeared", "uncovered", "changed")
+MOVER_CODE = 4                                              # the code of a mover's pixel in MoversResult.mask
+MOVER_CANDIDATES = 1 << 2 | 1 << 4                          # cand_bits: appeared and changed; 1 << 3 adds the uncovered pixels
+MOVERS_DEFAULTS = dict(min_disp=1.0, sigma0=0.5, sigma_min=0.05, gate_g=3.0, gate_p=25.0, radius=0, cand_bits=MOVER_CANDIDATES, max_diff=1.0,
+                       min_pixels=64, grow=2, max_movers=64)           # the scalars of movers, in the order of movers_args
+
+
+def movers_args(min_disp, sigma0, sigma_min, gate_g, gate_p, radius, cand_bits, max_diff, min_pixels, grow, max_movers):
+    """The validated scalars of movers, in the order of the C call."""
+    if not gate_p > 0:
+        raise ValueError(f"gate_p must be > 0 (inf: no photometric test), got {gate_p}")
+    cand_bits = _int_in("cand_bits", cand_bits, 0, 31)
+    if cand_bits & 3:
+        raise ValueError(f"cand_bits must leave bits 0 and 1 clear (untested and static pixels are no candidates), got {cand_bits}")
+    if not max_diff >= 0:
+        raise ValueError(f"max_diff must be >= 0 (inf allowed), got {max_diff}")
+    return (_finite_pos("min_disp", min_disp), _finite_nonneg("sigma0", sigma0), _finite_pos("sigma_min", sigma_min), _finite_pos("gate_g", gate_g),
+            float(gate_p), _int_in("radius", radius, 0, 2), cand_bits, float(max_diff), _int_in("min_pixels", min_pixels, 1, 2 ** 31 - 1),
+            _int_in("grow", grow, 0, 8), _int_in("max_movers", max_movers, 1, 65536))
+
+
+def movers(rgb_prev, disp_prev, rgb_cur, disp_cur, cameras, pose, sigma_prev=None, mask_prev=None, sigma_cur=None, mask_cur=None, min_disp=1.0,
+           sigma0=0.5, sigma_min=0.05, gate_g=3.0, gate_p=25.0, radius=0, cand_bits=MOVER_CANDIDATES, max_diff=1.0, min_pixels=64, grow=2,
+           max_movers=64, labels=True, mask_out=None):
+    """The moving objects between two consecutive frames (include/lwsnet_movers.h, lws_movers): per pixel of the current frame the
+    evidence against a rigid scene under the camera motion `pose`, the connected components of the candidate pixels, and per
+    component of at least min_pixels pixels -- a mover -- its box, disparity and depth.  rgb uint8 [B,H,W,3]; disp float32 [B,1,H,W];
+    sigmas float32 [B,1,H,W] in px or None (sigma0 everywhere); masks uint8 lws_lr_check code maps or None; pose: the float32
+    [B,2,12] device tensor egomotion or track returns, or what geometry.relative_pose returns.  mask_out: None (a new tensor) or the
+    tensor to write, which may be mask_cur itself.  The defaults were chosen on synthetic scenes only; they have not met real data.
+    Returns a MoversResult; nothing is read back."""
+    scalars = movers_args(min_disp, sigma0, sigma_min, gate_g, gate_p, radius, cand_bits, max_diff, min_pixels, grow, max_movers)
+    if cameras is None:
+        raise ValueError("movers needs cameras")
+    if pose is None:
+        raise ValueError("movers needs pose, the motion between the two frames")
+    d, mask_cur, cam = _geometry_inputs(disp_cur, mask_cur, cameras, scalars[0], float("inf"))
+    B, _, H, W = d.shape
+    _int_indexed(H, W, "disp_cur", "movers", sides=True)
+    dp = _tensor_of(disp_prev, "disp_prev", torch.float32, d.shape, d.device)
+    r0, r1 = (_tensor_of(r, name, torch.uint8, (B, H, W, 3), d.device) for r, name in ((rgb_prev, "rgb_prev"), (rgb_cur, "rgb_cur")))
+    sp, sc = (None if s is None else _tensor_of(s, name, torch.float32, d.shape, d.device) for s, name in ((sigma_prev, "sigma_prev"), (sigma_cur, "sigma_cur")))
+    if mask_prev is not None:
+        mask_prev = _tensor_of(mask_prev, "mask_prev", torch.uint8, d.shape, d.device, " (the lws_lr_check code map)")
+    pose_dev = _device_rows(pose, "pose", (B, 2, 12), d.device, lambda: temporal_pose_rows(pose, B))
+    max_movers = scalars[-1]
+    work = _workspace("lws_movers_workspace", d.device, B, H, W, max_movers)
+    evidence = torch.empty(d.shape, device=d.device, dtype=torch.uint8)
+    if mask_out is None:
+        mask_out = torch.empty(d.shape, device=d.device, dtype=torch.uint8)
+    elif not (isinstance(mask_out, torch.Tensor) and mask_out.dtype == torch.uint8 and tuple(mask_out.shape) == tuple(d.shape)
+              and mask_out.device == d.device and mask_out.is_contiguous()):
+        raise ValueError(f"mask_out must be a contiguous uint8 {tuple(d.shape)} tensor on {d.device}")
+    lab = torch.empty(d.shape, device=d.device, dtype=torch.int32) if labels else None
+    rows = torch.empty((B, max_movers, 8), device=d.device, dtype=torch.int32)
+    vals = torch.empty((B, max_movers, 2), device=d.device, dtype=torch.float32)
+    info = torch.empty((B, 8), device=d.device, dtype=torch.int32)
+    _call("lws_movers", d.device, r0, dp, sp, mask_prev, r1, d, sc, mask_cur, cam, pose_dev, B, H, W, *scalars, work, evidence, mask_out, lab,
+          rows, vals, info)
+    return MoversResult(evidence, mask_out, lab, rows, vals, info)
+
+
 SpeckleResult = namedtuple("SpeckleResult", ["disp", "mask", "labels", "counts"])
 SpeckleResult.__doc__ = """What speckle_filter returns: the filtered (filled if asked) maps float32 [B,1,H,W], the uint8 code map (1 kept,
 3 speckle, the input code or 0 for an invalid pixel), labels int32 [B,1,H,W] (None unless want_labels) and counts, an int64

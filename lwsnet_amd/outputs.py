@@ -423,6 +423,56 @@ def save_track(stem, frame, log, track):
     return [stem + "_track.png"]
 
 
+MOVERS_CODES = ("untested", "static", "appeared", "uncovered", "changed")          # lws_movers' evidence codes 0 .. 4
+MOVERS_COLOURS = np.array([[0, 0, 0], [90, 90, 90], [230, 25, 75], [0, 130, 200], [255, 225, 25]], np.uint8)   # by code
+MOVERS_OUTLINE = np.array([255, 255, 255], np.uint8)
+
+
+def movers_line(info, rows, vals):
+    """The log line of one frame's ops.MoversResult (info [8], rows [K,8], vals [K,2] of one image, on the host): the pixels per
+    evidence code, the movers, and the box and depth of the nearest mover that has a slot."""
+    text = "Movers: " + ", ".join("{} = {}".format(n, c) for n, c in zip(("tested",) + MOVERS_CODES[1:], info[:5]))
+    text += ", components = {}, movers = {}, masked pixels = {}".format(info[5], info[6], info[7])
+    held = np.flatnonzero(np.asarray(rows)[:, 0] > 0)
+    if len(held):
+        j = held[np.argmin(np.asarray(vals)[held, 1])]
+        n, x0, x1, y0, y1 = (int(v) for v in rows[j][:5])
+        text += ", nearest = #{} x {}..{} y {}..{} ({} px) at {:.2f} m".format(j, x0, x1, y0, y1, n, float(vals[j][1]))
+    return text
+
+
+def movers_to_rgb(evidence, labels):
+    """<stem>_movers.png: the colour of each pixel's evidence code (MOVERS_COLOURS: untested black, static grey, appeared red,
+    uncovered blue, changed yellow); a mover's pixel with a 4-neighbour that is not of the same mover (or at the image's edge) is
+    drawn in MOVERS_OUTLINE."""
+    rgb = MOVERS_COLOURS[np.asarray(evidence)]
+    lab = np.asarray(labels)
+    pad = np.pad(lab, 1, constant_values=-2)
+    edge = np.zeros(lab.shape, bool)
+    for dy, dx in ((0, 1), (2, 1), (1, 0), (1, 2)):
+        edge |= pad[dy:dy + lab.shape[0], dx:dx + lab.shape[1]] != lab
+    rgb[(lab >= 0) & edge] = MOVERS_OUTLINE
+    return rgb
+
+
+def save_movers(stem, frame, log, movers):
+    """--save_movers: <stem>_movers.png (movers_to_rgb) and <stem>_movers.csv, one line per mover that has a slot, of the frame's
+    ops.MoversResult; all black and the header alone for a frame that was not segmented (movers None)."""
+    h, w = _rgb_on_host(frame.left).shape[:2]
+    lines = ["mover,pixels,x_min,x_max,y_min,y_max,appeared,uncovered,changed,disparity,depth"]
+    if movers is None:
+        rgb = np.zeros((h, w, 3), np.uint8)
+    else:
+        rgb = movers_to_rgb(movers.evidence[0, 0].cpu().numpy(), movers.labels[0, 0].cpu().numpy())
+        rows, vals = movers.rows[0].cpu().numpy(), movers.vals[0].cpu().numpy()
+        lines += ["{},{},{:.4f},{:.4f}".format(j, ",".join(str(int(v)) for v in rows[j]), vals[j][0], vals[j][1]) for j in np.flatnonzero(rows[:, 0] > 0)]
+    io.save_png(stem + "_movers.png", rgb)
+    with open(stem + "_movers.csv", "w") as f:
+        f.write("\n".join(lines) + "\n")
+    log.info("Save movers = {}_movers.png, {}_movers.csv".format(stem, stem))
+    return [stem + "_movers.png", stem + "_movers.csv"]
+
+
 def save_tsdf(stem, log, view):
     """--save_tsdf: <stem>_tsdf.png, the volume ray-cast into the frame's own pose (an ops.TsdfView), coloured as the stage maps."""
     io.save_png(stem + "_tsdf.png", io.disparity_to_color(view.disp[0, 0].cpu().numpy()))

@@ -131,6 +131,14 @@ class ChainResult(namedtuple("ChainResult", ["disp", "lr_masks", "speckle_masks"
         new.occ_masks, new.occ_density = self.occ_masks, self.occ_density      # (_replace copies the tuple's seven only)
         return new
 
+    def with_stage4_keep(self, keep):
+        """This result with another stage-4 code map, also where there were no `keep` codes: the other stages then keep every pixel
+        (all 1), which is what having no codes meant for them."""
+        import torch
+        new = self._replace(keep=(list(self.keep[:3]) if self.keep is not None else [torch.ones_like(keep) for _ in range(3)]) + [keep])
+        new.occ_masks, new.occ_density = self.occ_masks, self.occ_density
+        return new
+
 
 def run_chain(model, left, right, options, guide=None):
     """One batch through the forward (or forward_lr, or forward_occ), the speckle filter and the weighted median, as `options` has them on (the

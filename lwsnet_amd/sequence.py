@@ -1,11 +1,13 @@
 """The stages of the inference CLI that treat the frames of directory mode as a sequence -- `--egomotion`, `--tsdf_track`,
-`--temporal`, `--tsdf` (lwsnet_amd/inference.py's docstring describes the flags) -- and the one source of their poses.
+`--movers`, `--temporal`, `--tsdf` (lwsnet_amd/inference.py's docstring describes the flags) -- and the one source of their poses.
 
 A stage is an object with four methods, and the run's stages are a tuple that inference.inference() walks with a `for`, in the
-order ego-motion (on the chain's own map), model tracking (the estimate refined against the volume), filter, volume (on what the
+order ego-motion (on the chain's own map), model tracking (the estimate refined against the volume), movers (what disagrees with
+that motion leaves the `keep` codes), filter, volume (on what the
 filter left): step(s, log) takes the record of a processed
 pair -- index, frame, res (the ChainResult), conf, and what the stages of this frame made so far: ego (the ops.EgoResult, None on a
-first frame), track (the ops.TrackResult of --tsdf_track, None on a first frame), fused (the ops.TemporalResult; res then holds the fused map in the chain's place), view (the ops.TsdfView of
+first frame), track (the ops.TrackResult of --tsdf_track, None on a first frame), movers (the ops.MoversResult of --movers, None on a frame that
+was not segmented), fused (the ops.TemporalResult; res then holds the fused map in the chain's place), view (the ops.TsdfView of
 --save_tsdf) -- and leaves what it made in it; skip(path, log) hears of a pair that was skipped; save(s, stem, log) writes the stage's own
 per-frame file beside the colour file and finish(log) the file at the end of the run, both returning the paths.  A new stage is a
 class like these, its flags' add_* / *_DEFAULTS / check_* beside it, its name in begin(), and its check called by inference.main().
@@ -112,6 +114,19 @@ def add_sequence_arguments(p):
     p.add_argument("--track_lambda", type=float, default=S, metavar="L", help="tsdf_track: the weight of the point-to-plane term, 0 switches it off (default 1)")
     p.add_argument("--track_gate", type=float, default=S, metavar="G", help="tsdf_track: the gate of the point-to-plane residual in standard deviations (default 4)")
     p.add_argument("--save_track", action="store_true", default=S, help="tsdf_track: write <stem>_track.png, the point-to-plane residual at the final pose in standard deviations, coloured")
+    p.add_argument("--movers", action="store_true", default=S,
+                   help="segment what moves between consecutive frames under the motion of --poses or --egomotion (--tsdf_track: the tracked one) "
+                        "and take it out of the `keep` codes, so that --temporal and --tsdf never fuse it (directory mode, sequential only; "
+                        "needs a camera; not in the reference)")
+    p.add_argument("--movers_gate", type=float, default=S, metavar="G", help="movers: the gate of the disparity residual in standard deviations (default 3)")
+    p.add_argument("--movers_gate_p", type=float, default=S, metavar="P", help="movers: the gate of the grey-level residual (default 25; inf switches the term off)")
+    p.add_argument("--movers_radius", type=int, default=S, metavar="R", help="movers: the window of taps in the previous frame, 0 .. 2 (default 0: one tap)")
+    p.add_argument("--movers_min_pixels", type=int, default=S, metavar="N", help="movers: the smallest component that is a mover (default 64)")
+    p.add_argument("--movers_grow", type=int, default=S, metavar="N", help="movers: pixels around a mover that leave the `keep` codes with it, 0 .. 8 (default 2)")
+    p.add_argument("--movers_uncovered", action="store_true", default=S,
+                   help="movers: uncovered pixels are candidates too -- a receding mover is then found, and so is every disocclusion")
+    p.add_argument("--save_movers", action="store_true", default=S,
+                   help="movers: write <stem>_movers.png (the evidence codes in colour, movers outlined) and <stem>_movers.csv (one line per mover)")
 
 
 TEMPORAL_DEFAULTS = dict(temporal=False, poses=None, temporal_gate=3.0, temporal_q=0.0, temporal_sigma="0.5", temporal_hold=False, save_temporal=False)
@@ -128,7 +143,7 @@ def check_temporal_arguments(p, args):
     post.set_defaults(args, **TEMPORAL_DEFAULTS)
     args.temporal = args.temporal or args.save_temporal
     if not args.temporal:
-        if given or (args.poses is not None and not getattr(args, "tsdf", False)):
+        if given or (args.poses is not None and not getattr(args, "tsdf", False) and not getattr(args, "movers", False)):
             p.error("--poses, --temporal_gate, --temporal_q, --temporal_sigma and --temporal_hold need --temporal")
         return None
     ego = bool(getattr(args, "egomotion", False))
@@ -256,6 +271,32 @@ def check_track_arguments(p, args):
     post.in_range(p.error, "--track_gate", args.track_gate, TRACK_HUBER_G, float("inf"))
 
 
+MOVERS_DEFAULTS = dict(movers=False, movers_gate=3.0, movers_gate_p=25.0, movers_radius=0, movers_min_pixels=64, movers_grow=2,
+                       movers_uncovered=False, save_movers=False)
+
+
+def check_movers_arguments(p, args):
+    """--movers, behind the checks of the other sequence flags: rejects what the segmentation does not support, before any model or
+    GPU work; sets the defaults.  Returns read_poses' where neither --temporal nor --tsdf read the file of --poses, else None."""
+    given = [f for f in MOVERS_DEFAULTS if f != "movers" and hasattr(args, f)]      # (SUPPRESS: there only if given)
+    post.set_defaults(args, **MOVERS_DEFAULTS)
+    if not args.movers:
+        if given:
+            p.error("--movers_gate, --movers_gate_p, --movers_radius, --movers_min_pixels, --movers_grow, --movers_uncovered and --save_movers need --movers")
+        return None
+    _a_sequence(p, args, "movers", "save_movers", "follows")
+    if getattr(args, "poses", None) is None and not getattr(args, "egomotion", False):
+        p.error("--movers needs the motion between the frames: --poses PATH or --egomotion")
+    post.in_range(p.error, "--movers_gate", args.movers_gate, strict=True)
+    if not args.movers_gate_p > 0:
+        p.error(f"--movers_gate_p must be > 0 (inf switches the term off), got {args.movers_gate_p}")
+    post.in_range(p.error, "--movers_radius", args.movers_radius, 0, 2)
+    post.in_range(p.error, "--movers_min_pixels", args.movers_min_pixels, 1, 2 ** 31 - 1)
+    post.in_range(p.error, "--movers_grow", args.movers_grow, 0, 8)
+    read = getattr(args, "temporal", False) or getattr(args, "tsdf", False) or getattr(args, "egomotion", False)     # an earlier check read the file, or there is none
+    return None if read else read_poses(p, args)
+
+
 class PoseSource:
     """The poses of a run's pairs.  poses: the float64 [N,3,4] of --poses, line i for pair i; None: they are estimated, and `odometry`
     is the run's egomotion.Odometry from the ego-motion stage's first frame on, its k-th pose that of the k-th pair processed; with
@@ -275,21 +316,25 @@ class PoseSource:
             return self.tracker.poses()[-1]
         return self.poses[self.seen[-1]] if self.poses is not None else self.odometry.poses()[-1]
 
-    def relative(self, s, log):
-        """TemporalFilter.step's motion from the pair processed before to the current one (the record s); None: the filter starts anew."""
+    def relative(self, s, log, warn=True):
+        """TemporalFilter.step's motion from the pair processed before to the current one (the record s); None: the filter starts anew.
+        warn=False: an untrusted motion is answered with None and no line in the log (the movers stage asks before the filter does and
+        says its own)."""
         from . import ops
         if self.poses is not None:
             from .geometry import relative_pose
             return None if len(self.seen) < 2 else relative_pose(self.poses[self.seen[-2]], self.poses[self.seen[-1]])
         if self.tracker is not None:
             if s.track is not None and int(s.track.status[0]) & ops.TRACK_UNTRUSTED:
-                log.warning("Temporal: the tracked pose of %s is not to be trusted (status %d): the filter starts anew", s.frame.path,
-                            int(s.track.status[0]))
+                if warn:
+                    log.warning("Temporal: the tracked pose of %s is not to be trusted (status %d): the filter starts anew", s.frame.path,
+                                int(s.track.status[0]))
                 return None
             return None if s.track is None else s.track.pose
         if s.ego is not None and int(s.ego.status[0]) & ops.EGO_UNTRUSTED:
-            log.warning("Temporal: the ego-motion estimate of %s is not to be trusted (status %d): the filter starts anew", s.frame.path,
-                        int(s.ego.status[0]))
+            if warn:
+                log.warning("Temporal: the ego-motion estimate of %s is not to be trusted (status %d): the filter starts anew", s.frame.path,
+                            int(s.ego.status[0]))
             return None
         return None if s.ego is None else s.ego.pose
 
@@ -388,6 +433,38 @@ class _Tracker(_Stage):
 
     def save(self, s, stem, log):
         return out.save_track(stem, s.frame, log, s.track) if self.args.save_track else []
+
+
+class _Movers(_Stage):
+    """--movers: step() segments what moved between the pair processed before and this one, on the chain's own stage-4 map and `keep`
+    codes under the source's motion, with a MoverSegmenter (made on the first frame); it leaves the ops.MoversResult in s.movers and
+    its code map in the place of the stage-4 `keep` of s.res -- a run without checks gets a `keep` where there was none -- so that
+    the filter and the volume behind it never take a mover.  A frame without a trusted motion is not segmented and keeps its codes.
+    It reads back, once, for the log."""
+    segmenter = None
+
+    def step(self, s, log):
+        import torch
+        from . import ops
+        from .movers import MoverSegmenter
+        a = self.args
+        if self.segmenter is None:
+            bits = ops.MOVER_CANDIDATES | (1 << 3 if a.movers_uncovered else 0)
+            self.segmenter = MoverSegmenter(s.frame.cam, gate_g=a.movers_gate, gate_p=a.movers_gate_p, radius=a.movers_radius,
+                                            min_pixels=a.movers_min_pixels, grow=a.movers_grow, cand_bits=bits, min_disp=a.min_disp)
+        first = self.segmenter.prev is None
+        (disp, keep), pose = _stage4(s.res), self.source.relative(s, log, warn=False)
+        with torch.cuda.device(disp.device):
+            s.movers = self.segmenter.step(out.rgb_on_device(s.frame.left, disp.device), disp, pose, mask=keep)
+        if s.movers is None:
+            if not first:
+                log.warning("Movers: %s has no trusted motion from the pair before it: the frame is not segmented", s.frame.path)
+            return
+        log.info(out.movers_line(s.movers.info[0].cpu().tolist(), s.movers.rows[0].cpu().numpy(), s.movers.vals[0].cpu().numpy()))
+        s.res = s.res.with_stage4_keep(s.movers.mask)
+
+    def save(self, s, stem, log):
+        return out.save_movers(stem, s.frame, log, s.movers) if self.args.save_movers else []
 
 
 class _Sequence(_Stage):
@@ -500,12 +577,13 @@ class _Volume(_Stage):
 def begin(args, pairs, device, log, poses=None):
     """(the PoseSource, the stages that are on, in the order they run) of a run over `pairs` pairs.  poses: what the checks read;
     a namespace that skipped the checks gets the flags' defaults and its --poses file read here."""
-    post.set_defaults(args, **TEMPORAL_DEFAULTS, **EGO_DEFAULTS, **TSDF_DEFAULTS, **TSDF_MESH_DEFAULTS, **TSDF_FOLLOW_DEFAULTS, **TRACK_DEFAULTS)
+    post.set_defaults(args, **TEMPORAL_DEFAULTS, **EGO_DEFAULTS, **TSDF_DEFAULTS, **TSDF_MESH_DEFAULTS, **TSDF_FOLLOW_DEFAULTS, **TRACK_DEFAULTS,
+                      **MOVERS_DEFAULTS)
     if poses is None and args.poses is not None and not args.egomotion:
         from .geometry import read_kitti_poses
         poses = read_kitti_poses(args.poses)
     source = PoseSource(pairs, None if args.egomotion else poses)
-    on = ((args.egomotion, _Odometry, ()), (args.tsdf_track, _Tracker, ()), (args.temporal, _Sequence, ()), (args.tsdf, _Volume, (device, log)))
+    on = ((args.egomotion, _Odometry, ()), (args.tsdf_track, _Tracker, ()), (args.movers, _Movers, ()), (args.temporal, _Sequence, ()), (args.tsdf, _Volume, (device, log)))
     stages = tuple(cls(args, source, *more) for flag, cls, more in on if flag)
     for st in stages:
         if isinstance(st, _Tracker):
