@@ -428,8 +428,6 @@ int check_hist_args(const char *who, const float *disp, int B, int H, int W, flo
     return LWS_OK;
 }
 
-constexpr int64_t round256(int64_t n) { return (n + 255) / 256 * 256; }
-
 }  // namespace
 
 }  // namespace lws

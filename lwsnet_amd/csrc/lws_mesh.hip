@@ -340,8 +340,6 @@ __global__ __launch_bounds__(kThreads) void k_mesh_scatter(const float *__restri
     }
 }
 
-constexpr int64_t round256(int64_t n) { return (n + 255) / 256 * 256; }
-
 int check_mesh_args(const char *who, const float *disp, const float *cam, int B, int H, int W, float min_disp, float max_depth,
                     float max_jump)
 {

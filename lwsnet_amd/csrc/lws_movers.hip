@@ -22,12 +22,12 @@
 //   k_mv_flags     one thread per pixel: is it a member of a mover (a byte), and its label
 //   k_mv_grow_x    the flags dilated along the row by `grow`
 //   k_mv_apply     ... and along the column: mask_out, and its pixels of code 4 added to info[7]
-// A record is 12 words: {n, x_min, x_max, y_min, y_max, n2, n3, n4, SQ (two words), the mover's number (-1: none), unused}.
-// Determinism: what crosses lanes or workgroups is an integer add, min or max, whose order cannot show; the words shared inside a
-// launch (parent[] in k_mv_border and k_mv_flatten, the records in k_mv_pixels, info[7] in k_mv_apply) are touched through relaxed
-// agent-scope atomics only, each word standing for itself; everything else crosses at kernel boundaries.  0 bytes of scratch.
-#include <climits>
-
+// A record is 12 words: the head of lws_cclkit.h {n, x_min, x_max, y_min, y_max, the mover's number (-1: none), SQ (two words)}, then
+// n2, n3, n4 and an unused word.
+// lws_cclkit.h holds the steps this labeller shares with lws_speckle.hip and lws_objects.hip -- the union-find, the tile geometry,
+// the tile-edge pairs, the flatten, the wave merge, the record's head, the numbering -- and the invariant, termination, memory-scope
+// and determinism arguments they rest on.  The words shared inside a launch here: parent[] in k_mv_border and k_mv_flatten, the
+// records in k_mv_pixels, info[7] in k_mv_apply.  0 bytes of scratch.
 #include "lwsnet_movers.h"
 
 #include "lws_cclkit.h"
@@ -46,19 +46,12 @@ using motionkit::blend;
 using motionkit::grey_rule;
 using takekit::u16f;
 constexpr int kEH = 4, kEW = 64;            // the pixels of a workgroup of k_mv_evidence: a wave is one row segment
-constexpr int kTH = 32, kTW = 64;           // the tile of k_mv_tile
-constexpr int kTile = kTH * kTW;
 constexpr int kMaxMovers = 65536;
 constexpr int kMaxRadius = 2, kMaxGrow = 8;
 constexpr int kRec = 12;                    // words per record
-constexpr int kPer = 8;                     // pixels per thread in the numbering kernels
-constexpr int kBlock = kThreads * kPer;     // ... and per workgroup
-enum { R_N = 0, R_X0, R_X1, R_Y0, R_Y1, R_N2, R_N3, R_N4, R_SQ = 8, R_NUM = 10 };
+enum { R_N2 = kHeadWords, R_N3, R_N4 };
 enum { kUntested = 0, kStatic = 1, kAppeared = 2, kUncovered = 3, kChanged = 4 };
 constexpr int kMoverCode = 4;               // mask_out's code of a mover's pixel
-
-typedef unsigned long long u64;
-typedef unsigned u32;
 
 struct Gates {
     float min_disp, sigma0, sigma_min, gate_g, gate_p;
@@ -151,21 +144,15 @@ __global__ __launch_bounds__(kThreads) void k_mv_evidence(const uint8_t *__restr
     if (t < 4) part[4 * ((int64_t)b * gridDim.x + blockIdx.x) + t] = block_total(s_n, t);
 }
 
-// joined iff |a - b| <= max_diff; a pixel that is no candidate is staged as NaN, which joins nothing
-__device__ __forceinline__ bool mv_joined(float a, float b, float max_diff) { return fabsf(a - b) <= max_diff; }
-
 // The record of a root that holds nothing yet
 __device__ __forceinline__ void rec_init(int *r)
 {
-    int4 *q = reinterpret_cast<int4 *>(r);
-    q[0] = make_int4(0, INT_MAX, -1, INT_MAX);
-    q[1] = make_int4(-1, 0, 0, 0);
-    q[2] = make_int4(0, 0, -1, 0);
+    Head::init(r);
+    reinterpret_cast<int4 *>(r)[2] = make_int4(0, 0, 0, 0);
 }
 
 // grid (ntx * nty, B), 256 threads: tile (tx, ty) of image b, 8 pixels per thread, a wave a row of the tile.  LDS 16 KiB: s_d (the
-// disparity of a candidate, NaN elsewhere and outside the image) and s_par, indexed l = 64 * (row in the tile) + (column in the
-// tile), which grows with the raster index.
+// disparity of a candidate, NaN elsewhere and outside the image) and s_par, indexed l as in lws_cclkit.h.
 __global__ __launch_bounds__(kThreads) void k_mv_tile(const float *__restrict__ disp, const uint8_t *__restrict__ evidence, int H, int W,
                                                      int ntx, unsigned cand_bits, float max_diff, int *__restrict__ parent,
                                                      int *__restrict__ rec)
@@ -174,11 +161,11 @@ __global__ __launch_bounds__(kThreads) void k_mv_tile(const float *__restrict__ 
     __shared__ int s_par[kTile];
     const int t = threadIdx.x, b = blockIdx.y;
     const int ty = blockIdx.x / ntx, tx = blockIdx.x - ty * ntx;
-    const int y0 = ty * kTH, x0 = tx * kTW;
+    const int y0 = ty * kTileRows, x0 = tx * kTileCols;
     const int64_t img = (int64_t)b * H * W;
 
     for (int l = t; l < kTile; l += kThreads) {
-        const int y = y0 + l / kTW, x = x0 + (l & (kTW - 1));
+        const int y = y0 + l / kTileCols, x = x0 + (l & (kTileCols - 1));
         float d = __builtin_nanf("");
         if (y < H && x < W) {
             const int64_t p = img + (int64_t)y * W + x;
@@ -188,176 +175,87 @@ __global__ __launch_bounds__(kThreads) void k_mv_tile(const float *__restrict__ 
         s_par[l] = l;
     }
     __syncthreads();
-    for (int l = t; l < kTile; l += kThreads) {             // the joins to the right and below, inside the tile
-        const int ry = l / kTW, rx = l & (kTW - 1);
-        const float d = s_d[l];
-        if (rx + 1 < kTW && mv_joined(d, s_d[l + 1], max_diff)) lds_unite(s_par, l, l + 1);
-        if (ry + 1 < kTH && mv_joined(d, s_d[l + kTW], max_diff)) lds_unite(s_par, l, l + kTW);
-    }
+    for (int l = t; l < kTile; l += kThreads)
+        join_right_below(s_d, s_par, l, (l & (kTileCols - 1)) + 1 < kTileCols, l / kTileCols + 1 < kTileRows, max_diff);
     __syncthreads();
     for (int l = t; l < kTile; l += kThreads) {
-        const int y = y0 + l / kTW, x = x0 + (l & (kTW - 1));
+        const int y = y0 + l / kTileCols, x = x0 + (l & (kTileCols - 1));
         if (y >= H || x >= W) continue;
         const int64_t p = img + (int64_t)y * W + x;
         int gp = -1;
         if (!__builtin_isnan(s_d[l])) {
             const int r = lds_find(s_par, l);
-            gp = (y0 + r / kTW) * W + x0 + (r & (kTW - 1));
+            gp = tile_to_index(r, y0, x0, W);
             if (r == l) rec_init(rec + p * kRec);
         }
         parent[p] = gp;
     }
 }
 
-// grid (ceil(n / 256), B), n = (nty - 1) * W + (ntx - 1) * H: thread g < (nty - 1) * W is the pair (y - 1, x), (y, x) on the top
-// edge of a tile row, the others the pair (y, x - 1), (y, x) on the left edge of a tile column (k_sp_border's pairs).  parent[] is
-// shared between workgroups here: agent-scope atomics only (g_find, g_unite).
+// grid (ceil(n / 256), B), n = (nty - 1) * W + (ntx - 1) * H: one thread per pair of pixels across a tile edge (lws_cclkit.h)
 __global__ __launch_bounds__(kThreads) void k_mv_border(const float *__restrict__ disp, int H, int W, int nty, int ntx, float max_diff,
                                                        int *__restrict__ parent)
 {
-    const int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    const int64_t nh = (int64_t)(nty - 1) * W, nv = (int64_t)(ntx - 1) * H;
-    if (g >= nh + nv) return;
-    const int64_t img = (int64_t)blockIdx.y * H * W;
-    int p, q;
-    if (g < nh) {
-        const int e = (int)(g / W), x = (int)(g - (int64_t)e * W), y = (e + 1) * kTH;
-        q = y * W + x;
-        p = q - W;
-    } else {
-        const int64_t v = g - nh;
-        const int e = (int)(v / H), y = (int)(v - (int64_t)e * H), x = (e + 1) * kTW;
-        q = y * W + x;
-        p = q - 1;
-    }
-    int *par = parent + img;
-    if (ld_agent(par + p) < 0 || ld_agent(par + q) < 0) return;     // the sign of a parent word never changes
-    if (mv_joined(disp[img + p], disp[img + q], max_diff)) g_unite(par, p, q);
+    unite_tile_edges(disp, H, W, nty, ntx, max_diff, parent);
 }
 
-// grid (ceil(HW / 256), B): one thread per pixel.  No union runs in this launch, so a root stays a root: every candidate finds it
-// and points at it (an atomic min: r <= parent[p], the invariant holds).  Afterwards parent[p] is the component's first pixel.
-__global__ __launch_bounds__(kThreads) void k_mv_flatten(int HW, int *__restrict__ parent)
-{
-    const int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (g >= HW) return;
-    const int p = (int)g;
-    int *par = parent + (int64_t)blockIdx.y * HW;
-    if (ld_agent(par + p) < 0) return;
-    const int r = g_find(par, p);
-    if (r != p) __hip_atomic_fetch_min(par + p, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// grid (ceil(HW / 256), B): one thread per pixel; afterwards parent[p] is the component's first pixel (lws_cclkit.h)
+__global__ __launch_bounds__(kThreads) void k_mv_flatten(int HW, int *__restrict__ parent) { flatten_elements(HW, parent); }
 
 // What a set of member pixels adds to a record
 struct Acc {
-    int n, x0, x1, y0, y1, n2, n3, n4;
-    u64 sq;
+    Head h;
+    int n2, n3, n4;
+
+    static __device__ __forceinline__ Acc none() { return Acc{Head::none(), 0, 0, 0}; }
+    __device__ __forceinline__ void merge(const Acc &b) { h.merge(b.h), n2 += b.n2, n3 += b.n3, n4 += b.n4; }
+    __device__ __forceinline__ Acc lane_xor(int o) const { return Acc{h.lane_xor(o), __shfl_xor(n2, o, 64), __shfl_xor(n3, o, 64), __shfl_xor(n4, o, 64)}; }
+    // into the record of root `root` of the image's records: integer atomics only
+    __device__ __forceinline__ void add_to(int *rec, int root) const
+    {
+        int *r = rec + (int64_t)root * kRec;
+        h.add_to(r);
+        if (n2) a_add(r + R_N2, n2);
+        if (n3) a_add(r + R_N3, n3);
+        if (n4) a_add(r + R_N4, n4);
+    }
 };
 
-__device__ __forceinline__ Acc acc_none() { return Acc{0, INT_MAX, -1, INT_MAX, -1, 0, 0, 0, 0ull}; }
-
-__device__ __forceinline__ void acc_merge(Acc &a, const Acc &b)
-{
-    a.n += b.n, a.n2 += b.n2, a.n3 += b.n3, a.n4 += b.n4, a.sq += b.sq;
-    a.x0 = min(a.x0, b.x0), a.x1 = max(a.x1, b.x1), a.y0 = min(a.y0, b.y0), a.y1 = max(a.y1, b.y1);
-}
-
-template <typename T>
-__device__ __forceinline__ void a_add(T *p, T v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void a_min(int *p, int v) { __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void a_max(int *p, int v) { __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// a into the record r: integer atomics only
-__device__ __forceinline__ void rec_add(int *r, const Acc &a)
-{
-    a_add(r + R_N, a.n);
-    a_min(r + R_X0, a.x0), a_max(r + R_X1, a.x1), a_min(r + R_Y0, a.y0), a_max(r + R_Y1, a.y1);
-    if (a.n2) a_add(r + R_N2, a.n2);
-    if (a.n3) a_add(r + R_N3, a.n3);
-    if (a.n4) a_add(r + R_N4, a.n4);
-    a_add(reinterpret_cast<u64 *>(r + R_SQ), a.sq);
-}
-
-// grid (ceil(HW / 256), B): one thread per pixel, whole waves (they shuffle).  The lanes of the wave that share the root of its
-// first candidate are merged through a butterfly and that lane adds the result to the root's record; every other candidate adds for
-// itself -- as k_ob_pixels flushes its cells.  A wave inside one mover costs one set of atomics.
+// grid (ceil(HW / 256), B): one thread per pixel, whole waves (cclkit::wave_add shuffles): every candidate into its root's record.
+// A wave inside one mover costs one set of atomics.
 __global__ __launch_bounds__(kThreads) void k_mv_pixels(const float *__restrict__ disp, const uint8_t *__restrict__ evidence, int HW, int W,
                                                        const int *__restrict__ parent, int *__restrict__ rec)
 {
     const int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     const int64_t img = (int64_t)blockIdx.y * HW;
-    const int lane = threadIdx.x & 63;
     int root = -1;
-    Acc a = acc_none();
+    Acc a = Acc::none();
     if (g < HW) {
         const int p = (int)g;
         root = parent[img + p];
         if (root >= 0) {
             const int y = p / W, x = p - y * W, code = evidence[img + p];
-            a = Acc{1, x, x, y, y, code == kAppeared, code == kUncovered, code == kChanged, (u64)(int)u16f(disp[img + p])};
+            a = Acc{Head::pixel(x, y, (u64)(int)u16f(disp[img + p])), code == kAppeared, code == kUncovered, code == kChanged};
         }
     }
-    const u64 pend = __ballot(root >= 0);
-    if (pend == 0) return;                                  // (wave-uniform)
-    const int lead = __ffsll((long long)pend) - 1;
-    const int r0 = __shfl(root, lead, 64);
-    const bool mine = root == r0;
-    Acc r = mine ? a : acc_none();                          // (the other lanes: the identity in the butterfly)
-    if (__popcll(__ballot(mine)) > 1) {                     // (wave-uniform)
-        for (int o = 32; o > 0; o >>= 1) {
-            Acc v;
-            v.n = __shfl_xor(r.n, o, 64), v.sq = __shfl_xor(r.sq, o, 64);
-            v.x0 = __shfl_xor(r.x0, o, 64), v.x1 = __shfl_xor(r.x1, o, 64), v.y0 = __shfl_xor(r.y0, o, 64), v.y1 = __shfl_xor(r.y1, o, 64);
-            v.n2 = __shfl_xor(r.n2, o, 64), v.n3 = __shfl_xor(r.n3, o, 64), v.n4 = __shfl_xor(r.n4, o, 64);
-            acc_merge(r, v);
-        }
-    }
-    int *r_img = rec + img * kRec;
-    if (lane == lead) rec_add(r_img + (int64_t)r0 * kRec, r);
-    else if (root >= 0 && !mine) rec_add(r_img + (int64_t)root * kRec, a);
+    wave_add(a, root, rec + img * kRec);
 }
 
-// The eight consecutive pixels cb .. cb + 7 of a thread: bit i of the result is set iff pixel cb + i is a mover's root (its
-// component's first pixel, n >= min_pixels).  components, if given, gains the roots among them.
-__device__ __forceinline__ unsigned mover_roots(const int *__restrict__ par, const int *__restrict__ r_img, int64_t cb, int HW, int min_pixels,
-                                                int *components)
-{
-    unsigned keep = 0u;
-#pragma unroll
-    for (int i = 0; i < kPer; ++i) {
-        const int64_t c = cb + i;
-        if (c >= HW || par[c] != (int)c) continue;
-        if (components) *components += 1;
-        if (r_img[c * kRec + R_N] >= min_pixels) keep |= 1u << i;
-    }
-    return keep;
-}
-
-// The numbering is the three-launch scan of lws_point_cloud over the pixels in raster order, in blocks of 2048 pixels (8 consecutive
-// pixels per thread): per-block counts, a per-image exclusive scan of them, a ranked write.
+// The numbering (lws_cclkit.h) over the pixels in raster order; a kept root is a mover's.
 // grid (nblk, B), 256 threads: cnt[b][blk] = {movers' roots, components} of the block.
 __global__ __launch_bounds__(kThreads) void k_mv_count(const int *__restrict__ parent, const int *__restrict__ rec, int HW, int min_pixels,
                                                       int *__restrict__ cnt)
 {
     __shared__ int s_n[kWaves][2];
     const int blk = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
-    int sums[2] = {0, 0};
-    sums[0] = __popc(mover_roots(parent + (int64_t)b * HW, rec + (int64_t)b * HW * kRec, ((int64_t)blk * kThreads + t) * kPer, HW, min_pixels,
-                                 sums + 1));
+    const Kept k = kept_roots<kRec>(parent + (int64_t)b * HW, rec + (int64_t)b * HW * kRec, ((int64_t)blk * kThreads + t) * kPer, HW, min_pixels);
+    int sums[2] = {(int)__popc(k.bits), k.roots};
     block_sum_n(sums, s_n);
     if (t < 2) cnt[2 * ((int64_t)b * gridDim.x + blk) + t] = block_total(s_n, t);
 }
 
-__device__ __forceinline__ void store_mover(int32_t *__restrict__ rows, float *__restrict__ vals, const int r[8], float d, float z)
-{
-#pragma unroll
-    for (int i = 0; i < 8; ++i) rows[i] = r[i];
-    vals[0] = d, vals[1] = z;
-}
-
-// grid (B), 256 threads: cnt[b][blk][0] becomes the movers before the block (an exclusive scan over the image's blocks, 256 a
-// round); the slots of rows / vals past the movers, which k_mv_write does not touch; and info, with info[7] = 0 for k_mv_apply to
-// add to.  part: k_mv_evidence's counts, npart workgroups per image.
+// grid (B), 256 threads: cnt[b][blk][0] becomes the movers before the block; the slots of rows / vals past the movers; and info,
+// with info[7] = 0 for k_mv_apply to add to.  part: k_mv_evidence's counts, npart workgroups per image.
 __global__ __launch_bounds__(kThreads) void k_mv_scan(int *__restrict__ cnt, int nblk, const int *__restrict__ part, int npart, int max_movers,
                                                      int32_t *__restrict__ rows, float *__restrict__ vals, int32_t *__restrict__ info)
 {
@@ -366,34 +264,22 @@ __global__ __launch_bounds__(kThreads) void k_mv_scan(int *__restrict__ cnt, int
     const int b = blockIdx.x, t = threadIdx.x;
     int *c = cnt + 2 * (int64_t)b * nblk;
     const int *e = part + 4 * (int64_t)b * npart;
-    int before = 0, sums[5] = {0, 0, 0, 0, 0};              // components, then the pixels of evidence 1 .. 4
-    for (int i0 = 0; i0 < nblk; i0 += kThreads) {
-        const int i = i0 + t;
-        const int at = block_scan(i < nblk ? c[2 * i] : 0, s_w, before);
-        if (i < nblk) {
-            c[2 * i] = at;
-            sums[0] += c[2 * i + 1];
-        }
-        __syncthreads();                                    // s_w is rewritten by the next round
-    }
+    int sums[5] = {0, 0, 0, 0, 0};                          // components, then the pixels of evidence 1 .. 4
+    const int movers = scan_blocks(c, 2, nblk, s_w, [&](int i) { sums[0] += c[2 * i + 1]; });
     for (int i = t; i < npart; i += kThreads)
         for (int j = 0; j < 4; ++j) sums[1 + j] += e[4 * (int64_t)i + j];
-    const int none[8] = {0, -1, -1, -1, -1, -1, -1, 0};
-    int32_t *orow = rows + (int64_t)b * max_movers * 8;
-    float *oval = vals + (int64_t)b * max_movers * 2;
-    for (int j = min(before, max_movers) + t; j < max_movers; j += kThreads) store_mover(orow + 8 * (int64_t)j, oval + 2 * (int64_t)j, none, 0.0f, 0.0f);
+    clear_slots<2>(rows + (int64_t)b * max_movers * 8, vals + (int64_t)b * max_movers * 2, movers, max_movers);
     block_sum_n(sums, s_n);
     if (t == 0) {
         int32_t *o = info + 8 * (int64_t)b;
         const int n1 = block_total(s_n, 1), n2 = block_total(s_n, 2), n3 = block_total(s_n, 3), n4 = block_total(s_n, 4);
         o[0] = (n1 + n2) + (n3 + n4), o[1] = n1, o[2] = n2, o[3] = n3, o[4] = n4;
-        o[5] = block_total(s_n, 0), o[6] = before, o[7] = 0;
+        o[5] = block_total(s_n, 0), o[6] = movers, o[7] = 0;
     }
 }
 
-// grid (nblk, B), 256 threads: a mover's number is the movers before its block plus those before it inside the block; below
-// max_movers its slot of rows / vals is written and its record gets the number for k_mv_flags.  Every other root's record holds
-// -1 since k_mv_tile.
+// grid (nblk, B), 256 threads: below max_movers a mover's slot of rows / vals is written and its record gets the number for
+// k_mv_flags.  Every other root's record holds -1 since k_mv_tile.
 __global__ __launch_bounds__(kThreads) void k_mv_write(const int *__restrict__ parent, int *__restrict__ rec, const float *__restrict__ cam,
                                                       const int *__restrict__ cnt, int HW, int min_pixels, int max_movers,
                                                       int32_t *__restrict__ rows, float *__restrict__ vals)
@@ -405,22 +291,17 @@ __global__ __launch_bounds__(kThreads) void k_mv_write(const int *__restrict__ p
     float *oval = vals + (int64_t)b * max_movers * 2;
     const float fb = load_cam(cam, b).fb;
     const int64_t cb = ((int64_t)blk * kThreads + t) * kPer;
-    const unsigned keep = mover_roots(parent + (int64_t)b * HW, r_img, cb, HW, min_pixels, nullptr);
-    int before = cnt[2 * ((int64_t)b * gridDim.x + blk)];
-    int j = block_scan((int)__popc(keep), s_w, before);
-    for (int i = 0; i < kPer; ++i) {
-        if (!((keep >> i) & 1u)) continue;
+    const unsigned keep = kept_roots<kRec>(parent + (int64_t)b * HW, r_img, cb, HW, min_pixels).bits;
+    for_each_kept(keep, cnt[2 * ((int64_t)b * gridDim.x + blk)], s_w, [&](int i, int j) {
+        if (j >= max_movers) return;
         int *r = r_img + (cb + i) * kRec;
-        if (j < max_movers) {
-            const int n = r[R_N];
-            const u64 sq = *reinterpret_cast<const u64 *>(r + R_SQ);
-            const float d = (float)(((double)sq / (double)n) / 256.0);
-            const int ri[8] = {n, r[R_X0], r[R_X1], r[R_Y0], r[R_Y1], r[R_N2], r[R_N3], r[R_N4]};
-            store_mover(orow + 8 * (int64_t)j, oval + 2 * (int64_t)j, ri, d, fb / d);
-            r[R_NUM] = j;
-        }
-        ++j;
-    }
+        const Head h = Head::load(r);
+        const float d = h.mean_disp();
+        const int ri[8] = {h.n, h.x0, h.x1, h.y0, h.y1, r[R_N2], r[R_N3], r[R_N4]};
+        const float vf[2] = {d, fb / d};
+        store_slot(orow, oval, j, ri, vf);
+        r[H_NUM] = j;
+    });
 }
 
 // grid (ceil(HW / 256), B): one thread per pixel: flag[p] = 1 iff p is a member of a mover, capped or not; labels (if given) = the
@@ -433,9 +314,9 @@ __global__ __launch_bounds__(kThreads) void k_mv_flags(int HW, const int *__rest
     const int64_t img = (int64_t)blockIdx.y * HW;
     const int root = parent[img + g];
     const int *r = rec + (img + (root < 0 ? 0 : root)) * kRec;
-    const bool mover = root >= 0 && r[R_N] >= min_pixels;
+    const bool mover = root >= 0 && r[H_N] >= min_pixels;
     flag[img + g] = mover ? 1 : 0;
-    if (labels) labels[img + g] = mover ? r[R_NUM] : -1;
+    if (labels) labels[img + g] = mover ? r[H_NUM] : -1;
 }
 
 // grid (ceil(HW / 256), B): out[y, x] = 1 iff in[y, x - grow .. x + grow] holds a 1 inside the row
@@ -473,8 +354,6 @@ __global__ __launch_bounds__(kThreads) void k_mv_apply(int HW, int W, int grow, 
     const int n = block_sum(any, s_n);
     if (threadIdx.x == 0 && n > 0) a_add(info + 8 * (int64_t)blockIdx.y + 7, n);
 }
-
-constexpr int64_t round256(int64_t n) { return (n + 255) / 256 * 256; }
 
 struct Layout {                             // the parts of the workspace, in bytes from its start
     int64_t parent, rec, flag, flag_x, part, cnt, end;
@@ -558,7 +437,7 @@ int lws_movers(const uint8_t *rgb_prev, const float *disp_prev, const float *sig
     uint8_t *flag = reinterpret_cast<uint8_t *>(ws + l.flag), *flag_x = reinterpret_cast<uint8_t *>(ws + l.flag_x);
     int *part = reinterpret_cast<int *>(ws + l.part), *cnt = reinterpret_cast<int *>(ws + l.cnt);
     const int HW = H * W, npart = l.nbx * l.nby;
-    const int ntx = (W + kTW - 1) / kTW, nty = (H + kTH - 1) / kTH;
+    const int ntx = (W + kTileCols - 1) / kTileCols, nty = (H + kTileRows - 1) / kTileRows;
     const int64_t pairs = (int64_t)(nty - 1) * W + (int64_t)(ntx - 1) * H;
     const unsigned per_pixel = (unsigned)(((int64_t)HW + kThreads - 1) / kThreads);
     const Gates g = {min_disp, sigma0, sigma_min, gate_g, gate_p, radius};

@@ -18,14 +18,12 @@
 //   k_ob_scan     of 2048 cells, a per-image exclusive scan of the blocks' counts with info and the empty slots, and the ranked
 //   k_ob_write    write of rows / vals and of the number into the root's record
 //   k_ob_labels   (labels != NULL) one workgroup per strip and image: the object's number per pixel
-// A record is 16 words: {n, x_min, x_max, y_min, y_max, other cells, SQ (two words), the ordered keys of X_min, X_max, Y_min,
-// Y_max, Z_min, Z_max, the largest row kr, the object's number (-1: none)}.
-// Determinism: what crosses lanes or workgroups is an integer add, min or max (the floats as ordered keys), whose order cannot
-// show; the words shared inside a launch (parent[] in k_ob_border and k_ob_flatten, the records in k_ob_pixels and k_ob_cells) are
-// touched through relaxed agent-scope atomics only, each word standing for itself; everything else crosses at kernel boundaries.
-// 0 bytes of scratch.
-#include <climits>
-
+// A record is 16 words: the head of lws_cclkit.h {n, x_min, x_max, y_min, y_max, the object's number (-1: none), SQ (two words)}, the
+// ordered keys of X_min, X_max, Y_min, Y_max, Z_min, Z_max, the largest row kr, the other cells.
+// lws_cclkit.h holds the steps this labeller shares with lws_speckle.hip and lws_movers.hip -- the union-find, the tile geometry, the
+// flatten, the wave merge, the record's head, the numbering -- and the invariant, termination, memory-scope and determinism arguments
+// they rest on (the floats cross lanes and workgroups as ordered keys: integers too).  The words shared inside a launch here:
+// parent[] in k_ob_border and k_ob_flatten, the records in k_ob_pixels and k_ob_cells.  0 bytes of scratch.
 #include "lwsnet_objects.h"
 
 #include "lws_cclkit.h"
@@ -41,66 +39,53 @@ using namespace geomkit;
 using namespace takekit;                    // the limits, Item / load_item, Rule / bin_of, u16f
 using namespace cclkit;
 using namespace packkit;                    // kThreads, kWaves, block_scan
-constexpr int kTK = 32, kTS = 64;           // the tile of k_ob_tile: rows (bins) x columns (strips)
-constexpr int kTile = kTK * kTS;
+constexpr int kTK = 32, kTS = 64;           // the tile of k_ob_tile: rows (bins) x columns (strips); tests/test_objects_cpu.py reads this line
+static_assert(kTK == kTileRows && kTS == kTileCols, "the cell tile is the labellers' tile (lws_cclkit.h)");
 constexpr int kMaxCells = 1 << 22;          // S * nbins: the workspace stays below 286 MB per image
 constexpr int kMaxObjects = 65536;
 constexpr int kRec = 16;                    // words per record
-constexpr int kPer = 8;                     // cells per thread in the numbering kernels
-constexpr int kBlock = kThreads * kPer;     // ... and per workgroup
-enum { R_N = 0, R_X0, R_X1, R_Y0, R_Y1, R_CELLS, R_SQ, R_KEY = 8, R_KR = 14, R_NUM = 15 };
-
-typedef unsigned long long u64;
-typedef unsigned u32;
+enum { R_KEY = kHeadWords, R_KR = 14, R_CELLS = 15 };
 
 // What a set of member pixels adds to a record.  key[]: X_min, X_max, Y_min, Y_max, Z_min, Z_max as opkit::key_of words (no NaN comes here)
 struct Acc {
-    u32 n;
-    int x0, x1, y0, y1;
-    u64 sq;
+    Head h;
     u32 key[6];
+
+    static __device__ __forceinline__ Acc none() { return Acc{Head::none(), {~0u, 0u, ~0u, 0u, ~0u, 0u}}; }
+    __device__ __forceinline__ void merge(const Acc &b)
+    {
+        h.merge(b.h);
+#pragma unroll
+        for (int i = 0; i < 6; i += 2) key[i] = min(key[i], b.key[i]), key[i + 1] = max(key[i + 1], b.key[i + 1]);
+    }
+    __device__ __forceinline__ Acc lane_xor(int o) const
+    {
+        Acc v = {h.lane_xor(o), {}};
+#pragma unroll
+        for (int i = 0; i < 6; ++i) v.key[i] = __shfl_xor(key[i], o, 64);
+        return v;
+    }
+    // into the record of cell `cell` of the image's records: integer atomics only
+    __device__ __forceinline__ void add_to(u32 *rec, int cell) const
+    {
+        u32 *r = rec + (int64_t)cell * kRec;
+        h.add_to(reinterpret_cast<int *>(r));
+#pragma unroll
+        for (int i = 0; i < 6; i += 2) a_min(r + R_KEY + i, key[i]), a_max(r + R_KEY + i + 1, key[i + 1]);
+    }
 };
-
-__device__ __forceinline__ Acc acc_none() { return Acc{0u, INT_MAX, -1, INT_MAX, -1, 0ull, {~0u, 0u, ~0u, 0u, ~0u, 0u}}; }
-
-__device__ __forceinline__ void acc_merge(Acc &a, const Acc &b)
-{
-    a.n += b.n, a.sq += b.sq;
-    a.x0 = min(a.x0, b.x0), a.x1 = max(a.x1, b.x1), a.y0 = min(a.y0, b.y0), a.y1 = max(a.y1, b.y1);
-#pragma unroll
-    for (int i = 0; i < 6; i += 2) a.key[i] = min(a.key[i], b.key[i]), a.key[i + 1] = max(a.key[i + 1], b.key[i + 1]);
-}
-
-template <typename T>
-__device__ __forceinline__ void a_add(T *p, T v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <typename T>
-__device__ __forceinline__ void a_min(T *p, T v) { __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <typename T>
-__device__ __forceinline__ void a_max(T *p, T v) { __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// a into the record r: integer atomics only
-__device__ __forceinline__ void rec_add(u32 *r, const Acc &a)
-{
-    int *ri = reinterpret_cast<int *>(r);
-    a_add(r + R_N, a.n);
-    a_min(ri + R_X0, a.x0), a_max(ri + R_X1, a.x1), a_min(ri + R_Y0, a.y0), a_max(ri + R_Y1, a.y1);
-    a_add(reinterpret_cast<u64 *>(r + R_SQ), a.sq);
-#pragma unroll
-    for (int i = 0; i < 6; i += 2) a_min(r + R_KEY + i, a.key[i]), a_max(r + R_KEY + i + 1, a.key[i + 1]);
-}
 
 // The record of a cell in row kr that holds nothing yet
 __device__ __forceinline__ void rec_init(u32 *r, int kr)
 {
+    Head::init(reinterpret_cast<int *>(r));
     int4 *q = reinterpret_cast<int4 *>(r);
-    q[0] = make_int4(0, INT_MAX, -1, INT_MAX);
-    q[1] = make_int4(-1, 0, 0, 0);
     q[2] = make_int4(-1, 0, -1, 0);
-    q[3] = make_int4(-1, 0, kr, -1);
+    q[3] = make_int4(-1, 0, kr, 0);
 }
 
 // grid (ntk * nts, B), 256 threads: the tile (tk, ts) of image b, 8 cells per thread.  LDS 16 KiB: s_occ, s_par, indexed
-// l = 64 * (row in the tile) + (column in the tile), which grows with c.  udisp is read with the bins along the threads.
+// l as in lws_cclkit.h, which grows with c.  udisp is read with the bins along the threads.
 __global__ __launch_bounds__(kThreads) void k_ob_tile(const uint32_t *__restrict__ udisp, int S, int nbins, int nts, unsigned min_count,
                                                      int *__restrict__ parent, u32 *__restrict__ rec)
 {
@@ -137,8 +122,7 @@ __global__ __launch_bounds__(kThreads) void k_ob_tile(const uint32_t *__restrict
         const int c = kr * S + s;
         int p = -1;
         if (s_occ[l]) {
-            const int r = lds_find(s_par, l);
-            p = (kr0 + r / kTS) * S + s0 + (r & (kTS - 1));
+            p = tile_to_index(lds_find(s_par, l), kr0, s0, S);
             rec_init(rec + (cells + c) * kRec, kr);
         }
         parent[cells + c] = p;
@@ -148,7 +132,7 @@ __global__ __launch_bounds__(kThreads) void k_ob_tile(const uint32_t *__restrict
 // grid (ceil(n / 256), B), n = (ntk - 1) * S + (nts - 1) * nbins: thread g < (ntk - 1) * S is the cell (kr, s) on the first row of
 // a tile row, joined with (kr - 1, s - 1 .. s + 1); the others the cell (kr, s) on the first column of a tile column, joined with
 // (kr - 1 .. kr + 1, s - 1).  Together: every pair of neighbours in different tiles (some twice, which a union does not mind).
-// parent[] is shared between workgroups here: agent-scope atomics only (g_find, g_unite).
+// parent[] is shared between workgroups here (g_find, g_unite); the sign of a parent word never changes (lws_cclkit.h).
 __global__ __launch_bounds__(kThreads) void k_ob_border(int S, int nbins, int ntk, int nts, int *__restrict__ parent)
 {
     const int g = blockIdx.x * kThreads + threadIdx.x;
@@ -164,7 +148,7 @@ __global__ __launch_bounds__(kThreads) void k_ob_border(int S, int nbins, int nt
         kr = v - e * nbins, s = (e + 1) * kTS, dk = 1, ds = 0;      // (kr - 1 + j, s - 1)
     }
     const int q = kr * S + s;
-    if (ld_agent(par + q) < 0) return;                      // the sign of a parent word never changes
+    if (ld_agent(par + q) < 0) return;
     for (int j = 0; j < 3; ++j) {
         const int nk = kr - 1 + dk * j, ns = s - 1 + ds * j;
         if (nk < 0 || nk >= nbins || ns < 0 || ns >= S) continue;
@@ -173,44 +157,8 @@ __global__ __launch_bounds__(kThreads) void k_ob_border(int S, int nbins, int nt
     }
 }
 
-// grid (ceil(N / 256), B): one thread per cell.  No union runs in this launch, so a root stays a root: every occupied cell finds
-// it and points at it (an atomic min: r <= parent[c], the invariant holds).  Afterwards parent[c] is the component's smallest c.
-__global__ __launch_bounds__(kThreads) void k_ob_flatten(int N, int *__restrict__ parent)
-{
-    const int c = blockIdx.x * kThreads + threadIdx.x;
-    if (c >= N) return;
-    int *par = parent + (int64_t)blockIdx.y * N;
-    if (ld_agent(par + c) < 0) return;
-    const int r = g_find(par, c);
-    if (r != c) __hip_atomic_fetch_min(par + c, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The lanes of the wave that share the cell of its first lane with one (>= 0) are merged through a butterfly and that lane adds
-// the result to the cell's record; every other lane with a cell adds for itself -- as k_sp_tile counts its sizes.  A wave inside one
-// fronto-parallel obstacle costs one set of atomics; a wave over scattered cells meets no contention to begin with, and pays no
-// butterfly when its first cell is one lane's alone.  Every lane of the wave must call (cell < 0: nothing to add).
-__device__ __forceinline__ void wave_flush(const Acc &a, int cell, u32 *__restrict__ rec)
-{
-    const int lane = threadIdx.x & 63;
-    const u64 pend = __ballot(cell >= 0);
-    if (pend == 0) return;                                  // (wave-uniform)
-    const int lead = __ffsll((long long)pend) - 1;
-    const int c0 = __shfl(cell, lead, 64);
-    const bool mine = cell == c0;
-    Acc r = mine ? a : acc_none();                          // (the other lanes: the identity in the butterfly)
-    if (__popcll(__ballot(mine)) > 1) {                     // (wave-uniform)
-        for (int o = 32; o > 0; o >>= 1) {
-            Acc v;
-            v.n = __shfl_xor(r.n, o, 64), v.sq = __shfl_xor(r.sq, o, 64);
-            v.x0 = __shfl_xor(r.x0, o, 64), v.x1 = __shfl_xor(r.x1, o, 64), v.y0 = __shfl_xor(r.y0, o, 64), v.y1 = __shfl_xor(r.y1, o, 64);
-#pragma unroll
-            for (int i = 0; i < 6; ++i) v.key[i] = __shfl_xor(r.key[i], o, 64);
-            acc_merge(r, v);
-        }
-    }
-    if (lane == lead) rec_add(rec + (int64_t)c0 * kRec, r);
-    else if (cell >= 0 && !mine) rec_add(rec + (int64_t)cell * kRec, a);
-}
+// grid (ceil(N / 256), B): one thread per cell; afterwards parent[c] is the component's smallest c (lws_cclkit.h)
+__global__ __launch_bounds__(kThreads) void k_ob_flatten(int N, int *__restrict__ parent) { flatten_elements(N, parent); }
 
 // The occupied bins of strip s as a bit mask in LDS (s_occ: kMaxBins / 32 words); a barrier before it is read
 __device__ __forceinline__ void stage_occupied(const uint32_t *__restrict__ u, int nbins, unsigned min_count, u32 *s_occ)
@@ -224,7 +172,7 @@ __device__ __forceinline__ void stage_occupied(const uint32_t *__restrict__ u, i
 
 // grid (S, B), 256 threads: the strip blockIdx.x of image blockIdx.y, read as k_stixels reads it.  A member pixel -- it takes part
 // and its cell (s, q) is occupied -- goes into its cell's record: the runs of equal bins of an item first, then the lanes of the
-// wave with the same cell (wave_flush).  A cell belongs to one strip, hence to this workgroup alone.
+// wave with the same cell (cclkit::wave_add).  A cell belongs to one strip, hence to this workgroup alone.
 __global__ __launch_bounds__(kThreads) void k_ob_pixels(const float *__restrict__ disp, const float *__restrict__ cam,
                                                        const uint8_t *__restrict__ codes, const uint32_t *__restrict__ udisp, int H, int W,
                                                        float min_disp, float max_depth, unsigned code_bits, int width, int sub, int nbins,
@@ -241,9 +189,9 @@ __global__ __launch_bounds__(kThreads) void k_ob_pixels(const float *__restrict_
 
     stage_occupied(udisp + ((int64_t)b * S + s) * nbins, nbins, min_count, s_occ);
     __syncthreads();
-    for (int i0 = 0; i0 < items; i0 += kThreads) {          // (whole waves go round: wave_flush shuffles)
+    for (int i0 = 0; i0 < items; i0 += kThreads) {          // (whole waves go round: wave_add shuffles)
         const int i = i0 + t;
-        Acc a[4] = {acc_none(), acc_none(), acc_none(), acc_none()};
+        Acc a[4] = {Acc::none(), Acc::none(), Acc::none(), Acc::none()};
         int cell[4] = {-1, -1, -1, -1};
         if (i < items) {
             const int y = i / nc, xs = 4 * (i - y * nc);
@@ -257,16 +205,16 @@ __global__ __launch_bounds__(kThreads) void k_ob_pixels(const float *__restrict_
                 const float z = c.fb / it.d[j];
                 const float X = back_x(c, x, z), Y = back_y(c, y, z);
                 const u32 kx = key_of(X), ky = key_of(Y), kz = key_of(z);
-                a[j] = Acc{1u, x, x, y, y, (u64)(int)u16f(it.d[j]), {kx, kx, ky, ky, kz, kz}};
+                a[j] = Acc{Head::pixel(x, y, (u64)(int)u16f(it.d[j])), {kx, kx, ky, ky, kz, kz}};
                 cell[j] = (nbins - 1 - q) * S + s;
             }
             // a fronto-parallel obstacle puts its pixels into few bins: the runs of equal cells of an item go on as one
 #pragma unroll
             for (int j = 1; j < 4; ++j)
-                if (cell[j] >= 0 && cell[j] == cell[j - 1]) acc_merge(a[j], a[j - 1]), cell[j - 1] = -1;
+                if (cell[j] >= 0 && cell[j] == cell[j - 1]) a[j].merge(a[j - 1]), cell[j - 1] = -1;
         }
 #pragma unroll
-        for (int j = 0; j < 4; ++j) wave_flush(a[j], cell[j], r_img);
+        for (int j = 0; j < 4; ++j) wave_add(a[j], cell[j], r_img);
     }
 }
 
@@ -281,91 +229,50 @@ __global__ __launch_bounds__(kThreads) void k_ob_cells(int N, const int *__restr
     if (p < 0 || p == c) return;
     const u32 *m = rec + (cells + c) * kRec;
     u32 *r = rec + (cells + p) * kRec;
-    Acc a;
-    a.n = m[R_N], a.x0 = (int)m[R_X0], a.x1 = (int)m[R_X1], a.y0 = (int)m[R_Y0], a.y1 = (int)m[R_Y1];
-    a.sq = *reinterpret_cast<const u64 *>(m + R_SQ);
+    Acc a = {Head::load(reinterpret_cast<const int *>(m)), {}};
 #pragma unroll
     for (int i = 0; i < 6; ++i) a.key[i] = m[R_KEY + i];
-    rec_add(r, a);
+    a.add_to(rec + cells * kRec, p);
     a_add(r + R_CELLS, 1u);
     a_max(reinterpret_cast<int *>(r) + R_KR, (int)m[R_KR]);
 }
 
-__device__ __forceinline__ void store_object(int32_t *__restrict__ rows, float *__restrict__ vals, const int r[8], const float v[8])
-{
-#pragma unroll
-    for (int i = 0; i < 8; ++i) rows[i] = r[i], vals[i] = v[i];
-}
-
-// The eight consecutive cells cb .. cb + 7 of a thread: bit i of the result is set iff cell cb + i is a kept root (its component's
-// root, n >= min_pixels).  sums, if given, gains {occupied cells, components, member pixels of the kept ones}.
-__device__ __forceinline__ unsigned kept_roots(const int *__restrict__ par, const u32 *__restrict__ r_img, int cb, int N, int min_pixels,
-                                               int *sums)
-{
-    unsigned keep = 0u;
-#pragma unroll
-    for (int i = 0; i < kPer; ++i) {
-        const int c = cb + i;
-        const int p = c < N ? par[c] : -1;
-        if (sums) sums[0] += p >= 0, sums[1] += p == c;
-        if (p != c) continue;
-        const int n = (int)r_img[(int64_t)c * kRec + R_N];
-        if (n >= min_pixels) {
-            keep |= 1u << i;
-            if (sums) sums[2] += n;
-        }
-    }
-    return keep;
-}
-
-// The numbering is the three-launch scan of lws_point_cloud over the cells in c order, in blocks of 2048 cells (8 consecutive cells
-// per thread): per-block counts, a per-image exclusive scan of them, a ranked write.
+// The numbering (lws_cclkit.h) over the cells in c order.
 // grid (nblk, B), 256 threads: cnt[b][blk] = {kept roots, occupied cells, components, member pixels of the kept roots} of the block.
 __global__ __launch_bounds__(kThreads) void k_ob_count(const int *__restrict__ parent, const u32 *__restrict__ rec, int N, int min_pixels,
                                                       int *__restrict__ cnt)
 {
     __shared__ int s_n[kWaves][4];
     const int blk = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
-    int sums[4] = {0, 0, 0, 0};
-    sums[0] = __popc(kept_roots(parent + (int64_t)b * N, rec + (int64_t)b * N * kRec, (blk * kThreads + t) * kPer, N, min_pixels, sums + 1));
+    const Kept k = kept_roots<kRec>(parent + (int64_t)b * N, rec + (int64_t)b * N * kRec, (blk * kThreads + t) * kPer, N, min_pixels);
+    int sums[4] = {(int)__popc(k.bits), k.in_sets, k.roots, k.members};
     block_sum_n(sums, s_n);
     if (t < 4) cnt[4 * ((int64_t)b * gridDim.x + blk) + t] = block_total(s_n, t);
 }
 
-// grid (B), 256 threads: cnt[b][blk][0] becomes the kept roots before the block (an exclusive scan over the image's blocks, 256 a
-// round); info; and the slots of rows / vals past the kept components, which k_ob_write does not touch.
+// grid (B), 256 threads: cnt[b][blk][0] becomes the kept roots before the block; info; and the slots of rows / vals past the kept
+// components.
 __global__ __launch_bounds__(kThreads) void k_ob_scan(int *__restrict__ cnt, int nblk, int max_objects, int32_t *__restrict__ rows,
                                                      float *__restrict__ vals, int32_t *__restrict__ info)
 {
     __shared__ int s_w[kWaves];
     __shared__ int s_n[kWaves][3];
-    const int b = blockIdx.x, t = threadIdx.x;
+    const int b = blockIdx.x;
     int *c = cnt + 4 * (int64_t)b * nblk;
-    int before = 0, sums[3] = {0, 0, 0};
-    for (int i0 = 0; i0 < nblk; i0 += kThreads) {
-        const int i = i0 + t;
-        const int at = block_scan(i < nblk ? c[4 * i] : 0, s_w, before);
-        if (i < nblk) {
-            c[4 * i] = at;
-            for (int j = 0; j < 3; ++j) sums[j] += c[4 * i + 1 + j];
-        }
-        __syncthreads();                                    // s_w is rewritten by the next round
-    }
-    const int none[8] = {0, -1, -1, -1, -1, -1, -1, 0};
-    const float zero[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    int32_t *orow = rows + (int64_t)b * max_objects * 8;
-    float *oval = vals + (int64_t)b * max_objects * 8;
-    for (int j = min(before, max_objects) + t; j < max_objects; j += kThreads) store_object(orow + 8 * (int64_t)j, oval + 8 * (int64_t)j, none, zero);
+    int sums[3] = {0, 0, 0};
+    const int kept = scan_blocks(c, 4, nblk, s_w, [&](int i) {
+        for (int j = 0; j < 3; ++j) sums[j] += c[4 * i + 1 + j];
+    });
+    clear_slots<8>(rows + (int64_t)b * max_objects * 8, vals + (int64_t)b * max_objects * 8, kept, max_objects);
     block_sum_n(sums, s_n);
-    if (t == 0) {
+    if (threadIdx.x == 0) {
         int32_t *o = info + 4 * (int64_t)b;
-        o[0] = block_total(s_n, 0), o[1] = block_total(s_n, 1), o[2] = before, o[3] = block_total(s_n, 2);
+        o[0] = block_total(s_n, 0), o[1] = block_total(s_n, 1), o[2] = kept, o[3] = block_total(s_n, 2);
     }
 }
 
-// grid (nblk, B), 256 threads: a kept root's number is the kept roots before its block plus those before it inside the block;
-// below max_objects its slot of rows / vals is written, and its record gets the number (-1 past the cap) for k_ob_labels.  The
-// record of a root that is not kept holds -1 since k_ob_tile.
+// grid (nblk, B), 256 threads: below max_objects a kept root's slot of rows / vals is written, and its record gets the number
+// for k_ob_labels.  Every other root's record holds -1 since k_ob_tile.
 __global__ __launch_bounds__(kThreads) void k_ob_write(const int *__restrict__ parent, u32 *__restrict__ rec, const float *__restrict__ cam,
                                                       const int *__restrict__ cnt, int S, int nbins, int min_pixels, int max_objects,
                                                       int32_t *__restrict__ rows, float *__restrict__ vals)
@@ -377,24 +284,19 @@ __global__ __launch_bounds__(kThreads) void k_ob_write(const int *__restrict__ p
     float *oval = vals + (int64_t)b * max_objects * 8;
     const float fb = load_cam(cam, b).fb;
     const int cb = (blk * kThreads + t) * kPer;
-    const unsigned keep = kept_roots(parent + (int64_t)b * N, r_img, cb, N, min_pixels, nullptr);
-    int before = cnt[4 * ((int64_t)b * gridDim.x + blk)];
-    int j = block_scan((int)__popc(keep), s_w, before);
-    for (int i = 0; i < kPer; ++i) {
-        if (!((keep >> i) & 1u)) continue;
+    const unsigned keep = kept_roots<kRec>(parent + (int64_t)b * N, r_img, cb, N, min_pixels).bits;
+    for_each_kept(keep, cnt[4 * ((int64_t)b * gridDim.x + blk)], s_w, [&](int i, int j) {
+        if (j >= max_objects) return;
         u32 *r = r_img + (int64_t)(cb + i) * kRec;
-        if (j < max_objects) {
-            const int n = (int)r[R_N], k_max = nbins - 1 - (cb + i) / S, k_min = nbins - 1 - (int)r[R_KR];
-            const u64 sq = *reinterpret_cast<const u64 *>(r + R_SQ);
-            const float d = (float)(((double)sq / (double)n) / 256.0);
-            const int ri[8] = {n, (int)r[R_X0], (int)r[R_X1], (int)r[R_Y0], (int)r[R_Y1], k_min, k_max, (int)r[R_CELLS] + 1};
-            const float vf[8] = {d, fb / d, unkey(r[R_KEY]), unkey(r[R_KEY + 1]), unkey(r[R_KEY + 2]), unkey(r[R_KEY + 3]),
-                                 unkey(r[R_KEY + 4]), unkey(r[R_KEY + 5])};
-            store_object(orow + 8 * (int64_t)j, oval + 8 * (int64_t)j, ri, vf);
-            r[R_NUM] = (u32)j;
-        }
-        ++j;
-    }
+        const Head h = Head::load(reinterpret_cast<const int *>(r));
+        const int k_max = nbins - 1 - (cb + i) / S, k_min = nbins - 1 - (int)r[R_KR];
+        const float d = h.mean_disp();
+        const int ri[8] = {h.n, h.x0, h.x1, h.y0, h.y1, k_min, k_max, (int)r[R_CELLS] + 1};
+        const float vf[8] = {d, fb / d, unkey(r[R_KEY]), unkey(r[R_KEY + 1]), unkey(r[R_KEY + 2]), unkey(r[R_KEY + 3]),
+                             unkey(r[R_KEY + 4]), unkey(r[R_KEY + 5])};
+        store_slot(orow, oval, j, ri, vf);
+        r[H_NUM] = (u32)j;
+    });
 }
 
 // grid (S, B), 256 threads: the strip blockIdx.x of image blockIdx.y.  The number of each bin's component in LDS (16 KB), then the
@@ -413,7 +315,7 @@ __global__ __launch_bounds__(kThreads) void k_ob_labels(const float *__restrict_
 
     for (int k = t; k < nbins; k += kThreads) {
         const int p = parent[cells + (int64_t)(nbins - 1 - k) * S + s];
-        s_lab[k] = p < 0 ? -1 : (int)rec[(cells + p) * kRec + R_NUM];
+        s_lab[k] = p < 0 ? -1 : (int)rec[(cells + p) * kRec + H_NUM];
     }
     __syncthreads();
     for (int i = t; i < items; i += kThreads) {
@@ -428,8 +330,6 @@ __global__ __launch_bounds__(kThreads) void k_ob_labels(const float *__restrict_
         }
     }
 }
-
-constexpr int64_t round256(int64_t n) { return (n + 255) / 256 * 256; }
 
 // The checks lws_objects_workspace and lws_objects share; S: the strips
 int check_grid(const char *who, int B, int W, int width, int nbins, int &S)

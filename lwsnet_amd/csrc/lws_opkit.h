@@ -20,6 +20,9 @@ namespace lws::opkit {
 // ---- host half ----
 __host__ __device__ __forceinline__ bool aligned(const void *p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; }   // n = 2^k
 
+// a part of a workspace, in bytes: the next part starts 256-byte aligned
+constexpr int64_t round256(int64_t n) { return (n + 255) / 256 * 256; }
+
 // true when the byte ranges [a, a + na) and [b, b + nb) intersect (a null pointer is no range)
 static inline bool overlap(const void *a, int64_t na, const void *b, int64_t nb)
 {

@@ -1,6 +1,6 @@
 // The pieces of the count -> scan -> ranked-scatter kernels, which pack records in a fixed order without an atomic: lws_point_cloud
-// (lws_geometry.hip), lws_surface_mesh (lws_mesh.hip), lws_tsdf_points (lws_tsdf.hip) and the numbering of lws_objects
-// (lws_objects.hip).  The count is opkit::block_sum; here are the exclusive scan of one value per thread, the scan of an array by
+// (lws_geometry.hip), lws_surface_mesh (lws_mesh.hip), lws_tsdf_points (lws_tsdf.hip) and the numbering of lws_objects and
+// lws_movers (lws_cclkit.h).  The count is opkit::block_sum; here are the exclusive scan of one value per thread, the scan of an array by
 // one workgroup, and the rank of a thread's set bits from wave ballots.  All of it is integer arithmetic in thread order, for
 // workgroups of 256 threads; s_w is always kWaves words of the caller's LDS.
 #pragma once

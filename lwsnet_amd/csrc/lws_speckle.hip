@@ -10,14 +10,11 @@
 //   k_sp_apply    one workgroup per row: codes, out (with the row fill of lws_rowkit.h), labels, per-row counts
 //   k_sp_counts   (counts != NULL) one workgroup per image: the per-row counts summed in a fixed order
 //
-// The invariant every loop rests on (lws_cclkit.h holds the union-find and its termination arguments): parent[p] <= p in raster
-// order, always (a root is the FIRST pixel of its set, a union hangs the later root under the earlier one with an atomic min).  A
-// find walk therefore strictly decreases and ends after at most p steps whatever other workgroups do meanwhile; no loop waits for
-// another thread's progress.
-// Words shared between workgroups inside a launch (parent[] in k_sp_border and k_sp_flatten, size[] in k_sp_flatten) are touched
-// through relaxed agent-scope atomics only (each word stands for itself: there is no payload to publish behind it); everything
-// else crosses between workgroups at kernel boundaries.  Only ROOTS are ever re-parented, so a non-root pixel keeps the parent
-// k_sp_tile gave it, and after k_sp_flatten every pixel is two plain loads from its label: parent[parent[p]].
+// lws_cclkit.h holds the steps this labeller shares with lws_objects.hip and lws_movers.hip -- the union-find, the tile geometry,
+// the tile-edge pairs, the flatten -- and the invariant (parent[p] <= p in raster order), termination and memory-scope arguments
+// they rest on.  The words shared inside a launch here: parent[] in k_sp_border and k_sp_flatten, size[] in k_sp_flatten.  Only
+// ROOTS are ever re-parented, so a non-root pixel keeps the parent k_sp_tile gave it, and after k_sp_flatten every pixel is two
+// plain loads from its label: parent[parent[p]].
 // Sizes: counted per tile in LDS (one add per wave for the wave's leading root, an LDS add for the other lanes), then ONE integer
 // atomic add per tile-local component to its global root: a 450 k-pixel component costs a few hundred adds on its word, not 450 k.
 // Integer atomics only, so the result does not depend on their order.  0 bytes of scratch.
@@ -31,15 +28,10 @@ namespace {
 
 using namespace rowkit;                                     // kThreads, kWaves, kMaxW and the pieces of k_sp_apply
 using namespace opkit;
-using namespace cclkit;                                    // lds_find, lds_unite, ld_agent, g_find, g_unite
-constexpr int kTH = 32, kTW = 64;                           // the tile of k_sp_tile
-constexpr int kTile = kTH * kTW;
+using namespace cclkit;                                    // the tile, the union-find, the tile edges, the flatten
 constexpr int kQuadsPerThread = kTile / 4 / kThreads;       // 2
 
 __device__ __forceinline__ bool sp_valid(float d, bool ok) { return ok && __builtin_isfinite(d) && d > 0.0f; }
-
-// joined iff |a - b| <= max_diff; an invalid pixel is staged as NaN, which joins nothing
-__device__ __forceinline__ bool sp_joined(float a, float b, float max_diff) { return fabsf(a - b) <= max_diff; }
 
 __device__ __forceinline__ void store_quad_i(int *__restrict__ p, int x, int W, const int v[4])
 {
@@ -63,12 +55,12 @@ __global__ __launch_bounds__(kThreads) void k_sp_tile(const float *__restrict__ 
     __shared__ __attribute__((aligned(16))) int s_cnt[kTile];
     const int t = threadIdx.x, lane = t & 63, b = blockIdx.y;
     const int ty = blockIdx.x / ntx, tx = blockIdx.x - ty * ntx;
-    const int y0 = ty * kTH, x0 = tx * kTW;
+    const int y0 = ty * kTileRows, x0 = tx * kTileCols;
     const int64_t img = (int64_t)b * H * W;
     const float nan = __builtin_nanf("");
 
     for (int k = 0; k < kQuadsPerThread; ++k) {
-        const int q = t + k * kThreads, ry = q / (kTW / 4), rx = 4 * (q % (kTW / 4));
+        const int q = t + k * kThreads, ry = q / (kTileCols / 4), rx = 4 * (q % (kTileCols / 4));
         const int y = y0 + ry, x = x0 + rx;
         float d[4] = {nan, nan, nan, nan};
         if (y < H && x < W) {
@@ -94,7 +86,7 @@ __global__ __launch_bounds__(kThreads) void k_sp_tile(const float *__restrict__ 
 #pragma unroll
             for (int i = 0; i < 4; ++i) d[i] = sp_valid(d[i], ok[i]) ? d[i] : nan;
         }
-        const int l = ry * kTW + rx;
+        const int l = ry * kTileCols + rx;
         *reinterpret_cast<float4 *>(s_d + l) = make_float4(d[0], d[1], d[2], d[3]);
         *reinterpret_cast<int4 *>(s_par + l) = make_int4(l, l + 1, l + 2, l + 3);
         *reinterpret_cast<int4 *>(s_cnt + l) = make_int4(0, 0, 0, 0);
@@ -103,14 +95,9 @@ __global__ __launch_bounds__(kThreads) void k_sp_tile(const float *__restrict__ 
 
     // the joins to the right and below, inside the tile
     for (int k = 0; k < kQuadsPerThread; ++k) {
-        const int q = t + k * kThreads, ry = q / (kTW / 4), rx = 4 * (q % (kTW / 4));
+        const int q = t + k * kThreads, ry = q / (kTileCols / 4), rx = 4 * (q % (kTileCols / 4));
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int l = ry * kTW + rx + i;
-            const float d = s_d[l];
-            if (rx + i + 1 < kTW && sp_joined(d, s_d[l + 1], max_diff)) lds_unite(s_par, l, l + 1);
-            if (ry + 1 < kTH && sp_joined(d, s_d[l + kTW], max_diff)) lds_unite(s_par, l, l + kTW);
-        }
+        for (int i = 0; i < 4; ++i) join_right_below(s_d, s_par, ry * kTileCols + rx + i, rx + i + 1 < kTileCols, ry + 1 < kTileRows, max_diff);
     }
     __syncthreads();
 
@@ -118,7 +105,7 @@ __global__ __launch_bounds__(kThreads) void k_sp_tile(const float *__restrict__ 
     // once, the others one by one -- a tile inside one plateau costs 32 LDS adds, not 2048 on one word
     int root[kQuadsPerThread][4];
     for (int k = 0; k < kQuadsPerThread; ++k) {
-        const int q = t + k * kThreads, l0 = (q / (kTW / 4)) * kTW + 4 * (q % (kTW / 4));
+        const int q = t + k * kThreads, l0 = (q / (kTileCols / 4)) * kTileCols + 4 * (q % (kTileCols / 4));
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int l = l0 + i;
@@ -138,14 +125,14 @@ __global__ __launch_bounds__(kThreads) void k_sp_tile(const float *__restrict__ 
     __syncthreads();
 
     for (int k = 0; k < kQuadsPerThread; ++k) {
-        const int q = t + k * kThreads, ry = q / (kTW / 4), rx = 4 * (q % (kTW / 4));
+        const int q = t + k * kThreads, ry = q / (kTileCols / 4), rx = 4 * (q % (kTileCols / 4));
         const int y = y0 + ry, x = x0 + rx;
         if (y >= H || x >= W) continue;
         int pv[4], sv[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int r = root[k][i], l = ry * kTW + rx + i;
-            pv[i] = r < 0 ? -1 : (y0 + r / kTW) * W + x0 + r % kTW;
+            const int r = root[k][i], l = ry * kTileCols + rx + i;
+            pv[i] = r < 0 ? -1 : tile_to_index(r, y0, x0, W);
             sv[i] = r == l ? s_cnt[l] : 0;
         }
         const int64_t row = img + (int64_t)y * W;
@@ -154,30 +141,11 @@ __global__ __launch_bounds__(kThreads) void k_sp_tile(const float *__restrict__ 
     }
 }
 
-// grid (ceil(n / 256), B), n = (nty - 1) * W + (ntx - 1) * H: thread g < (nty - 1) * W is the pair (y - 1, x), (y, x) on the
-// top edge of a tile row, the others the pair (y, x - 1), (y, x) on the left edge of a tile column.  parent[] is shared between
-// workgroups here: agent-scope atomics only (g_find, g_unite).
+// grid (ceil(n / 256), B), n = (nty - 1) * W + (ntx - 1) * H: one thread per pair of pixels across a tile edge (lws_cclkit.h)
 __global__ __launch_bounds__(kThreads) void k_sp_border(const float *__restrict__ disp, int H, int W, int nty, int ntx, float max_diff,
                                                        int *__restrict__ parent)
 {
-    const int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    const int64_t nh = (int64_t)(nty - 1) * W, nv = (int64_t)(ntx - 1) * H;
-    if (g >= nh + nv) return;
-    const int64_t img = (int64_t)blockIdx.y * H * W;
-    int p, q;
-    if (g < nh) {
-        const int e = (int)(g / W), x = (int)(g - (int64_t)e * W), y = (e + 1) * kTH;
-        q = y * W + x;
-        p = q - W;
-    } else {
-        const int64_t v = g - nh;
-        const int e = (int)(v / H), y = (int)(v - (int64_t)e * H), x = (e + 1) * kTW;
-        q = y * W + x;
-        p = q - 1;
-    }
-    int *par = parent + img;
-    if (ld_agent(par + p) < 0 || ld_agent(par + q) < 0) return;     // the sign of a parent word never changes
-    if (sp_joined(disp[img + p], disp[img + q], max_diff)) g_unite(par, p, q);
+    unite_tile_edges(disp, H, W, nty, ntx, max_diff, parent);
 }
 
 // grid (ceil(H * W / 256), B): one thread per pixel; the tile-local roots (size > 0) find their global root r, point at it and
@@ -191,10 +159,8 @@ __global__ __launch_bounds__(kThreads) void k_sp_flatten(int HW, int *__restrict
     int *par = parent + (int64_t)blockIdx.y * HW, *sz = size + (int64_t)blockIdx.y * HW;
     const int n = ld_agent(sz + p);
     if (n <= 0) return;
-    const int r = g_find(par, p);
-    if (r == p) return;
-    __hip_atomic_fetch_min(par + p, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // r <= parent[p]: the invariant holds
-    __hip_atomic_fetch_add(sz + r, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int r = point_at_root(par, p);
+    if (r != p) a_add(sz + r, n);
 }
 
 // grid (H, B), 256 threads: one workgroup per row, thread t owns the quads t, t + 256, ... of it (lws_rowkit.h).  parent[] and
@@ -291,8 +257,6 @@ __global__ __launch_bounds__(kThreads) void k_sp_counts(const int *__restrict__ 
     if (t < 3) counts[3 * (int64_t)b + t] = sum4(s_n[0][t], s_n[1][t], s_n[2][t], s_n[3][t]);
 }
 
-constexpr int64_t round256(int64_t n) { return (n + 255) / 256 * 256; }
-
 }  // namespace
 
 }  // namespace lws
@@ -331,7 +295,7 @@ int lws_speckle_filter(const float *disp, const uint8_t *mask, int B, int H, int
     int *parent = static_cast<int *>(workspace);
     int *size = reinterpret_cast<int *>(static_cast<char *>(workspace) + round256(px * (int64_t)sizeof(int)));
     int *row_cnt = counts ? reinterpret_cast<int *>(static_cast<char *>(workspace) + 2 * round256(px * (int64_t)sizeof(int))) : nullptr;
-    const int ntx = (W + kTW - 1) / kTW, nty = (H + kTH - 1) / kTH;
+    const int ntx = (W + kTileCols - 1) / kTileCols, nty = (H + kTileRows - 1) / kTileRows;
     const int64_t pairs = (int64_t)(nty - 1) * W + (int64_t)(ntx - 1) * H;
     const int HW = H * W;
     hipStream_t st = (hipStream_t)stream;

@@ -20,7 +20,7 @@ torch = pytest.importorskip("torch")
 from test_gpu_geometry import KITTI15_CALIB, assert_bits, cam_rows, cu, misaligned  # noqa: E402
 from test_gpu_ground import ROAD, all_buffers, reference, road_cameras, roads, run_ops, run_raw  # noqa: E402
 from test_gpu_stixels import random_maps, raw_stixels, stix_ops  # noqa: E402
-from test_objects_cpu import CAM1, OBJ, PATTERNS, pattern, road_objects, tile  # noqa: E402
+from test_objects_cpu import CAM1, OBJ, PATTERNS, pattern, road_objects, second_round_case, tile  # noqa: E402
 from test_stixels_cpu import STIX  # noqa: E402
 
 F = np.float32
@@ -187,6 +187,16 @@ def test_hand_made_cells(dev, hip_lib, name):
     want = O.run(d, CAM1, codes, udisp, p)
     assert want[3][0].tolist() == want_info and want[0][0, :len(want_rows)].tolist() == want_rows
     check(obj_ops(d, [Camera(100.0, 100.0, 7.5, 15.5, 0.5)], codes, udisp, p, dev), want, name)
+
+
+def test_numbering_scan_second_round(dev, hip_lib):
+    """S * nbins = 524 352 cells: the per-image scan of the numbering goes round twice, and kept roots stand in the first block,
+    in the last block of round one, in the first block of round two and in the last cell."""
+    from lwsnet_amd.geometry import Camera
+    d, codes, udisp, p, want_rows, want_info = second_round_case()
+    want = O.run(d, CAM1, codes, udisp, p)
+    assert want[3][0].tolist() == want_info and want[0][0, :len(want_rows)].tolist() == want_rows
+    check(obj_ops(d, [Camera(100.0, 100.0, 7.5, 15.5, 0.5)], codes, udisp, p, dev), want, "second round")
 
 
 def test_a_foreign_udisp_is_followed_as_it_is(dev, hip_lib):

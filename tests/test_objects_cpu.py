@@ -119,6 +119,33 @@ def test_reference_on_hand_made_cells(name):
     assert (labels >= len(want_rows)).sum() == 0 and (labels >= 0).sum() == sum(r[0] for r in want_rows)
 
 
+# ---- the numbering's per-image scan takes 256 blocks of 2048 cells a round: a cell from c = 524 288 on is scanned in round two ----
+WIDE = dict(min_disp=0.25, max_depth=INF, code_bits=1 << 2, width=1, sub=1, nbins=64, min_count=1, min_pixels=1, max_objects=8)
+WIDE_W = 8193                                               # S = W strips of one column (W <= 16384): S * nbins = 524 352 cells, 257 blocks
+
+
+def second_round_case():
+    """(d, codes, udisp, p, the rows expected, the info expected) of a 2 x 8193 image whose four kept components are single cells
+    of one or two pixels: in the first block, in the last block of the scan's first round, in the first block of its second round
+    and in the last cell.  c = (nbins - 1 - k) * S + s; written down by hand as PATTERNS is."""
+    S, nbins = WIDE_W, WIDE["nbins"]
+    cells = {(5, 63): 2, (7000, 0): 1, (8130, 0): 2, (8192, 0): 1}
+    c = [(nbins - 1 - k) * S + s for s, k in cells]
+    assert [v // 2048 for v in c] == [0, 255, 256, 256] and c[1] < 256 * 2048 <= c[2] and c[3] == S * nbins - 1
+    d, codes = O.cell_map(2, WIDE_W, WIDE["width"], WIDE["sub"], cells)
+    want_rows = [[2, 5, 5, 0, 1, 63, 63, 1], [1, 7000, 7000, 0, 0, 0, 0, 1], [2, 8130, 8130, 0, 1, 0, 0, 1], [1, 8192, 8192, 0, 0, 0, 0, 1]]
+    return d, codes, O.udisp_of(d, CAM1, codes, WIDE), WIDE, want_rows, [4, 4, 4, 6]
+
+
+def test_reference_on_the_scan_second_round():
+    d, codes, udisp, p, want_rows, want_info = second_round_case()
+    rows, vals, labels, info = O.run(d, CAM1, codes, udisp, p)
+    assert info[0].tolist() == want_info and rows[0, :4].tolist() == want_rows
+    assert (rows[0, 4:] == np.array(O.EMPTY_ROW)).all() and (vals[0, 4:].view(np.uint32) == 0).all()
+    assert [int((labels == j).sum()) for j in range(-1, 5)] == [2 * WIDE_W - 6, 2, 1, 2, 1, 0]
+    assert vals[0, :4, 0].tolist() == [63.5, 0.5, 0.5, 0.5] and vals[0, :4, 1].tolist() == [float(F(50.0) / F(63.5)), 100.0, 100.0, 100.0]
+
+
 def test_reference_orders_the_zeros_and_follows_a_foreign_udisp():
     """-0.0 < +0.0 in the minima and maxima (a pixel on the optical axis has X = +0.0, one left of it times a tiny z may give -0.0);
     a udisp that is not the map's own is followed as it is: occupied and joined come from it alone."""
