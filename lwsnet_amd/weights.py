@@ -97,6 +97,20 @@ def _fan_in(key, shape):
     return shape[1] * rf
 
 
+def bn_scale_shift(sd, prefix, eps=1e-5):
+    """Eval-mode BatchNorm ``prefix`` folded to ``y = fmaf(x, s, t)``: s = gamma / sqrt(var + eps), t = beta - mean * s, every
+    step rounded to float32 -- the sequence fold_bn (csrc/lws_params.hip) performs on the host.  One channel at a time: each step
+    is taken in float64 and rounded once to float32, which for +, -, *, / and sqrt of float32 operands is the float32 result.
+    A gamma of exactly 0 (a pruned channel) gives s = +-0 and t = beta."""
+    g, b, m, v = (np.asarray(sd[f"{prefix}.{name}"], dtype=np.float32) for name in BN_SUFFIXES)
+    s, t = np.empty(g.shape, np.float32), np.empty(g.shape, np.float32)
+    for i in range(g.size):
+        root = np.float32(np.sqrt(np.float64(np.float32(np.float64(v[i]) + np.float64(np.float32(eps))))))
+        s[i] = np.float32(np.float64(g[i]) / np.float64(root))
+        t[i] = np.float32(np.float64(b[i]) - np.float64(np.float32(np.float64(m[i]) * np.float64(s[i]))))
+    return s, t
+
+
 def make_state_dict(seed=7, args=None, calibrated=True):
     """Seeded synthetic weights: ``{key: float32 ndarray}`` in spec order.
 

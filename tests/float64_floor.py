@@ -229,14 +229,40 @@ class Case:
 
 
 _STATE = {}
+_FAMILY = None          # the parameter family (tests/param_families.py) that `state_dict` and `case` are under: see `under_family`
 
 
-def state_dict(constructor=None, calibrated=True):
-    """(args, state dict): the default model's (seed 7) or CONSTRUCTORS[constructor]'s (seed 13)."""
+class under_family:
+    """with under_family("signed"): ... -- inside, `state_dict` gives the seeded state dict transformed by that parameter family
+    (tests/param_families.py) and `case` builds and caches its cases under it, so that the builders, the C runners and the
+    split emulation serve the families without a second copy.  The ids, seeds and inputs of a case do not depend on the family;
+    None is the seeded family itself."""
+
+    def __init__(self, family):
+        self.family = family
+
+    def __enter__(self):
+        global _FAMILY
+        self.saved, _FAMILY = _FAMILY, self.family
+        return self
+
+    def __exit__(self, *a):
+        global _FAMILY
+        _FAMILY = self.saved
+
+
+def state_dict(constructor=None, calibrated=True, family=False):
+    """(args, state dict): the default model's (seed 7) or CONSTRUCTORS[constructor]'s (seed 13); under `family` (default: the one
+    of the enclosing `under_family`, else none) transformed by tests/param_families.py."""
     from lwsnet_amd.weights import default_args, make_state_dict
-    key = (constructor, calibrated)
+    family = _FAMILY if family is False else family
+    key = (constructor, calibrated) if family is None else (constructor, calibrated, family)
     if key not in _STATE:
-        if constructor is None:
+        if family is not None:
+            import param_families
+            args, sd = state_dict(constructor, calibrated, None)
+            _STATE[key] = (args, param_families.apply(sd, args, family))
+        elif constructor is None:
             args = default_args()
             _STATE[key] = (args, make_state_dict(7, args, calibrated=calibrated))
         else:
@@ -395,8 +421,9 @@ _CASE = {}
 
 
 def case(family, params):
-    """The Case of CASES[family]'s entry `params`: built once, shared by every test that needs it, never modified."""
-    key = (family, params)
+    """The Case of CASES[family]'s entry `params` (under the parameter family of the enclosing `under_family`, if any): built
+    once, shared by every test that needs it, never modified."""
+    key = (family, params) if _FAMILY is None else (family, params, _FAMILY)
     if key not in _CASE:
         _CASE[key] = _BUILDERS[family](params)
     return _CASE[key]
